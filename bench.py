@@ -1,15 +1,21 @@
 #!/usr/bin/env python3
 """bench.py — RGB/IR image-pairs/sec of the ICAFusion hot path on MI355X (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W        (N>1: launched by torch.distributed.run, one rank per GPU)
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+                                                         (N>1: launched by torch.distributed.run, one rank per GPU)
 
 One step = one pass of the hot path over one batch of synthetic pairs already resident in HBM:
 two-stream backbone -> 3x DMFF -> PANet head -> Detect (one hipGraph replay) -> device NMS -> [N>1: RCCL all-gather
 of the detection blocks].  Steps are pipelined as a serving loop pipelines them: `--depth` batches in flight (default 2, each with
 its own plan / buffers / forward stream, so the low-occupancy tail of one forward overlaps the full-width layers of the next) and
 the NMS of a batch on a further stream; every step does all of its work inside the timed region.  Default workload = BASELINE.json configs[1]: yolov5s + DMFF, bf16, batch 32, 640x640.
-Rank 0 prints ONE JSON line with the contract fields plus `roofline` (dominant kernel, HIP-event timed) and
-`cpu_baseline` (the CPU oracle = a port of the reference's algorithm, timed on this host's cores; N=1 only).
+
+A plain run sets up, runs W warm-up steps, times exactly K steps once and prints ONE JSON line with the contract fields
+(`value` = pairs/s of the K steps, `ms_per_step` = milliseconds of one of them).  `--dump-outputs DIR` writes the last timed
+step's detections as .npy files (inputs and weights are seeded: two builds compare output for output).  `--full` adds
+everything else: the timed region repeated (`--repeats`, `--min-timed-seconds`; `value` = the median region), forward-only and
+NMS-alone rates, `roofline` and per-kernel figures (HIP-event timed), batch-1 latency, the host-fed rate and `cpu_baseline`
+(the CPU oracle = a port of the reference's algorithm, timed on this host's cores; N=1 only).
 """
 import argparse
 import json
@@ -20,6 +26,7 @@ import time
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
+import numpy as np  # noqa: E402
 import torch  # noqa: E402
 import yaml   # noqa: E402
 
@@ -54,10 +61,15 @@ def parse():
     ap.add_argument("--no-autotune", action="store_true")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
-    ap.add_argument("--repeats", type=int, default=9, help="the timed region (K steps between barriers) is run at least this many times; "
-                    "`value` is the median run, min / max are reported beside it")
-    ap.add_argument("--min-timed-seconds", type=float, default=3.0, help="keep repeating the timed region (same K steps each) until this much "
-                    "timed GPU work has been done: one region is K x ~2 ms, too short for a utilisation sampler to see (0 = exactly --repeats regions)")
+    ap.add_argument("--full", action="store_true", help="besides the headline figure, measure everything else: repeated timed regions, "
+                    "forward-only / NMS-alone rates, roofline and per-kernel figures, batch-1 latency, host-fed rate, CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last timed step computed "
+                    "(detections.npy, counts.npy; float32) into DIR")
+    ap.add_argument("--repeats", type=int, default=None, help="the timed region (K steps between barriers) is run at least this many times; "
+                    "`value` is the median run, min / max are reported beside it (default: 9 with --full, 1 otherwise)")
+    ap.add_argument("--min-timed-seconds", type=float, default=None, help="keep repeating the timed region (same K steps each) until this much "
+                    "timed GPU work has been done: one region is K x ~2 ms, too short for a utilisation sampler to see (0 = exactly --repeats regions; "
+                    "default: 3.0 with --full, 0 otherwise)")
     ap.add_argument("--no-fuse-tail", action="store_true", help="materialise DMFF's merged tensor instead of the fused-tail GEMM")
     ap.add_argument("--no-overlap", action="store_true", help="run NMS on the forward stream (no cross-batch overlap)")
     ap.add_argument("--depth", type=int, default=2, help="batches in flight, each with its own plan (buffers, hipGraph) and forward stream: the "
@@ -67,7 +79,12 @@ def parse():
     ap.add_argument("--no-latency", action="store_true", help="skip the batch-1 latency measurement (latency_ms_b1)")
     ap.add_argument("--dry-run", action="store_true", help="launcher check: start the ranks, initialise the process group (RCCL with GPUs, gloo "
                     "without), all-gather one detection block, print {n_gpus, backend} and exit - no model, no timing")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.repeats is None:
+        args.repeats = 9 if args.full else 1
+    if args.min_timed_seconds is None:
+        args.min_timed_seconds = 3.0 if args.full else 0.0
+    return args
 
 
 def spawn_ranks(args):
@@ -251,108 +268,16 @@ def h2d_feed(model, args, B, H, W, dev):
                     "forward from uint8 (icaf_stem2 / icaf_preprocess_u8) + NMS; median of 3 x K steps"}
 
 
-def main():
-    args = parse()
-    if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
-        sys.exit(spawn_ranks(args))
-    if args.dry_run:
-        sys.exit(dry_run(args))
-    from icafusion_amd import dist as D
+def full_figures(args, cfg, sd, model, pipe, B, H, W, n_local, dev, rank, world, barrier, workload):
+    """--full: everything beyond the headline figure, measured after the timed region on the same plans.  Every rank takes part
+    (the per-rank rate has a collective); returns the fields rank 0 adds to the JSON line (None on the other ranks)."""
     from icafusion_amd import ops
-    from icafusion_amd.options import OPT
     from icafusion_amd.models.yolo import Model
-    from icafusion_amd.synth import synth_images, synth_state_dict
     from icafusion_amd.pipeline import DetectionPipeline
+    from icafusion_amd.synth import synth_images
     import torch.distributed as tdist
-
-    rank, world, local = D.init_from_env()
-    if world != args.gpus:             # (a launcher's WORLD_SIZE wins; n_gpus in the JSON line is the world size that ran)
-        if rank == 0:
-            print(f"[bench] WORLD_SIZE={world} != --gpus {args.gpus}; using WORLD_SIZE", file=sys.stderr)
-    assert torch.cuda.is_available(), "bench.py needs an MI355X"
-    torch.cuda.set_device(local)
-    dev = torch.device("cuda", local)
-    affinity = None
-    if world > 1 and os.environ.get("ICAF_NO_PIN") != "1":      # one process per GPU: keep each rank's host threads next to its GPU
-        pr = torch.cuda.get_device_properties(local)
-        bus = f"{getattr(pr, 'pci_domain_id', 0):04x}:{pr.pci_bus_id:02x}:{pr.pci_device_id:02x}.0" if hasattr(pr, "pci_bus_id") else None
-        affinity = D.pin_to_gpu_numa(local, int(os.environ.get("LOCAL_WORLD_SIZE", world)), bus)
-        if affinity.get("pinned"):
-            torch.set_num_threads(max(1, min(8, affinity["cpus"])))
-
-    tag = {"kaist": "kaist", "FLIR": "FLIR", "VEDAI": "VEDAI", "LLVIP": "LLVIP"}[args.dataset]
-    yaml_name = f"yolov5{args.model}_Transfusion_{tag}.yaml"
-    cfg = yaml.safe_load(open(os.path.join(ROOT, "models", "transformer", yaml_name)))
-    model = Model(cfg).eval()
-    sd = synth_state_dict(model, seed=0)
-    model.load_state_dict(sd)
-    for i in (20, 21, 22):
-        model.model[i].crosstransformer[0].loops = args.loops
-        model.model[i].fuse_tail = not args.no_fuse_tail
-    model = model.to(dev)
-    model.compute_dtype = DT[args.dtype]
-    model.static_outputs = True
-    model.fold_upsample = args.fold_upsample
-    model.autotune = not args.no_autotune
-    B, H, W = args.batch, args.height, args.width
-    strong = args.global_batch > 0
-    if strong:                          # contiguous shards of a fixed global batch; uneven splits pad the short ranks to the longest shard
-        lo, hi = D.shard_range(args.global_batch, rank, world)
-        n_local, B = hi - lo, D.padded_local_batch(args.global_batch, world)
-    else:
-        n_local = B
-    default_cache = os.path.join(ROOT, "profiles", "tune_cache.json")     # committed igemm tile choices: the same kernels
-    if args.tune_cache and os.path.exists(args.tune_cache):               # run (and were profiled) from round to round;
-        ops.load_tune_cache(args.tune_cache)                              # layers missing from it are tuned on the spot
-    elif not args.tune_cache and os.path.exists(default_cache):
-        ops.load_tune_cache(default_cache)
-    model.use_graph = not args.no_graph
-    if args.force_gather and world == 1 and not tdist.is_initialized():
-        os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
-        os.environ.setdefault("MASTER_PORT", "29517")
-        tdist.init_process_group(backend="nccl", rank=0, world_size=1)
-    pipe = DetectionPipeline(model, B, H, W, dev, conf_thres=args.conf, iou_thres=args.iou, world=world,
-                             overlap=not args.no_overlap, depth=args.depth, force_gather=args.force_gather and world == 1)
-    plan = pipe.plan
-    if args.tune_cache and rank == 0:
-        ops.save_tune_cache(args.tune_cache)
-    # inputs resident in HBM before the timed region: each rank synthesises its own shard of the global batch
-    rgb, ir = synth_images(B, H, W, seed=100 + rank)              # (strong scaling: rows >= n_local of a short rank are padding pairs)
-    for pl in pipe.plans:
-        pl.inputs[0].copy_(rgb.to(dev))
-        pl.inputs[1].copy_(ir.to(dev))
-    nc = cfg["nc"]
-    sp = pipe.fwd_stream.cuda_stream
-    torch.cuda.synchronize()
-    step = pipe.step
-
-    def barrier():
-        if world > 1:
-            tdist.barrier()
-
-    for _ in range(args.warmup):
-        step()
-    # The timed region of the contract — barrier + synchronize, exactly K steps, synchronize + barrier, MAX over ranks — is
-    # run `repeats` times back to back; `value` comes from the MEDIAN run.  One region is only K x ~2.6 ms long, and a single
-    # sample of it moves by several per cent with the box's clocks / whatever else the host is doing.
-    runs = []
-    while len(runs) < max(1, args.repeats) or (sum(runs) < args.min_timed_seconds and len(runs) < 2000):
-        torch.cuda.synchronize()
-        barrier()
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        for _ in range(args.steps):
-            det, count = step()[:2]
-        pipe.synchronize()                      # (N > 1: also sends a gather group that K steps left incomplete)
-        torch.cuda.synchronize()
-        barrier()
-        el = time.perf_counter() - t0
-        if world > 1:
-            t = torch.tensor([el], dtype=torch.float64, device=dev)
-            tdist.all_reduce(t, op=tdist.ReduceOp.MAX)
-            el = float(t.item())
-        runs.append(el)
-    elapsed = sorted(runs)[len(runs) // 2]
+    plan, step, sp = pipe.plan, pipe.step, pipe.fwd_stream.cuda_stream
+    gf = GFLOP_PER_PAIR.get((args.model, H, W))
     # per-rank rate (each rank's own clock around K of its steps, no barrier inside): the spread over ranks shows a slow GPU / link
     torch.cuda.synchronize()
     barrier()
@@ -442,8 +367,6 @@ def main():
                  "avg_launch_us_with_second_forward_in_flight": over_us, "launches_per_step": dn // reps,
                  "share_of_forward_kernel_time": round(dms / reps / total_ms, 3)})
     att = per_kernel.get("cross_attention")
-    workload = (f"{yaml_name[:-5]} + DMFF(loops={args.loops}) {args.dtype}, batch {B}/GPU, "
-                f"{H}x{W} synthetic RGB/IR pairs, seeded random weights, NMS conf {args.conf} iou {args.iou}")
     # SQ counters of the same command line (committed summary, see sq_counters): which pipe a kernel keeps busy.  `bound` = the roof the
     # dominant kernel sits closest to: HBM (algorithmic bytes / time / 8 TB/s), MFMA (pipe-busy fraction by the counters when there are
     # counters, FLOPs / time / dense peak otherwise) or VALU issue (fraction of the SIMDs' cycles in which a vector instruction issues:
@@ -490,28 +413,9 @@ def main():
                       "attention_mfma_busy": sq.get("cross_attention", {}).get("mfma_util"),
                       "note": "LN + QKV, crossed attention, out-proj + MLP (+ reduce) of all three levels and iterations; pooling / merge / the 1x1 fuse conv are not in it"}
 
-    if rank == 0:
-        pairs = (args.global_batch if strong else B * world) * args.steps
-        value = pairs / elapsed
-        gf = GFLOP_PER_PAIR.get((args.model, H, W))
+    out = None
+    if rank == 0:                      # rank 0 reports
         out = {
-            "metric": "RGB/IR image-pairs/sec (two-stream forward + NMS)", "value": round(value, 2), "unit": "pairs/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(1e3 * elapsed / args.steps, 3),
-            "repeats": len(runs), "timed_seconds": round(sum(runs), 3), "value_min": round(pairs / max(runs), 2), "value_max": round(pairs / min(runs), 2),
-            "higher_is_better": True, "scaling": "strong" if strong else "weak", "vs_baseline": None, "dtype": args.dtype, "data": "synthetic",
-            "config": {"workload": workload,
-                       "global_batch": args.global_batch if strong else B * world,
-                       "local_batches": [D.shard_range(args.global_batch, r, world)[1] - D.shard_range(args.global_batch, r, world)[0]
-                                         for r in range(world)] if strong else [B] * world,
-                       "parallelism": f"dp{world} (pairs sharded, one all-gather of detections)",
-                       "world_size_of_process_group": tdist.get_world_size() if world > 1 else 1,
-                       "rank0_cpu_affinity": affinity,
-                       "backend": tdist.get_backend() if world > 1 else None,
-                       "graph": not args.no_graph, "nms_overlapped_with_next_forward": not args.no_overlap, "batches_in_flight": pipe.depth, "forced_one_rank_all_gather": bool(pipe.gather and world == 1),
-                       "all_gather": {"steps_per_collective": pipe.group, "bytes_per_rank_per_collective": int(pipe.group_block.numel() * 4) if pipe.group > 1 else int(pipe.group_block.numel() * 4 // max(1, len(pipe.runners))),
-                                      "stream": "own stream behind the group's last NMS"} if pipe.gather else None,
-                       "fused_paths": pipe.plans[0].fusion_report(),
-                       "plan_options": OPT.as_dict(), "plan_options_not_default": OPT.non_default()},
             "per_rank_pairs_per_s": {"min": round(min(rank_rates), 2), "max": round(max(rank_rates), 2),
                                      "note": "each rank's own clock around K steps of its shard (value = all ranks, max-over-ranks time)"},
             "forward_only_pairs_per_s": round(B / (fwd_tp_ms * 1e-3), 2),       # same batches-in-flight as `value`, no NMS
@@ -532,8 +436,6 @@ def main():
                 "tflops": round(att[1] / (att[0] * 1e-3) / 1e12, 2), "ms_per_step": round(att[0] / reps, 4),
                 "mfma_frac_of_dense_peak": round(att[1] / (att[0] * 1e-3) / 1e12 / PEAK_TFLOPS[args.dtype], 4)},
             "kernels": kernels,
-            "plan_buffer_MB": round(plan.nbytes / 2 ** 20, 1),
-            "detections_first_image": int(count.reshape(-1)[0]),
         }
         if pipe_busy:
             fr = out["forward_roofline"]
@@ -575,7 +477,7 @@ def main():
             pm = json.load(open(tf))
             pk = pm.get("kernels", {})
             k = pk.get(dname)
-            if pm.get("workload") == out["config"]["workload"] and k \
+            if pm.get("workload") == workload and k \
                     and "fetch_bytes_corrected" in k and "write_bytes_uncorrected" in k:
                 roof["traffic"] = round(k["fetch_bytes_corrected"] + k["write_bytes_uncorrected"])
                 roof["traffic_detail"] = {"fetch_bytes": round(k["fetch_bytes_corrected"]),
@@ -601,6 +503,154 @@ def main():
             fused = Model(cfg).eval()
             fused.load_state_dict(sd)
             out["cpu_baseline"] = cpu_baseline(cfg, fused.fuse().state_dict(), args, args.loops)
+    return out
+
+
+def dump_outputs(out_dir, det, count):
+    """What the last timed step returned to its caller: det (world, B, max_det, 6) boxes xyxy / conf / class and count (world, B)
+    detections per image.  Rows at and past an image's count are not detections and are written as zeros."""
+    os.makedirs(out_dir, exist_ok=True)
+    det = det.float().cpu().numpy().copy()
+    count = count.cpu().numpy()
+    det[np.arange(det.shape[-2]) >= count[..., None]] = 0.0
+    np.save(os.path.join(out_dir, "detections.npy"), det.astype(np.float32))
+    np.save(os.path.join(out_dir, "counts.npy"), count.astype(np.float32))
+
+
+def main():
+    args = parse()
+    if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
+        sys.exit(spawn_ranks(args))
+    if args.dry_run:
+        sys.exit(dry_run(args))
+    from icafusion_amd import dist as D
+    from icafusion_amd import ops
+    from icafusion_amd.options import OPT
+    from icafusion_amd.models.yolo import Model
+    from icafusion_amd.synth import synth_images, synth_state_dict
+    from icafusion_amd.pipeline import DetectionPipeline
+    import torch.distributed as tdist
+
+    rank, world, local = D.init_from_env()
+    if world != args.gpus:             # (a launcher's WORLD_SIZE wins; n_gpus in the JSON line is the world size that ran)
+        if rank == 0:
+            print(f"[bench] WORLD_SIZE={world} != --gpus {args.gpus}; using WORLD_SIZE", file=sys.stderr)
+    assert torch.cuda.is_available(), "bench.py needs an MI355X"
+    torch.cuda.set_device(local)
+    dev = torch.device("cuda", local)
+    affinity = None
+    if world > 1 and os.environ.get("ICAF_NO_PIN") != "1":      # one process per GPU: keep each rank's host threads next to its GPU
+        pr = torch.cuda.get_device_properties(local)
+        bus = f"{getattr(pr, 'pci_domain_id', 0):04x}:{pr.pci_bus_id:02x}:{pr.pci_device_id:02x}.0" if hasattr(pr, "pci_bus_id") else None
+        affinity = D.pin_to_gpu_numa(local, int(os.environ.get("LOCAL_WORLD_SIZE", world)), bus)
+        if affinity.get("pinned"):
+            torch.set_num_threads(max(1, min(8, affinity["cpus"])))
+
+    tag = {"kaist": "kaist", "FLIR": "FLIR", "VEDAI": "VEDAI", "LLVIP": "LLVIP"}[args.dataset]
+    yaml_name = f"yolov5{args.model}_Transfusion_{tag}.yaml"
+    cfg = yaml.safe_load(open(os.path.join(ROOT, "models", "transformer", yaml_name)))
+    model = Model(cfg).eval()
+    sd = synth_state_dict(model, seed=0)
+    model.load_state_dict(sd)
+    for i in (20, 21, 22):
+        model.model[i].crosstransformer[0].loops = args.loops
+        model.model[i].fuse_tail = not args.no_fuse_tail
+    model = model.to(dev)
+    model.compute_dtype = DT[args.dtype]
+    model.static_outputs = True
+    model.fold_upsample = args.fold_upsample
+    model.autotune = not args.no_autotune
+    B, H, W = args.batch, args.height, args.width
+    strong = args.global_batch > 0
+    if strong:                          # contiguous shards of a fixed global batch; uneven splits pad the short ranks to the longest shard
+        lo, hi = D.shard_range(args.global_batch, rank, world)
+        n_local, B = hi - lo, D.padded_local_batch(args.global_batch, world)
+    else:
+        n_local = B
+    default_cache = os.path.join(ROOT, "profiles", "tune_cache.json")     # committed igemm tile choices: the same kernels
+    if args.tune_cache and os.path.exists(args.tune_cache):               # run (and were profiled) from round to round;
+        ops.load_tune_cache(args.tune_cache)                              # layers missing from it are tuned on the spot
+    elif not args.tune_cache and os.path.exists(default_cache):
+        ops.load_tune_cache(default_cache)
+    model.use_graph = not args.no_graph
+    if args.force_gather and world == 1 and not tdist.is_initialized():
+        os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
+        os.environ.setdefault("MASTER_PORT", "29517")
+        tdist.init_process_group(backend="nccl", rank=0, world_size=1)
+    pipe = DetectionPipeline(model, B, H, W, dev, conf_thres=args.conf, iou_thres=args.iou, world=world,
+                             overlap=not args.no_overlap, depth=args.depth, force_gather=args.force_gather and world == 1)
+    plan = pipe.plan
+    if args.tune_cache and rank == 0:
+        ops.save_tune_cache(args.tune_cache)
+    # inputs resident in HBM before the timed region: each rank synthesises its own shard of the global batch
+    rgb, ir = synth_images(B, H, W, seed=100 + rank)              # (strong scaling: rows >= n_local of a short rank are padding pairs)
+    for pl in pipe.plans:
+        pl.inputs[0].copy_(rgb.to(dev))
+        pl.inputs[1].copy_(ir.to(dev))
+    nc = cfg["nc"]
+    torch.cuda.synchronize()
+    step = pipe.step
+
+    def barrier():
+        if world > 1:
+            tdist.barrier()
+
+    for _ in range(args.warmup):
+        step()
+    # The timed region of the contract — barrier + synchronize, exactly K steps, synchronize + barrier, MAX over ranks.  A plain run
+    # runs it once.  --full runs it `repeats` times back to back and `value` comes from the MEDIAN run: one region is only K x ~2.6 ms
+    # long, and a single sample of it moves by several per cent with the box's clocks / whatever else the host is doing.
+    runs = []
+    while len(runs) < max(1, args.repeats) or (sum(runs) < args.min_timed_seconds and len(runs) < 2000):
+        torch.cuda.synchronize()
+        barrier()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(args.steps):
+            det, count = step()[:2]
+        pipe.synchronize()                      # (N > 1: also sends a gather group that K steps left incomplete)
+        torch.cuda.synchronize()
+        barrier()
+        el = time.perf_counter() - t0
+        if world > 1:
+            t = torch.tensor([el], dtype=torch.float64, device=dev)
+            tdist.all_reduce(t, op=tdist.ReduceOp.MAX)
+            el = float(t.item())
+        runs.append(el)
+    elapsed = sorted(runs)[len(runs) // 2]
+    first_count = int(count.reshape(-1)[0])
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, det, count)
+    workload = (f"{yaml_name[:-5]} + DMFF(loops={args.loops}) {args.dtype}, batch {B}/GPU, "
+                f"{H}x{W} synthetic RGB/IR pairs, seeded random weights, NMS conf {args.conf} iou {args.iou}")
+    extra = full_figures(args, cfg, sd, model, pipe, B, H, W, n_local, dev, rank, world, barrier, workload) if args.full else None
+
+    if rank == 0:
+        pairs = (args.global_batch if strong else B * world) * args.steps
+        value = pairs / elapsed
+        out = {
+            "metric": "RGB/IR image-pairs/sec (two-stream forward + NMS)", "value": round(value, 2), "unit": "pairs/s",
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(1e3 * elapsed / args.steps, 3),
+            "repeats": len(runs), "timed_seconds": round(sum(runs), 3), "value_min": round(pairs / max(runs), 2), "value_max": round(pairs / min(runs), 2),
+            "higher_is_better": True, "scaling": "strong" if strong else "weak", "vs_baseline": None, "dtype": args.dtype, "data": "synthetic",
+            "config": {"workload": workload,
+                       "global_batch": args.global_batch if strong else B * world,
+                       "local_batches": [D.shard_range(args.global_batch, r, world)[1] - D.shard_range(args.global_batch, r, world)[0]
+                                         for r in range(world)] if strong else [B] * world,
+                       "parallelism": f"dp{world} (pairs sharded, one all-gather of detections)",
+                       "world_size_of_process_group": tdist.get_world_size() if world > 1 else 1,
+                       "rank0_cpu_affinity": affinity,
+                       "backend": tdist.get_backend() if world > 1 else None,
+                       "graph": not args.no_graph, "nms_overlapped_with_next_forward": not args.no_overlap, "batches_in_flight": pipe.depth, "forced_one_rank_all_gather": bool(pipe.gather and world == 1),
+                       "all_gather": {"steps_per_collective": pipe.group, "bytes_per_rank_per_collective": int(pipe.group_block.numel() * 4) if pipe.group > 1 else int(pipe.group_block.numel() * 4 // max(1, len(pipe.runners))),
+                                      "stream": "own stream behind the group's last NMS"} if pipe.gather else None,
+                       "fused_paths": pipe.plans[0].fusion_report(),
+                       "plan_options": OPT.as_dict(), "plan_options_not_default": OPT.non_default()},
+            "plan_buffer_MB": round(plan.nbytes / 2 ** 20, 1),
+            "detections_first_image": first_count,
+        }
+        if extra:
+            out.update(extra)
         # ONE JSON line, and the LAST thing on stdout: RCCL prints a version banner through C stdio when its first communicator comes up
         # (N > 1, --force-gather); flush that buffer first, or it lands after (or inside) the line when the process exits
         import ctypes

@@ -70,6 +70,14 @@ def test_shard_and_gather_world2():
     assert res == [(0, True, (0, 3)), (1, True, (3, 6))]
 
 
+def _launcher_env():
+    """Environment of a launcher subprocess: no torchrun variables, and no GPU — these ranks are gloo ranks on the host even where a
+    GPU exists (with one, N ranks would each ask for their own device ordinal)."""
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    env["HIP_VISIBLE_DEVICES"] = env["CUDA_VISIBLE_DEVICES"] = "-1"
+    return env
+
+
 def test_bench_launches_its_own_ranks():
     """`python bench.py --gpus 2` with no torchrun environment must start two ranks itself (it silently ran one and reported
     n_gpus 1).  --dry-run stops after the process group + one detection-block all-gather (gloo here, RCCL on a GPU node)."""
@@ -77,7 +85,7 @@ def test_bench_launches_its_own_ranks():
     import subprocess
     import sys
     repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    env = _launcher_env()
     r = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--gpus", "2", "--dry-run"], capture_output=True, text=True, timeout=300, env=env)
     assert r.returncode == 0, r.stdout[-1000:] + r.stderr[-3000:]
     line = [l for l in r.stdout.splitlines() if l.startswith("{")][-1]
@@ -116,7 +124,7 @@ def test_bench_strong_scaling_launch_with_four_ranks_and_an_uneven_split():
     import subprocess
     import sys
     repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    env = _launcher_env()
     r = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--gpus", "4", "--global-batch", "10", "--dry-run"],
                        capture_output=True, text=True, timeout=300, env=env)
     assert r.returncode == 0, r.stdout[-1000:] + r.stderr[-3000:]
@@ -139,7 +147,7 @@ def test_bench_world8_dry_run_of_the_eight_gpu_baseline_configurations(name, cfg
     import subprocess
     import sys
     repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    env = _launcher_env()
     env["OMP_NUM_THREADS"] = "1"
     bench = os.path.join(repo, "bench.py")
     with socket.socket() as s:

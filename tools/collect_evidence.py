@@ -1,13 +1,13 @@
 #!/usr/bin/env python3
-"""Copy the summaries a tools/gpu_evidence.sh call left in gpurun_out/ into profiles/ under the round's prefix (the files the judge reads are the
-tracked ones under profiles/; gpurun_out/ is scratch).      python tools/collect_evidence.py r05"""
+"""Copy the summaries a tools/gpu_evidence.sh call left in its results folder ($OUT, default results/) into profiles/ under the round's
+prefix (the tracked files are the ones under profiles/; the results folder is scratch).      [OUT=dir] python tools/collect_evidence.py r05"""
 import os
 import shutil
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 tag = sys.argv[1]
-G, P = os.path.join(ROOT, "gpurun_out"), os.path.join(ROOT, "profiles")
+G, P = os.path.join(ROOT, os.environ.get("OUT") or "results"), os.path.join(ROOT, "profiles")
 CFG = {"c3": "c3_l_bf16_b32_640", "c4": "c4_s_bf16_b64_512x640_loops3", "c5": "c5_l_vedai_f16_b16_1280"}
 pairs = [("bench.json", f"{tag}_bench_s_bf16_b32.json"), ("prof_default_kernel_stats.csv", f"{tag}_bench_s_bf16_b32_kernel_stats.csv"),
          ("prof_depth1_kernel_stats.csv", f"{tag}_bench_s_bf16_b32_depth1_kernel_stats.csv"),

@@ -9,7 +9,7 @@
 #           its own HIP context); TESTS_LIB = the library they run on (default: the product library)
 #   LIBS    space-separated "<name>:<path to a variant .so, empty = product library>" (tools/build_variant.py writes the variants); ENVS likewise
 #           "<name>:<VAR=value,VAR=value>" for A/B switches read from the environment
-#   BENCH   bench.py arguments (always with --no-cpu-baseline --no-latency --no-h2d); CONFIG = c3 / c4 / c5 adds that BASELINE configuration's shard
+#   BENCH   bench.py arguments (always with --full --no-cpu-baseline --no-latency --no-h2d); CONFIG = c3 / c4 / c5 adds that BASELINE configuration's shard
 #           arguments and its committed tune cache (a /tmp copy: a re-tune inside the call must not edit the tracked file)
 #   REPS    interleaved repetitions (default 2): lib1 lib2 lib1 lib2 ... — box drift hits every leg alike
 #   FIELDS  extra dotted paths into the bench line printed per run (kernels.<name> prints that kernel's microseconds per step)
@@ -51,9 +51,9 @@ if [ -n "${BENCH+x}" ] || [ -n "$CONFIG" ]; then
     for spec in $LIBS ${ENVS:+$ENVS}; do
       name=${spec%%:*}; val=${spec#*:}; f=gpurun_out/${TAG}_${name}$r
       if [[ " $ENVS " == *" $spec "* ]]; then
-        env $(echo "$val" | tr ',' ' ') timeout ${BENCH_TIMEOUT:-300} python bench.py --no-cpu-baseline --no-latency --no-h2d $CARGS $BENCH > $f.json 2> $f.err
+        env $(echo "$val" | tr ',' ' ') timeout ${BENCH_TIMEOUT:-300} python bench.py --full --no-cpu-baseline --no-latency --no-h2d $CARGS $BENCH > $f.json 2> $f.err
       else
-        ICAF_LIB=${val:+$R/$val} timeout ${BENCH_TIMEOUT:-300} python bench.py --no-cpu-baseline --no-latency --no-h2d $CARGS $BENCH > $f.json 2> $f.err
+        ICAF_LIB=${val:+$R/$val} timeout ${BENCH_TIMEOUT:-300} python bench.py --full --no-cpu-baseline --no-latency --no-h2d $CARGS $BENCH > $f.json 2> $f.err
       fi
       show $f.json
     done
