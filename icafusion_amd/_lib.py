@@ -84,6 +84,7 @@ SIGNATURES = {
     "icaf_bottleneck": (_i, [C.POINTER(BneckArgs), _p]),
     "icaf_conv2d_kernel_name": (_i, [C.POINTER(ConvArgs), C.c_char_p, _i]),
     "icaf_sppf_pool": (_i, [_p, _i, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p]),
+    "icaf_sppf_config": (_i, [_i, _i, _i, _i, C.POINTER(_i)]),
     "icaf_upsample_nearest": (_i, [_p, _i, _p, _i, _i, _i, _i, _i, _i, _i, _p]),
     "icaf_copy_channels": (_i, [_p, _i, _p, _i, _i, _ll, _i, _p]),
     "icaf_axpby": (_i, [_p, _i, _p, _i, _p, _i, _i, _ll, _i, _f, _f, _p]),
@@ -91,6 +92,7 @@ SIGNATURES = {
                                    _f, _f, _f, _f, _p]),
     "icaf_layernorm": (_i, [_p, _p, _p, _p, _p, _p, _i, _ll, _i, _i, _f, _p]),
     "icaf_cross_attention": (_i, [_p, _p, _i, _i, _i, _i, _i, _p]),
+    "icaf_cross_attention_config": (_i, [_i, _i, _i, _i, _i, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)]),
     "icaf_dmff_ln_qkv": (_i, [C.POINTER(DmffArgs), _p]),
     "icaf_dmff_attn_mlp": (_i, [C.POINTER(DmffArgs), _p]),
     "icaf_dmff_wide_ln_qkv": (_i, [C.POINTER(DmffArgs), _p]),
@@ -100,6 +102,7 @@ SIGNATURES = {
     "icaf_dmff_attn_mlp_lds_bytes": (_i, [_i, _i, _i, _i, C.POINTER(_sz)]),
     "icaf_dmff_upsample_merge": (_i, [_p, _p, _i, _p, _i, _p, _i, _i, _i, _i, _i, _i, _i, _i, _p]),
     "icaf_detect_decode": (_i, [_p, _i, _p, _p, _p, _i, _i, _i, _i, _i, _ll, _ll, _f, C.POINTER(_f), _p]),
+    "icaf_detect_decode_kernel": (_i, [_p, _i, _p, _p, _i, _i, _i, _i, _i, C.POINTER(_i)]),
     "icaf_detect_conv": (_i, [C.POINTER(ConvArgs), _p, _p, _p, _i, _i, _ll, _ll, _f, C.POINTER(_f), _p]),
     "icaf_match_predictions": (_i, [_p, _p, _i, _i, _p, _p, _i, _p, _p, _i, _p, _p, _p]),
     "icaf_nms_workspace_bytes": (_i, [_i, _ll, _i, _i, C.POINTER(_sz)]),

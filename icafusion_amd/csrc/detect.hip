@@ -229,6 +229,25 @@ static int launch_detect_conv(const ConvP& p, const DetectEpi<NA, NO>& epi, hipS
 
 using namespace icaf;
 
+// Which kernel icaf_detect_decode launches, decided in ONE place for the launch and for icaf_detect_decode_kernel.  Per-pixel kernel:
+// 3 anchors, no in {6, 8, 14}, 8-byte aligned pixel runs and output rows, unless the probe knob detect_elementwise is set.
+enum { DETECT_PIXEL = 0, DETECT_ELEMENT = 1 };
+
+static int detect_select(const float* p, int ldp, const float* z, const float* raw, int B, int ny, int nx, int na, int no) {
+    const bool aligned = ldp % 2 == 0 && ((uintptr_t)p & 7) == 0 && ((uintptr_t)z & 7) == 0 && (!raw || ((uintptr_t)raw & 7) == 0);
+    const bool pixel = na == 3 && (no == 6 || no == 8 || no == 14) && aligned && (long long)B * ny * nx < (1ll << 31) && !g_opt.detect_elementwise;
+    return pixel ? DETECT_PIXEL : DETECT_ELEMENT;
+}
+
+extern "C" int icaf_detect_decode_kernel(const float* p, int ldp, const float* z, const float* raw, int B, int ny, int nx, int na, int no,
+                                         int* kernel) {
+    if (!p || !z || !kernel) return fail(ICAF_ERR_ARG, "icaf_detect_decode_kernel: null pointer");
+    if (na < 1 || na > 8 || no < 6 || ldp < na * no) return fail(ICAF_ERR_ARG, "icaf_detect_decode_kernel: bad na/no/ldp");
+    if (B < 1 || ny < 1 || nx < 1) return fail(ICAF_ERR_ARG, "icaf_detect_decode_kernel: empty level");
+    *kernel = detect_select(p, ldp, z, raw, B, ny, nx, na, no);
+    return ICAF_OK;
+}
+
 extern "C" int icaf_detect_decode(const float* p, int ldp, float* z, float* logits, float* raw, int B, int ny, int nx, int na, int no,
                                   long long rows_total, long long row_offset, float stride, const float* anchors_px, icaf_stream_t s) {
     if (!p || !z || !anchors_px) return fail(ICAF_ERR_ARG, "icaf_detect_decode: null pointer");
@@ -240,9 +259,7 @@ extern "C" int icaf_detect_decode(const float* p, int ldp, float* z, float* logi
     long long blocks = (cells + 255) / 256;
     if (blocks > 256 * 32) blocks = 256 * 32;
     if (B < 1 || ny < 1 || nx < 1) return fail(ICAF_ERR_ARG, "icaf_detect_decode: empty level");
-    // per-pixel kernel: 3 anchors, even `no` in use, 8-byte aligned pixel runs and output rows
-    const bool aligned = ldp % 2 == 0 && ((uintptr_t)p & 7) == 0 && ((uintptr_t)z & 7) == 0 && (!raw || ((uintptr_t)raw & 7) == 0);
-    if (na == 3 && aligned && (long long)B * ny * nx < (1ll << 31) && !g_opt.detect_elementwise) {
+    if (detect_select(p, ldp, z, raw, B, ny, nx, na, no) == DETECT_PIXEL) {
         if (no == 6) return launch_detect_pixel<3, 6>(p, ldp, z, logits, raw, B, ny, nx, rows_total, row_offset, stride, anc, S(s));
         if (no == 8) return launch_detect_pixel<3, 8>(p, ldp, z, logits, raw, B, ny, nx, rows_total, row_offset, stride, anc, S(s));
         if (no == 14) return launch_detect_pixel<3, 14>(p, ldp, z, logits, raw, B, ny, nx, rows_total, row_offset, stride, anc, S(s));

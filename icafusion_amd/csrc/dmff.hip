@@ -463,21 +463,22 @@ __global__ __launch_bounds__(256) void upsample_merge_kernel(const typename Elem
     }
 }
 
-template <int DT, int DKP>
-static int launch_attn(const void* qkv, void* out, int B, int N, int C, int DK, int heads, hipStream_t s) {
-    using T = typename Elem<DT>::type;
-    constexpr int EB = Elem<DT>::BYTES;
+// The launch choice of icaf_cross_attention — padded head dimension, query splits per head, XCD remap — made in ONE place for the launch
+// and for icaf_cross_attention_config (tests read it back there; the probe knob attn_qsplit is part of the choice).
+struct AttnCfg { int dk, dkp, nqt, qsplit, remap; };
+
+static int attn_select(int dtype, int B, int N, int C, int heads, AttnCfg& c) {
+    if (dtype < ICAF_F32 || dtype > ICAF_F16) return fail(ICAF_ERR_ARG, "icaf_cross_attention: bad dtype %d", dtype);
+    if (heads < 1 || C % heads) return fail(ICAF_ERR_ARG, "icaf_cross_attention: C=%d not divisible by heads=%d", C, heads);
+    const int DK = C / heads, vec = dtype == ICAF_F32 ? 4 : 8;
+    if (DK % vec) return fail(ICAF_ERR_UNSUPPORTED, "icaf_cross_attention: head dim %d must be a multiple of %d for this dtype", DK, vec);
+    if (B < 1 || N < 1 || 2LL * B > 65535) return fail(ICAF_ERR_ARG, "icaf_cross_attention: bad B/N");
+    if (DK > 128) return fail(ICAF_ERR_UNSUPPORTED, "icaf_cross_attention: head dim %d > 128", DK);
+    c.dk = DK;
+    c.dkp = DK <= 16 ? 16 : DK <= 32 ? 32 : DK <= 48 ? 48 : DK <= 64 ? 64 : DK <= 96 ? 96 : 128;
     const int NP = (N + 31) & ~31;
-    const size_t lds = (size_t)NP * (DKP * EB + 16) + (size_t)(DKP + (AttnCore<DT, DKP>::ones_row() ? 1 : 0)) * ((size_t)NP * EB + 16);
-    if (lds > 160 * 1024) return fail(ICAF_ERR_UNSUPPORTED, "icaf_cross_attention: %zu bytes of LDS needed (N=%d, dk=%d) exceed 160 KiB", lds, N, DK);
-    static std::atomic<bool> attr_set[ICAF_MAX_DEVICES];          // per instantiation and per device
-    int dev = 0;
-    ICAF_HIP(hipGetDevice(&dev));
-    if (lds > 64 * 1024 && dev >= 0 && dev < ICAF_MAX_DEVICES && !attr_set[dev]) {
-        ICAF_HIP(hipFuncSetAttribute((const void*)cross_attn_kernel<DT, DKP>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        attr_set[dev] = true;
-    }
     const int nqt = NP / 32;
+    c.nqt = nqt;
     // Query splits per head: every split stages the head's K / V^T again (25 - 100 KB through scalar LDS transposition writes), so as FEW as
     // the chip needs: two workgroups per CU (512) must exist, beyond that one split — except at d_k <= 16 with many query tiles, where a wave
     // walking seven tiles alone is the longer pole (round 5, same box, batch 32: yolov5s P3 28.5 us with 4 splits, 25.5 with 2, 26.5 with 1;
@@ -492,24 +493,44 @@ static int launch_attn(const void* qkv, void* out, int B, int N, int C, int DK, 
         const int forced = g_opt.attn_qsplit;
         if (forced > 0) qsplit = forced < nqt ? forced : nqt;
     }
+    c.qsplit = qsplit;
+    c.remap = (2 * B) % 8 == 0 && heads * DK == C;                  // whole (direction, image) groups per XCD
+    return ICAF_OK;
+}
+
+template <int DT, int DKP>
+static int launch_attn(const void* qkv, void* out, int B, int N, int C, int heads, const AttnCfg& c, hipStream_t s) {
+    using T = typename Elem<DT>::type;
+    constexpr int EB = Elem<DT>::BYTES;
+    const int DK = c.dk, qsplit = c.qsplit;
+    const int NP = (N + 31) & ~31;
+    const size_t lds = (size_t)NP * (DKP * EB + 16) + (size_t)(DKP + (AttnCore<DT, DKP>::ones_row() ? 1 : 0)) * ((size_t)NP * EB + 16);
+    if (lds > 160 * 1024) return fail(ICAF_ERR_UNSUPPORTED, "icaf_cross_attention: %zu bytes of LDS needed (N=%d, dk=%d) exceed 160 KiB", lds, N, DK);
+    static std::atomic<bool> attr_set[ICAF_MAX_DEVICES];          // per instantiation and per device
+    int dev = 0;
+    ICAF_HIP(hipGetDevice(&dev));
+    if (lds > 64 * 1024 && dev >= 0 && dev < ICAF_MAX_DEVICES && !attr_set[dev]) {
+        ICAF_HIP(hipFuncSetAttribute((const void*)cross_attn_kernel<DT, DKP>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        attr_set[dev] = true;
+    }
     const float scale_l2e = (float)((1.0 / sqrt((double)DK)) * 1.4426950408889634);
-    const bool remap = (2 * B) % 8 == 0 && heads * DK == C;          // whole (direction, image) groups per XCD
     dim3 grid((unsigned)qsplit, (unsigned)heads, (unsigned)(2 * B));
-    if (remap) grid = dim3((unsigned)(qsplit * heads * 2 * B), 1u, 1u);
-    hipLaunchKernelGGL((cross_attn_kernel<DT, DKP>), grid, dim3(256), lds, s, (const T*)qkv, (T*)out, B, N, C, DK, NP, scale_l2e, remap ? qsplit : 0);
+    if (c.remap) grid = dim3((unsigned)(qsplit * heads * 2 * B), 1u, 1u);
+    hipLaunchKernelGGL((cross_attn_kernel<DT, DKP>), grid, dim3(256), lds, s, (const T*)qkv, (T*)out, B, N, C, DK, NP, scale_l2e, c.remap ? qsplit : 0);
     ICAF_LAUNCH_CHECK();
     return ICAF_OK;
 }
 
 template <int DT>
-static int dispatch_attn(const void* qkv, void* out, int B, int N, int C, int DK, int heads, hipStream_t s) {
-    if (DK <= 16) return launch_attn<DT, 16>(qkv, out, B, N, C, DK, heads, s);
-    if (DK <= 32) return launch_attn<DT, 32>(qkv, out, B, N, C, DK, heads, s);
-    if (DK <= 48) return launch_attn<DT, 48>(qkv, out, B, N, C, DK, heads, s);
-    if (DK <= 64) return launch_attn<DT, 64>(qkv, out, B, N, C, DK, heads, s);
-    if (DK <= 96) return launch_attn<DT, 96>(qkv, out, B, N, C, DK, heads, s);
-    if (DK <= 128) return launch_attn<DT, 128>(qkv, out, B, N, C, DK, heads, s);
-    return fail(ICAF_ERR_UNSUPPORTED, "icaf_cross_attention: head dim %d > 128", DK);
+static int dispatch_attn(const void* qkv, void* out, int B, int N, int C, int heads, const AttnCfg& c, hipStream_t s) {
+    switch (c.dkp) {
+        case 16: return launch_attn<DT, 16>(qkv, out, B, N, C, heads, c, s);
+        case 32: return launch_attn<DT, 32>(qkv, out, B, N, C, heads, c, s);
+        case 48: return launch_attn<DT, 48>(qkv, out, B, N, C, heads, c, s);
+        case 64: return launch_attn<DT, 64>(qkv, out, B, N, C, heads, c, s);
+        case 96: return launch_attn<DT, 96>(qkv, out, B, N, C, heads, c, s);
+        default: return launch_attn<DT, 128>(qkv, out, B, N, C, heads, c, s);
+    }
 }
 
 }  // namespace icaf
@@ -613,11 +634,19 @@ extern "C" int icaf_layernorm(const void* x, void* y, const float* gamma0, const
 
 extern "C" int icaf_cross_attention(const void* qkv, void* out, int dtype, int B, int N, int C, int heads, icaf_stream_t s) {
     if (!qkv || !out) return fail(ICAF_ERR_ARG, "icaf_cross_attention: null pointer");
-    if (heads < 1 || C % heads) return fail(ICAF_ERR_ARG, "icaf_cross_attention: C=%d not divisible by heads=%d", C, heads);
-    const int DK = C / heads, vec = dtype == ICAF_F32 ? 4 : 8;
-    if (DK % vec) return fail(ICAF_ERR_UNSUPPORTED, "icaf_cross_attention: head dim %d must be a multiple of %d for this dtype", DK, vec);
-    if (B < 1 || N < 1 || 2LL * B > 65535) return fail(ICAF_ERR_ARG, "icaf_cross_attention: bad B/N");
-    DISPATCH_DT(dtype, dispatch_attn, qkv, out, B, N, C, DK, heads, S(s));
+    AttnCfg c;
+    if (const int st = attn_select(dtype, B, N, C, heads, c)) return st;
+    DISPATCH_DT(dtype, dispatch_attn, qkv, out, B, N, C, heads, c, S(s));
+}
+
+extern "C" int icaf_cross_attention_config(int dtype, int B, int N, int C, int heads, int* dkp, int* qsplit, int* remap) {
+    if (!dkp || !qsplit || !remap) return fail(ICAF_ERR_ARG, "icaf_cross_attention_config: null pointer");
+    AttnCfg c;
+    if (const int st = attn_select(dtype, B, N, C, heads, c)) return st;
+    *dkp = c.dkp;
+    *qsplit = c.qsplit;
+    *remap = c.remap;
+    return ICAF_OK;
 }
 
 extern "C" int icaf_dmff_upsample_merge(const void* tokens, const void* fea_rgb, int ld_rgb, const void* fea_ir, int ld_ir, void* out,

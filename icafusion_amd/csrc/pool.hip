@@ -337,6 +337,26 @@ extern "C" int icaf_preprocess_u8(const unsigned char* img, void* out, int dtype
 }
 
 
+// Channel vectors per workgroup of icaf_sppf_pool (0 = the global-memory kernel), chosen in ONE place for the launch and for
+// icaf_sppf_config: the largest group whose plane fits.  A cap of 2 (twice the workgroups) is faster in isolation
+// (lab/probes/sppf_vpb.py, 64 x 20x20 x 256 bf16: 32.7 -> 29.3 us) and slower in the forward (35 -> 40 us, input not cache-resident)
+static int sppf_select(int dtype, int H, int W, int C) {
+    const int nv = C / vec_of(dtype);
+    int cap = 8;
+    if (g_opt.sppf_vpb > 0) cap = g_opt.sppf_vpb;                                         // probe knob (icaf_set_option)
+    for (int c : {8, 4, 2, 1})
+        if (c <= cap && nv % c == 0 && (size_t)H * W * c * 32 <= 60 * 1024) return c;
+    return 0;
+}
+
+extern "C" int icaf_sppf_config(int dtype, int H, int W, int C, int* vpb) {
+    if (!vpb) return fail(ICAF_ERR_ARG, "icaf_sppf_config: null pointer");
+    if (dtype < 0 || dtype > 2) return fail(ICAF_ERR_ARG, "icaf_sppf_config: bad dtype");
+    if (H < 1 || W < 1 || C < 1 || C % vec_of(dtype)) return fail(ICAF_ERR_ARG, "icaf_sppf_config: bad geometry");
+    *vpb = sppf_select(dtype, H, W, C);
+    return ICAF_OK;
+}
+
 extern "C" int icaf_sppf_pool(const void* x, int ldx, void* y1, void* y2, void* y3, int ldy, int dtype, int B, int H, int W, int C,
                               int k, icaf_stream_t s) {
     if (!x || !y1 || !y2 || !y3) return fail(ICAF_ERR_ARG, "icaf_sppf_pool: null pointer");
@@ -344,12 +364,7 @@ extern "C" int icaf_sppf_pool(const void* x, int ldx, void* y1, void* y2, void* 
     const int vec = vec_of(dtype);
     if (C % vec || ldx % vec || ldy % vec || !(k & 1)) return fail(ICAF_ERR_ARG, "icaf_sppf_pool: C/ld must be multiples of %d and k odd", vec);
     const int nv = C / vec;
-    // channel vectors per workgroup: the largest group whose plane fits.  A cap of 2 (twice the workgroups) is faster in isolation
-    // (lab/probes/sppf_vpb.py, 64 x 20x20 x 256 bf16: 32.7 -> 29.3 us) and slower in the forward (35 -> 40 us, input not cache-resident)
-    int vpb = 0, cap = 8;
-    if (g_opt.sppf_vpb > 0) cap = g_opt.sppf_vpb;                                         // probe knob (icaf_set_option)
-    for (int c : {8, 4, 2, 1})
-        if (c <= cap && nv % c == 0 && (size_t)H * W * c * 32 <= 60 * 1024) { vpb = c; break; }
+    const int vpb = sppf_select(dtype, H, W, C);
     if (vpb) {
         const size_t lds = (size_t)H * W * vpb * 32;
         dim3 grid((unsigned)(B * (nv / vpb))), block(256);

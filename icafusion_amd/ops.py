@@ -533,6 +533,13 @@ def sppf_pool(x, y1, y2, y3, k, name="sppf_pool"):
                   nbytes=nb)
 
 
+def sppf_config(dtype, H, W, Cc):
+    """Channel vectors per workgroup icaf_sppf_pool picks for this geometry (0 = the global-memory kernel), the probe knob included."""
+    v = C.c_int(-1)
+    check(lib().icaf_sppf_config(dtype_code(dtype), H, W, Cc, C.byref(v)), "icaf_sppf_config")
+    return v.value
+
+
 def upsample_nearest(x, y, scale, name="upsample_nearest"):
     B, H, W, Cc, ldx = _act_geom(x)
     By, Hy, Wy, Cy, ldy = _act_geom(y)
@@ -594,6 +601,14 @@ def cross_attention(qkv, out, B, N, heads, name="cross_attention"):
     nb = (qkv.numel() + out.numel()) * qkv.element_size()
     return Launch(lib().icaf_cross_attention, (qkv.data_ptr(), out.data_ptr(), dtype_code(qkv.dtype), B, N, Cc,
                                                heads), keep=(qkv, out), name=name, flops=flops, nbytes=nb)
+
+
+def cross_attention_config(dtype, B, N, Cc, heads):
+    """(padded head dimension, query splits per head, XCD remap 0 / 1) icaf_cross_attention picks for this shape, the probe knob included."""
+    dkp, qs, rm = C.c_int(-1), C.c_int(-1), C.c_int(-1)
+    check(lib().icaf_cross_attention_config(dtype_code(dtype), B, N, Cc, heads, C.byref(dkp), C.byref(qs), C.byref(rm)),
+          "icaf_cross_attention_config")
+    return dkp.value, qs.value, rm.value
 
 
 def dmff_fused_lds_bytes(C_, N, heads, dt):
@@ -751,6 +766,15 @@ def detect_decode(p, z, logits, raw, na, no, row_offset, stride, anchors_px, nam
                   (p.data_ptr(), ldp, z.data_ptr(), logits.data_ptr() if logits is not None else None,
                    raw.data_ptr() if raw is not None else None, B, ny, nx, na, no, z.shape[1], row_offset,
                    float(stride), arr), keep=(p, z, logits, raw, arr), name=name, nbytes=nb)
+
+
+def detect_decode_kernel(p, z, raw, na, no):
+    """Kernel icaf_detect_decode launches for these tensors: 0 = one thread per pixel, 1 = one thread per element (alignment counts)."""
+    B, ny, nx, cp, ldp = _act_geom(p)
+    k = C.c_int(-1)
+    check(lib().icaf_detect_decode_kernel(p.data_ptr(), ldp, z.data_ptr(), raw.data_ptr() if raw is not None else None, B, ny, nx, na, no,
+                                          C.byref(k)), "icaf_detect_decode_kernel")
+    return k.value
 
 
 def detect_conv_ok(x, na, no, cin):

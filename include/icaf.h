@@ -198,6 +198,9 @@ int icaf_conv2d_kernel_name(const icaf_conv_args* a, char* buf, int buf_len);
  */
 int icaf_sppf_pool(const void* x, int ldx, void* y1, void* y2, void* y3, int ldy, int dtype, int B, int H, int W,
                    int C, int k, icaf_stream_t s);
+/* launch choice of icaf_sppf_pool for this geometry (SPPF.forward, models/common.py:262-267): *vpb = channel vectors per
+ * workgroup of the LDS kernel (8 / 4 / 2 / 1, the probe knob "sppf_vpb" included), 0 = the global-memory kernel */
+int icaf_sppf_config(int dtype, int H, int W, int C, int* vpb);
 int icaf_upsample_nearest(const void* x, int ldx, void* y, int ldy, int dtype, int B, int H, int W, int C,
                           int scale, icaf_stream_t s);
 int icaf_copy_channels(const void* x, int ldx, void* y, int ldy, int dtype, long long rows, int C,
@@ -228,6 +231,9 @@ int icaf_layernorm(const void* x, void* y, const float* gamma0, const float* bet
                    const float* beta1, int dtype, long long rows_per_group, int C, int groups, float eps,
                    icaf_stream_t s);
 int icaf_cross_attention(const void* qkv, void* out, int dtype, int B, int N, int C, int heads, icaf_stream_t s);
+/* launch choice of icaf_cross_attention (CrossAttention.forward :670-685): *dkp = padded head dimension of the kernel instance,
+ * *qsplit = query splits per head (the probe knob "attn_qsplit" included), *remap = 1 when the one-dimensional XCD-grouped grid is used */
+int icaf_cross_attention_config(int dtype, int B, int N, int C, int heads, int* dkp, int* qsplit, int* remap);
 int icaf_dmff_upsample_merge(const void* tokens, const void* fea_rgb, int ld_rgb, const void* fea_ir, int ld_ir,
                              void* out, int ldo, int dtype, int B, int H, int W, int C, int th, int tw,
                              icaf_stream_t s);
@@ -241,6 +247,11 @@ int icaf_dmff_upsample_merge(const void* tokens, const void* fea_rgb, int ld_rgb
 int icaf_detect_decode(const float* p, int ldp, float* z, float* logits, float* raw, int B, int ny, int nx, int na,
                        int no, long long rows_total, long long row_offset, float stride, const float* anchors_px,
                        icaf_stream_t s);
+/* which kernel icaf_detect_decode launches for these arguments (models/yolo_test.py:43-65): *kernel = 0 one thread per pixel
+ * (3 anchors, no in {6, 8, 14}, 8-byte aligned rows), 1 one thread per element (every other head, or the probe knob
+ * "detect_elementwise").  Pointers, not shapes: their alignment is part of the choice; nothing is read through them. */
+int icaf_detect_decode_kernel(const float* p, int ldp, const float* z, const float* raw, int B, int ny, int nx, int na,
+                              int no, int* kernel);
 /* A Detect level in ONE launch (16-bit feature maps, 3 anchors, no in {6, 8, 14}): the level's 1x1 output convolution
  * (models/yolo_test.py:50; `a` describes it as for icaf_conv2d: 1x1, no activation, groups 1, Cout = na * no; a->y is ignored)
  * with the decode above as the epilogue of the persistent streaming GEMM — the fp32 conv map is never written.  z / logits / raw

@@ -82,7 +82,9 @@ def sample_idx(numel, tag, n=2048):
     return g.integers(0, numel, size=min(n, numel))
 
 
-def model_case(yt, name, yaml_name, batch, h, w, seed, loops=None):
+def model_case(yt, name, yaml_name, batch, h, w, seed, loops=None, sample_logits=False):
+    """sample_logits: store 2048 seeded samples of the logits (tag 99, plus `logits_shape`) instead of the whole tensor — keeps a
+    many-class, batch-2 fixture under 1 MB; the scores in `z` are still recorded in full."""
     ref_cfg = os.path.join(REF, "models", "transformer", yaml_name)
     ours = yaml.safe_load(open(os.path.join(REPO, "models", "transformer", yaml_name)))
     assert ours == yaml.safe_load(open(ref_cfg)), "config surface drifted from the reference"
@@ -106,6 +108,9 @@ def model_case(yt, name, yaml_name, batch, h, w, seed, loops=None):
     for hk in hooks:
         hk.remove()
     rec.update(z=z.numpy(), logits=logits.numpy())
+    if sample_logits:
+        rec["logits"] = logits.reshape(-1)[torch.from_numpy(sample_idx(logits.numel(), 99))].numpy().copy()
+        rec["logits_shape"] = np.asarray(logits.shape)
     for l, r in enumerate(raws):
         flat = r.reshape(-1)
         rec[f"raw{l}"] = flat[torch.from_numpy(sample_idx(flat.numel(), 100 + l))].numpy().copy()
@@ -397,6 +402,9 @@ def main():
     if "--n-only" in sys.argv:                        # yolov5n + DMFF (16-channel stem, C = 64 / 128 / 256 fusion blocks), added later
         model_case(yt, "model_n_flir_352x320_b2", "yolov5n_Transfusion_FLIR.yaml", 2, 352, 320, seed=14)
         return
+    if "--seadrone-only" in sys.argv:                 # nc = 7 (no = 12): the Detect levels run icaf_conv2d + the per-element decode kernel
+        model_case(yt, "model_m_seadrone_320_b2", "yolov5m_Transfusion_SeaDrone.yaml", 2, 320, 320, seed=16, sample_logits=True)
+        return
     if "--half-only" in sys.argv:                     # the real reference run in bf16 / fp16 on the CPU
         half_case(yt, "reference_16bit")
         return
@@ -437,6 +445,7 @@ def main():
     model_case(yt, "model_n_flir_352x320_b2", "yolov5n_Transfusion_FLIR.yaml", 2, 352, 320, seed=14)
     match_case(general, "match_predictions")
     model_case(yt, "model_s_kaist_544x672_b1", "yolov5s_Transfusion_kaist.yaml", 1, 544, 672, seed=15)
+    model_case(yt, "model_m_seadrone_320_b2", "yolov5m_Transfusion_SeaDrone.yaml", 2, 320, 320, seed=16, sample_logits=True)
     results_case(general, "result_files")
     pool_window_case(common, "adaptive_pool_windows")
     dataset_case("rect_dataset")

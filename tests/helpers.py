@@ -1,4 +1,5 @@
 """Shared helpers for the parity tests (test infrastructure; may import the oracle)."""
+import contextlib
 import os
 
 import numpy as np
@@ -33,3 +34,29 @@ def load_golden(name):
 def rel_err(a, b):
     a = np.asarray(a, np.float64); b = np.asarray(b, np.float64)
     return float(np.abs(a - b).max() / (np.abs(b).max() + 1e-12))
+
+
+def golden_logits(g, logits):
+    """(ours, the golden's) class logits of a model fixture: the whole tensor, or — for a fixture that recorded only seeded samples
+    of them (`logits_shape`, make_golden.py `sample_logits`) — ours sampled at the same indices."""
+    logits = np.asarray(logits)
+    if "logits_shape" not in g.files:
+        return logits, g["logits"]
+    assert tuple(logits.shape) == tuple(g["logits_shape"]), (logits.shape, g["logits_shape"])
+    return logits.reshape(-1)[sample_idx(logits.size, 99)], g["logits"]
+
+
+@contextlib.contextmanager
+def lib_option(name, value):
+    """Set one of libicaf.so's probe knobs (options.PlanOptions fields tagged lib=True) for the body of a `with`, and restore the
+    process's own value afterwards.  The knobs are pushed into the library once, when it is loaded: writing ICAF_OPTIONS or a legacy
+    variable into os.environ later changes nothing (tests/test_host_logic.py guards against such writes)."""
+    from icafusion_amd import _lib
+    from icafusion_amd.options import OPT
+    restore = OPT.lib_options()[name]
+    lib = _lib.lib()
+    _lib.check(lib.icaf_set_option(name.encode(), int(value)), f"icaf_set_option({name}, {value})")
+    try:
+        yield
+    finally:
+        _lib.check(lib.icaf_set_option(name.encode(), int(restore)), f"icaf_set_option({name}, {restore})")

@@ -1,6 +1,7 @@
 """Kernel-level parity on the MI355X: every C-ABI entry point vs the CPU oracle / plain fp32 torch on the same seeded
 inputs.  fp32 builds are held to 1e-3 relative (they land around 1e-6); bf16 / f16 builds carry their own tolerance,
 stated next to each check."""
+import contextlib
 import math
 
 import numpy as np
@@ -10,6 +11,7 @@ import torch.nn.functional as F
 
 pytestmark = pytest.mark.gpu
 
+from helpers import lib_option           # noqa: E402
 from icafusion_amd import ops            # noqa: E402
 from icafusion_amd.engine import Plan    # noqa: E402
 from oracle import icaf_oracle as oracle  # noqa: E402
@@ -1008,6 +1010,69 @@ def test_sppf_upsample_copy(dt):
     assert torch.equal(from_act(cp[..., 16:]), y1)
 
 
+def _sppf_ref(x, k):
+    y1 = F.max_pool2d(x, k, 1, k // 2)
+    y2 = F.max_pool2d(y1, k, 1, k // 2)
+    return y1, y2, F.max_pool2d(y2, k, 1, k // 2)
+
+
+def _sppf_run(x, dt, k, strided):
+    """icaf_sppf_pool on x (NCHW fp32, CPU); strided: x is a channel slice of a wider buffer and y1 / y2 / y3 are slices of one buffer
+    with a padded pixel stride (3C + one vector), whose padding must come back untouched.  Returns the three maps (NCHW fp32, CPU)."""
+    B, C, H, W = x.shape
+    xa = to_act(x, dt, pad_to=C + 16 if strided else None)
+    ld = 3 * C + (ops.VEC[dt] if strided else 0)
+    yb = torch.full((B, H, W, ld), -3.0, dtype=dt, device=DEV)
+    run(ops.sppf_pool(xa, yb[..., :C], yb[..., C:2 * C], yb[..., 2 * C:3 * C], k))
+    if strided:
+        assert bool((yb[..., 3 * C:] == -3.0).all()), "sppf wrote into the padding of its output rows"
+    return [from_act(yb[..., i * C:(i + 1) * C]) for i in range(3)]
+
+
+SPPF_CASES = [
+    # B, H, W, C, k, strided, {dtype: channel vectors per workgroup (0 = global-memory kernel)}
+    (2, 12, 20, 64, 5, True, {torch.float32: 8, torch.bfloat16: 8, torch.float16: 8}),
+    (3, 20, 20, 128, 3, True, {torch.float32: 4, torch.bfloat16: 4, torch.float16: 4}),
+    (1, 17, 21, 96, 5, True, {torch.float32: 4, torch.bfloat16: 4, torch.float16: 4}),     # the odd P5 map of the 544 x 672 rect batch
+    (2, 12, 20, 48, 9, True, {torch.float32: 4, torch.bfloat16: 2, torch.float16: 2}),     # C = 48: 6 vectors in 16 bit
+    (2, 30, 30, 64, 9, False, {torch.float32: 2, torch.bfloat16: 2, torch.float16: 2}),
+    (1, 40, 40, 512, 5, True, {torch.float32: 1, torch.bfloat16: 1, torch.float16: 1}),    # config 5 (1280^2): 40 x 40 at P5
+    (2, 48, 48, 64, 5, True, {torch.float32: 0, torch.bfloat16: 0, torch.float16: 0}),     # above ~1,920 pixels: the global-memory kernel
+    (1, 45, 50, 32, 3, False, {torch.float32: 0, torch.bfloat16: 0, torch.float16: 0}),
+    (1, 44, 52, 48, 9, True, {torch.float32: 0, torch.bfloat16: 0, torch.float16: 0}),
+]
+
+
+@pytest.mark.parametrize("dt", DTYPES)
+@pytest.mark.parametrize("case", SPPF_CASES, ids=lambda c: f"{c[0]}x{c[1]}x{c[2]}x{c[3]}-k{c[4]}{'-strided' if c[5] else ''}")
+def test_sppf_pool_every_branch(case, dt):
+    """Every launch branch of icaf_sppf_pool — LDS kernel with 8 / 4 / 2 / 1 channel vectors per workgroup and the global-memory kernel —
+    against the chain of F.max_pool2d(k, 1, k // 2): max pooling is exact, so bit for bit."""
+    B, H, W, C, k, strided, vpb = case
+    assert ops.sppf_config(dt, H, W, C) == vpb[dt]
+    x = rnd((B, C, H, W), 300 + H + C + k, 1.0)
+    got = _sppf_run(x, dt, k, strided)
+    for i, (g, r) in enumerate(zip(got, _sppf_ref(q(x, dt), k))):
+        assert torch.equal(g, r), f"y{i + 1}"
+
+
+@pytest.mark.parametrize("dt", DTYPES)
+def test_sppf_pool_forced_vectors_per_workgroup(dt):
+    """The probe knob sppf_vpb takes effect (the query shows it) and changes no bit of the result."""
+    B, H, W, C, k = 2, 12, 20, 64, 5
+    x = rnd((B, C, H, W), 333, 1.0)
+    ref = _sppf_ref(q(x, dt), k)
+    with lib_option("sppf_vpb", 0):
+        assert ops.sppf_config(dt, H, W, C) == 8
+        base = _sppf_run(x, dt, k, True)
+    for cap in (1, 2, 4):
+        with lib_option("sppf_vpb", cap):
+            assert ops.sppf_config(dt, H, W, C) == cap
+            got = _sppf_run(x, dt, k, True)
+        for i, (g, b, r) in enumerate(zip(got, base, ref)):
+            assert torch.equal(g, b) and torch.equal(g, r), f"vpb {cap}: y{i + 1}"
+
+
 POOL_CASES = [(2, 128, 40, 40, 20, 20), (1, 64, 40, 40, 16, 16), (1, 64, 64, 80, 20, 20), (2, 32, 10, 10, 10, 10),
               (1, 64, 68, 84, 20, 20),
               (1, 32, 30, 33, 7, 9),      # overlapping windows, token grid not a multiple of the 2x4 block per thread
@@ -1055,7 +1120,7 @@ def test_dmff_pool_tokens_and_upsample_merge(case, dt):
 
 
 @pytest.mark.parametrize("dt", DTYPES)
-@pytest.mark.parametrize("C", [64, 128, 512, 1024])
+@pytest.mark.parametrize("C", [64, 128, 512, 1024, 192, 384, 768])      # + the yolov5m widths
 def test_layernorm(C, dt):
     rows = 37
     x = rnd((2, rows, C), 31, 2.0) + 0.5
@@ -1094,6 +1159,95 @@ def test_cross_attention(case, dt):
         close(out[d].float().cpu(), ref, dt, f"cross attention dir {d} {case}", factor=2)
 
 
+def _attn_ref(f, B, N, C, heads):
+    """fp32 softmax(q k^T / sqrt(d_k)) v of both directions: f (2, B * N, 3C) -> (2, B * N, C)"""
+    dk = C // heads
+    f = f.reshape(2, B, N, 3, heads, dk)
+    out = []
+    for d in range(2):
+        qq = f[1 - d, :, :, 0].permute(0, 2, 1, 3)          # queries come from the OTHER modality
+        kk = f[d, :, :, 1].permute(0, 2, 1, 3)
+        vv = f[d, :, :, 2].permute(0, 2, 1, 3)
+        att = torch.softmax(qq @ kk.transpose(-1, -2) / math.sqrt(dk), -1)
+        out.append((att @ vv).permute(0, 2, 1, 3).reshape(B * N, C))
+    return torch.stack(out)
+
+
+# (N, C) at heads = 8: the production levels (yolov5n/s/m/l at 640: P3 400 tokens, P4 256, P5 100), then padded head dimensions
+# (d_k 40 -> 48, 72 -> 96) and ragged token counts
+ATT_PROD = [(400, 64), (400, 128), (400, 192), (400, 256), (256, 256), (256, 384), (256, 512), (100, 512), (100, 768), (100, 1024)]
+ATT_EDGE = [(256, 320), (100, 576), (77, 128), (130, 384)]
+ATT_MATRIX = [pytest.param(n, c, True, id=f"N{n}-C{c}") for n, c in ATT_PROD] + [pytest.param(n, c, False, id=f"N{n}-C{c}") for n, c in ATT_EDGE]
+ATT_BATCHES = (1, 3, 4, 32)                        # 2B % 8 == 0 (4, 32): the XCD-remapped one-dimensional grid; 32 for the production pairs only
+
+
+def _att_batches(prod):
+    return ATT_BATCHES if prod else ATT_BATCHES[:-1]
+
+
+def _att_splits(N):
+    """forced attn_qsplit settings: 0 = the library's choice, 1, 2, one split per query tile, and beyond that (clamped to nqt)"""
+    nqt = (N + 31) // 32
+    return (0, 1, 2, nqt, nqt + 5)
+
+
+@pytest.mark.parametrize("dt", DTYPES)
+@pytest.mark.parametrize("N,C,prod", ATT_MATRIX)
+def test_cross_attention_launch_matrix(N, C, prod, dt):
+    """icaf_cross_attention over the launch choices the production shapes make (batches 16 - 64: one or two query splits, XCD remap on)
+    and the ones small batches make (many splits, no remap), every split count forced through the probe knob:
+      - every run is within the fp32 softmax reference's tolerance (as test_cross_attention);
+      - every split count gives the SAME BITS: each 32-query tile is computed by one wave from the same K / V^T in LDS, same key order;
+      - the remapped grid gives the SAME BITS as the plain grid on the same images (batch 4 / 32 against batch 1 / 3)."""
+    heads, dk = 8, C // 8
+    bs = _att_batches(prod)
+    qkv = rnd((2, max(bs) * N, 3 * C), 4000 + N + C, 1.0)
+    qkv[:, :, :2 * C] *= 1.5                      # sharpen the softmax a little
+    ref = _attn_ref(q(qkv, dt), max(bs), N, C, heads)
+    nqt = (N + 31) // 32
+    outs = {}
+    for B in bs:
+        qg = qkv[:, :B * N].contiguous().to(DEV).to(dt)
+        runs = []
+        for forced in _att_splits(N):
+            with lib_option("attn_qsplit", forced):
+                dkp, qsplit, remap = ops.cross_attention_config(dt, B, N, C, heads)
+                out = torch.full((2, B * N, C), float("nan"), dtype=dt, device=DEV)
+                run(ops.cross_attention(qg, out, B, N, heads))
+            assert dkp == next(p for p in (16, 32, 48, 64, 96, 128) if p >= dk) and remap == int((2 * B) % 8 == 0)
+            assert 1 <= qsplit <= nqt and (forced == 0 or qsplit == min(forced, nqt)), (forced, qsplit)
+            got = out.float().cpu()
+            close(got, ref[:, :B * N], dt, f"attention N={N} C={C} B={B} qsplit={qsplit} remap={remap}", factor=2)
+            runs.append((qsplit, got))
+        for qs, got in runs[1:]:
+            assert torch.equal(got, runs[0][1]), f"B={B}: {qs} query splits differ from {runs[0][0]}"
+        outs[B] = runs[0][1]
+    for i, Ba in enumerate(bs):                   # the same image gives the same bits at every batch, remapped grid or not
+        for Bb in bs[i + 1:]:
+            assert torch.equal(outs[Bb][:, :Ba * N], outs[Ba]), f"batch {Bb} differs from batch {Ba} on the same images"
+
+
+def test_cross_attention_launch_matrix_covers_every_cell():
+    """The case list of test_cross_attention_launch_matrix must reach every (padded head dimension, XCD remap, one / several query
+    splits) cell of the kernel — read back through icaf_cross_attention_config, so a later change to the list or the heuristic that
+    leaves a cell unreached fails here."""
+    cells = set()
+    for p in ATT_MATRIX:
+        N, C, prod = p.values
+        for dt in DTYPES:
+            for B in _att_batches(prod):
+                for forced in _att_splits(N):
+                    with lib_option("attn_qsplit", forced):
+                        dkp, qsplit, remap = ops.cross_attention_config(dt, B, N, C, 8)
+                    cells.add((dkp, remap, qsplit > 1))
+    want = {(d, r, s) for d in (16, 32, 48, 64, 96, 128) for r in (0, 1) for s in (False, True)}
+    assert want <= cells, sorted(want - cells)
+    # the production corner: benchmarked batches run one or two splits with the remap on
+    with lib_option("attn_qsplit", 0):
+        assert ops.cross_attention_config(torch.bfloat16, 32, 400, 128, 8) == (16, 2, 1)
+        assert ops.cross_attention_config(torch.bfloat16, 32, 100, 1024, 8) == (128, 1, 1)
+
+
 def test_cross_attention_softmax_spike():
     """Force the online-softmax rescale branch: one key dominates late in the key order."""
     B, N, C, heads = 1, 256, 128, 8
@@ -1110,17 +1264,19 @@ def test_cross_attention_softmax_spike():
 
 
 @pytest.mark.parametrize("dt", [torch.bfloat16, torch.float16])
-@pytest.mark.parametrize("C", [128, 256, 384, 512])
+@pytest.mark.parametrize("C", [128, 256, 384, 512, 768, 1024])
 def test_cross_attention_late_spikes_in_16_bit(C, dt):
     """The 16-bit attention loop (attn_core.h) defers the running maximum until a tile exceeds it by 2^6 in the exponent domain, takes the
     softmax denominator out of the matrix pipe (d_k = 16 / 48: a ones row of V^T; d_k = 32: an extra MFMA) and rescales O — and with it
     the denominator — on the cold path.  Keys that dominate LATE in the key order, by less and by much more than the deferral slack,
-    in the last (partly padded) key tile as well, exercise every one of those paths (d_k = 16, 32, 48, 64)."""
-    B, N, heads = 2, 300, 8
+    in the last (partly padded) key tile as well, exercise every one of those paths (d_k = 16, 32, 48, 64, 96, 128)."""
+    B, heads = 2, 8
+    N = 300 if C <= 768 else 100                  # d_k = 128: 300 keys need more LDS than a workgroup has; yolov5l's P5 level has 100 tokens
+    spikes = ((40, 1.2), (131, 3.0), (222, 7.0), (297, 12.0)) if N == 300 else ((13, 1.2), (44, 3.0), (74, 7.0), (99, 12.0))
     dk = C // heads
     qkv = rnd((2, B * N, 3 * C), 47, 0.4)
     qkv[:, :, :C] = qkv[:, :, :C].abs() + 0.3                     # positive queries: a large positive key raises every score of its column
-    for key, amp in ((40, 1.2), (131, 3.0), (222, 7.0), (297, 12.0)):   # growing spikes: below the slack, around it, far above it
+    for key, amp in spikes:                                        # growing spikes: below the slack, around it, far above it
         qkv[0, key, C:2 * C] = amp
         qkv[1, N + key, C:2 * C] = amp * 0.9
     qg = qkv.to(DEV).to(dt).contiguous()
@@ -1133,29 +1289,29 @@ def test_cross_attention_late_spikes_in_16_bit(C, dt):
         close(out[d].float().cpu(), ref, dt, f"late spikes dir {d} C={C}", factor=2)
 
 
-@pytest.mark.parametrize("path", ["pixel", "element"])
-@pytest.mark.parametrize("nc", [1, 3, 9])
-def test_detect_decode(nc, path, monkeypatch):
-    """Both kernels behind icaf_detect_decode: one thread per pixel (3 anchors, no = 6 / 8 / 14) and the general one thread per element."""
-    if path == "element":
-        monkeypatch.setenv("ICAF_DETECT_ELEMENTWISE", "1")
-    B, na, no = 2, 3, nc + 5
-    anchors = [[10, 13, 16, 30, 33, 23], [30, 61, 62, 45, 59, 119], [116, 90, 156, 198, 373, 326]]
-    dims = [(12, 20), (6, 10), (3, 5)]
+ANCHORS3 = [[10, 13, 16, 30, 33, 23], [30, 61, 62, 45, 59, 119], [116, 90, 156, 198, 373, 326]]
+
+
+def _detect_levels(B, na, nc, anchors, dims, seed=50, pads=(0, 2, 2), z_shift=0):
+    """icaf_detect_decode on three levels against the oracle's Detect (identity 1x1 conv, so it sees the same maps); returns the
+    kernel icaf_detect_decode_kernel reports per level.  pads: extra floats per pixel of each level's map (ldp = na * no + pad);
+    z_shift: z starts that many floats into its allocation (4-byte aligned only when odd)."""
+    no = nc + 5
     rows = sum(na * h * w for h, w in dims)
-    z = torch.zeros((B, rows, no), dtype=torch.float32, device=DEV)
+    zbuf = torch.zeros(B * rows * no + z_shift, dtype=torch.float32, device=DEV)
+    z = zbuf[z_shift:].view(B, rows, no)
     lg = torch.zeros((B, rows, nc), dtype=torch.float32, device=DEV)
-    feats, raws, off = [], [], 0
+    feats, raws, kernels, off = [], [], [], 0
     for l, (h, w) in enumerate(dims):
-        p = rnd((B, na * no, h, w), 50 + l, 2.0)
+        p = rnd((B, na * no, h, w), seed + l, 2.0)
         feats.append(p)
-        pa = torch.zeros((B, h, w, na * no + (2 if l else 0)), dtype=torch.float32, device=DEV)     # dense (as the plan allocates it) / padded pixel stride
+        pa = torch.zeros((B, h, w, na * no + pads[l]), dtype=torch.float32, device=DEV)
         pa[..., :na * no] = p.permute(0, 2, 3, 1).to(DEV)
         raw = torch.zeros((B, na, h, w, no), dtype=torch.float32, device=DEV)
+        kernels.append(ops.detect_decode_kernel(pa[..., :na * no], z, raw, na, no))
         run(ops.detect_decode(pa[..., :na * no], z, lg, raw, na, no, off, oracle.STRIDES[l], anchors[l]))
         raws.append(raw)
         off += na * h * w
-    # oracle: identity "conv" weights so detect() sees the same maps
     sd = {}
     for l in range(3):
         sd[f"d.m.{l}.weight"] = torch.eye(na * no).reshape(na * no, na * no, 1, 1)
@@ -1165,6 +1321,42 @@ def test_detect_decode(nc, path, monkeypatch):
     assert torch.equal(lg.cpu(), rl)
     for a, b in zip(raws, rr):
         assert torch.equal(a.cpu(), b)
+    return kernels
+
+
+@pytest.mark.parametrize("path", ["pixel", "element"])
+@pytest.mark.parametrize("nc", [1, 3, 9])
+def test_detect_decode(nc, path):
+    """Both kernels behind icaf_detect_decode: one thread per pixel (3 anchors, no = 6 / 8 / 14) and the general one thread per element,
+    forced here through the library's probe knob (the query confirms which one ran)."""
+    knob = lib_option("detect_elementwise", 1) if path == "element" else contextlib.nullcontext()
+    with knob:
+        kernels = _detect_levels(2, 3, nc, ANCHORS3, [(12, 20), (6, 10), (3, 5)])       # dense (as the plan allocates it) / padded pixel stride
+    assert kernels == [1 if path == "element" else 0] * 3
+
+
+DETECT_FALLBACK_CASES = [
+    # B, na, nc, dims, pads, z_shift: each reaches the per-element kernel without the knob
+    pytest.param(2, 3, 2, [(12, 20), (6, 10), (3, 5)], (0, 0, 3), 0, id="no7"),                 # odd no, odd ldp (21)
+    pytest.param(2, 3, 7, [(16, 20), (8, 10), (4, 5)], (0, 4, 1), 0, id="no12-seadrone"),       # yolov5m SeaDrone: nc = 7
+    pytest.param(1, 3, 80, [(8, 12), (4, 6), (2, 3)], (0, 1, 2), 0, id="no85-coco"),            # 80 classes
+    pytest.param(3, 1, 1, [(10, 14), (5, 7), (3, 4)], (0, 2, 1), 0, id="na1-no6"),
+    pytest.param(2, 2, 3, [(9, 13), (5, 7), (3, 4)], (0, 2, 0), 0, id="na2-no8"),
+    pytest.param(2, 4, 9, [(8, 10), (4, 5), (2, 3)], (0, 2, 4), 0, id="na4-no14"),
+    pytest.param(2, 3, 3, [(12, 20), (6, 10), (3, 5)], (1, 3, 5), 0, id="no8-odd-ldp"),         # per-pixel head, but odd pixel strides
+    pytest.param(2, 3, 1, [(12, 20), (6, 10), (3, 5)], (0, 2, 0), 1, id="no6-z-4byte"),         # per-pixel head, but z only 4-byte aligned
+]
+
+
+@pytest.mark.parametrize("B,na,nc,dims,pads,z_shift", DETECT_FALLBACK_CASES)
+def test_detect_decode_per_element_fallback(B, na, nc, dims, pads, z_shift):
+    """The per-element decode kernel is the production path of every head the per-pixel kernels do not take (na != 3, no not in
+    {6, 8, 14}, a pixel stride or output row that is not 8-byte aligned): no knob, same oracle, same tolerances."""
+    if na == 3:
+        anchors = ANCHORS3
+    else:                                          # ad hoc anchors, distinct w / h per anchor (a swapped pair shows)
+        anchors = [[float(8 * (l + 1) * (a + 1) + 3 * k + 1) for a in range(na) for k in range(2)] for l in range(3)]
+    assert _detect_levels(B, na, nc, anchors, dims, seed=150 + 7 * na + nc, pads=pads, z_shift=z_shift) == [1, 1, 1]
 
 
 @pytest.mark.parametrize("dt", [torch.bfloat16, torch.float16])

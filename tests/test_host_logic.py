@@ -1,5 +1,7 @@
 """CPU-only checks of the host side: config surface, module tree / state_dict layout, C-ABI export table, error paths."""
+import ast
 import ctypes
+import dataclasses
 import os
 import re
 
@@ -352,3 +354,86 @@ def test_plan_options_are_one_object_filled_from_one_variable():
             if f.endswith((".py", ".hip", ".h")) and f not in ("options.py", "build.py", "_lib.py"):
                 text = open(os.path.join(root, f)).read()
                 assert not re.search(r"environ[^\n]*ICAF_|getenv\(\"ICAF_(?!S2_CLK)", text), f
+
+
+def _switch_names():
+    from icafusion_amd.options import PlanOptions
+    return {"ICAF_OPTIONS"} | {f.metadata["env"] for f in dataclasses.fields(PlanOptions)}
+
+
+def _is_os_environ(node):
+    return (isinstance(node, ast.Attribute) and node.attr == "environ" and isinstance(node.value, ast.Name) and node.value.id == "os") or \
+        (isinstance(node, ast.Name) and node.id == "environ")
+
+
+def dead_switch_writes(path, text, names):
+    """`path:line` of every in-process write of a PlanOptions switch (or ICAF_OPTIONS) in one Python source: setenv / putenv,
+    os.environ[...] = / |=, os.environ.update / setdefault.  options.py reads them ONCE, at import, and the library's probe knobs are
+    pushed into libicaf.so when it loads — a later write in the same process silently runs the default.  An environment built for a
+    child process (dict(os.environ, ...), env = {...}; env[...] = ...) is not flagged."""
+    def key(node):
+        return node.value if isinstance(node, ast.Constant) and isinstance(node.value, str) else None
+
+    hits = []
+    for node in ast.walk(ast.parse(text, filename=path)):
+        keys = []
+        if isinstance(node, ast.Call) and isinstance(node.func, ast.Attribute):
+            attr = node.func.attr
+            if attr in ("setenv", "putenv") and node.args:                         # monkeypatch.setenv / os.putenv
+                keys = [key(node.args[0])]
+            elif attr in ("update", "setdefault") and _is_os_environ(node.func.value):
+                keys = [kw.arg for kw in node.keywords]
+                for a in node.args[:1 if attr == "setdefault" else len(node.args)]:
+                    keys += [key(k) for k in a.keys] if isinstance(a, ast.Dict) else [key(a)]
+        elif isinstance(node, (ast.Assign, ast.AugAssign)):
+            for t in (node.targets if isinstance(node, ast.Assign) else [node.target]):
+                if isinstance(t, ast.Subscript) and _is_os_environ(t.value):
+                    keys.append(key(t.slice))
+        hits += [(node.lineno, k) for k in keys if k in names]
+    return [f"{path}:{line}: {k}" for line, k in sorted(hits)]
+
+
+def test_no_test_or_probe_writes_a_dead_switch():
+    """A test or probe that writes a switch into its own environment after import changes nothing — that is how the per-element Detect
+    decode kernel went untested for a whole round (test_detect_decode set ICAF_DETECT_ELEMENTWISE; lab/probes/sppf_vpb.py set
+    ICAF_SPPF_VPB).  Library knobs go through tests/helpers.py::lib_option; plan switches through a child process's environment.
+    The switch names come from PlanOptions, so a switch added later is covered without touching this test."""
+    names = _switch_names()
+    hits = []
+    for top in ("tests", os.path.join("lab", "probes")):
+        for root, _, files in os.walk(os.path.join(REPO, top)):
+            for f in sorted(files):
+                if f.endswith(".py"):
+                    path = os.path.join(root, f)
+                    hits += dead_switch_writes(os.path.relpath(path, REPO), open(path).read(), names)
+    assert not hits, "in-process writes of ICAF switches (read once, at import):\n" + "\n".join(hits)
+
+
+def test_dead_switch_guard_flags_every_form_of_write():
+    """The guard itself: the two writes it was written for, every other in-process form, and what it must let through."""
+    names = _switch_names()
+    assert {"ICAF_OPTIONS", "ICAF_DETECT_ELEMENTWISE", "ICAF_SPPF_VPB", "ICAF_ATTN_QSPLIT", "ICAF_DMFF_FUSE"} <= names
+    bad = '''import os
+def test_detect_decode(nc, path, monkeypatch):
+    if path == "element":
+        monkeypatch.setenv("ICAF_DETECT_ELEMENTWISE", "1")
+for cap in (8, 4, 2, 1):
+        os.environ["ICAF_SPPF_VPB"] = str(cap)
+os.environ.update(ICAF_DMFF_FUSE="0")
+os.environ.update({"ICAF_OPTIONS": "attn_qsplit=1"})
+os.environ.setdefault("ICAF_ATTN_QSPLIT", "2")
+os.putenv("ICAF_CWIDE", "0")
+os.environ["ICAF_OPTIONS"] += ",dmff_wide=0"
+'''
+    hits = dead_switch_writes("x.py", bad, names)
+    assert hits == ["x.py:4: ICAF_DETECT_ELEMENTWISE", "x.py:6: ICAF_SPPF_VPB", "x.py:7: ICAF_DMFF_FUSE", "x.py:8: ICAF_OPTIONS",
+                    "x.py:9: ICAF_ATTN_QSPLIT", "x.py:10: ICAF_CWIDE", "x.py:11: ICAF_OPTIONS"], hits
+    ok = '''import os, subprocess, sys
+env = dict(os.environ, ICAF_DMFF_FUSE="0")
+env["ICAF_OPTIONS"] = "attn_qsplit=1"
+subprocess.run([sys.executable, "-c", "pass"], env={**os.environ, "ICAF_SPPF_VPB": "2"})
+os.environ["MASTER_PORT"] = "29500"
+os.environ.update(RANK="0")
+x = os.environ.get("ICAF_LIB")
+'''
+    assert dead_switch_writes("ok.py", ok, names) == []

@@ -28,6 +28,18 @@ def test_plan_builds_on_cpu(cfg_name, dtype):
         assert not any(x.startswith("stem") or x.startswith("bottleneck") or x.endswith("+1x1") for x in n)
 
 
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16, torch.float32])
+def test_seadrone_plan_decodes_each_level_with_its_own_launch(dtype):
+    """yolov5m SeaDrone (nc = 7, no = 12): icaf_detect_conv is built for no in {6, 8, 14}, so even the 16-bit plan must end in three
+    (1x1 conv, decode) pairs — icaf_conv2d into an fp32 map, then icaf_detect_decode (its per-element kernel) — never the one-launch level."""
+    m = Model(load_cfg("yolov5m_Transfusion_SeaDrone.yaml")).eval()
+    assert m.model[-1].no == 12
+    n = names(m.build_plan(2, 320, 352, "cpu", dtype))
+    assert "detect_conv+decode" not in n
+    assert n.count("detect_decode") == 3 and n.count("detect_conv") == 3
+    assert n[-6:] == ["detect_conv", "detect_decode"] * 3
+
+
 def test_yolov5s_plan_level_fusions_and_their_switches():
     m = Model(load_cfg("yolov5s_Transfusion_kaist.yaml")).eval()
     base = names(m.build_plan(2, 320, 320, "cpu", torch.bfloat16))
