@@ -9,6 +9,7 @@ classes still duck-type as nn.Modules taking/returning NCHW-shaped tensors.
 There is deliberately no PyTorch / CPU fallback: calling a module with CPU tensors, in training mode, or without
 libicaf.so raises.
 """
+import functools
 import math
 
 import torch
@@ -144,6 +145,29 @@ class Conv(HipModule):
             b = (b - bn.running_mean.detach().float()) * scale + bn.bias.detach().float()
         return w, b
 
+    def packed(self, plan, twin=None, also=(), twin_also=(), swap_halves=False, cin_slice=None, transform=None, cin_pad=None):
+        """-> (wp, kp, bp), the launch form of this layer's weights: BN folded, `also` appended along Cout, the K halves swapped /
+        the K columns cin_slice kept, `transform` (ops.s2d_conv_weight) applied, Cin padded to cin_pad, cast to plan.dtype; with
+        `twin` the two streams stacked.  Cached on self under a key derived from exactly these arguments: whoever asks for the same
+        packing gets the same tensor, and nobody spells a key."""
+        assert len(twin_also) == (len(also) if twin is not None else 0)
+        key = ("pack", plan.dtype, plan.device, id(twin), tuple(map(id, also)), tuple(map(id, twin_also)), bool(swap_halves),
+               None if cin_slice is None else tuple(cin_slice), transform, cin_pad)
+
+        def make():
+            rows = []
+            for convs in [(self,) + tuple(also)] + ([(twin,) + tuple(twin_also)] if twin is not None else []):
+                ws, bs = zip(*(c.folded() for c in convs))
+                w, b = torch.cat(ws), torch.cat(bs)
+                if swap_halves:
+                    h = w.shape[1] // 2
+                    w = torch.cat((w[:, h:], w[:, :h]), 1)
+                if cin_slice is not None:
+                    w = w[:, cin_slice[0]:cin_slice[1]]
+                rows.append((w if transform is None else transform(w), b))
+            return ops.pack_streams(rows, plan.dtype, cin_pad)
+        return self._cached(key, make)
+
     def emit(self, plan, x, out=None, res=None, twin=None, also=(), twin_also=(), pre_term=None, swap_halves=False,
              chain=None, pre_nearest=False, cin_slice=None):
         """Append this layer's launch.
@@ -178,35 +202,7 @@ class Conv(HipModule):
                    ((kh, kw), (sh, sw), (ph, pw), c1, self._act_code()), "fused convs must share geometry"
         vec = ops.VEC[plan.dtype]
         paired = twin is not None
-        assert len(twin_also) == (len(also) if paired else 0)
-
-        def streams():
-            """[(Conv, ...)] per stream: the convs whose folded weights are concatenated along Cout."""
-            rows = [(self,) + tuple(also)]
-            if paired:
-                rows.append((twin,) + tuple(twin_also))
-            return rows
-        key_tail = (plan.dtype, plan.device, id(twin), tuple(id(e) for e in also), bool(swap_halves))
-        if cin_slice is not None:
-            key_tail += (tuple(cin_slice),)
-
-        def pack(transform, cin_pad):
-            packs = []
-            for convs in streams():
-                ws, bs = zip(*(c.folded() for c in convs))
-                w, b = torch.cat(ws), torch.cat(bs)
-                if swap_halves:
-                    h = w.shape[1] // 2
-                    w = torch.cat((w[:, h:], w[:, :h]), 1)
-                if cin_slice is not None:
-                    w = w[:, cin_slice[0]:cin_slice[1]]
-                wp, kp = ops.pack_conv_weight(transform(w), plan.dtype, cin_pad)
-                packs.append((wp, kp, ops.pack_bias(b, c2)))
-            if not paired:
-                return packs[0]
-            return (torch.stack([p[0] for p in packs]).contiguous(), packs[0][1],
-                    torch.stack([p[2] for p in packs]).contiguous())
-
+        packed = functools.partial(self.packed, plan, twin, also, twin_also, swap_halves, cin_slice)
         if isinstance(x, ImageIn):
             assert x.pair == paired
             B, _, H, W = x.shape
@@ -214,7 +210,7 @@ class Conv(HipModule):
             if (s2d and self.fuse_stem and plan.dtype in (torch.bfloat16, torch.float16) and c1 == 3 and c2 in (32, 64)
                     and not also and res is None and (not x.u8 or (paired and x.c0 == 0))):
                 # staging + convolution in one persistent kernel reading the NCHW image itself (stem.hip)
-                wp, kp, bp = self._cached(("s2d",) + key_tail, lambda: pack(ops.s2d_conv_weight, 16))
+                wp, kp, bp = packed(transform=ops.s2d_conv_weight, cin_pad=16)
                 if out is None:
                     out = plan.act(B, H // 2, W // 2, c2, pair=paired)
                 plan.add(ops.stem(x.t, wp, kp, bp, out, c2))
@@ -224,14 +220,14 @@ class Conv(HipModule):
                 pre = plan.act(B, H // 2, W // 2, cpad, pair=paired)
                 plan.add(ops.preprocess_u8(x.t, pre, 1, x.c0, name="preprocess_u8_s2d") if x.u8
                          else ops.preprocess(x.t, pre, 1, name="preprocess_s2d"))
-                wp, kp, bp = self._cached(("s2d",) + key_tail, lambda: pack(ops.s2d_conv_weight, cpad))
+                wp, kp, bp = packed(transform=ops.s2d_conv_weight, cin_pad=cpad)
                 x, c1, (kh, kw, sh, sw, ph, pw) = pre, cpad, (3, 3, 1, 1, 1, 1)
             else:
                 cpad = -(-c1 // vec) * vec
                 pre = plan.act(B, H, W, cpad, pair=paired)
                 plan.add(ops.preprocess_u8(x.t, pre, 0, x.c0, name="preprocess_u8_pad") if x.u8
                          else ops.preprocess(x.t, pre, 0, name="preprocess_pad"))
-                wp, kp, bp = self._cached(("pad",) + key_tail, lambda: pack(lambda w: w, cpad))
+                wp, kp, bp = packed(cin_pad=cpad)
                 x, c1 = pre, cpad
         else:
             assert (x.dim() == 5) == paired
@@ -241,7 +237,7 @@ class Conv(HipModule):
                 raise ValueError(f"Conv expects {c1} input channels, got {x.shape[-1]}")
             if c1 % vec:
                 raise NotImplementedError(f"channel count {c1} must be a multiple of {vec} for dtype {plan.dtype}")
-            wp, kp, bp = self._cached(("std",) + key_tail, lambda: pack(lambda w: w, None))
+            wp, kp, bp = packed()
         B, H, W = x.shape[-4:-1]
         Ho, Wo = (H + 2 * ph - kh) // sh + 1, (W + 2 * pw - kw) // sw + 1
         if out is None:
@@ -252,17 +248,7 @@ class Conv(HipModule):
             keep = len(chain) > 3 and bool(chain[3])
             x2 = chain[4] if len(chain) > 4 else None
             n2 = sum(c.conv.out_channels for c in convs)
-
-            def pack2():
-                packs = []
-                for row in ([convs] + ([twin_convs] if paired else [])):
-                    ws, bs = zip(*(c.folded() for c in row))
-                    w2p, kp2 = ops.pack_conv_weight(torch.cat(ws), plan.dtype)
-                    packs.append((w2p, kp2, ops.pack_bias(torch.cat(bs), n2)))
-                if not paired:
-                    return packs[0]
-                return (torch.stack([p[0] for p in packs]).contiguous(), packs[0][1], torch.stack([p[2] for p in packs]).contiguous())
-            w2p, kp2, b2p = self._cached(("chain",) + key_tail + tuple(id(c) for c in convs), pack2)
+            w2p, kp2, b2p = convs[0].packed(plan, twin_convs[0] if paired else None, convs[1:], twin_convs[1:] if paired else ())
             ch = dict(w=w2p, kp=kp2, bias=b2p, y=y2, cout=n2, keep=keep)
             if x2 is not None:
                 ch["x2"] = x2
@@ -290,24 +276,9 @@ class Conv(HipModule):
 
     def emit_stem2(self, plan, x, twin, nxt, nxt_twin, convs, twin_convs, y2):
         """Rows 0-2a of both streams as one launch; y2 = the pair act the C3's cv1 | cv2 write."""
-        key_tail = (plan.dtype, plan.device, id(twin))
-
-        def stack(packs):
-            return (torch.stack([p[0] for p in packs]).contiguous(), packs[0][1], torch.stack([p[2] for p in packs]).contiguous())
-
-        def pack_row(rows, transform, cin_pad):
-            packs = []
-            for convs_ in rows:
-                ws, bs = zip(*(c.folded() for c in convs_))
-                w, b = torch.cat(ws), torch.cat(bs)
-                wp, kp = ops.pack_conv_weight(transform(w), plan.dtype, cin_pad)
-                packs.append((wp, kp, ops.pack_bias(b, w.shape[0])))
-            return stack(packs)
-        w0, kp0, b0 = self._cached(("s2d",) + key_tail + ((), False), lambda: pack_row([(self,), (twin,)], ops.s2d_conv_weight, 16))
-        w1, kp1, b1 = nxt._cached(("std",) + (plan.dtype, plan.device, id(nxt_twin), (), False),
-                                  lambda: pack_row([(nxt,), (nxt_twin,)], lambda w: w, None))
-        w2, kp2, b2 = nxt._cached(("chain",) + (plan.dtype, plan.device, id(nxt_twin), (), False) + tuple(id(c) for c in convs),
-                                  lambda: pack_row([convs, twin_convs], lambda w: w, None))
+        w0, kp0, b0 = self.packed(plan, twin, transform=ops.s2d_conv_weight, cin_pad=16)
+        w1, kp1, b1 = nxt.packed(plan, nxt_twin)
+        w2, kp2, b2 = convs[0].packed(plan, twin_convs[0], convs[1:], twin_convs[1:])
         n2 = sum(c.conv.out_channels for c in convs)
         plan.add(ops.stem2(x.t, w0, kp0, b0, w1, kp1, b1, w2, kp2, b2, y2, self.conv.out_channels, nxt.conv.out_channels, n2))
         return y2
@@ -386,32 +357,13 @@ class Bottleneck(HipModule):
         output; the Bottleneck's own output is then never written (`out` is ignored)."""
         c = self.cv1.conv.in_channels
         paired = twin is not None
-        mods = [self] + ([twin] if paired else [])
         tail = None
         if cv3 is not None:
             k3, k3t, x2, y3 = cv3
-
-            def pack3():          # K columns in the order [cv2 | m]: exactly Conv.emit(swap_halves=True)'s packing (shared cache key)
-                packs = []
-                for cv in [k3] + ([k3t] if paired else []):
-                    w, b = cv.folded()
-                    h = w.shape[1] // 2
-                    wp, kp = ops.pack_conv_weight(torch.cat((w[:, h:], w[:, :h]), 1), plan.dtype)
-                    packs.append((wp, kp, ops.pack_bias(b, w.shape[0])))
-                if not paired:
-                    return packs[0]
-                return (torch.stack([p[0] for p in packs]).contiguous(), packs[0][1], torch.stack([p[2] for p in packs]).contiguous())
-            w3, kp3, b3 = k3._cached(("std", plan.dtype, plan.device, id(k3t), (), True), pack3)
+            w3, kp3, b3 = k3.packed(plan, k3t, swap_halves=True)          # K columns in the order [cv2 | m]
             tail = dict(w=w3, kp=kp3, bias=b3, y=y3, cout=k3.conv.out_channels, x2=x2)
-
-        def make():
-            p1 = [ops.pack_conv_weight(m.cv1.folded()[0], plan.dtype) for m in mods]
-            p2 = [ops.pack_conv_weight(m.cv2.folded()[0], plan.dtype) for m in mods]
-            b1 = [ops.pack_bias(m.cv1.folded()[1], c) for m in mods]
-            b2 = [ops.pack_bias(m.cv2.folded()[1], c) for m in mods]
-            st = (lambda ts: torch.stack(ts).contiguous()) if paired else (lambda ts: ts[0])
-            return st([p[0] for p in p1]), p1[0][1], st(b1), st([p[0] for p in p2]), p2[0][1], st(b2)
-        w1, kp1, b1, w2, kp2, b2 = self._cached(("bneck", plan.dtype, plan.device, id(twin)), make)
+        w1, kp1, b1 = self.cv1.packed(plan, twin.cv1 if paired else None)
+        w2, kp2, b2 = self.cv2.packed(plan, twin.cv2 if paired else None)
         plan.add(ops.bottleneck(x, w1, kp1, b1, w2, kp2, b2, None if tail else out, c, self.add, 1 if c == 32 else 2, cv3=tail))
         return tail["y"] if tail else out
 
@@ -470,11 +422,7 @@ class C3(HipModule):
             # a-half of cv1 | cv2 runs at LOW resolution (fp32 out, a quarter of the pixels) and enters the GEMM over b as its
             # nearest-resized pre-activation term; nn.Upsample's output and the Concat buffer are never written or read.
             ca, cb = vcat.low.shape[-1], vcat.other.shape[-1]
-
-            def make_a():
-                w = torch.cat([self.cv1.folded()[0], self.cv2.folded()[0]])[:, :ca]
-                return ops.pack_conv_weight(w, plan.dtype)
-            wa, kpa = self._cached(("upterm", plan.dtype, plan.device, ca), make_a)
+            wa, kpa, _ = self.cv1.packed(plan, also=(self.cv2,), cin_slice=(0, ca))           # (the bias stays in the GEMM over b)
             Bl, hl, wl, _ = vcat.low.shape
             P = plan.empty((Bl, hl, wl, 2 * c_), torch.float32)
             plan.add(ops.conv2d(vcat.low, wa, kpa, None, P, 1, 1, 1, 1, 0, 0, ca, 2 * c_, ops.ACT_NONE, name="c3_up_term"))
@@ -597,6 +545,7 @@ class NiNfusion(HipModule):
 
     # the packed-weight / launch logic is Conv's (a Conv without .bn and without bias)
     folded = Conv.folded
+    packed = Conv.packed
     _act_code = Conv._act_code
     fuse_stem = False
 
@@ -710,21 +659,12 @@ class CrossTransformerBlock(HipModule):
             ca = self.crossatt
             dt, f = plan.dtype, (lambda t: t.detach().float())
 
-            def stack(ws, bs):
-                packs = [ops.pack_matrix(w, dt) for w in ws]
-                wp = torch.stack([p[0] for p in packs]).contiguous()
-                bp = torch.stack([ops.pack_bias(b, b.numel()) for b in bs]).contiguous()
-                return wp, packs[0][1], bp
-            qkv = stack([torch.cat([f(getattr(ca, f"{n}_proj_{m}").weight) for n in ("que", "key", "val")])
-                         for m in ("vis", "ir")],
-                        [torch.cat([f(getattr(ca, f"{n}_proj_{m}").bias) for n in ("que", "key", "val")])
-                         for m in ("vis", "ir")])
-            outp = stack([f(ca.out_proj_vis.weight), f(ca.out_proj_ir.weight)],
-                         [f(ca.out_proj_vis.bias), f(ca.out_proj_ir.bias)])
-            fc1 = stack([f(self.mlp_vis[0].weight), f(self.mlp_ir[0].weight)],
-                        [f(self.mlp_vis[0].bias), f(self.mlp_ir[0].bias)])
-            fc2 = stack([f(self.mlp_vis[2].weight), f(self.mlp_ir[2].weight)],
-                        [f(self.mlp_vis[2].bias), f(self.mlp_ir[2].bias)])
+            def lin(vis, ir):          # one nn.Linear (or several, concatenated along the outputs) per modality
+                return ops.pack_streams([(torch.cat([f(l.weight) for l in ls]), torch.cat([f(l.bias) for l in ls])) for ls in (vis, ir)], dt)
+            qkv = lin(*([getattr(ca, f"{n}_proj_{m}") for n in ("que", "key", "val")] for m in ("vis", "ir")))
+            outp = lin([ca.out_proj_vis], [ca.out_proj_ir])
+            fc1 = lin([self.mlp_vis[0]], [self.mlp_ir[0]])
+            fc2 = lin([self.mlp_vis[2]], [self.mlp_ir[2]])
             ln = {k: f(v).contiguous() for k, v in (("a1w", ca.LN1.weight), ("a1b", ca.LN1.bias),
                                                     ("a2w", ca.LN2.weight), ("a2b", ca.LN2.bias),
                                                     ("mw", self.LN2.weight), ("mb", self.LN2.bias))}
@@ -921,12 +861,7 @@ class TransformerFusionBlock(HipModule):
         for j, blk in enumerate(blocks):
             tok = blk.emit_tokens(plan, tok, B, N, final_out=final if j == len(blocks) - 1 else None)
         conv = self.conv1x1_out
-
-        def make():
-            w, _ = conv.folded()                                              # BN scale folded in; bias stays in the main GEMM
-            wp, kp = ops.pack_conv_weight(w, plan.dtype)
-            return wp, kp
-        wp, kp = self._cached(("tailw", plan.dtype, plan.device), make)
+        wp, kp, _ = conv.packed(plan)                                         # BN scale folded in; bias stays in the main GEMM
         P = plan.empty((B, th, tw, C), torch.float32)
         plan.add(ops.conv2d(tokcat.view(B * N, 1, 1, 2 * C), wp, kp, None, P.view(B * N, 1, 1, C), 1, 1, 1, 1, 0, 0,
                             2 * C, C, ops.ACT_NONE, name="dmff_tail_tokens"))
@@ -978,11 +913,8 @@ class Detect(HipModule):
             _, ny, nx, c = x.shape
             conv = self.m[l]
             nout = self.na * self.no
-
-            def make(conv=conv):
-                wp, kp = ops.pack_conv_weight(conv.weight.detach().float(), plan.dtype)
-                return wp, kp, ops.pack_bias(conv.bias.detach().float(), conv.out_channels)
-            wp, kp, bp = self._cached(("det", l, plan.dtype, plan.device), make)
+            wp, kp, bp = self._cached(("det", l, plan.dtype, plan.device), lambda: ops.pack_streams(
+                [(conv.weight.detach().float(), conv.bias.detach().float())], plan.dtype))
             raw = plan.empty((B, self.na, ny, nx, self.no), torch.float32)
             if self.fuse_decode and ops.detect_conv_ok(x, self.na, self.no, c):
                 # 16-bit maps: conv + decode in ONE launch (icaf_detect_conv) - the fp32 conv map never reaches HBM

@@ -100,6 +100,19 @@ def pack_conv_weight(w4d, dt, cin_pad=None):
     return pack_matrix(w.reshape(co, -1).contiguous(), dt)
 
 
+def pack_streams(rows, dt, cin_pad=None):
+    """rows: one fp32 (weight [Cout][K] or [Cout][Cin][kh][kw], bias [Cout] or None) per stream -> (wp, kp, bp): the plain [Np][Kp] /
+    [Np] packs for one row, the contiguous stacks [2][Np][Kp] / [2][Np] for two (bp is None where the biases are)."""
+    packs = []
+    for w, b in rows:
+        wp, kp = pack_matrix(w, dt) if w.dim() == 2 else pack_conv_weight(w, dt, cin_pad)
+        packs.append((wp, None if b is None else pack_bias(b, w.shape[0])))
+    if len(packs) == 1:
+        return packs[0][0], kp, packs[0][1]
+    wps, bps = zip(*packs)
+    return torch.stack(wps).contiguous(), kp, None if bps[0] is None else torch.stack(bps).contiguous()
+
+
 _FRAG_CACHE = {}              # id(packed tensor) -> (weakref to it, fragment-major copy); entries die with the packed tensor
 # (execution switches — which kernels the tuner may offer a layer, retune requests — live in options.PlanOptions; read as OPT.<field>)
 # (Round 5's persistent long-K GEMM — launch configuration 67, igemm_pers.hip — and the persistent halo-patch 3x3 — 90 + shape, cwpers.hip — were removed

@@ -160,9 +160,7 @@ def test_conv_streaming_kernel(case, dt):
     rs = [rnd((B, cout, Ho, Wo), 57 + g) for g in range(G)] if use_res else None
     stk = (lambda t: torch.stack(t).contiguous()) if G == 2 else (lambda t: t[0])
     xa = stk([to_act(x, dt, pad_to=cin + 16) for x in xs])
-    packs = [ops.pack_conv_weight(w.to(DEV), dt) for w in ws]
-    wp, kp = stk([p0[0] for p0 in packs]), packs[0][1]
-    bp = stk([ops.pack_bias(b.to(DEV), cout) for b in bs])
+    wp, kp, bp = ops.pack_streams([(w.to(DEV), b.to(DEV)) for w, b in zip(ws, bs)], dt)
     ra = stk([to_act(r, dt) for r in rs]) if use_res else None
     ldy = -(-cout // 8) * 8 + 8
     outs = []
@@ -220,18 +218,14 @@ def test_conv3x3_resident_filter_kernel(case, dt):
     rs = [rnd((B, cout, H, W), 77 + g) for g in range(G)] if use_res else None
     stk = (lambda t: torch.stack(t).contiguous()) if G == 2 else (lambda t: t[0])
     xa = stk([to_act(x, dt) for x in xs])
-    packs = [ops.pack_conv_weight(w.to(DEV), dt) for w in ws]
-    wp, kp = stk([p0[0] for p0 in packs]), packs[0][1]
-    bp = stk([ops.pack_bias(b.to(DEV), cout) for b in bs])
+    wp, kp, bp = ops.pack_streams([(w.to(DEV), b.to(DEV)) for w, b in zip(ws, bs)], dt)
     ra = stk([to_act(r, dt) for r in rs]) if use_res else None
     ch = None
     if chain:
         c2, keep = chain
         w2s = [rnd((c2, cout, 1, 1), 81 + g, 1.0 / math.sqrt(cout)) for g in range(G)]
         b2s = [rnd((c2,), 83 + g, 0.2) for g in range(G)]
-        p2 = [ops.pack_conv_weight(w.to(DEV), dt) for w in w2s]
-        w2p, kp2 = stk([p0[0] for p0 in p2]), p2[0][1]
-        b2p = stk([ops.pack_bias(b.to(DEV), c2) for b in b2s])
+        w2p, kp2, b2p = ops.pack_streams([(w.to(DEV), b.to(DEV)) for w, b in zip(w2s, b2s)], dt)
     outs = []
     for tile in (71, 2 if not chain else 22):
         shape = (G, B, H, W) if G == 2 else (B, H, W)
@@ -285,18 +279,14 @@ def test_conv3x3_resident_patch_streamed_weights_kernel(case, dt, shape):
     rs = [rnd((B, cout, H, W), 177 + g) for g in range(G)] if use_res else None
     stk = (lambda t: torch.stack(t).contiguous()) if G == 2 else (lambda t: t[0])
     xa = stk([to_act(x, dt) for x in xs])
-    packs = [ops.pack_conv_weight(w.to(DEV), dt) for w in ws]
-    wp, kp = stk([p0[0] for p0 in packs]), packs[0][1]
-    bp = stk([ops.pack_bias(b.to(DEV), cout) for b in bs])
+    wp, kp, bp = ops.pack_streams([(w.to(DEV), b.to(DEV)) for w, b in zip(ws, bs)], dt)
     ra = stk([to_act(r, dt) for r in rs]) if use_res else None
     ch = None
     if chain:
         c2, keep = chain
         w2s = [rnd((c2, cout, 1, 1), 181 + g, 1.0 / math.sqrt(cout)) for g in range(G)]
         b2s = [rnd((c2,), 183 + g, 0.2) for g in range(G)]
-        p2 = [ops.pack_conv_weight(w.to(DEV), dt) for w in w2s]
-        w2p, kp2 = stk([p0[0] for p0 in p2]), p2[0][1]
-        b2p = stk([ops.pack_bias(b.to(DEV), c2) for b in b2s])
+        w2p, kp2, b2p = ops.pack_streams([(w.to(DEV), b.to(DEV)) for w, b in zip(w2s, b2s)], dt)
     outs = []
     for tile in (shape, 28 if not chain else 21):
         shape = (G, B, H, W) if G == 2 else (B, H, W)
@@ -350,17 +340,13 @@ def test_conv3x3_with_c3_tail_equals_two_launches(case, dt, tile):
     stk = (lambda t: torch.stack(t).contiguous()) if G == 2 else (lambda t: t[0])
     shape = (G, B, H, W) if G == 2 else (B, H, W)
     xa = stk([to_act(x, dt) for x in xs])
-    packs = [ops.pack_conv_weight(w.to(DEV), dt) for w in ws]
-    wp, kp = stk([p0[0] for p0 in packs]), packs[0][1]
-    bp = stk([ops.pack_bias(b.to(DEV), c) for b in bs])
+    wp, kp, bp = ops.pack_streams([(w.to(DEV), b.to(DEV)) for w, b in zip(ws, bs)], dt)
     ra = stk([to_act(r, dt) for r in rs]) if use_res else None
     # the buffer cv3 reads in the two-launch form: [m | x2] (as C3.emit places them); the tail reads its x2 half in place
     cat = torch.full(shape + (2 * c,), 7.0, dtype=dt, device=DEV)
     for g in range(G):
         (cat[g] if G == 2 else cat)[..., c:] = to_act(x2s[g], dt)
-    p3 = [ops.pack_conv_weight(w.to(DEV), dt) for w in w3s]
-    w3p, kp3 = stk([p0[0] for p0 in p3]), p3[0][1]
-    b3p = stk([ops.pack_bias(b.to(DEV), 2 * c) for b in b3s])
+    w3p, kp3, b3p = ops.pack_streams([(w.to(DEV), b.to(DEV)) for w, b in zip(w3s, b3s)], dt)
     assert kp3 == 2 * c
     # one launch
     y_unused = torch.full(shape + (c,), 7.0, dtype=dt, device=DEV)
@@ -421,16 +407,12 @@ def test_conv3x3_stride2_resident_patch_kernel(case, dt):
     bs = [rnd((cout,), 275 + g, 0.2) for g in range(G)]
     stk = (lambda t: torch.stack(t).contiguous()) if G == 2 else (lambda t: t[0])
     xa = stk([to_act(x, dt) for x in xs])
-    packs = [ops.pack_conv_weight(w.to(DEV), dt) for w in ws]
-    wp, kp = stk([p0[0] for p0 in packs]), packs[0][1]
-    bp = stk([ops.pack_bias(b.to(DEV), cout) for b in bs])
+    wp, kp, bp = ops.pack_streams([(w.to(DEV), b.to(DEV)) for w, b in zip(ws, bs)], dt)
     Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
     if c2:
         w2s = [rnd((c2, cout, 1, 1), 281 + g, 1.0 / math.sqrt(cout)) for g in range(G)]
         b2s = [rnd((c2,), 283 + g, 0.2) for g in range(G)]
-        p2 = [ops.pack_conv_weight(w.to(DEV), dt) for w in w2s]
-        w2p, kp2 = stk([p0[0] for p0 in p2]), p2[0][1]
-        b2p = stk([ops.pack_bias(b.to(DEV), c2) for b in b2s])
+        w2p, kp2, b2p = ops.pack_streams([(w.to(DEV), b.to(DEV)) for w, b in zip(w2s, b2s)], dt)
     outs = []
     for tile in (tile_id, 1 if c2 else 28):
         shape = (G, B, Ho, Wo) if G == 2 else (B, Ho, Wo)
@@ -498,9 +480,7 @@ def test_conv_weights_from_registers_kernel(case, dt):
     rs = [rnd((B, cout, Ho, Wo), 67 + g) for g in range(G)] if use_res else None
     stk = (lambda t: torch.stack(t).contiguous()) if G == 2 else (lambda t: t[0])
     xa = stk([to_act(x, dt) for x in xs])
-    packs = [ops.pack_conv_weight(w.to(DEV), dt) for w in ws]
-    wp, kp = stk([p0[0] for p0 in packs]), packs[0][1]
-    bp = stk([ops.pack_bias(b.to(DEV), cout) for b in bs])
+    wp, kp, bp = ops.pack_streams([(w.to(DEV), b.to(DEV)) for w, b in zip(ws, bs)], dt)
     ra = stk([to_act(r, dt) for r in rs]) if use_res else None
     ldy = -(-cout // 8) * 8 + 8
     outs = []
@@ -611,14 +591,12 @@ def test_fused_bottleneck_equals_two_launches(case, dt):
     def stack(ts):
         return torch.stack(ts).contiguous() if paired else ts[0]
     xa = stack([to_act(x, dt) for x in xs])
-    p1 = [ops.pack_conv_weight(w.to(DEV), dt) for w in w1]
-    p2 = [ops.pack_conv_weight(w.to(DEV), dt) for w in w2]
-    w1p, w2p = stack([p[0] for p in p1]), stack([p[0] for p in p2])
-    b1p, b2p = stack([ops.pack_bias(b.to(DEV), c) for b in b1]), stack([ops.pack_bias(b.to(DEV), c) for b in b2])
+    w1p, kp1, b1p = ops.pack_streams([(w.to(DEV), b.to(DEV)) for w, b in zip(w1, b1)], dt)
+    w2p, kp2, b2p = ops.pack_streams([(w.to(DEV), b.to(DEV)) for w, b in zip(w2, b2)], dt)
     y_f, y_u, t = torch.zeros_like(xa), torch.zeros_like(xa), torch.zeros_like(xa)
-    run(ops.bottleneck(xa, w1p, p1[0][1], b1p, w2p, p2[0][1], b2p, y_f, c, add, shape))
-    run(ops.conv2d(xa, w1p, p1[0][1], b1p, t, 1, 1, 1, 1, 0, 0, c, c, ops.ACT_SILU))
-    run(ops.conv2d(t, w2p, p2[0][1], b2p, y_u, 3, 3, 1, 1, 1, 1, c, c, ops.ACT_SILU, res=xa if add else None))
+    run(ops.bottleneck(xa, w1p, kp1, b1p, w2p, kp2, b2p, y_f, c, add, shape))
+    run(ops.conv2d(xa, w1p, kp1, b1p, t, 1, 1, 1, 1, 0, 0, c, c, ops.ACT_SILU))
+    run(ops.conv2d(t, w2p, kp2, b2p, y_u, 3, 3, 1, 1, 1, 1, c, c, ops.ACT_SILU, res=xa if add else None))
     assert torch.equal(y_f, y_u), "fused Bottleneck must match the two-launch form bit for bit"
     for g in range(G):
         tt = q(F.silu(F.conv2d(q(xs[g], dt), q(w1[g], dt), b1[g])), dt)
@@ -644,21 +622,19 @@ def test_bottleneck_with_chained_cv3_equals_two_launches(case, dt):
     b3 = [rnd((c3,), 213 + g, 0.2) for g in range(G)]
     st = (lambda ts: torch.stack(ts).contiguous()) if paired else (lambda ts: ts[0])
     cat = st([to_act(x, dt) for x in xs])
-    p1 = [ops.pack_conv_weight(w.to(DEV), dt) for w in w1]
-    p2 = [ops.pack_conv_weight(w.to(DEV), dt) for w in w2]
-    p3 = [ops.pack_conv_weight(torch.cat((w[:, c:], w[:, :c]), 1).to(DEV), dt) for w in w3]     # -> [cv2 | m]
-    w1p, w2p, w3p = (st([p_[0] for p_ in ps]) for ps in (p1, p2, p3))
-    b1p, b2p, b3p = (st([ops.pack_bias(b.to(DEV), n) for b in bs]) for bs, n in ((b1, c), (b2, c), (b3, c3)))
+    w1p, kp1, b1p = ops.pack_streams([(w.to(DEV), b.to(DEV)) for w, b in zip(w1, b1)], dt)
+    w2p, kp2, b2p = ops.pack_streams([(w.to(DEV), b.to(DEV)) for w, b in zip(w2, b2)], dt)
+    w3p, kp3, b3p = ops.pack_streams([(torch.cat((w[:, c:], w[:, :c]), 1).to(DEV), b.to(DEV)) for w, b in zip(w3, b3)], dt)     # -> [cv2 | m]
     a, bhalf, a2 = cat[..., :c], cat[..., c:2 * c], cat[..., 2 * c:]
     lead = (G, B) if paired else (B,)
     y_u = torch.zeros((*lead, H, W, c3), dtype=dt, device=DEV)
     y_f = torch.full((*lead, H, W, c3 + 8), 7.0, dtype=dt, device=DEV)
-    run(ops.bottleneck(a, w1p, p1[0][1], b1p, w2p, p2[0][1], b2p, a2, c, add, 1))
-    run(ops.conv2d(cat[..., c:], w3p, p3[0][1], b3p, y_u, 1, 1, 1, 1, 0, 0, 2 * c, c3, ops.ACT_SILU))
+    run(ops.bottleneck(a, w1p, kp1, b1p, w2p, kp2, b2p, a2, c, add, 1))
+    run(ops.conv2d(cat[..., c:], w3p, kp3, b3p, y_u, 1, 1, 1, 1, 0, 0, 2 * c, c3, ops.ACT_SILU))
     m_out = a2.clone()
     a2.fill_(3.0)                                                      # the fused launch must not need (or write) slot a'
-    run(ops.bottleneck(a, w1p, p1[0][1], b1p, w2p, p2[0][1], b2p, None, c, add, 1,
-                       cv3=dict(w=w3p, kp=p3[0][1], bias=b3p, y=y_f[..., :c3], cout=c3, x2=bhalf)))
+    run(ops.bottleneck(a, w1p, kp1, b1p, w2p, kp2, b2p, None, c, add, 1,
+                       cv3=dict(w=w3p, kp=kp3, bias=b3p, y=y_f[..., :c3], cout=c3, x2=bhalf)))
     assert torch.equal(y_f[..., :c3], y_u)
     assert bool((y_f[..., c3:] == 7.0).all()) and bool((a2 == 3.0).all())
     for g in range(G):
@@ -694,25 +670,23 @@ def test_conv_with_chained_1x1_equals_two_launches(case, dt):
     b2 = [rnd((c2,), 89 + g, 0.2) for g in range(G)]
     stk = (lambda ts: torch.stack(ts).contiguous()) if paired else (lambda ts: ts[0])
     xa = stk([to_act(x, dt) for x in xs])
-    p1 = [ops.pack_conv_weight(w.to(DEV), dt) for w in w1]
-    p2 = [ops.pack_conv_weight(w.to(DEV), dt) for w in w2]
-    w1p, w2p = stk([p_[0] for p_ in p1]), stk([p_[0] for p_ in p2])
-    b1p, b2p = stk([ops.pack_bias(b.to(DEV), c1) for b in b1]), stk([ops.pack_bias(b.to(DEV), c2) for b in b2])
+    w1p, kp1, b1p = ops.pack_streams([(w.to(DEV), b.to(DEV)) for w, b in zip(w1, b1)], dt)
+    w2p, kp2, b2p = ops.pack_streams([(w.to(DEV), b.to(DEV)) for w, b in zip(w2, b2)], dt)
     Ho, Wo = (H + 2 - 3) // st + 1, (W + 2 - 3) // st + 1
     shp = (G, B, Ho, Wo) if paired else (B, Ho, Wo)
     mid = torch.zeros((*shp, c1), dtype=dt, device=DEV)
     y_u = torch.zeros((*shp, c2 + 8), dtype=dt, device=DEV)[..., :c2]
     y_f = torch.zeros((*shp, c2 + 8), dtype=dt, device=DEV)[..., :c2]
-    run(ops.conv2d(xa, w1p, p1[0][1], b1p, mid, 3, 3, st, st, 1, 1, cin, c1, ops.ACT_SILU))
-    run(ops.conv2d(mid, w2p, p2[0][1], b2p, y_u, 1, 1, 1, 1, 0, 0, c1, c2, ops.ACT_SILU))
+    run(ops.conv2d(xa, w1p, kp1, b1p, mid, 3, 3, st, st, 1, 1, cin, c1, ops.ACT_SILU))
+    run(ops.conv2d(mid, w2p, kp2, b2p, y_u, 1, 1, 1, 1, 0, 0, c1, c2, ops.ACT_SILU))
     dummy = torch.zeros((*shp, c1), dtype=dt, device=DEV)
-    run(ops.conv2d(xa, w1p, p1[0][1], b1p, dummy, 3, 3, st, st, 1, 1, cin, c1, ops.ACT_SILU, tile=tile,
-                   chain=dict(w=w2p, kp=p2[0][1], bias=b2p, y=y_f, cout=c2)))
+    run(ops.conv2d(xa, w1p, kp1, b1p, dummy, 3, 3, st, st, 1, 1, cin, c1, ops.ACT_SILU, tile=tile,
+                   chain=dict(w=w2p, kp=kp2, bias=b2p, y=y_f, cout=c2)))
     assert float(dummy.abs().max()) == 0.0, "the intermediate tensor must not be written"
     assert torch.equal(y_f, y_u)
     y_k = torch.zeros_like(y_f)
-    run(ops.conv2d(xa, w1p, p1[0][1], b1p, dummy, 3, 3, st, st, 1, 1, cin, c1, ops.ACT_SILU, tile=tile,
-                   chain=dict(w=w2p, kp=p2[0][1], bias=b2p, y=y_k, cout=c2, keep=True)))
+    run(ops.conv2d(xa, w1p, kp1, b1p, dummy, 3, 3, st, st, 1, 1, cin, c1, ops.ACT_SILU, tile=tile,
+                   chain=dict(w=w2p, kp=kp2, bias=b2p, y=y_k, cout=c2, keep=True)))
     assert torch.equal(dummy, mid) and torch.equal(y_k, y_u), "chain_keep writes both layers' outputs"
     for g in range(G):
         t = q(F.silu(F.conv2d(q(xs[g], dt), q(w1[g], dt), b1[g], st, 1)), dt)
@@ -734,16 +708,14 @@ def test_bottleneck_3x3_with_shortcut_chained_to_next_1x1(case, dt):
     b1, b2 = [rnd((c,), 239 + g, 0.2) for g in range(G)], [rnd((c,), 241 + g, 0.2) for g in range(G)]
     stk = (lambda xs: torch.stack(xs).contiguous()) if paired else (lambda xs: xs[0])
     ta = stk([to_act(t, dt) for t in ts])
-    p1 = [ops.pack_conv_weight(w.to(DEV), dt) for w in w1]
-    p2 = [ops.pack_conv_weight(w.to(DEV), dt) for w in w2]
-    w1p, w2p = stk([p_[0] for p_ in p1]), stk([p_[0] for p_ in p2])
-    b1p, b2p = stk([ops.pack_bias(b.to(DEV), c) for b in b1]), stk([ops.pack_bias(b.to(DEV), c) for b in b2])
+    w1p, kp1, b1p = ops.pack_streams([(w.to(DEV), b.to(DEV)) for w, b in zip(w1, b1)], dt)
+    w2p, kp2, b2p = ops.pack_streams([(w.to(DEV), b.to(DEV)) for w, b in zip(w2, b2)], dt)
     a_u, a_f = stk([to_act(r, dt) for r in rs]), stk([to_act(r, dt) for r in rs])
     n_u, n_f = torch.zeros_like(a_u), torch.zeros_like(a_u)
-    run(ops.conv2d(ta, w1p, p1[0][1], b1p, a_u, 3, 3, 1, 1, 1, 1, c, c, ops.ACT_SILU, res=a_u))
-    run(ops.conv2d(a_u, w2p, p2[0][1], b2p, n_u, 1, 1, 1, 1, 0, 0, c, c, ops.ACT_SILU))
-    run(ops.conv2d(ta, w1p, p1[0][1], b1p, a_f, 3, 3, 1, 1, 1, 1, c, c, ops.ACT_SILU, res=a_f, tile=tile,
-                   chain=dict(w=w2p, kp=p2[0][1], bias=b2p, y=n_f, cout=c, keep=True)))
+    run(ops.conv2d(ta, w1p, kp1, b1p, a_u, 3, 3, 1, 1, 1, 1, c, c, ops.ACT_SILU, res=a_u))
+    run(ops.conv2d(a_u, w2p, kp2, b2p, n_u, 1, 1, 1, 1, 0, 0, c, c, ops.ACT_SILU))
+    run(ops.conv2d(ta, w1p, kp1, b1p, a_f, 3, 3, 1, 1, 1, 1, c, c, ops.ACT_SILU, res=a_f, tile=tile,
+                   chain=dict(w=w2p, kp=kp2, bias=b2p, y=n_f, cout=c, keep=True)))
     assert torch.equal(a_f, a_u) and torch.equal(n_f, n_u)
     for g in range(G):
         m = q(F.silu(F.conv2d(q(ts[g], dt), q(w1[g], dt), b1[g], 1, 1)), dt) + q(rs[g], dt)
@@ -837,12 +809,10 @@ def test_conv2d_fp32_output_and_groups(dt):
     res = rnd((2, rows, cout), 8)
     xg = x.to(DEV).to(dt).contiguous()
     rg = res.to(DEV).to(dt).contiguous()
-    packs = [ops.pack_matrix(w[g].to(DEV), dt) for g in range(2)]
-    wp = torch.stack([p_[0] for p_ in packs]).contiguous()
-    bp = torch.stack([ops.pack_bias(b[g].to(DEV), cout) for g in range(2)]).contiguous()
+    wp, kp, bp = ops.pack_streams([(w[g].to(DEV), b[g].to(DEV)) for g in range(2)], dt)
     y = torch.zeros((2, rows, cout), dtype=dt, device=DEV)
     gs = dict(x=xg.stride(0), w=wp.stride(0), bias=bp.stride(0), y=y.stride(0), res=rg.stride(0))
-    run(ops.conv2d(xg[0].view(rows, 1, 1, cin), wp, packs[0][1], bp, y[0].view(rows, 1, 1, cout), 1, 1, 1, 1, 0, 0, cin,
+    run(ops.conv2d(xg[0].view(rows, 1, 1, cin), wp, kp, bp, y[0].view(rows, 1, 1, cout), 1, 1, 1, 1, 0, 0, cin,
                    cout, ops.ACT_GELU, res=rg[0].view(rows, 1, 1, cout), alpha_acc=(0.5, 2.0), alpha_res=(1.5, -1.0),
                    groups=2, group_strides=gs))
     for g, (aa, ar) in enumerate(((0.5, 1.5), (2.0, -1.0))):
@@ -911,9 +881,7 @@ def test_persistent_stem_equals_staging_plus_conv(case, dt):
     g = np.random.default_rng(61)
     ws = [rnd((cout, 3, 6, 6), 62 + i, 1.0 / math.sqrt(108)) for i in range(G)]
     bs = [rnd((cout,), 64 + i, 0.2) for i in range(G)]
-    packs = [ops.pack_conv_weight(ops.s2d_conv_weight(w.to(DEV)), dt, 16) for w in ws]
-    st = (lambda ts: torch.stack(ts).contiguous()) if paired else (lambda ts: ts[0])
-    wp, kp, bp = st([p_[0] for p_ in packs]), packs[0][1], st([ops.pack_bias(b.to(DEV), cout) for b in bs])
+    wp, kp, bp = ops.pack_streams([(ops.s2d_conv_weight(w.to(DEV)), b.to(DEV)) for w, b in zip(ws, bs)], dt, 16)
     if u8:
         img = torch.from_numpy(g.integers(0, 256, (B, 6, H, W), dtype=np.uint8)).to(DEV)
     else:
@@ -949,12 +917,9 @@ def test_stem2_equals_stem_then_chained_conv(case, dt):
     b0 = [rnd((32,), 168 + i, 0.2) for i in range(G)]
     b1 = [rnd((64,), 170 + i, 0.2) for i in range(G)]
     b2 = [rnd((c2,), 172 + i, 0.2) for i in range(G)]
-    st = (lambda ts: torch.stack(ts).contiguous()) if paired else (lambda ts: ts[0])
-    p0 = [ops.pack_conv_weight(ops.s2d_conv_weight(w.to(DEV)), dt, 16) for w in w0]
-    p1 = [ops.pack_conv_weight(w.to(DEV), dt) for w in w1]
-    p2 = [ops.pack_conv_weight(w.to(DEV), dt) for w in w2]
-    w0p, w1p, w2p = (st([p_[0] for p_ in ps]) for ps in (p0, p1, p2))
-    b0p, b1p, b2p = (st([ops.pack_bias(b.to(DEV), n) for b in bs]) for bs, n in ((b0, 32), (b1, 64), (b2, c2)))
+    w0p, kp0, b0p = ops.pack_streams([(ops.s2d_conv_weight(w.to(DEV)), b.to(DEV)) for w, b in zip(w0, b0)], dt, 16)
+    w1p, kp1, b1p = ops.pack_streams([(w.to(DEV), b.to(DEV)) for w, b in zip(w1, b1)], dt)
+    w2p, kp2, b2p = ops.pack_streams([(w.to(DEV), b.to(DEV)) for w, b in zip(w2, b2)], dt)
     if u8:
         img = torch.from_numpy(g.integers(0, 256, (B, 6, H, W), dtype=np.uint8)).to(DEV)
     else:
@@ -968,10 +933,10 @@ def test_stem2_equals_stem_then_chained_conv(case, dt):
     dummy = torch.zeros((*lead, Ho, Wo, 64), dtype=dt, device=DEV)
     y_u = torch.zeros((*lead, Ho, Wo, c2 + 8), dtype=dt, device=DEV)[..., :c2]
     y_f = torch.full((*lead, Ho, Wo, c2 + 8), 7.0, dtype=dt, device=DEV)
-    run(ops.stem(img, w0p, p0[0][1], b0p, t0, 32))
-    run(ops.conv2d(t0, w1p, p1[0][1], b1p, dummy, 3, 3, 2, 2, 1, 1, 32, 64, ops.ACT_SILU,
-                   chain=dict(w=w2p, kp=p2[0][1], bias=b2p, y=y_u, cout=c2)))
-    run(ops.stem2(img, w0p, p0[0][1], b0p, w1p, p1[0][1], b1p, w2p, p2[0][1], b2p, y_f[..., :c2], 32, 64, c2))
+    run(ops.stem(img, w0p, kp0, b0p, t0, 32))
+    run(ops.conv2d(t0, w1p, kp1, b1p, dummy, 3, 3, 2, 2, 1, 1, 32, 64, ops.ACT_SILU,
+                   chain=dict(w=w2p, kp=kp2, bias=b2p, y=y_u, cout=c2)))
+    run(ops.stem2(img, w0p, kp0, b0p, w1p, kp1, b1p, w2p, kp2, b2p, y_f[..., :c2], 32, 64, c2))
     assert torch.equal(y_f[..., :c2], y_u)
     assert bool((y_f[..., c2:] == 7.0).all()), "channels beyond C2 must not be written"
     x0 = (img[:, :3].cpu().float() / 255.0) if u8 else (img[0] if paired else img).cpu()

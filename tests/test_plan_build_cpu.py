@@ -192,3 +192,55 @@ def test_chain_plans_for_host_fed_pipelines_have_no_graph_branches():
     assert a.branches and any(l.branch for l in a.launches)
     assert not b.branches and not any(l.branch for l in b.launches)
     assert [l.name for l in a.launches] == [l.name for l in b.launches]
+
+
+def test_packed_weights_are_shared_between_sites_and_packed_once(monkeypatch):
+    """Conv.packed derives its cache key from its arguments, so the fused launches and a plain Conv.emit of the same layers hold the SAME
+    tensors (one device copy, one fragment-major copy in ops.frag_weights), and a second plan packs nothing."""
+    from icafusion_amd import ops
+    from icafusion_amd.engine import ImageIn, Plan
+    dt = torch.bfloat16
+    m = Model(load_cfg("yolov5s_Transfusion_kaist.yaml")).eval()
+    plan = m.build_plan(2, 320, 320, "cpu", dt)
+    ir0 = min(m.stream_twins())
+    (stem, conv1, c3), (stem_t, conv1_t, c3_t) = m.model[0:3], m.model[ir0:ir0 + 3]
+    stem2, bneck = plan.launches[:2]
+    assert (stem2.name, bneck.name) == ("stem+conv3x3s2+1x1", "bottleneck+cv3")
+    s = Plan("cpu", dt)
+    stem.emit(s, ImageIn(torch.zeros((2, 1, 3, 64, 64))), twin=stem_t)
+    conv1.emit(s, s.act(1, 32, 32, 32, pair=True), twin=conv1_t)
+    c3.cv1.emit(s, s.act(1, 16, 16, 64, pair=True), twin=c3_t.cv1, also=(c3.cv2,), twin_also=(c3_t.cv2,))
+    c3.cv3.emit(s, s.act(1, 16, 16, 64, pair=True), twin=c3_t.cv3, swap_halves=True)
+    assert [l.name for l in s.launches] == ["stem", "conv3x3s2", "conv1x1s1", "conv1x1s1"]
+    w0, b0, w1, b1, w2, b2 = stem2.keep[2:8]                       # ops.stem2: keep = (args, img, w0, b0, w1, b1, w2, b2, y)
+    assert s.launches[0].keep[1] is w0 and s.launches[0].keep[2] is b0          # ops.stem: keep = (img, w, bias, y)
+    assert s.launches[1].keep[2] is w1 and s.launches[1].keep[3] is b1          # ops.conv2d: keep = (args, x, w, bias, ...)
+    assert s.launches[2].keep[2] is w2 and s.launches[2].keep[3] is b2
+    tail = bneck.keep[4]                                           # ops.bottleneck: keep = (args, the 3x3's keep, w1, bias1, cv3)
+    assert s.launches[3].keep[2] is tail["w"] and s.launches[3].keep[3] is tail["bias"]
+    calls, pack_matrix = [], ops.pack_matrix
+    monkeypatch.setattr(ops, "pack_matrix", lambda *a: calls.append(a) or pack_matrix(*a))
+    c3.cv3.packed(s, c3_t.cv3)                                     # (cv3 with its K halves in place: no launch of this plan uses it)
+    assert len(calls) == 2
+    again = m.build_plan(2, 320, 320, "cpu", dt)
+    assert len(calls) == 2 and again.launches[0].keep[2] is w0 and len(again.launches) == len(plan.launches)
+
+
+def test_packed_cache_key_follows_every_argument():
+    """Two Conv.packed calls that differ in any one argument get different cache entries; equal calls get the same one."""
+    from icafusion_amd.engine import Plan
+    a, b, c = (Conv(64, 32, 1).eval() for _ in range(3))
+    plan = Plan("cpu", torch.bfloat16)
+
+    def flip(w):
+        return w.flip(1)
+    variants = [{}, dict(cin_pad=72), dict(swap_halves=True), dict(cin_slice=(0, 32)), dict(cin_slice=(32, 64)), dict(also=(b,)), dict(also=(c,)),
+                dict(also=(b, c)), dict(transform=flip), dict(twin=c), dict(twin=b, also=(c,), twin_also=(a,)), dict(twin=b, also=(c,), twin_also=(c,))]
+    got = [a.packed(plan, **v) for v in variants]
+    assert len({id(g) for g in got}) == len(variants) == len(a._cache) and len({id(g[0]) for g in got}) == len(variants)
+    assert all(a.packed(plan, **v) is g for v, g in zip(variants, got)) and len(a._cache) == len(variants)
+    assert a.packed(Plan("cpu", torch.float16)) is not got[0] and got[0][0].dtype == torch.bfloat16
+    base, padded, swapped, low = (g[0] for g in got[:4])
+    assert padded.shape[1] > base.shape[1] == 64 and torch.equal(padded[:, :64], base) and not padded[:, 64:].any()
+    assert torch.equal(swapped[:, :32], base[:, 32:]) and torch.equal(swapped[:, 32:], base[:, :32]) and torch.equal(low[:, :32], base[:, :32])
+    assert got[9][0].shape == (2,) + tuple(base.shape) and torch.equal(got[9][0][0], base) and got[9][2].shape == (2, base.shape[0])
