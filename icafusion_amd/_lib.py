@@ -133,6 +133,11 @@ def lib():
         if not os.path.exists(LIB_PATH):
             raise IcafError(f"{LIB_PATH} not found — build it with `python -m icafusion_amd.build` "
                             "(hipcc --offload-arch=gfx950); icafusion_amd has no CPU / PyTorch fallback")
+        # torch first: its wheel carries its own HIP runtime, and a process in which libicaf.so brought the system's runtime in BEFORE torch
+        # initialises the GPU ends up with two of them — the second reports "no ROCm-capable device" at its first launch
+        # (`python __graft_entry__.py --smoke`: build() loads the library, smoke() then imports torch).  Loaded after torch, the
+        # library shares the one runtime whose streams and allocations it is handed anyway.
+        import torch  # noqa: F401
         handle = C.CDLL(LIB_PATH)
         for name, (res, args) in SIGNATURES.items():
             try:

@@ -141,7 +141,9 @@ template <> __device__ __forceinline__ void mma_step<ICAF_F32>(f32x16& acc, cons
 }
 
 // x * sigmoid(x) with the hardware exp2 / rcp (each ~1 ulp): 5 VALU ops instead of ~25 for expf + IEEE division.
-// For very negative x, exp2 overflows to +inf, rcp(inf) = 0 and the product is -0: the correct limit.
+// For very negative x, exp2 overflows to +inf, rcp(inf) = 0 and the product is -0; the reciprocal already returns 0 once 1 + e exceeds 2^126
+// (its result would be subnormal), so the result is -0 for v < -87.3, where the true value is below 89 * 2^-126 = 1.05e-36.  Elsewhere the error
+// is at most (7 + 2 |v| sigmoid(-v)) * 2^-24 of the result (roundings counted in tests/numerics.py; checked over every finite 16-bit input).
 __device__ __forceinline__ float silu_f(float v) {
     const float e = __builtin_amdgcn_exp2f(v * -1.4426950408889634f);
     return v * __builtin_amdgcn_rcpf(1.0f + e);
@@ -170,7 +172,8 @@ __device__ __forceinline__ void silu4_f(const float (&x)[4], float (&y)[4]) {
 #endif
 }
 __device__ __forceinline__ float gelu_f(float v) { return 0.5f * v * (1.0f + erff(v * 0.70710678118654752440f)); }
-// GELU(erf) for the 16-bit kernels: erf by Abramowitz & Stegun 7.1.26 (|error| <= 1.5e-7, far below half a unit of bf16 / f16),
+// GELU(erf) for the 16-bit kernels: erf by Abramowitz & Stegun 7.1.26 (|error| <= 1.5e-7: GELU within 0.5 |v| (1.5e-7 + 2^-23) + 25 * 2^-24 |result| —
+// an ABSOLUTE bound: far below half a unit of bf16 / f16 for |v| ~ 1, several fp16 units of the tiny results at v <= -3.5; tests/numerics.py),
 // one hardware exp2 + one rcp + 7 FMAs instead of libm's erff (~100 instructions; measured: 13 k cycles per [64 x 128] hidden chunk,
 // 60-75 % of the fused block kernel's MLP phase and most of the per-layer fc1 epilogue).  The fp32 parity build keeps erff.
 __device__ __forceinline__ float gelu_fast_f(float v) {

@@ -99,6 +99,18 @@ int icaf_stem2(const icaf_stem2_args* a, icaf_stream_t s);
  * Wp = packed weights [Np][Kp] (K-major, Np = Cout rounded up to 128, Kp = K rounded up to 64 elements, zero
  * padded).  `groups` > 1 batches independent problems (the two modalities of DMFF) in gridDim.z; the *_gs
  * fields are the per-group strides in ELEMENTS (bytes/sizeof for x,w,y,res; floats for bias).
+ *
+ * Rounding.  The sum, bias, pre term, activation and alpha_acc are evaluated in fp32.  The result is rounded to out_dtype (nearest even,
+ * subnormals kept); with a residual, alpha_res * res is then added to that ROUNDED value by one fp32 fma and the sum rounded to out_dtype
+ * again — the rounding points of the unfused layers (a convolution's output is a tensor of the storage type, the shortcut adds to it).
+ * With fp32 output nothing is rounded in between.  ACT_SILU uses the hardware exp2 / reciprocal (-0 for pre-activations below -87.3, where
+ * the true value is below 1.05e-36); ACT_GELU is erff in the fp32 build and Abramowitz & Stegun 7.1.26 in the 16-bit builds, accurate to
+ * 0.5 |v| (1.5e-7 + 2^-23) in ABSOLUTE terms: several fp16 units of the result for v <= -3.5.
+ * Reads and writes.  x, res and pre may be channel slices of wider buffers holding anything, Inf and NaN included: no launch configuration
+ * lets a channel outside [0, Cin) of a pixel, or outside [0, Cout) of res / pre, reach a result, and none writes outside [0, Cout) of
+ * y / y2.  (The LDS-DMA pipelines prefetch K slices past the end of a pixel row — inside the buffer range of the view — into ring stages
+ * that are never consumed.)  Inside the views the usual IEEE rules hold: an Inf in x reaches every output whose receptive field holds it.
+ * tests/test_gpu_exact.py checks all of this bit for bit on every launch configuration.
  */
 typedef struct icaf_conv_args {
     const void* x;
