@@ -83,6 +83,7 @@ SIGNATURES = {
     "icaf_conv2d": (_i, [C.POINTER(ConvArgs), _p]),
     "icaf_bottleneck": (_i, [C.POINTER(BneckArgs), _p]),
     "icaf_conv2d_kernel_name": (_i, [C.POINTER(ConvArgs), C.c_char_p, _i]),
+    "icaf_conv2d_config_ids": (_i, [C.POINTER(_i), _i]),
     "icaf_sppf_pool": (_i, [_p, _i, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p]),
     "icaf_sppf_config": (_i, [_i, _i, _i, _i, C.POINTER(_i)]),
     "icaf_upsample_nearest": (_i, [_p, _i, _p, _i, _i, _i, _i, _i, _i, _i, _p]),

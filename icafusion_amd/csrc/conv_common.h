@@ -25,6 +25,30 @@ constexpr int ROWB = 64;        // bytes of K per LDS row per slice
 constexpr int ROWS = 80;        // padded LDS row stride in bytes (register-staged pipeline)
 constexpr int NTHREADS = 256;
 
+// Host side of the launch-configuration families that icaf_conv2d dispatches to (igemm.hip: kFamilies): `check` returns 0 if the shape can
+// run these args, else an error code with the reason in last_error(); `launch` runs after its check has passed; `tag` names the shape.
+// ctile.hip
+int ctile_conv_check(const icaf_conv_args* a, const ConvP& p, int shape);
+int launch_ctile(const icaf_conv_args* a, const ConvP& p, int shape, hipStream_t s);
+const char* ctile_tag(int shape);
+// igemm_stream.hip
+int stream_check(const icaf_conv_args* a, const ConvP& p, int shape);
+int launch_stream(const icaf_conv_args* a, const ConvP& p, int shape, hipStream_t s);
+const char* stream_tag(int shape);
+// igemm_wreg.hip
+int wreg_check(const icaf_conv_args* a, const ConvP& p, int shape);
+int launch_wreg(const icaf_conv_args* a, const ConvP& p, int shape, hipStream_t s);
+const char* wreg_tag(int shape);
+// cstream.hip
+int cstream_check(const icaf_conv_args* a, const ConvP& p, int shape);
+int launch_cstream(const icaf_conv_args* a, const ConvP& p, int shape, hipStream_t s);
+const char* cstream_tag(int shape);
+// cwide.hip
+int cwide_check(const icaf_conv_args* a, const ConvP& p, int shape);
+int launch_cwide(const icaf_conv_args* a, const ConvP& p, int shape, hipStream_t s);
+const char* cwide_tag(int shape);
+int launch_bneck(const icaf_conv_args* a, const ConvP& p, int shape, hipStream_t s);      // ctile.hip (icaf_bottleneck)
+
 // DT = the layer's storage type: the 16-bit builds evaluate GELU's erf by a 1.5e-7-accurate polynomial (gelu_fast_f), fp32 by erff
 template <int ACT, int DT = ICAF_F32> __device__ __forceinline__ float apply_act(float v) {
     if constexpr (ACT == ICAF_ACT_SILU) return silu_f(v);

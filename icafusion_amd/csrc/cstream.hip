@@ -282,7 +282,9 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 // ---------------------------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------------------------
-int cstream_check(const icaf_conv_args* a, const ConvP& p) {
+const char* cstream_tag(int) { return "8x16n64"; }
+
+int cstream_check(const icaf_conv_args* a, const ConvP& p, int) {      // (one shape: id 71)
     if (a->dtype == ICAF_F32 || a->out_dtype != a->dtype) return fail(ICAF_ERR_UNSUPPORTED, "cstream: 16-bit types, out dtype == dtype");
     if (a->kh != 3 || a->kw != 3 || a->sh != 1 || a->sw != 1 || a->ph != 1 || a->pw != 1) return fail(ICAF_ERR_UNSUPPORTED, "cstream: 3x3 / stride 1 / pad 1 layers");
     if (a->Cin != CS_C || a->Cout > CS_C || a->Cout % 8 || a->Kp != 9 * CS_C) return fail(ICAF_ERR_UNSUPPORTED, "cstream: built for 64 -> (<= 64) channels (Cin = %d, Cout = %d, Kp = %d)", a->Cin, a->Cout, a->Kp);
@@ -314,9 +316,7 @@ static int launch_cstream_cfg(const ConvP& p, int groups, hipStream_t s) {
     return ICAF_OK;
 }
 
-int launch_cstream(const icaf_conv_args* a, const ConvP& p, hipStream_t s) {
-    int st = cstream_check(a, p);
-    if (st) return st;
+int launch_cstream(const icaf_conv_args* a, const ConvP& p, int, hipStream_t s) {
     if (a->dtype == ICAF_BF16) return a->w2 ? launch_cstream_cfg<ICAF_BF16, true>(p, a->groups, s) : launch_cstream_cfg<ICAF_BF16, false>(p, a->groups, s);
     return a->w2 ? launch_cstream_cfg<ICAF_F16, true>(p, a->groups, s) : launch_cstream_cfg<ICAF_F16, false>(p, a->groups, s);
 }

@@ -423,7 +423,7 @@ static int ilog2(int v) { int l = 0; while ((1 << l) < v) ++l; return l; }
 const char* ctile_tag(int shape) { return (shape >= 1 && shape <= 5) ? kShapes[shape - 1].tag : "?"; }
 
 // 0 if shape `id` can run these args, else an error code with the reason in last_error()
-int ctile_check(const icaf_conv_args* a, const ConvP& p, int shape) {
+static int ctile_check(const icaf_conv_args* a, const ConvP& p, int shape) {
     if (shape < 1 || shape > 5) return fail(ICAF_ERR_ARG, "ctile: unknown shape %d", shape);
     const CtileShape& sh = kShapes[shape - 1];
     const int eb = a->dtype == ICAF_F32 ? 4 : 2;
@@ -504,10 +504,13 @@ int launch_bneck(const icaf_conv_args* a, const ConvP& p, int shape, hipStream_t
     return launch_ctile_cfg<ICAF_F16, 8, 16, 64, 1, true>(p, a->groups, s);
 }
 
-int launch_ctile(const icaf_conv_args* a, const ConvP& p, int shape, hipStream_t s) {
-    int st = ctile_check(a, p, shape);
-    if (st) return st;
+// a plain convolution (icaf_conv2d, ids 40 + shape): the shape's conditions, and no chained layer
+int ctile_conv_check(const icaf_conv_args* a, const ConvP& p, int shape) {
     if (a->w2) return fail(ICAF_ERR_UNSUPPORTED, "ctile: no chained 1x1 (icaf_bottleneck chains the C3's cv3)");
+    return ctile_check(a, p, shape);
+}
+
+int launch_ctile(const icaf_conv_args* a, const ConvP& p, int shape, hipStream_t s) {
     if (a->dtype == ICAF_BF16) return launch_ctile_dt<ICAF_BF16>(p, a->groups, shape, s);
     if (a->dtype == ICAF_F16) return launch_ctile_dt<ICAF_F16>(p, a->groups, shape, s);
     return launch_ctile_dt<ICAF_F32>(p, a->groups, shape, s);

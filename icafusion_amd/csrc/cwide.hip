@@ -495,8 +495,6 @@ static int launch_cwide_dt(const icaf_conv_args* a, const ConvP& p, int shape, h
 
 // shapes: see kCw (tile id 80 + shape)
 int launch_cwide(const icaf_conv_args* a, const ConvP& p, int shape, hipStream_t s) {
-    int st = cwide_check(a, p, shape);
-    if (st) return st;
     return a->dtype == ICAF_BF16 ? launch_cwide_dt<ICAF_BF16>(a, p, shape, s) : launch_cwide_dt<ICAF_F16>(a, p, shape, s);
 }
 

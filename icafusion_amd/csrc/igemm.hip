@@ -433,78 +433,62 @@ __global__ __launch_bounds__(NTHREADS) void igemm_kernel(const ConvP p) {
 // ---------------------------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------------------------
-struct TileCfg { int id, bm, bn; const char* tag; };
-static const TileCfg kTiles[] = {{1, 128, 128, "128x128"}, {2, 128, 64, "128x64"}, {3, 256, 32, "256x32"}, {4, 64, 64, "64x64"},
-                                 {5, 256, 128, "256x128"}, {6, 256, 256, "256x256"}, {7, 0, 0, "-"}, {8, 128, 128, "128x128w8"},
-                                 {9, 128, 64, "128x64w8"}};
-
-// Launch configuration id = tile (1..4) + 10 * pipeline:
-//   pipeline 0: LDS-DMA, 64-byte slices, 3-stage ring      pipeline 1: register-staged (fallback)
-//   pipeline 2: LDS-DMA, 128-byte slices, 2-stage ring     pipeline 3: LDS-DMA, 128-byte slices, 3-stage ring
+// igemm launch configuration id = tile + 10 * pipeline.
 // Tiles 8 (128x128) and 9 (128x64) are the 128-row tiles with 8 wavefronts (the tuner uses 8: +1.3 % on the forward; 9 wins
 // isolated timings but loses in the graph, where it competes with the DMFF branches for wave slots, so it is not a candidate).
 // Tiles 5 (256x128) and 6 (256x256) are 8-wavefront workgroups (one per CU, 96 / 128 KB ring) that exist only on
 // pipeline 2 for the 16-bit types: they halve the L2 -> LDS bytes per FLOP of the 128x128 tile, which is what bounds
 // the deep layers (the LDS-DMA feed tops out near 20 bytes / clock / CU).
-// ctile.hip
-int ctile_check(const icaf_conv_args* a, const ConvP& p, int shape);
-int launch_ctile(const icaf_conv_args* a, const ConvP& p, int shape, hipStream_t s);
-int launch_bneck(const icaf_conv_args* a, const ConvP& p, int shape, hipStream_t s);
-const char* ctile_tag(int shape);
-// igemm_stream.hip
-int stream_check(const icaf_conv_args* a, const ConvP& p, int shape);
-int launch_stream(const icaf_conv_args* a, const ConvP& p, int shape, hipStream_t s);
-const char* stream_tag(int shape);
-// cstream.hip
-int cstream_check(const icaf_conv_args* a, const ConvP& p);
-int launch_cstream(const icaf_conv_args* a, const ConvP& p, hipStream_t s);
-// cwide.hip
-int cwide_check(const icaf_conv_args* a, const ConvP& p, int shape);
-int launch_cwide(const icaf_conv_args* a, const ConvP& p, int shape, hipStream_t s);
-const char* cwide_tag(int shape);
-// igemm_wreg.hip
-int wreg_check(const icaf_conv_args* a, const ConvP& p, int shape);
-int launch_wreg(const icaf_conv_args* a, const ConvP& p, int shape, hipStream_t s);
-const char* wreg_tag(int shape);
+struct TileCfg { int bm, bn, nw; const char* tag; };          // pixels x channels of the tile, wavefronts
+static const TileCfg kTiles[] = {{128, 128, 4, "128x128"}, {128, 64, 4, "128x64"}, {256, 32, 4, "256x32"}, {64, 64, 4, "64x64"},
+                                 {256, 128, 8, "256x128"}, {256, 256, 8, "256x256"}, {0, 0, 0, "-"}, {128, 128, 8, "128x128w8"},
+                                 {128, 64, 8, "128x64w8"}};
+struct PipeCfg { int rb, ns; const char* tag; };              // bytes of K per slice, ring depth (0: register-staged fallback)
+static const PipeCfg kPipes[] = {{64, 3, "_dma64x3"}, {0, 0, "_reg"}, {128, 2, "_dma128x2"}, {128, 3, "_dma128x3"}};
 
-//   40 + shape: 3x3 direct convolution from an LDS halo tile (ctile.hip); 50 + shape: persistent streaming GEMM for 1x1 layers
-//   (igemm_stream.hip); 60 + shape: weight operand fed from registers (igemm_wreg.hip); an explicit request that the layer cannot
-//   satisfy is an error (the autotuner skips it), it is never chosen silently.  71: persistent 3x3 with a resident filter (cstream.hip);
-//   80 + shape: 3x3 (stride 1 / 2) from a resident halo patch with the weights streamed per wave into registers (cwide.hip).
-static int pick_tile(const icaf_conv_args* a, const ConvP& p) {
-    const bool dma_ok = p.x_bytes != 0;
-    if (a->tile > 40 && a->tile < 90) return a->tile;
-    if (a->tile >= 1 && a->tile <= 34 && a->tile % 10 >= 1 && a->tile % 10 <= 4) {
-        const int pipe = a->tile / 10;
-        return (pipe != 1 && !dma_ok) ? a->tile % 10 + 10 : a->tile;
-    }
-    if (a->tile == 25 || a->tile == 26 || a->tile == 28 || a->tile == 29) return a->tile;          // validated in launch_tile
-    if (a->x2) return 81;                           // C3 tail: cwide.hip only (its check names what the layer must look like)
+// the igemm ids that are built: tiles 1-4 on every pipeline, the 8-wavefront tiles 5 / 6 / 8 / 9 on pipeline 2 only
+static bool igemm_built(int id) {
+    const int pipe = id / 10, t = id % 10;
+    return id >= 1 && pipe <= 3 && ((t >= 1 && t <= 4) || (pipe == 2 && t != 0 && t != 7));
+}
+
+// Which tile x pipeline builds carry the chained 1x1 (16-bit types: its W2 must fit in LDS behind the ring / staging) and the pre term.
+// The launch templates prune their instantiations with these, igemm_check tests the same expressions.
+constexpr bool chain_built(int bm, int bn, int nw, int rb, int ns) {
+    const int ring = ns * (bm + bn) * rb, out = bm * (bn * 2 + 16);
+    return bn >= 64 && ns * rb != 384 && (nw == 4 ? bm == 128 : bn == 256) && (ring > out ? ring : out) + 1024 + bn * bn * 2 <= 160 * 1024;
+}
+constexpr bool pre_built(int bm, int rb, int ns) { return bm == 128 && ns * rb != 384; }     // 4- and 8-wavefront 128-row tiles
+
+// 0 if igemm configuration `id` can run these args, else an error code with the reason in last_error(): every run-time condition of
+// the launch templates below (which only prune, by `if constexpr`, what is not built)
+static int igemm_check(const icaf_conv_args* a, const ConvP& p, int id) {
+    if (!igemm_built(id)) return fail(ICAF_ERR_ARG, "icaf_conv2d: unknown launch configuration %d", id);
+    const int t = id % 10;
+    const TileCfg& tc = kTiles[t - 1];
+    const PipeCfg& pc = kPipes[id / 10];
     const bool f32 = a->dtype == ICAF_F32 || a->out_dtype == ICAF_F32;
-    const int N = a->Cout;
-    const long long M = p.M;
-    auto blocks = [&](int t) { return ((M + kTiles[t - 1].bm - 1) / kTiles[t - 1].bm) * ((N + kTiles[t - 1].bn - 1) / kTiles[t - 1].bn) * a->groups; };
-    int t;
-    if (N > 64 && !f32) t = 1;
-    else if (N > 32) t = 2;
-    else t = 3;
-    // small problems: prefer more, smaller workgroups so every CU gets several
-    if (t == 1 && blocks(1) < 512 && blocks(2) > blocks(1)) t = 2;
-    if (blocks(t) < 512 && blocks(4) > blocks(t)) t = 4;
-    if (!dma_ok) return t + 10;
-    const int eb = a->dtype == ICAF_F32 ? 4 : 2;
-    if (a->w2) {                                    // chained 1x1: the N tile must hold every channel of both layers
-        const int c = a->Cout > a->Cout2 ? a->Cout : a->Cout2;
-        const bool w128 = ((long long)a->Cin * eb) % 128 == 0;
-        if (c <= 64) return w128 ? 22 : 2;
-        return w128 ? 21 : 1;                       // (c > 128 is rejected at launch: W2 would not fit beside the ring)
+    if (t == 1 && a->out_dtype == ICAF_F32) return fail(ICAF_ERR_UNSUPPORTED, "tile 128x128 has no fp32-output build");
+    if (tc.nw == 8) {
+        if (f32) return fail(ICAF_ERR_UNSUPPORTED, t >= 8 ? "8-wavefront 128-row tiles exist for 16-bit types only" : "tiles 256x128 / 256x256 exist for 16-bit types only");
+        if (p.x_bytes == 0) return fail(ICAF_ERR_UNSUPPORTED, "tile %s runs on the LDS-DMA pipeline only: operand exceeds the 2 GiB buffer-descriptor range", tc.tag);
     }
-    if (a->pre) {                                   // only tiles 1 / 2 on pipelines 0 / 2 carry the pre term
-        if (t > 2) t = 2;
-        return ((long long)a->Cin * eb) % 128 == 0 ? t + 20 : t;
+    if (!a->w2 && !a->pre) return ICAF_OK;
+    if (pc.rb == 0) return fail(ICAF_ERR_UNSUPPORTED, "icaf_conv2d: `pre` / chained 1x1 are not built for the register-staged pipeline");
+    const bool whole_taps = (a->Cin * (a->dtype == ICAF_F32 ? 4 : 2)) % pc.rb == 0;          // a K slice never straddles two filter taps
+    if (a->w2) {       // chained 1x1 (icaf.h): one N tile of 64 / 128 / 256 channels, tap-uniform K slices, pipelines 0 and 2
+        if (a->act != ICAF_ACT_SILU || f32 || !chain_built(tc.bm, tc.bn, tc.nw, pc.rb, pc.ns) || !whole_taps || a->Cout > tc.bn || a->Cout2 > tc.bn ||
+            a->pre || (a->res && !a->chain_keep) || (a->chain_keep && (a->alpha_acc[0] != 1.0f || a->alpha_acc[1] != 1.0f)))
+            return fail(ICAF_ERR_UNSUPPORTED, "icaf_conv2d: the chained 1x1 needs a 16-bit SiLU layer with Cout, Cout2 <= the N tile (64 / 128 / 256), "
+                                              "Cin*bytes %% %d == 0, no pre term, a residual only together with chain_keep, on pipelines 0 / 2", pc.rb);
+        return ICAF_OK;
     }
-    // full 128-byte lines whenever a pixel's tap (or two adjacent taps) provides them
-    return (long long)p.K * eb >= 256 ? t + 20 : t;
+    // pre-activation bilinear term (DMFF fused tail): 1x1 + SiLU on the 128-row tiles only
+    if (a->act != ICAF_ACT_SILU || a->out_dtype != a->dtype || !pre_built(tc.bm, pc.rb, pc.ns) || !whole_taps ||
+        a->kh != 1 || a->kw != 1 || a->sh != 1 || a->sw != 1 || a->ph != 0 || a->pw != 0)
+        return fail(ICAF_ERR_UNSUPPORTED, "icaf_conv2d: `pre` is built for 1x1 / stride 1 SiLU layers with Cin*bytes %% %d == 0 on tiles 128x128 / 128x64 "
+                                          "(pipelines 0 and 2; 8-wavefront 128x128 on pipeline 2)", pc.rb);
+    return ICAF_OK;
 }
 
 template <int DT, int ODT, int BM, int BN, int WM, int WN, int ACT, int RB, int NS, int MODE, bool PRE = false, bool CHAIN = false>
@@ -519,31 +503,21 @@ static int launch_dma_mode(const ConvP& q, dim3 grid, hipStream_t s) {
     return ICAF_OK;
 }
 
+// (igemm_check has accepted the launch: the `fail`s below are reached only if it and the `if constexpr` pruning disagree)
 template <int DT, int ODT, int BM, int BN, int WM, int WN, int ACT, int RB, int NS>
 static int launch_dma(const ConvP& q, dim3 grid, hipStream_t s) {
+    if (q.w2) {       // chained 1x1: tap-uniform K slices
+        if constexpr (ACT == ICAF_ACT_SILU && ODT == DT && DT != ICAF_F32 && chain_built(BM, BN, (BM / WM) * (BN / WN), RB, NS))
+            return launch_dma_mode<DT, ODT, BM, BN, WM, WN, ACT, RB, NS, 2, false, true>(q, grid, s);
+        return fail(ICAF_ERR_UNSUPPORTED, "icaf_conv2d: no chained-1x1 build of this tile / pipeline / type");
+    }
+    if (q.pre) {      // pre-activation term: a plain row-major pixel operand
+        if constexpr (ACT == ICAF_ACT_SILU && ODT == DT && pre_built(BM, RB, NS))
+            return launch_dma_mode<DT, ODT, BM, BN, WM, WN, ACT, RB, NS, 1, true>(q, grid, s);
+        return fail(ICAF_ERR_UNSUPPORTED, "icaf_conv2d: no `pre` build of this tile / pipeline / type");
+    }
     const int eb = DT == ICAF_F32 ? 4 : 2;
     const bool whole_taps = (q.Cin * eb) % RB == 0;          // a K slice never straddles two filter taps
-    if (q.w2) {       // chained 1x1 (icaf.h): one N tile of 64 / 128 / 256 channels, tap-uniform K slices, pipelines 0 and 2
-        if constexpr (ACT == ICAF_ACT_SILU && ODT == DT && DT != ICAF_F32 && BN >= 64 && NS * RB != 384 &&
-                      ((BM / WM) * (BN / WN) == 4 ? BM == 128 : BN == 256)) {
-            constexpr int lds_need = (NS * (BM + BN) * RB > TileLds<DT, ODT, BM, BN>::OUT_BYTES ? NS * (BM + BN) * RB : TileLds<DT, ODT, BM, BN>::OUT_BYTES) + 1024 + BN * BN * 2;
-            if constexpr (lds_need <= 160 * 1024) {
-                if (whole_taps && q.Cout <= BN && q.Cout2 <= BN && !q.pre && (!q.res || q.keep1) &&
-                    (!q.keep1 || (q.alpha_acc[0] == 1.0f && q.alpha_acc[1] == 1.0f)))
-                    return launch_dma_mode<DT, ODT, BM, BN, WM, WN, ACT, RB, NS, 2, false, true>(q, grid, s);
-            }
-        }
-        return fail(ICAF_ERR_UNSUPPORTED, "icaf_conv2d: the chained 1x1 needs a 16-bit SiLU layer with Cout, Cout2 <= the N tile (64 / 128 / 256), "
-                                          "Cin*bytes %% %d == 0, no pre term, a residual only together with chain_keep, on pipelines 0 / 2", RB);
-    }
-    if (q.pre) {      // pre-activation bilinear term (DMFF fused tail): 1x1 + SiLU on the 128-row tiles only
-        if constexpr (ACT == ICAF_ACT_SILU && ODT == DT && BM == 128 && NS * RB != 384) {      // 4- and 8-wavefront 128-row tiles
-            if (whole_taps && q.kh == 1 && q.kw == 1 && q.sh == 1 && q.sw == 1 && q.ph == 0 && q.pw == 0)
-                return launch_dma_mode<DT, ODT, BM, BN, WM, WN, ACT, RB, NS, 1, true>(q, grid, s);
-        }
-        return fail(ICAF_ERR_UNSUPPORTED, "icaf_conv2d: `pre` is built for 1x1 / stride 1 SiLU layers with Cin*bytes %% %d == 0 on tiles 128x128 / 128x64 "
-                                          "(pipelines 0 and 2; 8-wavefront 128x128 on pipeline 2)", RB);
-    }
     if (whole_taps && q.kh == 1 && q.kw == 1 && q.sh == 1 && q.sw == 1 && q.ph == 0 && q.pw == 0)
         return launch_dma_mode<DT, ODT, BM, BN, WM, WN, ACT, RB, NS, 1>(q, grid, s);
     if (whole_taps) return launch_dma_mode<DT, ODT, BM, BN, WM, WN, ACT, RB, NS, 2>(q, grid, s);
@@ -557,7 +531,6 @@ static int launch_act(const ConvP& q, dim3 grid, int pipe, hipStream_t s) {
         case 2: return launch_dma<DT, ODT, BM, BN, WM, WN, ACT, 128, 2>(q, grid, s);
         case 3: return launch_dma<DT, ODT, BM, BN, WM, WN, ACT, 128, 3>(q, grid, s);
         default:
-            if (q.pre || q.w2) return fail(ICAF_ERR_UNSUPPORTED, "icaf_conv2d: `pre` / chained 1x1 are not built for the register-staged pipeline");
             igemm_kernel<DT, ODT, BM, BN, WM, WN, ACT><<<grid, dim3(NTHREADS), 0, s>>>(q);
             ICAF_LAUNCH_CHECK();
             return ICAF_OK;
@@ -570,7 +543,7 @@ static int launch_cfg(const ConvP& p, int groups, int pipe, hipStream_t s) {
     q.mtiles = (p.M + BM - 1) / BM;
     q.ntiles = (p.Cout + BN - 1) / BN;
     if (pipe != 1) {       // the DMA pipelines walk K in RB-byte slices
-        const int eb = DT == ICAF_F32 ? 4 : 2, bk = (pipe == 0 ? 64 : 128) / eb;
+        const int eb = DT == ICAF_F32 ? 4 : 2, bk = kPipes[pipe].rb / eb;
         q.nchunks = (p.K + bk - 1) / bk;
     }
     dim3 grid((unsigned)(q.mtiles * q.ntiles), 1, (unsigned)groups);
@@ -595,35 +568,103 @@ static int launch_big(const ConvP& p, int groups, hipStream_t s) {
 template <int DT, int ODT>
 static int launch_tile(const ConvP& p, int groups, int cfg, hipStream_t s) {
     const int pipe = cfg / 10;
+    constexpr bool f32 = DT == ICAF_F32 || ODT == ICAF_F32;
     switch (cfg % 10) {
-        case 1:
-            if constexpr (ODT == ICAF_F32) return fail(ICAF_ERR_UNSUPPORTED, "tile 128x128 has no fp32-output build");
-            else return launch_cfg<DT, ODT, 128, 128, 64, 64>(p, groups, pipe, s);
+        case 1: if constexpr (ODT != ICAF_F32) return launch_cfg<DT, ODT, 128, 128, 64, 64>(p, groups, pipe, s); break;
         case 2: return launch_cfg<DT, ODT, 128, 64, 64, 32>(p, groups, pipe, s);
         case 3: return launch_cfg<DT, ODT, 256, 32, 64, 32>(p, groups, pipe, s);
         case 4: return launch_cfg<DT, ODT, 64, 64, 32, 32>(p, groups, pipe, s);
-        case 8:                                       // 128x128 / 128x64 tiles with 8 wavefronts (64x32 / 32x32 each): more waves
-        case 9:                                       // per SIMD to hide latency, same LDS footprint as the 4-wave tiles
-            if constexpr (DT == ICAF_F32 || ODT == ICAF_F32) return fail(ICAF_ERR_UNSUPPORTED, "8-wavefront 128-row tiles exist for 16-bit types only");
-            else {
-                if (pipe != 2 || p.x_bytes == 0) return fail(ICAF_ERR_UNSUPPORTED, "8-wavefront 128-row tiles run on pipeline 2 only (ids 28 / 29)");
-                return cfg % 10 == 8 ? launch_big<DT, ODT, 128, 128, 64, 32>(p, groups, s) : launch_big<DT, ODT, 128, 64, 32, 32>(p, groups, s);
-            }
-        case 5:
-        case 6:
-            if constexpr (DT == ICAF_F32 || ODT == ICAF_F32) return fail(ICAF_ERR_UNSUPPORTED, "tiles 256x128 / 256x256 exist for 16-bit types only");
-            else {
-                if (pipe != 2 || p.x_bytes == 0) return fail(ICAF_ERR_UNSUPPORTED, "tiles 256x128 / 256x256 run on the 128-byte LDS-DMA pipeline only (id 25 / 26)");
-                return cfg % 10 == 5 ? launch_big<DT, ODT, 256, 128, 64, 64>(p, groups, s) : launch_big<DT, ODT, 256, 256, 128, 64>(p, groups, s);
-            }
-        default: return fail(ICAF_ERR_ARG, "unknown tile id %d", cfg);
+        case 5: if constexpr (!f32) return launch_big<DT, ODT, 256, 128, 64, 64>(p, groups, s); break;
+        case 6: if constexpr (!f32) return launch_big<DT, ODT, 256, 256, 128, 64>(p, groups, s); break;
+        case 8: if constexpr (!f32) return launch_big<DT, ODT, 128, 128, 64, 32>(p, groups, s); break;   // 128x128 / 128x64 tiles with 8 wavefronts (64x32 / 32x32
+        case 9: if constexpr (!f32) return launch_big<DT, ODT, 128, 64, 32, 32>(p, groups, s); break;    // each): more waves per SIMD to hide latency, same LDS footprint
     }
+    return fail(ICAF_ERR_UNSUPPORTED, "icaf_conv2d: launch configuration %d has no build for these types", cfg);
+}
+
+static int launch_igemm(const icaf_conv_args* a, const ConvP& p, int id, hipStream_t s) {
+    if (a->dtype == ICAF_BF16)
+        return a->out_dtype == ICAF_F32 ? launch_tile<ICAF_BF16, ICAF_F32>(p, a->groups, id, s) : launch_tile<ICAF_BF16, ICAF_BF16>(p, a->groups, id, s);
+    if (a->dtype == ICAF_F16)
+        return a->out_dtype == ICAF_F32 ? launch_tile<ICAF_F16, ICAF_F32>(p, a->groups, id, s) : launch_tile<ICAF_F16, ICAF_F16>(p, a->groups, id, s);
+    return launch_tile<ICAF_F32, ICAF_F32>(p, a->groups, id, s);
+}
+
+// One row per kernel family: the launch configuration ids it owns (shape = id - base), its check (0, or an error code with the reason
+// in last_error()), its launch (the check has passed) and the name of its kernel.  An id in no row is not a configuration.
+//   igemm (this file): tile + 10 * pipeline;  ctile.hip: 3x3 direct convolution from an LDS halo tile;  igemm_stream.hip: persistent
+//   streaming GEMM for 1x1 layers;  igemm_wreg.hip: weight operand fed from registers;  cstream.hip: persistent 3x3 with a resident
+//   filter;  cwide.hip: 3x3 (stride 1 / 2) from a resident halo patch with the weights streamed per wave into registers.
+struct ConvFamily {
+    int lo, hi, base;
+    bool (*built)(int id);                        // which ids of lo .. hi exist
+    int (*check)(const icaf_conv_args*, const ConvP&, int shape);
+    int (*launch)(const icaf_conv_args*, const ConvP&, int shape, hipStream_t);
+    void (*name)(const ConvFamily&, const icaf_conv_args*, int shape, char* buf, int len);
+    const char* prefix;                           // (shape_name's operands)
+    const char* (*tag)(int shape);
+};
+static const char* const kTypeName[] = {"f32", "bf16", "f16"};
+static bool whole_range(int) { return true; }
+static void shape_name(const ConvFamily& f, const icaf_conv_args* a, int shape, char* buf, int len) {      // <prefix>_<type>_<tag>
+    snprintf(buf, len, "%s_%s_%s", f.prefix, kTypeName[a->dtype], f.tag(shape));
+}
+static void igemm_name(const ConvFamily&, const icaf_conv_args* a, int id, char* buf, int len) {           // pipeline and both types
+    snprintf(buf, len, "igemm%s_%s_%s_%s", kPipes[id / 10].tag, kTypeName[a->dtype], kTypeName[a->out_dtype], kTiles[id % 10 - 1].tag);
+}
+static const ConvFamily kFamilies[] = {
+    {1, 34, 0, igemm_built, igemm_check, launch_igemm, igemm_name, nullptr, nullptr},
+    {41, 45, 40, whole_range, ctile_conv_check, launch_ctile, shape_name, "ctile", ctile_tag},
+    {51, 52, 50, whole_range, stream_check, launch_stream, shape_name, "igemm_stream", stream_tag},
+    {61, 66, 60, whole_range, wreg_check, launch_wreg, shape_name, "igemm_wreg", wreg_tag},
+    {71, 71, 70, whole_range, cstream_check, launch_cstream, shape_name, "cstream", cstream_tag},
+    {81, 85, 80, whole_range, cwide_check, launch_cwide, shape_name, "cwide", cwide_tag},
+};
+
+static const ConvFamily* family_of(int id) {
+    for (const ConvFamily& f : kFamilies)
+        if (id >= f.lo && id <= f.hi && f.built(id)) return &f;
+    return nullptr;
+}
+
+// An explicit configuration (a->tile != 0; validate: one that is built) is what runs — one the layer cannot satisfy is an error (the
+// autotuner skips it), never replaced silently.  The one documented remap: tiles 1-4 on an LDS-DMA pipeline run on the register-staged
+// pipeline (id % 10 + 10) when an operand exceeds the 2 GiB buffer-descriptor range.  a->tile == 0: the automatic choice below.
+static int pick_tile(const icaf_conv_args* a, const ConvP& p) {
+    const bool dma_ok = p.x_bytes != 0;
+    if (a->tile) return (a->tile < 40 && a->tile % 10 <= 4 && !dma_ok) ? a->tile % 10 + 10 : a->tile;
+    if (a->x2) return 81;                           // C3 tail: cwide.hip only (its check names what the layer must look like)
+    const bool f32 = a->dtype == ICAF_F32 || a->out_dtype == ICAF_F32;
+    const int N = a->Cout;
+    const long long M = p.M;
+    auto blocks = [&](int t) { return ((M + kTiles[t - 1].bm - 1) / kTiles[t - 1].bm) * ((N + kTiles[t - 1].bn - 1) / kTiles[t - 1].bn) * a->groups; };
+    int t;
+    if (N > 64 && !f32) t = 1;
+    else if (N > 32) t = 2;
+    else t = 3;
+    // small problems: prefer more, smaller workgroups so every CU gets several
+    if (t == 1 && blocks(1) < 512 && blocks(2) > blocks(1)) t = 2;
+    if (blocks(t) < 512 && blocks(4) > blocks(t)) t = 4;
+    if (!dma_ok) return t + 10;
+    const int eb = a->dtype == ICAF_F32 ? 4 : 2;
+    if (a->w2) {                                    // chained 1x1: the N tile must hold every channel of both layers
+        const int c = a->Cout > a->Cout2 ? a->Cout : a->Cout2;
+        const bool w128 = ((long long)a->Cin * eb) % 128 == 0;
+        if (c <= 64) return w128 ? 22 : 2;
+        return w128 ? 21 : 1;                       // (c > 128 is rejected by igemm_check: W2 would not fit beside the ring)
+    }
+    if (a->pre) {                                   // only tiles 1 / 2 on pipelines 0 / 2 carry the pre term
+        if (t > 2) t = 2;
+        return ((long long)a->Cin * eb) % 128 == 0 ? t + 20 : t;
+    }
+    // full 128-byte lines whenever a pixel's tap (or two adjacent taps) provides them
+    return (long long)p.K * eb >= 256 ? t + 20 : t;
 }
 
 static int validate(const icaf_conv_args* a) {
     if (!a || !a->x || !a->w || !a->y) return fail(ICAF_ERR_ARG, "icaf_conv2d: null pointer");
     if (a->groups < 1 || a->groups > 2) return fail(ICAF_ERR_ARG, "icaf_conv2d: groups must be 1 or 2");
-    if (a->tile < 0 || a->tile >= 90) return fail(ICAF_ERR_ARG, "icaf_conv2d: unknown launch configuration %d", a->tile);
+    if (a->tile != 0 && !family_of(a->tile)) return fail(ICAF_ERR_ARG, "icaf_conv2d: unknown launch configuration %d", a->tile);
     const int vec = a->dtype == ICAF_F32 ? 4 : 8;
     if (a->dtype < 0 || a->dtype > 2) return fail(ICAF_ERR_ARG, "icaf_conv2d: bad dtype %d", a->dtype);
     if (a->out_dtype != a->dtype && a->out_dtype != ICAF_F32) return fail(ICAF_ERR_ARG, "icaf_conv2d: out_dtype must equal dtype or be fp32");
@@ -689,31 +730,49 @@ int conv_prepare(const icaf_conv_args* a, ConvP& p) {
     return ICAF_OK;
 }
 
+// validate, fill, pick_tile, family lookup, that family's check: what icaf_conv2d launches and icaf_conv2d_kernel_name names
+static int resolve(const icaf_conv_args* a, ConvP& p, const ConvFamily*& f, int& shape) {
+    int st = conv_prepare(a, p);
+    if (st) return st;
+    const int id = pick_tile(a, p);
+    if (a->x2 && id != 81 && id != 82) return fail(ICAF_ERR_UNSUPPORTED, "icaf_conv2d: x2 (C3 tail) is built for launch configurations 81 / 82 only (tile %d)", id);
+    f = family_of(id);
+    if (!f) return fail(ICAF_ERR_ARG, "icaf_conv2d: unknown launch configuration %d", id);
+    shape = id - f->base;
+    return f->check(a, p, shape);
+}
+
 }  // namespace icaf
 
 using namespace icaf;
 
 extern "C" int icaf_conv2d(const icaf_conv_args* a, icaf_stream_t s) {
-    int st = validate(a);
-    if (st) return st;
     ConvP p;
-    fill(a, p);
-    const int tile = pick_tile(a, p);
-    hipStream_t hs = S(s);
-    if (a->x2 && tile != 81 && tile != 82) return fail(ICAF_ERR_UNSUPPORTED, "icaf_conv2d: x2 (C3 tail) is built for launch configurations 81 / 82 only (tile %d)", tile);
-    if (tile == 71) return launch_cstream(a, p, hs);        // persistent 3x3 with the filter resident in LDS (64 -> 64 channels)
-    if (tile > 80) return launch_cwide(a, p, tile - 80, hs);  // 3x3 (stride 1 / 2) from a resident halo patch, weights streamed into registers
-    if (tile > 70) return fail(ICAF_ERR_ARG, "unknown tile id %d", tile);
-    if (tile > 60) return launch_wreg(a, p, tile - 60, hs);
-    if (tile > 50) return launch_stream(a, p, tile - 50, hs);
-    if (tile > 40) return launch_ctile(a, p, tile - 40, hs);
-    if (a->dtype == ICAF_BF16)
-        return a->out_dtype == ICAF_F32 ? launch_tile<ICAF_BF16, ICAF_F32>(p, a->groups, tile, hs)
-                                        : launch_tile<ICAF_BF16, ICAF_BF16>(p, a->groups, tile, hs);
-    if (a->dtype == ICAF_F16)
-        return a->out_dtype == ICAF_F32 ? launch_tile<ICAF_F16, ICAF_F32>(p, a->groups, tile, hs)
-                                        : launch_tile<ICAF_F16, ICAF_F16>(p, a->groups, tile, hs);
-    return launch_tile<ICAF_F32, ICAF_F32>(p, a->groups, tile, hs);
+    const ConvFamily* f;
+    int shape;
+    const int st = resolve(a, p, f, shape);
+    return st ? st : f->launch(a, p, shape, S(s));
+}
+
+extern "C" int icaf_conv2d_kernel_name(const icaf_conv_args* a, char* buf, int buf_len) {
+    ConvP p;
+    const ConvFamily* f;
+    int shape;
+    const int st = resolve(a, p, f, shape);
+    if (st) return st;
+    f->name(*f, a, shape, buf, buf_len);
+    return ICAF_OK;
+}
+
+extern "C" int icaf_conv2d_config_ids(int* ids, int cap) {
+    int n = 0;
+    for (const ConvFamily& f : kFamilies)
+        for (int id = f.lo; id <= f.hi; ++id)
+            if (family_of(id)) {
+                if (ids && n < cap) ids[n] = id;
+                ++n;
+            }
+    return n;
 }
 
 extern "C" int icaf_bottleneck(const icaf_bneck_args* b, icaf_stream_t s) {
@@ -732,48 +791,4 @@ extern "C" int icaf_bottleneck(const icaf_bneck_args* b, icaf_stream_t s) {
     p.w1_bytes = (unsigned)((((long long)a->Cout + 127) / 128 * 128) * b->Kp1 * eb);
     p.x2 = b->x2; p.x2_gs = b->x2_gs; p.ldx2 = b->ldx2;
     return launch_bneck(a, p, b->shape, S(s));
-}
-
-extern "C" int icaf_conv2d_kernel_name(const icaf_conv_args* a, char* buf, int buf_len) {
-    int st = validate(a);
-    if (st) return st;
-    ConvP p;
-    fill(a, p);
-    const int tile = pick_tile(a, p);
-    if (a->x2 && tile != 81 && tile != 82) return fail(ICAF_ERR_UNSUPPORTED, "icaf_conv2d: x2 (C3 tail) is built for launch configurations 81 / 82 only (tile %d)", tile);
-    static const char* dn[] = {"f32", "bf16", "f16"};
-    if (tile == 71) {
-        st = cstream_check(a, p);
-        if (st) return st;
-        snprintf(buf, buf_len, "cstream_%s_8x16n64", dn[a->dtype]);
-        return ICAF_OK;
-    }
-    if (tile > 80) {
-        st = cwide_check(a, p, tile - 80);
-        if (st) return st;
-        snprintf(buf, buf_len, "cwide_%s_%s", dn[a->dtype], cwide_tag(tile - 80));
-        return ICAF_OK;
-    }
-    if (tile > 70) return fail(ICAF_ERR_ARG, "unknown tile id %d", tile);
-    if (tile > 60) {
-        st = wreg_check(a, p, tile - 60);
-        if (st) return st;
-        snprintf(buf, buf_len, "igemm_wreg_%s_%s", dn[a->dtype], wreg_tag(tile - 60));
-        return ICAF_OK;
-    }
-    if (tile > 50) {
-        st = stream_check(a, p, tile - 50);
-        if (st) return st;
-        snprintf(buf, buf_len, "igemm_stream_%s_%s", dn[a->dtype], stream_tag(tile - 50));
-        return ICAF_OK;
-    }
-    if (tile > 40) {
-        st = ctile_check(a, p, tile - 40);
-        if (st) return st;
-        snprintf(buf, buf_len, "ctile_%s_%s", dn[a->dtype], ctile_tag(tile - 40));
-        return ICAF_OK;
-    }
-    static const char* pn[] = {"_dma64x3", "_reg", "_dma128x2", "_dma128x3"};
-    snprintf(buf, buf_len, "igemm%s_%s_%s_%s", pn[tile / 10], dn[a->dtype], dn[a->out_dtype], kTiles[tile % 10 - 1].tag);
-    return ICAF_OK;
 }

@@ -186,8 +186,6 @@ static int launch_stream_act(const ConvP& p, int groups, hipStream_t s) {
 }
 
 int launch_stream(const icaf_conv_args* a, const ConvP& p, int shape, hipStream_t s) {
-    int st = stream_check(a, p, shape);
-    if (st) return st;
     if (a->dtype == ICAF_BF16) return shape == 1 ? launch_stream_act<ICAF_BF16, 128>(p, a->groups, s) : launch_stream_act<ICAF_BF16, 64>(p, a->groups, s);
     return shape == 1 ? launch_stream_act<ICAF_F16, 128>(p, a->groups, s) : launch_stream_act<ICAF_F16, 64>(p, a->groups, s);
 }

@@ -291,8 +291,6 @@ static int launch_wreg_shape(const icaf_conv_args* a, const ConvP& p, int shape,
 }
 
 int launch_wreg(const icaf_conv_args* a, const ConvP& p, int shape, hipStream_t s) {
-    int st = wreg_check(a, p, shape);
-    if (st) return st;
     return a->dtype == ICAF_BF16 ? launch_wreg_shape<ICAF_BF16>(a, p, shape, s) : launch_wreg_shape<ICAF_F16>(a, p, shape, s);
 }
 

@@ -115,9 +115,6 @@ def pack_streams(rows, dt, cin_pad=None):
 
 _FRAG_CACHE = {}              # id(packed tensor) -> (weakref to it, fragment-major copy); entries die with the packed tensor
 # (execution switches — which kernels the tuner may offer a layer, retune requests — live in options.PlanOptions; read as OPT.<field>)
-# (Round 5's persistent long-K GEMM — launch configuration 67, igemm_pers.hip — and the persistent halo-patch 3x3 — 90 + shape, cwpers.hip — were removed
-#  in round 6: the first won isolated and lost every benchmarked workload with two forwards in flight (yolov5l shard 3,813 -> 3,778 pairs/s), the second
-#  lost everywhere; no committed tune cache named either.  `git log -- icafusion_amd/csrc/igemm_pers.hip` has them; docs/HISTORY.md section 16 the numbers.)
 
 
 def frag_weights(w_packed):
@@ -188,12 +185,6 @@ def conv2d(x, w_packed, kp, bias, y, kh, kw, sh, sw, ph, pw, cin, cout, act, res
     a.alpha_acc[0], a.alpha_acc[1] = float(aa[0]), float(aa[1])
     a.alpha_res[0], a.alpha_res[1] = float(ar[0]), float(ar[1])
     a.tile = tile
-    wf = None
-    cw_layer = bool(OPT.cwide and act == ACT_SILU and cwide_shapes(kh, kw, sh, sw, ph, pw, cin, cout))                               # cwide.hip
-    if (x.dtype != torch.float32 and y.dtype == x.dtype and (cin * 2) % 128 == 0 and kp % 64 == 0 and pre is None
-            and ((OPT.wreg_gemm and chain is None and cout > 64) or cw_layer)):
-        wf = frag_weights(w_packed)                   # igemm_wreg.hip: weight operand from registers (tile ids 61 / 62)
-        a.wf, a.wf_gs = wf.data_ptr(), (wf.stride(0) if w_packed.dim() == 3 else 0)
     if pre is not None:               # fp32 coarse map (B, h, w, >= cout) added, bilinearly resized, before the activation
         Bp, hp, wp_, cp, ldp = _act_geom(pre)
         assert pre.dtype == torch.float32 and Bp == B and cp >= cout and groups == 1
@@ -215,6 +206,10 @@ def conv2d(x, w_packed, kp, bias, y, kh, kw, sh, sw, ph, pw, cin, cout, act, res
             Bx, Hx, Wx, cx2, ldx2 = _act_geom(x2)
             assert (Bx, Hx, Wx) == (B, Ho, Wo) and cx2 >= cout and x2.dtype == x.dtype and (x2.dim() == 5) == (x.dim() == 5)
             a.x2, a.ldx2, a.x2_gs = x2.data_ptr(), ldx2, (x2.stride(0) if x.dim() == 5 else 0)
+    wf = None
+    if wants_wf(a):                   # a kernel that feeds the weight operand from registers (igemm_wreg.hip, cwide.hip) is built for this layer
+        wf = frag_weights(w_packed)
+        a.wf, a.wf_gs = wf.data_ptr(), (wf.stride(0) if w_packed.dim() == 3 else 0)
     m = B * Ho * Wo
     flops = 2.0 * m * cout * kh * kw * cin * groups
     es, eo = x.element_size(), y.element_size()
@@ -263,23 +258,19 @@ def bottleneck(x, w1_packed, kp1, bias1, w2_packed, kp2, bias2, y, c, add, shape
 
 _TUNE_CACHE = {}
 _RETUNED = set()
-CTILE_SHAPES = {1: (32, 1), 2: (64, 1), 3: (64, 1), 4: (64, 2), 5: (128, 1)}     # shape id -> (BN, stride), ctile.hip
-CONV_PIPELINES = (0, 1, 2)        # LDS-DMA 64 B x3, register-staged, LDS-DMA 128 B x2 (3 = 128 B x3: never won)
+BUILT_NOT_OFFERED = (29, 31, 32, 33, 34)      # 128x64 with 8 wavefronts (graph_tune.py tries it), LDS-DMA 128 B x3 (pipeline 3: never won)
+# cwide.hip (80 + shape): (stride, Cin) -> ids, for Cout in multiples of 128 (stride 1: 128 -> 128 only); 8 x 16 / 8 x 8 output pixels per workgroup
+_CWIDE = {(1, 128): (81, 82), (2, 64): (83, 85), (2, 128): (84,)}
+_CTILE = {41: (32, 1), 42: (64, 1), 43: (64, 1), 44: (64, 2), 45: (128, 1)}     # ctile.hip (40 + shape): id -> (BN, stride)
+
+
+def _cwide_ids(s3, cin, cout):
+    return [] if (cout % 128 or (s3 == 1 and cout != 128)) else list(_CWIDE.get((s3, cin), ()))
 
 
 def cwide_shapes(kh, kw, sh, sw, ph, pw, cin, cout):
     """Tile ids (80 + shape) of cwide.hip that are built for this 3x3 layer: resident halo patch, weights streamed into registers."""
-    if (kh, kw, ph, pw) != (3, 3, 1, 1) or sh != sw or cout % 128:
-        return []
-    # 80 + shape: one tile per workgroup
-    if sh == 1:
-        return [81, 82] if (cin == 128 and cout == 128) else []          # 8 x 16 / 8 x 8 output pixels per workgroup
-    if sh == 2:
-        if cin == 64:
-            return [83, 85]                                              # stride 2, 64 -> 128 k: 8 x 16 / 8 x 8
-        if cin == 128:
-            return [84]                                                  # stride 2, 128 -> 128 k: 8 x 8
-    return []
+    return _cwide_ids(sh if ((kh, kw, ph, pw) == (3, 3, 1, 1) and sh == sw) else 0, cin, cout)
 
 
 def _conv_signature(a):
@@ -287,59 +278,64 @@ def _conv_signature(a):
             a.out_dtype, a.act, bool(a.res), bool(a.pre) + a.pre_mode, a.Cout2 if a.w2 else 0, 2 if a.x2 else bool(a.chain_keep))
 
 
+class _Layer:
+    """What the candidate rules ask of one conv (any object with ConvArgs' field names), derived once."""
+    def __init__(self, a):
+        self.same16 = a.dtype != F32 and a.out_dtype == a.dtype            # 16-bit in and out
+        self.pre, self.chain, self.tail, self.plain = bool(a.pre), bool(a.w2) and not a.x2, bool(a.w2) and bool(a.x2), not a.pre and not a.w2
+        self.taps128 = (a.Cin * 2) % 128 == 0                              # whole 128-byte K slices per filter tap (16-bit types)
+        self.s3 = a.sh if ((a.kh, a.kw, a.ph, a.pw) == (3, 3, 1, 1) and a.sh == a.sw) else 0      # 3x3 / pad 1 with stride s3 (0: another filter)
+        self.one = (a.kh, a.kw, a.sh, a.sw, a.ph, a.pw) == (1, 1, 1, 1, 0, 0)                     # plain 1x1
+        self.silu, self.pix = a.act == ACT_SILU, a.B * a.Ho * a.Wo
+        # the two families that read the fragment-major weight copy (icaf_conv_args.wf): offered once it exists, and it is built for them
+        self.wreg = self.same16 and self.taps128 and self.plain and a.Cout > 64 and OPT.wreg_gemm
+        self.cwide = _cwide_ids(self.s3, a.Cin, a.Cout) if (self.same16 and self.silu and not self.pre and OPT.cwide) else []
+
+
+def wants_wf(a):
+    """Does the layer get the fragment-major weight copy — is an igemm_wreg.hip or cwide.hip kernel built for it?"""
+    L = _Layer(a)
+    return bool(L.wreg or L.cwide)
+
+
 def conv_candidates(a):
-    """Launch-configuration ids worth timing for one conv (ConvArgs `a`): igemm tiles x pipelines, the 8-wavefront tiles,
-    the 3x3 halo-patch kernel; chained / pre-term launches only have the configurations that are built for them."""
-    cands = []
-    cs_ok = ((a.kh, a.kw, a.sh, a.sw, a.ph, a.pw) == (3, 3, 1, 1, 1, 1) and a.Cin == 64 and a.Cout <= 64 and a.Cout % 8 == 0 and a.dtype != F32
-             and a.out_dtype == a.dtype and a.act == ACT_SILU and not a.pre and OPT.cstream)
-    cw = (cwide_shapes(a.kh, a.kw, a.sh, a.sw, a.ph, a.pw, a.Cin, a.Cout)
-          if (a.dtype != F32 and a.wf and a.out_dtype == a.dtype and a.act == ACT_SILU and not a.pre and OPT.cwide) else [])
-    if a.w2 and a.x2:                  # C3 tail (the chained cv3 reads [tile | x2]): cwide.hip's 8 x 16 / 8 x 8 forms only
+    """Launch-configuration ids worth timing for one conv (ConvArgs `a`), each id's rule stated once, by kernel family; chained / pre-term
+    launches only have the configurations that are built for them.  Ids the library builds and no rule offers: BUILT_NOT_OFFERED."""
+    L = _Layer(a)
+    big1 = a.out_dtype != F32 and a.Cout > 64                              # the 128x128 tile: no fp32-output build, and 128x64 serves Cout <= 64
+    if L.tail:                         # C3 tail (the chained cv3 reads [tile | x2]): cwide.hip's 8 x 16 / 8 x 8 forms only
         # Below ~200 k pixels per stream (the 40 x 40 maps of yolov5s at batch 32 / 64: one round of 8 x 16 tiles for the chip) only the 8 x 8
         # form is offered: isolated timings prefer 8 x 16 there (2 workgroups of 252 registers and 70 KB per CU), but with a second forward in
         # flight that form starves the co-running kernels — same-box A/B of the whole bench: 15,858 with 8 x 16 against 16,082 without the tail and
         # 16,091 with 8 x 8 (3 workgroups of 168 registers and 35 KB).  The 80 x 80 / 160 x 160 maps of yolov5l have 4 - 16 x the tiles: tuned.
-        cands = ([82] if a.B * a.Ho * a.Wo < OPT.tail_8x16_minpix else [81, 82]) if OPT.cwide else []
-    elif a.w2:                         # chained 1x1: one N tile covering both layers, LDS-DMA pipelines 0 / 2
-        t = 2 if max(a.Cout, a.Cout2) <= 64 else 1
-        cands = [t, t + 20]
-        if cw and a.Cout == 128 and a.Cout2 <= 128 and a.Cout2 % 32 == 0:
-            cands += cw                                                      # resident halo patch, weights (and the chained 1x1's) streamed into registers (cwide.hip)
-        if cs_ok and a.Cout == 64 and a.Cout2 <= 64:
-            cands.append(71)                 # persistent 3x3 with the filter (and the chained 1x1) resident in LDS (cstream.hip)
-    elif a.pre:                          # pre-activation term: built for tiles 128x128 / 128x64 on the LDS-DMA pipelines 0 / 2
-        cands = [t + 10 * pipe for pipe in (0, 2) for t in (1, 2) if not (t == 1 and (a.out_dtype == F32 or a.Cout <= 64))]
-        if a.dtype != F32 and a.out_dtype == a.dtype and a.Cout >= 128 and (a.Cin * 2) % 128 == 0:
+        return ([82] if L.pix < OPT.tail_8x16_minpix else [81, 82]) if OPT.cwide else []
+    cands = []
+    # ---- igemm.hip: tile + 10 * pipeline (0: LDS-DMA 64 B x3, 1: register-staged, 2: LDS-DMA 128 B x2; 3 = 128 B x3 never won) ----
+    if L.chain:                        # chained 1x1: one N tile covering both layers, LDS-DMA pipelines 0 / 2
+        cands += [2, 22] if max(a.Cout, a.Cout2) <= 64 else [1, 21]
+    elif L.pre:                        # pre-activation term: built for tiles 128x128 / 128x64 on the LDS-DMA pipelines 0 / 2
+        cands += [t + 10 * pipe for pipe in (0, 2) for t in (1, 2) if t == 2 or big1]
+        if L.same16 and a.Cout >= 128 and L.taps128:
             cands.append(28)                 # the 8-wavefront 128x128 tile carries the pre term as well
-        if (a.dtype != F32 and a.out_dtype == a.dtype and (a.Cin * 2) % 128 == 0 and a.Cout % 8 == 0 and OPT.stream_gemm and a.act == ACT_SILU
-                and (a.kh, a.kw, a.sh, a.sw, a.ph, a.pw) == (1, 1, 1, 1, 0, 0) and a.groups == 1):
-            cands.append(52)                 # ... and so does the persistent streaming GEMM (1x1 SiLU layers)
-            if a.Cout > 64:
-                cands.append(51)
-    for pipe in (() if (a.pre or a.w2) else CONV_PIPELINES):
-        for t in (1, 2, 3, 4):
-            if t == 1 and (a.out_dtype == F32 or a.Cout <= 64):
-                continue
-            if t == 3 and a.Cout > 32:
-                continue
-            cands.append(t + 10 * pipe)
-    if a.dtype != F32 and a.out_dtype == a.dtype and not a.pre and not a.w2:            # 8-wavefront tiles (128-byte LDS-DMA pipeline only)
-        if a.Cout >= 128:
-            cands.append(25)
-            cands.append(28)
-        if a.Cout >= 256:
-            cands.append(26)
-    if (a.dtype != F32 and a.out_dtype == a.dtype and not a.pre and not a.w2 and (a.Cin * 2) % 128 == 0 and a.Cout % 8 == 0 and OPT.stream_gemm):
-        cands.append(52)                     # persistent streaming implicit GEMM (igemm_stream.hip): 128 x 64 tile ...
-        if a.Cout > 64:
-            cands.append(51)                 # ... and 128 x 128; a launch the shape rules out returns an error and is skipped
-    if cs_ok and not a.w2:
+    else:
+        cands += [t + 10 * pipe for pipe in (0, 1, 2) for t in (1, 2, 3, 4) if (t != 1 or big1) and (t != 3 or a.Cout <= 32)]
+        if L.same16 and a.Cout >= 128:       # 8-wavefront tiles (128-byte LDS-DMA pipeline only)
+            cands += [25, 28] + ([26] if a.Cout >= 256 else [])
+    # ---- igemm_stream.hip: persistent streaming GEMM, 128 x 64 (52) and 128 x 128 (51), also with the pre term of 1x1 SiLU layers; a launch
+    #      the device's CU count rules out returns an error and is skipped ----
+    if (L.same16 and L.taps128 and a.Cout % 8 == 0 and OPT.stream_gemm
+            and (L.plain or (L.pre and L.silu and L.one and a.groups == 1))):
+        cands += [52] + ([51] if a.Cout > 64 else [])
+    # ---- cstream.hip: persistent 3x3 with the filter (and a chained 1x1) resident in LDS, 64 -> (<= 64) channels ----
+    if (L.s3 == 1 and a.Cin == 64 and a.Cout <= 64 and a.Cout % 8 == 0 and L.same16 and L.silu and not L.pre and OPT.cstream
+            and (not L.chain or (a.Cout == 64 and a.Cout2 <= 64))):
         cands.append(71)
-    if cw and not a.w2:
-        cands += cw
-    if a.wf and OPT.wreg_gemm and not a.pre and not a.w2:
-        cands.append(61)                     # weights fed from registers (igemm_wreg.hip): 128 x 128 ...
+    # ---- cwide.hip: resident halo patch, weights (and the chained 1x1's) streamed into registers ----
+    if a.wf and (not L.chain or (a.Cout == 128 and a.Cout2 <= 128 and a.Cout2 % 32 == 0)):
+        cands += L.cwide
+    # ---- igemm_wreg.hip: weights fed from registers ----
+    if a.wf and L.wreg:
+        cands.append(61)                     # 128 x 128 ...
         if a.Cout > 128 and -(-a.Cout // 256) * 256 <= -(-a.Cout // 128) * 128:
             cands.append(62)                 # ... and 128 x 256 (its last channel tile must stay inside the packed Np = Cout rounded up to 128: wreg_check)
         # round 4: a wave owns 64 channels — the pixel feed per MAC halves
@@ -347,15 +343,20 @@ def conv_candidates(a):
             cands.append(64)                 # 128 x 256 with four waves: two workgroups per CU
         if a.Cout > 256 and a.Cout % 512 == 0 and a.act != ACT_GELU:
             cands.append(63)                 # 128 x 512 with eight waves
-        if a.B * a.Ho * a.Wo * a.groups <= OPT.wreg64_maxpix:  # few pixels (the 20 x 20 / 40 x 40 rows at batch 32): 64-pixel tiles double the workgroups
+        if L.pix * a.groups <= OPT.wreg64_maxpix:  # few pixels (the 20 x 20 / 40 x 40 rows at batch 32): 64-pixel tiles double the workgroups
             cands.append(66)                 # 64 x 128, four waves x 32 channels
             if a.Cout > 128 and a.Cout % 256 == 0:
                 cands.append(65)             # 64 x 256, four waves x 64 channels
-    if (a.kh, a.kw, a.ph, a.pw) == (3, 3, 1, 1) and a.act == ACT_SILU and a.out_dtype == a.dtype and not a.pre and not a.w2:
-        for shape, (bn, stride) in CTILE_SHAPES.items():       # 3x3 direct convolution from an LDS halo patch
-            if a.sh == stride and a.sw == stride and a.Cout <= bn and (bn < 64 or a.Cout > bn // 2):
-                cands.append(40 + shape)
+    # ---- ctile.hip: 3x3 direct convolution from an LDS halo patch ----
+    if L.s3 and L.silu and a.out_dtype == a.dtype and L.plain:
+        cands += [i for i, (bn, stride) in _CTILE.items() if L.s3 == stride and a.Cout <= bn and (bn < 64 or a.Cout > bn // 2)]
     return cands
+
+
+def graph_tune_extras(a):
+    """Built ids that only tools/graph_tune.py tries (against the whole graph's replay time): 29, for plain 16-bit layers wider than the 256x32 tile."""
+    L = _Layer(a)
+    return [29] if (L.same16 and L.plain and a.Cout > 32) else []
 
 
 def autotune_conv(launch, stream_ptr, reps=3, context=()):
@@ -416,19 +417,20 @@ def autotune_conv(launch, stream_ptr, reps=3, context=()):
     return best
 
 
-def tile_valid(launch, tile, cands=None):
-    """Is launch configuration `tile` usable for this recorded conv launch — a candidate for its arguments AND accepted by the
-    library's check of that configuration (icaf_conv2d_kernel_name runs the same *_check functions the launch runs)?"""
+def config_valid(launch, tile):
+    """The library's verdict alone: does launch configuration `tile` run this recorded conv launch?  icaf_conv2d_kernel_name resolves a
+    launch exactly as icaf_conv2d does (same table row, same check) and launches nothing."""
     a = launch.keep[0]
-    if tile not in (conv_candidates(a) if cands is None else cands):
-        return False
-    saved = a.tile
-    a.tile = tile
+    saved, a.tile = a.tile, tile
     try:
-        buf = C.create_string_buffer(256)
-        return lib().icaf_conv2d_kernel_name(launch.args[0], buf, 256) == 0
+        return lib().icaf_conv2d_kernel_name(launch.args[0], C.create_string_buffer(256), 256) == 0
     finally:
         a.tile = saved
+
+
+def tile_valid(launch, tile, cands=None):
+    """Is launch configuration `tile` usable for this recorded conv launch — a candidate for its arguments AND accepted by the library?"""
+    return tile in (conv_candidates(launch.keep[0]) if cands is None else cands) and config_valid(launch, tile)
 
 
 def save_tune_cache(path):
@@ -709,8 +711,6 @@ def dmff_wide_ln_qkv(x, qkv, packs, ln, coef, eps, B, N, heads, name="dmff_ln_qk
     es = x.element_size()
     return Launch(lib().icaf_dmff_wide_ln_qkv, (C.byref(a),), keep=(a, x, qkv, wp, packs, ln), name=name, flops=2.0 * 2 * rows * Cc * 3 * Cc,
                   nbytes=2 * (rows * Cc * es + 3 * Cc * Cc * es + rows * 3 * Cc * es))
-
-
 
 
 def dmff_wide_ksplit(N, C_, hidden):

@@ -130,9 +130,13 @@ typedef struct icaf_conv_args {
     int out_dtype; /* y: same as dtype, or ICAF_F32 */
     float alpha_acc[2];
     float alpha_res[2];
-    int tile; /* 0 = auto; otherwise force a launch configuration (tuning / tests; a configuration the layer does not satisfy is an error,
-               * never replaced silently).  1-4 (+10 / 20 / 30 per pipeline), 25 / 26 / 28 / 29: igemm.hip tiles; 40 + shape: ctile.hip;
-               * 51 / 52: igemm_stream.hip; 61 - 66: igemm_wreg.hip; 71: cstream.hip; 80 + shape (81 - 85): cwide.hip.
+    int tile; /* 0 = auto; otherwise force a launch configuration (tuning / tests).  An id that is not built is ICAF_ERR_ARG, a built one the
+               * layer does not satisfy ICAF_ERR_UNSUPPORTED: neither is ever replaced silently (one exception: tiles 1 - 4 of an LDS-DMA
+               * pipeline run on the register-staged one, id % 10 + 10, when an operand exceeds the 2 GiB buffer-descriptor range).
+               * The built ids (icaf_conv2d_config_ids), one family of kernels per row of igemm.hip's table:
+               *   igemm.hip         tile + 10 * pipeline: 1 - 4, 11 - 14, 21 - 26, 28, 29, 31 - 34
+               *   ctile.hip         41 - 45          igemm_stream.hip  51, 52          igemm_wreg.hip  61 - 66
+               *   cstream.hip       71               cwide.hip         81 - 85
                * Every configuration of a layer produces the same bits (same K order, MFMA step, epilogue expressions). */
     /* Optional pre-activation term, bilinearly resized (align_corners=False) from a coarse fp32 map:
      *   y = alpha_res*res + alpha_acc * act( A.W + bias + bilinear(pre)[b][ho][wo][n] )
@@ -201,6 +205,8 @@ typedef struct icaf_bneck_args {
 int icaf_bottleneck(const icaf_bneck_args* a, icaf_stream_t s);
 /* name of the kernel instantiation icaf_conv2d would launch for these args (host string, for profiling) */
 int icaf_conv2d_kernel_name(const icaf_conv_args* a, char* buf, int buf_len);
+/* the launch configuration ids that are built, ascending: writes the first `cap` of them to ids (may be NULL), returns how many there are */
+int icaf_conv2d_config_ids(int* ids, int cap);
 
 /* ---- SPPF / upsample / copy ------------------------------------------------------------------------------
  * icaf_sppf_pool: the three chained k x k stride-1 max pools of SPPF.forward (models/common.py:262-267);

@@ -14,6 +14,8 @@ for its store paths (y2, chain_keep) and is compared there with the two launches
 icaf_dmff_wide_proj_mlp has no observable output of its own and is not covered.
 
 Every test prints the largest err / budget it saw before it asserts (`-s`); docs/HISTORY.md section 17 records them."""
+import ctypes
+
 import pytest
 import torch
 
@@ -226,6 +228,52 @@ def test_pre_activation_term_on_lattice_data(name, dt):
     case.inputs_intact(name)
     print(f"\n[pre] {name} {DT_ID[dt]}: {seen} launches")
     assert not failures, f"{len(failures)} launches failed:\n" + "\n".join(failures[:12])
+
+
+def status_of_both_entry_points(launch, tile):
+    """(icaf_conv2d_kernel_name's status, icaf_conv2d's status) for launch configuration `tile`; the launch, if accepted, is enqueued."""
+    launch.keep[0].tile = tile
+    named = 0 if ops.config_valid(launch, tile) else 1
+    st = launch.fn(*launch.args, ops.current_stream_ptr())
+    return named, st
+
+
+SMALL_SHAPES = [n for n, sh in nm.EXACT_SHAPES.items() if not sh[8].get("only16")]
+TABLE_PARAMS = [pytest.param(n, dt, False, id=f"{n}-{DT_ID[dt]}") for n in SMALL_SHAPES for dt in DTYPES] + \
+               [pytest.param(n, dt, True, id=f"{n}-{DT_ID[dt]}") for n in nm.PRE_SHAPES for dt in DTYPES]
+
+
+@pytest.mark.parametrize("name,dt,pre", TABLE_PARAMS)
+def test_kernel_name_and_launch_agree_on_every_configuration(name, dt, pre):
+    """Every id of the library's table (icaf_conv2d_config_ids), offered by conv_candidates or not, on every small shape, with and without SiLU
+    and residual: icaf_conv2d_kernel_name accepts exactly what icaf_conv2d accepts; what is accepted returns the expected bits (ACT_NONE) or
+    stays within the counted budget (SiLU); what is rejected comes back from the host check and leaves the NaN-prefilled output unwritten."""
+    case = Case(name, dt, pre=pre)
+    ids = (ctypes.c_int * 64)()
+    ids = ids[:ops.lib().icaf_conv2d_config_ids(ids, 64)]
+    assert sorted(ids) == sorted(set().union(*REQUIRED.values()))
+    failures, ran, refused = [], 0, 0
+    for act in (ACT_NONE, ACT_SILU):
+        for use_res in (False, True):
+            for tile in ids:
+                what = f"{name} {DT_ID[dt]} {ACT_NAME[act]} res={int(use_res)} tile {tile}"
+                y = case.output(dt)
+                launch = case.launch(y, act, use_res, tile)
+                named, st = status_of_both_entry_points(launch, tile)
+                torch.cuda.synchronize()
+                try:
+                    assert (named == 0) == (st == 0), f"name call says {named}, launch says {st}"
+                    if st == 0:
+                        case.check(y, act, use_res, dt, what)
+                        ran += 1
+                    else:
+                        nm.assert_same_bits(y.buf, y.before, what + ": a rejected configuration must not write")
+                        refused += 1
+                except AssertionError as e:
+                    failures.append(f"{what}: {str(e)[:400]}")
+    case.inputs_intact(name)
+    print(f"\n[table] {name} {DT_ID[dt]}: {ran} launches checked, {refused} refused by both entry points")
+    assert ran > 0 and not failures, f"{len(failures)} of {ran + refused + len(failures)} cases failed:\n" + "\n".join(failures[:12])
 
 
 def test_every_built_configuration_was_reached():

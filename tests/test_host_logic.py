@@ -247,11 +247,10 @@ def test_committed_tune_caches_only_name_configurations_the_tuner_would_time():
     for f in files:
         for key, tile in json.load(open(f)):
             (M, cout, cin, kh, kw, sh, sw, H, W, ldx, ldy, groups, dtype, out_dtype, act, res, pre, cout2, chain_keep) = key
-            cw = act == ops.ACT_SILU and bool(ops.cwide_shapes(kh, kw, sh, sw, kh // 2, kw // 2, cin, cout))
-            wf = (dtype != ops.F32 and out_dtype == dtype and (cin * 2) % 128 == 0 and not pre and ((not cout2 and cout > 64) or cw))   # ops.conv2d's rule
             a = SimpleNamespace(Cout=cout, Cin=cin, kh=kh, kw=kw, sh=sh, sw=sw, ph=kh // 2, pw=kw // 2, dtype=dtype, out_dtype=out_dtype,
-                                act=act, pre=bool(pre), w2=bool(cout2), Cout2=cout2, res=bool(res), wf=wf, groups=groups, B=1, Ho=1, Wo=M,
+                                act=act, pre=bool(pre), w2=bool(cout2), Cout2=cout2, res=bool(res), groups=groups, B=1, Ho=1, Wo=M,
                                 x2=chain_keep == 2)        # (the last field is 2 for a C3 tail: ops._conv_signature)
+            a.wf = ops.wants_wf(a)                         # the fragment-major copy exists exactly where ops.conv2d builds it
             assert tile in ops.conv_candidates(a), (os.path.basename(f), key, tile)
             assert ldy >= cout and ldx >= cin and M > 0 and groups in (1, 2)
             n += 1
@@ -437,3 +436,78 @@ os.environ.update(RANK="0")
 x = os.environ.get("ICAF_LIB")
 '''
     assert dead_switch_writes("ok.py", ok, names) == []
+
+
+def _conv_args(cin, cout, dtype, out_dtype, k=1, tile=0):
+    """ConvArgs of a B = 1, 16 x 16, k x k / stride 1 layer over host memory: enough for everything icaf_conv2d checks before its first HIP call."""
+    import ctypes as C
+    a = _lib.ConvArgs()
+    buf = (C.c_char * 4096)()
+    a.x = a.w = a.y = (C.addressof(buf) + 15) & ~15
+    a.groups, a.B, a.H, a.W, a.Cin, a.ldx, a.Ho, a.Wo, a.Cout, a.ldy = 1, 1, 16, 16, cin, cin, 16, 16, cout, cout
+    a.kh = a.kw = k
+    a.sh = a.sw = 1
+    a.ph = a.pw = k // 2
+    a.Kp = -(-k * k * cin // 64) * 64
+    a.dtype, a.out_dtype, a.tile = dtype, out_dtype, tile
+    a.alpha_acc[0] = a.alpha_acc[1] = a.alpha_res[0] = a.alpha_res[1] = 1.0
+    return a, buf
+
+
+def _both_entry_points(a):
+    """((status, message) of icaf_conv2d_kernel_name, (status, message) of icaf_conv2d with a NULL stream, the kernel name)"""
+    import ctypes as C
+    l = _lib.lib()
+    name = C.create_string_buffer(256)
+    st_name = l.icaf_conv2d_kernel_name(C.byref(a), name, 256)
+    msg_name = l.icaf_last_error()
+    st_run = l.icaf_conv2d(C.byref(a), None)
+    return (st_name, msg_name), (st_run, l.icaf_last_error()), name.value.decode()
+
+
+ERR_ARG, ERR_UNSUPPORTED = -1, -3          # include/icaf.h
+
+
+@pytest.mark.parametrize("tile", [-1, 5, 7, 10, 20, 27, 30, 35, 40, 46, 53, 67, 72, 86, 90])
+def test_unknown_launch_configuration_is_an_argument_error(tile):
+    """icaf.h: a configuration that is not built is an error, never replaced silently — from both entry points, before any device call."""
+    a, _keep = _conv_args(64, 128, _lib.BF16, _lib.BF16, tile=tile)
+    named, ran, _ = _both_entry_points(a)
+    assert named[0] == ran[0] == ERR_ARG, (tile, named, ran)
+    assert named[1] == ran[1] and str(tile).encode() in named[1]
+
+
+@pytest.mark.parametrize("dtype,out_dtype,tile,why", [
+    (_lib.F32, _lib.F32, 25, b"16-bit types only"), (_lib.BF16, _lib.F32, 21, b"no fp32-output build"),
+    (_lib.F32, _lib.F32, 28, b"16-bit types only"), (_lib.BF16, _lib.F32, 25, b"16-bit types only")])
+def test_kernel_name_and_launch_reject_the_same_igemm_configurations(dtype, out_dtype, tile, why):
+    """igemm_check runs for both entry points: a tile that has no build for the layer's types is refused by the name call exactly as by the launch."""
+    a, _keep = _conv_args(64, 128, dtype, out_dtype, tile=tile)
+    named, ran, _ = _both_entry_points(a)
+    assert named[0] == ran[0] == ERR_UNSUPPORTED, (named, ran)
+    assert named[1] == ran[1] and why in named[1], (named, ran)
+
+
+def test_built_configuration_ids_are_the_required_ones():
+    """icaf_conv2d_config_ids() = the ids tests/test_gpu_exact.py requires to be reached = everything conv_candidates can offer plus the
+    ids it never offers (the sweep of tools/plan_fingerprint.py --candidates, at default options)."""
+    import ctypes as C
+    import json
+    import subprocess
+    import sys
+
+    from icafusion_amd import ops
+    src = open(os.path.join(REPO, "tests", "test_gpu_exact.py")).read()
+    required = ast.literal_eval(re.search(r"^REQUIRED = (\{.*?\})\n[A-Z]", src, re.S | re.M).group(1))
+    want = sorted(set().union(*required.values()))
+    n = _lib.lib().icaf_conv2d_config_ids(None, 0)
+    ids = (C.c_int * n)()
+    assert _lib.lib().icaf_conv2d_config_ids(ids, n) == n == 39 and list(ids) == want
+    short = (C.c_int * 3)()
+    assert _lib.lib().icaf_conv2d_config_ids(short, 3) == n and list(short) == want[:3]
+    sweep = subprocess.run([sys.executable, os.path.join(REPO, "tools", "plan_fingerprint.py"), REPO, "--candidates"], capture_output=True, text=True,
+                           env={k: v for k, v in os.environ.items() if k != "ICAF_OPTIONS"})
+    assert sweep.returncode == 0, sweep.stderr[-2000:]
+    offered = set(json.loads(sweep.stdout.splitlines()[-1].split(" ", 1)[1]))
+    assert not offered & set(ops.BUILT_NOT_OFFERED)
+    assert sorted(offered | set(ops.BUILT_NOT_OFFERED)) == want

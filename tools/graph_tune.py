@@ -76,7 +76,7 @@ order = sorted(groups.items(), key=lambda kv: -kv[1]["ms"])[:a.top]
 for sig, g in order:
     args0 = g["launches"][0].keep[0]
     cur = args0.tile
-    cands = [c for c in ops.conv_candidates(args0) + ([29] if (args0.Cout > 32 and args0.dtype != ops.F32 and not args0.w2 and not args0.pre and args0.out_dtype == args0.dtype) else []) if c != cur]
+    cands = [c for c in ops.conv_candidates(args0) + ops.graph_tune_extras(args0) if c != cur]
     best_c, best_t = cur, base
     for c in cands:
         for l in g["launches"]:

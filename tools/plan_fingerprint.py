@@ -1,12 +1,18 @@
 """Fingerprint of the execution plans a source tree builds: every launch with every argument, pointers replaced by what they point at.
 
     python tools/plan_fingerprint.py REPO_ROOT [--digest] [--only SUBSTRING]
+    python tools/plan_fingerprint.py REPO_ROOT --candidates
 
 imports icafusion_amd from REPO_ROOT (any checkout, e.g. a `git worktree` of another commit; ICAF_LIB may point it at a libicaf.so built
 elsewhere), builds each configuration of MATRIX on the CPU with seeded parameters and prints one JSON line per configuration (--digest: its
 name and the line's sha256 instead).  Plan-owned buffers are named buf<N> in allocation order, every other storage w<sha256 of its bytes>,
 so two trees print the same bytes exactly when they record the same launches over the same packed weights, however the tensors are
 shared or cached.  Host code only: no kernel runs and no GPU is needed.
+
+--candidates prints instead one digest over the tuner's rules: for every layer signature of a grid (and of every committed tune cache), the
+set of launch configurations ops.conv_candidates offers and whether ops.wants_wf builds the fragment-major weight copy: every signature
+without the copy, and once more with it where the rule builds it (the states a plan can be in).  A second line lists every id offered.
+ICAF_OPTIONS in the environment selects the switches, as everywhere.  A tree from before ops.wants_wf is read with the rule its conv2d carried.
 """
 import argparse
 import contextlib
@@ -22,6 +28,7 @@ ap = argparse.ArgumentParser()
 ap.add_argument("root")
 ap.add_argument("--digest", action="store_true", help="print '<configuration> <sha256 of its JSON line>' instead of the JSON")
 ap.add_argument("--only", default="", help="configurations whose name contains this")
+ap.add_argument("--candidates", action="store_true", help="digest of conv_candidates / wants_wf over a grid of layer signatures instead")
 a = ap.parse_args()
 ROOT = os.path.abspath(a.root)
 sys.path.insert(0, ROOT)
@@ -32,6 +39,52 @@ from icafusion_amd.models import common                         # noqa: E402
 from icafusion_amd.models.yolo import Model                     # noqa: E402
 
 assert os.path.abspath(engine.__file__).startswith(ROOT + os.sep), f"icafusion_amd came from {engine.__file__}, not from {ROOT}"
+
+
+def candidate_sweep():
+    import glob
+    import itertools
+    from types import SimpleNamespace
+
+    from icafusion_amd import ops
+    wants_wf = getattr(ops, "wants_wf", None)
+    if wants_wf is None:             # an older tree: conv2d decided inline (the packed Kp is always a multiple of 64 for the 16-bit types)
+        def wants_wf(a):
+            cw = ops.OPT.cwide and a.act == ops.ACT_SILU and ops.cwide_shapes(a.kh, a.kw, a.sh, a.sw, a.ph, a.pw, a.Cin, a.Cout)
+            return (a.dtype != ops.F32 and a.out_dtype == a.dtype and (a.Cin * 2) % 128 == 0 and not a.pre
+                    and ((ops.OPT.wreg_gemm and not a.w2 and a.Cout > 64) or bool(cw)))
+    chans = (8, 16, 32, 48, 64, 96, 128, 192, 256, 384, 512, 1024)
+    types = ((ops.F32, ops.F32), (ops.BF16, ops.BF16), (ops.F16, ops.F16), (ops.BF16, ops.F32))
+    forms = (("plain", 0), ("pre", 0), ("chain", 32), ("chain", 64), ("chain", 128), ("tail", 256))
+
+    def layer(cout, cin, k, s, dt, odt, act, res, pre, cout2, tail, groups, pix):
+        return SimpleNamespace(Cout=cout, Cin=cin, kh=k, kw=k, sh=s, sw=s, ph=k // 2, pw=k // 2, dtype=dt, out_dtype=odt, act=act, pre=bool(pre),
+                               w2=bool(cout2), Cout2=cout2, x2=tail, res=bool(res), groups=groups, B=1, Ho=1, Wo=pix)
+
+    layers = [layer(cout, cin, k, s, dt, odt, act, False, form == "pre", c2, form == "tail", 1, pix)
+              for cin, cout, (k, s), (dt, odt), act, pix, (form, c2) in itertools.product(
+                  chans, chans, ((1, 1), (3, 1), (3, 2), (6, 2)), types, (0, 1, 2), (6400, 51200, 204800, 819200), forms)]
+    ncache = 0
+    for f in sorted(glob.glob(os.path.join(ROOT, "profiles", "tune_cache*.json"))):
+        for (M, cout, cin, kh, kw, sh, sw, _, _, _, _, groups, dt, odt, act, res, pre, cout2, keep), _ in json.load(open(f)):
+            layers.append(layer(cout, cin, kh, sh, dt, odt, act, res, pre, cout2, keep == 2, groups, M))      # (keep == 2: ops._conv_signature)
+            ncache += 1
+    h, reached, n = hashlib.sha256(), set(), 0
+    for a in layers:
+        want = bool(wants_wf(a))
+        for a.wf in (False, True)[:1 + want]:
+            cands = sorted(set(ops.conv_candidates(a)))
+            reached.update(cands)
+            h.update(repr((sorted(vars(a).items()), cands, want)).encode())
+            n += 1
+    print(f"{len(layers)} layers ({ncache} from the tune caches), {n} signatures, {len(reached)} configurations offered", file=sys.stderr)
+    print(f"candidates {h.hexdigest()}")
+    print(f"offered {json.dumps(sorted(reached))}")
+
+
+if a.candidates:
+    candidate_sweep()
+    sys.exit(0)
 
 B, H, W = 2, 320, 352
 YAMLS = ["yolov5n_Transfusion_kaist.yaml", "yolov5s_Transfusion_kaist.yaml", "yolov5m_Transfusion_kaist.yaml", "yolov5l_Transfusion_VEDAI.yaml",
