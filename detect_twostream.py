@@ -8,7 +8,8 @@ image-folder path: `--source1` visible images, `--source2` infrared images, zipp
                                 deterministic synthetic weights so that the whole path can be exercised)
 
 Per pair: letterbox to --img-size (utils/datasets.py), uint8 -> device, one forward (hipGraph replay) + device NMS,
-boxes scaled back to the original image, optional YOLO-format txt / annotated images.  The per-frame
+boxes scaled back to the original image, optional YOLO-format txt / annotated images.  `--augment` runs the reference's test-time
+augmentation (three passes per pair, merged before NMS).  The per-frame
 `Done. (…s, …Hz)` and final `Average Speed` lines are the reference's (:160,198).  Webcam / video sources, the
 second-stage classifier and --view-img need OpenCV and are out of scope."""
 import argparse
@@ -54,8 +55,6 @@ def load_model(opt, device):
 
 @torch.no_grad()
 def detect(opt):
-    if getattr(opt, "augment", False):
-        raise NotImplementedError("test-time augmentation (models/yolo_test.py:116-132) is outside the inference hot path")
     device = select_device(opt.device)
     save_img = not opt.nosave
     save_dir = increment_path(Path(opt.project) / opt.name, exist_ok=opt.exist_ok)
@@ -70,7 +69,8 @@ def detect(opt):
     for (path, img, im0, _), (path2, img2, im0_, _) in zip(dataset, dataset2):
         img6 = torch.from_numpy(np.concatenate((img, img2), 0)).unsqueeze(0).to(device)     # uint8 (1, 6, H, W)
         t1 = time_synchronized()
-        pred = model.forward_u8(img6)[0]           # /255, RGB/IR split and the cast happen in the staging kernel
+        # /255, RGB/IR split and the cast happen in the staging kernel; --augment: the three passes of models/yolo_test.py:116-131
+        pred = (model.forward_u8(img6, augment=True) if getattr(opt, "augment", False) else model.forward_u8(img6))[0]
         pred = non_max_suppression(pred, opt.conf_thres, opt.iou_thres, classes=opt.classes, agnostic=opt.agnostic_nms)
         t2 = time_synchronized()
         det = pred[0]
@@ -127,7 +127,8 @@ def parse_opt(argv=None):
     ap.add_argument("--hide-labels", default=False, action="store_true")
     ap.add_argument("--hide-conf", default=True, action="store_true", help="accepted for the reference's command lines: its default is True and "
                     "cannot be switched off (:224), i.e. boxes carry the class name only — which is what is drawn here")
-    ap.add_argument("--augment", action="store_true", help="test-time augmentation: not built, raises")
+    ap.add_argument("--augment", action="store_true", help="test-time augmentation (models/yolo_test.py:116-131): scales 1 / 0.83 / 0.67, "
+                    "the 0.83 pass flipped left-right; needs --img-size >= 448")
     return ap.parse_args(argv)
 
 

@@ -69,6 +69,10 @@ class DmffArgs(C.Structure):
                 ("x32", C.c_void_p), ("y32", C.c_void_p)]          # fp32 residual stream across iterations (icaf.h)
 
 
+class TtaPass(C.Structure):
+    _fields_ = [("dst", C.c_void_p), ("Hr", C.c_int), ("Wr", C.c_int), ("Hp", C.c_int), ("Wp", C.c_int), ("flip", C.c_int), ("reserved", C.c_int)]
+
+
 _p, _i, _ll, _f, _sz = C.c_void_p, C.c_int, C.c_longlong, C.c_float, C.c_size_t
 # symbol -> (restype, argtypes); must list every function declared in include/icaf.h
 SIGNATURES = {
@@ -105,6 +109,8 @@ SIGNATURES = {
     "icaf_detect_decode": (_i, [_p, _i, _p, _p, _p, _i, _i, _i, _i, _i, _ll, _ll, _f, C.POINTER(_f), _p]),
     "icaf_detect_decode_kernel": (_i, [_p, _i, _p, _p, _i, _i, _i, _i, _i, C.POINTER(_i)]),
     "icaf_detect_conv": (_i, [C.POINTER(ConvArgs), _p, _p, _p, _i, _i, _ll, _ll, _f, C.POINTER(_f), _p]),
+    "icaf_tta_stage": (_i, [_p, _i, _i, _i, _i, _i, C.POINTER(TtaPass), _i, _p]),
+    "icaf_tta_merge": (_i, [C.POINTER(_p), C.POINTER(_ll), C.POINTER(_f), C.POINTER(_i), _i, _p, _i, _i, _f, _p]),
     "icaf_match_predictions": (_i, [_p, _p, _i, _i, _p, _p, _i, _p, _p, _i, _p, _p, _p]),
     "icaf_nms_workspace_bytes": (_i, [_i, _ll, _i, _i, C.POINTER(_sz)]),
     "icaf_nms": (_i, [_p, _i, _ll, _i, _f, _f, _i, _i, C.POINTER(_i), _i, _i, _i, _f, _p, _p, _p, _p, _sz, _p]),

@@ -32,6 +32,7 @@ class Plan:
         self.device, self.dtype = torch.device(device), dtype
         self.launches = []
         self.inputs = []        # static input tensors, filled by the caller before run()
+        self.input_pair = None  # Model plans with fp32 inputs: both of them as one (2, B, 3, H, W) tensor
         self.outputs = None
         self.graph = None
         self.nbytes = 0
@@ -156,6 +157,32 @@ class Plan:
         for i, l in enumerate(self.launches):
             out.append((l.name, evs[i].elapsed_ms(evs[i + 1]), l.flops, l.bytes))
         return out
+
+
+class TtaPlan:
+    """Test-time augmentation (reference models/yolo_test.py:116-131) as one replayable unit: the full-size plan, one ordinary plan per
+    scaled pass, the staging launch that resizes / flips / pads the full-size input into the scaled plans' inputs, and the merge launch
+    that de-scales, de-flips and concatenates the passes' decoded rows.  `inputs` are the full-size plan's inputs, `outputs` the merged
+    z (B, sum N_i, no).  A replay enqueues stage -> every plan (its own hipGraph when it has one) -> merge on the caller's stream and
+    allocates nothing.  The plans are held here, so the model's plan cache may drop them without freeing them."""
+
+    def __init__(self, plans, stage, merge, merged, passes):
+        self.plans, self.stage, self.merge = plans, stage, merge
+        self.inputs, self.outputs = plans[0].inputs, merged
+        self.passes = passes                                        # [(scale, flip, Hr, Wr, Hp, Wp)], full size first
+        self.device, self.dtype = plans[0].device, plans[0].dtype
+        self.nbytes = merged.numel() * merged.element_size()        # own buffers only: the plans are counted under their own keys
+
+    @property
+    def launches(self):
+        return [self.stage] + [l for p in self.plans for l in p.launches] + [self.merge]
+
+    def run(self, stream_ptr=None):
+        sp = stream_ptr if stream_ptr is not None else ops.current_stream_ptr()
+        self.stage(sp)
+        for p in self.plans:
+            p.run(sp)
+        self.merge(sp)
 
 
 def concat_view(xs):

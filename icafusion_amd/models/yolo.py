@@ -18,7 +18,7 @@ import torch
 import torch.nn as nn
 
 from .. import ops
-from ..engine import ImageIn, Plan
+from ..engine import ImageIn, Plan, TtaPlan
 from .common import (C3, SPPF, Add, Bottleneck, Concat, Conv, Detect, HipModule, NiNfusion,  # noqa: F401
                      TransformerFusionBlock, VirtualCat, emit_upsample)
 
@@ -29,6 +29,24 @@ _NAMESPACE = {"Conv": Conv, "C3": C3, "SPPF": SPPF, "Bottleneck": Bottleneck, "C
 
 def make_divisible(x, divisor):
     return math.ceil(x / divisor) * divisor
+
+
+# Test-time augmentation: the passes of the reference's Model.forward(augment=True) (models/yolo_test.py:118-119)
+TTA_SCALES = (1, 0.83, 0.67)
+TTA_FLIPS = (None, 3, None)            # 3 = left-right (x.flip(3)); the reference's set has no up-down flip
+
+
+def tta_sizes(H, W, gs=32):
+    """[(scale, flip, Hr, Wr, Hp, Wp)] of the passes for an H x W input: scale_img (utils/torch_utils.py:257-267) resizes to
+    (int(H * s), int(W * s)) and pads to the next multiple of gs of H * s / W * s, all in Python double arithmetic; ratio 1 returns the
+    input unchanged.  640 x 640: 531 -> 544 and 428 -> 448."""
+    out = []
+    for s, f in zip(TTA_SCALES, TTA_FLIPS):
+        if s == 1.0:
+            out.append((s, f, H, W, H, W))
+        else:
+            out.append((s, f, int(H * s), int(W * s), math.ceil(H * s / gs) * gs, math.ceil(W * s / gs) * gs))
+    return out
 
 
 def check_anchor_order(m):
@@ -208,9 +226,86 @@ class Model(HipModule):
 
     # -- reference API ----------------------------------------------------------------------------------------
     def forward(self, x, x2, augment=False, profile=False):
+        """augment=True: test-time augmentation, `(torch.cat(y, 1), None)` over the passes (scale, flip) = (1, -), (0.83, left-right),
+        (0.67, -) of the reference's models/yolo_test.py:116-131: each pass runs scale_img (utils/torch_utils.py:257-267) of the
+        (flipped) images through the plain forward, its boxes are divided by the scale and mirrored back, rows in pass order.  The
+        reference's own loop is broken for the two-stream model (:122-123 scale only `x` and call forward_once(xi) without the second
+        image: a TypeError); what it plainly means is built: the SAME flip and scale for both modalities.  Inputs whose 0.67 pass
+        would hand a DMFF block a map smaller than its anchor grid raise ValueError (tta_min_size)."""
         if augment:
-            raise NotImplementedError("test-time augmentation is outside the hot path (reference models/yolo_test.py:116-132)")
+            return self._forward_augment(x, x2)
         return self.forward_once(x, x2, profile)
+
+    def tta_min_size(self):
+        """Smallest (H, W) forward(augment=True) accepts, derived from the model: the positional embedding of a
+        TransformerFusionBlock has vert_anchors x horz_anchors rows (models/common.py:817-823), so the map it reads — the padded
+        size of the SMALLEST pass over the stride of the rows feeding it — must not be smaller than that grid."""
+        gs = int(self.stride.max())
+        probe = 32 * gs
+        shapes = self._layer_shapes(1, probe, probe)
+        need_h = need_w = gs
+        for m in self.model:
+            if isinstance(m, TransformerFusionBlock) and not isinstance(m.f, int):
+                _, h, w = shapes[m.f[0]]
+                need_h, need_w = max(need_h, m.vert_anchors * (probe // h)), max(need_w, m.horz_anchors * (probe // w))
+
+        def smallest(need):          # the smallest multiple of gs whose every pass is padded to at least `need`
+            v = gs
+            while min(p[4] for p in tta_sizes(v, v, gs)) < need:
+                v += gs
+            return v
+        return smallest(need_h), smallest(need_w)
+
+    def tta_plan_for(self, B, H, W, device="cuda", dtype=None, u8=False, slot=0, branches=True):
+        """The engine.TtaPlan of forward(augment=True) / forward_u8(augment=True) for this shape: the full-size plan (u8: fed by the
+        uint8 batch) and one ordinary fp32-input plan per scaled pass, all from plan_for — cached beside them under the same cap.
+        They ARE the cached plans of those shapes and slots (a plain forward at 544 x 544 replays the plan a 640 x 640 TTA step uses for
+        its 0.83 pass): as with plan_for, two users of one slot must not be in flight at the same time."""
+        gs = int(self.stride.max())
+        if H % gs or W % gs:
+            raise ValueError(f"input size {H}x{W} must be a multiple of the max stride {gs}")
+        min_h, min_w = self.tta_min_size()
+        if H < min_h or W < min_w:
+            raise ValueError(f"test-time augmentation needs an input of at least {min_h}x{min_w}, got {H}x{W}: the "
+                             f"{min(TTA_SCALES)} pass must not hand a DMFF block a map smaller than its anchor grid")
+        dt = dtype or self.compute_dtype or next(self.parameters()).dtype
+        device = torch.device(device)
+        if device.type == "cuda" and device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        key = (B, H, W, dt, device, "tta") + (("u8",) if u8 else ()) + (("slot", slot) if slot else ()) + (() if branches else ("chain",))
+        plans = self.__dict__.setdefault("_plans", {})
+        tp = plans.pop(key, None)
+        if tp is None:
+            passes = tta_sizes(H, W, gs)
+            subs = [self.plan_for(B, p[4], p[5], device, dt, u8=u8 and i == 0, slot=slot, branches=branches) for i, p in enumerate(passes)]
+            full = subs[0]
+            src = full.inputs[0] if u8 else full.input_pair
+            stage = ops.tta_stage(src, [(sp.input_pair, p[2], p[3], p[1] == 3) for sp, p in zip(subs[1:], passes[1:])])
+            zs = [sp.outputs[0] for sp in subs]
+            merged = torch.zeros((B, sum(z.shape[1] for z in zs), zs[0].shape[2]), dtype=torch.float32, device=device)
+            merge = ops.tta_merge(zs, [p[0] for p in passes], [p[1] == 3 for p in passes], merged, W)
+            tp = TtaPlan(subs, stage, merge, merged, passes)
+            plans = self.__dict__.setdefault("_plans", {})
+        plans[key] = tp
+        return tp
+
+    def _forward_augment(self, x, x2=None):
+        """x, x2: the fp image pair, or x alone: the uint8 (B, 6, H, W) batch."""
+        if self.training:
+            raise NotImplementedError("icafusion_amd implements the eval-mode inference path only (call .eval())")
+        u8 = x2 is None
+        if not (x.is_cuda and (u8 or x2.is_cuda)):
+            raise RuntimeError("icafusion_amd.Model runs on the MI355X only: move the model and inputs to cuda "
+                               "(no CPU fallback exists; the CPU reference is oracle/icaf_oracle.py, test-only)")
+        if not u8 and x.shape != x2.shape:
+            raise ValueError(f"RGB and IR batches must match, got {tuple(x.shape)} vs {tuple(x2.shape)}")
+        B, _, H, W = x.shape
+        tp = self.tta_plan_for(B, H, W, x.device, u8=u8)
+        for dst, t in zip(tp.inputs, (x,) if u8 else (x, x2)):
+            if t.data_ptr() != dst.data_ptr():
+                dst.copy_(t)
+        tp.run()
+        return (tp.outputs if self.static_outputs else tp.outputs.clone()), None
 
     def fuse(self):
         """Fold BatchNorm into the convs in place (reference models/yolo_test.py:182-190)."""
@@ -290,11 +385,11 @@ class Model(HipModule):
         plan = Plan(device, dtype)
         if u8:
             img6 = torch.zeros((B, 6, H, W), dtype=torch.uint8, device=device)
-            plan.inputs = [img6]
+            plan.inputs, plan.input_pair = [img6], None
             in_pair, in_rgb, in_ir = ImageIn(img6, 0, pair=True), ImageIn(img6, 0), ImageIn(img6, 3)
         else:
             imgs = torch.zeros((2, B, 3, H, W), dtype=torch.float32, device=device)   # RGB and IR staging, adjacent
-            plan.inputs = [imgs[0], imgs[1]]
+            plan.inputs, plan.input_pair = [imgs[0], imgs[1]], imgs     # input_pair: both as one (2, B, 3, H, W) tensor
             in_pair, in_rgb, in_ir = ImageIn(imgs), ImageIn(imgs[0]), ImageIn(imgs[1])
         shapes = self._layer_shapes(B, H, W)
         # nn.Upsample -> Concat([-1, j]) -> C3 (head rows 24-26, 28-30): the C3's first 1x1 commutes with the nearest
@@ -482,14 +577,17 @@ class Model(HipModule):
             return z, logits, raws
         return z.clone(), logits.clone(), [r.clone() for r in raws]
 
-    def forward_u8(self, img6):
+    def forward_u8(self, img6, augment=False):
         """Forward from the dataloader's uint8 (B, 6, H, W) RGB+IR batch (reference test.py:116-128 does
         `.to(device).float() / 255`, splits `[:, :3]` / `[:, 3:]`, then `model(img_rgb, img_ir)`): same outputs as
-        forward(), one quarter of the input bytes, no fp32 image ever materialised."""
+        forward(), one quarter of the input bytes, no fp32 image ever materialised.  augment=True: as forward(augment=True),
+        the scaled passes staged straight from the uint8 batch."""
         if self.training:
             raise NotImplementedError("icafusion_amd implements the eval-mode inference path only (call .eval())")
         if not img6.is_cuda or img6.dtype != torch.uint8 or img6.dim() != 4 or img6.shape[1] != 6:
             raise ValueError("forward_u8 expects a cuda uint8 tensor of shape (B, 6, H, W)")
+        if augment:
+            return self._forward_augment(img6)
         B, _, H, W = img6.shape
         if H % 32 or W % 32:
             raise ValueError(f"input size {H}x{W} must be a multiple of the max stride 32")

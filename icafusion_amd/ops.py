@@ -819,6 +819,37 @@ def detect_conv(x, w_packed, kp, bias, z, logits, raw, na, no, row_offset, strid
                   flops=2.0 * m * na * no * cin, nbytes=nb)
 
 
+def tta_stage(src, passes, name="tta_stage"):
+    """scale_img of both modalities for every scaled pass of test-time augmentation in one launch (icaf_tta_stage).  src: the
+    full-size fp32 (2, B, 3, H, W) staging pair or the uint8 (B, 6, H, W) batch; passes: [(dst, Hr, Wr, flip)] with dst the fp32
+    (2, B, 3, Hp, Wp) staging pair of the pass's plan."""
+    u8 = src.dtype == torch.uint8
+    assert src.is_contiguous() and (src.dim() == 4 and src.shape[1] >= 6 if u8 else src.dtype == torch.float32 and src.dim() == 5 and src.shape[0] == 2)
+    B, _, H, W = src.shape[-4:]
+    arr = (_lib.TtaPass * len(passes))()
+    nb = 2 * B * 3 * H * W * (1 if u8 else 4)                  # algorithmic bytes: the source once, every output once
+    for p, (dst, hr, wr, flip) in zip(arr, passes):
+        assert dst.dtype == torch.float32 and dst.is_contiguous() and dst.dim() == 5 and dst.shape[:3] == (2, B, 3)
+        p.dst, p.Hr, p.Wr, p.Hp, p.Wp, p.flip = dst.data_ptr(), hr, wr, dst.shape[3], dst.shape[4], int(bool(flip))
+        nb += dst.numel() * 4
+    return Launch(lib().icaf_tta_stage, (src.data_ptr(), int(u8), src.shape[1] if u8 else 3, B, H, W, arr, len(passes)),
+                  keep=(src, arr, [p[0] for p in passes]), name=name, nbytes=nb)
+
+
+def tta_merge(zs, scales, flips, out, width, name="tta_merge"):
+    """De-scale, de-flip and concatenate the passes' decoded rows (icaf_tta_merge): zs[i] (B, N_i, no) fp32 -> out (B, sum N_i, no)."""
+    B, _, no = out.shape
+    n = len(zs)
+    assert out.dtype == torch.float32 and out.is_contiguous() and sum(z.shape[1] for z in zs) == out.shape[1]
+    assert all(z.dtype == torch.float32 and z.is_contiguous() and z.shape[0] == B and z.shape[2] == no for z in zs)
+    ptrs = (C.c_void_p * n)(*[z.data_ptr() for z in zs])
+    rows = (C.c_longlong * n)(*[z.shape[1] for z in zs])
+    sc = (C.c_float * n)(*[float(s) for s in scales])
+    fl = (C.c_int * n)(*[int(bool(f)) for f in flips])
+    return Launch(lib().icaf_tta_merge, (ptrs, rows, sc, fl, n, out.data_ptr(), B, no, float(width)),
+                  keep=(zs, out, ptrs, rows, sc, fl), name=name, nbytes=2 * out.numel() * 4)
+
+
 class NmsRunner:
     """Pre-allocated NMS launch for a fixed (B, rows, nc) — graph-capturable; results stay on the device."""
 

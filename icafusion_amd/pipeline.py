@@ -45,12 +45,14 @@ HOST_FED_BRANCHES = OPT.pipe_branches             # keep the hipGraph's parallel
 
 class DetectionPipeline:
     def __init__(self, model, batch, height, width, device, conf_thres=0.25, iou_thres=0.45, classes=None,
-                 agnostic=False, multi_label=False, max_det=300, world=1, overlap=True, force_gather=False, depth=1, u8=False):
-        """u8=True: the plans take the dataloader's uint8 (B, 6, H, W) RGB+IR batch (Model.forward_u8: `/255`, split and cast in the
+                 agnostic=False, multi_label=False, max_det=300, world=1, overlap=True, force_gather=False, depth=1, u8=False, augment=False):
+        """augment=True: every step is a test-time-augmentation step (Model.forward(augment=True), reference models/yolo_test.py:116-131:
+        the plans are engine.TtaPlan objects) and NMS runs over the merged rows of the three passes (55,755 per image at 640 x 640).
+        u8=True: the plans take the dataloader's uint8 (B, 6, H, W) RGB+IR batch (Model.forward_u8: `/255`, split and cast in the
         staging kernel, reference test.py:116-123) — `submit_u8` then feeds them from (pinned) host memory with the H2D copy on its own
         stream, overlapped with the forwards in flight."""
         self.model, self.device, self.world = model, torch.device(device), world
-        self.u8 = bool(u8)
+        self.u8, self.augment = bool(u8), bool(augment)
         self.gather = world > 1 or bool(force_gather)       # force_gather: run the all-gather even with one rank (hardware test of the RCCL path)
         self.nms_args = dict(conf_thres=conf_thres, iou_thres=iou_thres, classes=classes, agnostic=agnostic,
                              multi_label=multi_label, max_det=max_det)
@@ -69,7 +71,8 @@ class DetectionPipeline:
         # (host-fed: chain graphs.  A graph with parallel branches replays them on streams of its own, which share hardware queues with the copy
         #  and NMS streams: same box, one process each, 13,578 pairs/s with the branches, 15,153 without, 15,172 with no graph at all — and
         #  16,100-16,500 with the inputs resident, where the branches are worth 3 %)
-        self.plans = [model.plan_for(batch, height, width, self.device, u8=self.u8, slot=s, branches=HOST_FED_BRANCHES or not (self.u8 and overlap))
+        plan_for = model.tta_plan_for if self.augment else model.plan_for
+        self.plans = [plan_for(batch, height, width, self.device, u8=self.u8, slot=s, branches=HOST_FED_BRANCHES or not (self.u8 and overlap))
                       for s in range(self.nplans)]
         # (a HIGH-PRIORITY stream: HIP maps the streams of a process onto a few hardware queues, and a copy stream that shares its queue with
         #  a forward stream waits behind that stream's graph — the copies then do not overlap the forwards at all; priority streams get
@@ -78,7 +81,7 @@ class DetectionPipeline:
         self.copy_stream = self.copy_streams[0] if self.u8 else None
         self.copied = [[torch.cuda.Event() for _ in self.copy_streams] for _ in self.plans]
         self.plan = self.plans[0]
-        self.z = self.plan.outputs[0]
+        self.z = self._z(self.plan)
         # `depth` forward streams; plan p always replays on stream p % depth (alternating a graph between two streams cost the host-fed loop a
         # third of its rate), so at most `depth` forwards run at once by construction
         self.fwd_streams = [torch.cuda.Stream(device=self.device) for _ in range(self.depth)]
@@ -114,6 +117,10 @@ class DetectionPipeline:
         self.gen, self.pending, self.gathers = 0, 0, 0               # generation the NEXT gather writes; steps since the last gather; gathers issued
         self.n = 0
         self.last = None
+
+    def _z(self, plan):
+        """The decoded rows NMS reads: a TtaPlan's output IS the merged z, a plain plan's is (z, logits, raws)."""
+        return plan.outputs if self.augment else plan.outputs[0]
 
     @property
     def inputs(self):
@@ -232,7 +239,7 @@ class DetectionPipeline:
         ns.wait_event(self.fwd_done[pi])
         if self.gather and self.gathers and self.pending == 0:
             ns.wait_event(self.gather_done)                # the last gather has read the blocks this group's NMS launches overwrite
-        det, count, keep = nms_device(plan.outputs[0], stream_ptr=ns.cuda_stream, runner=self.deep_runners[pi], **self.nms_args)
+        det, count, keep = nms_device(self._z(plan), stream_ptr=ns.cuda_stream, runner=self.deep_runners[pi], **self.nms_args)
         out = (det[None], count[None])
         if self.gather:
             out = self._gather(self.group_block, pi)

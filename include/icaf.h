@@ -336,6 +336,37 @@ int icaf_dmff_wide_proj_mlp_split(const icaf_dmff_args* a, const void* att, floa
 int icaf_dmff_wide_reduce(const icaf_dmff_args* a, const float* partial, int ksplit, icaf_stream_t s);
 int icaf_dmff_attn_mlp_lds_bytes(int C, int N, int heads, int dtype, size_t* bytes);
 
+/* ---- test-time augmentation (models/yolo_test.py:116-131, utils/torch_utils.py:257-267) ---------------------
+ * Model.forward(augment=True) runs three passes, (scale, flip) = (1, -), (0.83, left-right), (0.67, -), and concatenates their decoded
+ * rows.  The reference's loop scales only `x` and calls forward_once(xi) without the second image (:122-123, a TypeError for the
+ * two-stream model); built here is what it plainly means: the SAME flip and scale for both modalities.
+ *
+ * icaf_tta_stage: scale_img (utils/torch_utils.py:257-267) of `x.flip(3) if flip else x` for both modalities and up to
+ *   ICAF_TTA_MAX_PASSES scaled passes in ONE launch: F.interpolate(size = (Hr, Wr), 'bilinear', align_corners=False) followed by
+ *   F.pad(right, bottom, value = 0.447) up to (Hp, Wp), written as the fp32 NCHW [2][B][3][Hp][Wp] input of the pass's plan.
+ *   src: fp32 [2][B][3][H][W] (both modalities adjacent), or src_u8 != 0: the dataloader's uint8 [B][ctot][H][W] batch, modality m =
+ *   channels [3m, 3m + 3), value = (float)u8 / 255.0f exactly as icaf_preprocess_u8 (the result equals staging from u8.float() / 255
+ *   bit for bit).  Arithmetic of torch's CPU kernel, all fp32: scale = (float)in / (float)out, src = fmaf(scale, d + 0.5f, -0.5f)
+ *   clamped below at 0, i0 = min((int)src, in - 1), i1 = min(i0 + 1, in - 1), l1 = src - i0, l0 = 1 - l1,
+ *   v = ly0 * (lx0 * a00 + lx1 * a01) + ly1 * (lx0 * a10 + lx1 * a11), no contraction; the flip is folded into the source column.
+ *   Wp % 4 == 0 and 16-byte aligned dst (one 16-byte store per thread and row); Hr <= Hp, Wr <= Wp.
+ * icaf_tta_merge: the de-scale / de-flip and torch.cat(y, 1) of :125-131.  z[i]: [B][rows[i]][no] fp32 (the pass's decoded rows),
+ *   out: [B][sum rows][no]; out[..., :4] = z / scale[i] (a correctly rounded fp32 division, as torch's `/=`: never a reciprocal
+ *   multiply), then for flip[i] != 0 out[..., 0] = width - out[..., 0]; columns >= 4 are copied.  z / rows / scale / flip are HOST arrays
+ *   of npass <= ICAF_TTA_MAX_PASSES + 1 entries (z[i] device pointers). */
+enum { ICAF_TTA_MAX_PASSES = 3 };
+typedef struct icaf_tta_pass {
+    float* dst;        /* [2][B][3][Hp][Wp] fp32 */
+    int Hr, Wr;        /* resized size: (int)(H * ratio), (int)(W * ratio) */
+    int Hp, Wp;        /* padded size: ceil(H * ratio / gs) * gs, ceil(W * ratio / gs) * gs */
+    int flip;          /* != 0: x.flip(3) before the resize */
+    int reserved;
+} icaf_tta_pass;
+int icaf_tta_stage(const void* src, int src_u8, int ctot, int B, int H, int W, const icaf_tta_pass* passes, int npass,
+                   icaf_stream_t s);
+int icaf_tta_merge(const float* const* z, const long long* rows, const float* scale, const int* flip, int npass, float* out,
+                   int B, int no, float width, icaf_stream_t s);
+
 /* ---- NMS (utils/general.py:518-607 + torchvision.ops.nms semantics) ----------------------------------------
  * pred: [B][rows][5+nc] fp32 (cx, cy, w, h, obj, cls...).  Per image: obj > conf filter, conf = obj*cls, best
  * class or multi-label expansion, optional class filter (host int array), top max_nms by score (stable),
