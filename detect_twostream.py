@@ -9,7 +9,8 @@ image-folder path: `--source1` visible images, `--source2` infrared images, zipp
 
 Per pair: letterbox to --img-size (utils/datasets.py), uint8 -> device, one forward (hipGraph replay) + device NMS,
 boxes scaled back to the original image, optional YOLO-format txt / annotated images.  `--augment` runs the reference's test-time
-augmentation (three passes per pair, merged before NMS).  The per-frame
+augmentation (three passes per pair, merged before NMS).  `--device-letterbox` hands the decoded frames over as they are: the letterbox and the
+mapping of the boxes back to the image then run on the device (Model.forward_frames, ops.scale_detections), same outputs.  The per-frame
 `Done. (…s, …Hz)` and final `Average Speed` lines are the reference's (:160,198).  Webcam / video sources, the
 second-stage classifier and --view-img need OpenCV and are out of scope."""
 import argparse
@@ -19,6 +20,7 @@ from pathlib import Path
 import numpy as np
 import torch
 
+from icafusion_amd import ops
 from icafusion_amd.models.experimental import attempt_load
 from icafusion_amd.models.yolo import Model
 from icafusion_amd.utils.datasets import LoadImages, imwrite_bgr
@@ -62,22 +64,38 @@ def detect(opt):
     model = load_model(opt, device)
     stride = int(model.stride.max())
     names = model.names
-    dataset, dataset2 = LoadImages(opt.source1, opt.img_size, stride), LoadImages(opt.source2, opt.img_size, stride)
+    on_device = bool(getattr(opt, "device_letterbox", False))      # native frames in, native boxes out: no host letterbox / scale_coords
+    dataset, dataset2 = (LoadImages(src, opt.img_size, stride, native=on_device) for src in (opt.source1, opt.source2))
     if len(dataset) != len(dataset2):
         raise ValueError(f"{len(dataset)} visible images vs {len(dataset2)} infrared images")
     t0, img_num, fps_sum = time.time(), 0, 0.0
     for (path, img, im0, _), (path2, img2, im0_, _) in zip(dataset, dataset2):
-        img6 = torch.from_numpy(np.concatenate((img, img2), 0)).unsqueeze(0).to(device)     # uint8 (1, 6, H, W)
+        if on_device:
+            frames = [torch.from_numpy(x).unsqueeze(0).to(device) for x in (im0, im0_)]      # uint8 (1, H0, W0, 3) BGR, as decoded
+            net_shape = (opt.img_size, opt.img_size)
+        else:
+            img6 = torch.from_numpy(np.concatenate((img, img2), 0)).unsqueeze(0).to(device)     # uint8 (1, 6, H, W)
+            net_shape = tuple(img6.shape[2:])
         t1 = time_synchronized()
         # /255, RGB/IR split and the cast happen in the staging kernel; --augment: the three passes of models/yolo_test.py:116-131
-        pred = (model.forward_u8(img6, augment=True) if getattr(opt, "augment", False) else model.forward_u8(img6))[0]
+        if on_device:
+            out, geometry = model.forward_frames(frames[0], frames[1], opt.img_size, bgr=True, augment=getattr(opt, "augment", False))
+            pred = out[0]
+        else:
+            pred = (model.forward_u8(img6, augment=True) if getattr(opt, "augment", False) else model.forward_u8(img6))[0]
         pred = non_max_suppression(pred, opt.conf_thres, opt.iou_thres, classes=opt.classes, agnostic=opt.agnostic_nms)
         t2 = time_synchronized()
         det = pred[0]
         p = Path(path)
-        s = "%gx%g " % tuple(img6.shape[2:])
+        s = "%gx%g " % net_shape
+        if len(det) and on_device:
+            block = det.unsqueeze(0).contiguous()
+            ops.scale_detections(block, torch.tensor([len(det)], dtype=torch.int32, device=det.device), geometry.scale,
+                                 round=True)(ops.current_stream_ptr())
+            det = block[0]
         if len(det):
-            det[:, :4] = scale_coords(img6.shape[2:], det[:, :4], im0.shape).round()
+            if not on_device:
+                det[:, :4] = scale_coords(img6.shape[2:], det[:, :4], im0.shape).round()
             for c in det[:, -1].unique():
                 n = int((det[:, -1] == c).sum())
                 s += f"{n} {names[int(c)]}{'s' * (n > 1)}, "
@@ -129,6 +147,8 @@ def parse_opt(argv=None):
                     "cannot be switched off (:224), i.e. boxes carry the class name only — which is what is drawn here")
     ap.add_argument("--augment", action="store_true", help="test-time augmentation (models/yolo_test.py:116-131): scales 1 / 0.83 / 0.67, "
                     "the 0.83 pass flipped left-right; needs --img-size >= 448")
+    ap.add_argument("--device-letterbox", action="store_true", help="hand the native frames to the device: letterbox and the mapping of the "
+                    "boxes back to the image run as HIP kernels (Model.forward_frames, ops.scale_detections) instead of numpy / torch on the host")
     return ap.parse_args(argv)
 
 

@@ -73,6 +73,14 @@ class TtaPass(C.Structure):
     _fields_ = [("dst", C.c_void_p), ("Hr", C.c_int), ("Wr", C.c_int), ("Hp", C.c_int), ("Wp", C.c_int), ("flip", C.c_int), ("reserved", C.c_int)]
 
 
+class FrameGeom(C.Structure):
+    _fields_ = [("offset", C.c_longlong), ("h0", C.c_int), ("w0", C.c_int), ("pitch", C.c_int), ("ch", C.c_int), ("nh", C.c_int), ("nw", C.c_int),
+                ("top", C.c_int), ("left", C.c_int), ("sx", C.c_float), ("sy", C.c_float)]
+
+
+LETTERBOX_LDS_BYTES = 20480                 # ICAF_LETTERBOX_LDS_BYTES (icaf.h): the staging budget of one letterbox workgroup
+
+
 _p, _i, _ll, _f, _sz = C.c_void_p, C.c_int, C.c_longlong, C.c_float, C.c_size_t
 # symbol -> (restype, argtypes); must list every function declared in include/icaf.h
 SIGNATURES = {
@@ -111,6 +119,8 @@ SIGNATURES = {
     "icaf_detect_conv": (_i, [C.POINTER(ConvArgs), _p, _p, _p, _i, _i, _ll, _ll, _f, C.POINTER(_f), _p]),
     "icaf_tta_stage": (_i, [_p, _i, _i, _i, _i, _i, C.POINTER(TtaPass), _i, _p]),
     "icaf_tta_merge": (_i, [C.POINTER(_p), C.POINTER(_ll), C.POINTER(_f), C.POINTER(_i), _i, _p, _i, _i, _f, _p]),
+    "icaf_letterbox_frames": (_i, [_p, _p, _i, _i, _p, _i, _i, _i, _i, _p]),
+    "icaf_scale_detections": (_i, [_p, _p, _i, _i, _p, _i, _p, _p]),
     "icaf_match_predictions": (_i, [_p, _p, _i, _i, _p, _p, _i, _p, _p, _i, _p, _p, _p]),
     "icaf_nms_workspace_bytes": (_i, [_i, _ll, _i, _i, C.POINTER(_sz)]),
     "icaf_nms": (_i, [_p, _i, _ll, _i, _f, _f, _i, _i, C.POINTER(_i), _i, _i, _i, _f, _p, _p, _p, _p, _sz, _p]),

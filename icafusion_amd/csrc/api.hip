@@ -30,7 +30,8 @@ extern "C" int icaf_set_option(const char* name, int value) {
     if (!strcmp(name, "detect_elementwise")) g_opt.detect_elementwise = value;
     else if (!strcmp(name, "attn_qsplit")) g_opt.attn_qsplit = value;
     else if (!strcmp(name, "sppf_vpb")) g_opt.sppf_vpb = value;
-    else return fail(ICAF_ERR_ARG, "icaf_set_option: unknown option '%s' (detect_elementwise, attn_qsplit, sppf_vpb)", name);
+    else if (!strcmp(name, "letterbox_direct")) g_opt.letterbox_direct = value;
+    else return fail(ICAF_ERR_ARG, "icaf_set_option: unknown option '%s' (detect_elementwise, attn_qsplit, sppf_vpb, letterbox_direct)", name);
     return ICAF_OK;
 }
 extern "C" int icaf_version(void) { return 100; }

@@ -546,6 +546,31 @@ static int nms_layout(int B, long long rows, int nc, int multi, void* base, NmsW
 // bit-identical to the numpy statement of the same formula (icafusion_amd/utils/metrics.py, the test oracle).
 constexpr int MATCH_MAX_DET = 1024, MATCH_MAX_LABELS = 2048;
 
+// scale_coords + clip_coords (utils/general.py:386-407) of one xyxy box, sc = {gain, pad_x, pad_y, w0, h0}: THE expression of the mapping,
+// shared by match_predictions_kernel and scale_detections_kernel (tests/golden/match_predictions.npz, made by the reference, guards both)
+__device__ __forceinline__ void native_box(const float* __restrict__ sc, float& x1, float& y1, float& x2, float& y2) {
+    const float gain = sc[0], padx = sc[1], pady = sc[2], w0 = sc[3], h0 = sc[4];
+    x1 = (x1 - padx) / gain; x2 = (x2 - padx) / gain; y1 = (y1 - pady) / gain; y2 = (y2 - pady) / gain;
+    x1 = fminf(fmaxf(x1, 0.0f), w0); x2 = fminf(fmaxf(x2, 0.0f), w0);
+    y1 = fminf(fmaxf(y1, 0.0f), h0); y2 = fminf(fmaxf(y2, 0.0f), h0);
+}
+
+// det [B][max_det][6] -> out (may alias det: a thread reads its row before it writes it): rows < count[b] mapped to the native image,
+// optionally rounded half-to-even (torch.round, detect_twostream.py:80), conf / cls copied; rows >= count[b] zeroed
+__global__ __launch_bounds__(256) void scale_detections_kernel(const float* det, const int* __restrict__ count, int max_det,
+                                                               const float* __restrict__ scale, int round, float* out) {
+    const int b = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= max_det) return;
+    const long long row = ((long long)b * max_det + i) * 6;
+    float x1 = 0.0f, y1 = 0.0f, x2 = 0.0f, y2 = 0.0f, conf = 0.0f, cls = 0.0f;
+    if (i < count[b]) {
+        x1 = det[row]; y1 = det[row + 1]; x2 = det[row + 2]; y2 = det[row + 3]; conf = det[row + 4]; cls = det[row + 5];
+        native_box(scale + b * 5, x1, y1, x2, y2);
+        if (round) { x1 = rintf(x1); y1 = rintf(y1); x2 = rintf(x2); y2 = rintf(y2); }
+    }
+    out[row] = x1; out[row + 1] = y1; out[row + 2] = x2; out[row + 3] = y2; out[row + 4] = conf; out[row + 5] = cls;
+}
+
 __global__ __launch_bounds__(256) void match_predictions_kernel(const float* __restrict__ det, const int* __restrict__ count, int max_det,
                                                                 const float* __restrict__ labels, const int* __restrict__ label_off,
                                                                 const float* __restrict__ scale, const float* __restrict__ iouv, int T,
@@ -556,17 +581,11 @@ __global__ __launch_bounds__(256) void match_predictions_kernel(const float* __r
     const int b = blockIdx.x, tid = threadIdx.x;
     const int n = min(count[b], max_det), l0 = label_off[b], nl = label_off[b + 1] - l0;
     const float* db = det + (long long)b * max_det * 6;
-    float gain = 1.0f, padx = 0.0f, pady = 0.0f, w0 = 3.0e38f, h0 = 3.0e38f;
-    if (scale) { gain = scale[b * 5]; padx = scale[b * 5 + 1]; pady = scale[b * 5 + 2]; w0 = scale[b * 5 + 3]; h0 = scale[b * 5 + 4]; }
     for (int i = tid; i < nl; i += 256) claimed[i] = 0;
     for (int i = tid; i < n; i += 256) {
         float x1 = db[i * 6], y1 = db[i * 6 + 1], x2 = db[i * 6 + 2], y2 = db[i * 6 + 3];
         const float cls = db[i * 6 + 5];
-        if (scale) {
-            x1 = (x1 - padx) / gain; x2 = (x2 - padx) / gain; y1 = (y1 - pady) / gain; y2 = (y2 - pady) / gain;
-            x1 = fminf(fmaxf(x1, 0.0f), w0); x2 = fminf(fmaxf(x2, 0.0f), w0);
-            y1 = fminf(fmaxf(y1, 0.0f), h0); y2 = fminf(fmaxf(y2, 0.0f), h0);
-        }
+        if (scale) native_box(scale + b * 5, x1, y1, x2, y2);
         if (predn) {
             float* o = predn + ((long long)b * max_det + i) * 4;
             o[0] = x1; o[1] = y1; o[2] = x2; o[3] = y2;
@@ -668,6 +687,15 @@ extern "C" int icaf_match_predictions(const float* det, const int* count, int B,
     if (max_labels_per_image > MATCH_MAX_LABELS) return fail(ICAF_ERR_UNSUPPORTED, "icaf_match_predictions: at most %d labels per image", MATCH_MAX_LABELS);
     if (max_labels_per_image > 0 && !labels) return fail(ICAF_ERR_ARG, "icaf_match_predictions: labels missing");
     match_predictions_kernel<<<dim3((unsigned)B), dim3(256), 0, S(s)>>>(det, count, max_det, labels, label_off, scale, iouv, T, correct, predn);
+    ICAF_LAUNCH_CHECK();
+    return ICAF_OK;
+}
+
+extern "C" int icaf_scale_detections(const float* det, const int* count, int B, int max_det, const float* scale, int round, float* out,
+                                     icaf_stream_t s) {
+    if (!det || !count || !scale || !out) return fail(ICAF_ERR_ARG, "icaf_scale_detections: null pointer");
+    if (B < 1 || B > 65535 || max_det < 1) return fail(ICAF_ERR_ARG, "icaf_scale_detections: B must be in [1, 65535], max_det positive");
+    scale_detections_kernel<<<dim3((unsigned)((max_det + 255) / 256), (unsigned)B), dim3(256), 0, S(s)>>>(det, count, max_det, scale, round, out);
     ICAF_LAUNCH_CHECK();
     return ICAF_OK;
 }

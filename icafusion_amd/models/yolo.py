@@ -14,6 +14,7 @@ import math
 from copy import deepcopy
 from pathlib import Path
 
+import numpy as np
 import torch
 import torch.nn as nn
 
@@ -599,6 +600,61 @@ class Model(HipModule):
         if self.static_outputs:
             return z, logits, raws
         return z.clone(), logits.clone(), [r.clone() for r in raws]
+
+    def forward_frames(self, rgb, ir, img_size=640, bgr=True, augment=False):
+        """Forward from NATIVE camera frames: rgb / ir are cuda uint8 tensors (B, H0, W0, ch) in decoder layout (interleaved, ch = 3 or
+        1) or lists of (H0_i, W0_i, ch) tensors for ragged sizes; a pair shares its size.  The letterbox to img_size (an int or (H, W);
+        utils.datasets.letterbox, byte for byte) runs on the device straight into the uint8 plan's input, then the plan (or the TTA plan)
+        replays: the result is bit-identical to forward_u8 of the host-letterboxed batch.  bgr=True: frames are BGR as imread_bgr / cv2
+        deliver them (the planes become RGB, LoadImages' `[:, :, ::-1]`).  Returns (forward_u8's result, FrameGeometry): .scale is the
+        cuda (B, 5) rows {gain, pad_x, pad_y, w0, h0} ops.scale_detections takes, .scale_host / .geom their host twins.  Frames are
+        copied into an arena owned by the model; after the first call of a set of shapes nothing is allocated."""
+        if self.training:
+            raise NotImplementedError("icafusion_amd implements the eval-mode inference path only (call .eval())")
+        fr = [list(t) if isinstance(t, (list, tuple)) else [t[i] for i in range(t.shape[0])] if torch.is_tensor(t) and t.dim() == 4 else None
+              for t in (rgb, ir)]
+        if fr[0] is None or fr[1] is None or not fr[0] or len(fr[0]) != len(fr[1]):
+            raise ValueError("forward_frames expects two (B, H0, W0, ch) tensors or two equally long lists of (H0, W0, ch) tensors")
+        for f in fr[0] + fr[1]:
+            if not torch.is_tensor(f) or not f.is_cuda or f.dtype != torch.uint8 or f.dim() != 3 or f.shape[2] not in (1, 3):
+                raise ValueError("forward_frames expects cuda uint8 frames of shape (H0, W0, ch), ch = 3 or 1")
+        B = len(fr[0])
+        shapes = [tuple(f.shape[:2]) for f in fr[0]]
+        if shapes != [tuple(f.shape[:2]) for f in fr[1]]:
+            raise ValueError("the RGB and IR frame of a pair must have the same size")
+        H, W = (img_size, img_size) if isinstance(img_size, int) else img_size
+        gs = int(self.stride.max())
+        if H % gs or W % gs:
+            raise ValueError(f"input size {H}x{W} must be a multiple of the max stride {gs}")
+        device = fr[0][0].device
+        key = (H, W, tuple(shapes), tuple(int(f.shape[2]) for f in fr[0] + fr[1]), device)
+        states = self.__dict__.setdefault("_frame_states", {})
+        st = states.pop(key, None)
+        if st is None:
+            geom1, scale = ops.frame_geometry(shapes, (H, W))
+            geom = np.concatenate((geom1, geom1))
+            nbytes = ops.pack_frames(geom, key[3])
+            st = {"geom": geom, "geom_dev": ops.geom_tensor(geom, device), "arena": torch.zeros((nbytes,), dtype=torch.uint8, device=device),
+                  "info": ops.FrameGeometry(geom, scale, torch.from_numpy(scale).to(device)), "dst": None, "launch": None}
+            while len(states) >= 8:                       # a few sets of shapes stay resident (arena + table each)
+                states.pop(next(iter(states)))
+        states[key] = st
+        plan = (self.tta_plan_for if augment else self.plan_for)(B, H, W, device, u8=True)
+        dst = plan.inputs[0]
+        if st["dst"] is not dst:                          # the plan was rebuilt (evicted from the cache): bind the launch to its new input
+            st["launch"], st["dst"] = ops.letterbox_frames(st["arena"], st["geom"], st["geom_dev"], dst, swap_rb=bgr), dst
+        for g, f in zip(st["geom"], fr[0] + fr[1]):
+            o, n = int(g["offset"]), f.numel()
+            st["arena"][o:o + n].view(f.shape).copy_(f)
+        st["launch"].args = st["launch"].args[:8] + (int(bool(bgr)),)
+        st["launch"](ops.current_stream_ptr())
+        plan.run()
+        if augment:
+            return ((plan.outputs if self.static_outputs else plan.outputs.clone()), None), st["info"]
+        z, logits, raws = plan.outputs
+        if self.static_outputs:
+            return (z, logits, raws), st["info"]
+        return (z.clone(), logits.clone(), [r.clone() for r in raws]), st["info"]
 
     def plan_for(self, B, H, W, device="cuda", dtype=None, u8=False, slot=0, branches=True):
         """Pre-build (and return) the execution plan; its .inputs are the static RGB / IR staging buffers (u8: the one

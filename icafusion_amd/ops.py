@@ -5,14 +5,17 @@ stride ld = t.stride(2) may exceed C (channel slice of a wider NHWC buffer).  Ev
 one kernel on a stream or returns a `Launch` record that does so later (used by the static execution plan).
 PyTorch only provides device memory and streams here — none of its operators run on the hot path.
 """
+import collections
+import contextlib
 import ctypes as C
 import weakref
 
+import numpy as np
 import torch
 
 from . import _lib
 from .options import OPT
-from ._lib import BneckArgs, ConvArgs, DmffArgs, Stem2Args, check, lib, F32, BF16, F16, ACT_NONE, ACT_SILU, ACT_GELU  # noqa: F401
+from ._lib import BneckArgs, ConvArgs, DmffArgs, FrameGeom, Stem2Args, check, lib, F32, BF16, F16, ACT_NONE, ACT_SILU, ACT_GELU  # noqa: F401
 
 _DT = {torch.float32: F32, torch.bfloat16: BF16, torch.float16: F16}
 VEC = {torch.float32: 4, torch.bfloat16: 8, torch.float16: 8}     # elements per 16-byte vector
@@ -885,6 +888,151 @@ class NmsRunner:
                             stream_ptr if stream_ptr is not None else current_stream_ptr())
         check(st, "icaf_nms")
         return self.det, self.count, self.keep
+
+
+# ------------------------------------------------------------------------------------------------------------
+# native camera frames: device letterbox in, native-space boxes out
+# ------------------------------------------------------------------------------------------------------------
+# one row per (modality, image): the layout of icaf_frame_geom (include/icaf.h)
+GEOM_DTYPE = np.dtype([("offset", "<i8"), ("h0", "<i4"), ("w0", "<i4"), ("pitch", "<i4"), ("ch", "<i4"), ("nh", "<i4"), ("nw", "<i4"),
+                       ("top", "<i4"), ("left", "<i4"), ("sx", "<f4"), ("sy", "<f4")])
+assert GEOM_DTYPE.itemsize == C.sizeof(FrameGeom) == 48
+FRAME_ALIGN = 256          # frames start on this boundary inside an arena (the kernel needs 16)
+# what a forward from frames hands back beside its result: the descriptor rows, the scale_coords rows, and those on the device
+FrameGeometry = collections.namedtuple("FrameGeometry", "geom scale_host scale")
+
+
+def frame_geometry(shapes, new_shape, scaleup=True):
+    """The letterbox of native (h0, w0) frames to `new_shape` as numbers (utils.datasets.letterbox_geometry is the one definition of r,
+    new_unpad, dw / dh and the round(d -+ 0.1) split): returns (geom, scale).  geom: GEOM_DTYPE rows, one per shape — h0, w0, nh, nw,
+    top, left and the fp32 tap scales sx = w0 / nw, sy = h0 / nh; offset / pitch / ch are left 0 for pack_frames.  scale: float32
+    (n, 5) rows {gain, pad_x, pad_y, w0, h0} of scale_coords(new_shape, ., (h0, w0)) with ratio_pad=None (utils/general.py:82-93) — what
+    scale_detections and match_predictions take."""
+    from .utils.datasets import letterbox_geometry
+    if isinstance(new_shape, int):
+        new_shape = (new_shape, new_shape)
+    H, W = int(new_shape[0]), int(new_shape[1])
+    geom = np.zeros((len(shapes),), GEOM_DTYPE)
+    scale = np.zeros((len(shapes), 5), np.float32)
+    for i, (h0, w0) in enumerate(shapes):
+        h0, w0 = int(h0), int(w0)
+        if h0 < 1 or w0 < 1:
+            raise ValueError(f"frame {i}: empty shape {h0}x{w0}")
+        _, (nw, nh), _, (top, _, left, _) = letterbox_geometry((h0, w0), (H, W), scaleup)
+        if nw < 1 or nh < 1:
+            raise ValueError(f"frame {i}: {h0}x{w0} letterboxed to {H}x{W} leaves no pixel ({nh}x{nw})")
+        g = geom[i]
+        g["h0"], g["w0"], g["nh"], g["nw"], g["top"], g["left"] = h0, w0, nh, nw, top, left
+        g["sx"], g["sy"] = np.float32(w0 / nw), np.float32(h0 / nh)
+        gain = min(H / h0, W / w0)
+        scale[i] = (gain, (W - w0 * gain) / 2, (H - h0 * gain) / 2, w0, h0)
+    return geom, scale
+
+
+def pack_frames(geom, channels, pitch=None, base=0):
+    """Lay frames out back to back in a byte arena: fills offset / pitch / ch of the rows (pitch: bytes per row, default w0 * ch; frames
+    start on FRAME_ALIGN boundaries from `base` on) and returns the first free byte behind them."""
+    chans = [channels] * len(geom) if isinstance(channels, int) else list(channels)
+    pitches = [pitch] * len(geom) if pitch is None or isinstance(pitch, int) else list(pitch)
+    off = int(base)
+    for g, ch, p in zip(geom, chans, pitches):
+        off = -(-off // FRAME_ALIGN) * FRAME_ALIGN
+        g["offset"], g["ch"], g["pitch"] = off, int(ch), int(g["w0"]) * int(ch) if p is None else int(p)
+        off += int(g["h0"]) * int(g["pitch"])
+    return off
+
+
+def letterbox_staged(g):
+    """The budget rule of icaf_letterbox_frames for one descriptor row (include/icaf.h): True = its tiles stage their source rectangle
+    in LDS, False = they tap global memory (frames scaled down so far that a 32 x 64 tile's rectangle exceeds the budget)."""
+    sx, sy = np.float32(g["sx"]), np.float32(g["sy"])
+    if not (sx < 1024 and sy < 1024):
+        return False
+    rows = min(int(g["h0"]), int(np.float32(32) * sy) + 4)
+    cols = min(int(g["w0"]), int(np.float32(64) * sx) + 4)
+    return rows * ((cols * int(g["ch"]) + 30) >> 4) * 16 <= _lib.LETTERBOX_LDS_BYTES
+
+
+def validate_frames(geom, arena_bytes, H, W):
+    """Host check of descriptor rows against an arena of `arena_bytes` and an H x W output: raises ValueError with the reason.  The
+    kernel trusts the table — nothing reaches the device before this has passed."""
+    for i, g in enumerate(geom):
+        off, h0, w0, pitch, ch, nh, nw, top, left = (int(g[k]) for k in ("offset", "h0", "w0", "pitch", "ch", "nh", "nw", "top", "left"))
+        if ch not in (1, 3):
+            raise ValueError(f"frame {i}: {ch} interleaved channels (1 or 3)")
+        if h0 < 1 or w0 < 1 or nh < 1 or nw < 1:
+            raise ValueError(f"frame {i}: empty frame or resized block ({h0}x{w0} -> {nh}x{nw})")
+        if pitch < w0 * ch:
+            raise ValueError(f"frame {i}: pitch {pitch} is less than a row of {w0} pixels x {ch} channels")
+        if off < 0 or off % 16:
+            raise ValueError(f"frame {i}: offset {off} must be a non-negative multiple of 16")
+        if off + h0 * pitch > arena_bytes:
+            raise ValueError(f"frame {i}: bytes [{off}, {off + h0 * pitch}) leave the arena of {arena_bytes} bytes")
+        if top < 0 or left < 0 or top + nh > H or left + nw > W:
+            raise ValueError(f"frame {i}: resized block {nh}x{nw} at ({top}, {left}) leaves the {H}x{W} output")
+        if not (g["sx"] > 0 and g["sy"] > 0):
+            raise ValueError(f"frame {i}: tap scales must be positive")
+
+
+def geom_tensor(geom, device=None, pin=False):
+    """Descriptor rows as the flat uint8 tensor the device table is copied from / lives in."""
+    t = torch.from_numpy(np.ascontiguousarray(geom).view(np.uint8).reshape(-1).copy())
+    if device is not None:
+        return t.to(device)
+    return t.pin_memory() if pin else t
+
+
+def letterbox_frames(arena, geom, geom_dev, dst, swap_rb=True, c0=0, name="letterbox_frames"):
+    """Letterbox the frames of a byte arena into the uint8 (B, ctot, H, W) plan input (icaf_letterbox_frames).  arena: flat cuda uint8;
+    geom: the HOST descriptor rows (nstreams * B, entry modality * B + image) the device table `geom_dev` holds — or will hold by the
+    time the launch runs, for a table refreshed per step (validate_frames each refresh) — validated here, before any device call;
+    modality m fills channels [3m, 3m + 3)."""
+    if arena.dtype != torch.uint8 or not arena.is_contiguous() or arena.dim() != 1:
+        raise ValueError("the arena must be a flat contiguous uint8 tensor")
+    if dst.dtype != torch.uint8 or not dst.is_contiguous() or dst.dim() != 4:
+        raise ValueError("dst must be a contiguous uint8 (B, ctot, H, W) tensor")
+    B, ctot, H, W = dst.shape
+    n = len(geom)
+    if n % B or n == 0 or 3 * (n // B) > ctot:
+        raise ValueError(f"{n} descriptors for a batch of {B} images with {ctot} channels")
+    if W % 16:
+        raise ValueError(f"output width {W} must be a multiple of 16")
+    if geom_dev.numel() * geom_dev.element_size() < n * GEOM_DTYPE.itemsize:
+        raise ValueError("the device table is smaller than the descriptor rows")
+    validate_frames(geom, arena.numel(), H, W)
+    if not (arena.is_cuda and dst.is_cuda and geom_dev.is_cuda):
+        raise ValueError("arena, table and dst must be cuda tensors (no CPU fallback exists)")
+    nb = sum(int(g["h0"]) * int(g["w0"]) * int(g["ch"]) for g in geom) + n * 3 * H * W       # frames read once, planes written once
+    return Launch(lib().icaf_letterbox_frames, (arena.data_ptr(), geom_dev.data_ptr(), n // B, B, dst.data_ptr(), ctot, H, W, int(bool(swap_rb))),
+                  keep=(arena, geom_dev, dst), name=name, nbytes=nb)
+
+
+def scale_detections(det, count, scale, out=None, round=False, name="scale_detections"):
+    """scale_coords + clip_coords (+ torch.round) of an NMS output block on the device (icaf_scale_detections): det (B, max_det, 6) /
+    count (B,) int32, scale (B, 5) fp32 device rows {gain, pad_x, pad_y, w0, h0}; out defaults to det (in place).  Rows >= count[b]
+    come out as zeros."""
+    out = det if out is None else out
+    if det.dim() != 3 or det.shape[2] != 6 or det.dtype != torch.float32 or not det.is_contiguous() or not det.is_cuda:
+        raise ValueError("det must be a contiguous cuda float32 (B, max_det, 6) tensor")
+    if out.shape != det.shape or out.dtype != det.dtype or not out.is_contiguous() or out.device != det.device:
+        raise ValueError("out must match det")
+    B, max_det, _ = det.shape
+    if count.dtype != torch.int32 or count.numel() != B or not count.is_contiguous() or count.device != det.device:
+        raise ValueError("count must be a cuda int32 (B,) tensor")
+    if scale.dtype != torch.float32 or tuple(scale.shape) != (B, 5) or not scale.is_contiguous() or scale.device != det.device:
+        raise ValueError("scale must be a cuda float32 (B, 5) tensor of {gain, pad_x, pad_y, w0, h0} rows")
+    return Launch(lib().icaf_scale_detections, (det.data_ptr(), count.data_ptr(), B, max_det, scale.data_ptr(), int(bool(round)), out.data_ptr()),
+                  keep=(det, count, scale, out), name=name, nbytes=2 * det.numel() * 4)
+
+
+@contextlib.contextmanager
+def letterbox_direct(on=True):
+    """Force icaf_letterbox_frames onto its direct path (no LDS staging) inside a `with`: an A/B knob of the library, it changes no result."""
+    check(lib().icaf_set_option(b"letterbox_direct", int(bool(on))), "icaf_set_option(letterbox_direct)")
+    try:
+        yield
+    finally:
+        check(lib().icaf_set_option(b"letterbox_direct", 0), "icaf_set_option(letterbox_direct)")
 
 
 # ------------------------------------------------------------------------------------------------------------

@@ -20,6 +20,7 @@ keep output buffers) and its gathered block, so the tensors step n returned stay
 slot — and two pipelines of the same shape never share buffers.  Results of step i are valid after `synchronize()`.
 PyTorch streams / events are used as plumbing only; every kernel on both streams is ours (plus RCCL).
 """
+import numpy as np
 import torch
 
 from . import dist as D
@@ -45,14 +46,19 @@ HOST_FED_BRANCHES = OPT.pipe_branches             # keep the hipGraph's parallel
 
 class DetectionPipeline:
     def __init__(self, model, batch, height, width, device, conf_thres=0.25, iou_thres=0.45, classes=None,
-                 agnostic=False, multi_label=False, max_det=300, world=1, overlap=True, force_gather=False, depth=1, u8=False, augment=False):
-        """augment=True: every step is a test-time-augmentation step (Model.forward(augment=True), reference models/yolo_test.py:116-131:
+                 agnostic=False, multi_label=False, max_det=300, world=1, overlap=True, force_gather=False, depth=1, u8=False, augment=False,
+                 frames=None, frame_channels=(3, 3), frames_bgr=True, round_boxes=False):
+        """frames=(max_h0, max_w0): the pipeline also takes NATIVE camera frames (`submit_frames`; implies u8): every plan owns a frame arena
+        for `batch` pairs of up to that size (frame_channels: interleaved channels of the RGB / IR frames, 3 or 1) and a geometry table;
+        the letterbox runs on the device in front of the plan and the boxes come back in native image space (round_boxes: torch.round
+        applied, as detect_twostream.py:80).  frames_bgr: the frames are BGR (planes become RGB).
+        augment=True: every step is a test-time-augmentation step (Model.forward(augment=True), reference models/yolo_test.py:116-131:
         the plans are engine.TtaPlan objects) and NMS runs over the merged rows of the three passes (55,755 per image at 640 x 640).
         u8=True: the plans take the dataloader's uint8 (B, 6, H, W) RGB+IR batch (Model.forward_u8: `/255`, split and cast in the
         staging kernel, reference test.py:116-123) — `submit_u8` then feeds them from (pinned) host memory with the H2D copy on its own
         stream, overlapped with the forwards in flight."""
         self.model, self.device, self.world = model, torch.device(device), world
-        self.u8, self.augment = bool(u8), bool(augment)
+        self.u8, self.augment = bool(u8) or frames is not None, bool(augment)
         self.gather = world > 1 or bool(force_gather)       # force_gather: run the all-gather even with one rank (hardware test of the RCCL path)
         self.nms_args = dict(conf_thres=conf_thres, iou_thres=iou_thres, classes=classes, agnostic=agnostic,
                              multi_label=multi_label, max_det=max_det)
@@ -117,6 +123,151 @@ class DetectionPipeline:
         self.gen, self.pending, self.gathers = 0, 0, 0               # generation the NEXT gather writes; steps since the last gather; gathers issued
         self.n = 0
         self.last = None
+        self.frames = None
+        if frames is not None:
+            self._init_frames(batch, height, width, frames, frame_channels, frames_bgr, round_boxes)
+
+    def _init_frames(self, B, H, W, frames, chans, bgr, round_boxes):
+        """Per plan: a byte arena (RGB frames in its first half, IR frames in its second) and ONE table allocation — 2B descriptor rows
+        for the letterbox, then B scale_coords rows for scale_detections — with a pinned host twin it is copied from."""
+        max_h0, max_w0 = int(frames[0]), int(frames[1])
+        chans = tuple(int(c) for c in chans)
+        if max_h0 < 1 or max_w0 < 1 or len(chans) != 2 or any(c not in (1, 3) for c in chans):
+            raise ValueError(f"frames=(max_h0, max_w0) with frame_channels of 1 or 3 each, got {frames} / {chans}")
+        A = ops.FRAME_ALIGN
+        cap = [B * (-(-(max_h0 * max_w0 * c) // A) * A) for c in chans]          # bytes per modality
+        gb = 2 * B * ops.GEOM_DTYPE.itemsize
+        probe, _ = ops.frame_geometry([(max_h0, max_w0)] * B, (H, W))
+        probe = np.concatenate((probe, probe))
+        ops.pack_frames(probe[:B], chans[0])
+        ops.pack_frames(probe[B:], chans[1], base=cap[0])
+        self.frames = {"B": B, "H": H, "W": W, "max": (max_h0, max_w0), "chans": chans, "cap": cap, "geom_bytes": gb, "cache": {},
+                       "arena": [], "tab_dev": [], "tab_host": [], "letterbox": [], "scale_rows": [], "scale_launch": {}, "pending": None,
+                       "round": bool(round_boxes)}
+        f = self.frames
+        for plan in self.plans:
+            arena = torch.zeros((sum(cap),), dtype=torch.uint8, device=self.device)
+            tab = torch.zeros((gb + B * 20,), dtype=torch.uint8, device=self.device)
+            f["arena"].append(arena)
+            f["tab_dev"].append(tab)
+            f["tab_host"].append(torch.zeros((gb + B * 20,), dtype=torch.uint8).pin_memory())
+            f["scale_rows"].append(tab[gb:].view(torch.float32).view(B, 5))
+            f["letterbox"].append(ops.letterbox_frames(arena, probe, tab, plan.inputs[0], swap_rb=bgr))
+
+    def _frame_table(self, shapes, contiguous):
+        """(table bytes, descriptor rows) of one step's frames, cached per set of shapes: the geometry, the arena layout (a uniform
+        batch whose frames are whole 16-byte multiples keeps its layout, so ONE copy per modality moves it; other frames start on
+        FRAME_ALIGN boundaries) and the validation against this pipeline's arena and output size."""
+        f = self.frames
+        key = (tuple(shapes), contiguous)
+        hit = f["cache"].get(key)
+        if hit is None:
+            B, chans, cap = f["B"], f["chans"], f["cap"]
+            for h0, w0 in shapes:
+                if h0 > f["max"][0] or w0 > f["max"][1]:
+                    raise ValueError(f"a {h0}x{w0} frame exceeds the pipeline's frames={f['max']}")
+            geom1, scale = ops.frame_geometry(shapes, (f["H"], f["W"]))
+            geom = np.concatenate((geom1, geom1))
+            for m, base in ((0, 0), (1, cap[0])):
+                rows = geom[m * B:(m + 1) * B]
+                if contiguous[m]:
+                    ops.pack_frames(rows, chans[m])
+                    fb = int(rows[0]["h0"]) * int(rows[0]["pitch"])
+                    rows["offset"] = base + fb * np.arange(B)
+                else:
+                    end = ops.pack_frames(rows, chans[m], base=base)
+                    if end - base > cap[m]:
+                        raise ValueError(f"the frames of modality {m} need {end - base} bytes of the arena's {cap[m]}")
+            ops.validate_frames(geom, sum(cap), f["H"], f["W"])
+            table = np.concatenate((geom.view(np.uint8).reshape(-1), scale.view(np.uint8).reshape(-1)))
+            if len(f["cache"]) >= 64:
+                f["cache"].pop(next(iter(f["cache"])))
+            hit = f["cache"][key] = (torch.from_numpy(table), geom)
+        return hit
+
+    def submit_frames(self, rgb, ir):
+        """One batch of NATIVE frames through the pipeline: rgb / ir are uint8 (B, H0, W0, ch) tensors or lists of (H0_i, W0_i, ch) tensors,
+        in pinned host memory or on the device; a pair shares its size, sizes may change from step to step.  The frames and the step's
+        geometry table are copied on the copy stream(s) under the events submit_u8 uses, the letterbox runs on the plan's forward stream in
+        front of its graph, scale_detections on the NMS stream behind NMS: the (det, count) step() returns hold NATIVE-space boxes (rows >=
+        count zeroed), and so does the gathered block of a process group.  Host buffers must stay untouched until their copy has run
+        (`pipe.copied[n % pipe.nplans]`, as for submit_u8)."""
+        f = self.frames
+        if f is None:
+            raise ValueError("DetectionPipeline(frames=(max_h0, max_w0)) takes native frames")
+        B, chans = f["B"], f["chans"]
+        mods, contiguous = [], []
+        for m, t in enumerate((rgb, ir)):
+            uniform = torch.is_tensor(t) and t.dim() == 4
+            fr = [t[i] for i in range(t.shape[0])] if uniform else list(t) if isinstance(t, (list, tuple)) else None
+            if fr is None or len(fr) != B:
+                raise ValueError(f"submit_frames expects (B, H0, W0, ch) tensors or lists of (H0, W0, ch) tensors for a batch of {B}")
+            for x in fr:
+                if not torch.is_tensor(x) or x.dtype != torch.uint8 or x.dim() != 3 or x.shape[2] != chans[m]:
+                    raise ValueError(f"modality {m}: frames must be uint8 (H0, W0, {chans[m]}) tensors")
+            contiguous.append(bool(uniform and t.is_contiguous() and (t[0].numel() % 16 == 0)))
+            mods.append((t, fr))
+        shapes = [tuple(x.shape[:2]) for x in mods[0][1]]
+        if shapes != [tuple(x.shape[:2]) for x in mods[1][1]]:
+            raise ValueError("the RGB and IR frame of a pair must have the same size")
+        table, geom = self._frame_table(shapes, tuple(contiguous))        # raises before anything is enqueued
+        pi = self.n % self.nplans
+        fs = self.fwd_streams[pi % self.depth]
+        arena, ncs = f["arena"][pi], len(self.copy_streams)
+        on_device = any(x.is_cuda for _, fr in mods for x in fr)
+        if self.n >= self.nplans:
+            self.copied[pi][0].synchronize()                                # the last copy OUT of this plan's pinned table (nplans steps ago) has run
+        f["tab_host"][pi].copy_(table)
+        cur = torch.cuda.current_stream(self.device)
+        for k, cs in enumerate(self.copy_streams):                          # the batch in `ncs` slices of images, one copy stream each
+            lo, hi = B * k // ncs, B * (k + 1) // ncs
+            if hi <= lo and k:
+                continue
+            if self.nplans == 1:                                            # sequential pipeline: behind everything the one plan has in flight
+                cs.wait_stream(fs)
+                cs.wait_stream(self.nms_stream)
+            elif self.n >= self.nplans:
+                cs.wait_event(self.fwd_done[pi])                            # this plan's previous forward has consumed its arena and table
+                if k == 0:
+                    cs.wait_event(self.nms_done_deep[pi])                   # ... and its scale_detections the scale rows
+            if on_device:
+                cs.wait_stream(cur)
+            with torch.cuda.stream(cs):
+                if k == 0:
+                    f["tab_dev"][pi].copy_(f["tab_host"][pi], non_blocking=True)
+                for m, (t, fr) in enumerate(mods):
+                    rows = geom[m * B:(m + 1) * B]
+                    if contiguous[m]:
+                        o, fb = int(rows[lo]["offset"]), t[0].numel()
+                        arena[o:o + (hi - lo) * fb].view(t[lo:hi].shape).copy_(t[lo:hi], non_blocking=True)
+                    else:
+                        for b in range(lo, hi):
+                            o = int(rows[b]["offset"])
+                            arena[o:o + fr[b].numel()].view(fr[b].shape).copy_(fr[b], non_blocking=True)
+            if on_device:
+                for t, fr in mods:
+                    for x in ([t] if torch.is_tensor(t) else fr):
+                        if x.is_cuda:
+                            x.record_stream(cs)
+            self.copied[pi][k].record(cs)
+            fs.wait_event(self.copied[pi][k])
+        f["letterbox"][pi](fs.cuda_stream)
+        f["pending"] = pi
+        try:
+            return self.step()
+        finally:
+            f["pending"] = None
+
+    def _native_boxes(self, runner, stream_ptr):
+        """Behind the NMS of a submit_frames step, on the NMS stream: the runner's block to native image space, in place."""
+        f = self.frames
+        if f is None or f["pending"] is None:
+            return
+        pi = f["pending"]
+        key = (id(runner), pi)
+        if key not in f["scale_launch"]:
+            f["scale_launch"][key] = ops.scale_detections(runner.det, runner.count, f["scale_rows"][pi], round=f["round"])
+        f["scale_launch"][key](stream_ptr)
 
     def _z(self, plan):
         """The decoded rows NMS reads: a TtaPlan's output IS the merged z, a plain plan's is (z, logits, raws)."""
@@ -193,6 +344,7 @@ class DetectionPipeline:
         if self.gather and self.gathers:
             ns.wait_event(self.gather_done)                 # the last gather has read this slot's block
         det, count, keep = nms_device(self.zbuf[i], stream_ptr=ns.cuda_stream, runner=self.runners[i], **self.nms_args)
+        self._native_boxes(self.runners[i], ns.cuda_stream)
         out = (det[None], count[None])
         if self.gather:
             out = self._gather(self.runners[i].block, 0)
@@ -240,6 +392,7 @@ class DetectionPipeline:
         if self.gather and self.gathers and self.pending == 0:
             ns.wait_event(self.gather_done)                # the last gather has read the blocks this group's NMS launches overwrite
         det, count, keep = nms_device(self._z(plan), stream_ptr=ns.cuda_stream, runner=self.deep_runners[pi], **self.nms_args)
+        self._native_boxes(self.deep_runners[pi], ns.cuda_stream)
         out = (det[None], count[None])
         if self.gather:
             out = self._gather(self.group_block, pi)

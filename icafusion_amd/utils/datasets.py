@@ -79,11 +79,10 @@ def resize_area(img, new_wh):
     return np.clip(np.floor(out + 0.5), 0, 255).astype(np.uint8)
 
 
-def letterbox(img, new_shape=(640, 640), color=(114, 114, 114), auto=True, scaleFill=False, scaleup=True, stride=32):
-    """Resize keeping the aspect ratio, then pad to `new_shape` with `color` (reference utils/datasets.py:1404-1444).
-    `auto` / `scaleFill` / `stride` are accepted and — exactly as in the reference, whose branches for them are
-    commented out — have no effect.  Returns (image, (ratio_w, ratio_h), (pad_w, pad_h)) with per-side paddings."""
-    shape = img.shape[:2]
+def letterbox_geometry(shape, new_shape=(640, 640), scaleup=True):
+    """THE numbers of the letterbox (reference utils/datasets.py:1404-1444) for a native (h0, w0): r, new_unpad = (nw, nh), the
+    per-side paddings (dw, dh) and the integer split (top, bottom, left, right) of an odd pad, round(d -+ 0.1).  `letterbox` below and
+    the device letterbox's descriptors (icafusion_amd.ops.frame_geometry) both take them from here."""
     if isinstance(new_shape, int):
         new_shape = (new_shape, new_shape)
     r = min(new_shape[0] / shape[0], new_shape[1] / shape[1])
@@ -91,10 +90,19 @@ def letterbox(img, new_shape=(640, 640), color=(114, 114, 114), auto=True, scale
         r = min(r, 1.0)
     new_unpad = int(round(shape[1] * r)), int(round(shape[0] * r))
     dw, dh = (new_shape[1] - new_unpad[0]) / 2, (new_shape[0] - new_unpad[1]) / 2
-    if shape[::-1] != new_unpad:
-        img = resize_bilinear(img, new_unpad)
     top, bottom = int(round(dh - 0.1)), int(round(dh + 0.1))
     left, right = int(round(dw - 0.1)), int(round(dw + 0.1))
+    return r, new_unpad, (dw, dh), (top, bottom, left, right)
+
+
+def letterbox(img, new_shape=(640, 640), color=(114, 114, 114), auto=True, scaleFill=False, scaleup=True, stride=32):
+    """Resize keeping the aspect ratio, then pad to `new_shape` with `color` (reference utils/datasets.py:1404-1444).
+    `auto` / `scaleFill` / `stride` are accepted and — exactly as in the reference, whose branches for them are
+    commented out — have no effect.  Returns (image, (ratio_w, ratio_h), (pad_w, pad_h)) with per-side paddings."""
+    shape = img.shape[:2]
+    r, new_unpad, (dw, dh), (top, bottom, left, right) = letterbox_geometry(shape, new_shape, scaleup)
+    if shape[::-1] != new_unpad:
+        img = resize_bilinear(img, new_unpad)
     out = np.empty((img.shape[0] + top + bottom, img.shape[1] + left + right, img.shape[2]), np.uint8)
     out[...] = np.asarray(color, np.uint8)
     out[top:top + img.shape[0], left:left + img.shape[1]] = img
@@ -116,9 +124,12 @@ def _list_images(path):
 
 class LoadImages:
     """Iterate the image files of a folder / glob / single path: yields (path, CHW RGB uint8 letterboxed, BGR original,
-    None) like the reference's LoadImages.__next__ (utils/datasets.py:205-241).  Video files are out of scope."""
+    None) like the reference's LoadImages.__next__ (utils/datasets.py:205-241).  Video files are out of scope.
+    native=True: no host letterbox — the second item is None and the consumer letterboxes the BGR original on the device
+    (Model.forward_frames)."""
 
-    def __init__(self, path, img_size=640, stride=32):
+    def __init__(self, path, img_size=640, stride=32, native=False):
+        self.native = bool(native)
         self.files = _list_images(path)
         self.nf = len(self.files)
         self.img_size, self.stride, self.mode, self.cap = img_size, stride, "image", None
@@ -138,6 +149,8 @@ class LoadImages:
         path = self.files[self.count]
         self.count += 1
         img0 = imread_bgr(path)
+        if self.native:
+            return path, None, img0, self.cap
         img = letterbox(img0, self.img_size, stride=self.stride)[0]
         img = np.ascontiguousarray(img[:, :, ::-1].transpose(2, 0, 1))
         return path, img, img0, self.cap

@@ -37,7 +37,9 @@ enum { ICAF_OK = 0, ICAF_ERR_ARG = -1, ICAF_ERR_HIP = -2, ICAF_ERR_UNSUPPORTED =
 const char* icaf_last_error(void);
 /* Probe knobs of the library, set by the host's one options object (icafusion_amd/options.py) when the library is loaded — the library reads no
  * environment variable: "detect_elementwise" (!= 0: icaf_detect_decode by the one-thread-per-element kernel), "attn_qsplit" (n > 0: query splits per
- * head of icaf_cross_attention), "sppf_vpb" (n > 0: cap on the channel vectors per workgroup of icaf_sppf_pool); 0 = the library's own choice.
+ * head of icaf_cross_attention), "sppf_vpb" (n > 0: cap on the channel vectors per workgroup of icaf_sppf_pool), "letterbox_direct" (!= 0:
+ * icaf_letterbox_frames taps global memory in every tile instead of staging in LDS; set by a caller for an A/B, not by the options object);
+ * 0 = the library's own choice.
  * ICAF_ERR_ARG for an unknown name.  None of them changes a result. */
 int icaf_set_option(const char* name, int value);
 int icaf_version(void);
@@ -366,6 +368,40 @@ int icaf_tta_stage(const void* src, int src_u8, int ctot, int B, int H, int W, c
                    icaf_stream_t s);
 int icaf_tta_merge(const float* const* z, const long long* rows, const float* scale, const int* flip, int npass, float* out,
                    int B, int no, float width, icaf_stream_t s);
+
+/* ---- native camera frames (utils/datasets.py: letterbox; detect_twostream.py:70-80) ---------------------------------------
+ * icaf_letterbox_frames: the host letterbox on the device, byte for byte.  arena: decoder-layout frames, h0 x w0 x ch interleaved uint8
+ *   (ch = 3, or 1: the one channel feeds all three planes), each with its own row pitch; geom: DEVICE table of nstreams * B descriptors,
+ *   entry modality * B + image, so that one static launch serves frames whose sizes change from step to step.  dst: the plan's uint8
+ *   [B][ctot][H][W] input, modality m = channels [3m, 3m + 3); every byte of those planes is written exactly once: rows [top, top + nh) x
+ *   columns [left, left + nw) the bilinear resize (half-pixel centres, edge clamp) of the frame, 114 elsewhere.  swap_rb != 0: source
+ *   channel 2 - c feeds plane c (BGR frames -> RGB planes).  Arithmetic of utils/datasets.py resize_bilinear, fp32, nothing fused:
+ *   s = (j + 0.5f) * scale - 0.5f (two rounded operations), i0 = floor(s) (may be -1), frac = s - i0 BEFORE i0 and i0 + 1 are clamped into
+ *   the frame, top = a00 * (1 - fx) + a01 * fx, bot likewise, out = top * (1 - fy) + bot * fy, result floor(out + 0.5f) clipped to 0..255;
+ *   sx = (float)(w0 / (double)nw), sy likewise, computed by the host (the kernel does not divide).  One workgroup per 32 x 64 output tile:
+ *   if the source rectangle a tile of that descriptor can tap fits ICAF_LETTERBOX_LDS_BYTES — at most ((int)(32 sy) + 4 capped at h0)
+ *   rows of ((int)(64 sx) + 4 capped at w0) * ch + 30 bytes, rounded down to whole 16-byte vectors — it is staged in LDS with aligned 16-byte
+ *   loads, otherwise (or with the probe knob "letterbox_direct") every tap is a clamped global load: any scale works.  No load leaves
+ *   the frame's h0 * pitch bytes.  The host guarantees (icafusion_amd/ops.py validates): offset % 16 == 0, pitch >= w0 * ch,
+ *   offset + h0 * pitch inside the arena, top + nh <= H, left + nw <= W; W % 16 == 0, arena and dst 16-byte aligned.
+ * icaf_scale_detections: scale_coords + clip_coords (utils/general.py:386-407) of an NMS output block on the device.  det
+ *   [B][max_det][6], count [B], scale [B][5] = {gain, pad_x, pad_y, w0, h0} (device rows, as icaf_match_predictions takes them);
+ *   out [B][max_det][6] may alias det.  Rows < count[b]: x = clamp((x - pad_x) / gain, 0, w0), y likewise with pad_y / h0 (an IEEE
+ *   division; the SAME device function icaf_match_predictions maps its boxes with), round != 0: then round-half-even (torch.round);
+ *   conf and cls copied.  Rows >= count[b] are written as zeros. */
+enum { ICAF_LETTERBOX_LDS_BYTES = 20480 };
+typedef struct icaf_frame_geom {
+    long long offset;      /* first byte of the frame in the arena (16-byte aligned) */
+    int h0, w0;            /* native size */
+    int pitch, ch;         /* bytes per row (>= w0 * ch); interleaved channels: 3 or 1 */
+    int nh, nw;            /* resized size (letterbox's new_unpad) */
+    int top, left;         /* where the resized block starts in the H x W output */
+    float sx, sy;          /* w0 / nw, h0 / nh rounded to fp32 */
+} icaf_frame_geom;
+int icaf_letterbox_frames(const void* arena, const icaf_frame_geom* geom, int nstreams, int B, void* dst, int ctot, int H, int W,
+                          int swap_rb, icaf_stream_t s);
+int icaf_scale_detections(const float* det, const int* count, int B, int max_det, const float* scale, int round, float* out,
+                          icaf_stream_t s);
 
 /* ---- NMS (utils/general.py:518-607 + torchvision.ops.nms semantics) ----------------------------------------
  * pred: [B][rows][5+nc] fp32 (cx, cy, w, h, obj, cls...).  Per image: obj > conf filter, conf = obj*cls, best
