@@ -70,13 +70,6 @@ __device__ __forceinline__ int xcd_tile(int ntile_total) {
     return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
 }
 
-#ifndef ICAF_EPI_FAST
-#define ICAF_EPI_FAST 1          // 1: the restructured write-back (round 5: adopted after the whole GPU suite ran green on the variant library and a same-box
-                                 //    A/B: default workload 16,141 -> 16,191 pairs/s, forward 2.191 -> 2.169 ms; yolov5l shard 3,726 -> 3,803, 9.34 -> 9.10 ms); 0: round 4's loop
-#endif
-#ifndef ICAF_PRE_WB
-#define ICAF_PRE_WB 1            // 1: the pre-activation term is added in the write-back phase from an fp32-staged tile (0: round 4's per-lane taps; A/B builds)
-#endif
 // ---- epilogue shared by both pipelines: bias + activation in registers, LDS staging, 16-byte write-back --------
 // row_to_m(tile_row) -> linear output pixel index (b, ho, wo), or -1 when the tile row lies outside the tensor.
 // PRE = true compiles the pre-activation bilinear term in (it costs ~40 registers, so only the few instantiations that
@@ -86,8 +79,8 @@ __device__ __forceinline__ int xcd_tile(int ntile_total) {
 // WB = true writes every final output vector (residual included) back into the staged LDS tile as well: igemm's chained
 // 1x1 then consumes, as its pixel operand, exactly what this layer stores.
 // FULLVEC = true: the caller has checked that whole BN-channel tiles are written (Cout % BN == 0) in 16-byte vectors without a residual — the
-// write-back is then one vector load and one store per thread and round; the general loop below compiles four fall-back paths in (a short last vector, a
-// scalar residual, unaligned rows), ~30 instructions of branching per round even when none is taken (icaf_bottleneck + cv3: eight rounds per workgroup).
+// write-back is then one vector load and one store per thread and round, with no run-time check of the fast loops' condition and no general loop
+// compiled in (icaf_bottleneck + cv3: eight rounds per workgroup).
 template <int DT, int ODT, int BM, int BN, int WM, int WN, int ACT, bool PRE, bool SECOND = false, bool WB = false, bool FULLVEC = false, typename RowMap>
 __device__ __forceinline__ void epilogue(f32x16 (&acc)[WN / 32][WM / 32], unsigned char* lds, const ConvP& p, int g, RowMap row_to_m, int n0) {
     using E = Elem<DT>;
@@ -102,8 +95,8 @@ __device__ __forceinline__ void epilogue(f32x16 (&acc)[WN / 32][WM / 32], unsign
     const float alpha_acc = SECOND ? 1.0f : p.alpha_acc[g], alpha_res = p.alpha_res[g];
     const float* __restrict__ bias = SECOND ? (p.bias2 ? p.bias2 + g * p.bias2_gs : nullptr) : (p.bias ? p.bias + g * p.bias_gs : nullptr);
     const int Cout = SECOND ? p.Cout2 : p.Cout, ldy = SECOND ? p.ldy2 : p.ldy, vec_y = SECOND ? p.vec_y2 : p.vec_y;
-    if constexpr (PRE && ICAF_PRE_WB) {
-        // Round 5 — the pre-activation term is added in the WRITE-BACK phase.  With the lane = pixel mapping of the accumulators every tap load was 64
+    if constexpr (PRE) {
+        // The pre-activation term is added in the WRITE-BACK phase.  With the lane = pixel mapping of the accumulators (round 4's per-lane taps) every tap load was 64
         // lanes x 16 bytes in 64 different rows of the fp32 map (a row is Cout * 4 = 512 - 2048 bytes): uncoalesced, 16 * TN * TM such loads per lane —
         // the three fuse convolutions of yolov5s took 154 us where plain 1x1 layers of their shapes take ~60.  Here the tile is staged as FP32
         // (acc + bias, exactly the sum the old path formed first), and the thread that writes a 16-byte output vector adds the term: the VPR threads of
@@ -181,6 +174,10 @@ __device__ __forceinline__ void epilogue(f32x16 (&acc)[WN / 32][WM / 32], unsign
                     const f32x4 t00 = *(const f32x4*)(pt4[0] + 4 * k4), t01 = *(const f32x4*)(pt4[1] + 4 * k4);
                     const f32x4 t10 = *(const f32x4*)(pt4[2] + 4 * k4), t11 = *(const f32x4*)(pt4[3] + 4 * k4);
                     {
+                        // No fp contraction in the bilinear arithmetic (here and in the tap set-up above): left to the compiler, different instantiations
+                        // (tiles) fused these products differently, so the same layer rounded differently from one tile shape to the next and a batch
+                        // shard stopped being bit-identical to the same rows of the full batch.  Do NOT write the fmas out with __builtin_fmaf instead:
+                        // that produced a 128x64 / 64-byte-pipeline kernel with wrong, run-to-run varying results at large grids (lab/probes/pre_check.py).
 #pragma clang fp contract(off)
                         const float wx0 = 1.0f - lx, wy0 = 1.0f - ly;
 #pragma unroll
@@ -210,44 +207,6 @@ __device__ __forceinline__ void epilogue(f32x16 (&acc)[WN / 32][WM / 32], unsign
         }
         return;
     }
-    // pre-activation bilinear term: the four source taps and weights of this lane's TM pixels (align_corners=False:
-    // src = max(0, (dst + 0.5) * in/out - 0.5), neighbours clamped), exactly as upsample_merge_kernel computes them
-    const float* pt[PRE ? TM : 1][4];
-    float plx[PRE ? TM : 1], ply[PRE ? TM : 1];
-    if constexpr (PRE) {
-        // No fp contraction in the bilinear arithmetic (here and where the term is evaluated below): left to the compiler,
-        // different instantiations (tiles) fused these products differently, so the same layer rounded differently from one
-        // tile shape to the next and a batch shard stopped being bit-identical to the same rows of the full batch.  (Writing
-        // the fmas out with __builtin_fmaf instead produced a 128x64 / 64-byte-pipeline kernel with wrong, run-to-run
-        // varying results at large grids — lab/probes/pre_check.py.)
-#pragma clang fp contract(off)
-        const float sy = (float)p.pre_h / (float)p.Ho, sx = (float)p.pre_w / (float)p.Wo;
-#pragma unroll
-        for (int b = 0; b < TM; ++b) {
-            const int m = row_to_m(wm * WM + b * 32 + l31);
-            const int mm = m < 0 ? 0 : m;
-            const int wo = mm % p.Wo, t = mm / p.Wo, ho = t % p.Ho, bi = t / p.Ho;
-            float fy = ((float)ho + 0.5f) * sy - 0.5f, fx = ((float)wo + 0.5f) * sx - 0.5f;
-            fy = fy < 0.0f ? 0.0f : fy;
-            fx = fx < 0.0f ? 0.0f : fx;
-            int y0 = (int)fy, x0 = (int)fx;
-            y0 = y0 < p.pre_h - 1 ? y0 : p.pre_h - 1;
-            x0 = x0 < p.pre_w - 1 ? x0 : p.pre_w - 1;
-            int y1 = y0 < p.pre_h - 1 ? y0 + 1 : y0, x1 = x0 < p.pre_w - 1 ? x0 + 1 : x0;
-            ply[b] = fy - (float)y0;
-            plx[b] = fx - (float)x0;
-            if (p.pre_mode == 1) {                 // nearest: one tap with weight 1 — the fma sequence below returns it exactly
-                y0 = y1 = (int)((long long)ho * p.pre_h / p.Ho);
-                x0 = x1 = (int)((long long)wo * p.pre_w / p.Wo);
-                ply[b] = plx[b] = 0.0f;
-            }
-            const float* base = p.pre + (long long)bi * p.pre_h * p.pre_w * p.ldpre;
-            pt[b][0] = base + (long long)(y0 * p.pre_w + x0) * p.ldpre;
-            pt[b][1] = base + (long long)(y0 * p.pre_w + x1) * p.ldpre;
-            pt[b][2] = base + (long long)(y1 * p.pre_w + x0) * p.ldpre;
-            pt[b][3] = base + (long long)(y1 * p.pre_w + x1) * p.ldpre;
-        }
-    }
 #pragma unroll
     for (int a = 0; a < TN; ++a) {
         // The four bias quads of this 32-channel block are fetched as ONE batch, unconditionally (clamped address +
@@ -269,24 +228,11 @@ __device__ __forceinline__ void epilogue(f32x16 (&acc)[WN / 32][WM / 32], unsign
 #pragma unroll
             for (int b = 0; b < TM; ++b) {
                 const int ml = wm * WM + b * 32 + l31;
-                float pv[4] = {0.f, 0.f, 0.f, 0.f};
-                if constexpr (PRE) if (n0 + nl < Cout) {
-                    const f32x4 t00 = *(const f32x4*)(pt[b][0] + n0 + nl), t01 = *(const f32x4*)(pt[b][1] + n0 + nl);
-                    const f32x4 t10 = *(const f32x4*)(pt[b][2] + n0 + nl), t11 = *(const f32x4*)(pt[b][3] + n0 + nl);
-                    {
-#pragma clang fp contract(off)
-                        const float wx0 = 1.0f - plx[b], wy0 = 1.0f - ply[b];
-#pragma unroll
-                        for (int j = 0; j < 4; ++j) {
-                            const float top = t00[j] * wx0 + t01[j] * plx[b];
-                            const float bot = t10[j] * wx0 + t11[j] * plx[b];
-                            pv[j] = top * wy0 + bot * ply[b];
-                        }
-                    }
-                }
                 float v[4], xin[4];
 #pragma unroll
-                for (int j = 0; j < 4; ++j) xin[j] = acc[a][b][4 * q + j] + bv[j] + pv[j];
+                // (+ 0.0f: what is left of the old pre-term path's zero term; the compiler may not fold it, so today's device code contains the add
+                //  — removing it changes every convolution kernel)
+                for (int j = 0; j < 4; ++j) xin[j] = acc[a][b][4 * q + j] + bv[j] + 0.0f;
                 apply_act4<ACT, DT>(xin, v);
 #pragma unroll
                 for (int j = 0; j < 4; ++j) v[j] *= alpha_acc;
@@ -319,10 +265,9 @@ __device__ __forceinline__ void epilogue(f32x16 (&acc)[WN / 32][WM / 32], unsign
         }
         return;
     }
-#if ICAF_EPI_FAST
     // The write-back as two checked fast loops — whole tiles in 16-byte vectors, without / with a vector residual — and ONE compact general loop (not unrolled, nothing held
-    // across iterations) for everything else, instead of the unrolled general loop below whose four fall-back paths cost ~30 instructions of branching
-    // per 16-byte store.  Same arithmetic in every path (staged vector + alpha_res * residual, fma per element).
+    // across iterations) for everything else, instead of one unrolled general loop whose four fall-back paths cost ~30 instructions of branching
+    // per 16-byte store (round 4's write-back: docs/HISTORY.md, "Variants removed from the source").  Same arithmetic in every path (staged vector + alpha_res * residual, fma per element).
     if constexpr (VO == E::VEC && NVEC % NT == 0 && (VPR & (VPR - 1)) == 0) {
         if (vec_y && n0 + BN <= Cout && (!rg || p.vec_r)) {            // (workgroup-uniform)
             if (!rg) {
@@ -385,7 +330,10 @@ __device__ __forceinline__ void epilogue(f32x16 (&acc)[WN / 32][WM / 32], unsign
         }
         return;
     }
-#endif
+    // Everything else.  In today's library that is the fp32 output of a 16-bit layer only: every instantiation whose output vectors match the
+    // residual's (VO == E::VEC) has whole power-of-two rounds and left through the branch above, so `rfast` below is false at compile time.  The
+    // prefetch stays written out all the same: without it the 180 fp32-output igemm kernels compile to different code.
+    static_assert(VO != E::VEC || (NVEC % NT == 0 && (VPR & (VPR - 1)) == 0), "a same-type tile now reaches the general write-back loop: its residual prefetch is live again");
     // residual vectors of all of this thread's output vectors first (one batch of loads in flight instead of a
     // load -> wait -> add -> store chain per vector)
     u32x4 rvec[NIT];
@@ -446,7 +394,7 @@ template <int DT, int ODT, int BM, int BN>
 struct TileLds {
     static constexpr int SO = BN * Elem<ODT>::BYTES + 16;
     static constexpr int OUT_BYTES = BM * SO;
-    static constexpr int PRE_BYTES = ICAF_PRE_WB ? BM * (BN * 4 + 16) : OUT_BYTES;      // pre-term launches stage the tile as fp32 (epilogue)
+    static constexpr int PRE_BYTES = BM * (BN * 4 + 16);      // pre-term launches stage the tile as fp32 (epilogue)
     static constexpr int REG_BYTES = 2 * (BM + BN) * ROWS;
 };
 

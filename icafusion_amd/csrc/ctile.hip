@@ -22,10 +22,6 @@
 #ifndef ICAF_CTILE_ABL
 #define ICAF_CTILE_ABL 0
 #endif
-// 1 = the fused Bottleneck + cv3 asks for its residual / cv2 vectors behind the 3x3 loop (the form before round 4; A/B builds only)
-#ifndef ICAF_CTILE_LATE3
-#define ICAF_CTILE_LATE3 0
-#endif
 
 namespace icaf {
 
@@ -130,7 +126,7 @@ __device__ __forceinline__ void ctile_body(const ConvP& p, const int lsp_arg, co
     // HBM round trip at the end of every workgroup's life and re-fetched lines the L2 had dropped: PMC 387 MB per launch for 210 MB read.)
     constexpr int VPR3 = BN / VEC, NIT3 = CHAIN3 ? BM * VPR3 / NTHREADS : 1;
     u32x4 rv[NIT3], cv2v[NIT3];
-    if constexpr (CHAIN3 && !ICAF_CTILE_LATE3) {
+    if constexpr (CHAIN3) {
         const typename E::type* __restrict__ rg = p.res ? (const typename E::type*)p.res + g * p.res_gs : nullptr;
         const typename E::type* __restrict__ x2g = (const typename E::type*)p.x2 + g * p.x2_gs;
 #pragma unroll
@@ -342,17 +338,6 @@ __device__ __forceinline__ void ctile_body(const ConvP& p, const int lsp_arg, co
         {
             constexpr int VPR = BN / VEC, NIT = BM * VPR / NTHREADS;   // 4 vectors per row and half, 4 rows per thread
             const typename E::type* __restrict__ rg = p.res ? (const typename E::type*)p.res + g * p.res_gs : nullptr;
-            if constexpr (ICAF_CTILE_LATE3) {                              // (A/B build: the loads where they were before round 4)
-                const typename E::type* __restrict__ x2g = (const typename E::type*)p.x2 + g * p.x2_gs;
-#pragma unroll
-                for (int it = 0; it < NIT; ++it) {
-                    const int idx = tid + it * NTHREADS, row = idx / VPR, cv = idx - row * VPR;
-                    const int m = row_to_m(row);
-                    const long long mm = m < 0 ? 0 : m;
-                    rv[it] = rg ? *(const u32x4*)(rg + mm * p.ldr + cv * VEC) : u32x4{0u, 0u, 0u, 0u};
-                    cv2v[it] = *(const u32x4*)(x2g + mm * p.ldx2 + cv * VEC);
-                }
-            }
             const float alpha_res = p.alpha_res[g];
 #pragma unroll
             for (int it = 0; it < NIT; ++it) {

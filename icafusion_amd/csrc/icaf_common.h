@@ -153,10 +153,6 @@ __device__ __forceinline__ float silu_f(float v) {
 // for two values instead of 16.  (Left to itself the compiler packs the bias add and the final product but not the two middle steps.)
 using f32x2 = __attribute__((ext_vector_type(2))) float;
 __device__ __forceinline__ void silu4_f(const float (&x)[4], float (&y)[4]) {
-#ifdef ICAF_NO_PK_SILU
-#pragma unroll
-    for (int e = 0; e < 4; ++e) y[e] = silu_f(x[e]);
-#else
     const f32x2 c = {-1.4426950408889634f, -1.4426950408889634f}, one = {1.0f, 1.0f};
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
@@ -169,7 +165,6 @@ __device__ __forceinline__ void silu4_f(const float (&x)[4], float (&y)[4]) {
         y[2 * h] = o[0];
         y[2 * h + 1] = o[1];
     }
-#endif
 }
 __device__ __forceinline__ float gelu_f(float v) { return 0.5f * v * (1.0f + erff(v * 0.70710678118654752440f)); }
 // GELU(erf) for the 16-bit kernels: erf by Abramowitz & Stegun 7.1.26 (|error| <= 1.5e-7: GELU within 0.5 |v| (1.5e-7 + 2^-23) + 25 * 2^-24 |result| —

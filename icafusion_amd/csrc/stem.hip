@@ -530,9 +530,6 @@ __global__ __launch_bounds__(S2_THREADS) void stem2_kernel(const Stem2P q) {
             u32x4 fp[2][9];
 #pragma unroll
             for (int tap = 0; tap < 9; ++tap) fp[0][tap] = *(const u32x4*)(s2d + s1_rd[0][tap % 3] + (tap / 3) * (S2_SPITCH * 32));
-#ifdef ICAF_S2_PRIO
-            if (job0 + (S2_JPW - 1) * (S2_THREADS / 64) < S2_NJOBS) __builtin_amdgcn_s_setprio(ICAF_S2_PRIO);      // the waves with a third job
-#endif
 #pragma unroll
             for (int jj = 0; jj < S2_JPW; ++jj) {
                 if (job0 + jj * (S2_THREADS / 64) >= S2_NJOBS) break;             // (wave-uniform)
@@ -566,9 +563,6 @@ __global__ __launch_bounds__(S2_THREADS) void stem2_kernel(const Stem2P q) {
             }
         }
         S2_STAMP(3);
-#ifdef ICAF_S2_PRIO
-        __builtin_amdgcn_s_setprio(0);
-#endif
         lds_barrier();                             // halo patch visible; the space-to-depth patch is free
         S2_STAMP(4);
 

@@ -3,7 +3,7 @@
 run the same script twice with ICAF_LIB=<variant .so> / unset).
 
     python tools/build_variant.py <tag> [file=path_or_git_rev ...] [-DNAME=VALUE | -f<compiler flag> | <file>.hip:<flag for that file> ...]
-e.g. python tools/build_variant.py oldepi conv_common.h=HEAD igemm.hip=HEAD        python tools/build_variant.py epifast -DICAF_EPI_FAST=1
+e.g. python tools/build_variant.py oldepi conv_common.h=HEAD igemm.hip=HEAD        python tools/build_variant.py cwnodma -DICAF_CW_ABL=1
 writes icafusion_amd/lib/libicaf_<tag>.so (git-ignored, travels with the gpurun snapshot)."""
 import os
 import shutil

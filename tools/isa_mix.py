@@ -15,12 +15,12 @@ import csv
 import json
 import os
 import re
-import subprocess
 import sys
 import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+sys.path[:0] = [ROOT, os.path.join(ROOT, "tools")]
+import device_asm                      # noqa: E402
 from icafusion_amd import build as B   # noqa: E402
 
 
@@ -46,29 +46,18 @@ def classify(op):
 
 def asm_of(src, outdir):
     out = os.path.join(outdir, src.replace(".hip", ".s"))
-    flags = [c for c in B.COMMON if c not in ("-fPIC", "-fvisibility=hidden", "-Rpass-analysis=kernel-resource-usage")] + B.PER_FILE.get(src, [])
-    subprocess.run([B.hipcc()] + flags + ["-S", "--cuda-device-only", "-o", out, os.path.join(B.CSRC, src)], check=True, capture_output=True)
+    device_asm.compile_asm(B, os.path.join(B.CSRC, src), out)
     return out
 
 
 def kernels_of(path):
     """mangled kernel name -> Counter of instruction classes (amdhsa kernels only)"""
-    text = open(path).read()
-    names = set(re.findall(r"^\s*\.amdhsa_kernel\s+(\S+)", text, re.M))
-    res, cur = {}, None
-    for line in text.split("\n"):
-        m = re.match(r"^(\S+):\s*(;.*)?$", line)
-        if m and not line.startswith(".L"):
-            cur = m.group(1) if m.group(1) in names else None
-            if cur:
-                res[cur] = collections.Counter()
-            continue
-        t = line.strip()
-        if t.startswith(".Lfunc_end"):                 # (not the first s_endpgm: a kernel with a uniform early exit has several)
-            cur = None
-        if cur is None or not t or t[0] in ";." or t.endswith(":"):
-            continue
-        res[cur][classify(t.split()[0])] += 1
+    res = {}
+    for name, lines in device_asm.split_kernels(open(path).read())[0].items():
+        res[name] = collections.Counter()
+        for t in map(str.strip, lines[1:]):
+            if t and t[0] not in ";." and not t.endswith(":"):
+                res[name][classify(t.split()[0])] += 1
     return res
 
 
