@@ -105,6 +105,7 @@ SIGNATURES = {
                                    _f, _f, _f, _f, _p]),
     "icaf_layernorm": (_i, [_p, _p, _p, _p, _p, _p, _i, _ll, _i, _i, _f, _p]),
     "icaf_cross_attention": (_i, [_p, _p, _i, _i, _i, _i, _i, _p]),
+    "icaf_dmff_pool_config": (_i, [_i] * 11 + [C.POINTER(_i)] * 4),
     "icaf_cross_attention_config": (_i, [_i, _i, _i, _i, _i, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)]),
     "icaf_dmff_ln_qkv": (_i, [C.POINTER(DmffArgs), _p]),
     "icaf_dmff_attn_mlp": (_i, [C.POINTER(DmffArgs), _p]),

@@ -533,6 +533,32 @@ static int dispatch_attn(const void* qkv, void* out, int B, int N, int C, int he
     }
 }
 
+// The launch choice of icaf_dmff_pool_tokens — element kernel or the separable rows kernel, its rows in flight R and token rows per workgroup TR,
+// 32- or 64-bit flat index of the element kernel — made in ONE place for the launch and for icaf_dmff_pool_config (tests read it back there;
+// the probe knob index64 is part of the choice).
+struct PoolCfg { int kernel, R, TR, index64; size_t row_lds; };
+
+static int pool_select(int dtype, int B, int H, int W, int C, int th, int tw, int kh, int kw, int sh, int sw, PoolCfg& c) {
+    if (dtype < ICAF_F32 || dtype > ICAF_F16) return fail(ICAF_ERR_ARG, "bad dtype %d", dtype);
+    const int vec = dtype == ICAF_F32 ? 4 : 8;
+    if (C < 1 || C % vec) return fail(ICAF_ERR_ARG, "icaf_dmff_pool_tokens: C/ld must be multiples of %d", vec);
+    if (B < 1 || th < 1 || tw < 1 || sh < 1 || sw < 1) return fail(ICAF_ERR_ARG, "icaf_dmff_pool_tokens: bad B / token grid / stride");
+    if ((th - 1) * sh + kh > H || (tw - 1) * sw + kw > W || kh < 1 || kw < 1) return fail(ICAF_ERR_ARG, "icaf_dmff_pool_tokens: window exceeds the feature map");
+    c.row_lds = (size_t)W * (C / vec) * (vec * sizeof(float) + 16);  // one token row: fp32 column sums + packed column maxima
+    c.kernel = 0; c.R = 0; c.TR = 0; c.index64 = 0;
+    if ((kh > sh || kw > sw) && c.row_lds <= 160 * 1024) {           // overlapping windows: the separable rows kernel
+        // two token rows per workgroup when both fit the LDS, share input rows (kh > sh), are loaded in one batch and still leave a workgroup per CU
+        c.TR = (2 * c.row_lds <= 160 * 1024 && kh > sh && kh + sh <= 12 && 2 * B * ((th + 1) / 2) >= 256) ? 2 : 1;
+        const int nrow = kh + (c.TR - 1) * sh;
+        c.R = nrow <= 4 ? 4 : nrow <= 8 ? 8 : 12;                    // rows in flight per item
+        c.kernel = 1;
+        return ICAF_OK;
+    }
+    const long long total = 2LL * B * th * tw * (C / vec);
+    c.index64 = total >= (1ll << 31) || g_opt.index64 != 0;          // (probe knob: the 64-bit instantiation at a size a test can afford)
+    return ICAF_OK;
+}
+
 }  // namespace icaf
 
 using namespace icaf;
@@ -540,19 +566,14 @@ using namespace icaf;
 namespace {
 template <int DT>
 int run_pool_tokens(const void* f0, int ld0, const void* f1, int ld1, const float* p0, const float* p1, void* tok, int B, int H, int W, int C,
-                    int th, int tw, int kh, int kw, int sh, int sw, float a0, float b0, float a1, float b1, hipStream_t s) {
+                    int th, int tw, int kh, int kw, int sh, int sw, float a0, float b0, float a1, float b1, const PoolCfg& c, hipStream_t s) {
     using T = typename Elem<DT>::type;
-    constexpr int V = Elem<DT>::VEC;
-    const size_t row_lds = (size_t)W * (C / V) * (V * sizeof(float) + 16);      // one token row: fp32 column sums + packed column maxima
-    if ((kh > sh || kw > sw) && row_lds <= 160 * 1024) {             // overlapping windows: separable, TR token rows per workgroup
-        // two token rows per workgroup when both fit the LDS, share input rows (kh > sh), are loaded in one batch and still leave a workgroup per CU
-        const int tr = (2 * row_lds <= 160 * 1024 && kh > sh && kh + sh <= 12 && 2 * B * ((th + 1) / 2) >= 256) ? 2 : 1;
-        const size_t rows_lds = tr * row_lds;
+    if (c.kernel == 1) {                                             // overlapping windows: separable, TR token rows per workgroup
+        const int tr = c.TR, rsel = c.R == 4 ? 0 : c.R == 8 ? 1 : 2;
+        const size_t rows_lds = tr * c.row_lds;
         static size_t attr_bytes[ICAF_MAX_DEVICES][3][2] = {};   // per device and instantiation
         int dev = 0;
         ICAF_HIP(hipGetDevice(&dev));
-        const int nrow = kh + (tr - 1) * sh;
-        const int rsel = nrow <= 4 ? 0 : nrow <= 8 ? 1 : 2;      // rows in flight per item: 4 / 8 / 12
         const void* fns[3][2] = {{(const void*)pool_tokens_rows_kernel<DT, 4, 1>, (const void*)pool_tokens_rows_kernel<DT, 4, 2>},
                                  {(const void*)pool_tokens_rows_kernel<DT, 8, 1>, (const void*)pool_tokens_rows_kernel<DT, 8, 2>},
                                  {(const void*)pool_tokens_rows_kernel<DT, 12, 1>, (const void*)pool_tokens_rows_kernel<DT, 12, 2>}};
@@ -574,7 +595,7 @@ int run_pool_tokens(const void* f0, int ld0, const void* f1, int ld1, const floa
     }
     const long long total = 2LL * B * th * tw * (C / Elem<DT>::VEC);
     const PoolDiv dv{make_fastdiv((unsigned)(C / Elem<DT>::VEC)), make_fastdiv((unsigned)(th * tw)), make_fastdiv((unsigned)tw)};
-    if (total < (1ll << 31))
+    if (!c.index64)
         pool_tokens_kernel<DT, true><<<dim3(grid_for(total)), dim3(256), 0, s>>>((const T*)f0, ld0, (const T*)f1, ld1, p0, p1, (T*)tok, B, H, W, C,
                                                                                   th, tw, kh, kw, sh, sw, a0, b0, a1, b1, dv);
     else
@@ -618,9 +639,22 @@ extern "C" int icaf_dmff_pool_tokens(const void* fea_rgb, int ld_rgb, const void
     if (!fea_rgb || !fea_ir || !pos_rgb || !pos_ir || !tokens) return fail(ICAF_ERR_ARG, "icaf_dmff_pool_tokens: null pointer");
     const int vec = dtype == ICAF_F32 ? 4 : 8;
     if (C % vec || ld_rgb % vec || ld_ir % vec) return fail(ICAF_ERR_ARG, "icaf_dmff_pool_tokens: C/ld must be multiples of %d", vec);
-    if ((th - 1) * sh + kh > H || (tw - 1) * sw + kw > W || kh < 1 || kw < 1) return fail(ICAF_ERR_ARG, "icaf_dmff_pool_tokens: window exceeds the feature map");
+    PoolCfg c;
+    if (const int st = pool_select(dtype, B, H, W, C, th, tw, kh, kw, sh, sw, c)) return st;
     DISPATCH_DT(dtype, run_pool_tokens, fea_rgb, ld_rgb, fea_ir, ld_ir, pos_rgb, pos_ir, tokens, B, H, W, C, th, tw, kh, kw, sh, sw, w1_rgb,
-                w2_rgb, w1_ir, w2_ir, S(s));
+                w2_rgb, w1_ir, w2_ir, c, S(s));
+}
+
+extern "C" int icaf_dmff_pool_config(int dtype, int B, int H, int W, int C, int th, int tw, int kh, int kw, int sh, int sw, int* kernel, int* R,
+                                     int* TR, int* index64) {
+    if (!kernel || !R || !TR || !index64) return fail(ICAF_ERR_ARG, "icaf_dmff_pool_config: null pointer");
+    PoolCfg c;
+    if (const int st = pool_select(dtype, B, H, W, C, th, tw, kh, kw, sh, sw, c)) return st;
+    *kernel = c.kernel;
+    *R = c.R;
+    *TR = c.TR;
+    *index64 = c.index64;
+    return ICAF_OK;
 }
 
 extern "C" int icaf_layernorm(const void* x, void* y, const float* gamma0, const float* beta0, const float* gamma1, const float* beta1,

@@ -393,7 +393,7 @@ extern "C" int icaf_upsample_nearest(const void* x, int ldx, void* y, int ldy, i
     if (total < 1) return fail(ICAF_ERR_ARG, "icaf_upsample_nearest: empty tensor");
     const UpsampleDiv dv{make_fastdiv((unsigned)(C / vec)), make_fastdiv((unsigned)(W * scale)), make_fastdiv((unsigned)(H * scale)),
                          make_fastdiv((unsigned)scale)};
-    if (total < (1ll << 31))
+    if (total < (1ll << 31) && !g_opt.index64)                       // (probe knob index64: the 64-bit instantiation at a size a test can afford)
         hipLaunchKernelGGL(upsample_kernel<true>, dim3(grid_for(total)), dim3(256), 0, S(s), (const u32x4*)x, ldx / vec, (u32x4*)y,
                            ldy / vec, B, H, W, C / vec, scale, dv);
     else

@@ -600,6 +600,14 @@ def dmff_pool_tokens(fea_rgb, fea_ir, pos_rgb, pos_ir, tokens, th, tw, kh, kw, s
                   keep=(fea_rgb, fea_ir, pos_rgb, pos_ir, tokens), name=name, nbytes=nb)
 
 
+def dmff_pool_config(dtype, B, H, W, Cc, th, tw, kh, kw, sh, sw):
+    """dict(kernel 0 = element / 1 = rows, R rows in flight, TR token rows per workgroup, index64) icaf_dmff_pool_tokens picks for this geometry,
+    the probe knob index64 included."""
+    v = [C.c_int(-1) for _ in range(4)]
+    check(lib().icaf_dmff_pool_config(dtype_code(dtype), B, H, W, Cc, th, tw, kh, kw, sh, sw, *(C.byref(x) for x in v)), "icaf_dmff_pool_config")
+    return dict(zip(("kernel", "R", "TR", "index64"), (x.value for x in v)))
+
+
 def layernorm(x, y, g0, b0, g1, b1, eps=1e-5, name="layernorm"):
     """x, y: (G, rows, C) contiguous; group g normalised with (g_g, b_g) fp32 vectors."""
     G, rows, Cc = x.shape

@@ -51,6 +51,7 @@ class PlanOptions:
     detect_elementwise: bool = _f(False, "ICAF_DETECT_ELEMENTWISE", "Detect decode by the one-thread-per-element kernel", lib=True)
     attn_qsplit: int = _f(0, "ICAF_ATTN_QSPLIT", "query splits per head of the attention kernel (0 = automatic)", lib=True)
     sppf_vpb: int = _f(0, "ICAF_SPPF_VPB", "channel vectors per workgroup of the SPPF kernel (0 = automatic)", lib=True)
+    index64: bool = _f(False, "ICAF_INDEX64", "token pooling (element kernel) and nearest upsample launch their 64-bit-index instantiations", lib=True)
 
     @staticmethod
     def _parse(f, text):

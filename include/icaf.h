@@ -38,8 +38,9 @@ const char* icaf_last_error(void);
 /* Probe knobs of the library, set by the host's one options object (icafusion_amd/options.py) when the library is loaded — the library reads no
  * environment variable: "detect_elementwise" (!= 0: icaf_detect_decode by the one-thread-per-element kernel), "attn_qsplit" (n > 0: query splits per
  * head of icaf_cross_attention), "sppf_vpb" (n > 0: cap on the channel vectors per workgroup of icaf_sppf_pool), "letterbox_direct" (!= 0:
- * icaf_letterbox_frames taps global memory in every tile instead of staging in LDS; set by a caller for an A/B, not by the options object);
- * 0 = the library's own choice.
+ * icaf_letterbox_frames taps global memory in every tile instead of staging in LDS; set by a caller for an A/B, not by the options object),
+ * "index64" (!= 0: the element kernel of icaf_dmff_pool_tokens and icaf_upsample_nearest launch the 64-bit-index instantiations they otherwise
+ * keep for 2^31 vectors and more); 0 = the library's own choice.
  * ICAF_ERR_ARG for an unknown name.  None of them changes a result. */
 int icaf_set_option(const char* name, int value);
 int icaf_version(void);
@@ -247,6 +248,11 @@ int icaf_dmff_pool_tokens(const void* fea_rgb, int ld_rgb, const void* fea_ir, i
                           const float* pos_ir, void* tokens, int dtype, int B, int H, int W, int C, int th, int tw,
                           int kh, int kw, int sh, int sw, float w1_rgb, float w2_rgb, float w1_ir, float w2_ir,
                           icaf_stream_t s);
+/* launch choice of icaf_dmff_pool_tokens for this geometry (same argument checks): *kernel = 0 (one thread per token element) / 1 (separable
+ * rows kernel, overlapping windows whose token row fits the LDS); rows kernel: *R = input rows in flight per item (4 / 8 / 12), *TR = token rows
+ * per workgroup (1 / 2), else 0; element kernel: *index64 = 1 when the 64-bit-index instantiation runs (the probe knob "index64" included) */
+int icaf_dmff_pool_config(int dtype, int B, int H, int W, int C, int th, int tw, int kh, int kw, int sh, int sw, int* kernel, int* R,
+                          int* TR, int* index64);
 int icaf_layernorm(const void* x, void* y, const float* gamma0, const float* beta0, const float* gamma1,
                    const float* beta1, int dtype, long long rows_per_group, int C, int groups, float eps,
                    icaf_stream_t s);

@@ -422,3 +422,434 @@ def out_hw(H, W, k, s, p):
 def shape_seed(name, dt, g=0):
     """Seed of the lattice operands of (shape, dtype, group): a function of the NAME, so adding a shape leaves the others' data alone."""
     return zlib.crc32(name.encode()) % 100000 * 100 + 10 * [F32, BF16, F16].index(dt) + g
+
+
+# ====================================================================================================================================
+# pooling, resize and merge kernels (dmff.hip: pool_tokens, upsample_merge; pool.hip: upsample_nearest, copy, axpby, staging).
+# Everything below is NHWC on the CPU: features (B, H, W, C), tokens (B, th * tw, C), pairs with the modality in front.
+# ====================================================================================================================================
+SECOND = 1.0 + 2.0 ** -10        # every budget below is first order in u = 2^-24; the products of two roundings it drops are < 2^-20 of it
+W_DYADIC, W_REAL = (0.5, 0.25), (0.4, 0.7)           # LearnableWeights pairs: exact in every type / what a checkpoint holds
+GRID_MAX = 4096                                      # grid_for(): at most this many workgroups of 256 threads ...
+STRIDE_ITEMS = GRID_MAX * 256                        # ... so vector items from 2^20 on belong to the second pass of the grid-stride loop
+FEA_GRID = {BF16: 6, F32: 6, F16: 9}                 # residual features of the merge: j / 2^s with |j| <= 4 * 2^s — representable, and the
+                                                     # sum with an interpolated integer needs more bits than the type keeps
+
+
+def f32w(w):
+    """The float the library receives for a Python weight, as an fp64 number."""
+    return float(torch.tensor(w, dtype=F32))
+
+
+def _gen(seed):
+    return torch.Generator().manual_seed(seed)
+
+
+def rnd(shape, seed, scale=1.0):
+    """The Gaussian inputs of tests/test_gpu_kernels.py (same generator), for the self-test's record of what close() accepts on them."""
+    import numpy as np
+    return torch.from_numpy(np.random.default_rng(seed).normal(0, scale, shape).astype(np.float32))
+
+
+def pool_lattice(B, H, W, C, N, seed):
+    """Lattice operands of one pooling launch for ONE modality: x integers in [-8, 8] — channels c % 4 == 1 hold ONLY negative values
+    (-8 .. -1), so a maximum that starts at 0 instead of -inf shows in every window — and pos = j / 1024, |j| <= 4096 (fp32, dyadic: ten fractional
+    bits, more than either 16-bit type keeps beside an integer part, so the stored token is a rounded one also where the arithmetic is exact)."""
+    g = _gen(seed)
+    x = torch.randint(-8, 9, (B, H, W, C), generator=g).float()
+    neg = torch.randint(-8, 0, (B, H, W, C), generator=g).float()
+    x[..., 1::4] = neg[..., 1::4]
+    pos = torch.randint(-4096, 4097, (N, C), generator=g).float() / 1024.0
+    return x, pos
+
+
+def _edges(n, t, k, s, R=12):
+    """Rows (or columns) of an n-long axis on both sides of every window boundary of the first, second and last token row (t rows,
+    window k, stride s), the two ends of the axis, and — for a window taller than the R rows a workgroup keeps in flight — both sides
+    of every R-chunk boundary of the first and the last window.  The rows two consecutive token rows share ([s, k)) are among them."""
+    out = {0, n - 1}
+    for i in {0, min(1, t - 1), t - 1}:
+        a, b = i * s, i * s + k - 1
+        out |= {a - 1, a, b, b + 1}
+        for c in range(R, k, R):
+            out |= {a + c - 1, a + c}
+    return sorted(v for v in out if 0 <= v < n)
+
+
+def probe_pixels(H, W, th, tw, kh, kw, sh, sw):
+    """The pixels a membership probe must sit on: the four corners, and every interesting row paired with every interesting column at
+    least once (rows and columns cycled against each other)."""
+    ry, cx = _edges(H, th, kh, sh), _edges(W, tw, kw, sw)
+    px = [(0, 0), (0, W - 1), (H - 1, 0), (H - 1, W - 1)]
+    px += [(ry[i % len(ry)], cx[i % len(cx)]) for i in range(max(len(ry), len(cx)))]
+    px += [(ry[i % len(ry)], cx[(i + len(cx) // 2) % len(cx)]) for i in range(max(len(ry), len(cx)))]      # a second column per row
+    return list(dict.fromkeys(px)), ry, cx
+
+
+def pool_probes(B, H, W, C, geom, g):
+    """Membership probes of modality g: channel c of image b is zero except at ONE pixel p(b, c), which holds a power of two
+    (2^-2 .. 2^2).  The first len(probe_pixels) slots (b, c) take the listed pixels (rotated by modality), the others seeded ones.
+    With w = (0, 1), pos = 0 a token is that power of two if its window covers the pixel and +0 otherwise — in every type."""
+    px, ry, cx = probe_pixels(H, W, *geom)
+    assert B * C >= len(px), f"{len(px)} probe pixels need more than {B * C} (image, channel) slots"
+    gen = _gen(9000 + 10 * H + W + g)
+    x = torch.zeros((B, H, W, C))
+    where = []
+    for i in range(B * C):
+        b, c = divmod(i, C)
+        y, xx = px[(i + 7 * g) % len(px)] if i < len(px) else (int(torch.randint(0, H, (1,), generator=gen)), int(torch.randint(0, W, (1,), generator=gen)))
+        x[b, y, xx, c] = 2.0 ** (i % 5 - 2)
+        where.append((y, xx))
+    assert set(px) <= set(where)
+    return x
+
+
+def windows(x, geom):
+    """(B, th, tw, C, kh, kw) view of the pooling windows of x (B, H, W, C)."""
+    th, tw, kh, kw, sh, sw = geom
+    assert (th - 1) * sh + kh <= x.shape[1] and (tw - 1) * sw + kw <= x.shape[2]
+    return x[:, :(th - 1) * sh + kh, :(tw - 1) * sw + kw].unfold(1, kh, sh).unfold(2, kw, sw)
+
+
+def pool_stats64(x, geom):
+    """fp64 (mean, max) over the explicit windows of x (B, H, W, C), each (B, th * tw, C)."""
+    win = windows(x.double(), geom)
+    B, th, tw, C = win.shape[:4]
+    avg = win.sum((-2, -1)) / float(geom[2] * geom[3])
+    return avg.reshape(B, th * tw, C), win.amax((-2, -1)).reshape(B, th * tw, C)
+
+
+def pool64(x, geom, w, pos, stats=None):
+    """fp64 reference of pool_tokens for one modality: (avg, max, w1 * avg + w2 * max + pos), each (B, th * tw, C); w as the library
+    receives it (fp32 values), windows explicit."""
+    avg, mx = stats if stats is not None else pool_stats64(x, geom)
+    return avg, mx, f32w(w[0]) * avg + f32w(w[1]) * mx + pos.double()
+
+
+def is_f32(x64):
+    return bool(torch.equal(x64.float().double(), x64))
+
+
+def pool_is_exact(avg, mx, w, pos, area):
+    """True when every step of the device expression (sum * inv_area) * w1 + mx * w2 + pos is exact in fp32 on this data, so that the
+    expected tokens are RNE(reference) bit for bit: the window sums are integers / dyadic (exact in any order), 1 / area is exact for a
+    power-of-two area or irrelevant when w1 = 0 (finite * 0 = 0), and each product and partial sum is an fp32 number."""
+    w1, w2 = f32w(w[0]), f32w(w[1])
+    if w1 != 0.0 and area & (area - 1):
+        return False
+    steps = ([avg, w1 * avg] if w1 != 0.0 else []) + [w2 * mx, w1 * avg + w2 * mx, w1 * avg + w2 * mx + pos.double()]
+    return all(is_f32(s) for s in steps)
+
+
+def pool_budget32(avg, mx, w, ref):
+    """fp32 budget of pool_tokens' o = (sum * inv_area) * w1 + mx * w2 + pos on lattice data (the window sum is exact), u = 2^-24:
+      inv_area = 1.0f / area        one rounding                                 u |w1 avg|
+      sum * inv_area                one rounding                                 u |w1 avg|
+      (..) * w1                     one rounding                                 u |w1 avg|
+      mx * w2                       one rounding (mx itself is an input: exact)  u |w2 mx|
+      (..) + (..)                   one rounding of the partial sum              u |w1 avg + w2 mx|
+      (..) + pos                    one rounding of the result                   u |ref|
+    A contraction to fma removes the rounding of the product it absorbs and adds none, so the count holds for either choice."""
+    w1, w2 = f32w(w[0]), f32w(w[1])
+    a, m = (w1 * avg).abs(), (w2 * mx).abs()
+    return U32 * (3.0 * a + m + (w1 * avg + w2 * mx).abs() + ref.abs()) * SECOND + SUB32
+
+
+def _axis64(n_out, n_in):
+    """fp64 source coordinate of align_corners=False resizing along one axis: (unclamped f, i0, i1, fraction)."""
+    fu = (torch.arange(n_out, dtype=torch.float64) + 0.5) * (n_in / n_out) - 0.5
+    f = fu.clamp(min=0.0)
+    i0 = f.floor().long().clamp(max=n_in - 1)
+    return fu, i0, (i0 + 1).clamp(max=n_in - 1), f - i0
+
+
+def merge64(tok, fea, dt, need_bound=True):
+    """fp64 reference and per-element bound of upsample_merge.  tok (2, B, th, tw, C), fea (2, B, H, W, C) -> ref, bound (B, H, W, 2C):
+    out[..., g*C + c] = bilinear(tok[g]) + fea[g], align_corners=False with clamped neighbours.
+
+    Budget (device expression: top = a00 (1 - lx) + a01 lx, bot likewise, o = (top (1 - ly) + bot ly) + r; u = 2^-24; M = the largest
+    magnitude among the four neighbours):
+      1 - lx                        one rounding, times |a00|                              <= u M
+      the two products and the sum  u (|a00| (1 - lx) + |a01| lx) + u |top|                <= 2u M        -> top, bot carry 3u M each
+      the vertical lerp             the same three terms on top / bot, plus their own errors weighted (1 - ly) + ly = 1:  6u M in all
+      + r                           one rounding of the result                             u |ref|
+      coordinates                   fy = fl(fl((h + 0.5) fl(th / H)) - 0.5): the ratio and the product carry u each relative to
+                                    (h + 0.5) th / H = f + 0.5, the subtraction u |f|:  |fy - f| <= dy = 3u (|f| + 1); fx likewise.  ly = fy - y0 is
+                                    exact (fy < 2^24 and y0 = floor fy).  Bilinear interpolation is continuous and piecewise linear in (fy, fx),
+                                    so the device value differs from the one at the true coordinate by at most slope * d, ALSO when fy lands on the
+                                    other side of an integer (where the slope is that of the adjacent cell): slope_y = the largest
+                                    |difference of vertically adjacent, horizontally interpolated rows| among rows y0 - 1 .. y1 + 1, slope_x likewise;
+                                    the mixed term is bounded by 4 M dy dx.
+    At dyadic ratios (identity, x2, x4, th = 1 with H a power of two) fy and every weight are exact and tests compare bits instead."""
+    _, B, th, tw, C = tok.shape
+    H, W = fea.shape[2], fea.shape[3]
+    T, Fe = tok.double(), fea.double()
+    fyu, y0, y1, ly = _axis64(H, th)
+    fxu, x0, x1, lx = _axis64(W, tw)
+    ly_, lx_ = ly.view(1, 1, H, 1, 1), lx.view(1, 1, 1, W, 1)
+    at = lambda ys, xs: T[:, :, ys][:, :, :, xs]                                   # (2, B, H, W, C)
+    hrow = lambda ys: at(ys, x0) * (1 - lx_) + at(ys, x1) * lx_                    # row ys interpolated horizontally
+    vcol = lambda xs: at(y0, xs) * (1 - ly_) + at(y1, xs) * ly_
+    v0, v1 = hrow(y0), hrow(y1)
+    interp = v0 * (1 - ly_) + v1 * ly_
+    ref = interp + Fe
+    if not need_bound:                                                             # (exact-bits cases of tens of MB)
+        return torch.cat((ref[0], ref[1]), -1), None
+    ym, yp, xm, xp = (y0 - 1).clamp(min=0), (y1 + 1).clamp(max=th - 1), (x0 - 1).clamp(min=0), (x1 + 1).clamp(max=tw - 1)
+    slope_y = torch.stack(((v1 - v0).abs(), (v0 - hrow(ym)).abs(), (hrow(yp) - v1).abs())).amax(0)
+    u0, u1 = vcol(x0), vcol(x1)
+    slope_x = torch.stack(((u1 - u0).abs(), (u0 - vcol(xm)).abs(), (vcol(xp) - u1).abs())).amax(0)
+    M = torch.stack((at(y0, x0).abs(), at(y0, x1).abs(), at(y1, x0).abs(), at(y1, x1).abs())).amax(0)
+    dy = (3.0 * U32 * (fyu.abs() + 1.0)).view(1, 1, H, 1, 1)
+    dx = (3.0 * U32 * (fxu.abs() + 1.0)).view(1, 1, 1, W, 1)
+    b32 = (U32 * (6.0 * M + ref.abs()) + slope_y * dy + slope_x * dx + 4.0 * M * dy * dx) * SECOND + SUB32
+    cat = lambda t: torch.cat((t[0], t[1]), -1)
+    ref, b32 = cat(ref), cat(b32)
+    return ref, storage_bound(ref, b32, dt)
+
+
+def merge_lattice(dt, B, H, W, C, th, tw, seed):
+    """Lattice operands of one merge launch: tokens integers in [-8, 8] (2, B, th, tw, C), features j / 2^s on FEA_GRID (2, B, H, W, C)."""
+    g = _gen(seed)
+    s = FEA_GRID[dt]
+    tok = torch.randint(-8, 9, (2, B, th, tw, C), generator=g).float()
+    fea = torch.randint(-4 * 2 ** s, 4 * 2 ** s, (2, B, H, W, C), generator=g).float() / 2 ** s
+    assert torch.equal(fea.to(dt).float(), fea) and torch.equal(tok.to(dt).float(), tok)
+    return tok, fea
+
+
+def nearest64(x, scale):
+    """nn.Upsample(scale, 'nearest') of x (B, H, W, C): out[ho, wo] = x[ho // scale, wo // scale]."""
+    B, H, W, C = x.shape
+    return x[:, torch.arange(H * scale) // scale][:, :, torch.arange(W * scale) // scale]
+
+
+def axpby_lattice(dt, shape, seed):
+    """Two integer operands for y = 128 x0 - 127 x1: |x| <= 8 (fp16: <= 64, so that the sums need more than its 11 bits).  Every product
+    and sum is an integer below 2^24: exact in fp32, so the stored bits are RNE of the true value."""
+    g, hi = _gen(seed), 64 if dt == F16 else 8
+    return tuple(torch.randint(-hi, hi + 1, shape, generator=g).float() for _ in range(2))
+
+
+def axpby64(x0, x1, a, b, dt):
+    """fp64 reference and bound of y = x0 * a + x1 * b (fp32 a, b): two products and one sum, u (|a x0| + |b x1| + |ref|); an fma
+    drops one of the three roundings."""
+    a, b = f32w(a), f32w(b)
+    p0, p1 = a * x0.double(), b * x1.double()
+    ref = p0 + p1
+    return ref, storage_bound(ref, U32 * (p0.abs() + p1.abs() + ref.abs()) * SECOND + SUB32, dt)
+
+
+def stage64(img, mode, cpad):
+    """The two staging layouts of an NCHW image batch (B, C, H, W) -> (B, H', W', cpad), fp64, channel padding zero: mode 0 = NHWC,
+    mode 1 = space-to-depth: channel sub * C + c with sub = 2 dy + dx taken from pixel (2 ho + dy, 2 wo + dx)."""
+    x = img.double()
+    B, C, H, W = x.shape
+    if mode == 1:
+        x = torch.cat([x[:, :, dy::2, dx::2] for dy in (0, 1) for dx in (0, 1)], 1)
+    x = x.permute(0, 2, 3, 1)
+    out = torch.zeros((*x.shape[:3], cpad), dtype=torch.float64)
+    out[..., :x.shape[3]] = x
+    return out
+
+
+def u8_expected(dt):
+    """Expected staged value of every uint8 level, in `dt`: RNE_dt of the fp32 quotient v / 255 (a true division, correctly rounded —
+    the fp64 quotient rounded to fp32 is asserted to be the same number, so there is no double-rounding case among the 256)."""
+    v = torch.arange(256, dtype=F32)
+    q32 = v / 255.0
+    assert torch.equal((v.double() / 255.0).float(), q32)
+    return q32.to(dt)
+
+
+def inexact_share(ref, dt):
+    """Share of the fp64 results that `dt` cannot represent (0 for fp32 by convention: budgets there are about the arithmetic)."""
+    if dt == F32:
+        return 0.0
+    r = ref.float().to(dt).double()
+    return float((r != ref).double().mean())
+
+
+def assert_rounding_exercised(ref, dt, what, least=0.05):
+    """A 16-bit check is worth something only if rounding happens: at least `least` of the results are not representable."""
+    share = inexact_share(ref, dt)
+    print(f"{what} {dt}: not representable {share:.3f}")
+    assert dt == F32 or share >= least, f"{what}: only {share:.4f} of the results need rounding in {dt}"
+    return share
+
+
+def check_pool(got, avg, mx, ref, w, pos, geom, dt, what):
+    """The check of one modality's tokens: the expected bits where every device step is exact (pool_is_exact), the counted budget
+    otherwise.  Returns the largest err / bound (0 stands for "bit-identical")."""
+    if pool_is_exact(avg, mx, w, pos, geom[2] * geom[3]):
+        assert_same_bits(got, rne(ref, dt) + 0.0, what)
+        return 0.0
+    return assert_budget(got, ref, storage_bound(ref, pool_budget32(avg, mx, w, ref), dt), what, signed=False)
+
+
+def check_merge(got, ref, bound, exact, dt, what):
+    if exact:
+        assert_same_bits(got, rne(ref, dt) + 0.0, what)
+        return 0.0
+    return assert_budget(got, ref, bound, what, signed=False)
+
+
+class PoisonedFlat:
+    """A contiguous tensor of `shape` in the middle of a flat buffer whose every other element holds `fill_bits` (operands without a
+    pixel stride: images, staged outputs, token arrays).  content None: the tensor itself holds the pattern too (an output)."""
+
+    def __init__(self, shape, dt, device, fill_bits, content=None, guard=64):
+        n = math.prod(shape)
+        self.buf = torch.empty((n + 2 * guard,), dtype=dt, device=device)
+        if dt == torch.uint8:
+            self.buf.fill_(fill_bits)
+        else:
+            bits(self.buf).fill_(fill_bits)
+        self.g, self.n = guard, n
+        self.view = self.buf[guard:guard + n].view(shape)
+        if content is not None:
+            self.view.copy_(content)
+        self.before = self.buf.clone()
+
+    def assert_outside_intact(self, what=""):
+        raw = (lambda t: t) if self.buf.dtype == torch.uint8 else bits
+        now, was = raw(self.buf), raw(self.before)
+        ne = now != was
+        ne[self.g:self.g + self.n] = False
+        assert not bool(ne.any()), f"{what}: {int(ne.sum())} elements around the tensor changed; first at flat index {_first(ne)}"
+
+
+# ---- torch emulations (fp32 arithmetic in the device's order, then RNE to storage); defects are planted here --------------------------
+def _store(x32, dt, defect):
+    return truncate(x32, dt) if defect == "trunc" and dt != F32 else x32.to(dt)
+
+
+def emulate_pool(x, geom, w, pos, dt, defect=None):
+    """pool_tokens for one modality.  x (B, H, W, C) fp32 holding `dt` values -> (B, th * tw, C) in dt.  defect: None | "lastcol" (the last
+    token column's window starts one pixel early) | "row12" (input row 12 of the window dropped) | "duprow" (the window's last row — the
+    clamped duplicate load — added twice) | "max0" (maximum starts at 0) | "short" (last token row of an odd th unwritten: NaN) |
+    "pos_nb" (pos of the next token) | "trunc"."""
+    th, tw, kh, kw, sh, sw = geom
+    win = windows(x, geom)
+    if defect == "lastcol":
+        win = win.clone()
+        c0 = (tw - 1) * sw - 1
+        win[:, :, tw - 1] = windows(x[:, :, c0:c0 + kw], (th, 1, kh, kw, sh, sw))[:, :, 0]
+    rows = [r for r in range(kh) if not (defect == "row12" and r == 12)]
+    B, C = x.shape[0], x.shape[3]
+    s = win[..., rows, :].sum((-2, -1))
+    m = win[..., rows, :].amax((-2, -1))
+    if defect == "duprow":
+        s = s + win[..., kh - 1, :].sum(-1)
+    if defect == "max0":
+        m = m.clamp(min=0.0)
+    p = pos.roll(-1, 0) if defect == "pos_nb" else pos
+    inv = torch.tensor(1.0, dtype=F32) / torch.tensor(float(kh * kw), dtype=F32)
+    o = (s.reshape(B, th * tw, C) * inv) * torch.tensor(w[0], dtype=F32) + m.reshape(B, th * tw, C) * torch.tensor(w[1], dtype=F32) + p
+    out = _store(o, dt, defect)
+    if defect == "short":
+        assert th % 2 == 1
+        out.view(B, th, tw, C)[:, th - 1] = float("nan")
+    return out
+
+
+def emulate_merge(tok, fea, dt, defect=None):
+    """upsample_merge: tok (2, B, th, tw, C), fea (2, B, H, W, C), fp32 holding `dt` values -> (B, H, W, 2C) in dt.  defect: None | "swap"
+    (each modality interpolates the OTHER one's tokens) | "align" (half-pixel offset dropped: align_corners behaviour) | "noclamp" (the right
+    neighbour of the last column is the next token in memory) | "trunc"."""
+    _, B, th, tw, C = tok.shape
+    H, W = fea.shape[2], fea.shape[3]
+    f32 = lambda v: torch.tensor(float(v), dtype=F32)
+
+    def axis(n_out, n_in):
+        if defect == "align":
+            f = torch.arange(n_out, dtype=F32) * (f32(n_in - 1) / f32(max(n_out - 1, 1)))
+        else:
+            f = (torch.arange(n_out, dtype=F32) + 0.5) * (f32(n_in) / f32(n_out)) - 0.5
+        f = f.clamp(min=0.0)
+        i0 = f.to(torch.int64).clamp(max=n_in - 1)
+        return i0, (i0 + 1).clamp(max=n_in - 1), f - i0.float()
+
+    y0, y1, ly = axis(H, th)
+    x0, x1, lx = axis(W, tw)
+    T = tok.flip(0) if defect == "swap" else tok
+    flat = T.reshape(2, B * th * tw, C)
+    last = B * th * tw - 1
+
+    def at(ys, xs, right):
+        n = ys.view(H, 1) * tw + (x0 + 1 if (right and defect == "noclamp") else xs).view(1, W)        # token index inside the image
+        idx = (torch.arange(B).view(B, 1, 1) * (th * tw) + n.view(1, H, W)).clamp(max=last)
+        return flat[:, idx]                                                                          # (2, B, H, W, C)
+
+    lx_, ly_ = lx.view(1, 1, 1, W, 1), ly.view(1, 1, H, 1, 1)
+    top = at(y0, x0, False) * (1.0 - lx_) + at(y0, x1, True) * lx_
+    bot = at(y1, x0, False) * (1.0 - lx_) + at(y1, x1, True) * lx_
+    o = (top * (1.0 - ly_) + bot * ly_) + fea
+    return _store(torch.cat((o[0], o[1]), -1), dt, defect)
+
+
+def emulate_nearest(x, scale, defect=None):
+    """upsample_nearest; defect "ceil": source index ceil(ho / scale) instead of floor."""
+    if defect != "ceil":
+        return nearest64(x, scale)
+    B, H, W, C = x.shape
+    iy = (-(-torch.arange(H * scale) // scale)).clamp(max=H - 1)
+    ix = (-(-torch.arange(W * scale) // scale)).clamp(max=W - 1)
+    return x[:, iy][:, :, ix]
+
+
+def emulate_axpby(x0, x1, a, b, dt, defect=None):
+    return _store(x0 * torch.tensor(a, dtype=F32) + x1 * torch.tensor(b, dtype=F32), dt, defect)
+
+
+def first_pass_only(out, prefill, dt):
+    """The defect of a grid-stride loop that never takes its second step: vector items from STRIDE_ITEMS on keep the prefill."""
+    flat = out.reshape(-1, VEC[dt]).clone()
+    assert flat.shape[0] > STRIDE_ITEMS, "the case has no second pass"
+    flat[STRIDE_ITEMS:] = prefill
+    return flat.reshape(out.shape)
+
+
+# ---- geometries of tests/test_gpu_exact_pool.py (here, so that the CPU self-test can check them) ---------------------------------------
+# name: (B, H, W, C, (th, tw, kh, kw, sh, sw), expected {dtype: (kernel, R, TR)}, flags).  Grids: rows kernel 2 * B * ceil(th / TR) workgroups.
+ELEM, ROWS = 0, 1
+_ALL = lambda k, r, t: {F32: (k, r, t), BF16: (k, r, t), F16: (k, r, t)}
+POOL_GEOMS = {
+    "r4tr1":     (1, 9, 11, 32, (7, 9, 3, 3, 1, 1), _ALL(ROWS, 4, 1), {}),                  # kh 3, sh 1; 14 workgroups (not a multiple of 8)
+    "r4tr2":     (16, 18, 12, 32, (16, 10, 3, 3, 1, 1), _ALL(ROWS, 4, 2), {}),              # the same window, 2 * 16 * 8 = 256 workgroups
+    "r8tr1":     (1, 11, 13, 32, (4, 5, 5, 5, 2, 2), _ALL(ROWS, 8, 1), {}),                 # kh 5, sh 2; 8 workgroups
+    "r8tr2":     (16, 35, 13, 32, (16, 5, 5, 5, 2, 2), _ALL(ROWS, 8, 2), {}),
+    "r12tr2":    (16, 40, 40, 32, (16, 16, 10, 10, 2, 2), _ALL(ROWS, 12, 2), {}),           # the default workload's P4 window
+    "r12tr1":    (1, 40, 40, 32, (16, 16, 10, 10, 2, 2), _ALL(ROWS, 12, 1), {}),
+    "chunks2":   (1, 31, 20, 32, (16, 16, 16, 5, 1, 1), _ALL(ROWS, 12, 1), {}),             # window taller than R: two chunks, clamped duplicates
+    "chunks3":   (1, 27, 10, 32, (3, 4, 25, 4, 1, 2), _ALL(ROWS, 12, 1), {}),               # kh 25: three chunks, the last holds one row; 6 workgroups
+    "horiz":     (1, 12, 14, 32, (4, 5, 3, 6, 3, 2), _ALL(ROWS, 4, 1), {}),                 # kh == sh, kw > sw: only the columns overlap
+    "oddth":     (32, 30, 33, 32, (7, 9, 6, 9, 4, 3), _ALL(ROWS, 12, 2), {}),               # TR 2 with th = 7: the last block of an image is short
+    "wrap":      (1, 8, 40, 256, (3, 19, 4, 4, 2, 2), _ALL(ROWS, 4, 1), {}),                # W * nv = 1280 (16 bit) / 2560 items: the item loop wraps
+    "hphase":    (16, 18, 70, 64, (16, 68, 3, 3, 1, 1), _ALL(ROWS, 4, 2), {}),              # 2 * 68 * nv = 1088 / 2176 outputs in the horizontal phase
+    "f32edge":   (1, 6, 40, 512, (3, 20, 4, 2, 1, 2), _ALL(ROWS, 4, 1), {}),                # fp32: one token row needs 163,840 bytes, the <= boundary
+    "f32over":   (1, 6, 41, 512, (3, 20, 4, 3, 1, 2), {F32: (ELEM, 0, 0), BF16: (ROWS, 4, 1), F16: (ROWS, 4, 1)}, {}),      # one more column: fp32 falls to the element kernel, windows overlapping
+    "e4x4":      (2, 16, 20, 32, (4, 5, 4, 4, 4, 4), _ALL(ELEM, 0, 0), dict(idx64=True)),   # non-overlapping 4 x 4
+    "ekw3":      (1, 9, 12, 32, (3, 4, 3, 3, 3, 3), _ALL(ELEM, 0, 0), dict(idx64=True)),    # kw 3: the four-wide load batch has a tail of three
+    "ekw6":      (1, 8, 19, 64, (4, 3, 2, 6, 2, 6), _ALL(ELEM, 0, 0), {}),                  # kw 6: one full batch and a tail of two
+    "e1x1":      (2, 5, 7, 32, (5, 7, 1, 1, 1, 1), _ALL(ELEM, 0, 0), dict(idx64=True)),     # identity
+    "ebig":      (11, 80, 80, 128, (80, 40, 1, 2, 1, 2), _ALL(ELEM, 0, 0), dict(big=True)), # 2 * 11 * 3200 * nv = 1,126,400 (16 bit) items > 2^20: second pass
+}
+# readback only: 2 * B * ceil(th / 2) on both sides of the 256 workgroups that two token rows per workgroup must leave
+TR_THRESHOLD = [((16, 18, 12, 32, (16, 10, 3, 3, 1, 1)), 2), ((128, 3, 12, 32, (1, 10, 3, 3, 1, 1)), 2), ((127, 4, 12, 32, (2, 10, 3, 3, 1, 1)), 1),
+                ((127, 3, 12, 32, (1, 10, 3, 3, 1, 1)), 1)]
+
+# merge geometries: name -> (B, H, W, C, th, tw, exact bits expected)
+MERGE_GEOMS = {
+    "identity":  (2, 10, 10, 32, 10, 10, True),
+    "x2":        (2, 14, 10, 32, 7, 5, True),
+    "x4":        (1, 12, 20, 32, 3, 5, True),
+    "th1":       (1, 4, 10, 32, 1, 5, True),        # both vertical neighbours clamped
+    "tw1":       (1, 12, 8, 32, 3, 1, True),
+    "th1tw1":    (2, 4, 8, 32, 1, 1, True),
+    "16to40":    (1, 40, 40, 32, 16, 16, False),
+    "20to68x84": (1, 68, 84, 32, 20, 20, False),
+    "7x9to30x33": (1, 30, 33, 32, 7, 9, False),
+    "big":       (6, 80, 80, 128, 20, 20, True),    # 6 * 6400 * 2 * nv = 1,228,800 (16 bit) vectors > 2^20, 20 MB of output; x4: exact bits
+}
+

@@ -344,7 +344,7 @@ def test_plan_options_are_one_object_filled_from_one_variable():
     assert o.non_default() == {"dmff_fuse": False, "dmff_wide": False, "retune_tiles": [63, 64], "pipe_copy_prio": 0}      # ICAF_OPTIONS wins over a legacy name
     with pytest.raises(ValueError):
         PlanOptions.from_env({"ICAF_OPTIONS": "dmff_fuze=0"})
-    assert set(o.lib_options()) == {"detect_elementwise", "attn_qsplit", "sppf_vpb"}
+    assert set(o.lib_options()) == {"detect_elementwise", "attn_qsplit", "sppf_vpb", "index64"}
     l = _lib.lib()
     assert l.icaf_set_option(b"attn_qsplit", 0) == 0 and l.icaf_set_option(b"no_such_knob", 1) != 0 and b"unknown option" in l.icaf_last_error()
     src = os.path.join(REPO, "icafusion_amd")

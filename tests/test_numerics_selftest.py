@@ -160,3 +160,223 @@ def test_ulp_and_rne():
     assert nm.truncate(t.float(), BF16).double().tolist() == [1.0, 1.0 + 2.0 ** -7]
     assert nm.truncate(-t.float(), F16).double().tolist() == [-(1.0 + 2.0 ** -8), -(1.0 + 3 * 2.0 ** -8)]
     assert nm.all_finite_patterns(BF16).shape == (65536,) and nm.f32_sweep_grid().shape == (3 * 65536,)
+
+
+# ====================================================================================================================================
+# pooling, resize and merge: the helpers behind tests/test_gpu_exact_pool.py, shown to fail
+# ====================================================================================================================================
+# What close() made of each planted defect, on rnd() data of the same shape, is printed as `old close() accepts: ...` (docs/HISTORY.md section 19).
+rnd_like = nm.rnd
+
+D16 = [BF16, F16]
+D16_IDS = ["bf16", "f16"]
+VERDICTS = {}                                        # (defect, dtype) -> close() accepted it on rnd() data
+
+
+def record(defect, dt, accepted):
+    VERDICTS[(defect, str(dt).split(".")[1])] = accepted
+    print(f"{defect} {dt}: rejected by the new checkers; old close() accepts: {accepted}")
+
+
+def pool_case(name, dt, w, probes=False, g=0):
+    B, H, W, C, geom, _, _ = nm.POOL_GEOMS[name]
+    if probes:
+        x, pos = nm.pool_probes(B, H, W, C, geom, g), torch.zeros((geom[0] * geom[1], C))
+    else:
+        x, pos = nm.pool_lattice(B, H, W, C, geom[0] * geom[1], nm.shape_seed(name, dt, g))
+    avg, mx, ref = nm.pool64(x, geom, w, pos)
+    return x, pos, geom, avg, mx, ref
+
+
+pool_check = nm.check_pool
+
+
+def old_pool_verdict(name, dt, w, defect):
+    """close() on rnd() data of the same geometry: reference fp64 on the dt-rounded input, the defective emulation as `got`."""
+    B, H, W, C, geom, _, _ = nm.POOL_GEOMS[name]
+    x = rnd_like((B, H, W, C), 21).to(dt).float()
+    pos = rnd_like((geom[0] * geom[1], C), 23, 0.3)
+    _, _, ref = nm.pool64(x, geom, w, pos)
+    got = nm.emulate_pool(x, geom, w, pos, dt, defect)
+    got = torch.nan_to_num(got.float(), nan=0.0).to(dt)          # (close() ran on zero-filled outputs: an unwritten element reads 0)
+    return old_close_accepts(got, ref, dt)
+
+
+@pytest.mark.parametrize("dt", [F32, BF16, F16], ids=["f32", "bf16", "f16"])
+@pytest.mark.parametrize("name", [n for n, g in nm.POOL_GEOMS.items() if not g[6].get("big")])
+def test_pool_clean_emulation_is_accepted_on_every_geometry(name, dt):
+    """Probes (max path: bits; sum path: bits at power-of-two areas, budget otherwise) and lattice data with both weight pairs."""
+    for probes, w in ((True, (0.0, 1.0)), (True, (1.0, 0.0)), (False, nm.W_DYADIC), (False, nm.W_REAL)):
+        x, pos, geom, avg, mx, ref = pool_case(name, dt, w, probes)
+        if probes and w == (0.0, 1.0):
+            assert nm.pool_is_exact(avg, mx, w, pos, geom[2] * geom[3])
+            assert set(ref.unique().tolist()) <= {0.0, 0.25, 0.5, 1.0, 2.0, 4.0} and float(ref.max()) > 0
+            assert bool((ref.reshape(x.shape[0], -1, x.shape[3]).amax(1) > 0).all()) or name == "ekw6", "a probe lies in no window"
+        r = pool_check(nm.emulate_pool(x, geom, w, pos, dt), avg, mx, ref, w, pos, geom, dt, f"clean {name} {w}")
+        if not probes:
+            nm.assert_rounding_exercised(ref, dt, f"pool {name} w={w}")
+            print(f"clean pool {name} {dt} w={w}: err / budget {r:.3f}")
+
+
+POOL_DEFECTS = [("lastcol", "r12tr1"), ("row12", "chunks2"), ("duprow", "chunks2"), ("max0", "r8tr1"), ("short", "oddth"), ("pos_nb", "r4tr1"),
+                ("trunc", "r8tr1")]
+
+
+@pytest.mark.parametrize("dt", D16, ids=D16_IDS)
+@pytest.mark.parametrize("defect,name", POOL_DEFECTS)
+def test_pool_defects_are_rejected(defect, name, dt):
+    """Each defect must fail at least one of the launches the GPU test makes for the geometry (probes on both paths, lattice data with both
+    weight pairs)."""
+    caught = []
+    for probes, w in ((True, (0.0, 1.0)), (True, (1.0, 0.0)), (False, nm.W_DYADIC), (False, nm.W_REAL)):
+        x, pos, geom, avg, mx, ref = pool_case(name, dt, w, probes)
+        if not probes and defect == "pos_nb":
+            assert not torch.equal(pos.roll(-1, 0), pos)
+        got = nm.emulate_pool(x, geom, w, pos, dt, defect)
+        if rejected(lambda: pool_check(got, avg, mx, ref, w, pos, geom, dt, defect)):
+            caught.append((probes, w))
+    assert caught, f"{defect}: no launch of the geometry rejects it"
+    if defect in ("lastcol", "row12", "duprow"):
+        assert any(p for p, _ in caught), f"{defect}: the membership probes must catch it on their own"
+    if defect == "max0":
+        assert (False, nm.W_REAL) in caught and (False, nm.W_DYADIC) in caught, "the all-negative channels must show a maximum that starts at 0"
+    print(f"{defect} on {name} {dt}: rejected by {caught}")
+    record("pool:" + defect, dt, old_pool_verdict(name, dt, nm.W_REAL, defect))
+
+
+def merge_case(name, dt):
+    B, H, W, C, th, tw, exact = nm.MERGE_GEOMS[name]
+    tok, fea = nm.merge_lattice(dt, B, H, W, C, th, tw, nm.shape_seed("merge" + name, dt))
+    ref, bound = nm.merge64(tok, fea, dt)
+    return tok, fea, ref, bound, exact
+
+
+merge_check = nm.check_merge
+
+
+@pytest.mark.parametrize("dt", [F32, BF16, F16], ids=["f32", "bf16", "f16"])
+@pytest.mark.parametrize("name", [n for n in nm.MERGE_GEOMS if n != "big"])
+def test_merge_clean_emulation_is_accepted(name, dt):
+    tok, fea, ref, bound, exact = merge_case(name, dt)
+    interp = torch.stack([F.interpolate(tok[g].double().permute(0, 3, 1, 2), size=fea.shape[2:4], mode="bilinear", align_corners=False)
+                          .permute(0, 2, 3, 1) + fea[g].double() for g in range(2)])
+    assert float((torch.cat((interp[0], interp[1]), -1) - ref).abs().max()) < 1e-12, "merge64 disagrees with F.interpolate in fp64"
+    r = merge_check(nm.emulate_merge(tok, fea, dt), ref, bound, exact, dt, f"clean merge {name}")
+    share = nm.assert_rounding_exercised(ref, dt, f"merge {name}")
+    print(f"clean merge {name} {dt}: err / budget {r:.3f}, not representable {share:.3f}")
+
+
+@pytest.mark.parametrize("dt", D16, ids=D16_IDS)
+@pytest.mark.parametrize("defect,name", [("swap", "x2"), ("swap", "16to40"), ("align", "x2"), ("align", "20to68x84"), ("noclamp", "x4"),
+                                         ("noclamp", "7x9to30x33"), ("trunc", "identity"), ("trunc", "16to40")])
+def test_merge_defects_are_rejected(defect, name, dt):
+    tok, fea, ref, bound, exact = merge_case(name, dt)
+    got = nm.emulate_merge(tok, fea, dt, defect)
+    assert rejected(lambda: merge_check(got, ref, bound, exact, dt, defect)), f"{defect} on {name}: accepted"
+    B, H, W, C, th, tw, _ = nm.MERGE_GEOMS[name]
+    tk = rnd_like((2, B, th, tw, C), 25).to(dt).float()
+    fe = rnd_like((2, B, H, W, C), 21).to(dt).float()
+    record(f"merge:{defect}:{name}", dt, old_close_accepts(nm.emulate_merge(tk, fe, dt, defect), nm.merge64(tk, fe, dt)[0], dt))
+
+
+@pytest.mark.parametrize("dt", D16, ids=D16_IDS)
+def test_nearest_ceil_at_scale_3_is_rejected(dt):
+    g = torch.Generator().manual_seed(5)
+    x = torch.randint(-8, 9, (2, 5, 7, 16), generator=g).float().to(dt)
+    nm.assert_same_bits(nm.emulate_nearest(x, 3), nm.nearest64(x, 3), "clean nearest")
+    assert torch.equal(nm.nearest64(x, 3).float().permute(0, 3, 1, 2), F.interpolate(x.float().permute(0, 3, 1, 2), scale_factor=3, mode="nearest"))
+    assert rejected(lambda: nm.assert_same_bits(nm.emulate_nearest(x, 3, "ceil"), nm.nearest64(x, 3), "ceil"))
+    xr = rnd_like((2, 5, 7, 16), 11).to(dt)
+    record("nearest:ceil", dt, old_close_accepts(nm.emulate_nearest(xr, 3, "ceil"), nm.nearest64(xr, 3).double(), dt))
+
+
+@pytest.mark.parametrize("dt", D16, ids=D16_IDS)
+def test_axpby_clean_truncated_and_first_pass_only(dt):
+    """axpby: (128, -127) on integers is exact (every product below 2^24); (0.4, 0.7) within the counted budget; truncation rejected by
+    both; a grid-stride loop that stops after its first 2^20 vector items leaves NaN behind, which both checks reject."""
+    rows, C = nm.STRIDE_ITEMS // 16 + 300, 128                                  # (rows * C / 8 > 2^20 vectors)
+    x0, x1 = nm.axpby_lattice(dt, (rows, C), 6)
+    ref, bound = nm.axpby64(x0, x1, 128.0, -127.0, dt)
+    clean = nm.emulate_axpby(x0, x1, 128.0, -127.0, dt)
+    nm.assert_same_bits(clean, nm.rne(ref, dt) + 0.0, "clean axpby")
+    nm.assert_rounding_exercised(ref, dt, "axpby (128, -127)")
+    assert rejected(lambda: nm.assert_same_bits(nm.emulate_axpby(x0, x1, 128.0, -127.0, dt, "trunc"), nm.rne(ref, dt) + 0.0, "trunc"))
+    record("axpby:trunc", dt, old_close_accepts(nm.emulate_axpby(x0, x1, 128.0, -127.0, dt, "trunc"), ref, dt))
+    half = nm.first_pass_only(clean, float("nan"), dt)
+    assert rejected(lambda: nm.assert_same_bits(half, nm.rne(ref, dt) + 0.0, "first pass only"))
+    assert rejected(lambda: nm.assert_budget(half, ref, bound, "first pass only", signed=False))
+    zero = nm.first_pass_only(clean, 0.0, dt)                                   # what close() saw: outputs came from torch.zeros ...
+    small = clean[:1000]                                                        # ... and no case was large enough to have a second pass
+    record("stride:first_pass_only (at the old test's size: never reached)", dt, old_close_accepts(small, ref[:1000], dt))
+    record("stride:first_pass_only (had the old test been this large)", dt, old_close_accepts(zero, ref, dt))
+    ref2, bound2 = nm.axpby64(x0[:4096], x1[:4096], 0.4, 0.7, dt)
+    r = nm.assert_budget(nm.emulate_axpby(x0[:4096], x1[:4096], 0.4, 0.7, dt), ref2, bound2, "clean axpby (0.4, 0.7)", signed=False)
+    assert rejected(lambda: nm.assert_budget(nm.emulate_axpby(x0[:4096], x1[:4096], 0.4, 0.7, dt, "trunc"), ref2, bound2, "trunc", signed=False))
+    print(f"axpby (0.4, 0.7) {dt}: clean err / budget {r:.3f}")
+
+
+@pytest.mark.parametrize("dt", [F32, BF16, F16], ids=["f32", "bf16", "f16"])
+def test_vector_written_past_C_is_rejected(dt):
+    """One vector written behind the 2C channels of the merged map (ldo = 2C + one vector): the view is as expected, the padding is not."""
+    tok, fea, ref, bound, exact = merge_case("x2", dt)
+    got = nm.emulate_merge(tok, fea, dt)
+    v = nm.VEC[dt]
+    y = nm.Poisoned(got.shape[:3], got.shape[3], dt, "cpu", nm.NAN_BITS[dt], lo=0, hi=v)
+    y.view.copy_(got)
+    merge_check(y.view, ref, bound, exact, dt, "clean")
+    y.assert_outside_intact("clean")
+    y.buf[1, 2, 3, got.shape[3]:] = 1.0
+    merge_check(y.view, ref, bound, exact, dt, "the view is still right")
+    assert rejected(lambda: y.assert_outside_intact("past C"))
+    f = nm.PoisonedFlat((3, 5), dt, "cpu", nm.NAN_BITS[dt], torch.ones((3, 5)))
+    f.assert_outside_intact("clean flat")
+    f.buf[f.g + f.n] = 1.0
+    assert rejected(lambda: f.assert_outside_intact("behind the tensor"))
+
+
+def test_staging_references():
+    img = torch.arange(2 * 3 * 4 * 6, dtype=F32).reshape(2, 3, 4, 6)
+    s0 = nm.stage64(img, 0, 8)
+    assert s0.shape == (2, 4, 6, 8) and float(s0[1, 2, 3, 1]) == float(img[1, 1, 2, 3]) and float(s0[..., 3:].abs().max()) == 0
+    s1 = nm.stage64(img, 1, 16)
+    assert s1.shape == (2, 2, 3, 16) and float(s1[1, 1, 2, 2 * 3 + 1]) == float(img[1, 1, 2 * 1 + 1, 2 * 2 + 0]) and float(s1[..., 12:].abs().max()) == 0
+    assert float(s1[0, 1, 1, 1 * 3 + 2]) == float(img[0, 2, 2, 3])               # sub = 1: dy 0, dx 1
+    for dt in (F32, BF16, F16):
+        e = nm.u8_expected(dt)
+        assert float(e[0]) == 0.0 and float(e[255]) == 1.0 and bool((e[1:].float() > e[:-1].float()).all())
+
+
+def test_pool_launch_choice_of_every_geometry():
+    """icaf_dmff_pool_config is host code: the table of tests/test_gpu_exact_pool.py is checked here without a GPU — the instantiation each
+    geometry names, all seven reached, both sides of the two-token-rows threshold, the fp32 LDS boundary, and the index64 knob."""
+    from helpers import lib_option
+    from icafusion_amd import ops
+    seen = set()
+    for name, (B, H, W, C, geom, want, _) in nm.POOL_GEOMS.items():
+        for dt in (F32, BF16, F16):
+            c = ops.dmff_pool_config(dt, B, H, W, C, *geom)
+            assert (c["kernel"], c["R"], c["TR"]) == want[dt], f"{name} {dt}: {c}"
+            assert c["index64"] == 0
+            seen.add(want[dt])
+    assert seen == {(nm.ELEM, 0, 0)} | {(nm.ROWS, r, t) for r in (4, 8, 12) for t in (1, 2)}
+    for (B, H, W, C, geom), tr in nm.TR_THRESHOLD:
+        assert 2 * B * ((geom[0] + 1) // 2) in (254, 256)
+        for dt in (F32, BF16, F16):
+            assert ops.dmff_pool_config(dt, B, H, W, C, *geom)["TR"] == tr
+    with lib_option("index64", 1):
+        assert ops.dmff_pool_config(BF16, 2, 16, 20, 32, 4, 5, 4, 4, 4, 4) == dict(kernel=0, R=0, TR=0, index64=1)
+        assert ops.dmff_pool_config(BF16, 1, 9, 11, 32, 7, 9, 3, 3, 1, 1) == dict(kernel=1, R=4, TR=1, index64=0)      # the rows kernel has no flat index
+    assert ops.dmff_pool_config(BF16, 2, 16, 20, 32, 4, 5, 4, 4, 4, 4)["index64"] == 0
+    from icafusion_amd._lib import IcafError
+    with pytest.raises(IcafError, match="window exceeds the feature map"):
+        ops.dmff_pool_config(BF16, 1, 9, 11, 32, 7, 9, 4, 3, 1, 1)
+    with pytest.raises(IcafError, match="multiples of 8"):
+        ops.dmff_pool_config(BF16, 1, 9, 11, 36, 7, 9, 3, 3, 1, 1)
+
+
+def test_close_verdicts_are_recorded():
+    """Closing: prints what close() accepted (docs/HISTORY.md section 19); every planted defect above left its verdict."""
+    if not VERDICTS:
+        print("run with the defect tests of this file (same process): nothing was recorded")
+    for k in sorted(VERDICTS):
+        print(f"close() on {k[0]} {k[1]}: {'ACCEPTS' if VERDICTS[k] else 'rejects'}")
