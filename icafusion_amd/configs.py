@@ -71,8 +71,33 @@ def transfusion_cfg(size="s", nc=1, loops=1, fusion="TransformerFusionBlock"):
             "backbone": backbone, "head": head}
 
 
-def _dump_model_yaml(cfg, title):
-    lines = [f"# {title}", "# generated by icafusion_amd/configs.py — two RGB/IR CSPDarknet streams, three DMFF",
+# (fusion block, dataset tag, nc) — the VGG16-backbone variants the reference ships
+VGG16_VARIANTS = [("Transfusion", "kaist", 1), ("Transfusion", "FLIR", 3), ("NiNfusion", "kaist", 1), ("NiNfusion", "FLIR", 3)]
+VGG16_BLOCKS = ((2, 3, 64), (2, 64, 128), (3, 128, 256), (3, 256, 512), (3, 512, 512))     # (num_convs, c1, c2), each closed by a 2x2 pool
+VGG16_TAPS = ((2, 7, 256), (3, 8, 512), (4, 9, 512))                                      # (RGB row, IR row, channels) at strides 8, 16, 32
+
+
+def vgg16_cfg(fusion="Transfusion", nc=1):
+    """Two VGG16 streams (five VGGblock rows each, models/common.py:109-128), DMFF ("Transfusion") or NiNfusion taps behind blocks 3, 4 and
+    5, and the yolov5l PANet head on 512 / 512 / 256 channels."""
+    backbone = [[f if i == 0 else -1, 1, "VGGblock", list(b)] for f in (-1, -4) for i, b in enumerate(VGG16_BLOCKS)]
+    for (a, b, c), (va, ha) in zip(VGG16_TAPS, TOKENS):
+        backbone.append([[a, b], 1, "NiNfusion", [1, 1]] if fusion == "NiNfusion" else [[a, b], 1, "TransformerFusionBlock", [c, va, ha]])
+    head = [
+        [-1, 1, "Conv", [512, 1, 1]], [-1, 1, "nn.Upsample", ["None", 2, "nearest"]], [[-1, 11], 1, "Concat", [1]],
+        [-1, 3, "C3", [512, False]],
+        [-1, 1, "Conv", [256, 1, 1]], [-1, 1, "nn.Upsample", ["None", 2, "nearest"]], [[-1, 10], 1, "Concat", [1]],
+        [-1, 3, "C3", [256, False]],
+        [-1, 1, "Conv", [256, 3, 2]], [[-1, 17], 1, "Concat", [1]], [-1, 3, "C3", [512, False]],
+        [-1, 1, "Conv", [512, 3, 2]], [[-1, 13], 1, "Concat", [1]], [-1, 3, "C3", [512, False]],
+        [[20, 23, 26], 1, "Detect", ["nc", "anchors"]],
+    ]
+    return {"nc": nc, "depth_multiple": 1.0, "width_multiple": 1.0, "anchors": [list(a) for a in ANCHORS],
+            "backbone": backbone, "head": head}
+
+
+def _dump_model_yaml(cfg, title, streams="CSPDarknet"):
+    lines = [f"# {title}", f"# generated by icafusion_amd/configs.py — two RGB/IR {streams} streams, three DMFF",
              "# (TransformerFusionBlock) taps at P3/P4/P5, PANet head, Detect.  Row = [from, number, module, args];",
              "# from=-4 feeds the IR image; optional trailing {loops_num: n} DMFF arg = number of parameter-shared iterations.",
              f"nc: {cfg['nc']}", f"depth_multiple: {cfg['depth_multiple']}", f"width_multiple: {cfg['width_multiple']}",
@@ -100,6 +125,10 @@ def write_all(root):
         name = f"yolov5{size}_{fusion}_{tag}.yaml"
         with open(os.path.join(root, "models", "transformer", name), "w") as f:
             f.write(_dump_model_yaml(transfusion_cfg(size, nc, fusion=fusion), name))
+    for fusion, tag, nc in VGG16_VARIANTS:
+        name = f"yolov5_VGG16_{fusion}_{tag}.yaml"
+        with open(os.path.join(root, "models", "transformer", name), "w") as f:
+            f.write(_dump_model_yaml(vgg16_cfg(fusion, nc), name, streams="VGG16"))
     for tag, (nc, names) in DATASETS.items():
         d = f"/data/{tag}"
         body = {"path": d, "train_rgb": f"{d}/visible/train/", "val_rgb": f"{d}/visible/test/",

@@ -49,10 +49,16 @@ int launch_cwide(const icaf_conv_args* a, const ConvP& p, int shape, hipStream_t
 const char* cwide_tag(int shape);
 int launch_bneck(const icaf_conv_args* a, const ConvP& p, int shape, hipStream_t s);      // ctile.hip (icaf_bottleneck)
 
+// Instantiation order.  tools/kernel_fingerprint.py --diff compares the assembly TEXT of every kernel, and local labels in that text carry the
+// function's ordinal in its translation unit.  Templates are instantiated depth first in the order they are first named, so an activation
+// dispatched next to the others inside launch_cfg / launch_stream_act / launch_wreg_act would renumber every kernel instantiated after it.
+// An activation added to a family is therefore selected at the ROOT of that family's dispatch (launch_igemm, launch_stream, launch_wreg:
+// `bool RELU`), in a branch written behind the existing ones: its kernels are numbered last and every other kernel's text stays byte-identical.
 // DT = the layer's storage type: the 16-bit builds evaluate GELU's erf by a 1.5e-7-accurate polynomial (gelu_fast_f), fp32 by erff
 template <int ACT, int DT = ICAF_F32> __device__ __forceinline__ float apply_act(float v) {
     if constexpr (ACT == ICAF_ACT_SILU) return silu_f(v);
     else if constexpr (ACT == ICAF_ACT_GELU) return DT == ICAF_F32 ? gelu_f(v) : gelu_fast_f(v);
+    else if constexpr (ACT == ICAF_ACT_RELU) return fmaxf(v, 0.0f);      // torch.relu for finite v (one v_max_f32)
     else return v;
 }
 // four values at once: SiLU goes through silu4_f (packed middle steps, same bits), everything else value by value

@@ -537,7 +537,8 @@ static int launch_act(const ConvP& q, dim3 grid, int pipe, hipStream_t s) {
     }
 }
 
-template <int DT, int ODT, int BM, int BN, int WM, int WN>
+// RELU: the root-level selector of ICAF_ACT_RELU — why it is a parameter of its own: conv_common.h, "Instantiation order"
+template <int DT, int ODT, int BM, int BN, int WM, int WN, bool RELU = false>
 static int launch_cfg(const ConvP& p, int groups, int pipe, hipStream_t s) {
     ConvP q = p;
     q.mtiles = (p.M + BM - 1) / BM;
@@ -547,47 +548,56 @@ static int launch_cfg(const ConvP& p, int groups, int pipe, hipStream_t s) {
         q.nchunks = (p.K + bk - 1) / bk;
     }
     dim3 grid((unsigned)(q.mtiles * q.ntiles), 1, (unsigned)groups);
+    if constexpr (RELU) return launch_act<DT, ODT, BM, BN, WM, WN, ICAF_ACT_RELU>(q, grid, pipe, s);
     if (p.act == ICAF_ACT_SILU) return launch_act<DT, ODT, BM, BN, WM, WN, ICAF_ACT_SILU>(q, grid, pipe, s);
     if (p.act == ICAF_ACT_GELU) return launch_act<DT, ODT, BM, BN, WM, WN, ICAF_ACT_GELU>(q, grid, pipe, s);
     return launch_act<DT, ODT, BM, BN, WM, WN, ICAF_ACT_NONE>(q, grid, pipe, s);
 }
 
 // 8-wavefront tiles: pipeline 2 only
-template <int DT, int ODT, int BM, int BN, int WM, int WN>
+template <int DT, int ODT, int BM, int BN, int WM, int WN, bool RELU = false>
 static int launch_big(const ConvP& p, int groups, hipStream_t s) {
     ConvP q = p;
     q.mtiles = (p.M + BM - 1) / BM;
     q.ntiles = (p.Cout + BN - 1) / BN;
     q.nchunks = (p.K + 63) / 64;                  // 128-byte slices of a 16-bit type
     dim3 grid((unsigned)(q.mtiles * q.ntiles), 1, (unsigned)groups);
+    if constexpr (RELU) return launch_dma<DT, ODT, BM, BN, WM, WN, ICAF_ACT_RELU, 128, 2>(q, grid, s);
     if (p.act == ICAF_ACT_SILU) return launch_dma<DT, ODT, BM, BN, WM, WN, ICAF_ACT_SILU, 128, 2>(q, grid, s);
     if (p.act == ICAF_ACT_GELU) return launch_dma<DT, ODT, BM, BN, WM, WN, ICAF_ACT_GELU, 128, 2>(q, grid, s);
     return launch_dma<DT, ODT, BM, BN, WM, WN, ICAF_ACT_NONE, 128, 2>(q, grid, s);
 }
 
-template <int DT, int ODT>
+template <int DT, int ODT, bool RELU = false>
 static int launch_tile(const ConvP& p, int groups, int cfg, hipStream_t s) {
     const int pipe = cfg / 10;
     constexpr bool f32 = DT == ICAF_F32 || ODT == ICAF_F32;
     switch (cfg % 10) {
-        case 1: if constexpr (ODT != ICAF_F32) return launch_cfg<DT, ODT, 128, 128, 64, 64>(p, groups, pipe, s); break;
-        case 2: return launch_cfg<DT, ODT, 128, 64, 64, 32>(p, groups, pipe, s);
-        case 3: return launch_cfg<DT, ODT, 256, 32, 64, 32>(p, groups, pipe, s);
-        case 4: return launch_cfg<DT, ODT, 64, 64, 32, 32>(p, groups, pipe, s);
-        case 5: if constexpr (!f32) return launch_big<DT, ODT, 256, 128, 64, 64>(p, groups, s); break;
-        case 6: if constexpr (!f32) return launch_big<DT, ODT, 256, 256, 128, 64>(p, groups, s); break;
-        case 8: if constexpr (!f32) return launch_big<DT, ODT, 128, 128, 64, 32>(p, groups, s); break;   // 128x128 / 128x64 tiles with 8 wavefronts (64x32 / 32x32
-        case 9: if constexpr (!f32) return launch_big<DT, ODT, 128, 64, 32, 32>(p, groups, s); break;    // each): more waves per SIMD to hide latency, same LDS footprint
+        case 1: if constexpr (ODT != ICAF_F32) return launch_cfg<DT, ODT, 128, 128, 64, 64, RELU>(p, groups, pipe, s); break;
+        case 2: return launch_cfg<DT, ODT, 128, 64, 64, 32, RELU>(p, groups, pipe, s);
+        case 3: return launch_cfg<DT, ODT, 256, 32, 64, 32, RELU>(p, groups, pipe, s);
+        case 4: return launch_cfg<DT, ODT, 64, 64, 32, 32, RELU>(p, groups, pipe, s);
+        case 5: if constexpr (!f32) return launch_big<DT, ODT, 256, 128, 64, 64, RELU>(p, groups, s); break;
+        case 6: if constexpr (!f32) return launch_big<DT, ODT, 256, 256, 128, 64, RELU>(p, groups, s); break;
+        case 8: if constexpr (!f32) return launch_big<DT, ODT, 128, 128, 64, 32, RELU>(p, groups, s); break;   // 128x128 / 128x64 tiles with 8 wavefronts (64x32 / 32x32
+        case 9: if constexpr (!f32) return launch_big<DT, ODT, 128, 64, 32, 32, RELU>(p, groups, s); break;    // each): more waves per SIMD to hide latency, same LDS footprint
     }
     return fail(ICAF_ERR_UNSUPPORTED, "icaf_conv2d: launch configuration %d has no build for these types", cfg);
 }
 
 static int launch_igemm(const icaf_conv_args* a, const ConvP& p, int id, hipStream_t s) {
+    if (a->act != ICAF_ACT_RELU) {
+        if (a->dtype == ICAF_BF16)
+            return a->out_dtype == ICAF_F32 ? launch_tile<ICAF_BF16, ICAF_F32>(p, a->groups, id, s) : launch_tile<ICAF_BF16, ICAF_BF16>(p, a->groups, id, s);
+        if (a->dtype == ICAF_F16)
+            return a->out_dtype == ICAF_F32 ? launch_tile<ICAF_F16, ICAF_F32>(p, a->groups, id, s) : launch_tile<ICAF_F16, ICAF_F16>(p, a->groups, id, s);
+        return launch_tile<ICAF_F32, ICAF_F32>(p, a->groups, id, s);
+    }
     if (a->dtype == ICAF_BF16)
-        return a->out_dtype == ICAF_F32 ? launch_tile<ICAF_BF16, ICAF_F32>(p, a->groups, id, s) : launch_tile<ICAF_BF16, ICAF_BF16>(p, a->groups, id, s);
+        return a->out_dtype == ICAF_F32 ? launch_tile<ICAF_BF16, ICAF_F32, true>(p, a->groups, id, s) : launch_tile<ICAF_BF16, ICAF_BF16, true>(p, a->groups, id, s);
     if (a->dtype == ICAF_F16)
-        return a->out_dtype == ICAF_F32 ? launch_tile<ICAF_F16, ICAF_F32>(p, a->groups, id, s) : launch_tile<ICAF_F16, ICAF_F16>(p, a->groups, id, s);
-    return launch_tile<ICAF_F32, ICAF_F32>(p, a->groups, id, s);
+        return a->out_dtype == ICAF_F32 ? launch_tile<ICAF_F16, ICAF_F32, true>(p, a->groups, id, s) : launch_tile<ICAF_F16, ICAF_F16, true>(p, a->groups, id, s);
+    return launch_tile<ICAF_F32, ICAF_F32, true>(p, a->groups, id, s);
 }
 
 // One row per kernel family: the launch configuration ids it owns (shape = id - base), its check (0, or an error code with the reason
@@ -676,7 +686,7 @@ static int validate(const icaf_conv_args* a) {
         return fail(ICAF_ERR_ARG, "icaf_conv2d: output size does not match input/kernel/stride/padding");
     const int ka = a->dtype == ICAF_F32 ? 32 : 64;
     if (a->Kp % ka || a->Kp < a->kh * a->kw * a->Cin) return fail(ICAF_ERR_ARG, "icaf_conv2d: Kp=%d must be a multiple of %d covering K=%d", a->Kp, ka, a->kh * a->kw * a->Cin);
-    if (a->act < 0 || a->act > 2) return fail(ICAF_ERR_ARG, "icaf_conv2d: bad activation code %d", a->act);
+    if (a->act < 0 || a->act > ICAF_ACT_RELU) return fail(ICAF_ERR_ARG, "icaf_conv2d: bad activation code %d", a->act);
     if (a->ldy < a->Cout) return fail(ICAF_ERR_ARG, "icaf_conv2d: ldy < Cout");
     if (a->res && a->ldr < a->Cout) return fail(ICAF_ERR_ARG, "icaf_conv2d: ldr < Cout");
     if ((long long)a->B * a->Ho * a->Wo > 0x7fffffffLL) return fail(ICAF_ERR_ARG, "icaf_conv2d: too many output pixels");

@@ -178,16 +178,22 @@ static int launch_stream_cfg(const ConvP& p, int groups, hipStream_t s) {
     return go(igemm_stream_kernel<DT, BN, ACT, 2>);
 }
 
-template <int DT, int BN>
+// RELU: the root-level selector of ICAF_ACT_RELU — why it is a parameter of its own: conv_common.h, "Instantiation order"
+template <int DT, int BN, bool RELU = false>
 static int launch_stream_act(const ConvP& p, int groups, hipStream_t s) {
+    if constexpr (RELU) return launch_stream_cfg<DT, BN, ICAF_ACT_RELU>(p, groups, s);
     if (p.act == ICAF_ACT_SILU) return launch_stream_cfg<DT, BN, ICAF_ACT_SILU>(p, groups, s);
     if (p.act == ICAF_ACT_GELU) return launch_stream_cfg<DT, BN, ICAF_ACT_GELU>(p, groups, s);
     return launch_stream_cfg<DT, BN, ICAF_ACT_NONE>(p, groups, s);
 }
 
 int launch_stream(const icaf_conv_args* a, const ConvP& p, int shape, hipStream_t s) {
-    if (a->dtype == ICAF_BF16) return shape == 1 ? launch_stream_act<ICAF_BF16, 128>(p, a->groups, s) : launch_stream_act<ICAF_BF16, 64>(p, a->groups, s);
-    return shape == 1 ? launch_stream_act<ICAF_F16, 128>(p, a->groups, s) : launch_stream_act<ICAF_F16, 64>(p, a->groups, s);
+    if (a->act != ICAF_ACT_RELU) {
+        if (a->dtype == ICAF_BF16) return shape == 1 ? launch_stream_act<ICAF_BF16, 128>(p, a->groups, s) : launch_stream_act<ICAF_BF16, 64>(p, a->groups, s);
+        return shape == 1 ? launch_stream_act<ICAF_F16, 128>(p, a->groups, s) : launch_stream_act<ICAF_F16, 64>(p, a->groups, s);
+    }
+    if (a->dtype == ICAF_BF16) return shape == 1 ? launch_stream_act<ICAF_BF16, 128, true>(p, a->groups, s) : launch_stream_act<ICAF_BF16, 64, true>(p, a->groups, s);
+    return shape == 1 ? launch_stream_act<ICAF_F16, 128, true>(p, a->groups, s) : launch_stream_act<ICAF_F16, 64, true>(p, a->groups, s);
 }
 
 }  // namespace icaf

@@ -233,7 +233,7 @@ int wreg_check(const icaf_conv_args* a, const ConvP& p, int shape) {
     if (a->Kp % 64) return fail(ICAF_ERR_UNSUPPORTED, "igemm_wreg: Kp must be a multiple of 64");
     if (((uintptr_t)a->wf & 15) || (a->wf_gs * 2) % 16) return fail(ICAF_ERR_ARG, "igemm_wreg: wf must be 16-byte aligned");
     if ((shape == 2 || shape == 4 || shape == 5) && a->Cout <= 128) return fail(ICAF_ERR_UNSUPPORTED, "igemm_wreg 128x256: Cout = %d <= 128 (use 128x128)", a->Cout);
-    if (shape == 3 && a->act == ICAF_ACT_GELU) return fail(ICAF_ERR_UNSUPPORTED, "igemm_wreg %s: built for SiLU / linear layers", wreg_tag(shape));
+    if (shape == 3 && a->act == ICAF_ACT_GELU) return fail(ICAF_ERR_UNSUPPORTED, "igemm_wreg %s: built for SiLU / ReLU / linear layers", wreg_tag(shape));
     if (shape == 3 && a->Cout <= 256) return fail(ICAF_ERR_UNSUPPORTED, "igemm_wreg 128x512: Cout = %d <= 256 (use 128x256)", a->Cout);
     // the fragment-major copy covers Np = Cout rounded up to 128 channels: a wider tile must not reach beyond it
     const int bn = (shape == 1 || shape == 6) ? 128 : shape == 3 ? 512 : 256;
@@ -263,29 +263,32 @@ static int launch_wreg_mode(const icaf_conv_args* a, const ConvP& p, int groups,
     return go(igemm_wreg_kernel<DT, NWV, ACT, 2, TN, BM>);
 }
 
-template <int DT, int NWV, int TN = 1, int BM = 128>
+// RELU: the root-level selector of ICAF_ACT_RELU — why it is a parameter of its own: conv_common.h, "Instantiation order"
+template <int DT, int NWV, int TN = 1, int BM = 128, bool RELU = false>
 static int launch_wreg_act(const icaf_conv_args* a, const ConvP& p, int groups, hipStream_t s) {
+    if constexpr (RELU) return launch_wreg_mode<DT, NWV, ICAF_ACT_RELU, TN, BM>(a, p, groups, s);      // every form, 128x512 included
     if (p.act == ICAF_ACT_SILU) return launch_wreg_mode<DT, NWV, ICAF_ACT_SILU, TN, BM>(a, p, groups, s);
     if constexpr (NWV == 4) { if (p.act == ICAF_ACT_GELU) return launch_wreg_mode<DT, NWV, ICAF_ACT_GELU, TN, BM>(a, p, groups, s); }
-    else if (p.act == ICAF_ACT_GELU && TN == 2) return fail(ICAF_ERR_UNSUPPORTED, "igemm_wreg 128x512: built for SiLU / linear layers");
+    else if (p.act == ICAF_ACT_GELU && TN == 2) return fail(ICAF_ERR_UNSUPPORTED, "igemm_wreg 128x512: built for SiLU / ReLU / linear layers");
     if constexpr (NWV == 8 && TN == 1) { if (p.act == ICAF_ACT_GELU) return launch_wreg_mode<DT, NWV, ICAF_ACT_GELU, TN, BM>(a, p, groups, s); }
     return launch_wreg_mode<DT, NWV, ICAF_ACT_NONE, TN, BM>(a, p, groups, s);
 }
 
-template <int DT>
+template <int DT, bool RELU = false>
 static int launch_wreg_shape(const icaf_conv_args* a, const ConvP& p, int shape, hipStream_t s) {
     switch (shape) {
-        case 1: return launch_wreg_act<DT, 4>(a, p, a->groups, s);
-        case 2: return launch_wreg_act<DT, 8>(a, p, a->groups, s);
-        case 3: return launch_wreg_act<DT, 8, 2>(a, p, a->groups, s);      // 128 x 512: eight waves x 64 channels
-        case 4: return launch_wreg_act<DT, 4, 2>(a, p, a->groups, s);      // 128 x 256: four waves x 64 channels
-        case 5: return launch_wreg_act<DT, 4, 2, 64>(a, p, a->groups, s);  //  64 x 256: four waves x 64 channels, half the pixels
-        default: return launch_wreg_act<DT, 4, 1, 64>(a, p, a->groups, s); //  64 x 128: four waves x 32 channels, half the pixels
+        case 1: return launch_wreg_act<DT, 4, 1, 128, RELU>(a, p, a->groups, s);
+        case 2: return launch_wreg_act<DT, 8, 1, 128, RELU>(a, p, a->groups, s);
+        case 3: return launch_wreg_act<DT, 8, 2, 128, RELU>(a, p, a->groups, s);      // 128 x 512: eight waves x 64 channels
+        case 4: return launch_wreg_act<DT, 4, 2, 128, RELU>(a, p, a->groups, s);      // 128 x 256: four waves x 64 channels
+        case 5: return launch_wreg_act<DT, 4, 2, 64, RELU>(a, p, a->groups, s);  //  64 x 256: four waves x 64 channels, half the pixels
+        default: return launch_wreg_act<DT, 4, 1, 64, RELU>(a, p, a->groups, s); //  64 x 128: four waves x 32 channels, half the pixels
     }
 }
 
 int launch_wreg(const icaf_conv_args* a, const ConvP& p, int shape, hipStream_t s) {
-    return a->dtype == ICAF_BF16 ? launch_wreg_shape<ICAF_BF16>(a, p, shape, s) : launch_wreg_shape<ICAF_F16>(a, p, shape, s);
+    if (a->act != ICAF_ACT_RELU) return a->dtype == ICAF_BF16 ? launch_wreg_shape<ICAF_BF16>(a, p, shape, s) : launch_wreg_shape<ICAF_F16>(a, p, shape, s);
+    return a->dtype == ICAF_BF16 ? launch_wreg_shape<ICAF_BF16, true>(a, p, shape, s) : launch_wreg_shape<ICAF_F16, true>(a, p, shape, s);
 }
 
 }  // namespace icaf

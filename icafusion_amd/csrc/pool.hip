@@ -232,6 +232,82 @@ __global__ __launch_bounds__(256) void sppf_lds_kernel(const typename Elem<DT>::
     }
 }
 
+// ---- 2-D max pooling (nn.MaxPool2d(k, s, p): the VGG blocks' 2 / 2 / 0 and ResNet's 3 / 2 / 1 window) ---------------------------------
+// One thread = one (output pixel, 16-byte channel vector).  The window is walked in torch's order (rows, then columns) with torch's
+// comparison — max = -inf, then `v > max || isnan(v)` takes v — on values widened to fp32 (exact for both 16-bit types), so the result is
+// the bits torch's CPU kernel returns: padding is skipped, never compared, and therefore never wins.
+struct PoolDiv { FastDiv nv, wo, ho; };
+
+template <int DT, bool I32>     // I32: flat vector index below 2^31 -> FastDiv instead of 64-bit divisions
+__global__ __launch_bounds__(256) void maxpool_kernel(const typename Elem<DT>::type* __restrict__ x, int ldx, typename Elem<DT>::type* __restrict__ y,
+                                                      int ldy, int B, int H, int W, int Ho, int Wo, int nv, int k, int st, int pad, PoolDiv dv) {
+    using E = Elem<DT>;
+    const long long total = (long long)B * Ho * Wo * nv;
+    for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long long)gridDim.x * blockDim.x) {
+        long long pix;
+        int v, wo, ho, b;
+        if constexpr (I32) {
+            unsigned int upix, uv, t, uwo, ub, uho;
+            fd_divmod((unsigned int)idx, dv.nv, upix, uv);
+            fd_divmod(upix, dv.wo, t, uwo);
+            fd_divmod(t, dv.ho, ub, uho);
+            pix = upix; v = (int)uv; wo = (int)uwo; ho = (int)uho; b = (int)ub;
+        } else {
+            v = (int)(idx % nv);
+            pix = idx / nv;
+            wo = (int)(pix % Wo);
+            const long long t = pix / Wo;
+            ho = (int)(t % Ho);
+            b = (int)(t / Ho);
+        }
+        float m[E::VEC];
+#pragma unroll
+        for (int j = 0; j < E::VEC; ++j) m[j] = -INFINITY;
+        const int h0 = ho * st - pad, w0 = wo * st - pad;
+        for (int dy = 0; dy < k; ++dy) {
+            const int hh = h0 + dy;
+            if ((unsigned)hh >= (unsigned)H) continue;
+            for (int dx = 0; dx < k; ++dx) {
+                const int ww = w0 + dx;
+                if ((unsigned)ww >= (unsigned)W) continue;
+                float f[E::VEC];
+                unpack16<DT>(*(const u32x4*)(x + (((long long)b * H + hh) * W + ww) * ldx + v * E::VEC), f);
+#pragma unroll
+                for (int j = 0; j < E::VEC; ++j) m[j] = (f[j] > m[j] || f[j] != f[j]) ? f[j] : m[j];
+            }
+        }
+        *(u32x4*)(y + pix * ldy + v * E::VEC) = pack16<DT>(m);
+    }
+}
+
+// the same pool one element per thread: pixel strides or base addresses that do not take 16-byte vectors
+template <int DT>
+__global__ __launch_bounds__(256) void maxpool_scalar_kernel(const typename Elem<DT>::type* __restrict__ x, int ldx, typename Elem<DT>::type* __restrict__ y,
+                                                             int ldy, int B, int H, int W, int Ho, int Wo, int C, int k, int st, int pad) {
+    using E = Elem<DT>;
+    const long long total = (long long)B * Ho * Wo * C;
+    for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long long)gridDim.x * blockDim.x) {
+        const int c = (int)(idx % C);
+        const long long pix = idx / C;
+        const int wo = (int)(pix % Wo);
+        const long long t = pix / Wo;
+        const int ho = (int)(t % Ho), b = (int)(t / Ho);
+        float m = -INFINITY;
+        const int h0 = ho * st - pad, w0 = wo * st - pad;
+        for (int dy = 0; dy < k; ++dy) {
+            const int hh = h0 + dy;
+            if ((unsigned)hh >= (unsigned)H) continue;
+            for (int dx = 0; dx < k; ++dx) {
+                const int ww = w0 + dx;
+                if ((unsigned)ww >= (unsigned)W) continue;
+                const float f = E::ld(x + (((long long)b * H + hh) * W + ww) * ldx + c);
+                m = (f > m || f != f) ? f : m;
+            }
+        }
+        E::st(y + pix * ldy + c, m);
+    }
+}
+
 // ---- nearest-neighbour integer upsample (writes a channel slice of the consumer's concat buffer) ---------------
 struct UpsampleDiv { FastDiv nv, wo, ho, scale; };
 
@@ -426,4 +502,45 @@ extern "C" int icaf_copy_channels(const void* x, int ldx, void* y, int ldy, int 
                        rows, C / vec);
     ICAF_LAUNCH_CHECK();
     return ICAF_OK;
+}
+
+// (behind every older entry point: the instantiation order of the kernels above — and with it their assembly text — stays what it was)
+template <int DT>
+static int launch_maxpool(const void* x, int ldx, void* y, int ldy, int B, int H, int W, int Ho, int Wo, int C, int k, int st, int pad, bool vec16,
+                          hipStream_t s) {
+    using T = typename Elem<DT>::type;
+    constexpr int vec = Elem<DT>::VEC;
+    if (!vec16) {
+        const long long total = (long long)B * Ho * Wo * C;
+        hipLaunchKernelGGL(maxpool_scalar_kernel<DT>, dim3(grid_for(total)), dim3(256), 0, s, (const T*)x, ldx, (T*)y, ldy, B, H, W, Ho, Wo, C, k, st, pad);
+    } else {
+        const int nv = C / vec;
+        const long long total = (long long)B * Ho * Wo * nv;
+        const PoolDiv dv{make_fastdiv((unsigned)nv), make_fastdiv((unsigned)Wo), make_fastdiv((unsigned)Ho)};
+        if (total < (1ll << 31))
+            hipLaunchKernelGGL((maxpool_kernel<DT, true>), dim3(grid_for(total)), dim3(256), 0, s, (const T*)x, ldx, (T*)y, ldy, B, H, W, Ho, Wo, nv, k, st, pad, dv);
+        else
+            hipLaunchKernelGGL((maxpool_kernel<DT, false>), dim3(grid_for(total)), dim3(256), 0, s, (const T*)x, ldx, (T*)y, ldy, B, H, W, Ho, Wo, nv, k, st, pad, dv);
+    }
+    ICAF_LAUNCH_CHECK();
+    return ICAF_OK;
+}
+
+extern "C" int icaf_maxpool2d(const void* x, int ldx, void* y, int ldy, int dtype, int B, int H, int W, int C, int k, int stride, int pad,
+                              icaf_stream_t s) {
+    if (!x || !y) return fail(ICAF_ERR_ARG, "icaf_maxpool2d: null pointer");
+    if (dtype < 0 || dtype > 2) return fail(ICAF_ERR_ARG, "icaf_maxpool2d: bad dtype");
+    if (!((k == 2 && stride == 2 && pad == 0) || (k == 3 && stride == 2 && pad == 1)))
+        return fail(ICAF_ERR_UNSUPPORTED, "icaf_maxpool2d: window (k, s, p) = (%d, %d, %d) is not built: (2, 2, 0) and (3, 2, 1) are", k, stride, pad);
+    const int vec = vec_of(dtype), eb = dtype == ICAF_F32 ? 4 : 2;
+    if (B < 1 || H < 1 || W < 1 || C < 1 || H + 2 * pad < k || W + 2 * pad < k) return fail(ICAF_ERR_ARG, "icaf_maxpool2d: bad geometry %d x %d x %d x %d", B, H, W, C);
+    if (C % vec) return fail(ICAF_ERR_ARG, "icaf_maxpool2d: C (%d) must be a multiple of %d", C, vec);
+    if (ldx < C || ldy < C) return fail(ICAF_ERR_ARG, "icaf_maxpool2d: ldx (%d) / ldy (%d) < C (%d)", ldx, ldy, C);
+    if (((uintptr_t)x | (uintptr_t)y) & (uintptr_t)(eb - 1)) return fail(ICAF_ERR_ARG, "icaf_maxpool2d: x / y must be aligned to the element size");
+    const int Ho = (H + 2 * pad - k) / stride + 1, Wo = (W + 2 * pad - k) / stride + 1;
+    if ((long long)B * H * W > 0x7fffffffLL) return fail(ICAF_ERR_ARG, "icaf_maxpool2d: too many pixels");
+    const bool vec16 = ldx % vec == 0 && ldy % vec == 0 && (((uintptr_t)x | (uintptr_t)y) & 15) == 0;
+    if (dtype == ICAF_F32) return launch_maxpool<ICAF_F32>(x, ldx, y, ldy, B, H, W, Ho, Wo, C, k, stride, pad, vec16, S(s));
+    if (dtype == ICAF_BF16) return launch_maxpool<ICAF_BF16>(x, ldx, y, ldy, B, H, W, Ho, Wo, C, k, stride, pad, vec16, S(s));
+    return launch_maxpool<ICAF_F16>(x, ldx, y, ldy, B, H, W, Ho, Wo, C, k, stride, pad, vec16, S(s));
 }

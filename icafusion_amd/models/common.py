@@ -318,6 +318,93 @@ class Conv(HipModule):
                 and _pair(k3.padding) == (0, 0) and k3.in_channels == 2 * k.out_channels and k3.out_channels == 256)
 
 
+class VGGblock(HipModule):
+    """num_convs x (Conv2d(3x3, padding 1, bias) + ReLU), then MaxPool2d(2, 2) (reference models/common.py:109-128; the reference's
+    `blk` list is not registered, so `vggblock` is the whole state_dict surface).  No BatchNorm: nothing to fold.  On the device: one
+    ReLU implicit-GEMM launch per conv (icaf_conv2d, ACT_RELU) and one icaf_maxpool2d; the block that reads the image runs its first
+    conv through icaf_vgg_stem in the 16-bit types, straight from the NCHW image."""
+
+    def __init__(self, num_convs, c1, c2):
+        super().__init__()
+        blk = [nn.Sequential(nn.Conv2d(in_channels=c1 if j == 0 else c2, out_channels=c2, kernel_size=3, padding=1), nn.ReLU())
+               for j in range(num_convs)]
+        blk.append(nn.MaxPool2d(kernel_size=2, stride=2))
+        self.vggblock = nn.Sequential(*blk)
+
+    # image-fed first conv as ONE kernel (icaf_vgg_stem, 16-bit types) instead of preprocess_pad + an igemm with K = 72.  Built and tested, OFF by
+    # default: measured on MI355X (tools/vgg_bench.py, profiles/vgg_bench.json: bf16, both streams, batch 32, 640 x 640, interleaved in one loop) the
+    # fused kernel takes 2.62 ms against 1.50 ms for the two generic launches (A/A spread 0.3 %) — 160 registers leave two waves per SIMD to hide
+    # 16 scalar image loads per lane and round; the generic route writes and re-reads only 16 bytes per pixel.
+    fuse_stem = False
+
+    def convs(self):
+        return [s[0] for s in self.vggblock if isinstance(s, nn.Sequential)]
+
+    def _packed(self, plan, j, twin, cin_pad=None, stem=False):
+        """(wp, kp, bp) of conv j in its launch form (ops.pack_streams), or with stem=True (w [64][32], bias fp32 [64]) for icaf_vgg_stem;
+        with `twin` the two streams stacked."""
+        def make():
+            ks = [b.convs()[j] for b in ((self,) if twin is None else (self, twin))]
+            rows = [(k.weight.detach().float(), k.bias.detach().float()) for k in ks]
+            if not stem:
+                return ops.pack_streams(rows, plan.dtype, cin_pad)
+            ws = [ops.vgg_stem_weight(w, plan.dtype) for w, _ in rows]
+            bs = [b.contiguous() for _, b in rows]
+            return (ws[0], 32, bs[0]) if twin is None else (torch.stack(ws).contiguous(), 32, torch.stack(bs).contiguous())
+        return self._cached(("pack", plan.dtype, plan.device, j, id(twin), cin_pad, stem), make)
+
+    def emit(self, plan, x, out=None, twin=None):
+        paired = twin is not None
+        vec = ops.VEC[plan.dtype]
+        pool = self.vggblock[-1]
+        if not isinstance(pool, nn.MaxPool2d) or pool.dilation not in (1, (1, 1)) or pool.ceil_mode:
+            raise NotImplementedError("VGGblock ends with a plain nn.MaxPool2d")
+        pk, ps, pp = (v if isinstance(v, int) else v[0] for v in (pool.kernel_size, pool.stride, pool.padding))
+        for s in list(self.vggblock)[:-1]:
+            if not (isinstance(s, nn.Sequential) and len(s) == 2 and isinstance(s[0], nn.Conv2d) and isinstance(s[1], nn.ReLU)):
+                raise NotImplementedError("VGGblock rows are Sequential(Conv2d, ReLU): another activation is outside the hot path")
+        for j, k in enumerate(self.convs()):
+            if (k.kernel_size, k.stride, _pair(k.padding), k.groups, k.dilation) != ((3, 3), (1, 1), (1, 1), 1, (1, 1)) or k.bias is None:
+                raise NotImplementedError("VGGblock convolutions are 3x3 / stride 1 / padding 1 with bias")
+            c1, c2 = k.in_channels, k.out_channels
+            if isinstance(x, ImageIn):
+                assert j == 0 and x.pair == paired
+                B, _, H, W = x.shape
+                y = plan.act(B, H, W, c2, pair=paired)
+                if self.fuse_stem and plan.dtype in (torch.bfloat16, torch.float16) and (c1, c2) == (3, 64):
+                    wp, _, bp = self._packed(plan, 0, twin, stem=True)
+                    plan.add(ops.vgg_stem(x.t, wp, bp, y, c0=x.c0 if x.u8 else 0))
+                    x = y
+                    continue
+                cpad = -(-c1 // vec) * vec
+                pre = plan.act(B, H, W, cpad, pair=paired)
+                plan.add(ops.preprocess_u8(x.t, pre, 0, x.c0, name="preprocess_u8_pad") if x.u8
+                         else ops.preprocess(x.t, pre, 0, name="preprocess_pad"))
+                wp, kp, bp = self._packed(plan, 0, twin, cin_pad=cpad)
+                x, c1 = pre, cpad
+            else:
+                assert (x.dim() == 5) == paired
+                if x.shape[-1] != c1:
+                    raise ValueError(f"VGGblock conv {j} expects {c1} input channels, got {x.shape[-1]}")
+                if c1 % vec:
+                    raise NotImplementedError(f"channel count {c1} must be a multiple of {vec} for dtype {plan.dtype}")
+                B, H, W = x.shape[-4:-1]
+                y = plan.act(B, H, W, c2, pair=paired)
+                wp, kp, bp = self._packed(plan, j, twin)
+            plan.add(ops.conv2d(x, wp, kp, bp, y, 3, 3, 1, 1, 1, 1, c1, c2, ops.ACT_RELU, name="vgg_conv3x3"))
+            x = y
+        B, H, W, c2 = x.shape[-4:]
+        Ho, Wo = (H + 2 * pp - pk) // ps + 1, (W + 2 * pp - pk) // ps + 1
+        if out is None:
+            out = plan.act(B, Ho, Wo, c2, pair=paired)
+        if paired and out.stride(0) != B * out.stride(1):      # the streams are channel slices of one fusion buffer: one launch each
+            for g in range(2):
+                plan.add(ops.maxpool2d(x[g], out[g], pk, ps, pp, name="vgg_maxpool"))
+        else:
+            plan.add(ops.maxpool2d(x, out, pk, ps, pp, name="vgg_maxpool"))
+        return out
+
+
 class Bottleneck(HipModule):
     """1x1 -> 3x3 with optional identity shortcut (reference models/common.py:184-194); the shortcut add is the
     residual term of the second conv's epilogue (which may write in place over its own residual: every output

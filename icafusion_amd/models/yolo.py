@@ -21,11 +21,11 @@ import torch.nn as nn
 from .. import ops
 from ..engine import ImageIn, Plan, TtaPlan
 from .common import (C3, SPPF, Add, Bottleneck, Concat, Conv, Detect, HipModule, NiNfusion,  # noqa: F401
-                     TransformerFusionBlock, VirtualCat, emit_upsample)
+                     TransformerFusionBlock, VGGblock, VirtualCat, emit_upsample)
 
 logger = logging.getLogger(__name__)
 _NAMESPACE = {"Conv": Conv, "C3": C3, "SPPF": SPPF, "Bottleneck": Bottleneck, "Concat": Concat, "Detect": Detect,
-              "TransformerFusionBlock": TransformerFusionBlock, "NiNfusion": NiNfusion, "Add": Add, "nn": nn}
+              "TransformerFusionBlock": TransformerFusionBlock, "NiNfusion": NiNfusion, "Add": Add, "VGGblock": VGGblock, "nn": nn}
 
 
 def make_divisible(x, divisor):
@@ -101,6 +101,8 @@ def parse_model(d, ch):
             if m is C3:
                 args.insert(2, n)
                 n = 1
+        elif m is VGGblock:                                   # reference models/yolo_test.py:260-261: (num_convs, c1, c2) as written
+            c2 = args[2]
         elif m is Concat:
             c2 = sum(ch[x] for x in f)
         elif m is Detect:
@@ -162,7 +164,7 @@ def emit_any(m, plan, src, out=None, twin=None, lead=None):
     return m.emit(plan, src, out=out, **kw)
 
 
-PAIRABLE = (Conv, C3, SPPF)
+PAIRABLE = (Conv, C3, SPPF, VGGblock)
 
 
 def _same_structure(a, b):
@@ -177,7 +179,11 @@ def _same_structure(a, b):
         return False
     geo = lambda m: [(c.kernel_size, c.stride, c.padding, c.groups) for c in m.modules() if isinstance(c, nn.Conv2d)]  # noqa: E731
     acts = lambda m: [type(c.act) for c in m.modules() if isinstance(c, Conv)]                                       # noqa: E731
-    return geo(a) == geo(b) and acts(a) == acts(b)
+    # a VGGblock's activations and pool are plain torch modules of its `vggblock`: same kinds, same window
+    tail = lambda m: [(type(c), getattr(c, "kernel_size", None), getattr(c, "stride", None), getattr(c, "padding", None))      # noqa: E731
+                      for v in m.modules() if isinstance(v, VGGblock) for s in v.vggblock for c in (s if isinstance(s, nn.Sequential) else [s])
+                      if not isinstance(c, nn.Conv2d)]
+    return geo(a) == geo(b) and acts(a) == acts(b) and tail(a) == tail(b)
 
 
 class Model(HipModule):
@@ -278,7 +284,13 @@ class Model(HipModule):
         tp = plans.pop(key, None)
         if tp is None:
             passes = tta_sizes(H, W, gs)
-            subs = [self.plan_for(B, p[4], p[5], device, dt, u8=u8 and i == 0, slot=slot, branches=branches) for i, p in enumerate(passes)]
+            # passes padded to the SAME size (inputs of a stride or two: 32 x 32 pads every pass to 32 x 32) need plans of their own — one plan
+            # cannot hold two passes' inputs: the k-th repeat of a size takes the plan of slot + 100 k
+            seen, subs = {}, []
+            for i, p in enumerate(passes):
+                k = seen.get((p[4], p[5], u8 and i == 0), 0)
+                seen[(p[4], p[5], u8 and i == 0)] = k + 1
+                subs.append(self.plan_for(B, p[4], p[5], device, dt, u8=u8 and i == 0, slot=slot + 100 * k, branches=branches))
             full = subs[0]
             src = full.inputs[0] if u8 else full.input_pair
             stage = ops.tta_stage(src, [(sp.input_pair, p[2], p[3], p[1] == 3) for sp, p in zip(subs[1:], passes[1:])])
@@ -309,7 +321,7 @@ class Model(HipModule):
         return (tp.outputs if self.static_outputs else tp.outputs.clone()), None
 
     def fuse(self):
-        """Fold BatchNorm into the convs in place (reference models/yolo_test.py:182-190)."""
+        """Fold BatchNorm into the convs in place (reference models/yolo_test.py:182-190).  A VGGblock has none: nothing to fold."""
         for m in self.model.modules():
             if type(m) is Conv and hasattr(m, "bn"):
                 with torch.no_grad():
@@ -343,6 +355,10 @@ class Model(HipModule):
                 cur = (m.cv3.conv.out_channels, src[1], src[2])
             elif isinstance(m, SPPF):
                 cur = (m.cv2.conv.out_channels, src[1], src[2])
+            elif isinstance(m, VGGblock):               # 3x3 / s1 / p1 convs keep the size, the closing pool halves it (floor)
+                pool = m.vggblock[-1]
+                k, s_, p = (v if isinstance(v, int) else v[0] for v in (pool.kernel_size, pool.stride, pool.padding))
+                cur = (m.convs()[-1].out_channels, (src[1] + 2 * p - k) // s_ + 1, (src[2] + 2 * p - k) // s_ + 1)
             elif isinstance(m, nn.Upsample):
                 s = int(m.scale_factor)
                 cur = (src[0], src[1] * s, src[2] * s)

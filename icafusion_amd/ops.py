@@ -15,7 +15,7 @@ import torch
 
 from . import _lib
 from .options import OPT
-from ._lib import BneckArgs, ConvArgs, DmffArgs, FrameGeom, Stem2Args, check, lib, F32, BF16, F16, ACT_NONE, ACT_SILU, ACT_GELU  # noqa: F401
+from ._lib import BneckArgs, ConvArgs, DmffArgs, FrameGeom, Stem2Args, check, lib, F32, BF16, F16, ACT_NONE, ACT_SILU, ACT_GELU, ACT_RELU  # noqa: F401
 
 _DT = {torch.float32: F32, torch.bfloat16: BF16, torch.float16: F16}
 VEC = {torch.float32: 4, torch.bfloat16: 8, torch.float16: 8}     # elements per 16-byte vector
@@ -303,7 +303,10 @@ def wants_wf(a):
 
 def conv_candidates(a):
     """Launch-configuration ids worth timing for one conv (ConvArgs `a`), each id's rule stated once, by kernel family; chained / pre-term
-    launches only have the configurations that are built for them.  Ids the library builds and no rule offers: BUILT_NOT_OFFERED."""
+    launches only have the configurations that are built for them.  Ids the library builds and no rule offers: BUILT_NOT_OFFERED.
+    Activations: igemm.hip, igemm_stream.hip and igemm_wreg.hip dispatch on all four codes (128 x 512 of igemm_wreg not on GELU); cstream.hip,
+    cwide.hip, ctile.hip and every chained / pre-term launch are SiLU-only — `L.silu` below is the library's own check, so a ReLU layer
+    (VGGblock) is never offered an id of theirs."""
     L = _Layer(a)
     big1 = a.out_dtype != F32 and a.Cout > 64                              # the 128x128 tile: no fp32-output build, and 128x64 serves Cout <= 64
     if L.tail:                         # C3 tail (the chained cv3 reads [tile | x2]): cwide.hip's 8 x 16 / 8 x 8 forms only
@@ -538,6 +541,52 @@ def stem2(img, w0, kp0, b0, w1, kp1, b1, w2, kp2, b2, y, c0, c1, c2, name="stem+
     flops = 2.0 * g * B * (hs * ws * c0 * 144 + Ho * Wo * (c1 * 9 * c0 + c2 * c1))
     nb = g * B * (3 * H * W * (1 if u8 else 4) + Ho * Wo * c2 * y.element_size())
     return Launch(lib().icaf_stem2, (C.byref(a),), keep=(a, img, w0, b0, w1, b1, w2, b2, y), name=name, flops=flops, nbytes=nb)
+
+
+def vgg_stem_weight(w4d, dt):
+    """[64][3][3][3] fp32 -> [64][32] in dtype dt: K = 27 in the order (ky, kx, c), zero-padded to 32 (icaf_vgg_stem)."""
+    co, ci, kh, kw = w4d.shape
+    assert (co, ci, kh, kw) == (64, 3, 3, 3)
+    out = torch.zeros((co, 32), dtype=dt, device=w4d.device)
+    out[:, :27] = w4d.permute(0, 2, 3, 1).reshape(co, 27).to(dt)
+    return out
+
+
+def vgg_stem(img, w, bias, y, c0=0, name="vgg_stem"):
+    """Image-fed 3x3 / s1 / p1 conv 3 -> 64 + bias + ReLU in one launch (icaf_vgg_stem).  img: fp32 (B, 3, H, W) / (2, B, 3, H, W) [both
+    streams], or uint8 (B, Ctot, H, W) read from channel c0 on (both streams: [c0, c0 + 6)); w: vgg_stem_weight packs ([64][32], stacked per
+    stream for a pair act y), bias fp32 [64] / [2][64]; y: act or pair act of 64 channels at the image's resolution."""
+    u8 = img.dtype == torch.uint8
+    paired = y.dim() == 5
+    g = 2 if paired else 1
+    assert img.is_contiguous() and (u8 or img.dtype == torch.float32)
+    if u8:
+        assert img.dim() == 4 and c0 + 3 * g <= img.shape[1]
+        B, ctot, H, W = img.shape
+    else:
+        assert img.dim() == (5 if paired else 4) and img.shape[-3] == 3 and c0 == 0
+        B, _, H, W = img.shape[-4:]
+        ctot = 3
+    By, Ho, Wo, cy, ldy = _act_geom(y)
+    assert (By, Ho, Wo) == (B, H, W) and cy >= 64 and w.dtype == y.dtype and w.shape[-2:] == (64, 32) and w.dim() == (3 if paired else 2)
+    assert bias.dtype == torch.float32 and bias.shape[-1] >= 64 and w.is_contiguous() and bias.stride(-1) == 1
+    nb = g * B * 3 * H * W * (1 if u8 else 4) + g * B * H * W * 64 * y.element_size()
+    flops = 2.0 * g * B * H * W * 64 * 27
+    return Launch(lib().icaf_vgg_stem, (img.data_ptr() + c0 * H * W, int(u8), ctot, w.data_ptr(), bias.data_ptr(), y.data_ptr(), ldy,
+                                        dtype_code(y.dtype), g, B, H, W, 64, 32,
+                                        w.stride(0) if paired else 0, bias.stride(0) if paired else 0, y.stride(0) if paired else 0),
+                  keep=(img, w, bias, y), name=name, flops=flops, nbytes=nb)
+
+
+def maxpool2d(x, y, k=2, s=2, p=0, name="maxpool2d"):
+    """nn.MaxPool2d(k, s, p) over an act or a pair act (2B images): (k, s, p) = (2, 2, 0) or (3, 2, 1), floor output size."""
+    x, y = flat_pair(x), flat_pair(y)
+    B, H, W, Cc, ldx = _act_geom(x)
+    By, Ho, Wo, Cy, ldy = _act_geom(y)
+    assert (By, Cy) == (B, Cc) and (Ho, Wo) == ((H + 2 * p - k) // s + 1, (W + 2 * p - k) // s + 1) and y.dtype == x.dtype
+    nb = (B * H * W + B * Ho * Wo) * Cc * x.element_size()
+    return Launch(lib().icaf_maxpool2d, (x.data_ptr(), ldx, y.data_ptr(), ldy, dtype_code(x.dtype), B, H, W, Cc, k, s, p),
+                  keep=(x, y), name=name, nbytes=nb)
 
 
 def sppf_pool(x, y1, y2, y3, k, name="sppf_pool"):

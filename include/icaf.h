@@ -31,7 +31,7 @@ extern "C" {
 typedef void* icaf_stream_t; /* hipStream_t */
 
 enum { ICAF_F32 = 0, ICAF_BF16 = 1, ICAF_F16 = 2 };
-enum { ICAF_ACT_NONE = 0, ICAF_ACT_SILU = 1, ICAF_ACT_GELU = 2 };
+enum { ICAF_ACT_NONE = 0, ICAF_ACT_SILU = 1, ICAF_ACT_GELU = 2, ICAF_ACT_RELU = 3 };
 enum { ICAF_OK = 0, ICAF_ERR_ARG = -1, ICAF_ERR_HIP = -2, ICAF_ERR_UNSUPPORTED = -3 };
 
 const char* icaf_last_error(void);
@@ -90,6 +90,18 @@ typedef struct icaf_stem2_args {
 } icaf_stem2_args;
 int icaf_stem2(const icaf_stem2_args* a, icaf_stream_t s);
 
+/* Image-fed first layer of a VGG block (models/common.py:109-128: Conv2d(3, 64, 3, padding=1) + ReLU, yaml rows 0 and 5 of the
+ * yolov5_VGG16_* files) in one launch, both streams: y = ReLU(conv3x3 / s1 / p1 (img) + bias) computed straight from the NCHW images
+ * (img / img_u8 / ctot as icaf_stem; the uint8 value / 255 is a true division, as icaf_preprocess_u8) — no staged copy of the images is
+ * written.  w: [nstreams][64][32] in the storage type, K = 27 in the order (ky, kx, c) zero-padded to 32 (icafusion_amd.ops.vgg_stem_weight);
+ * bias: fp32 [nstreams][64]; y: NHWC [nstreams][B][H][W][ldy], written as 128-byte pixels with 16-byte stores (ldy % 8 == 0, 16-byte aligned);
+ * *_gs = per-stream strides in elements / floats.  The images are rounded to the storage type first (what the staged copy of the generic
+ * route holds), products and the 27-term sum are fp32, bias and ReLU fp32, ONE rounding at the store.  16-bit types, Cout = 64, Kp = 32,
+ * H, W <= 2^20; everything else is refused before any launch (fp32 runs icaf_preprocess_* + icaf_conv2d). */
+int icaf_vgg_stem(const void* img, int img_u8, int ctot, const void* w, const float* bias, void* y, int ldy, int dtype,
+                  int nstreams, int B, int H, int W, int Cout, int Kp, long long w_gs, long long bias_gs, long long y_gs,
+                  icaf_stream_t s);
+
 /* ---- implicit-GEMM convolution / linear ------------------------------------------------------------------
  * Replaces Conv.forward / fuseforward (models/common.py:48-60: SiLU(BN(Conv2d))) with BN folded into the
  * weights (utils/torch_utils.py:182-202), nn.Linear (+GELU) inside CrossAttention / CrossTransformerBlock
@@ -106,7 +118,7 @@ int icaf_stem2(const icaf_stem2_args* a, icaf_stream_t s);
  * Rounding.  The sum, bias, pre term, activation and alpha_acc are evaluated in fp32.  The result is rounded to out_dtype (nearest even,
  * subnormals kept); with a residual, alpha_res * res is then added to that ROUNDED value by one fp32 fma and the sum rounded to out_dtype
  * again — the rounding points of the unfused layers (a convolution's output is a tensor of the storage type, the shortcut adds to it).
- * With fp32 output nothing is rounded in between.  ACT_SILU uses the hardware exp2 / reciprocal (-0 for pre-activations below -87.3, where
+ * With fp32 output nothing is rounded in between.  ACT_RELU is max(v, 0), torch.relu for every finite v; ACT_SILU uses the hardware exp2 / reciprocal (-0 for pre-activations below -87.3, where
  * the true value is below 1.05e-36); ACT_GELU is erff in the fp32 build and Abramowitz & Stegun 7.1.26 in the 16-bit builds, accurate to
  * 0.5 |v| (1.5e-7 + 2^-23) in ABSOLUTE terms: several fp16 units of the result for v <= -3.5.
  * Reads and writes.  x, res and pre may be channel slices of wider buffers holding anything, Inf and NaN included: no launch configuration
@@ -140,6 +152,8 @@ typedef struct icaf_conv_args {
                *   igemm.hip         tile + 10 * pipeline: 1 - 4, 11 - 14, 21 - 26, 28, 29, 31 - 34
                *   ctile.hip         41 - 45          igemm_stream.hip  51, 52          igemm_wreg.hip  61 - 66
                *   cstream.hip       71               cwide.hip         81 - 85
+               * ACT_RELU runs on igemm.hip, igemm_stream.hip and igemm_wreg.hip; ctile / cstream / cwide and the chained / pre-term launches
+               * are SiLU-only and answer ICAF_ERR_UNSUPPORTED before any device call.
                * Every configuration of a layer produces the same bits (same K order, MFMA step, epilogue expressions). */
     /* Optional pre-activation term, bilinearly resized (align_corners=False) from a coarse fp32 map:
      *   y = alpha_res*res + alpha_acc * act( A.W + bias + bilinear(pre)[b][ho][wo][n] )
@@ -224,6 +238,13 @@ int icaf_sppf_pool(const void* x, int ldx, void* y1, void* y2, void* y3, int ldy
 int icaf_sppf_config(int dtype, int H, int W, int C, int* vpb);
 int icaf_upsample_nearest(const void* x, int ldx, void* y, int ldy, int dtype, int B, int H, int W, int C,
                           int scale, icaf_stream_t s);
+/* nn.MaxPool2d(k, stride, pad) over an NHWC tensor (models/common.py:122: the 2 / 2 / 0 pool closing a VGGblock; 3 / 2 / 1 is ResNet's):
+ * y[b][ho][wo][c] = max over the window's pixels INSIDE the image (padding never takes part: it acts as -inf), Ho = (H + 2 pad - k) /
+ * stride + 1 (floor).  x / y may be channel slices (ldx, ldy >= C); a pair activation is 2 B images.  The bits are those of torch's CPU
+ * kernel (same scan order and comparison, NaN propagates).  C must be a multiple of the 16-byte vector width (4 fp32 / 8 16-bit); 16-byte
+ * loads and stores where ldx, ldy and both addresses allow, one element per thread otherwise.  Other windows: ICAF_ERR_UNSUPPORTED. */
+int icaf_maxpool2d(const void* x, int ldx, void* y, int ldy, int dtype, int B, int H, int W, int C, int k, int stride, int pad,
+                   icaf_stream_t s);
 int icaf_copy_channels(const void* x, int ldx, void* y, int ldy, int dtype, long long rows, int C,
                        icaf_stream_t s);
 /* icaf_axpby: y = a*x0 + b*x1 over `rows` pixels of C channels — the `Add` fusion block (models/common.py:324-331:
