@@ -30,7 +30,7 @@ class ConvArgs(C.Structure):
         ("w2_gs", C.c_longlong), ("bias2_gs", C.c_longlong), ("y2_gs", C.c_longlong),
         ("Kp2", C.c_int), ("Cout2", C.c_int), ("ldy2", C.c_int), ("chain_keep", C.c_int),
         ("wf", C.c_void_p), ("wf_gs", C.c_longlong),
-        ("x2", C.c_void_p), ("x2_gs", C.c_longlong), ("ldx2", C.c_int), ("reserved2", C.c_int),
+        ("x2", C.c_void_p), ("x2_gs", C.c_longlong), ("ldx2", C.c_int), ("res_mode", C.c_int),
     ]
 
 
@@ -109,6 +109,7 @@ SIGNATURES = {
     "icaf_cross_attention": (_i, [_p, _p, _i, _i, _i, _i, _i, _p]),
     "icaf_dmff_pool_config": (_i, [_i] * 11 + [C.POINTER(_i)] * 4),
     "icaf_cross_attention_config": (_i, [_i, _i, _i, _i, _i, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)]),
+    "icaf_cross_attention_form": (_i, [_i, _i, _i, _i, _i, C.POINTER(_i)]),
     "icaf_dmff_ln_qkv": (_i, [C.POINTER(DmffArgs), _p]),
     "icaf_dmff_attn_mlp": (_i, [C.POINTER(DmffArgs), _p]),
     "icaf_dmff_wide_ln_qkv": (_i, [C.POINTER(DmffArgs), _p]),

@@ -96,9 +96,37 @@ def vgg16_cfg(fusion="Transfusion", nc=1):
             "backbone": backbone, "head": head}
 
 
-def _dump_model_yaml(cfg, title, streams="CSPDarknet"):
-    lines = [f"# {title}", f"# generated by icafusion_amd/configs.py — two RGB/IR {streams} streams, three DMFF",
-             "# (TransformerFusionBlock) taps at P3/P4/P5, PANet head, Detect.  Row = [from, number, module, args];",
+# (fusion block, dataset tag, nc) — the ResNet50-backbone variants the reference ships
+RESNET50_VARIANTS = [("Transfusion", "kaist", 1), ("Transfusion", "FLIR", 3), ("NiNfusion", "kaist", 1), ("NiNfusion", "FLIR", 3)]
+# (c1, c2, stride, is_first, num_blocks) as the reference writes them: the 7x7 stem row, then 3-4-6-3 bottleneck blocks ending on 4 * c2 channels
+RESNET50_ROWS = ((3, 64, 1, True, 1), (64, 64, 1, False, 3), (256, 128, 2, False, 4), (512, 256, 2, False, 6), (1024, 512, 2, False, 3))
+RESNET50_TAPS = ((2, 7, 512), (3, 8, 1024), (4, 9, 2048))                                 # (RGB row, IR row, channels) at strides 8, 16, 32
+
+
+def resnet50_cfg(fusion="Transfusion", nc=1):
+    """Two ResNet50 streams (five ResNetlayer rows each, models/common.py:131-181), DMFF ("Transfusion") or NiNfusion taps behind rows 2, 3
+    and 4 (C = 512 / 1024 / 2048), and a PANet head on the reference's widths 1024 / 512 / 512 / 1024 / 1024 / 2048."""
+    backbone = [[f if i == 0 else -1, 1, "ResNetlayer", list(r)] for f in (-1, -4) for i, r in enumerate(RESNET50_ROWS)]
+    for (a, b, c), (va, ha) in zip(RESNET50_TAPS, TOKENS):
+        backbone.append([[a, b], 1, "NiNfusion", [1, 1]] if fusion == "NiNfusion" else [[a, b], 1, "TransformerFusionBlock", [c, va, ha]])
+    head = [
+        [-1, 1, "Conv", [1024, 1, 1]], [-1, 1, "nn.Upsample", ["None", 2, "nearest"]], [[-1, 11], 1, "Concat", [1]],
+        [-1, 3, "C3", [1024, False]],
+        [-1, 1, "Conv", [512, 1, 1]], [-1, 1, "nn.Upsample", ["None", 2, "nearest"]], [[-1, 10], 1, "Concat", [1]],
+        [-1, 3, "C3", [512, False]],
+        [-1, 1, "Conv", [512, 3, 2]], [[-1, 17], 1, "Concat", [1]], [-1, 3, "C3", [1024, False]],
+        [-1, 1, "Conv", [1024, 3, 2]], [[-1, 13], 1, "Concat", [1]], [-1, 3, "C3", [2048, False]],
+        [[20, 23, 26], 1, "Detect", ["nc", "anchors"]],
+    ]
+    return {"nc": nc, "depth_multiple": 1.0, "width_multiple": 1.0, "anchors": [list(a) for a in ANCHORS],
+            "backbone": backbone, "head": head}
+
+
+def _dump_model_yaml(cfg, title, streams="CSPDarknet", fusion="Transfusion"):
+    """fusion: what the header says the three taps are — the files written before the ResNet50 ones keep the DMFF wording whatever they fuse with"""
+    taps = {"Transfusion": ("three DMFF", "# (TransformerFusionBlock)"), "NiNfusion": ("three NiNfusion", "# (concatenate + 1x1 Conv)")}[fusion]
+    lines = [f"# {title}", f"# generated by icafusion_amd/configs.py — two RGB/IR {streams} streams, {taps[0]}",
+             f"{taps[1]} taps at P3/P4/P5, PANet head, Detect.  Row = [from, number, module, args];",
              "# from=-4 feeds the IR image; optional trailing {loops_num: n} DMFF arg = number of parameter-shared iterations.",
              f"nc: {cfg['nc']}", f"depth_multiple: {cfg['depth_multiple']}", f"width_multiple: {cfg['width_multiple']}",
              "anchors:"]
@@ -129,6 +157,10 @@ def write_all(root):
         name = f"yolov5_VGG16_{fusion}_{tag}.yaml"
         with open(os.path.join(root, "models", "transformer", name), "w") as f:
             f.write(_dump_model_yaml(vgg16_cfg(fusion, nc), name, streams="VGG16"))
+    for fusion, tag, nc in RESNET50_VARIANTS:
+        name = f"yolov5_ResNet50_{fusion}_{tag}.yaml"
+        with open(os.path.join(root, "models", "transformer", name), "w") as f:
+            f.write(_dump_model_yaml(resnet50_cfg(fusion, nc), name, streams="ResNet50", fusion=fusion))
     for tag, (nc, names) in DATASETS.items():
         d = f"/data/{tag}"
         body = {"path": d, "train_rgb": f"{d}/visible/train/", "val_rgb": f"{d}/visible/test/",

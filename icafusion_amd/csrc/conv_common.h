@@ -55,11 +55,46 @@ int launch_bneck(const icaf_conv_args* a, const ConvP& p, int shape, hipStream_t
 // An activation added to a family is therefore selected at the ROOT of that family's dispatch (launch_igemm, launch_stream, launch_wreg:
 // `bool RELU`), in a branch written behind the existing ones: its kernels are numbered last and every other kernel's text stays byte-identical.
 // DT = the layer's storage type: the 16-bit builds evaluate GELU's erf by a 1.5e-7-accurate polynomial (gelu_fast_f), fp32 by erff
+// ACT_RELU_RES: the epilogue-internal form of icaf_conv_args.res_mode = 1 (icaf.h): ReLU with the residual added IN FRONT of it,
+//   y = relu(A.W + bias + res)       (a ResNet bottleneck's conv3 + bn3 + shortcut add + ReLU, reference models/common.py:149-156)
+// It is a value of the kernels' ACT template parameter, not a fifth public activation code: the mode is then a compile-time property of
+// every epilogue, an existing kernel's mangled name and text do not change, and the instantiations hang behind the ReLU ones at the root
+// of each family's dispatch (`int RELU`: 0 = by p.act, 1 = ReLU, 2 = ReLU with the residual in front).
+constexpr int ACT_RELU_RES = 16 + ICAF_ACT_RELU;
 template <int ACT, int DT = ICAF_F32> __device__ __forceinline__ float apply_act(float v) {
     if constexpr (ACT == ICAF_ACT_SILU) return silu_f(v);
     else if constexpr (ACT == ICAF_ACT_GELU) return DT == ICAF_F32 ? gelu_f(v) : gelu_fast_f(v);
-    else if constexpr (ACT == ICAF_ACT_RELU) return fmaxf(v, 0.0f);      // torch.relu for finite v (one v_max_f32)
+    else if constexpr (ACT == ICAF_ACT_RELU || ACT == ACT_RELU_RES) return fmaxf(v, 0.0f);      // torch.relu for finite v (one v_max_f32)
     else return v;
+}
+// res_mode = 1: the four residual values a lane's accumulator quad meets — channels n .. n + 3 of output pixel m (m < 0: a tile row outside
+// the tensor), read in the storage type and widened to fp32.  One 8-byte (fp32: 16-byte) load where the residual view takes vectors
+// (vec_r: ldr and the base are whole 16-byte vectors, n is a multiple of 4) and the quad lies inside [0, Cout); element by element otherwise,
+// and never outside [0, Cout) of a pixel.
+template <int DT> __device__ __forceinline__ void load_res_quad(const typename Elem<DT>::type* __restrict__ rg, int m, int ldr, int n, int Cout, int vec_r, float (&r)[4]) {
+    using E = Elem<DT>;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) r[j] = 0.0f;
+    if (m < 0 || n >= Cout) return;
+    const typename E::type* rp = rg + (long long)m * ldr + n;
+    if (vec_r && n + 4 <= Cout) {
+        if constexpr (DT == ICAF_F32) {
+            const f32x4 t = *(const f32x4*)rp;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) r[j] = t[j];
+        } else {
+            const u32x2 t = *(const u32x2*)rp;
+            if constexpr (DT == ICAF_BF16) {
+                r[0] = __uint_as_float(t[0] << 16); r[1] = __uint_as_float(t[0] & 0xffff0000u);
+                r[2] = __uint_as_float(t[1] << 16); r[3] = __uint_as_float(t[1] & 0xffff0000u);
+            } else {
+                r[0] = f16_to_f32((unsigned short)(t[0] & 0xffffu)); r[1] = f16_to_f32((unsigned short)(t[0] >> 16));
+                r[2] = f16_to_f32((unsigned short)(t[1] & 0xffffu)); r[3] = f16_to_f32((unsigned short)(t[1] >> 16));
+            }
+        }
+    } else {
+        for (int j = 0; j < 4 && n + j < Cout; ++j) r[j] = E::ld(rp + j);
+    }
 }
 // four values at once: SiLU goes through silu4_f (packed middle steps, same bits), everything else value by value
 template <int ACT, int DT = ICAF_F32> __device__ __forceinline__ void apply_act4(const float (&x)[4], float (&y)[4]) {
@@ -101,6 +136,7 @@ __device__ __forceinline__ void epilogue(f32x16 (&acc)[WN / 32][WM / 32], unsign
     const float alpha_acc = SECOND ? 1.0f : p.alpha_acc[g], alpha_res = p.alpha_res[g];
     const float* __restrict__ bias = SECOND ? (p.bias2 ? p.bias2 + g * p.bias2_gs : nullptr) : (p.bias ? p.bias + g * p.bias_gs : nullptr);
     const int Cout = SECOND ? p.Cout2 : p.Cout, ldy = SECOND ? p.ldy2 : p.ldy, vec_y = SECOND ? p.vec_y2 : p.vec_y;
+    static_assert(ACT != ACT_RELU_RES || (!PRE && !SECOND && !WB && !FULLVEC && ODT == DT), "res_mode = 1: a plain same-type layer");
     if constexpr (PRE) {
         // The pre-activation term is added in the WRITE-BACK phase.  With the lane = pixel mapping of the accumulators (round 4's per-lane taps) every tap load was 64
         // lanes x 16 bytes in 64 different rows of the fp32 map (a row is Cout * 4 = 512 - 2048 bytes): uncoalesced, 16 * TN * TM such loads per lane —
@@ -239,6 +275,12 @@ __device__ __forceinline__ void epilogue(f32x16 (&acc)[WN / 32][WM / 32], unsign
                 // (+ 0.0f: what is left of the old pre-term path's zero term; the compiler may not fold it, so today's device code contains the add
                 //  — removing it changes every convolution kernel)
                 for (int j = 0; j < 4; ++j) xin[j] = acc[a][b][4 * q + j] + bv[j] + 0.0f;
+                if constexpr (ACT == ACT_RELU_RES) {       // the residual joins the fp32 sum in front of the ReLU: ONE rounding, at the store
+                    float rq[4];
+                    load_res_quad<DT>((const typename E::type*)p.res + g * p.res_gs, row_to_m(ml), p.ldr, n0 + nl, Cout, p.vec_r, rq);
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) xin[j] += rq[j];
+                }
                 apply_act4<ACT, DT>(xin, v);
 #pragma unroll
                 for (int j = 0; j < 4; ++j) v[j] *= alpha_acc;
@@ -257,7 +299,8 @@ __device__ __forceinline__ void epilogue(f32x16 (&acc)[WN / 32][WM / 32], unsign
     __syncthreads();
 
     typename EO::type* __restrict__ yg = SECOND ? (typename EO::type*)p.y2 + g * p.y2_gs : (typename EO::type*)p.y + g * p.y_gs;
-    const typename E::type* __restrict__ rg = (!SECOND && p.res) ? (const typename E::type*)p.res + g * p.res_gs : nullptr;
+    // (ACT_RELU_RES has consumed the residual above: its write-back is the one of a layer without one)
+    const typename E::type* __restrict__ rg = (!SECOND && p.res && ACT != ACT_RELU_RES) ? (const typename E::type*)p.res + g * p.res_gs : nullptr;
     constexpr int VPR = BN / VO;                       // 16-byte vectors per staged row
     constexpr int NVEC = BM * VPR;
     constexpr int NIT = (NVEC + NT - 1) / NT;

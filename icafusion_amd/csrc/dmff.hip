@@ -254,6 +254,66 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const typename Elem<DT>:
     }
 }
 
+// fp32 rows of 1024 < C <= 2048 (the parity build of a DMFF level at C = 2048): layernorm_kernel's statements with MAXV vectors per lane
+// (8: 32 value registers more).  layernorm_kernel itself stays as it is and serves every row it served.
+template <int DT, int MAXV>
+__device__ __forceinline__ void layernorm_row(const typename Elem<DT>::type* __restrict__ x, typename Elem<DT>::type* __restrict__ y,
+                                              const float* __restrict__ g0, const float* __restrict__ b0,
+                                              const float* __restrict__ g1, const float* __restrict__ b1,
+                                              long long rows_per_group, int C, int groups, float eps) {
+    using E = Elem<DT>;
+    const int lane = threadIdx.x & 63;
+    const long long row = (long long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    if (row >= rows_per_group * groups) return;
+    const int grp = (int)(row / rows_per_group);
+    const float* gam = grp ? g1 : g0;
+    const float* bet = grp ? b1 : b0;
+    const int nv = C / E::VEC;
+    float val[MAXV][E::VEC];
+    float s = 0.0f;
+#pragma unroll
+    for (int i = 0; i < MAXV; ++i) {
+        const int v = lane + 64 * i;
+        if (v < nv) {
+            unpack16<DT>(*(const u32x4*)(x + row * C + v * E::VEC), val[i]);
+#pragma unroll
+            for (int j = 0; j < E::VEC; ++j) s += val[i][j];
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+    const float mean = s / (float)C;
+    float q = 0.0f;
+#pragma unroll
+    for (int i = 0; i < MAXV; ++i) {
+        const int v = lane + 64 * i;
+        if (v < nv) {
+#pragma unroll
+            for (int j = 0; j < E::VEC; ++j) { const float d = val[i][j] - mean; q += d * d; }
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) q += __shfl_xor(q, o);
+    const float rstd = 1.0f / sqrtf(q / (float)C + eps);
+#pragma unroll
+    for (int i = 0; i < MAXV; ++i) {
+        const int v = lane + 64 * i;
+        if (v < nv) {
+            float o[E::VEC];
+#pragma unroll
+            for (int j = 0; j < E::VEC; ++j) o[j] = (val[i][j] - mean) * rstd * gam[v * E::VEC + j] + bet[v * E::VEC + j];
+            *(u32x4*)(y + row * C + v * E::VEC) = pack16<DT>(o);
+        }
+    }
+}
+template <int DT>
+__global__ __launch_bounds__(256) void layernorm_wide_kernel(const typename Elem<DT>::type* __restrict__ x, typename Elem<DT>::type* __restrict__ y,
+                                                             const float* __restrict__ g0, const float* __restrict__ b0,
+                                                             const float* __restrict__ g1, const float* __restrict__ b1,
+                                                             long long rows_per_group, int C, int groups, float eps) {
+    layernorm_row<DT, 8>(x, y, g0, b0, g1, b1, rows_per_group, C, groups, eps);
+}
+
 // ---------------------------------------------------------------------------------------------------------------
 // Cross attention (reference models/common.py:670-685)
 //   out[dir] = softmax( Q_{1-dir} K_dir^T / sqrt(dk) ) V_dir          per (batch, head), dir = 0 (RGB) / 1 (IR)
@@ -463,9 +523,259 @@ __global__ __launch_bounds__(256) void upsample_merge_kernel(const typename Elem
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// Cross attention, key-streaming form: the shapes whose K / V^T of a head do not fit the LDS (cross_attn_kernel keeps them resident) or
+// whose head dimension exceeds 128 — ResNet50's C = 2048 level (d_k = 256), the fp32 parity build of its C = 1024 level.
+//
+// Same arithmetic as the resident kernel, same key order: S^T = K Q^T per 32-key tile, online softmax (deferred maximum in the 16-bit
+// types; VALU row sums and no deferral in fp32, and VALU row sums throughout: d_k >= 64 has no free O^T rows), P from registers into
+// O^T += V^T P^T.  What differs is where K and V^T live: they pass through LDS one 32-key tile at a time, double-buffered — the tile
+// t + 1 is fetched into registers before the arithmetic of tile t, transposed into the other stage behind it, ONE workgroup barrier per
+// tile (a stage is overwritten one barrier after its last reader).  Plain loads and __syncthreads: no counted wait.
+//
+// Registers: a 32-query tile's O^T is DKP / 2 fp32 registers per lane, 128 at d_k = 256.  Up to DKP = 128 a wave owns a whole head for
+// its query tile (four query tiles per workgroup round, as in the resident kernel).  At DKP = 256 the d rows of a head are split over a
+// PAIR of waves (TDW = 4 tiles of 32 rows each): both compute the same score tile and the same softmax — identical bits, no exchange —
+// and each accumulates and stores its half of O^T; a workgroup round is two query tiles.  The score MFMAs are issued twice (16 + 8
+// MFMAs per wave and tile instead of 16 + 16 at one wave per SIMD), in exchange for two waves per SIMD and no spill.
+// Q: the lane's own query row in registers (QSTEPS x 16 bytes) up to 64 registers; beyond that (fp32 at DKP = 256: 128 registers) the
+// fragment is re-read from global memory in the score loop — every key tile touches the same 32 rows, L2-resident; the fp32 MFMA step
+// (four 32x32x2 instructions) covers it.
+// ---------------------------------------------------------------------------------------------------------------
+template <int DT, int DKP>
+__global__ __launch_bounds__(256) void cross_attn_stream_kernel(const typename Elem<DT>::type* __restrict__ qkv,
+                                                                typename Elem<DT>::type* __restrict__ out, int B, int N, int C, int DK,
+                                                                int NP, float scale_l2e, int xq) {
+    using E = Elem<DT>;
+    using T = typename E::type;
+    constexpr int VEC = E::VEC, EB = E::BYTES;
+    constexpr int KSTEP = 2 * VEC, QSTEPS = DKP / KSTEP, TD = DKP / 32, PSTEPS = 32 / KSTEP;
+    constexpr int TDW = TD < 4 ? TD : 4;           // 32-row d tiles of O^T per wave
+    constexpr int DSPLIT = TD / TDW;               // waves sharing a query tile (1 or 2)
+    constexpr int QW = 4 / DSPLIT;                 // query tiles per workgroup round
+    constexpr bool QGLOBAL = QSTEPS > 16;          // query fragments re-read from global memory instead of held in registers
+    constexpr int DEFER = DT == ICAF_F32 ? 0 : 6;  // as AttnCore: p <= 2^6 between rescales
+    constexpr int KS = DKP * EB + 16;              // K row stride (bytes), odd multiple of 16
+    constexpr int VS = 32 * EB + 16;               // V^T row stride (bytes): 32 keys, odd multiple of 16
+    constexpr int STAGE = 32 * KS + DKP * VS;
+    constexpr int NVK = DKP / VEC;                 // 16-byte vectors per K / V row
+    constexpr int G = EB == 2 ? 4 : 1;             // keys per staging item (16-bit: four, transposed with 8-byte stores as the resident kernel does)
+    constexpr int ITEMS = (32 / G) * NVK;
+    constexpr int NITEM = (ITEMS + 255) / 256;     // staging items per thread
+    static_assert(DKP % 32 == 0 && TD % TDW == 0 && (DSPLIT == 1 || DSPLIT == 2), "d split");
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+
+    const int tid = threadIdx.x, lane = tid & 63, l31 = lane & 31, hi = lane >> 5;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    int h, qx, qsplit, grp;                        // placement: as cross_attn_kernel
+    if (xq > 0) {
+        qsplit = xq;
+        const int heads = C / DK, per = qsplit * heads;
+        const int bid = blockIdx.x, xcd = bid & 7, idx = bid >> 3;
+        const int gi = idx / per, rem = idx - gi * per;
+        grp = gi * 8 + xcd;
+        h = rem / qsplit;
+        qx = rem - h * qsplit;
+    } else {
+        h = blockIdx.y; qx = blockIdx.x; qsplit = (int)gridDim.x; grp = blockIdx.z;
+    }
+    const int dir = grp / B, b = grp - dir * B;
+    const long long row3 = 3LL * C;
+    const T* kvbase = qkv + ((long long)(dir * B + b) * N) * row3 + (long long)h * DK;
+    const T* qbase = qkv + ((long long)((1 - dir) * B + b) * N) * row3 + (long long)h * DK;
+
+    // ---- staging of key tile c: global -> registers, registers -> LDS stage (K row-major, V^T with the keys permuted as vt_phys) ----
+    u32x4 kq[NITEM][G], vq[NITEM][G];
+    auto stage_load = [&](int c) {
+#pragma unroll
+        for (int it = 0; it < NITEM; ++it) {
+            const int idx = tid + it * 256;
+            const int kg = idx / NVK, v = idx - kg * NVK;
+#pragma unroll
+            for (int i = 0; i < G; ++i) {
+                const int key = c * 32 + kg * G + i;
+                kq[it][i] = u32x4{0u, 0u, 0u, 0u};
+                vq[it][i] = u32x4{0u, 0u, 0u, 0u};
+                if (idx < ITEMS && key < N && v * VEC < DK) {
+                    kq[it][i] = *(const u32x4*)(kvbase + (long long)key * row3 + C + v * VEC);
+                    vq[it][i] = *(const u32x4*)(kvbase + (long long)key * row3 + 2 * C + v * VEC);
+                }
+            }
+        }
+    };
+    auto stage_store = [&](unsigned char* st) {
+        unsigned char* Ks = st;
+        unsigned char* Vt = st + 32 * KS;
+#pragma unroll
+        for (int it = 0; it < NITEM; ++it) {
+            const int idx = tid + it * 256;
+            if (idx >= ITEMS) continue;
+            const int kg = idx / NVK, v = idx - kg * NVK, key0 = kg * G;          // key0: tile-local
+#pragma unroll
+            for (int i = 0; i < G; ++i) *(u32x4*)(Ks + (key0 + i) * KS + v * 16) = kq[it][i];
+            const int pk = vt_phys<DT>(key0);
+            if constexpr (EB == 2) {
+#pragma unroll
+                for (int j = 0; j < 8; ++j) {                                      // d row v * 8 + j: element j of each of the four keys' vectors
+                    u32x2 w;
+                    if (j & 1) {
+                        w[0] = (vq[it][0][j >> 1] >> 16) | (vq[it][1][j >> 1] & 0xffff0000u);
+                        w[1] = (vq[it][2][j >> 1] >> 16) | (vq[it][3][j >> 1] & 0xffff0000u);
+                    } else {
+                        w[0] = (vq[it][0][j >> 1] & 0xffffu) | (vq[it][1][j >> 1] << 16);
+                        w[1] = (vq[it][2][j >> 1] & 0xffffu) | (vq[it][3][j >> 1] << 16);
+                    }
+                    *(u32x2*)(Vt + (v * 8 + j) * VS + pk * 2) = w;
+                }
+            } else {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) *(unsigned int*)(Vt + (v * 4 + j) * VS + pk * 4) = vq[it][0][j];
+            }
+        }
+    };
+
+    const int nkt = NP >> 5;                       // key tiles = query tiles
+    const int qslot = wave / DSPLIT, dpart = wave - qslot * DSPLIT;
+    const int ngroups = (nkt + QW - 1) / QW;
+    const float c = scale_l2e;
+    const float defer = DEFER ? (float)DEFER / c : 0.0f;
+    for (int g = qx; g < ngroups; g += qsplit) {
+        const int qt = g * QW + qslot;
+        const bool active = qt < nkt;              // (wave-uniform; an idle wave still stages and meets the barriers)
+        const int q = qt * 32 + l31;
+        const bool qok = active && q < N;
+        u32x4 qf[QGLOBAL ? 1 : QSTEPS];
+        if constexpr (!QGLOBAL) {
+#pragma unroll
+            for (int st = 0; st < QSTEPS; ++st) {
+                const int off = st * KSTEP + hi * VEC;
+                u32x4 v = {0u, 0u, 0u, 0u};
+                if (qok && off < DK) v = *(const u32x4*)(qbase + (long long)q * row3 + off);
+                qf[st] = v;
+            }
+        }
+        f32x16 acc[TDW];
+#pragma unroll
+        for (int t = 0; t < TDW; ++t)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[t][r] = 0.0f;
+        float m = -INFINITY, l = 0.0f;
+
+        stage_load(0);
+        stage_store(smem);
+        __syncthreads();
+        for (int kt = 0; kt < nkt; ++kt) {
+            const bool more = kt + 1 < nkt;
+            if (more) stage_load(kt + 1);
+            if (active) {
+                const unsigned char* Ks = smem + (kt & 1) * STAGE;
+                const unsigned char* Vt = Ks + 32 * KS;
+                const unsigned char* krow = Ks + l31 * KS + hi * 16;
+                f32x16 s;
+#pragma unroll
+                for (int r = 0; r < 16; ++r) s[r] = 0.0f;
+#pragma unroll
+                for (int st = 0; st < QSTEPS; ++st) {
+                    const u32x4 kf = *(const u32x4*)(krow + st * 32);
+                    if constexpr (QGLOBAL) {
+                        const int off = st * KSTEP + hi * VEC;
+                        u32x4 v = {0u, 0u, 0u, 0u};
+                        if (qok && off < DK) v = *(const u32x4*)(qbase + (long long)q * row3 + off);
+                        mma_step<DT>(s, kf, v);
+                    } else {
+                        mma_step<DT>(s, kf, qf[st]);
+                    }
+                }
+                // softmax of the tile: AttnCore's statements (attn_core.h) for the instantiations without free O^T rows
+                if (kt == nkt - 1 && (nkt << 5) != N) {                  // only the last key tile can hold padding keys
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) {
+                        const int key = kt * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi;
+                        s[r] = key < N ? s[r] : -INFINITY;
+                    }
+                }
+                float tmax = fmaxf(s[0], s[1]);
+#pragma unroll
+                for (int r = 2; r < 16; ++r) tmax = fmaxf(tmax, s[r]);
+                tmax = xhalf_max(tmax);
+                if (__any(tmax > m + defer)) {
+                    const float m_new = fmaxf(m, tmax);
+                    const float alpha = __builtin_amdgcn_exp2f((m - m_new) * c);
+                    l *= alpha;
+#pragma unroll
+                    for (int t = 0; t < TDW; ++t)
+#pragma unroll
+                        for (int r = 0; r < 16; ++r) acc[t][r] *= alpha;
+                    m = m_new;
+                }
+                const float mc = m * c;
+                float psum = 0.0f;
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const float pv = __builtin_amdgcn_exp2f(__builtin_fmaf(s[r], c, -mc));
+                    s[r] = pv;
+                    psum += pv;
+                }
+                l += psum;
+#pragma unroll
+                for (int st = 0; st < PSTEPS; ++st) {
+                    const u32x4 pf = attn_pack_p<DT>(s, st);
+#pragma unroll
+                    for (int td = 0; td < TDW; ++td) {
+                        const u32x4 vf = *(const u32x4*)(Vt + ((dpart * TDW + td) * 32 + l31) * VS + (hi * VEC + st * KSTEP) * EB);
+                        mma_step<DT>(acc[td], vf, pf);
+                    }
+                }
+            }
+            if (more) stage_store(smem + ((kt + 1) & 1) * STAGE);
+            __syncthreads();
+        }
+        const float lsum = l + __shfl_xor(l, 32);
+        const float inv = 1.0f / lsum;
+        if (qok) {
+            T* orow = out + ((long long)(dir * B + b) * N + q) * C + (long long)h * DK;
+#pragma unroll
+            for (int td = 0; td < TDW; ++td)
+#pragma unroll
+                for (int g4 = 0; g4 < 4; ++g4) {
+                    const int d0 = (dpart * TDW + td) * 32 + 8 * g4 + 4 * hi;
+                    if (d0 < DK) {
+                        const float v0 = acc[td][4 * g4] * inv, v1 = acc[td][4 * g4 + 1] * inv, v2 = acc[td][4 * g4 + 2] * inv,
+                                    v3 = acc[td][4 * g4 + 3] * inv;
+                        if constexpr (EB == 4) {
+                            *(f32x4*)(orow + d0) = f32x4{v0, v1, v2, v3};
+                        } else if constexpr (DT == ICAF_BF16) {
+                            u32x2 pk;
+                            pk[0] = pack2_bf16(v0, v1);
+                            pk[1] = pack2_bf16(v2, v3);
+                            *(u32x2*)(orow + d0) = pk;
+                        } else {
+                            u32x2 pk;
+                            pk[0] = pack2_f16(v0, v1);
+                            pk[1] = pack2_f16(v2, v3);
+                            *(u32x2*)(orow + d0) = pk;
+                        }
+                    }
+                }
+        }
+    }
+}
+
 // The launch choice of icaf_cross_attention — padded head dimension, query splits per head, XCD remap — made in ONE place for the launch
 // and for icaf_cross_attention_config (tests read it back there; the probe knob attn_qsplit is part of the choice).
-struct AttnCfg { int dk, dkp, nqt, qsplit, remap; };
+struct AttnCfg { int dk, dkp, nqt, qsplit, remap, form; size_t lds; };
+
+// LDS bytes of the resident form (cross_attn_kernel): K rows + V^T rows (+ the ones row where the instantiation has free O^T rows)
+static size_t attn_resident_lds(int dtype, int N, int dkp) {
+    const int eb = dtype == ICAF_F32 ? 4 : 2, NP = (N + 31) & ~31;
+    const bool ones = dtype != ICAF_F32 && (dkp % 32) == 16;       // AttnCore::FREE
+    return (size_t)NP * (dkp * eb + 16) + (size_t)(dkp + (ones ? 1 : 0)) * ((size_t)NP * eb + 16);
+}
+// LDS bytes of the streaming form (cross_attn_stream_kernel): two stages of a 32-key tile of K and V^T
+static size_t attn_stream_lds(int dtype, int dkp) {
+    const int eb = dtype == ICAF_F32 ? 4 : 2;
+    return 2 * ((size_t)32 * (dkp * eb + 16) + (size_t)dkp * (32 * eb + 16));
+}
 
 static int attn_select(int dtype, int B, int N, int C, int heads, AttnCfg& c) {
     if (dtype < ICAF_F32 || dtype > ICAF_F16) return fail(ICAF_ERR_ARG, "icaf_cross_attention: bad dtype %d", dtype);
@@ -473,18 +783,29 @@ static int attn_select(int dtype, int B, int N, int C, int heads, AttnCfg& c) {
     const int DK = C / heads, vec = dtype == ICAF_F32 ? 4 : 8;
     if (DK % vec) return fail(ICAF_ERR_UNSUPPORTED, "icaf_cross_attention: head dim %d must be a multiple of %d for this dtype", DK, vec);
     if (B < 1 || N < 1 || 2LL * B > 65535) return fail(ICAF_ERR_ARG, "icaf_cross_attention: bad B/N");
-    if (DK > 128) return fail(ICAF_ERR_UNSUPPORTED, "icaf_cross_attention: head dim %d > 128", DK);
+    if (DK > 256) return fail(ICAF_ERR_UNSUPPORTED, "icaf_cross_attention: head dim %d > 256", DK);
     c.dk = DK;
     c.dkp = DK <= 16 ? 16 : DK <= 32 ? 32 : DK <= 48 ? 48 : DK <= 64 ? 64 : DK <= 96 ? 96 : 128;
     const int NP = (N + 31) & ~31;
     const int nqt = NP / 32;
     c.nqt = nqt;
+    // Which form.  The resident kernel (K / V^T of a head in LDS for the workgroup's lifetime) wherever it is built: d_k <= 128 and at most
+    // 160 KiB.  Everything else — and, with the probe knob attn_stream, everything — streams key tiles through LDS (cross_attn_stream_kernel),
+    // built for head dimensions padded to 64 / 128 / 256 (d_k = 192 runs the 256 instance: zero columns of K, zero rows of V^T).
+    c.lds = DK <= 128 ? attn_resident_lds(dtype, N, c.dkp) : 0;
+    c.form = (DK > 128 || c.lds > 160 * 1024 || g_opt.attn_stream != 0) ? 1 : 0;
+    int qs_max = (nqt + 3) / 4;
+    if (c.form) {
+        c.dkp = DK <= 64 ? 64 : DK <= 128 ? 128 : 256;
+        c.lds = attn_stream_lds(dtype, c.dkp);
+        const int qw = c.dkp == 256 ? 2 : 4;                            // query tiles per workgroup round (the kernel's QW)
+        qs_max = (nqt + qw - 1) / qw;
+    }
     // Query splits per head: every split stages the head's K / V^T again (25 - 100 KB through scalar LDS transposition writes), so as FEW as
     // the chip needs: two workgroups per CU (512) must exist, beyond that one split — except at d_k <= 16 with many query tiles, where a wave
     // walking seven tiles alone is the longer pole (round 5, same box, batch 32: yolov5s P3 28.5 us with 4 splits, 25.5 with 2, 26.5 with 1;
     // yolov5l P3 44.3 -> 33.3 and P4 27.1 -> 22.1 with ONE split; P5 levels already ran one).  Small batches keep the splits: they are the
     // only parallelism there.
-    const int qs_max = (nqt + 3) / 4;
     int qsplit = (DK <= 16 && nqt > 8) ? 2 : 1;
     const long long wgs1 = (long long)2 * B * heads;                  // workgroups with one split
     if (wgs1 * qsplit < 512) qsplit = (int)((512 + wgs1 - 1) / wgs1);
@@ -497,6 +818,11 @@ static int attn_select(int dtype, int B, int N, int C, int heads, AttnCfg& c) {
     c.remap = (2 * B) % 8 == 0 && heads * DK == C;                  // whole (direction, image) groups per XCD
     return ICAF_OK;
 }
+
+// the streaming form's launch: defined behind every other launch of this file (its kernels are instantiated last)
+static int attn_stream_dispatch(int dtype, const void* qkv, void* out, int B, int N, int C, int heads, const AttnCfg& c, hipStream_t s);
+static int layernorm_wide_dispatch(const void* x, void* y, const float* g0, const float* b0, const float* g1, const float* b1, long long rpg, int C,
+                                   int groups, float eps, hipStream_t s);
 
 template <int DT, int DKP>
 static int launch_attn(const void* qkv, void* out, int B, int N, int C, int heads, const AttnCfg& c, hipStream_t s) {
@@ -662,7 +988,9 @@ extern "C" int icaf_layernorm(const void* x, void* y, const float* gamma0, const
     if (!x || !y || !gamma0 || !beta0) return fail(ICAF_ERR_ARG, "icaf_layernorm: null pointer");
     if (groups < 1 || groups > 2 || (groups == 2 && (!gamma1 || !beta1))) return fail(ICAF_ERR_ARG, "icaf_layernorm: bad groups");
     const int vec = dtype == ICAF_F32 ? 4 : 8;
-    if (C % vec || C > 64 * 4 * vec) return fail(ICAF_ERR_ARG, "icaf_layernorm: C=%d must be a multiple of %d and <= %d", C, vec, 64 * 4 * vec);
+    if (C % vec || C > 2048) return fail(ICAF_ERR_ARG, "icaf_layernorm: C=%d must be a multiple of %d and <= 2048", C, vec);
+    if (C > 64 * 4 * vec)        // fp32 rows wider than 1024: eight vectors per lane (layernorm_wide_kernel)
+        return layernorm_wide_dispatch(x, y, gamma0, beta0, gamma1 ? gamma1 : gamma0, beta1 ? beta1 : beta0, rows_per_group, C, groups, eps, S(s));
     DISPATCH_DT(dtype, run_layernorm, x, y, gamma0, beta0, gamma1 ? gamma1 : gamma0, beta1 ? beta1 : beta0, rows_per_group, C, groups, eps, S(s));
 }
 
@@ -670,6 +998,7 @@ extern "C" int icaf_cross_attention(const void* qkv, void* out, int dtype, int B
     if (!qkv || !out) return fail(ICAF_ERR_ARG, "icaf_cross_attention: null pointer");
     AttnCfg c;
     if (const int st = attn_select(dtype, B, N, C, heads, c)) return st;
+    if (c.form) return attn_stream_dispatch(dtype, qkv, out, B, N, C, heads, c, S(s));
     DISPATCH_DT(dtype, dispatch_attn, qkv, out, B, N, C, heads, c, S(s));
 }
 
@@ -690,3 +1019,54 @@ extern "C" int icaf_dmff_upsample_merge(const void* tokens, const void* fea_rgb,
     if (C % vec || ld_rgb % vec || ld_ir % vec || ldo % vec || ldo < 2 * C) return fail(ICAF_ERR_ARG, "icaf_dmff_upsample_merge: bad strides");
     DISPATCH_DT(dtype, run_upsample_merge, tokens, fea_rgb, ld_rgb, fea_ir, ld_ir, out, ldo, B, H, W, C, th, tw, S(s));
 }
+
+// ---- launches whose kernels are instantiated behind every older kernel of this file (tools/kernel_fingerprint.py compares assembly text) ----
+extern "C" int icaf_cross_attention_form(int dtype, int B, int N, int C, int heads, int* form) {
+    if (!form) return fail(ICAF_ERR_ARG, "icaf_cross_attention_form: null pointer");
+    AttnCfg c;
+    if (const int st = attn_select(dtype, B, N, C, heads, c)) return st;
+    *form = c.form;
+    return ICAF_OK;
+}
+
+namespace icaf {
+template <int DT, int DKP>
+static int launch_attn_stream(const void* qkv, void* out, int B, int N, int C, int heads, const AttnCfg& c, hipStream_t s) {
+    using T = typename Elem<DT>::type;
+    const int NP = (N + 31) & ~31;
+    const size_t lds = c.lds;
+    if (lds > 160 * 1024) return fail(ICAF_ERR_UNSUPPORTED, "icaf_cross_attention: %zu bytes of LDS needed by the streaming form exceed 160 KiB", lds);
+    static std::atomic<bool> attr_set[ICAF_MAX_DEVICES];          // per instantiation and per device
+    int dev = 0;
+    ICAF_HIP(hipGetDevice(&dev));
+    if (lds > 64 * 1024 && dev >= 0 && dev < ICAF_MAX_DEVICES && !attr_set[dev]) {
+        ICAF_HIP(hipFuncSetAttribute((const void*)cross_attn_stream_kernel<DT, DKP>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        attr_set[dev] = true;
+    }
+    const float scale_l2e = (float)((1.0 / sqrt((double)c.dk)) * 1.4426950408889634);
+    dim3 grid((unsigned)c.qsplit, (unsigned)heads, (unsigned)(2 * B));
+    if (c.remap) grid = dim3((unsigned)(c.qsplit * heads * 2 * B), 1u, 1u);
+    hipLaunchKernelGGL((cross_attn_stream_kernel<DT, DKP>), grid, dim3(256), lds, s, (const T*)qkv, (T*)out, B, N, C, c.dk, NP, scale_l2e,
+                       c.remap ? c.qsplit : 0);
+    ICAF_LAUNCH_CHECK();
+    return ICAF_OK;
+}
+template <int DT>
+static int dispatch_attn_stream(const void* qkv, void* out, int B, int N, int C, int heads, const AttnCfg& c, hipStream_t s) {
+    switch (c.dkp) {
+        case 64: return launch_attn_stream<DT, 64>(qkv, out, B, N, C, heads, c, s);
+        case 128: return launch_attn_stream<DT, 128>(qkv, out, B, N, C, heads, c, s);
+        default: return launch_attn_stream<DT, 256>(qkv, out, B, N, C, heads, c, s);
+    }
+}
+static int attn_stream_dispatch(int dtype, const void* qkv, void* out, int B, int N, int C, int heads, const AttnCfg& c, hipStream_t s) {
+    DISPATCH_DT(dtype, dispatch_attn_stream, qkv, out, B, N, C, heads, c, s);
+}
+static int layernorm_wide_dispatch(const void* x, void* y, const float* g0, const float* b0, const float* g1, const float* b1, long long rpg, int C,
+                                   int groups, float eps, hipStream_t s) {
+    const long long rows = rpg * groups;
+    layernorm_wide_kernel<ICAF_F32><<<dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s>>>((const float*)x, (float*)y, g0, b0, g1, b1, rpg, C, groups, eps);
+    ICAF_LAUNCH_CHECK();
+    return ICAF_OK;
+}
+}  // namespace icaf

@@ -537,8 +537,9 @@ static int launch_act(const ConvP& q, dim3 grid, int pipe, hipStream_t s) {
     }
 }
 
-// RELU: the root-level selector of ICAF_ACT_RELU — why it is a parameter of its own: conv_common.h, "Instantiation order"
-template <int DT, int ODT, int BM, int BN, int WM, int WN, bool RELU = false>
+// RELU: the root-level selector of ICAF_ACT_RELU (1) and of ReLU with the residual in front, res_mode = 1 (2) — why it is a parameter of
+// its own: conv_common.h, "Instantiation order"
+template <int DT, int ODT, int BM, int BN, int WM, int WN, int RELU = 0>
 static int launch_cfg(const ConvP& p, int groups, int pipe, hipStream_t s) {
     ConvP q = p;
     q.mtiles = (p.M + BM - 1) / BM;
@@ -548,27 +549,29 @@ static int launch_cfg(const ConvP& p, int groups, int pipe, hipStream_t s) {
         q.nchunks = (p.K + bk - 1) / bk;
     }
     dim3 grid((unsigned)(q.mtiles * q.ntiles), 1, (unsigned)groups);
-    if constexpr (RELU) return launch_act<DT, ODT, BM, BN, WM, WN, ICAF_ACT_RELU>(q, grid, pipe, s);
+    if constexpr (RELU == 2) return launch_act<DT, ODT, BM, BN, WM, WN, ACT_RELU_RES>(q, grid, pipe, s);
+    if constexpr (RELU == 1) return launch_act<DT, ODT, BM, BN, WM, WN, ICAF_ACT_RELU>(q, grid, pipe, s);
     if (p.act == ICAF_ACT_SILU) return launch_act<DT, ODT, BM, BN, WM, WN, ICAF_ACT_SILU>(q, grid, pipe, s);
     if (p.act == ICAF_ACT_GELU) return launch_act<DT, ODT, BM, BN, WM, WN, ICAF_ACT_GELU>(q, grid, pipe, s);
     return launch_act<DT, ODT, BM, BN, WM, WN, ICAF_ACT_NONE>(q, grid, pipe, s);
 }
 
 // 8-wavefront tiles: pipeline 2 only
-template <int DT, int ODT, int BM, int BN, int WM, int WN, bool RELU = false>
+template <int DT, int ODT, int BM, int BN, int WM, int WN, int RELU = 0>
 static int launch_big(const ConvP& p, int groups, hipStream_t s) {
     ConvP q = p;
     q.mtiles = (p.M + BM - 1) / BM;
     q.ntiles = (p.Cout + BN - 1) / BN;
     q.nchunks = (p.K + 63) / 64;                  // 128-byte slices of a 16-bit type
     dim3 grid((unsigned)(q.mtiles * q.ntiles), 1, (unsigned)groups);
-    if constexpr (RELU) return launch_dma<DT, ODT, BM, BN, WM, WN, ICAF_ACT_RELU, 128, 2>(q, grid, s);
+    if constexpr (RELU == 2) return launch_dma<DT, ODT, BM, BN, WM, WN, ACT_RELU_RES, 128, 2>(q, grid, s);
+    if constexpr (RELU == 1) return launch_dma<DT, ODT, BM, BN, WM, WN, ICAF_ACT_RELU, 128, 2>(q, grid, s);
     if (p.act == ICAF_ACT_SILU) return launch_dma<DT, ODT, BM, BN, WM, WN, ICAF_ACT_SILU, 128, 2>(q, grid, s);
     if (p.act == ICAF_ACT_GELU) return launch_dma<DT, ODT, BM, BN, WM, WN, ICAF_ACT_GELU, 128, 2>(q, grid, s);
     return launch_dma<DT, ODT, BM, BN, WM, WN, ICAF_ACT_NONE, 128, 2>(q, grid, s);
 }
 
-template <int DT, int ODT, bool RELU = false>
+template <int DT, int ODT, int RELU = 0>
 static int launch_tile(const ConvP& p, int groups, int cfg, hipStream_t s) {
     const int pipe = cfg / 10;
     constexpr bool f32 = DT == ICAF_F32 || ODT == ICAF_F32;
@@ -594,10 +597,19 @@ static int launch_igemm(const icaf_conv_args* a, const ConvP& p, int id, hipStre
         return launch_tile<ICAF_F32, ICAF_F32>(p, a->groups, id, s);
     }
     if (a->dtype == ICAF_BF16)
-        return a->out_dtype == ICAF_F32 ? launch_tile<ICAF_BF16, ICAF_F32, true>(p, a->groups, id, s) : launch_tile<ICAF_BF16, ICAF_BF16, true>(p, a->groups, id, s);
+        return a->out_dtype == ICAF_F32 ? launch_tile<ICAF_BF16, ICAF_F32, 1>(p, a->groups, id, s) : launch_tile<ICAF_BF16, ICAF_BF16, 1>(p, a->groups, id, s);
     if (a->dtype == ICAF_F16)
-        return a->out_dtype == ICAF_F32 ? launch_tile<ICAF_F16, ICAF_F32, true>(p, a->groups, id, s) : launch_tile<ICAF_F16, ICAF_F16, true>(p, a->groups, id, s);
-    return launch_tile<ICAF_F32, ICAF_F32, true>(p, a->groups, id, s);
+        return a->out_dtype == ICAF_F32 ? launch_tile<ICAF_F16, ICAF_F32, 1>(p, a->groups, id, s) : launch_tile<ICAF_F16, ICAF_F16, 1>(p, a->groups, id, s);
+    return launch_tile<ICAF_F32, ICAF_F32, 1>(p, a->groups, id, s);
+}
+// res_mode = 1 (validate: ReLU, a residual, out_dtype == dtype, no pre / chain): named behind everything else, so instantiated last
+static int launch_igemm_res(const icaf_conv_args* a, const ConvP& p, int id, hipStream_t s) {
+    if (a->dtype == ICAF_BF16) return launch_tile<ICAF_BF16, ICAF_BF16, 2>(p, a->groups, id, s);
+    if (a->dtype == ICAF_F16) return launch_tile<ICAF_F16, ICAF_F16, 2>(p, a->groups, id, s);
+    return launch_tile<ICAF_F32, ICAF_F32, 2>(p, a->groups, id, s);
+}
+static int launch_igemm_any(const icaf_conv_args* a, const ConvP& p, int id, hipStream_t s) {
+    return a->res_mode ? launch_igemm_res(a, p, id, s) : launch_igemm(a, p, id, s);
 }
 
 // One row per kernel family: the launch configuration ids it owns (shape = id - base), its check (0, or an error code with the reason
@@ -623,7 +635,7 @@ static void igemm_name(const ConvFamily&, const icaf_conv_args* a, int id, char*
     snprintf(buf, len, "igemm%s_%s_%s_%s", kPipes[id / 10].tag, kTypeName[a->dtype], kTypeName[a->out_dtype], kTiles[id % 10 - 1].tag);
 }
 static const ConvFamily kFamilies[] = {
-    {1, 34, 0, igemm_built, igemm_check, launch_igemm, igemm_name, nullptr, nullptr},
+    {1, 34, 0, igemm_built, igemm_check, launch_igemm_any, igemm_name, nullptr, nullptr},
     {41, 45, 40, whole_range, ctile_conv_check, launch_ctile, shape_name, "ctile", ctile_tag},
     {51, 52, 50, whole_range, stream_check, launch_stream, shape_name, "igemm_stream", stream_tag},
     {61, 66, 60, whole_range, wreg_check, launch_wreg, shape_name, "igemm_wreg", wreg_tag},
@@ -687,6 +699,7 @@ static int validate(const icaf_conv_args* a) {
     const int ka = a->dtype == ICAF_F32 ? 32 : 64;
     if (a->Kp % ka || a->Kp < a->kh * a->kw * a->Cin) return fail(ICAF_ERR_ARG, "icaf_conv2d: Kp=%d must be a multiple of %d covering K=%d", a->Kp, ka, a->kh * a->kw * a->Cin);
     if (a->act < 0 || a->act > ICAF_ACT_RELU) return fail(ICAF_ERR_ARG, "icaf_conv2d: bad activation code %d", a->act);
+    if (a->res_mode < 0 || a->res_mode > 1) return fail(ICAF_ERR_ARG, "icaf_conv2d: res_mode must be 0 (residual behind the activation) or 1 (in front of it), got %d", a->res_mode);
     if (a->ldy < a->Cout) return fail(ICAF_ERR_ARG, "icaf_conv2d: ldy < Cout");
     if (a->res && a->ldr < a->Cout) return fail(ICAF_ERR_ARG, "icaf_conv2d: ldr < Cout");
     if ((long long)a->B * a->Ho * a->Wo > 0x7fffffffLL) return fail(ICAF_ERR_ARG, "icaf_conv2d: too many output pixels");
@@ -744,6 +757,11 @@ int conv_prepare(const icaf_conv_args* a, ConvP& p) {
 static int resolve(const icaf_conv_args* a, ConvP& p, const ConvFamily*& f, int& shape) {
     int st = conv_prepare(a, p);
     if (st) return st;
+    // res_mode = 1, y = relu(A.W + bias + res), exists in exactly one form (icaf.h); which families carry it: their own checks
+    if (a->res_mode == 1 && (!a->res || a->act != ICAF_ACT_RELU || a->alpha_acc[0] != 1.0f || a->alpha_acc[1] != 1.0f || a->alpha_res[0] != 1.0f ||
+                             a->alpha_res[1] != 1.0f || a->pre || a->w2 || a->x2 || a->out_dtype != a->dtype))
+        return fail(ICAF_ERR_UNSUPPORTED, "icaf_conv2d: res_mode = 1 needs a residual, ACT_RELU, alpha_acc = alpha_res = 1, no pre term, no chained layer "
+                                          "and out_dtype == dtype");
     const int id = pick_tile(a, p);
     if (a->x2 && id != 81 && id != 82) return fail(ICAF_ERR_UNSUPPORTED, "icaf_conv2d: x2 (C3 tail) is built for launch configurations 81 / 82 only (tile %d)", id);
     f = family_of(id);
@@ -794,6 +812,7 @@ extern "C" int icaf_bottleneck(const icaf_bneck_args* b, icaf_stream_t s) {
     if (b->Kp1 * eb != 128) return fail(ICAF_ERR_ARG, "icaf_bottleneck: the packed 1x1 weights must have 128-byte rows (Kp1 = %d)", b->Kp1);
     if (a->pre) return fail(ICAF_ERR_ARG, "icaf_bottleneck: no pre-activation term");
     if (a->x2) return fail(ICAF_ERR_ARG, "icaf_bottleneck: conv.x2 must be NULL (the block's cv2 half is icaf_bneck_args.x2)");
+    if (a->res_mode) return fail(ICAF_ERR_UNSUPPORTED, "icaf_bottleneck: res_mode = 1 is a form of icaf_conv2d only");
     if (a->x == a->y) return fail(ICAF_ERR_ARG, "icaf_bottleneck: in-place operation is not possible (neighbouring patches read x)");
     ConvP p;
     fill(a, p);

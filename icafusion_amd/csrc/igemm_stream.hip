@@ -72,6 +72,13 @@ struct StoreEpi {
                 float v[4];
 #pragma unroll
                 for (int j = 0; j < 4; ++j) v[j] = acc[b][4 * qd + j] + bq[qd][j] + pv[j];
+                if constexpr (ACT == ACT_RELU_RES) {       // res_mode = 1: the residual joins the fp32 sum in front of the ReLU (conv_common.h)
+                    const int m = m0 + ml;
+                    float rq[4];
+                    load_res_quad<DT>(rg, m < M ? m : -1, ldr, n0 + nl, Cout, 1, rq);      // (stream_check: the residual takes 16-byte vectors)
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) v[j] += rq[j];
+                }
                 apply_act4<ACT, DT>(v, v);
 #pragma unroll
                 for (int j = 0; j < 4; ++j) v[j] *= alpha_acc;
@@ -92,7 +99,7 @@ struct StoreEpi {
             const int m = m0 + row, n = n0 + cv * E::VEC;
             u32x4 sv = *(const u32x4*)(stg + row * SO + cv * 16);
             if (m < M && n < Cout) {
-                if (rg) {                              // the shared epilogue's arithmetic (conv_common.h): staged value + alpha_res * residual
+                if (rg && ACT != ACT_RELU_RES) {       // the shared epilogue's arithmetic (conv_common.h): staged value + alpha_res * residual
                     float v[E::VEC], r[E::VEC];
                     unpack16<DT>(sv, v);
                     unpack16<DT>(*(const u32x4*)(rg + (long long)m * ldr + n), r);
@@ -178,10 +185,12 @@ static int launch_stream_cfg(const ConvP& p, int groups, hipStream_t s) {
     return go(igemm_stream_kernel<DT, BN, ACT, 2>);
 }
 
-// RELU: the root-level selector of ICAF_ACT_RELU — why it is a parameter of its own: conv_common.h, "Instantiation order"
-template <int DT, int BN, bool RELU = false>
+// RELU (an int, not a flag): the root-level selector, 0 = by p.act, 1 = ICAF_ACT_RELU, 2 = ReLU with the residual in front (res_mode = 1) — why
+// it is a parameter of its own: conv_common.h, "Instantiation order"
+template <int DT, int BN, int RELU = 0>
 static int launch_stream_act(const ConvP& p, int groups, hipStream_t s) {
-    if constexpr (RELU) return launch_stream_cfg<DT, BN, ICAF_ACT_RELU>(p, groups, s);
+    if constexpr (RELU == 2) return launch_stream_cfg<DT, BN, ACT_RELU_RES>(p, groups, s);
+    if constexpr (RELU == 1) return launch_stream_cfg<DT, BN, ICAF_ACT_RELU>(p, groups, s);
     if (p.act == ICAF_ACT_SILU) return launch_stream_cfg<DT, BN, ICAF_ACT_SILU>(p, groups, s);
     if (p.act == ICAF_ACT_GELU) return launch_stream_cfg<DT, BN, ICAF_ACT_GELU>(p, groups, s);
     return launch_stream_cfg<DT, BN, ICAF_ACT_NONE>(p, groups, s);
@@ -192,8 +201,12 @@ int launch_stream(const icaf_conv_args* a, const ConvP& p, int shape, hipStream_
         if (a->dtype == ICAF_BF16) return shape == 1 ? launch_stream_act<ICAF_BF16, 128>(p, a->groups, s) : launch_stream_act<ICAF_BF16, 64>(p, a->groups, s);
         return shape == 1 ? launch_stream_act<ICAF_F16, 128>(p, a->groups, s) : launch_stream_act<ICAF_F16, 64>(p, a->groups, s);
     }
-    if (a->dtype == ICAF_BF16) return shape == 1 ? launch_stream_act<ICAF_BF16, 128, true>(p, a->groups, s) : launch_stream_act<ICAF_BF16, 64, true>(p, a->groups, s);
-    return shape == 1 ? launch_stream_act<ICAF_F16, 128, true>(p, a->groups, s) : launch_stream_act<ICAF_F16, 64, true>(p, a->groups, s);
+    if (!a->res_mode) {
+        if (a->dtype == ICAF_BF16) return shape == 1 ? launch_stream_act<ICAF_BF16, 128, 1>(p, a->groups, s) : launch_stream_act<ICAF_BF16, 64, 1>(p, a->groups, s);
+        return shape == 1 ? launch_stream_act<ICAF_F16, 128, 1>(p, a->groups, s) : launch_stream_act<ICAF_F16, 64, 1>(p, a->groups, s);
+    }
+    if (a->dtype == ICAF_BF16) return shape == 1 ? launch_stream_act<ICAF_BF16, 128, 2>(p, a->groups, s) : launch_stream_act<ICAF_BF16, 64, 2>(p, a->groups, s);
+    return shape == 1 ? launch_stream_act<ICAF_F16, 128, 2>(p, a->groups, s) : launch_stream_act<ICAF_F16, 64, 2>(p, a->groups, s);
 }
 
 }  // namespace icaf

@@ -263,10 +263,12 @@ static int launch_wreg_mode(const icaf_conv_args* a, const ConvP& p, int groups,
     return go(igemm_wreg_kernel<DT, NWV, ACT, 2, TN, BM>);
 }
 
-// RELU: the root-level selector of ICAF_ACT_RELU — why it is a parameter of its own: conv_common.h, "Instantiation order"
-template <int DT, int NWV, int TN = 1, int BM = 128, bool RELU = false>
+// RELU (an int, not a flag): the root-level selector, 0 = by p.act, 1 = ICAF_ACT_RELU, 2 = ReLU with the residual in front (res_mode = 1) — why
+// it is a parameter of its own: conv_common.h, "Instantiation order"
+template <int DT, int NWV, int TN = 1, int BM = 128, int RELU = 0>
 static int launch_wreg_act(const icaf_conv_args* a, const ConvP& p, int groups, hipStream_t s) {
-    if constexpr (RELU) return launch_wreg_mode<DT, NWV, ICAF_ACT_RELU, TN, BM>(a, p, groups, s);      // every form, 128x512 included
+    if constexpr (RELU == 2) return launch_wreg_mode<DT, NWV, ACT_RELU_RES, TN, BM>(a, p, groups, s);       // res_mode = 1: every form as well
+    if constexpr (RELU == 1) return launch_wreg_mode<DT, NWV, ICAF_ACT_RELU, TN, BM>(a, p, groups, s);      // every form, 128x512 included
     if (p.act == ICAF_ACT_SILU) return launch_wreg_mode<DT, NWV, ICAF_ACT_SILU, TN, BM>(a, p, groups, s);
     if constexpr (NWV == 4) { if (p.act == ICAF_ACT_GELU) return launch_wreg_mode<DT, NWV, ICAF_ACT_GELU, TN, BM>(a, p, groups, s); }
     else if (p.act == ICAF_ACT_GELU && TN == 2) return fail(ICAF_ERR_UNSUPPORTED, "igemm_wreg 128x512: built for SiLU / ReLU / linear layers");
@@ -274,7 +276,7 @@ static int launch_wreg_act(const icaf_conv_args* a, const ConvP& p, int groups, 
     return launch_wreg_mode<DT, NWV, ICAF_ACT_NONE, TN, BM>(a, p, groups, s);
 }
 
-template <int DT, bool RELU = false>
+template <int DT, int RELU = 0>
 static int launch_wreg_shape(const icaf_conv_args* a, const ConvP& p, int shape, hipStream_t s) {
     switch (shape) {
         case 1: return launch_wreg_act<DT, 4, 1, 128, RELU>(a, p, a->groups, s);
@@ -288,7 +290,8 @@ static int launch_wreg_shape(const icaf_conv_args* a, const ConvP& p, int shape,
 
 int launch_wreg(const icaf_conv_args* a, const ConvP& p, int shape, hipStream_t s) {
     if (a->act != ICAF_ACT_RELU) return a->dtype == ICAF_BF16 ? launch_wreg_shape<ICAF_BF16>(a, p, shape, s) : launch_wreg_shape<ICAF_F16>(a, p, shape, s);
-    return a->dtype == ICAF_BF16 ? launch_wreg_shape<ICAF_BF16, true>(a, p, shape, s) : launch_wreg_shape<ICAF_F16, true>(a, p, shape, s);
+    if (!a->res_mode) return a->dtype == ICAF_BF16 ? launch_wreg_shape<ICAF_BF16, 1>(a, p, shape, s) : launch_wreg_shape<ICAF_F16, 1>(a, p, shape, s);
+    return a->dtype == ICAF_BF16 ? launch_wreg_shape<ICAF_BF16, 2>(a, p, shape, s) : launch_wreg_shape<ICAF_F16, 2>(a, p, shape, s);
 }
 
 }  // namespace icaf

@@ -405,6 +405,168 @@ class VGGblock(HipModule):
         return out
 
 
+def _fold_conv_bn(conv, bn):
+    """fp32 (weight, bias) of Conv2d + BatchNorm2d in eval mode — Conv.folded's arithmetic for a bare pair of torch modules."""
+    w = conv.weight.detach().float()
+    b = conv.bias.detach().float() if conv.bias is not None else torch.zeros(w.shape[0], device=w.device)
+    scale = bn.weight.detach().float() / torch.sqrt(bn.running_var.detach().float() + bn.eps)
+    return w * scale[:, None, None, None], (b - bn.running_mean.detach().float()) * scale + bn.bias.detach().float()
+
+
+def _pack_conv_bn(owner, plan, tag, pairs, cin_pad=None):
+    """(wp, kp, bp) of one (conv, bn) pair per stream in its launch form (ops.pack_streams), BatchNorm folded HERE, when the weights are
+    packed — the modules keep their BatchNorm, as the reference's fuse() leaves them (it only touches Conv).  Cached on `owner`."""
+    key = ("pack", plan.dtype, plan.device, tag, tuple(id(c) for c, _ in pairs), cin_pad)
+    return owner._cached(key, lambda: ops.pack_streams([_fold_conv_bn(c, b) for c, b in pairs], plan.dtype, cin_pad))
+
+
+class ResNetblock(HipModule):
+    """ResNet bottleneck (reference models/common.py:131-156): relu(bn1(conv1 1x1)) -> relu(bn2(conv2 3x3 / stride)) -> bn3(conv3 1x1) +
+    shortcut(x) -> relu, the shortcut a 1x1 / stride convolution + BatchNorm where the shape changes and the identity otherwise.  On the
+    device: three ReLU implicit-GEMM launches (four with a shortcut convolution, which has no activation), BatchNorm folded when the
+    weights are packed, and the add + ReLU in conv3's epilogue with the residual IN FRONT of the activation (icaf.h: res_mode = 1)."""
+    expansion = 4
+
+    def __init__(self, c1, c2, stride=1):
+        super().__init__()
+        self.conv1 = nn.Conv2d(in_channels=c1, out_channels=c2, kernel_size=1, bias=False)
+        self.bn1 = nn.BatchNorm2d(c2)
+        self.conv2 = nn.Conv2d(in_channels=c2, out_channels=c2, kernel_size=3, stride=stride, padding=1, bias=False)
+        self.bn2 = nn.BatchNorm2d(c2)
+        self.conv3 = nn.Conv2d(in_channels=c2, out_channels=self.expansion * c2, kernel_size=1, bias=False)
+        self.bn3 = nn.BatchNorm2d(self.expansion * c2)
+        self.shortcut = nn.Sequential()
+        if stride != 1 or c1 != self.expansion * c2:
+            self.shortcut = nn.Sequential(nn.Conv2d(in_channels=c1, out_channels=self.expansion * c2, kernel_size=1, stride=stride, bias=False),
+                                          nn.BatchNorm2d(self.expansion * c2))
+
+    def _check(self):
+        k1, k2, k3 = self.conv1, self.conv2, self.conv3
+        ok = ((k1.kernel_size, k1.stride, _pair(k1.padding)) == ((1, 1), (1, 1), (0, 0)) and k2.kernel_size == (3, 3) and _pair(k2.padding) == (1, 1)
+              and k2.stride[0] == k2.stride[1] and (k3.kernel_size, k3.stride, _pair(k3.padding)) == ((1, 1), (1, 1), (0, 0))
+              and all(k.groups == 1 and k.dilation == (1, 1) for k in (k1, k2, k3))
+              and k1.out_channels == k2.in_channels and k2.out_channels == k3.in_channels)
+        sc = list(self.shortcut)
+        if sc:
+            ok = ok and (len(sc) == 2 and isinstance(sc[0], nn.Conv2d) and isinstance(sc[1], nn.BatchNorm2d) and sc[0].kernel_size == (1, 1)
+                         and _pair(sc[0].padding) == (0, 0) and sc[0].stride == k2.stride and sc[0].groups == 1
+                         and sc[0].in_channels == k1.in_channels and sc[0].out_channels == k3.out_channels)
+        else:
+            ok = ok and k2.stride == (1, 1) and k1.in_channels == k3.out_channels
+        if not ok:
+            raise NotImplementedError("ResNetblock: 1x1 -> 3x3 / stride -> 1x1 with a 1x1 / stride shortcut convolution or the identity")
+
+    def emit(self, plan, x, out=None, twin=None):
+        self._check()
+        paired = twin is not None
+        assert (x.dim() == 5) == paired
+        vec = ops.VEC[plan.dtype]
+        c1, c2, c3 = self.conv1.in_channels, self.conv1.out_channels, self.conv3.out_channels
+        s = self.conv2.stride[0]
+        if x.shape[-1] != c1:
+            raise ValueError(f"ResNetblock expects {c1} input channels, got {x.shape[-1]}")
+        if c1 % vec or c2 % vec:
+            raise NotImplementedError(f"channel counts {c1}, {c2} must be multiples of {vec} for dtype {plan.dtype}")
+        blocks = (self,) if twin is None else (self, twin)
+        pack = lambda tag, get: _pack_conv_bn(self, plan, (tag, id(twin)), [get(b) for b in blocks])     # noqa: E731
+        B, H, W = x.shape[-4:-1]
+        Ho, Wo = (H + 2 - 3) // s + 1, (W + 2 - 3) // s + 1
+        t1 = plan.act(B, H, W, c2, pair=paired)
+        wp, kp, bp = pack("conv1", lambda b: (b.conv1, b.bn1))
+        plan.add(ops.conv2d(x, wp, kp, bp, t1, 1, 1, 1, 1, 0, 0, c1, c2, ops.ACT_RELU, name="resnet_conv1x1"))
+        t2 = plan.act(B, Ho, Wo, c2, pair=paired)
+        wp, kp, bp = pack("conv2", lambda b: (b.conv2, b.bn2))
+        plan.add(ops.conv2d(t1, wp, kp, bp, t2, 3, 3, s, s, 1, 1, c2, c2, ops.ACT_RELU, name=f"resnet_conv3x3s{s}"))
+        res = x
+        if len(self.shortcut):
+            res = plan.act(B, Ho, Wo, c3, pair=paired)
+            wp, kp, bp = pack("shortcut", lambda b: (b.shortcut[0], b.shortcut[1]))
+            plan.add(ops.conv2d(x, wp, kp, bp, res, 1, 1, s, s, 0, 0, c1, c3, ops.ACT_NONE, name=f"resnet_shortcut1x1s{s}"))
+        if out is None:
+            out = plan.act(B, Ho, Wo, c3, pair=paired)
+        wp, kp, bp = pack("conv3", lambda b: (b.conv3, b.bn3))
+        plan.add(ops.conv2d(t2, wp, kp, bp, out, 1, 1, 1, 1, 0, 0, c2, c3, ops.ACT_RELU, res=res, res_pre_act=True, name="resnet_conv1x1+res"))
+        return out
+
+
+class ResNetlayer(HipModule):
+    """One yaml row of a ResNet50 stream (reference models/common.py:159-181; the reference's `blk` list is not registered, `layer` is the
+    whole state_dict surface).  is_first: Conv2d(7x7 / s2 / p3) + BatchNorm + ReLU + MaxPool2d(3, 2, 1) — on the device the staging kernel
+    (image -> NHWC, channels padded to one 16-byte vector), one ReLU implicit-GEMM launch walking the 49 taps (K = 49 x the padded
+    channels) and icaf_maxpool2d.  Otherwise num_blocks ResNetblocks, the first with `stride`."""
+    expansion = 4
+
+    def __init__(self, c1, c2, stride=1, is_first=False, num_blocks=1):
+        super().__init__()
+        self.is_first = is_first
+        if self.is_first:
+            self.layer = nn.Sequential(nn.Conv2d(in_channels=c1, out_channels=c2, kernel_size=7, stride=2, padding=3, bias=False),
+                                       nn.BatchNorm2d(c2), nn.ReLU(), nn.MaxPool2d(kernel_size=3, stride=2, padding=1))
+        else:
+            blk = [ResNetblock(c1, c2, stride)] + [ResNetblock(self.expansion * c2, c2, 1) for _ in range(num_blocks - 1)]
+            self.layer = nn.Sequential(*blk)
+
+    def out_shape(self, H, W):
+        """(C, H', W') of this row's output for an H x W input."""
+        if self.is_first:
+            k, pool = self.layer[0], self.layer[3]
+            (kh, kw), (sh, sw), (ph, pw) = k.kernel_size, k.stride, _pair(k.padding)
+            pk, ps, pp = (v if isinstance(v, int) else v[0] for v in (pool.kernel_size, pool.stride, pool.padding))
+            H, W = (H + 2 * ph - kh) // sh + 1, (W + 2 * pw - kw) // sw + 1
+            return k.out_channels, (H + 2 * pp - pk) // ps + 1, (W + 2 * pp - pk) // ps + 1
+        for b in self.layer:
+            s = b.conv2.stride[0]
+            H, W = (H + 2 - 3) // s + 1, (W + 2 - 3) // s + 1
+        return self.layer[-1].conv3.out_channels, H, W
+
+    def emit(self, plan, x, out=None, twin=None):
+        paired = twin is not None
+        if not self.is_first:
+            blocks = list(self.layer)
+            for j, b in enumerate(blocks):
+                if not isinstance(b, ResNetblock):
+                    raise NotImplementedError("ResNetlayer rows are ResNetblocks")
+                x = b.emit(plan, x, out=out if j == len(blocks) - 1 else None, twin=twin.layer[j] if paired else None)
+            return x
+        mods = list(self.layer)
+        if not (len(mods) == 4 and isinstance(mods[0], nn.Conv2d) and isinstance(mods[1], nn.BatchNorm2d) and isinstance(mods[2], nn.ReLU)
+                and isinstance(mods[3], nn.MaxPool2d) and mods[3].dilation in (1, (1, 1)) and not mods[3].ceil_mode
+                and mods[0].groups == 1 and mods[0].dilation == (1, 1)):
+            raise NotImplementedError("the first ResNetlayer is Conv2d + BatchNorm2d + ReLU + a plain MaxPool2d")
+        k, pool = mods[0], mods[3]
+        (kh, kw), (sh, sw), (ph, pw) = k.kernel_size, k.stride, _pair(k.padding)
+        pk, ps, pp = (v if isinstance(v, int) else v[0] for v in (pool.kernel_size, pool.stride, pool.padding))
+        vec = ops.VEC[plan.dtype]
+        c1, c2 = k.in_channels, k.out_channels
+        layers = (self,) if twin is None else (self, twin)
+        if isinstance(x, ImageIn):
+            assert x.pair == paired
+            B, _, H, W = x.shape
+            cpad = -(-c1 // vec) * vec
+            pre = plan.act(B, H, W, cpad, pair=paired)
+            plan.add(ops.preprocess_u8(x.t, pre, 0, x.c0, name="preprocess_u8_pad") if x.u8 else ops.preprocess(x.t, pre, 0, name="preprocess_pad"))
+            x, cin = pre, cpad
+        else:
+            assert (x.dim() == 5) == paired
+            if x.shape[-1] != c1 or c1 % vec:
+                raise ValueError(f"ResNetlayer stem expects {c1} input channels in whole {vec}-element vectors, got {x.shape[-1]}")
+            B, H, W = x.shape[-4:-1]
+            cin = c1
+        wp, kp, bp = _pack_conv_bn(self, plan, ("stem", id(twin)), [(l.layer[0], l.layer[1]) for l in layers], cin_pad=cin)
+        Hc, Wc = (H + 2 * ph - kh) // sh + 1, (W + 2 * pw - kw) // sw + 1
+        y = plan.act(B, Hc, Wc, c2, pair=paired)
+        plan.add(ops.conv2d(x, wp, kp, bp, y, kh, kw, sh, sw, ph, pw, cin, c2, ops.ACT_RELU, name=f"resnet_stem{kh}x{kw}s{sh}"))
+        Ho, Wo = (Hc + 2 * pp - pk) // ps + 1, (Wc + 2 * pp - pk) // ps + 1
+        if out is None:
+            out = plan.act(B, Ho, Wo, c2, pair=paired)
+        if paired and out.stride(0) != B * out.stride(1):      # the streams are channel slices of one buffer: one launch each
+            for g in range(2):
+                plan.add(ops.maxpool2d(y[g], out[g], pk, ps, pp, name="resnet_maxpool"))
+        else:
+            plan.add(ops.maxpool2d(y, out, pk, ps, pp, name="resnet_maxpool"))
+        return out
+
+
 class Bottleneck(HipModule):
     """1x1 -> 3x3 with optional identity shortcut (reference models/common.py:184-194); the shortcut add is the
     residual term of the second conv's epilogue (which may write in place over its own residual: every output

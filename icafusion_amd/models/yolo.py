@@ -21,11 +21,11 @@ import torch.nn as nn
 from .. import ops
 from ..engine import ImageIn, Plan, TtaPlan
 from .common import (C3, SPPF, Add, Bottleneck, Concat, Conv, Detect, HipModule, NiNfusion,  # noqa: F401
-                     TransformerFusionBlock, VGGblock, VirtualCat, emit_upsample)
+                     ResNetblock, ResNetlayer, TransformerFusionBlock, VGGblock, VirtualCat, emit_upsample)
 
 logger = logging.getLogger(__name__)
 _NAMESPACE = {"Conv": Conv, "C3": C3, "SPPF": SPPF, "Bottleneck": Bottleneck, "Concat": Concat, "Detect": Detect,
-              "TransformerFusionBlock": TransformerFusionBlock, "NiNfusion": NiNfusion, "Add": Add, "VGGblock": VGGblock, "nn": nn}
+              "TransformerFusionBlock": TransformerFusionBlock, "NiNfusion": NiNfusion, "Add": Add, "VGGblock": VGGblock, "ResNetlayer": ResNetlayer, "nn": nn}
 
 
 def make_divisible(x, divisor):
@@ -103,6 +103,8 @@ def parse_model(d, ch):
                 n = 1
         elif m is VGGblock:                                   # reference models/yolo_test.py:260-261: (num_convs, c1, c2) as written
             c2 = args[2]
+        elif m is ResNetlayer:                                # reference models/yolo_test.py:255-259: (c1, c2, stride, is_first, num_blocks) as
+            c2 = args[1] if args[3] is True else args[1] * 4  # written; the stem row keeps c2, every other row ends on expansion * c2
         elif m is Concat:
             c2 = sum(ch[x] for x in f)
         elif m is Detect:
@@ -164,7 +166,7 @@ def emit_any(m, plan, src, out=None, twin=None, lead=None):
     return m.emit(plan, src, out=out, **kw)
 
 
-PAIRABLE = (Conv, C3, SPPF, VGGblock)
+PAIRABLE = (Conv, C3, SPPF, VGGblock, ResNetlayer)
 
 
 def _same_structure(a, b):
@@ -183,7 +185,11 @@ def _same_structure(a, b):
     tail = lambda m: [(type(c), getattr(c, "kernel_size", None), getattr(c, "stride", None), getattr(c, "padding", None))      # noqa: E731
                       for v in m.modules() if isinstance(v, VGGblock) for s in v.vggblock for c in (s if isinstance(s, nn.Sequential) else [s])
                       if not isinstance(c, nn.Conv2d)]
-    return geo(a) == geo(b) and acts(a) == acts(b) and tail(a) == tail(b)
+    # a ResNetlayer's stem row: the same flag, and the same plain torch modules (BatchNorm eps, ReLU, pool window) behind the convolution
+    stem = lambda m: [(v.is_first,) + tuple((type(c), getattr(c, "eps", None), getattr(c, "kernel_size", None), getattr(c, "stride", None),  # noqa: E731
+                                             getattr(c, "padding", None)) for c in v.layer if v.is_first and not isinstance(c, nn.Conv2d))
+                      for v in m.modules() if isinstance(v, ResNetlayer)]
+    return geo(a) == geo(b) and acts(a) == acts(b) and tail(a) == tail(b) and stem(a) == stem(b)
 
 
 class Model(HipModule):
@@ -321,7 +327,8 @@ class Model(HipModule):
         return (tp.outputs if self.static_outputs else tp.outputs.clone()), None
 
     def fuse(self):
-        """Fold BatchNorm into the convs in place (reference models/yolo_test.py:182-190).  A VGGblock has none: nothing to fold."""
+        """Fold BatchNorm into the convs in place (reference models/yolo_test.py:182-190).  A VGGblock has none: nothing to fold.  A
+        ResNetlayer keeps its BatchNorms, as in the reference (its fuse() only touches Conv): they are folded when the weights are packed."""
         for m in self.model.modules():
             if type(m) is Conv and hasattr(m, "bn"):
                 with torch.no_grad():
@@ -359,6 +366,8 @@ class Model(HipModule):
                 pool = m.vggblock[-1]
                 k, s_, p = (v if isinstance(v, int) else v[0] for v in (pool.kernel_size, pool.stride, pool.padding))
                 cur = (m.convs()[-1].out_channels, (src[1] + 2 * p - k) // s_ + 1, (src[2] + 2 * p - k) // s_ + 1)
+            elif isinstance(m, ResNetlayer):            # 7x7 / s2 / p3 + 3 / 2 / 1 pool for the stem row, the blocks' 3x3 strides otherwise (floor)
+                cur = m.out_shape(src[1], src[2])
             elif isinstance(m, nn.Upsample):
                 s = int(m.scale_factor)
                 cur = (src[0], src[1] * s, src[2] * s)

@@ -156,9 +156,11 @@ def s2d_conv_weight(w4d):
 # launches
 # ------------------------------------------------------------------------------------------------------------
 def conv2d(x, w_packed, kp, bias, y, kh, kw, sh, sw, ph, pw, cin, cout, act, res=None, alpha_acc=1.0,
-           alpha_res=1.0, groups=1, group_strides=None, tile=0, name="conv2d", pre=None, chain=None, pre_nearest=False):
+           alpha_res=1.0, groups=1, group_strides=None, tile=0, name="conv2d", pre=None, chain=None, pre_nearest=False, res_pre_act=False):
     """Record an implicit-GEMM conv / linear.  x, y, res are acts; for groups=2 they are the group-0 views and
-    group_strides = dict(x=, w=, bias=, y=, res=) gives element strides to group 1."""
+    group_strides = dict(x=, w=, bias=, y=, res=) gives element strides to group 1.
+    res_pre_act: the residual is added IN FRONT of the activation, y = relu(conv(x) + bias + res) rounded once (icaf.h: res_mode = 1; a
+    ResNet bottleneck's conv3): ReLU layers with a residual, unit alphas, no pre term and no chained layer only — the library refuses the rest."""
     B, H, W, cx, ldx = _act_geom(x)
     By, Ho, Wo, cy, ldy = _act_geom(y)
     assert cx >= cin and cy >= cout and By == B
@@ -188,6 +190,7 @@ def conv2d(x, w_packed, kp, bias, y, kh, kw, sh, sw, ph, pw, cin, cout, act, res
     a.alpha_acc[0], a.alpha_acc[1] = float(aa[0]), float(aa[1])
     a.alpha_res[0], a.alpha_res[1] = float(ar[0]), float(ar[1])
     a.tile = tile
+    a.res_mode = int(bool(res_pre_act))
     if pre is not None:               # fp32 coarse map (B, h, w, >= cout) added, bilinearly resized, before the activation
         Bp, hp, wp_, cp, ldp = _act_geom(pre)
         assert pre.dtype == torch.float32 and Bp == B and cp >= cout and groups == 1
@@ -278,7 +281,7 @@ def cwide_shapes(kh, kw, sh, sw, ph, pw, cin, cout):
 
 def _conv_signature(a):
     return (a.B * a.Ho * a.Wo, a.Cout, a.Cin, a.kh, a.kw, a.sh, a.sw, a.H, a.W, a.ldx, a.ldy, a.groups, a.dtype,
-            a.out_dtype, a.act, bool(a.res), bool(a.pre) + a.pre_mode, a.Cout2 if a.w2 else 0, 2 if a.x2 else bool(a.chain_keep))
+            a.out_dtype, a.act, bool(a.res) + getattr(a, "res_mode", 0), bool(a.pre) + a.pre_mode, a.Cout2 if a.w2 else 0, 2 if a.x2 else bool(a.chain_keep))
 
 
 class _Layer:
@@ -306,8 +309,11 @@ def conv_candidates(a):
     launches only have the configurations that are built for them.  Ids the library builds and no rule offers: BUILT_NOT_OFFERED.
     Activations: igemm.hip, igemm_stream.hip and igemm_wreg.hip dispatch on all four codes (128 x 512 of igemm_wreg not on GELU); cstream.hip,
     cwide.hip, ctile.hip and every chained / pre-term launch are SiLU-only — `L.silu` below is the library's own check, so a ReLU layer
-    (VGGblock) is never offered an id of theirs."""
+    (VGGblock) is never offered an id of theirs.  res_mode = 1 (the residual in front of the ReLU, ResNetblock's conv3) exists on the
+    families that run ReLU, as a plain same-type ReLU layer with a residual; any other request has no configuration at all."""
     L = _Layer(a)
+    if getattr(a, "res_mode", 0) and not (a.res_mode == 1 and a.res and a.act == ACT_RELU and L.plain and a.out_dtype == a.dtype):
+        return []
     big1 = a.out_dtype != F32 and a.Cout > 64                              # the 128x128 tile: no fp32-output build, and 128x64 serves Cout <= 64
     if L.tail:                         # C3 tail (the chained cv3 reads [tile | x2]): cwide.hip's 8 x 16 / 8 x 8 forms only
         # Below ~200 k pixels per stream (the 40 x 40 maps of yolov5s at batch 32 / 64: one round of 8 x 16 tiles for the chip) only the 8 x 8
@@ -684,6 +690,24 @@ def cross_attention_config(dtype, B, N, Cc, heads):
     check(lib().icaf_cross_attention_config(dtype_code(dtype), B, N, Cc, heads, C.byref(dkp), C.byref(qs), C.byref(rm)),
           "icaf_cross_attention_config")
     return dkp.value, qs.value, rm.value
+
+
+def cross_attention_form(dtype, B, N, Cc, heads):
+    """0: icaf_cross_attention runs the resident kernel for this shape, 1: the key-streaming one (icaf.h), the probe knob included."""
+    form = C.c_int(-1)
+    check(lib().icaf_cross_attention_form(dtype_code(dtype), B, N, Cc, heads, C.byref(form)), "icaf_cross_attention_form")
+    return form.value
+
+
+@contextlib.contextmanager
+def attn_stream(on=True):
+    """Force icaf_cross_attention onto its key-streaming form inside a `with` (icaf.h: icaf_cross_attention_form): an A/B knob of the
+    library for timings and tests.  Like letterbox_direct it is set by a caller, not by the options object."""
+    check(lib().icaf_set_option(b"attn_stream", int(bool(on))), "icaf_set_option(attn_stream)")
+    try:
+        yield
+    finally:
+        check(lib().icaf_set_option(b"attn_stream", 0), "icaf_set_option(attn_stream)")
 
 
 def dmff_fused_lds_bytes(C_, N, heads, dt):

@@ -14,6 +14,7 @@ import torch
 _KEEP = ("anchors", "anchor_grid")
 _DETECT = re.compile(r"\.m\.\d+\.(weight|bias)$")
 _RESBN = re.compile(r"\.m\.\d+\.cv2\.bn\.weight$")   # last BN of a residual Bottleneck: small gain keeps deep stacks O(1)
+_RESBN3 = re.compile(r"\.bn3\.weight$")               # last BN of a ResNet bottleneck (16 of them in a ResNet50 stream): the same rule
 
 
 def _rng(seed, key):
@@ -45,7 +46,7 @@ def synth_tensor(key, shape, dtype=torch.float32, seed=0):
         a = g.normal(0.0, 1.35 / np.sqrt(fan_in), n)
     elif len(shape) == 2:                       # linear weight (out, in)
         a = g.normal(0.0, 1.0 / np.sqrt(shape[1]), n)
-    elif _RESBN.search(key):
+    elif _RESBN.search(key) or _RESBN3.search(key):
         a = g.uniform(0.15, 0.45, n)
     elif leaf == "weight":                      # BN / LN gain
         a = g.uniform(0.7, 1.3, n)

@@ -40,7 +40,8 @@ const char* icaf_last_error(void);
  * head of icaf_cross_attention), "sppf_vpb" (n > 0: cap on the channel vectors per workgroup of icaf_sppf_pool), "letterbox_direct" (!= 0:
  * icaf_letterbox_frames taps global memory in every tile instead of staging in LDS; set by a caller for an A/B, not by the options object),
  * "index64" (!= 0: the element kernel of icaf_dmff_pool_tokens and icaf_upsample_nearest launch the 64-bit-index instantiations they otherwise
- * keep for 2^31 vectors and more); 0 = the library's own choice.
+ * keep for 2^31 vectors and more), "attn_stream" (!= 0: icaf_cross_attention launches the key-streaming form for every shape, for A/B timings
+ * and tests; set by a caller, not by the options object); 0 = the library's own choice.
  * ICAF_ERR_ARG for an unknown name.  None of them changes a result. */
 int icaf_set_option(const char* name, int value);
 int icaf_version(void);
@@ -118,7 +119,8 @@ int icaf_vgg_stem(const void* img, int img_u8, int ctot, const void* w, const fl
  * Rounding.  The sum, bias, pre term, activation and alpha_acc are evaluated in fp32.  The result is rounded to out_dtype (nearest even,
  * subnormals kept); with a residual, alpha_res * res is then added to that ROUNDED value by one fp32 fma and the sum rounded to out_dtype
  * again — the rounding points of the unfused layers (a convolution's output is a tensor of the storage type, the shortcut adds to it).
- * With fp32 output nothing is rounded in between.  ACT_RELU is max(v, 0), torch.relu for every finite v; ACT_SILU uses the hardware exp2 / reciprocal (-0 for pre-activations below -87.3, where
+ * With fp32 output nothing is rounded in between.  With res_mode = 1 (below) the residual is widened to fp32 and added IN FRONT of the
+ * activation: sum, bias, residual and ReLU in fp32, one rounding at the store.  ACT_RELU is max(v, 0), torch.relu for every finite v; ACT_SILU uses the hardware exp2 / reciprocal (-0 for pre-activations below -87.3, where
  * the true value is below 1.05e-36); ACT_GELU is erff in the fp32 build and Abramowitz & Stegun 7.1.26 in the 16-bit builds, accurate to
  * 0.5 |v| (1.5e-7 + 2^-23) in ABSOLUTE terms: several fp16 units of the result for v <= -3.5.
  * Reads and writes.  x, res and pre may be channel slices of wider buffers holding anything, Inf and NaN included: no launch configuration
@@ -193,7 +195,17 @@ typedef struct icaf_conv_args {
      * bit-identical to the two launches. */
     const void* x2;
     long long x2_gs;
-    int ldx2, reserved2;
+    int ldx2;
+    /* Where the residual enters.  0: behind the activation, y = alpha_res*res + alpha_acc*act(...) as above (the YOLO Bottleneck).
+     * 1: in front of it,
+     *   y = relu( A.W + bias + res )
+     * — a ResNet bottleneck's conv3 + bn3 (folded) + shortcut add + ReLU (models/common.py:149-156) as one launch.  res is read in the storage
+     * type and widened to fp32; the sum and the ReLU are fp32 and there is ONE rounding, at the store.  (The reference in a 16-bit type rounds
+     * three times: after bn3, after the add, after the ReLU.)  Accepted in exactly this form: res != NULL, act == ICAF_ACT_RELU, all four
+     * alphas 1, no pre, no w2 / x2, out_dtype == dtype — anything else is ICAF_ERR_UNSUPPORTED before any device call; a value other than
+     * 0 / 1 is ICAF_ERR_ARG.  It runs on the families that run ACT_RELU (igemm.hip, igemm_stream.hip, igemm_wreg.hip), every
+     * configuration giving the same bits; ctile / cstream / cwide refuse it as they refuse ReLU.  It is no activation code. */
+    int res_mode;
 } icaf_conv_args;
 
 int icaf_conv2d(const icaf_conv_args* a, icaf_stream_t s);
@@ -256,7 +268,8 @@ int icaf_axpby(const void* x0, int ld0, const void* x1, int ld1, void* y, int ld
  * icaf_dmff_pool_tokens: AdaptivePool2d avg + max (models/common.py:868-891), LearnableWeights mix
  *   (:579-587) and positional embedding add (:817-823) for both modalities.
  *   tokens[g][b][n][c] = w1_g*avg + w2_g*max + pos_g[n][c],  g = 0 (RGB) / 1 (IR),  n = th*W' + tw.
- * icaf_layernorm: nn.LayerNorm(C), eps 1e-5 over the last dim; group g uses (gamma_g, beta_g)
+ * icaf_layernorm: nn.LayerNorm(C), eps 1e-5 over the last dim, C <= 2048 in whole 16-byte vectors (fp32 rows wider than 1024 run an
+ *   instantiation with eight vectors per lane; every other row the one it always ran); group g uses (gamma_g, beta_g)
  *   (CrossAttention.LN1/LN2 :646,:651; CrossTransformerBlock.LN2 applied to both groups :749-750).
  * icaf_cross_attention: the two crossed softmax(QK^T/sqrt(dk))V products of CrossAttention.forward (:670-685).
  *   qkv[g][row][3C] holds [q | k | v] of modality g; out[0] = softmax(q_1 k_0^T) v_0, out[1] = softmax(q_0 k_1^T) v_1
@@ -281,6 +294,13 @@ int icaf_cross_attention(const void* qkv, void* out, int dtype, int B, int N, in
 /* launch choice of icaf_cross_attention (CrossAttention.forward :670-685): *dkp = padded head dimension of the kernel instance,
  * *qsplit = query splits per head (the probe knob "attn_qsplit" included), *remap = 1 when the one-dimensional XCD-grouped grid is used */
 int icaf_cross_attention_config(int dtype, int B, int N, int C, int heads, int* dkp, int* qsplit, int* remap);
+/* Which kernel icaf_cross_attention launches for this shape (same argument checks): *form = 0, the resident form — K and V^T of a head stay in
+ * LDS for the workgroup's lifetime: d_k <= 128 and at most 160 KiB, unchanged; *form = 1, the key-streaming form — K and V^T pass through LDS
+ * in double-buffered 32-key tiles, same online softmax and key order: 128 < d_k <= 256 (a multiple of the 16-byte vector) and every shape whose
+ * resident K / V^T exceed 160 KiB (fp32 at N = 256, d_k = 128), or everything with the probe knob "attn_stream".  For form 1
+ * icaf_cross_attention_config reports the streaming instance's padded head dimension (64 / 128 / 256; d_k = 192 runs the 256 instance), its query
+ * splits (a workgroup round is four query tiles, two at 256, where a pair of waves shares a query tile and splits the head's d rows) and remap. */
+int icaf_cross_attention_form(int dtype, int B, int N, int C, int heads, int* form);
 int icaf_dmff_upsample_merge(const void* tokens, const void* fea_rgb, int ld_rgb, const void* fea_ir, int ld_ir,
                              void* out, int ldo, int dtype, int B, int H, int W, int C, int th, int tw,
                              icaf_stream_t s);
