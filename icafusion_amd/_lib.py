@@ -79,6 +79,8 @@ class FrameGeom(C.Structure):
 
 
 LETTERBOX_LDS_BYTES = 20480                 # ICAF_LETTERBOX_LDS_BYTES (icaf.h): the staging budget of one letterbox workgroup
+RESIZE_LDS_BYTES = 20480                    # ICAF_RESIZE_LDS_BYTES: the fp32 rows one icaf_resize_frames workgroup keeps between its two passes
+RESIZE_MAX_TAPS = 8                         # ICAF_RESIZE_MAX_TAPS: taps per output whose weights it tabulates
 
 
 _p, _i, _ll, _f, _sz = C.c_void_p, C.c_int, C.c_longlong, C.c_float, C.c_size_t
@@ -124,6 +126,7 @@ SIGNATURES = {
     "icaf_tta_stage": (_i, [_p, _i, _i, _i, _i, _i, C.POINTER(TtaPass), _i, _p]),
     "icaf_tta_merge": (_i, [C.POINTER(_p), C.POINTER(_ll), C.POINTER(_f), C.POINTER(_i), _i, _p, _i, _i, _f, _p]),
     "icaf_letterbox_frames": (_i, [_p, _p, _i, _i, _p, _i, _i, _i, _i, _p]),
+    "icaf_resize_frames": (_i, [_p, _p, _p, _i, _i, _p, _i, _i, _i, _i, _p]),
     "icaf_scale_detections": (_i, [_p, _p, _i, _i, _p, _i, _p, _p]),
     "icaf_match_predictions": (_i, [_p, _p, _i, _i, _p, _p, _i, _p, _p, _i, _p, _p, _p]),
     "icaf_nms_workspace_bytes": (_i, [_i, _ll, _i, _i, C.POINTER(_sz)]),

@@ -33,7 +33,8 @@ extern "C" int icaf_set_option(const char* name, int value) {
     else if (!strcmp(name, "letterbox_direct")) g_opt.letterbox_direct = value;
     else if (!strcmp(name, "index64")) g_opt.index64 = value;
     else if (!strcmp(name, "attn_stream")) g_opt.attn_stream = value;
-    else return fail(ICAF_ERR_ARG, "icaf_set_option: unknown option '%s' (detect_elementwise, attn_qsplit, sppf_vpb, letterbox_direct, index64, attn_stream)", name);
+    else if (!strcmp(name, "area_direct")) g_opt.area_direct = value;
+    else return fail(ICAF_ERR_ARG, "icaf_set_option: unknown option '%s' (detect_elementwise, attn_qsplit, sppf_vpb, letterbox_direct, index64, attn_stream, area_direct)", name);
     return ICAF_OK;
 }
 extern "C" int icaf_version(void) { return 100; }

@@ -626,14 +626,17 @@ class Model(HipModule):
             return z, logits, raws
         return z.clone(), logits.clone(), [r.clone() for r in raws]
 
-    def forward_frames(self, rgb, ir, img_size=640, bgr=True, augment=False):
+    def forward_frames(self, rgb, ir, img_size=640, bgr=True, augment=False, val_size=None):
         """Forward from NATIVE camera frames: rgb / ir are cuda uint8 tensors (B, H0, W0, ch) in decoder layout (interleaved, ch = 3 or
         1) or lists of (H0_i, W0_i, ch) tensors for ragged sizes; a pair shares its size.  The letterbox to img_size (an int or (H, W);
         utils.datasets.letterbox, byte for byte) runs on the device straight into the uint8 plan's input, then the plan (or the TTA plan)
         replays: the result is bit-identical to forward_u8 of the host-letterboxed batch.  bgr=True: frames are BGR as imread_bgr / cv2
         deliver them (the planes become RGB, LoadImages' `[:, :, ::-1]`).  Returns (forward_u8's result, FrameGeometry): .scale is the
         cuda (B, 5) rows {gain, pad_x, pad_y, w0, h0} ops.scale_detections takes, .scale_host / .geom their host twins.  Frames are
-        copied into an arena owned by the model; after the first call of a set of shapes nothing is allocated."""
+        copied into an arena owned by the model; after the first call of a set of shapes nothing is allocated.
+        val_size (an int): the VALIDATION loader's geometry instead (PairedValSet; ops.val_geometry(shapes, val_size, img_size)) — longest
+        side to val_size (pixel-area average when shrinking, utils.datasets.resize_area_scalar byte for byte; bilinear when growing), then
+        padded into img_size, the batch's letterbox shape; .scale then holds test.py's ratio_pad rows."""
         if self.training:
             raise NotImplementedError("icafusion_amd implements the eval-mode inference path only (call .eval())")
         fr = [list(t) if isinstance(t, (list, tuple)) else [t[i] for i in range(t.shape[0])] if torch.is_tensor(t) and t.dim() == 4 else None
@@ -652,14 +655,20 @@ class Model(HipModule):
         if H % gs or W % gs:
             raise ValueError(f"input size {H}x{W} must be a multiple of the max stride {gs}")
         device = fr[0][0].device
-        key = (H, W, tuple(shapes), tuple(int(f.shape[2]) for f in fr[0] + fr[1]), device)
+        key = (H, W, tuple(shapes), tuple(int(f.shape[2]) for f in fr[0] + fr[1]), device, val_size)
         states = self.__dict__.setdefault("_frame_states", {})
         st = states.pop(key, None)
         if st is None:
-            geom1, scale = ops.frame_geometry(shapes, (H, W))
+            mode = None
+            if val_size is None:
+                geom1, scale = ops.frame_geometry(shapes, (H, W))
+            else:
+                geom1, mode1, scale = ops.val_geometry(shapes, val_size, (H, W))
+                mode = np.concatenate((mode1, mode1))
             geom = np.concatenate((geom1, geom1))
             nbytes = ops.pack_frames(geom, key[3])
             st = {"geom": geom, "geom_dev": ops.geom_tensor(geom, device), "arena": torch.zeros((nbytes,), dtype=torch.uint8, device=device),
+                  "mode": mode, "mode_dev": None if mode is None else torch.from_numpy(mode).to(device),
                   "info": ops.FrameGeometry(geom, scale, torch.from_numpy(scale).to(device)), "dst": None, "launch": None}
             while len(states) >= 8:                       # a few sets of shapes stay resident (arena + table each)
                 states.pop(next(iter(states)))
@@ -667,11 +676,15 @@ class Model(HipModule):
         plan = (self.tta_plan_for if augment else self.plan_for)(B, H, W, device, u8=True)
         dst = plan.inputs[0]
         if st["dst"] is not dst:                          # the plan was rebuilt (evicted from the cache): bind the launch to its new input
-            st["launch"], st["dst"] = ops.letterbox_frames(st["arena"], st["geom"], st["geom_dev"], dst, swap_rb=bgr), dst
+            if st["mode"] is None:
+                st["launch"] = ops.letterbox_frames(st["arena"], st["geom"], st["geom_dev"], dst, swap_rb=bgr)
+            else:
+                st["launch"] = ops.resize_frames(st["arena"], st["geom"], st["mode_dev"], st["geom_dev"], dst, swap_rb=bgr, mode=st["mode"])
+            st["dst"] = dst
         for g, f in zip(st["geom"], fr[0] + fr[1]):
             o, n = int(g["offset"]), f.numel()
             st["arena"][o:o + n].view(f.shape).copy_(f)
-        st["launch"].args = st["launch"].args[:8] + (int(bool(bgr)),)
+        st["launch"].args = st["launch"].args[:-1] + (int(bool(bgr)),)
         st["launch"](ops.current_stream_ptr())
         plan.run()
         if augment:

@@ -1088,6 +1088,88 @@ def letterbox_frames(arena, geom, geom_dev, dst, swap_rb=True, c0=0, name="lette
                   keep=(arena, geom_dev, dst), name=name, nbytes=nb)
 
 
+def val_geometry(shapes, img_size, batch_shape):
+    """The validation loader's two steps for native (h0, w0) frames as numbers (PairedValSet.__getitem__; reference utils/datasets.py:
+    1116-1122 + letterbox): returns (geom, mode, scale).  Step 1, the loader's own numbers: r = img_size / max(h0, w0), (nw, nh) =
+    (int(w0 r), int(h0 r)) unless r == 1; mode 1 (pixel-area average) for r < 1, mode 0 for r > 1 (bilinear up-scale) and r == 1 (copy).
+    Step 2, letterbox_geometry((nh, nw), batch_shape, scaleup=False), must be pure padding — what the loader's rectangular batch shapes
+    and a square img_size batch give; a frame it would resize a second time raises ValueError.  geom: GEOM_DTYPE rows as frame_geometry's
+    (offset / pitch / ch left for pack_frames); mode: int32 per row; scale: float32 (n, 5) rows {nh / h0, dw, dh, w0, h0} — scale_coords'
+    ratio_pad form, the rows test.py builds from the loader's `shapes`."""
+    from .utils.datasets import letterbox_geometry
+    if isinstance(batch_shape, int):
+        batch_shape = (batch_shape, batch_shape)
+    H, W = int(batch_shape[0]), int(batch_shape[1])
+    n = len(shapes)
+    geom, mode, scale = np.zeros((n,), GEOM_DTYPE), np.zeros((n,), np.int32), np.zeros((n, 5), np.float32)
+    for i, (h0, w0) in enumerate(shapes):
+        h0, w0 = int(h0), int(w0)
+        if h0 < 1 or w0 < 1:
+            raise ValueError(f"frame {i}: empty shape {h0}x{w0}")
+        r = img_size / max(h0, w0)
+        nh, nw = (int(h0 * r), int(w0 * r)) if r != 1 else (h0, w0)
+        if nw < 1 or nh < 1:
+            raise ValueError(f"frame {i}: {h0}x{w0} with its longest side at {img_size} leaves no pixel ({nh}x{nw})")
+        _, new_unpad, (dw, dh), (top, _, left, _) = letterbox_geometry((nh, nw), (H, W), scaleup=False)
+        if new_unpad != (nw, nh):
+            raise ValueError(f"frame {i}: {h0}x{w0} -> {nh}x{nw} does not fit the {H}x{W} batch by padding alone (letterbox would resize it to "
+                             f"{new_unpad[1]}x{new_unpad[0]})")
+        g = geom[i]
+        g["h0"], g["w0"], g["nh"], g["nw"], g["top"], g["left"] = h0, w0, nh, nw, top, left
+        g["sx"], g["sy"] = np.float32(w0 / nw), np.float32(h0 / nh)
+        mode[i] = 1 if r < 1 else 0
+        scale[i] = (nh / h0, dw, dh, w0, h0)
+    return geom, mode, scale
+
+
+def area_staged(g):
+    """The budget rule of icaf_resize_frames for one mode-1 descriptor row (include/icaf.h): True = its tiles tabulate their weights and keep
+    the fp32 rows of the vertical pass in LDS, at least two output rows at a time; False = direct path (a shrink of 7 x and more on an axis, or
+    source spans too wide for two rows)."""
+    h0, w0, nh, nw, ch = (int(g[k]) for k in ("h0", "w0", "nh", "nw", "ch"))
+    sy, sx = h0 / nh, w0 / nw
+    if int(sy) + 2 > _lib.RESIZE_MAX_TAPS or int(sx) + 2 > _lib.RESIZE_MAX_TAPS:
+        return False
+    floats = ((min(w0, int(64.0 * sx) + 2) * ch + 3) & ~3) + 4
+    return min(32, _lib.RESIZE_LDS_BYTES // (4 * floats)) >= 2
+
+
+def resize_frames(arena, geom, mode_dev, geom_dev, dst, swap_rb=True, mode=None, name="resize_frames"):
+    """letterbox_frames with a resize mode per descriptor (icaf_resize_frames): mode 0 rows are letterbox_frames' bilinear resize, mode 1
+    rows the pixel-area average of utils.datasets.resize_area_scalar, byte for byte.  mode: the HOST int rows the device table `mode_dev`
+    (int32) holds; both None = every row mode 0.  Validated here, before any device call: validate_frames, and nh <= h0, nw <= w0 for mode 1."""
+    if arena.dtype != torch.uint8 or not arena.is_contiguous() or arena.dim() != 1:
+        raise ValueError("the arena must be a flat contiguous uint8 tensor")
+    if dst.dtype != torch.uint8 or not dst.is_contiguous() or dst.dim() != 4:
+        raise ValueError("dst must be a contiguous uint8 (B, ctot, H, W) tensor")
+    B, ctot, H, W = dst.shape
+    n = len(geom)
+    if n % B or n == 0 or 3 * (n // B) > ctot:
+        raise ValueError(f"{n} descriptors for a batch of {B} images with {ctot} channels")
+    if W % 16:
+        raise ValueError(f"output width {W} must be a multiple of 16")
+    if geom_dev.numel() * geom_dev.element_size() < n * GEOM_DTYPE.itemsize:
+        raise ValueError("the device table is smaller than the descriptor rows")
+    if (mode is None) != (mode_dev is None):
+        raise ValueError("the mode table needs its host rows and its device copy, or neither (all rows mode 0)")
+    if mode is not None:
+        if len(mode) != n or mode_dev.dtype != torch.int32 or not mode_dev.is_contiguous() or mode_dev.numel() < n:
+            raise ValueError(f"the mode table must hold one int32 per descriptor ({n}), host and device")
+    validate_frames(geom, arena.numel(), H, W)
+    for i in range(n if mode is not None else 0):
+        md, g = int(mode[i]), geom[i]
+        if md not in (0, 1):
+            raise ValueError(f"frame {i}: mode {md} (0 = bilinear, 1 = area)")
+        if md == 1 and (int(g["nh"]) > int(g["h0"]) or int(g["nw"]) > int(g["w0"])):
+            raise ValueError(f"frame {i}: the area mode only shrinks ({int(g['h0'])}x{int(g['w0'])} -> {int(g['nh'])}x{int(g['nw'])})")
+    if not (arena.is_cuda and dst.is_cuda and geom_dev.is_cuda and (mode_dev is None or mode_dev.is_cuda)):
+        raise ValueError("arena, tables and dst must be cuda tensors (no CPU fallback exists)")
+    nb = sum(int(g["h0"]) * int(g["w0"]) * int(g["ch"]) for g in geom) + n * 3 * H * W       # frames read once, planes written once
+    return Launch(lib().icaf_resize_frames, (arena.data_ptr(), geom_dev.data_ptr(), mode_dev.data_ptr() if mode_dev is not None else None,
+                                             n // B, B, dst.data_ptr(), ctot, H, W, int(bool(swap_rb))),
+                  keep=(arena, geom_dev, mode_dev, dst), name=name, nbytes=nb)
+
+
 def scale_detections(det, count, scale, out=None, round=False, name="scale_detections"):
     """scale_coords + clip_coords (+ torch.round) of an NMS output block on the device (icaf_scale_detections): det (B, max_det, 6) /
     count (B,) int32, scale (B, 5) fp32 device rows {gain, pad_x, pad_y, w0, h0}; out defaults to det (in place).  Rows >= count[b]
@@ -1114,6 +1196,16 @@ def letterbox_direct(on=True):
         yield
     finally:
         check(lib().icaf_set_option(b"letterbox_direct", 0), "icaf_set_option(letterbox_direct)")
+
+
+@contextlib.contextmanager
+def area_direct(on=True):
+    """Force the area rows of icaf_resize_frames onto their direct path (no LDS) inside a `with`: an A/B knob of the library, it changes no result."""
+    check(lib().icaf_set_option(b"area_direct", int(bool(on))), "icaf_set_option(area_direct)")
+    try:
+        yield
+    finally:
+        check(lib().icaf_set_option(b"area_direct", 0), "icaf_set_option(area_direct)")
 
 
 # ------------------------------------------------------------------------------------------------------------

@@ -79,6 +79,39 @@ def resize_area(img, new_wh):
     return np.clip(np.floor(out + 0.5), 0, 255).astype(np.uint8)
 
 
+def resize_area_scalar(img, new_wh):
+    """resize_area with the order of every operation fixed, so that a kernel can reproduce it bit for bit (icaf_resize_frames, mode 1).
+    Weights exactly as resize_area.weights (float64 overlap over s, rounded to float32).  Vertical pass first: v[o][x][c] = sum over h of
+    w_y[o][h] * f[h][x][c], taps in ascending h, float32 accumulator from 0, each product rounded to float32 and then added (no FMA);
+    then the horizontal pass over the float32 v in ascending x by the same rule; floor(out + 0.5) clipped to 0..255.  Zero-weight taps
+    add +0 to a non-negative sum and change nothing, so only the (int)s + 2 pixels from floor(j s) on are visited.  Equal to resize_area
+    except where the exact average is a tie k + 0.5 (within 1e-4): there BLAS' undefined summation order and this one can fall on
+    different sides, one grey level apart (tests/test_val_frames_host.py)."""
+    h, w = img.shape[:2]
+    nw, nh = new_wh
+    if (nw, nh) == (w, h):
+        return img
+
+    def taps(n_in, n_out):
+        s = n_in / n_out
+        lo = np.arange(n_out, dtype=np.float64) * s
+        hi = lo + s
+        px = lo.astype(np.int64)[:, None] + np.arange(int(s) + 2, dtype=np.int64)[None]            # (n_out, taps), ascending
+        ov = np.clip(np.minimum(hi[:, None], px + 1.0) - np.maximum(lo[:, None], px.astype(np.float64)), 0.0, None)
+        wgt = np.where(px < n_in, (ov / s).astype(np.float32), np.float32(0))
+        return np.minimum(px, n_in - 1), wgt.astype(np.float32)
+
+    def one_pass(f, idx, wgt):                                                                     # along axis 0 of f
+        acc = np.zeros((idx.shape[0],) + f.shape[1:], np.float32)
+        for t in range(idx.shape[1]):                                                              # tap t of every output at once
+            acc = acc + wgt[:, t].reshape((-1,) + (1,) * (f.ndim - 1)) * f[idx[:, t]]
+        return acc
+    f = img.astype(np.float32)
+    v = one_pass(f, *taps(h, nh))
+    out = one_pass(np.ascontiguousarray(v.swapaxes(0, 1)), *taps(w, nw)).swapaxes(0, 1)
+    return np.clip(np.floor(out + np.float32(0.5)), 0, 255).astype(np.uint8)
+
+
 def letterbox_geometry(shape, new_shape=(640, 640), scaleup=True):
     """THE numbers of the letterbox (reference utils/datasets.py:1404-1444) for a native (h0, w0): r, new_unpad = (nw, nh), the
     per-side paddings (dw, dh) and the integer split (top, bottom, left, right) of an odd pad, round(d -+ 0.1).  `letterbox` below and
@@ -204,10 +237,12 @@ def _read_labels(path):
 class PairedValSet:
     """RGB + IR validation pairs with YOLO txt labels.  `__getitem__` -> (6xHxW uint8 tensor = cat(rgb, ir) as
     utils/datasets.py:1022-1024, labels (n, 6) [0, cls, cx, cy, w, h] normalised to the letterboxed image, rgb path,
-    ((h0, w0), ((h / h0, w / w0), (pad_w, pad_h))) for scale_coords)."""
+    ((h0, w0), ((h / h0, w / w0), (pad_w, pad_h))) for scale_coords).  native=True: no host resize — the first item is (rgb BGR frame, ir BGR
+    frame, (H, W) letterbox shape of the batch) as decoded, everything else is the same; collate_fn then yields (rgb list, ir list, (H, W))."""
 
     def __init__(self, path_rgb, path_ir, img_size=640, batch_size=16, rect=False, pad=0.0, stride=32, single_cls=False,
-                 label_paths=None):
+                 label_paths=None, native=False):
+        self.native = bool(native)
         self.rgb, self.ir = _image_files(path_rgb), _image_files(path_ir)
         if not self.rgb or len(self.rgb) != len(self.ir):
             raise FileNotFoundError(f"{len(self.rgb)} RGB images under {path_rgb} vs {len(self.ir)} IR images under {path_ir}")
@@ -254,47 +289,68 @@ class PairedValSet:
     def __len__(self):
         return len(self.rgb)
 
-    def __getitem__(self, i):
-        a, b = imread_bgr(self.rgb[i]), imread_bgr(self.ir[i])
-        h0, w0 = a.shape[:2]
-        r = self.img_size / max(h0, w0)                 # longest side -> img_size (load_image_rgb_ir, :1116-1122)
-        if r != 1:
-            resize = resize_area if r < 1 else resize_bilinear
-            a, b = resize(a, (int(w0 * r), int(h0 * r))), resize(b, (int(w0 * r), int(h0 * r)))
-        h, w = a.shape[:2]
-        shape = tuple(int(v) for v in self.batch_shapes[self.batch[i]]) if self.rect else self.img_size
-        a, ratio, pad = letterbox(a, shape, auto=False, scaleup=False)
-        b = letterbox(b, shape, auto=False, scaleup=False)[0]
+    def val_size(self, h0, w0):
+        """(h, w) after load_image_rgb_ir's first step (:1116-1122): longest side -> img_size, int() truncation; and r."""
+        r = self.img_size / max(h0, w0)
+        return ((int(h0 * r), int(w0 * r)) if r != 1 else (h0, w0)), r
+
+    def _labels_shapes(self, i, h0, w0):
+        """What __getitem__ returns beside the pixels, from the geometry alone (both modes): labels (n, 6) normalised to the letterboxed
+        image, the `shapes` tuple for scale_coords and the letterbox shape (H, W) of the item's batch."""
+        (h, w), _ = self.val_size(h0, w0)
+        shape = tuple(int(v) for v in self.batch_shapes[self.batch[i]]) if self.rect else (self.img_size, self.img_size)
+        r, new_unpad, pad, (top, bottom, left, right) = letterbox_geometry((h, w), shape, scaleup=False)
+        ratio = (r, r)
+        H, W = new_unpad[1] + top + bottom, new_unpad[0] + left + right
         lab = self.labels[i]
         out = np.zeros((len(lab), 6), np.float32)
         if len(lab):        # normalised xywh of the file -> pixel xyxy of the letterboxed image -> normalised xywh of it (:961-986)
-            H, W = a.shape[:2]
             gw, gh = ratio[0] * w, ratio[1] * h
             x1, y1 = gw * (lab[:, 1] - lab[:, 3] / 2) + pad[0], gh * (lab[:, 2] - lab[:, 4] / 2) + pad[1]
             x2, y2 = gw * (lab[:, 1] + lab[:, 3] / 2) + pad[0], gh * (lab[:, 2] + lab[:, 4] / 2) + pad[1]
             out[:, 1] = lab[:, 0]
             out[:, 2], out[:, 3] = (x1 + x2) / 2 / W, (y1 + y2) / 2 / H
             out[:, 4], out[:, 5] = (x2 - x1) / W, (y2 - y1) / H
+        return torch.from_numpy(out), ((h0, w0), ((h / h0, w / w0), pad)), (H, W)
+
+    def __getitem__(self, i):
+        a, b = imread_bgr(self.rgb[i]), imread_bgr(self.ir[i])
+        h0, w0 = a.shape[:2]
+        labels, shapes, shape = self._labels_shapes(i, h0, w0)
+        if self.native:     # decode only: the consumer resizes and pads on the device (Model.forward_frames(val_size=...))
+            return (torch.from_numpy(a), torch.from_numpy(b), shape), labels, self.rgb[i], shapes
+        (h, w), r = self.val_size(h0, w0)               # longest side -> img_size (load_image_rgb_ir, :1116-1122)
+        if r != 1:
+            resize = resize_area if r < 1 else resize_bilinear
+            a, b = resize(a, (w, h)), resize(b, (w, h))
+        a = letterbox(a, shape, auto=False, scaleup=False)[0]
+        b = letterbox(b, shape, auto=False, scaleup=False)[0]
         chw = lambda x: np.ascontiguousarray(x[:, :, ::-1].transpose(2, 0, 1))      # noqa: E731
         img6 = torch.from_numpy(np.concatenate((chw(a), chw(b)), 0))
-        return img6, torch.from_numpy(out), self.rgb[i], ((h0, w0), ((h / h0, w / w0), pad))
+        return img6, labels, self.rgb[i], shapes
 
     @staticmethod
     def collate_fn(batch):
         img, label, path, shapes = zip(*batch)
         for i, l in enumerate(label):
             l[:, 0] = i                 # image index inside the batch (reference :1053-1058)
+        if isinstance(img[0], tuple):   # native items: the frames stay lists (a batch can be ragged), one letterbox shape per batch
+            rgb, ir, shape = zip(*img)
+            if len(set(shape)) != 1:
+                raise ValueError(f"native frames of one batch must share their letterbox shape, got {sorted(set(shape))}")
+            return (list(rgb), list(ir), shape[0]), torch.cat(label, 0), path, shapes
         return torch.stack(img, 0), torch.cat(label, 0), path, shapes
 
 
 def create_dataloader_rgb_ir(path1, path2, imgsz, batch_size, stride=32, opt=None, hyp=None, augment=False, cache=False, pad=0.0,
-                             rect=False, rank=-1, world_size=1, workers=0, image_weights=False, quad=False, prefix="", sampler=None):
+                             rect=False, rank=-1, world_size=1, workers=0, image_weights=False, quad=False, prefix="", sampler=None,
+                             native=False):
     """Reference signature (utils/datasets.py:102-129) -> (loader, dataset); test.py:100 calls it with rect=True, pad=0.5.
     augment / hyp / image_weights / quad belong to training and must be off."""
     if augment or image_weights or quad:
         raise NotImplementedError("training-time loading (augment / image_weights / quad) is outside the inference hot path")
     ds = PairedValSet(path1, path2, imgsz, batch_size, rect=rect, pad=pad, stride=int(stride),
-                      single_cls=bool(getattr(opt, "single_cls", False)))
+                      single_cls=bool(getattr(opt, "single_cls", False)), native=native)
     batch_size = min(batch_size, len(ds))
     loader = torch.utils.data.DataLoader(ds, batch_size=batch_size, shuffle=False, num_workers=int(workers),
                                          collate_fn=PairedValSet.collate_fn)

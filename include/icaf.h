@@ -41,7 +41,8 @@ const char* icaf_last_error(void);
  * icaf_letterbox_frames taps global memory in every tile instead of staging in LDS; set by a caller for an A/B, not by the options object),
  * "index64" (!= 0: the element kernel of icaf_dmff_pool_tokens and icaf_upsample_nearest launch the 64-bit-index instantiations they otherwise
  * keep for 2^31 vectors and more), "attn_stream" (!= 0: icaf_cross_attention launches the key-streaming form for every shape, for A/B timings
- * and tests; set by a caller, not by the options object); 0 = the library's own choice.
+ * and tests; set by a caller, not by the options object), "area_direct" (!= 0: the area rows of icaf_resize_frames recompute their vertical
+ * sums per horizontal tap instead of staging them in LDS; set by a caller for an A/B, not by the options object); 0 = the library's own choice.
  * ICAF_ERR_ARG for an unknown name.  None of them changes a result. */
 int icaf_set_option(const char* name, int value);
 int icaf_version(void);
@@ -449,6 +450,29 @@ int icaf_letterbox_frames(const void* arena, const icaf_frame_geom* geom, int ns
                           int swap_rb, icaf_stream_t s);
 int icaf_scale_detections(const float* det, const int* count, int B, int max_det, const float* scale, int round, float* out,
                           icaf_stream_t s);
+
+/* ---- native validation frames (utils/datasets.py:1116-1122, load_image_rgb_ir: longest side to img_size, then letterbox's padding) ----
+ * icaf_resize_frames: icaf_letterbox_frames with a resize mode per descriptor, so that one launch serves a rectangular validation batch
+ *   that mixes frames that shrink, frames that grow and frames that are copied.  arena, geom (DEVICE table, 48-byte rows), dst, swap_rb
+ *   and the rule "every byte of the planes written exactly once, 114 outside the block" are icaf_letterbox_frames'.  mode: DEVICE int
+ *   array parallel to geom, or NULL = every row 0.
+ *   mode 0: the bilinear arithmetic of icaf_letterbox_frames (the same device functions; sx / sy as there).
+ *   mode 1: the pixel-area average of utils.datasets.resize_area_scalar, byte for byte; needs nh <= h0 and nw <= w0 (the host checks:
+ *     icafusion_amd/ops.py resize_frames); sx / sy are not read.  Per axis s = n_in / (double)n_out on the device; output j covers
+ *     [lo, hi) = [j * s, j * s + s) in fp64, the weight of source pixel px < n_in is (float)(max(min(hi, px + 1) - max(lo, px), 0) / s),
+ *     pixels floor(lo) .. floor(lo) + (int)s + 1 are looked at and a weight of 0 is skipped.  Vertical pass first,
+ *     v[o][x][c] = sum_h wy[o][h] * f[h][x][c] in ascending h, then the horizontal pass over v in ascending x: fp32 accumulator from 0,
+ *     each product rounded to fp32 and then added (no FMA); result floor(out + 0.5f) clipped to 0..255.
+ *   One workgroup per 32 x 64 output tile.  A mode-1 tile tabulates its weights in LDS (at most ICAF_RESIZE_MAX_TAPS per output, i.e.
+ *   s < 7 on both axes) and works through its resized rows in sub-tiles of R rows: threads own four source byte columns of one output
+ *   row and run the vertical taps down the frame (one aligned 32-bit load per tap where pitch % 4 == 0, bytes inside w0 * ch otherwise;
+ *   no load leaves h0 * pitch), the fp32 v rows go to LDS, and after a barrier one lane per output column runs the horizontal taps from
+ *   there.  R = min(32, ICAF_RESIZE_LDS_BYTES / (4 * F)), F = (min(w0, (int)(64 * s_x) + 2) * ch rounded up to 4) + 4 floats per v row.
+ *   Descriptors with R < 2 or more taps than the tables hold — or every one, with the probe knob "area_direct" — take the direct path:
+ *   the same operations in the same order without LDS, each horizontal tap recomputing its vertical sum from the frame. */
+enum { ICAF_RESIZE_LDS_BYTES = 20480, ICAF_RESIZE_MAX_TAPS = 8 };
+int icaf_resize_frames(const void* arena, const icaf_frame_geom* geom, const int* mode, int nstreams, int B, void* dst, int ctot, int H,
+                       int W, int swap_rb, icaf_stream_t s);
 
 /* ---- NMS (utils/general.py:518-607 + torchvision.ops.nms semantics) ----------------------------------------
  * pred: [B][rows][5+nc] fp32 (cx, cy, w, h, obj, cls...).  Per image: obj > conf filter, conf = obj*cls, best

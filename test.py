@@ -11,7 +11,8 @@ batches), conf 0.001 / IoU 0.5 multi-label NMS, boxes mapped back to native imag
 batch shape compiles its own execution plan (hipGraph); Model keeps them in a byte-capped LRU (Model.plan_cache_bytes).
 `--save-txt` / `--save-conf` / `--save-json` leave the reference's result files (per-image `frame,x,y,w,h[,conf]` lines + `result.txt`,
 the input of the KAIST miss-rate evaluator; `<weights>_predictions.json`) under `--project/--name` (icafusion_amd/utils/results.py);
-`--task speed` runs at conf 0.25 / IoU 0.45 as the reference does.  Not carried over (all outside the metric): plots / wandb /
+`--task speed` runs at conf 0.25 / IoU 0.45 as the reference does.  `--device-letterbox` uploads the frames as decoded: the loader's
+longest-side resize (pixel-area average when shrinking) and the padding run on the device (Model.forward_frames(val_size=...)).  Not carried over (all outside the metric): plots / wandb /
 `--save-hybrid` auto-labelling / `--task study` / the pycocotools call / the MR evaluator itself (the reference's MR call site is
 disabled and returns zeros, test.py:260-285); `--augment` raises (test-time augmentation is not built)."""
 import argparse
@@ -67,7 +68,7 @@ def summarize(stats, nc, names, seen, verbose=False):
 @torch.no_grad()
 def test(data, weights=None, batch_size=32, imgsz=640, conf_thres=0.001, iou_thres=0.5, single_cls=False, model=None,
          dataloader=None, device="0", compute_dtype=None, cfg=None, verbose=False, save_json=False, save_txt=False, save_conf=True,
-         save_dir=None, augment=False):
+         save_dir=None, augment=False, device_letterbox=False):
     if augment:
         raise NotImplementedError("test-time augmentation (models/yolo_test.py:116-132) is outside the inference hot path")
     if isinstance(data, str):
@@ -91,7 +92,7 @@ def test(data, weights=None, batch_size=32, imgsz=640, conf_thres=0.001, iou_thr
         gs = int(max(float(model.stride.max()), 32))                      # grid size = max stride (test.py:68)
         # the reference passes `opt` (test.py:100), whose single_cls makes the dataset zero the label classes (utils/datasets.py:465-466)
         dataloader = create_dataloader_rgb_ir(data["val_rgb"], data["val_ir"], imgsz, batch_size, gs, argparse.Namespace(single_cls=single_cls),
-                                              pad=0.5, rect=True)[0]
+                                              pad=0.5, rect=True, native=device_letterbox)[0]
     writer = None
     if save_txt or save_json:                                           # result files of the reference (utils/results.py)
         listing = label_listing(os.path.dirname(dataloader.dataset.label_files[0])) if save_txt else None
@@ -101,10 +102,16 @@ def test(data, weights=None, batch_size=32, imgsz=640, conf_thres=0.001, iou_thr
     names = data.get("names", [str(i) for i in range(nc)])
     stats, seen, t_inf, t_nms = [], 0, 0.0, 0.0
     for img, targets, paths, shapes in dataloader:
-        img = img.to(dev, non_blocking=True)                     # uint8 (B, 6, H, W): cat(rgb, ir), test.py:116-123
-        nb, _, height, width = img.shape
-        t = time_synchronized()
-        out = model.forward_u8(img)[0]
+        if device_letterbox:                                     # native BGR frames as decoded: resized and padded on the device
+            rgb, ir, (height, width) = img
+            rgb, ir, nb = [f.to(dev, non_blocking=True) for f in rgb], [f.to(dev, non_blocking=True) for f in ir], len(rgb)
+            t = time_synchronized()
+            out = model.forward_frames(rgb, ir, img_size=(height, width), val_size=imgsz)[0][0]
+        else:
+            img = img.to(dev, non_blocking=True)                 # uint8 (B, 6, H, W): cat(rgb, ir), test.py:116-123
+            nb, _, height, width = img.shape
+            t = time_synchronized()
+            out = model.forward_u8(img)[0]
         t_inf += time_synchronized() - t
         targets = targets.clone()
         targets[:, 2:] *= torch.tensor([width, height, width, height])
@@ -120,7 +127,7 @@ def test(data, weights=None, batch_size=32, imgsz=640, conf_thres=0.001, iou_thr
             labels = targets[targets[:, 0] == si, 1:]
             tcls_all.append(labels[:, 0].tolist())
             tbox = xywh2xyxy(labels[:, 1:5])
-            scale_coords(img[si].shape[1:], tbox, shapes[si][0], shapes[si][1])               # native-space labels
+            scale_coords((height, width), tbox, shapes[si][0], shapes[si][1])                 # native-space labels
             lab_rows.append(torch.cat((labels[:, :1], tbox), 1))
             off.append(off[-1] + len(labels))
             (h0, w0), ((gain, _), (padw, padh)) = shapes[si][0], shapes[si][1]
@@ -153,7 +160,7 @@ def test(data, weights=None, batch_size=32, imgsz=640, conf_thres=0.001, iou_thr
     return (mp, mr, map50, map_, 0.0, 0.0, 0.0), maps, tt
 
 
-if __name__ == "__main__":
+def parse_opt(argv=None):
     ap_ = argparse.ArgumentParser(prog="test.py")
     ap_.add_argument("--weights", nargs="+", type=str, default=None)
     ap_.add_argument("--cfg", type=str, default="models/transformer/yolov5s_Transfusion_kaist.yaml")
@@ -170,6 +177,8 @@ if __name__ == "__main__":
     ap_.add_argument("--task", default="val", help="val / test / train: one validation pass (the reference reads val_rgb / val_ir for all three); "
                                                    "speed: conf 0.25 / IoU 0.45, nothing saved")
     ap_.add_argument("--augment", action="store_true", help="test-time augmentation: not built, raises")
+    ap_.add_argument("--device-letterbox", action="store_true", help="upload the native frames; the loader's resize (area average when "
+                                                                     "shrinking) and the padding run on the device")
     ap_.add_argument("--save-txt", action="store_true", help="per-image result lines + result.txt under <project>/<name>/labels")
     ap_.add_argument("--save-conf", action="store_true", help="append the confidence to every --save-txt line")
     ap_.add_argument("--save-json", action="store_true", help="<project>/<name>/<weights>_predictions.json")
@@ -177,7 +186,11 @@ if __name__ == "__main__":
     ap_.add_argument("--project", default="runs/test")
     ap_.add_argument("--name", default="exp")
     ap_.add_argument("--exist-ok", action="store_true")
-    o = ap_.parse_args()
+    return ap_.parse_args(argv)
+
+
+if __name__ == "__main__":
+    o = parse_opt()
     print(o)
     if o.save_hybrid:
         raise NotImplementedError("--save-hybrid (label + prediction auto-labelling, test.py:134-135) is outside the inference hot path")
@@ -187,8 +200,10 @@ if __name__ == "__main__":
     imgsz = check_img_size(o.img_size, 32)
     if o.task == "speed":                                                   # test.py:420-422
         for w in (o.weights or [None]):
-            test(o.data, [w] if w else None, o.batch_size, imgsz, 0.25, 0.45, o.single_cls, device=o.device, compute_dtype=dtype, cfg=o.cfg)
+            test(o.data, [w] if w else None, o.batch_size, imgsz, 0.25, 0.45, o.single_cls, device=o.device, compute_dtype=dtype, cfg=o.cfg,
+                 device_letterbox=o.device_letterbox)
     else:
         save_dir = increment_path(os.path.join(o.project, o.name), exist_ok=o.exist_ok) if (o.save_txt or o.save_json) else None
         test(o.data, o.weights, o.batch_size, imgsz, o.conf_thres, o.iou_thres, o.single_cls, device=o.device, compute_dtype=dtype, cfg=o.cfg,
-             verbose=o.verbose, save_json=o.save_json, save_txt=o.save_txt, save_conf=o.save_conf, save_dir=save_dir, augment=o.augment)
+             verbose=o.verbose, save_json=o.save_json, save_txt=o.save_txt, save_conf=o.save_conf, save_dir=save_dir, augment=o.augment,
+             device_letterbox=o.device_letterbox)
