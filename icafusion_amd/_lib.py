@@ -81,6 +81,7 @@ class FrameGeom(C.Structure):
 LETTERBOX_LDS_BYTES = 20480                 # ICAF_LETTERBOX_LDS_BYTES (icaf.h): the staging budget of one letterbox workgroup
 RESIZE_LDS_BYTES = 20480                    # ICAF_RESIZE_LDS_BYTES: the fp32 rows one icaf_resize_frames workgroup keeps between its two passes
 RESIZE_MAX_TAPS = 8                         # ICAF_RESIZE_MAX_TAPS: taps per output whose weights it tabulates
+MISSRATE_MAX_DET, MISSRATE_KEEP, MISSRATE_MAX_LABELS, MISSRATE_SETUPS = 1024, 1000, 256, 7     # ICAF_MISSRATE_*: store rows / maxDets / labels per image / set-ups
 
 
 _p, _i, _ll, _f, _sz = C.c_void_p, C.c_int, C.c_longlong, C.c_float, C.c_size_t
@@ -131,6 +132,8 @@ SIGNATURES = {
     "icaf_match_predictions": (_i, [_p, _p, _i, _i, _p, _p, _i, _p, _p, _i, _p, _p, _p]),
     "icaf_nms_workspace_bytes": (_i, [_i, _ll, _i, _i, C.POINTER(_sz)]),
     "icaf_nms": (_i, [_p, _i, _ll, _i, _f, _f, _i, _i, C.POINTER(_i), _i, _i, _i, _f, _p, _p, _p, _p, _sz, _p]),
+    "icaf_missrate_stage": (_i, [_p, _p, _p, _p, _i, _i, _p, _p, _i, _i, _p]),
+    "icaf_missrate_match": (_i, [_p, _p, _p, _p, _p, _i, _i, _p, _p, _i, _p, _p, _p, _p, _p]),
     "icaf_graph_begin": (_i, [_p]),
     "icaf_graph_end": (_i, [_p, C.POINTER(_p)]),
     "icaf_graph_launch": (_i, [_p, _p]),

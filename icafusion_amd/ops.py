@@ -1188,6 +1188,119 @@ def scale_detections(det, count, scale, out=None, round=False, name="scale_detec
                   keep=(det, count, scale, out), name=name, nbytes=2 * det.numel() * 4)
 
 
+class MissrateTable:
+    """The label table of a KAIST annotation file on the device (utils.missrate.load_annotations -> missrate_table)."""
+    __slots__ = ("box", "height", "occlusion", "ignore", "off", "images", "labels", "max_labels")
+
+
+def missrate_table(table, device="cuda"):
+    """Label table of utils.missrate.load_annotations -> device tensors for missrate_match.  ValueError, before anything is uploaded, when
+    an image holds more than 256 labels (one workgroup keeps an image's labels in the registers of a wave) or the arrays disagree."""
+    off = np.asarray(table["off"], dtype=np.int64)
+    G = len(table["id"])
+    if off.ndim != 1 or len(off) < 2 or off[0] != 0 or off[-1] != G or (np.diff(off) < 0).any():
+        raise ValueError("off must be ascending offsets from 0 to the number of labels, one image at least")
+    if np.asarray(table["box"]).shape != (G, 4) or any(len(table[k]) != G for k in ("height", "occlusion", "ignore")):
+        raise ValueError("box (G, 4), height, occlusion and ignore (G,) must describe the same labels")
+    most = int(np.diff(off).max())
+    if most > _lib.MISSRATE_MAX_LABELS:
+        raise ValueError(f"image {int(np.diff(off).argmax())} holds {most} labels; icaf_missrate_match takes at most {_lib.MISSRATE_MAX_LABELS}")
+    if torch.device(device).type != "cuda":
+        raise ValueError("the label table lives on a cuda device (no CPU fallback exists)")
+    t = MissrateTable()
+    t.box = torch.from_numpy(np.array(table["box"], dtype=np.float64)).to(device)
+    t.height = torch.from_numpy(np.array(table["height"], dtype=np.float64)).to(device)
+    t.occlusion = torch.from_numpy(np.array(table["occlusion"], dtype=np.int32)).to(device)
+    t.ignore = torch.from_numpy(np.array(table["ignore"], dtype=np.int32)).to(device)
+    t.off = torch.from_numpy(off.astype(np.int32)).to(device)
+    t.images, t.labels, t.max_labels = len(off) - 1, G, most
+    return t
+
+
+def _missrate_store(dt, dt_count):
+    if dt.dim() != 3 or dt.shape[2] != 5 or dt.dtype != torch.float64 or not dt.is_contiguous() or not dt.is_cuda:
+        raise ValueError("dt must be a contiguous cuda float64 (I, cap, 5) tensor")
+    I, cap, _ = dt.shape
+    if I < 1 or cap < 1 or cap > _lib.MISSRATE_MAX_DET:
+        raise ValueError(f"the detection store holds {I} images x {cap} rows; cap must be in [1, {_lib.MISSRATE_MAX_DET}]")
+    if dt_count.dtype != torch.int32 or dt_count.numel() != I or not dt_count.is_contiguous() or dt_count.device != dt.device:
+        raise ValueError("dt_count must be a cuda int32 (I,) tensor")
+    return I, cap
+
+
+def missrate_stage(predn, det, count, image_index, image_index_dev, dt, dt_count, name="missrate_stage"):
+    """One validation batch into the detection store of the KAIST miss-rate evaluation (icaf_missrate_stage): predn (B, max_det, 4)
+    native-space xyxy and det (B, max_det, 6) / count (B,) int32 as match_predictions leaves them; image_index: the HOST ints (store row
+    of every image of the batch, distinct, inside the store) that the device int32 tensor `image_index_dev` holds.  Rows
+    [0, min(count, cap)) of dt[image_index[b]] become {x1, y1, x2 - x1, y2 - y1 (fp32), score} in fp64, dt_count[image_index[b]] that
+    bound.  Validated here, before any device call."""
+    if det.dim() != 3 or det.shape[2] != 6 or det.dtype != torch.float32 or not det.is_contiguous() or not det.is_cuda:
+        raise ValueError("det must be a contiguous cuda float32 (B, max_det, 6) tensor")
+    B, max_det, _ = det.shape
+    if tuple(predn.shape) != (B, max_det, 4) or predn.dtype != torch.float32 or not predn.is_contiguous() or predn.device != det.device:
+        raise ValueError("predn must be a contiguous cuda float32 (B, max_det, 4) tensor beside det")
+    if count.dtype != torch.int32 or count.numel() != B or not count.is_contiguous() or count.device != det.device:
+        raise ValueError("count must be a cuda int32 (B,) tensor")
+    I, cap = _missrate_store(dt, dt_count)
+    if dt.device != det.device:
+        raise ValueError("the detection store and the batch must share a device")
+    idx = [int(v) for v in image_index]
+    if len(idx) != B or len(set(idx)) != B or min(idx) < 0 or max(idx) >= I:
+        raise ValueError(f"image_index must name {B} distinct rows of the {I}-image store")
+    if image_index_dev.dtype != torch.int32 or not image_index_dev.is_contiguous() or image_index_dev.numel() < B or image_index_dev.device != det.device:
+        raise ValueError("image_index_dev must be a cuda int32 tensor of at least B entries")
+    return Launch(lib().icaf_missrate_stage, (predn.data_ptr(), det.data_ptr(), count.data_ptr(), image_index_dev.data_ptr(), B, max_det,
+                                             dt.data_ptr(), dt_count.data_ptr(), I, cap),
+                  keep=(predn, det, count, image_index_dev, dt, dt_count), name=name, nbytes=B * max_det * (20 + 40))
+
+
+def missrate_outputs(tab, cap, device):
+    """Output tensors of missrate_match: order (I, cap) int32, dt_gt (I, cap, 7) int32, dt_ignore (I, cap) uint8, gt_ignore (G,) uint8."""
+    return (torch.zeros((tab.images, cap), dtype=torch.int32, device=device),
+            torch.full((tab.images, cap, _lib.MISSRATE_SETUPS), -1, dtype=torch.int32, device=device),
+            torch.zeros((tab.images, cap), dtype=torch.uint8, device=device), torch.zeros((max(tab.labels, 1),), dtype=torch.uint8, device=device))
+
+
+def missrate_match(tab, dt, dt_count, order, dt_gt, dt_ignore, gt_ignore, name="missrate_match"):
+    """Score sort + ignore-aware greedy matching of every image under the seven KAIST set-ups in one launch (icaf_missrate_match;
+    reference evaluation_script.py:46-294).  tab: missrate_table; dt (I, cap, 5) fp64 / dt_count (I,) int32: the detection store; the
+    outputs as missrate_outputs allocates them.  Rows at or beyond dt_count[i] (and positions >= 1000) keep what they held."""
+    if not isinstance(tab, MissrateTable):
+        raise ValueError("tab must come from missrate_table")
+    I, cap = _missrate_store(dt, dt_count)
+    if I != tab.images:
+        raise ValueError(f"the store holds {I} images, the label table {tab.images}")
+    for t, shape, dtype, what in ((order, (I, cap), torch.int32, "order"), (dt_gt, (I, cap, _lib.MISSRATE_SETUPS), torch.int32, "dt_gt"),
+                                  (dt_ignore, (I, cap), torch.uint8, "dt_ignore")):
+        if tuple(t.shape) != shape or t.dtype != dtype or not t.is_contiguous() or t.device != dt.device:
+            raise ValueError(f"{what} must be a contiguous {dtype} tensor of shape {shape} beside dt")
+    if gt_ignore.dtype != torch.uint8 or gt_ignore.numel() < tab.labels or not gt_ignore.is_contiguous() or gt_ignore.device != dt.device:
+        raise ValueError("gt_ignore must be a cuda uint8 tensor with one entry per label")
+    if tab.off.device != dt.device:
+        raise ValueError("the label table and the detection store must share a device")
+    return Launch(lib().icaf_missrate_match, (tab.box.data_ptr() or None, tab.height.data_ptr() or None, tab.occlusion.data_ptr() or None,
+                                             tab.ignore.data_ptr() or None, tab.off.data_ptr(), I, tab.max_labels, dt.data_ptr(),
+                                             dt_count.data_ptr(), cap, order.data_ptr(), dt_gt.data_ptr(), dt_ignore.data_ptr(),
+                                             gt_ignore.data_ptr()),
+                  keep=(tab, dt, dt_count, order, dt_gt, dt_ignore, gt_ignore), name=name, nbytes=dt.numel() * 8 + I * cap * 33)
+
+
+def missrate_evaluate(table, dt, dt_count, device="cuda"):
+    """Host arrays in, host arrays out: upload the label table and the packed store (utils.missrate.pack_detections), one missrate_match
+    launch, download.  Returns a dict of numpy arrays order / dt_gt / dt_ignore / gt_ignore."""
+    dt, dt_count = np.array(dt, dtype=np.float64), np.array(dt_count, dtype=np.int32)            # copies: torch wants writable arrays
+    if dt.ndim != 3 or dt.shape[2] != 5 or dt_count.shape != (dt.shape[0],) or dt_count.min(initial=0) < 0 or dt_count.max(initial=0) > dt.shape[1]:
+        raise ValueError("dt must be (I, cap, 5) and dt_count (I,) with 0 <= dt_count <= cap")
+    if not np.isfinite(dt[:, :, 4][np.arange(dt.shape[1])[None, :] < dt_count[:, None]]).all():
+        raise ValueError("non-finite detection score")
+    tab = missrate_table(table, device)
+    dt_d, cnt_d = torch.from_numpy(dt).to(device), torch.from_numpy(dt_count).to(device)
+    outs = missrate_outputs(tab, dt.shape[1], dt_d.device)
+    missrate_match(tab, dt_d, cnt_d, *outs)(current_stream_ptr())
+    order, dt_gt, dt_ignore, gt_ignore = (o.cpu().numpy() for o in outs)
+    return {"order": order, "dt_gt": dt_gt, "dt_ignore": dt_ignore, "gt_ignore": gt_ignore[:tab.labels]}
+
+
 @contextlib.contextmanager
 def letterbox_direct(on=True):
     """Force icaf_letterbox_frames onto its direct path (no LDS staging) inside a `with`: an A/B knob of the library, it changes no result."""

@@ -499,6 +499,42 @@ int icaf_nms(const float* pred, int B, long long rows, int nc, float conf_thres,
              int agnostic, const int* classes_host, int n_classes, int max_det, int max_nms, float max_wh,
              float* det, int* count, int* keep_idx, void* workspace, size_t workspace_bytes, icaf_stream_t s);
 
+/* ---- KAIST log-average miss rate, per-image half (evaluation_script/evaluation_script.py:46-79, 119-179, 181-294, 478-497) ----------
+ * The reference evaluator's nine passes (All / Day / Night on set-up 0, near / medium / far / none / partial / heavy on set-ups 1-6) share
+ * their per-image work up to the set-up, so one launch matches every image under all seven set-ups; the FPPI sweep (:296-395, 432-475)
+ * runs on the host (icafusion_amd/utils/missrate.py).
+ * Set-ups (KAISTParams, :478-497): HtRng = [55,1e10] [115,1e10] [45,115] [1,45] [1,1e10] [1,1e10] [1,1e10], OccRng = {0,1} {0} {0} {0} {0} {1}
+ *   {2}, IoU threshold 0.5, maxDets 1000, bndRng = 5, 5, 635, 507.
+ * icaf_missrate_stage: one validation batch into the detection store.  predn [B][max_det][4] native-space xyxy and det [B][max_det][6]
+ *   (score in column 4) as icaf_match_predictions leaves them, count [B], image_index [B] (DEVICE ints: the image's row in the store, i.e.
+ *   frame - 1 of the result files).  Row i < min(count[b], max_det, cap) of dt[image_index[b]] becomes {x1, y1, x2 - x1, y2 - y1, score}:
+ *   the subtraction in fp32 (as the result-file writer's), then widened to fp64; dt_count[image_index[b]] = that bound.  An index outside
+ *   [0, I) writes nothing.  One launch, no host synchronisation.
+ * icaf_missrate_match: one workgroup per image.  Labels in annotation order: gt_box [G][4] fp64 (x, y, w, h), gt_height [G] fp64,
+ *   gt_occlusion [G], gt_ignore_base [G] (the file's `ignore`, 0 if absent), image i owning rows [gt_off[i], gt_off[i + 1]); detections
+ *   dt [I][cap][5] fp64 (x, y, w, h, score; an image's rows in arrival order) and dt_count [I]; max_labels_per_image is the HOST's
+ *   maximum of gt_off[i + 1] - gt_off[i].
+ *   gt_ignore [G]: bit s = ignored in set-up s (:59-71): the base flag, or height < lo, height > hi, occlusion not in OccRng[s], x < 5,
+ *     y < 5, x + w > 635 or y + h > 507.
+ *   order [I][cap]: sorted position -> arrival index, descending score, equal scores in arrival order (np.argsort(-score, 'mergesort'),
+ *     :129, :207); only the first 1000 positions are matched (:208).
+ *   dt_gt [I][cap][7], dt_ignore [I][cap]: per sorted position and set-up the matched row of the label table or -1, and bit s = matched to
+ *     an ignored label.  Labels are walked non-ignored first, then ignored, each group in annotation order (:205), with best = 0.5 (:229-250):
+ *     a taken non-ignored label is skipped; the walk stops at the first ignored label once anything has matched; a label with iou < best
+ *     is skipped; otherwise it is taken and best = iou.  Hence the maximal IoU >= 0.5 among the free non-ignored labels, the LATER label on a
+ *     tie; failing that the FIRST ignored label with IoU >= 0.5 (not the best one).  Only a non-ignored match consumes its label (:257-258).
+ *   IoU (:148-179) in fp64 without contraction: dx2 = dx + dw, iw = min(dx2, gx2) - max(dx1, gx1), zero overlap if iw <= 0, ih likewise,
+ *     t = iw * ih, union = dw * dh for an ignored label and (dw * dh + gw * gh) - t otherwise, iou = t / union (IEEE division).
+ *   Rows at or beyond dt_count[i] (and positions >= 1000) of the three per-detection outputs are left as they were; nothing is read or
+ *   written outside the tables.  ICAF_ERR_UNSUPPORTED before any device call for more than ICAF_MISSRATE_MAX_LABELS labels in an image or
+ *   cap > ICAF_MISSRATE_MAX_DET, ICAF_ERR_ARG for null pointers.  Scores must be finite (the host wrappers check before upload). */
+enum { ICAF_MISSRATE_MAX_DET = 1024, ICAF_MISSRATE_KEEP = 1000, ICAF_MISSRATE_MAX_LABELS = 256, ICAF_MISSRATE_SETUPS = 7 };
+int icaf_missrate_stage(const float* predn, const float* det, const int* count, const int* image_index, int B, int max_det, double* dt,
+                        int* dt_count, int I, int cap, icaf_stream_t s);
+int icaf_missrate_match(const double* gt_box, const double* gt_height, const int* gt_occlusion, const int* gt_ignore_base,
+                        const int* gt_off, int I, int max_labels_per_image, const double* dt, const int* dt_count, int cap, int* order,
+                        int* dt_gt, unsigned char* dt_ignore, unsigned char* gt_ignore, icaf_stream_t s);
+
 /* ---- HIP graph capture / events (so the Python host never needs a tracing compiler) ------------------------ */
 int icaf_graph_begin(icaf_stream_t s);
 int icaf_graph_end(icaf_stream_t s, void** graph_exec);

@@ -11,10 +11,11 @@ batches), conf 0.001 / IoU 0.5 multi-label NMS, boxes mapped back to native imag
 batch shape compiles its own execution plan (hipGraph); Model keeps them in a byte-capped LRU (Model.plan_cache_bytes).
 `--save-txt` / `--save-conf` / `--save-json` leave the reference's result files (per-image `frame,x,y,w,h[,conf]` lines + `result.txt`,
 the input of the KAIST miss-rate evaluator; `<weights>_predictions.json`) under `--project/--name` (icafusion_amd/utils/results.py);
+`--miss-rate ANNOTATIONS` adds the KAIST log-average miss rate (the evaluator of the reference's `evaluation_script/`: matching on the
+device, FPPI sweep in numpy; icafusion_amd/utils/missrate.py) and returns its dict as a fourth element; `--task speed` ignores it.
 `--task speed` runs at conf 0.25 / IoU 0.45 as the reference does.  `--device-letterbox` uploads the frames as decoded: the loader's
 longest-side resize (pixel-area average when shrinking) and the padding run on the device (Model.forward_frames(val_size=...)).  Not carried over (all outside the metric): plots / wandb /
-`--save-hybrid` auto-labelling / `--task study` / the pycocotools call / the MR evaluator itself (the reference's MR call site is
-disabled and returns zeros, test.py:260-285); `--augment` raises (test-time augmentation is not built)."""
+`--save-hybrid` auto-labelling / `--task study` / the pycocotools call / MR curves and plots; `--augment` raises (test-time augmentation is not built)."""
 import argparse
 import os
 import time
@@ -28,7 +29,8 @@ from icafusion_amd.models.yolo import Model
 from icafusion_amd.utils.datasets import create_dataloader_rgb_ir
 from icafusion_amd import ops
 from icafusion_amd.utils.general import check_img_size, increment_path, nms_device, scale_coords, xywh2xyxy
-from icafusion_amd.utils.results import ResultWriter, label_listing
+from icafusion_amd.utils import missrate
+from icafusion_amd.utils.results import ResultWriter, frame_index, label_listing
 from icafusion_amd.utils.metrics import ap_per_class
 from icafusion_amd.utils.torch_utils import select_device, time_synchronized
 
@@ -65,16 +67,53 @@ def summarize(stats, nc, names, seen, verbose=False):
     return (mp, mr, map50, map_), maps, lines
 
 
+class MissRate:
+    """KAIST log-average miss rate of one validation pass (`miss_rate=` / `--miss-rate`): every batch's native-space boxes are staged on
+    the device into the store the matching kernel reads (icaf_missrate_stage, at the image's position in the sorted label directory:
+    the `frame - 1` of result.txt), one icaf_missrate_match launch follows the loop, and utils.missrate.summarize runs the FPPI sweep."""
+
+    def __init__(self, ann_path, dataset, dev):
+        self.table = missrate.load_annotations(ann_path)
+        self.listing = label_listing(os.path.dirname(dataset.label_files[0]))
+        n_img, n_ann = len(dataset.label_files), len(self.table["image_id"])
+        if n_img != n_ann or len(self.listing) != n_ann:
+            raise ValueError(f"{ann_path} describes {n_ann} images, the data set holds {n_img} ({len(self.listing)} label files)")
+        stems = [os.path.splitext(n)[0].replace("_", "/") for n in self.listing]
+        if set(stems) <= set(self.table["im_name"]) and stems != list(self.table["im_name"]):
+            bad = next(i for i, (a, b) in enumerate(zip(stems, self.table["im_name"])) if a != b)
+            raise ValueError(f"frame {bad + 1} is {stems[bad]} in the label directory and {self.table['im_name'][bad]} in {ann_path}")
+        self.dev, self.tab, self.dt, self.count = dev, ops.missrate_table(self.table, dev), None, None
+
+    def stage(self, predn, det, count, paths):
+        if self.dt is None:                                                     # cap = NMS's max_det
+            self.dt = torch.zeros((self.tab.images, det.shape[1], 5), dtype=torch.float64, device=self.dev)
+            self.count = torch.zeros((self.tab.images,), dtype=torch.int32, device=self.dev)
+        index = [frame_index(self.listing, os.path.splitext(os.path.basename(p))[0]) for p in paths]
+        ops.missrate_stage(predn, det, count, index, torch.tensor(index, dtype=torch.int32, device=self.dev), self.dt,
+                           self.count)(ops.current_stream_ptr())
+
+    def finish(self):
+        if self.dt is None:
+            raise ValueError("no batch was staged")
+        outs = ops.missrate_outputs(self.tab, self.dt.shape[1], self.dev)
+        ops.missrate_match(self.tab, self.dt, self.count, *outs)(ops.current_stream_ptr())
+        order, dt_gt, dt_ignore, gt_ignore = (o.cpu().numpy() for o in outs)
+        dt, count = self.dt.cpu().numpy(), self.count.cpu().numpy()
+        return missrate.summarize(self.table, count, missrate.sorted_scores(dt, order, count), dt_gt, dt_ignore, gt_ignore[:self.tab.labels])
+
+
 @torch.no_grad()
 def test(data, weights=None, batch_size=32, imgsz=640, conf_thres=0.001, iou_thres=0.5, single_cls=False, model=None,
          dataloader=None, device="0", compute_dtype=None, cfg=None, verbose=False, save_json=False, save_txt=False, save_conf=True,
-         save_dir=None, augment=False, device_letterbox=False):
+         save_dir=None, augment=False, miss_rate=None, device_letterbox=False):
     if augment:
         raise NotImplementedError("test-time augmentation (models/yolo_test.py:116-132) is outside the inference hot path")
     if isinstance(data, str):
         with open(data) as f:
             data = yaml.safe_load(f)
     nc = 1 if single_cls else int(data["nc"])
+    if miss_rate and nc > 1:
+        raise ValueError(f"the KAIST miss rate is a one-class (person) metric: {nc} classes need --single-cls")
     if model is None:
         dev = select_device(device)
         if weights:
@@ -98,6 +137,7 @@ def test(data, weights=None, batch_size=32, imgsz=640, conf_thres=0.001, iou_thr
         listing = label_listing(os.path.dirname(dataloader.dataset.label_files[0])) if save_txt else None
         writer = ResultWriter(save_dir if save_dir is not None else increment_path("runs/test/exp"), save_txt=save_txt, save_conf=save_conf,
                               save_json=save_json, label_names=listing, weights=weights)
+    mr_eval = MissRate(miss_rate, dataloader.dataset, dev) if miss_rate else None
     iouv = np.linspace(0.5, 0.95, 10)
     names = data.get("names", [str(i) for i in range(nc)])
     stats, seen, t_inf, t_nms = [], 0, 0.0, 0.0
@@ -132,10 +172,12 @@ def test(data, weights=None, batch_size=32, imgsz=640, conf_thres=0.001, iou_thr
             off.append(off[-1] + len(labels))
             (h0, w0), ((gain, _), (padw, padh)) = shapes[si][0], shapes[si][1]
             scale.append([gain, padw, padh, w0, h0])
-        predn = torch.zeros((nb, det.shape[1], 4), dtype=torch.float32, device=dev) if writer else None     # native-space boxes
+        predn = torch.zeros((nb, det.shape[1], 4), dtype=torch.float32, device=dev) if writer or mr_eval else None     # native-space boxes
         correct = ops.match_predictions(det, count, torch.cat(lab_rows).float().contiguous().to(dev),
                                         torch.tensor(off, dtype=torch.int32, device=dev), torch.from_numpy(iouv.astype(np.float32)).to(dev),
                                         scale=torch.tensor(scale, dtype=torch.float32, device=dev), predn=predn)
+        if mr_eval:
+            mr_eval.stage(predn, det, count, paths)
         correct, cc, count = correct.cpu().numpy().astype(bool), det[..., 4:6].cpu().numpy(), count.cpu().numpy()
         predn = predn.cpu().numpy() if writer else None
         for si in range(nb):
@@ -157,6 +199,10 @@ def test(data, weights=None, batch_size=32, imgsz=640, conf_thres=0.001, iou_thr
     print("\n".join(lines))
     tt = tuple(x / max(seen, 1) * 1e3 for x in (t_inf, t_nms, t_inf + t_nms)) + (imgsz, imgsz, batch_size)
     print("Speed: %.1f/%.1f/%.1f ms inference/NMS/total per %gx%g image at batch-size %g" % tt)
+    if mr_eval:
+        mr_dict = mr_eval.finish()
+        print("\n".join(missrate.format_lines(mr_dict)))
+        return (mp, mr, map50, map_, 0.0, 0.0, 0.0), maps, tt, mr_dict
     return (mp, mr, map50, map_, 0.0, 0.0, 0.0), maps, tt
 
 
@@ -179,6 +225,8 @@ def parse_opt(argv=None):
     ap_.add_argument("--augment", action="store_true", help="test-time augmentation: not built, raises")
     ap_.add_argument("--device-letterbox", action="store_true", help="upload the native frames; the loader's resize (area average when "
                                                                      "shrinking) and the padding run on the device")
+    ap_.add_argument("--miss-rate", type=str, default=None, metavar="ANNOTATIONS",
+                     help="KAIST annotation JSON: also report the log-average miss rate (All / Day / Night, scale and occlusion subsets)")
     ap_.add_argument("--save-txt", action="store_true", help="per-image result lines + result.txt under <project>/<name>/labels")
     ap_.add_argument("--save-conf", action="store_true", help="append the confidence to every --save-txt line")
     ap_.add_argument("--save-json", action="store_true", help="<project>/<name>/<weights>_predictions.json")
@@ -206,4 +254,4 @@ if __name__ == "__main__":
         save_dir = increment_path(os.path.join(o.project, o.name), exist_ok=o.exist_ok) if (o.save_txt or o.save_json) else None
         test(o.data, o.weights, o.batch_size, imgsz, o.conf_thres, o.iou_thres, o.single_cls, device=o.device, compute_dtype=dtype, cfg=o.cfg,
              verbose=o.verbose, save_json=o.save_json, save_txt=o.save_txt, save_conf=o.save_conf, save_dir=save_dir, augment=o.augment,
-             device_letterbox=o.device_letterbox)
+             miss_rate=o.miss_rate, device_letterbox=o.device_letterbox)
