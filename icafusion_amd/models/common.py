@@ -33,6 +33,68 @@ def _pair(v):
     return (v, v) if isinstance(v, int) else tuple(v)
 
 
+def conv_out(n, k, s, p):
+    """Output extent of a k / stride s / padding p window over n positions (floor, as Conv2d and MaxPool2d)."""
+    return (n + 2 * p - k) // s + 1
+
+
+def conv2d_shape(k, H, W):
+    """(C, H', W') an nn.Conv2d makes of an H x W map."""
+    (kh, kw), (sh, sw), (ph, pw) = k.kernel_size, k.stride, _pair(k.padding)
+    return k.out_channels, conv_out(H, kh, sh, ph), conv_out(W, kw, sw, pw)
+
+
+def pool_window(pool):
+    """(kernel, stride, padding) of a square nn.MaxPool2d."""
+    return tuple(v if isinstance(v, int) else v[0] for v in (pool.kernel_size, pool.stride, pool.padding))
+
+
+def fold_bn(conv, bn=None):
+    """fp32 (weight, bias) of an nn.Conv2d, the eval-mode BatchNorm2d behind it folded in."""
+    w = conv.weight.detach().float()
+    b = conv.bias.detach().float() if conv.bias is not None else torch.zeros(w.shape[0], device=w.device)
+    if bn is not None:
+        scale = bn.weight.detach().float() / torch.sqrt(bn.running_var.detach().float() + bn.eps)
+        w = w * scale[:, None, None, None]
+        b = (b - bn.running_mean.detach().float()) * scale + bn.bias.detach().float()
+    return w, b
+
+
+def stage_image(plan, x, c1, s2d=False):
+    """Network image (ImageIn x, c1 channels) in, NHWC act out — s2d: in 2 x 2 space-to-depth form, 4 * c1 channels at half the size — the
+    channels padded to whole 16-byte vectors.  Allocates the act and appends the staging launch -> (act, its channel count)."""
+    B, _, H, W = x.shape
+    vec = ops.VEC[plan.dtype]
+    cpad = -(-(4 * c1 if s2d else c1) // vec) * vec
+    pre = plan.act(B, H // 2 if s2d else H, W // 2 if s2d else W, cpad, pair=x.pair)
+    tag = "s2d" if s2d else "pad"
+    plan.add(ops.preprocess_u8(x.t, pre, int(s2d), x.c0, name=f"preprocess_u8_{tag}") if x.u8
+             else ops.preprocess(x.t, pre, int(s2d), name=f"preprocess_{tag}"))
+    return pre, cpad
+
+
+def emit_maxpool(plan, x, pool, out, name):
+    """nn.MaxPool2d `pool` of the act / pair act x into `out` (allocated when None): one launch, or one per stream when the pair's halves
+    are channel slices of a fusion buffer."""
+    k, s, p = pool_window(pool)
+    B, H, W, C = x.shape[-4:]
+    if out is None:
+        out = plan.act(B, conv_out(H, k, s, p), conv_out(W, k, s, p), C, pair=x.dim() == 5)
+    if x.dim() == 5 and out.stride(0) != B * out.stride(1):
+        for g in range(2):
+            plan.add(ops.maxpool2d(x[g], out[g], k, s, p, name=name))
+    else:
+        plan.add(ops.maxpool2d(x, out, k, s, p, name=name))
+    return out
+
+
+def pair_signature(self):
+    """What must match for two rows to run as one groups = 2 launch sequence: state_dict keys and shapes, Conv2d geometries, Conv activations."""
+    return ([(k, tuple(v.shape)) for k, v in self.state_dict().items()],
+            [(c.kernel_size, c.stride, c.padding, c.groups) for c in self.modules() if isinstance(c, nn.Conv2d)],
+            [type(c.act) for c in self.modules() if isinstance(c, Conv)])
+
+
 def _module_dtype(m, fallback=torch.float32):
     forced = getattr(m, "compute_dtype", None)
     if forced is not None:
@@ -68,6 +130,27 @@ class HipModule(nn.Module):
         if key not in c:
             c[key] = make()
         return c[key]
+
+    def packed_convs(self, plan, streams, swap_halves=False, cin_slice=None, transform=None, cin_pad=None, pack=None):
+        """-> (wp, kp, bp), the launch form of convolution weights.  streams: per stream the (Conv2d, BatchNorm2d or None) pairs whose outputs
+        are concatenated along Cout; BatchNorm is folded, the K halves swapped / the K columns cin_slice kept, `transform` applied, then
+        pack(rows, dtype, cin_pad) — ops.pack_streams unless given — pads Cin, casts and stacks the streams.  Cached on self under a key derived
+        from exactly these arguments: whoever asks for the same packing gets the same tensor, and nobody spells a key."""
+        key = ("pack", plan.dtype, plan.device, tuple(tuple((id(c), id(b)) for c, b in s) for s in streams), bool(swap_halves),
+               None if cin_slice is None else tuple(cin_slice), transform, cin_pad, pack)
+
+        def make():
+            rows = []
+            for s in streams:
+                w, b = (torch.cat(t) for t in zip(*(fold_bn(conv, bn) for conv, bn in s)))
+                if swap_halves:
+                    h = w.shape[1] // 2
+                    w = torch.cat((w[:, h:], w[:, :h]), 1)
+                if cin_slice is not None:
+                    w = w[:, cin_slice[0]:cin_slice[1]]
+                rows.append((w if transform is None else transform(w), b))
+            return (pack or ops.pack_streams)(rows, plan.dtype, cin_pad)
+        return self._cached(key, make)
 
     # stand-alone call: NCHW tensor(s) in, NCHW-shaped tensor(s) out
     def forward(self, x):
@@ -136,37 +219,21 @@ class Conv(HipModule):
 
     def folded(self):
         """fp32 (weight, bias) with BatchNorm folded in."""
-        w = self.conv.weight.detach().float()
-        b = self.conv.bias.detach().float() if self.conv.bias is not None else torch.zeros(w.shape[0], device=w.device)
-        if hasattr(self, "bn"):
-            bn = self.bn
-            scale = bn.weight.detach().float() / torch.sqrt(bn.running_var.detach().float() + bn.eps)
-            w = w * scale[:, None, None, None]
-            b = (b - bn.running_mean.detach().float()) * scale + bn.bias.detach().float()
-        return w, b
+        return fold_bn(self.conv, getattr(self, "bn", None))
+
+    pair_signature = pair_signature
+
+    def out_shape(self, src):
+        return conv2d_shape(self.conv, src[1], src[2])
 
     def packed(self, plan, twin=None, also=(), twin_also=(), swap_halves=False, cin_slice=None, transform=None, cin_pad=None):
         """-> (wp, kp, bp), the launch form of this layer's weights: BN folded, `also` appended along Cout, the K halves swapped /
         the K columns cin_slice kept, `transform` (ops.s2d_conv_weight) applied, Cin padded to cin_pad, cast to plan.dtype; with
-        `twin` the two streams stacked.  Cached on self under a key derived from exactly these arguments: whoever asks for the same
-        packing gets the same tensor, and nobody spells a key."""
+        `twin` the two streams stacked.  Packed once per distinct set of arguments (HipModule.packed_convs, cached on self)."""
         assert len(twin_also) == (len(also) if twin is not None else 0)
-        key = ("pack", plan.dtype, plan.device, id(twin), tuple(map(id, also)), tuple(map(id, twin_also)), bool(swap_halves),
-               None if cin_slice is None else tuple(cin_slice), transform, cin_pad)
-
-        def make():
-            rows = []
-            for convs in [(self,) + tuple(also)] + ([(twin,) + tuple(twin_also)] if twin is not None else []):
-                ws, bs = zip(*(c.folded() for c in convs))
-                w, b = torch.cat(ws), torch.cat(bs)
-                if swap_halves:
-                    h = w.shape[1] // 2
-                    w = torch.cat((w[:, h:], w[:, :h]), 1)
-                if cin_slice is not None:
-                    w = w[:, cin_slice[0]:cin_slice[1]]
-                rows.append((w if transform is None else transform(w), b))
-            return ops.pack_streams(rows, plan.dtype, cin_pad)
-        return self._cached(key, make)
+        streams = [(self,) + tuple(also)] + ([(twin,) + tuple(twin_also)] if twin is not None else [])
+        return self.packed_convs(plan, [[(c.conv, getattr(c, "bn", None)) for c in convs] for convs in streams], swap_halves, cin_slice,
+                                 transform, cin_pad)
 
     def emit(self, plan, x, out=None, res=None, twin=None, also=(), twin_also=(), pre_term=None, swap_halves=False,
              chain=None, pre_nearest=False, cin_slice=None):
@@ -215,20 +282,10 @@ class Conv(HipModule):
                     out = plan.act(B, H // 2, W // 2, c2, pair=paired)
                 plan.add(ops.stem(x.t, wp, kp, bp, out, c2))
                 return out
+            x, c1 = stage_image(plan, x, c1, s2d)
+            wp, kp, bp = packed(transform=ops.s2d_conv_weight if s2d else None, cin_pad=c1)
             if s2d:                       # 6x6/s2/p2 over the image == 3x3/s1/p1 over space-to-depth(image)
-                cpad = -(-4 * c1 // vec) * vec
-                pre = plan.act(B, H // 2, W // 2, cpad, pair=paired)
-                plan.add(ops.preprocess_u8(x.t, pre, 1, x.c0, name="preprocess_u8_s2d") if x.u8
-                         else ops.preprocess(x.t, pre, 1, name="preprocess_s2d"))
-                wp, kp, bp = packed(transform=ops.s2d_conv_weight, cin_pad=cpad)
-                x, c1, (kh, kw, sh, sw, ph, pw) = pre, cpad, (3, 3, 1, 1, 1, 1)
-            else:
-                cpad = -(-c1 // vec) * vec
-                pre = plan.act(B, H, W, cpad, pair=paired)
-                plan.add(ops.preprocess_u8(x.t, pre, 0, x.c0, name="preprocess_u8_pad") if x.u8
-                         else ops.preprocess(x.t, pre, 0, name="preprocess_pad"))
-                wp, kp, bp = packed(cin_pad=cpad)
-                x, c1 = pre, cpad
+                kh, kw, sh, sw, ph, pw = 3, 3, 1, 1, 1, 1
         else:
             assert (x.dim() == 5) == paired
             if cin_slice is not None:
@@ -239,7 +296,7 @@ class Conv(HipModule):
                 raise NotImplementedError(f"channel count {c1} must be a multiple of {vec} for dtype {plan.dtype}")
             wp, kp, bp = packed()
         B, H, W = x.shape[-4:-1]
-        Ho, Wo = (H + 2 * ph - kh) // sh + 1, (W + 2 * pw - kw) // sw + 1
+        Ho, Wo = conv_out(H, kh, sh, ph), conv_out(W, kw, sw, pw)
         if out is None:
             out = plan.act(B, Ho, Wo, c2, pair=paired)
         ch = None
@@ -340,18 +397,25 @@ class VGGblock(HipModule):
     def convs(self):
         return [s[0] for s in self.vggblock if isinstance(s, nn.Sequential)]
 
+    def pair_signature(self):
+        """... and the plain torch modules behind the convolutions: the same activations, the same pool window."""
+        return pair_signature(self) + ([(type(c), getattr(c, "kernel_size", None), getattr(c, "stride", None), getattr(c, "padding", None))
+                                        for s in self.vggblock for c in (s if isinstance(s, nn.Sequential) else [s]) if not isinstance(c, nn.Conv2d)],)
+
+    def out_shape(self, src):                   # 3x3 / s1 / p1 convs keep the size, the closing pool halves it (floor)
+        k, s, p = pool_window(self.vggblock[-1])
+        return self.convs()[-1].out_channels, conv_out(src[1], k, s, p), conv_out(src[2], k, s, p)
+
+    @staticmethod
+    def _pack_stem(rows, dt, cin_pad):
+        """icaf_vgg_stem's form of the image-fed conv: w [64][32] per stream, bias fp32 [64]."""
+        ws, bs = [ops.vgg_stem_weight(w, dt) for w, _ in rows], [b.contiguous() for _, b in rows]
+        return (ws[0], 32, bs[0]) if len(rows) == 1 else (torch.stack(ws).contiguous(), 32, torch.stack(bs).contiguous())
+
     def _packed(self, plan, j, twin, cin_pad=None, stem=False):
-        """(wp, kp, bp) of conv j in its launch form (ops.pack_streams), or with stem=True (w [64][32], bias fp32 [64]) for icaf_vgg_stem;
-        with `twin` the two streams stacked."""
-        def make():
-            ks = [b.convs()[j] for b in ((self,) if twin is None else (self, twin))]
-            rows = [(k.weight.detach().float(), k.bias.detach().float()) for k in ks]
-            if not stem:
-                return ops.pack_streams(rows, plan.dtype, cin_pad)
-            ws = [ops.vgg_stem_weight(w, plan.dtype) for w, _ in rows]
-            bs = [b.contiguous() for _, b in rows]
-            return (ws[0], 32, bs[0]) if twin is None else (torch.stack(ws).contiguous(), 32, torch.stack(bs).contiguous())
-        return self._cached(("pack", plan.dtype, plan.device, j, id(twin), cin_pad, stem), make)
+        """(wp, kp, bp) of conv j in its launch form, or with stem=True in icaf_vgg_stem's; with `twin` the two streams stacked."""
+        blocks = (self,) if twin is None else (self, twin)
+        return self.packed_convs(plan, [[(b.convs()[j], None)] for b in blocks], cin_pad=cin_pad, pack=VGGblock._pack_stem if stem else None)
 
     def emit(self, plan, x, out=None, twin=None):
         paired = twin is not None
@@ -359,7 +423,6 @@ class VGGblock(HipModule):
         pool = self.vggblock[-1]
         if not isinstance(pool, nn.MaxPool2d) or pool.dilation not in (1, (1, 1)) or pool.ceil_mode:
             raise NotImplementedError("VGGblock ends with a plain nn.MaxPool2d")
-        pk, ps, pp = (v if isinstance(v, int) else v[0] for v in (pool.kernel_size, pool.stride, pool.padding))
         for s in list(self.vggblock)[:-1]:
             if not (isinstance(s, nn.Sequential) and len(s) == 2 and isinstance(s[0], nn.Conv2d) and isinstance(s[1], nn.ReLU)):
                 raise NotImplementedError("VGGblock rows are Sequential(Conv2d, ReLU): another activation is outside the hot path")
@@ -376,12 +439,8 @@ class VGGblock(HipModule):
                     plan.add(ops.vgg_stem(x.t, wp, bp, y, c0=x.c0 if x.u8 else 0))
                     x = y
                     continue
-                cpad = -(-c1 // vec) * vec
-                pre = plan.act(B, H, W, cpad, pair=paired)
-                plan.add(ops.preprocess_u8(x.t, pre, 0, x.c0, name="preprocess_u8_pad") if x.u8
-                         else ops.preprocess(x.t, pre, 0, name="preprocess_pad"))
-                wp, kp, bp = self._packed(plan, 0, twin, cin_pad=cpad)
-                x, c1 = pre, cpad
+                x, c1 = stage_image(plan, x, c1)
+                wp, kp, bp = self._packed(plan, 0, twin, cin_pad=c1)
             else:
                 assert (x.dim() == 5) == paired
                 if x.shape[-1] != c1:
@@ -393,31 +452,7 @@ class VGGblock(HipModule):
                 wp, kp, bp = self._packed(plan, j, twin)
             plan.add(ops.conv2d(x, wp, kp, bp, y, 3, 3, 1, 1, 1, 1, c1, c2, ops.ACT_RELU, name="vgg_conv3x3"))
             x = y
-        B, H, W, c2 = x.shape[-4:]
-        Ho, Wo = (H + 2 * pp - pk) // ps + 1, (W + 2 * pp - pk) // ps + 1
-        if out is None:
-            out = plan.act(B, Ho, Wo, c2, pair=paired)
-        if paired and out.stride(0) != B * out.stride(1):      # the streams are channel slices of one fusion buffer: one launch each
-            for g in range(2):
-                plan.add(ops.maxpool2d(x[g], out[g], pk, ps, pp, name="vgg_maxpool"))
-        else:
-            plan.add(ops.maxpool2d(x, out, pk, ps, pp, name="vgg_maxpool"))
-        return out
-
-
-def _fold_conv_bn(conv, bn):
-    """fp32 (weight, bias) of Conv2d + BatchNorm2d in eval mode — Conv.folded's arithmetic for a bare pair of torch modules."""
-    w = conv.weight.detach().float()
-    b = conv.bias.detach().float() if conv.bias is not None else torch.zeros(w.shape[0], device=w.device)
-    scale = bn.weight.detach().float() / torch.sqrt(bn.running_var.detach().float() + bn.eps)
-    return w * scale[:, None, None, None], (b - bn.running_mean.detach().float()) * scale + bn.bias.detach().float()
-
-
-def _pack_conv_bn(owner, plan, tag, pairs, cin_pad=None):
-    """(wp, kp, bp) of one (conv, bn) pair per stream in its launch form (ops.pack_streams), BatchNorm folded HERE, when the weights are
-    packed — the modules keep their BatchNorm, as the reference's fuse() leaves them (it only touches Conv).  Cached on `owner`."""
-    key = ("pack", plan.dtype, plan.device, tag, tuple(id(c) for c, _ in pairs), cin_pad)
-    return owner._cached(key, lambda: ops.pack_streams([_fold_conv_bn(c, b) for c, b in pairs], plan.dtype, cin_pad))
+        return emit_maxpool(plan, x, pool, out, "vgg_maxpool")
 
 
 class ResNetblock(HipModule):
@@ -468,24 +503,21 @@ class ResNetblock(HipModule):
         if c1 % vec or c2 % vec:
             raise NotImplementedError(f"channel counts {c1}, {c2} must be multiples of {vec} for dtype {plan.dtype}")
         blocks = (self,) if twin is None else (self, twin)
-        pack = lambda tag, get: _pack_conv_bn(self, plan, (tag, id(twin)), [get(b) for b in blocks])     # noqa: E731
+        # BatchNorm is folded HERE, when the weights are packed: the modules keep theirs, as the reference's fuse() leaves them (it only touches Conv)
+        pack = lambda k, bn: self.packed_convs(plan, [[(b.get_submodule(k), b.get_submodule(bn))] for b in blocks])     # noqa: E731
         B, H, W = x.shape[-4:-1]
-        Ho, Wo = (H + 2 - 3) // s + 1, (W + 2 - 3) // s + 1
+        Ho, Wo = conv_out(H, 3, s, 1), conv_out(W, 3, s, 1)
         t1 = plan.act(B, H, W, c2, pair=paired)
-        wp, kp, bp = pack("conv1", lambda b: (b.conv1, b.bn1))
-        plan.add(ops.conv2d(x, wp, kp, bp, t1, 1, 1, 1, 1, 0, 0, c1, c2, ops.ACT_RELU, name="resnet_conv1x1"))
+        plan.add(ops.conv2d(x, *pack("conv1", "bn1"), t1, 1, 1, 1, 1, 0, 0, c1, c2, ops.ACT_RELU, name="resnet_conv1x1"))
         t2 = plan.act(B, Ho, Wo, c2, pair=paired)
-        wp, kp, bp = pack("conv2", lambda b: (b.conv2, b.bn2))
-        plan.add(ops.conv2d(t1, wp, kp, bp, t2, 3, 3, s, s, 1, 1, c2, c2, ops.ACT_RELU, name=f"resnet_conv3x3s{s}"))
+        plan.add(ops.conv2d(t1, *pack("conv2", "bn2"), t2, 3, 3, s, s, 1, 1, c2, c2, ops.ACT_RELU, name=f"resnet_conv3x3s{s}"))
         res = x
         if len(self.shortcut):
             res = plan.act(B, Ho, Wo, c3, pair=paired)
-            wp, kp, bp = pack("shortcut", lambda b: (b.shortcut[0], b.shortcut[1]))
-            plan.add(ops.conv2d(x, wp, kp, bp, res, 1, 1, s, s, 0, 0, c1, c3, ops.ACT_NONE, name=f"resnet_shortcut1x1s{s}"))
+            plan.add(ops.conv2d(x, *pack("shortcut.0", "shortcut.1"), res, 1, 1, s, s, 0, 0, c1, c3, ops.ACT_NONE, name=f"resnet_shortcut1x1s{s}"))
         if out is None:
             out = plan.act(B, Ho, Wo, c3, pair=paired)
-        wp, kp, bp = pack("conv3", lambda b: (b.conv3, b.bn3))
-        plan.add(ops.conv2d(t2, wp, kp, bp, out, 1, 1, 1, 1, 0, 0, c2, c3, ops.ACT_RELU, res=res, res_pre_act=True, name="resnet_conv1x1+res"))
+        plan.add(ops.conv2d(t2, *pack("conv3", "bn3"), out, 1, 1, 1, 1, 0, 0, c2, c3, ops.ACT_RELU, res=res, res_pre_act=True, name="resnet_conv1x1+res"))
         return out
 
 
@@ -506,17 +538,19 @@ class ResNetlayer(HipModule):
             blk = [ResNetblock(c1, c2, stride)] + [ResNetblock(self.expansion * c2, c2, 1) for _ in range(num_blocks - 1)]
             self.layer = nn.Sequential(*blk)
 
-    def out_shape(self, H, W):
-        """(C, H', W') of this row's output for an H x W input."""
+    def pair_signature(self):
+        """... the same kind of row, and behind a stem's convolution the same plain torch modules (BatchNorm eps, ReLU, pool window)."""
+        return pair_signature(self) + (self.is_first, [(type(c), getattr(c, "eps", None), getattr(c, "kernel_size", None), getattr(c, "stride", None),
+                                                        getattr(c, "padding", None)) for c in self.layer if self.is_first and not isinstance(c, nn.Conv2d)])
+
+    def out_shape(self, src):                   # 7x7 / s2 / p3 + 3 / 2 / 1 pool for the stem row, the blocks' 3x3 strides otherwise (floor)
+        _, H, W = src
         if self.is_first:
-            k, pool = self.layer[0], self.layer[3]
-            (kh, kw), (sh, sw), (ph, pw) = k.kernel_size, k.stride, _pair(k.padding)
-            pk, ps, pp = (v if isinstance(v, int) else v[0] for v in (pool.kernel_size, pool.stride, pool.padding))
-            H, W = (H + 2 * ph - kh) // sh + 1, (W + 2 * pw - kw) // sw + 1
-            return k.out_channels, (H + 2 * pp - pk) // ps + 1, (W + 2 * pp - pk) // ps + 1
+            C, H, W = conv2d_shape(self.layer[0], H, W)
+            k, s, p = pool_window(self.layer[3])
+            return C, conv_out(H, k, s, p), conv_out(W, k, s, p)
         for b in self.layer:
-            s = b.conv2.stride[0]
-            H, W = (H + 2 - 3) // s + 1, (W + 2 - 3) // s + 1
+            H, W = conv_out(H, 3, b.conv2.stride[0], 1), conv_out(W, 3, b.conv2.stride[0], 1)
         return self.layer[-1].conv3.out_channels, H, W
 
     def emit(self, plan, x, out=None, twin=None):
@@ -535,36 +569,22 @@ class ResNetlayer(HipModule):
             raise NotImplementedError("the first ResNetlayer is Conv2d + BatchNorm2d + ReLU + a plain MaxPool2d")
         k, pool = mods[0], mods[3]
         (kh, kw), (sh, sw), (ph, pw) = k.kernel_size, k.stride, _pair(k.padding)
-        pk, ps, pp = (v if isinstance(v, int) else v[0] for v in (pool.kernel_size, pool.stride, pool.padding))
         vec = ops.VEC[plan.dtype]
         c1, c2 = k.in_channels, k.out_channels
         layers = (self,) if twin is None else (self, twin)
         if isinstance(x, ImageIn):
             assert x.pair == paired
-            B, _, H, W = x.shape
-            cpad = -(-c1 // vec) * vec
-            pre = plan.act(B, H, W, cpad, pair=paired)
-            plan.add(ops.preprocess_u8(x.t, pre, 0, x.c0, name="preprocess_u8_pad") if x.u8 else ops.preprocess(x.t, pre, 0, name="preprocess_pad"))
-            x, cin = pre, cpad
+            x, cin = stage_image(plan, x, c1)
         else:
             assert (x.dim() == 5) == paired
             if x.shape[-1] != c1 or c1 % vec:
                 raise ValueError(f"ResNetlayer stem expects {c1} input channels in whole {vec}-element vectors, got {x.shape[-1]}")
-            B, H, W = x.shape[-4:-1]
             cin = c1
-        wp, kp, bp = _pack_conv_bn(self, plan, ("stem", id(twin)), [(l.layer[0], l.layer[1]) for l in layers], cin_pad=cin)
-        Hc, Wc = (H + 2 * ph - kh) // sh + 1, (W + 2 * pw - kw) // sw + 1
-        y = plan.act(B, Hc, Wc, c2, pair=paired)
+        wp, kp, bp = self.packed_convs(plan, [[(l.layer[0], l.layer[1])] for l in layers], cin_pad=cin)
+        _, Hc, Wc = conv2d_shape(k, *x.shape[-3:-1])
+        y = plan.act(x.shape[-4], Hc, Wc, c2, pair=paired)
         plan.add(ops.conv2d(x, wp, kp, bp, y, kh, kw, sh, sw, ph, pw, cin, c2, ops.ACT_RELU, name=f"resnet_stem{kh}x{kw}s{sh}"))
-        Ho, Wo = (Hc + 2 * pp - pk) // ps + 1, (Wc + 2 * pp - pk) // ps + 1
-        if out is None:
-            out = plan.act(B, Ho, Wo, c2, pair=paired)
-        if paired and out.stride(0) != B * out.stride(1):      # the streams are channel slices of one buffer: one launch each
-            for g in range(2):
-                plan.add(ops.maxpool2d(y[g], out[g], pk, ps, pp, name="resnet_maxpool"))
-        else:
-            plan.add(ops.maxpool2d(y, out, pk, ps, pp, name="resnet_maxpool"))
-        return out
+        return emit_maxpool(plan, y, pool, out, "resnet_maxpool")
 
 
 class Bottleneck(HipModule):
@@ -630,6 +650,11 @@ class C3(HipModule):
         self.cv3 = Conv(2 * c_, c2, 1)
         self.m = nn.Sequential(*[Bottleneck(c_, c_, shortcut, g, e=1.0) for _ in range(n)])
 
+    pair_signature = pair_signature
+
+    def out_shape(self, src):
+        return self.cv3.conv.out_channels, src[1], src[2]
+
     fuse_cv3 = True      # n = 1, c_ = 32: Bottleneck + cv3 as one launch (icaf_bottleneck with a chained cv3)
     chain_bottlenecks = True     # n > 1: a Bottleneck's 3x3 (+ shortcut) and the next Bottleneck's 1x1 as one launch
 
@@ -643,12 +668,10 @@ class C3(HipModule):
             x = vcat.other
         if lead is not None and len(lead) == 4:        # (Conv, twin, stem, stem twin): x is the image pair itself
             B, _, H, W = x.shape
-            H, W = (H // 2 - 1) // 2 + 1, (W // 2 - 1) // 2 + 1
+            H, W = conv_out(H // 2, 3, 2, 1), conv_out(W // 2, 3, 2, 1)          # behind the 6x6 / s2 stem, then the 3x3 / s2 Conv
         elif lead is not None:
-            k = lead[0].conv
             B = x.shape[-4]
-            H = (x.shape[-3] + 2 * k.padding[0] - k.kernel_size[0]) // k.stride[0] + 1
-            W = (x.shape[-2] + 2 * k.padding[1] - k.kernel_size[1]) // k.stride[1] + 1
+            _, H, W = conv2d_shape(lead[0].conv, *x.shape[-3:-1])
         else:
             B, H, W = x.shape[-4:-1]
         c_ = self.cv1.conv.out_channels
@@ -722,10 +745,15 @@ class SPPF(HipModule):
         self.cv2 = Conv(c_ * 4, c2, 1, 1)
         self.m = nn.MaxPool2d(kernel_size=k, stride=1, padding=k // 2)
 
+    pair_signature = pair_signature
+
+    def out_shape(self, src):
+        return self.cv2.conv.out_channels, src[1], src[2]
+
     def emit(self, plan, x, out=None, twin=None):
         B, H, W = x.shape[-4:-1]
         c_ = self.cv1.conv.out_channels
-        k = self.m.kernel_size if isinstance(self.m.kernel_size, int) else self.m.kernel_size[0]
+        k = pool_window(self.m)[0]
         paired = twin is not None
         cat = plan.act(B, H, W, 4 * c_, pair=paired)
         self.cv1.emit(plan, x, out=cat[..., :c_], twin=twin.cv1 if paired else None)
@@ -751,6 +779,9 @@ class Concat(HipModule):
         super().__init__()
         self.d = dimension
 
+    def out_shape(self, srcs):
+        return sum(t[0] for t in srcs), srcs[0][1], srcs[0][2]
+
     def emit(self, plan, xs, out=None):
         if self.d != 1:
             raise NotImplementedError("only channel concatenation is on the hot path")
@@ -774,6 +805,9 @@ class Add(HipModule):
         super().__init__()
         self.w = weight
 
+    def out_shape(self, srcs):
+        return srcs[0]
+
     def emit(self, plan, xs, out=None):
         a, b = xs
         if out is None:
@@ -793,10 +827,12 @@ class NiNfusion(HipModule):
         self.act = nn.SiLU()
 
     # the packed-weight / launch logic is Conv's (a Conv without .bn and without bias)
-    folded = Conv.folded
     packed = Conv.packed
     _act_code = Conv._act_code
     fuse_stem = False
+
+    def out_shape(self, srcs):
+        return conv2d_shape(self.conv, srcs[0][1], srcs[0][2])
 
     def emit(self, plan, xs, out=None):
         x = self.concat.emit(plan, list(xs))
@@ -1052,6 +1088,7 @@ class TransformerFusionBlock(HipModule):
 
     # class-level (not set in __init__): instances un-pickled from reference checkpoints never ran this __init__
     fuse_tail = True         # run interpolate + residual + cat + conv1x1_out as one GEMM when the layout allows
+    out_shape = Add.out_shape
 
     def __init__(self, d_model, vert_anchors=16, horz_anchors=16, h=8, block_exp=4, n_layer=1, embd_pdrop=0.1,
                  attn_pdrop=0.1, resid_pdrop=0.1, loops_num=1):
@@ -1128,6 +1165,9 @@ class Detect(HipModule):
     # 16-bit plans: a level's 1x1 conv and its decode run as ONE launch (icaf_detect_conv; ICAF_DETECT_FUSE=0: A/B switch).  A class
     # default: un-pickled reference checkpoints never run this constructor.
     fuse_decode = OPT.detect_fuse
+
+    def out_shape(self, srcs):       # (z, logits, raws): nothing downstream reads a shape
+        return None
 
     def __init__(self, nc=80, anchors=(), ch=()):
         super().__init__()

@@ -149,8 +149,6 @@ def emit_any(m, plan, src, out=None, twin=None, lead=None):
     same row of the other backbone stream when both run as one paired launch sequence."""
     if isinstance(m, nn.Upsample):
         return emit_upsample(m, plan, src, out=out)
-    if isinstance(m, Detect):
-        return m.emit(plan, src)
     if isinstance(m, nn.Sequential):
         mods = list(m)
         for j, sub in enumerate(mods):
@@ -158,38 +156,30 @@ def emit_any(m, plan, src, out=None, twin=None, lead=None):
         return src
     if not hasattr(m, "emit"):
         raise NotImplementedError(f"layer type {type(m).__name__} is outside the hot path")
-    kw = {}
-    if twin is not None:
-        kw["twin"] = twin
-    if lead is not None:
-        kw["lead"] = lead
-    return m.emit(plan, src, out=out, **kw)
+    return m.emit(plan, src, **{k: v for k, v in (("out", out), ("twin", twin), ("lead", lead)) if v is not None})
 
 
-PAIRABLE = (Conv, C3, SPPF, VGGblock, ResNetlayer)
+def out_shape_any(m, src):
+    """(C, H, W) one yaml row makes of its source shape(s): the row's own rule (`out_shape`), torch's nn.Upsample, an nn.Sequential repeat."""
+    if isinstance(m, nn.Upsample):
+        s = int(m.scale_factor)
+        return src[0], src[1] * s, src[2] * s
+    if isinstance(m, nn.Sequential):
+        for sub in m:
+            src = out_shape_any(sub, src)
+        return src
+    if not hasattr(m, "out_shape"):
+        raise NotImplementedError(f"layer type {type(m).__name__} is outside the hot path")
+    return m.out_shape(src)
 
 
 def _same_structure(a, b):
+    """May rows a and b run as one groups = 2 launch sequence?  Same type, and equal in everything the type says must match."""
     if type(a) is not type(b):
         return False
     if isinstance(a, nn.Sequential):
         return len(a) == len(b) and all(_same_structure(x, y) for x, y in zip(a, b))
-    if not isinstance(a, PAIRABLE):
-        return False
-    sa, sb = a.state_dict(), b.state_dict()
-    if list(sa) != list(sb) or any(sa[k].shape != sb[k].shape for k in sa):
-        return False
-    geo = lambda m: [(c.kernel_size, c.stride, c.padding, c.groups) for c in m.modules() if isinstance(c, nn.Conv2d)]  # noqa: E731
-    acts = lambda m: [type(c.act) for c in m.modules() if isinstance(c, Conv)]                                       # noqa: E731
-    # a VGGblock's activations and pool are plain torch modules of its `vggblock`: same kinds, same window
-    tail = lambda m: [(type(c), getattr(c, "kernel_size", None), getattr(c, "stride", None), getattr(c, "padding", None))      # noqa: E731
-                      for v in m.modules() if isinstance(v, VGGblock) for s in v.vggblock for c in (s if isinstance(s, nn.Sequential) else [s])
-                      if not isinstance(c, nn.Conv2d)]
-    # a ResNetlayer's stem row: the same flag, and the same plain torch modules (BatchNorm eps, ReLU, pool window) behind the convolution
-    stem = lambda m: [(v.is_first,) + tuple((type(c), getattr(c, "eps", None), getattr(c, "kernel_size", None), getattr(c, "stride", None),  # noqa: E731
-                                             getattr(c, "padding", None)) for c in v.layer if v.is_first and not isinstance(c, nn.Conv2d))
-                      for v in m.modules() if isinstance(v, ResNetlayer)]
-    return geo(a) == geo(b) and acts(a) == acts(b) and tail(a) == tail(b) and stem(a) == stem(b)
+    return hasattr(a, "pair_signature") and a.pair_signature() == b.pair_signature()
 
 
 class Model(HipModule):
@@ -275,17 +265,12 @@ class Model(HipModule):
         They ARE the cached plans of those shapes and slots (a plain forward at 544 x 544 replays the plan a 640 x 640 TTA step uses for
         its 0.83 pass): as with plan_for, two users of one slot must not be in flight at the same time."""
         gs = int(self.stride.max())
-        if H % gs or W % gs:
-            raise ValueError(f"input size {H}x{W} must be a multiple of the max stride {gs}")
+        self._check_stride(H, W, gs)
         min_h, min_w = self.tta_min_size()
         if H < min_h or W < min_w:
             raise ValueError(f"test-time augmentation needs an input of at least {min_h}x{min_w}, got {H}x{W}: the "
                              f"{min(TTA_SCALES)} pass must not hand a DMFF block a map smaller than its anchor grid")
-        dt = dtype or self.compute_dtype or next(self.parameters()).dtype
-        device = torch.device(device)
-        if device.type == "cuda" and device.index is None:
-            device = torch.device("cuda", torch.cuda.current_device())
-        key = (B, H, W, dt, device, "tta") + (("u8",) if u8 else ()) + (("slot", slot) if slot else ()) + (() if branches else ("chain",))
+        dt, device, key = self._plan_key(B, H, W, device, dtype, u8, slot, branches, tta=True)
         plans = self.__dict__.setdefault("_plans", {})
         tp = plans.pop(key, None)
         if tp is None:
@@ -310,21 +295,7 @@ class Model(HipModule):
 
     def _forward_augment(self, x, x2=None):
         """x, x2: the fp image pair, or x alone: the uint8 (B, 6, H, W) batch."""
-        if self.training:
-            raise NotImplementedError("icafusion_amd implements the eval-mode inference path only (call .eval())")
-        u8 = x2 is None
-        if not (x.is_cuda and (u8 or x2.is_cuda)):
-            raise RuntimeError("icafusion_amd.Model runs on the MI355X only: move the model and inputs to cuda "
-                               "(no CPU fallback exists; the CPU reference is oracle/icaf_oracle.py, test-only)")
-        if not u8 and x.shape != x2.shape:
-            raise ValueError(f"RGB and IR batches must match, got {tuple(x.shape)} vs {tuple(x2.shape)}")
-        B, _, H, W = x.shape
-        tp = self.tta_plan_for(B, H, W, x.device, u8=u8)
-        for dst, t in zip(tp.inputs, (x,) if u8 else (x, x2)):
-            if t.data_ptr() != dst.data_ptr():
-                dst.copy_(t)
-        tp.run()
-        return (tp.outputs if self.static_outputs else tp.outputs.clone()), None
+        return self._forward_images((x,) if x2 is None else (x, x2), u8=x2 is None, augment=True)
 
     def fuse(self):
         """Fold BatchNorm into the convs in place (reference models/yolo_test.py:182-190).  A VGGblock has none: nothing to fold.  A
@@ -344,60 +315,28 @@ class Model(HipModule):
     # -- plan construction ------------------------------------------------------------------------------------
     def _layer_shapes(self, B, H, W):
         """Static (C, H, W) of every layer output, needed to place Concat inputs before they are produced."""
-        shapes, cur = [], None
+        shapes = []
         for m in self.model:
-            f = m.f
-            if f == -4 or (f == -1 and m.i == 0):
-                src = (3, H, W)
-            elif f == -1:
-                src = cur
-            elif isinstance(f, int):
-                src = shapes[f]
-            else:
-                src = [cur if j == -1 else shapes[j] for j in f]
-            if isinstance(m, Conv):
-                k, s, p = m.conv.kernel_size[0], m.conv.stride[0], m.conv.padding[0]
-                cur = (m.conv.out_channels, (src[1] + 2 * p - k) // s + 1, (src[2] + 2 * p - k) // s + 1)
-            elif isinstance(m, (C3,)):
-                cur = (m.cv3.conv.out_channels, src[1], src[2])
-            elif isinstance(m, SPPF):
-                cur = (m.cv2.conv.out_channels, src[1], src[2])
-            elif isinstance(m, VGGblock):               # 3x3 / s1 / p1 convs keep the size, the closing pool halves it (floor)
-                pool = m.vggblock[-1]
-                k, s_, p = (v if isinstance(v, int) else v[0] for v in (pool.kernel_size, pool.stride, pool.padding))
-                cur = (m.convs()[-1].out_channels, (src[1] + 2 * p - k) // s_ + 1, (src[2] + 2 * p - k) // s_ + 1)
-            elif isinstance(m, ResNetlayer):            # 7x7 / s2 / p3 + 3 / 2 / 1 pool for the stem row, the blocks' 3x3 strides otherwise (floor)
-                cur = m.out_shape(src[1], src[2])
-            elif isinstance(m, nn.Upsample):
-                s = int(m.scale_factor)
-                cur = (src[0], src[1] * s, src[2] * s)
-            elif isinstance(m, Concat):
-                cur = (sum(t[0] for t in src), src[0][1], src[0][2])
-            elif isinstance(m, (TransformerFusionBlock, Add)):
-                cur = src[0]
-            elif isinstance(m, NiNfusion):
-                k, s_, p = m.conv.kernel_size[0], m.conv.stride[0], m.conv.padding[0]
-                cur = (m.conv.out_channels, (src[0][1] + 2 * p - k) // s_ + 1, (src[0][2] + 2 * p - k) // s_ + 1)
-            elif isinstance(m, Detect):
-                cur = None
-            else:
-                raise NotImplementedError(f"layer type {type(m).__name__} is outside the hot path")
-            shapes.append(cur)
+            shapes.append(out_shape_any(m, self._source(m, (3, H, W), (3, H, W), shapes)))
         return shapes
+
+    @staticmethod
+    def _source(m, rgb, ir, outs):
+        """What row m reads, by its `from`: the RGB / IR network input, the previous row's output, one earlier row's or a list of them."""
+        if m.f == -4 or (m.f == -1 and m.i == 0):
+            return ir if m.f == -4 else rgb
+        prev = outs[-1] if outs else None
+        return prev if m.f == -1 else outs[m.f] if isinstance(m.f, int) else [prev if j == -1 else outs[j] for j in m.f]
 
     def stream_twins(self):
         """{IR-stream row -> RGB-stream row} for the leading run of rows that are pure chains (from = -1) with
         identical structure in both backbones.  Those rows run as ONE launch sequence over pair acts
         (groups = 2: per-stream weights, gridDim.z = stream): half the launches, twice the workgroups each."""
-        if not self.pair_streams:
-            return {}
         ir0 = next((m.i for m in self.model if m.f == -4), None)
         twins = {}
-        if ir0 is None or self.model[0].f != -1:
+        if not self.pair_streams or ir0 is None or self.model[0].f != -1:
             return twins
-        for k in range(ir0):
-            if ir0 + k >= len(self.model):
-                break
+        for k in range(min(ir0, len(self.model) - ir0)):
             a, b = self.model[k], self.model[ir0 + k]
             if a.f != -1 or b.f != (-4 if k == 0 else -1) or not _same_structure(a, b):
                 break
@@ -407,50 +346,74 @@ class Model(HipModule):
     def build_plan(self, B, H, W, device, dtype, u8=False):
         """u8=False: inputs are two fp32 NCHW images in [0, 1] (what the reference hands `model(img_rgb, img_ir)`);
         u8=True: ONE uint8 (B, 6, H, W) tensor, the dataloader's RGB+IR batch — `/255`, the channel split and the cast
-        happen in the staging kernel (reference test.py:116-123)."""
+        happen in the staging kernel (reference test.py:116-123).
+        A sequence of passes; plan-owned buffers are allocated in this order: inputs, concat buffers, DMFF pair buffers (each in row
+        order), then whatever emission allocates."""
         plan = Plan(device, dtype)
-        if u8:
-            img6 = torch.zeros((B, 6, H, W), dtype=torch.uint8, device=device)
-            plan.inputs, plan.input_pair = [img6], None
-            in_pair, in_rgb, in_ir = ImageIn(img6, 0, pair=True), ImageIn(img6, 0), ImageIn(img6, 3)
-        else:
-            imgs = torch.zeros((2, B, 3, H, W), dtype=torch.float32, device=device)   # RGB and IR staging, adjacent
-            plan.inputs, plan.input_pair = [imgs[0], imgs[1]], imgs     # input_pair: both as one (2, B, 3, H, W) tensor
-            in_pair, in_rgb, in_ir = ImageIn(imgs), ImageIn(imgs[0]), ImageIn(imgs[1])
+        images = self._plan_inputs(plan, B, H, W, u8)
         shapes = self._layer_shapes(B, H, W)
-        # nn.Upsample -> Concat([-1, j]) -> C3 (head rows 24-26, 28-30): the C3's first 1x1 commutes with the nearest
-        # up-sampling, so neither the up-sampled tensor nor the concat buffer is materialised (C3.emit, VirtualCat)
-        virtual = {}                                # Concat row -> Upsample row
-        if self.fold_upsample:
-            used = {}
-            for m in self.model:
-                for j in ([m.f] if isinstance(m.f, int) else m.f):
-                    used.setdefault(m.i - 1 if j == -1 else j, []).append(m.i)
-            for m in self.model:
-                nxt = self.model[m.i + 1] if m.i + 1 < len(self.model) else None
-                nx2 = self.model[m.i + 2] if m.i + 2 < len(self.model) else None
-                if (isinstance(m, nn.Upsample) and m.f == -1 and m.i > 0 and m.mode == "nearest" and m.scale_factor is not None
-                        and float(m.scale_factor) == int(m.scale_factor) and isinstance(nxt, Concat) and nxt.d == 1
-                        and not isinstance(nxt.f, int) and len(nxt.f) == 2 and nxt.f[0] == -1 and isinstance(nxt.f[1], int)
-                        and nxt.f[1] >= 0 and isinstance(nx2, C3) and nx2.f == -1 and used.get(m.i) == [nxt.i]
-                        and used.get(nxt.i) == [nx2.i]):
-                    virtual[nxt.i] = m.i
-        # Concat placement: producer layer index -> (concat buffer, channel offset)
-        placement, cat_bufs = {}, {}
+        virtual = self._upsample_folds()
+        placement = self._place_concats(plan, B, shapes, virtual)
+        dmff_pair = self._pair_dmff_inputs(plan, B, shapes, placement)
+        twins = self._twin_run(placement)
+        spans = self._emit_rows(plan, images, virtual, placement, dmff_pair, twins)
+        if self.branch_dmff:
+            self._assign_branches(plan, spans)
+        return plan
+
+    @staticmethod
+    def _plan_inputs(plan, B, H, W, u8):
+        """Allocates the staging buffer(s) and sets plan.inputs / plan.input_pair -> (both streams, RGB, IR) as ImageIn."""
+        if u8:
+            img6 = torch.zeros((B, 6, H, W), dtype=torch.uint8, device=plan.device)
+            plan.inputs, plan.input_pair = [img6], None
+            return ImageIn(img6, 0, pair=True), ImageIn(img6, 0), ImageIn(img6, 3)
+        imgs = torch.zeros((2, B, 3, H, W), dtype=torch.float32, device=plan.device)   # RGB and IR staging, adjacent
+        plan.inputs, plan.input_pair = [imgs[0], imgs[1]], imgs     # input_pair: both as one (2, B, 3, H, W) tensor
+        return ImageIn(imgs), ImageIn(imgs[0]), ImageIn(imgs[1])
+
+    def _row(self, i):
+        return self.model[i] if i < len(self.model) else None
+
+    def _upsample_folds(self):
+        """Reads the yaml rows -> {Concat row: Upsample row} of every nn.Upsample -> Concat([-1, j]) -> C3 run (head rows 24-26, 28-30) when
+        `fold_upsample` is set: the C3's first 1x1 commutes with the nearest up-sampling, so neither the up-sampled tensor nor the concat
+        buffer is materialised (C3.emit, VirtualCat)."""
+        virtual, used = {}, {}
+        if not self.fold_upsample:
+            return virtual
+        for m in self.model:
+            for j in ([m.f] if isinstance(m.f, int) else m.f):
+                used.setdefault(m.i - 1 if j == -1 else j, []).append(m.i)
+        for m in self.model:
+            nxt, nx2 = self._row(m.i + 1), self._row(m.i + 2)
+            if (isinstance(m, nn.Upsample) and m.f == -1 and m.i > 0 and m.mode == "nearest" and m.scale_factor is not None
+                    and float(m.scale_factor) == int(m.scale_factor) and isinstance(nxt, Concat) and nxt.d == 1
+                    and not isinstance(nxt.f, int) and len(nxt.f) == 2 and nxt.f[0] == -1 and isinstance(nxt.f[1], int)
+                    and nxt.f[1] >= 0 and isinstance(nx2, C3) and nx2.f == -1 and used.get(m.i) == [nxt.i]
+                    and used.get(nxt.i) == [nx2.i]):
+                virtual[nxt.i] = m.i
+        return virtual
+
+    def _place_concats(self, plan, B, shapes, virtual):
+        """Reads the Concat rows that are not folded away (`virtual`); allocates one buffer per Concat, in row order -> {producer row:
+        (concat buffer, channel offset, channels)}: the producers write their slice of it."""
+        placement = {}
         for m in self.model:
             if isinstance(m, Concat) and not isinstance(m.f, int) and m.i not in virtual:
                 srcs = [m.i - 1 if j == -1 else j for j in m.f]
                 if any(s in placement for s in srcs):
                     continue                       # a producer can live in only one concat buffer
                 C, h, w = shapes[m.i]
-                buf = plan.act(B, h, w, C)
-                cat_bufs[m.i] = buf
-                off = 0
+                buf, off = plan.act(B, h, w, C), 0
                 for s in srcs:
                     placement[s] = (buf, off, shapes[s][0])
                     off += shapes[s][0]
-        # DMFF inputs: the RGB and IR feature maps a TransformerFusionBlock reads are placed as adjacent channel slices
-        # of one (B, H, W, 2C) buffer, so its 1x1 fuse conv can read cat(rgb, ir) in place (common.py, fused tail)
+        return placement
+
+    def _pair_dmff_inputs(self, plan, B, shapes, placement):
+        """Reads the fusion rows and `placement`; allocates one (B, H, W, 2C) buffer per row whose two inputs are free, in row order -> {input row:
+        (buffer, channel offset, C, the other input row)}: adjacent channel slices, so the 1x1 fuse conv reads cat(rgb, ir) in place (common.py)."""
         dmff_pair = {}
         for m in self.model:
             if (isinstance(m, NiNfusion) or (isinstance(m, TransformerFusionBlock) and m.fuse_tail)) \
@@ -461,170 +424,166 @@ class Model(HipModule):
                 C, h, w = shapes[i]
                 buf = plan.act(B, h, w, 2 * C)
                 dmff_pair[i], dmff_pair[j] = (buf, 0, C, j), (buf, C, C, i)
-        twins = self.stream_twins()                 # a prefix run by construction; cut it at the first row that a
-        ir0 = min(twins) if twins else None         # Concat placement pins to another buffer
-        run = 0
+        return dmff_pair
+
+    def _twin_run(self, placement):
+        """stream_twins() — a prefix run by construction — cut at the first row that a Concat placement pins to another buffer."""
+        twins = self.stream_twins()
+        ir0, run = min(twins, default=None), 0
         while ir0 is not None and (ir0 + run) in twins and run not in placement and (ir0 + run) not in placement:
             run += 1
-        twins = {ir0 + k: k for k in range(run)}
-        rgb_rows = set(twins.values())
-        pair_out = {}
-        pending_stem = None
-        pending_lead = {}                           # C3 row -> ((Conv, twin Conv), conv input): rows fused into one launch
-        y, x = [], None
-        last_launch = {}                            # yaml row -> index of its last launch
+        return {ir0 + k: k for k in range(run)}
+
+    def _emit_rows(self, plan, images, virtual, placement, dmff_pair, twins):
+        """Reads the maps of the passes above; appends every row's launches to `plan` in yaml order (a twin run's IR rows with their RGB
+        rows) and sets plan.outputs -> {row: (its first launch, the end of its launches, emitted on its own)}."""
+        in_pair, in_rgb, in_ir = images
+        ir0, rgb_rows = min(twins, default=None), set(twins.values())
+        y, spans, pair_out, lead = [], {}, {}, {}
+
+        def done(x, *rows, own=False):              # every exit of the row loop: the row's output, and whose launches these were
+            y.append(x)
+            for r in rows:
+                spans[r] = (n0, len(plan.launches), own)
+        for m in self.model:
+            n0 = len(plan.launches)
+            if m.i in rgb_rows:                     # both streams in one paired launch sequence
+                po = pair_out[m.i] = self._emit_twin_row(plan, m, in_pair if m.i == 0 else pair_out[m.i - 1], ir0, rgb_rows, lead, dmff_pair)
+                done(None if po is None else po[0], m.i, ir0 + m.i)
+            elif m.i in twins:                      # already emitted with its RGB twin
+                po = pair_out[twins[m.i]]
+                done(None if po is None else po[1])
+            else:
+                x = self._emit_own_row(plan, m, self._source(m, in_rgb, in_ir, y), virtual, placement, dmff_pair)
+                done(x, m.i, own=m.i not in virtual and virtual.get(m.i + 1) != m.i)
+        plan.outputs = y[-1]
+        return spans
+
+    @staticmethod
+    def _defer(lead, row, convs, src):
+        """This row launches nothing: `convs` (with their input `src`) are emitted inside the launch of `row`, which pops them from `lead`."""
+        lead[row] = (convs, src)
+
+    def _emit_twin_row(self, plan, m, src, ir0, rgb_rows, lead, dmff_pair):
+        """RGB row m and its IR twin as one launch sequence over the pair act / image pair `src` -> their pair act, or None when the row
+        is deferred into a later row's launch (`lead`: {that row: (the Convs in front of it, their input)})."""
+        i, twin, nxt, nx2 = m.i, self.model[ir0 + m.i], self._row(m.i + 1), self._row(m.i + 2)
+        if (i == 0 and isinstance(m, Conv) and isinstance(nx2, C3) and {1, 2} <= rgb_rows and nxt.f == -1
+                and nx2.f == -1 and not ({0, 1, ir0, ir0 + 1} & (set(self.save) | set(dmff_pair)))
+                and m.stem2_ok(plan, src, nxt, nx2)):
+            return self._defer(lead, 1, (m, twin), src)              # rows 0-2a become one launch, emitted with the C3 row
+        if i == 1 and 1 in lead:                                     # ... the 3x3 behind that stem
+            stem, image = lead.pop(1)
+            return self._defer(lead, 2, (m, twin) + stem, image)
+        if (isinstance(m, Conv) and i > 0 and isinstance(nxt, C3) and (i + 1) in rgb_rows and nxt.f == -1
+                and i not in self.save and (ir0 + i) not in self.save and i not in dmff_pair
+                and m.chain_ok(plan, nxt)):
+            return self._defer(lead, i + 1, (m, twin), src)          # a down-sampling Conv, emitted together with the C3 row
+        convs, src = lead.pop(i, (None, src))
+        pout = None
+        if i in dmff_pair and dmff_pair[i][3] == ir0 + i:            # pair act = the two halves of the DMFF buffer
+            buf, _, c, _ = dmff_pair[i]
+            Bb, h, w, _ = buf.shape
+            pout = buf.as_strided((2, Bb, h, w, c), (c, h * w * 2 * c, w * 2 * c, 2 * c, 1))
+        return emit_any(m, plan, src, pout, twin=twin, lead=convs)
+
+    @staticmethod
+    def _emit_own_row(plan, m, src, virtual, placement, dmff_pair):
+        """A row outside the twin run, from its source(s) `src` -> its output: written into its slice of a concat / DMFF pair buffer where
+        one is placed; a folded Upsample / Concat row launches nothing and returns a description for the C3 behind it."""
+        if virtual.get(m.i + 1) == m.i:                              # the Upsample row of a fold
+            return src, int(m.scale_factor)
+        if m.i in virtual:                                           # its Concat: a description of cat(up(low), other)
+            (low, scale), other = src
+            return VirtualCat(low, scale, other)
+        buf, off, c = (placement.get(m.i) or dmff_pair.get(m.i) or (None, 0, 0))[:3]
+        return emit_any(m, plan, src, None if buf is None else buf[..., off:off + c])
+
+    def _assign_branches(self, plan, spans):
+        """Reads the rows' launch ranges (`spans`, _emit_rows); tags launches with graph-branch ids and fills plan.branches.  DMFF blocks other
+        than the last one become side branches of the captured graph: they depend only on their two backbone rows and nothing needs them before
+        the head, so they overlap with the deeper backbone rows and are joined before the first head launch.  Detect levels fed by earlier head
+        rows (P3, P4) only need that row: their 1x1 conv + decode run beside the remaining head rows and are joined at the end of the graph."""
+        def branch(first, end, after, row):
+            bid = len(plan.branches) + 1
+            for l in plan.launches[first:end]:
+                l.branch = bid
+            plan.branches[bid] = {"after": after, "join_before": None, "row": row}
         dmff_rows = [m.i for m in self.model if isinstance(m, (TransformerFusionBlock, NiNfusion, Add))]
         for m in self.model:
-            f = m.f
-            n_before = len(plan.launches)
-            if m.i in rgb_rows:                     # both streams in one paired launch sequence
-                src = in_pair if m.i == 0 else pair_out[m.i - 1]
-                nxt = self.model[m.i + 1] if m.i + 1 < len(self.model) else None
-                nx2 = self.model[m.i + 2] if m.i + 2 < len(self.model) else None
-                if (m.i == 0 and isinstance(m, Conv) and isinstance(nx2, C3) and {1, 2} <= rgb_rows and nxt.f == -1
-                        and nx2.f == -1 and not ({0, 1, ir0, ir0 + 1} & (set(self.save) | set(dmff_pair)))
-                        and m.stem2_ok(plan, src, nxt, nx2)):
-                    pending_stem = (m, self.model[ir0])             # rows 0-2a become one launch, emitted with the C3 row
-                    pair_out[0] = None
-                    y.append(None)
-                    last_launch[0] = last_launch[ir0] = len(plan.launches) - 1
-                    continue
-                if m.i == 1 and pending_stem is not None:
-                    pending_lead[2] = ((m, self.model[ir0 + 1]) + pending_stem, in_pair)
-                    pending_stem = None
-                    pair_out[1] = None
-                    y.append(None)
-                    last_launch[1] = last_launch[ir0 + 1] = len(plan.launches) - 1
-                    continue
-                if (isinstance(m, Conv) and m.i > 0 and isinstance(nxt, C3) and (m.i + 1) in rgb_rows and nxt.f == -1
-                        and m.i not in self.save and (ir0 + m.i) not in self.save and m.i not in dmff_pair
-                        and m.chain_ok(plan, nxt)):
-                    pending_lead[m.i + 1] = ((m, self.model[ir0 + m.i]), src)      # emitted together with the C3 row
-                    pair_out[m.i] = None
-                    y.append(None)
-                    last_launch[m.i] = last_launch[ir0 + m.i] = len(plan.launches) - 1
-                    continue
-                lead = None
-                if m.i in pending_lead:
-                    lead, src = pending_lead.pop(m.i)
-                pout = None
-                if m.i in dmff_pair and dmff_pair[m.i][3] == ir0 + m.i:       # pair act = the two halves of the DMFF buffer
-                    buf, _, c, _ = dmff_pair[m.i]
-                    Bb, h, w, _ = buf.shape
-                    pout = buf.as_strided((2, Bb, h, w, c), (c, h * w * 2 * c, w * 2 * c, 2 * c, 1))
-                pair_out[m.i] = emit_any(m, plan, src, pout, twin=self.model[ir0 + m.i], lead=lead)
-                x = pair_out[m.i][0]
-                y.append(x)
-                last_launch[m.i] = last_launch[ir0 + m.i] = len(plan.launches) - 1
+            f, (n0, n1, own) = m.f, spans[m.i]
+            if not own:
                 continue
-            if m.i in twins:                        # already emitted with its RGB twin
-                po = pair_out[twins[m.i]]
-                x = po[1] if po is not None else None
-                y.append(x)
-                continue
-            if f == -4:
-                src = in_ir
-            elif f == -1:
-                src = in_rgb if m.i == 0 else x
-            elif isinstance(f, int):
-                src = y[f]
-            else:
-                src = [x if j == -1 else y[j] for j in f]
-            if m.i + 1 in virtual and virtual[m.i + 1] == m.i:          # the Upsample row: nothing to launch
-                x = (src, int(m.scale_factor))
-                y.append(x)
-                last_launch[m.i] = len(plan.launches) - 1
-                continue
-            if m.i in virtual:                                          # its Concat: a description of cat(up(low), other)
-                (low, scale), other = src
-                x = VirtualCat(low, scale, other)
-                y.append(x)
-                last_launch[m.i] = len(plan.launches) - 1
-                continue
-            out = None
-            if m.i in placement:
-                buf, off, c = placement[m.i]
-                out = buf[..., off:off + c]
-            elif m.i in dmff_pair:
-                buf, off, c, _ = dmff_pair[m.i]
-                out = buf[..., off:off + c]
-            x = emit_any(m, plan, src, out)
-            y.append(x)
-            last_launch[m.i] = len(plan.launches) - 1
-            # DMFF blocks other than the last one become side branches of the captured graph: they depend only on their
-            # two backbone rows, and nothing needs them before the head, so they overlap with the deeper backbone rows
-            if self.branch_dmff and m.i in dmff_rows[:-1] and not isinstance(f, int) and len(plan.launches) > n_before:
-                bid = len(plan.branches) + 1
-                for l in plan.launches[n_before:]:
-                    l.branch = bid
-                plan.branches[bid] = {"after": max(last_launch[j] for j in f), "join_before": None, "row": m.i}
-            elif plan.branches and dmff_rows and m.i == dmff_rows[-1] + 1:
-                for b in plan.branches.values():          # joined before the first head launch
+            if m.i in dmff_rows[:-1] and not isinstance(f, int) and n1 > n0:
+                branch(n0, n1, max(spans[j][1] - 1 for j in f), m.i)
+            elif dmff_rows and m.i == dmff_rows[-1] + 1:
+                for b in plan.branches.values():
                     if b["join_before"] is None:
-                        b["join_before"] = n_before
-            if self.branch_dmff and isinstance(m, Detect) and not isinstance(f, int):
-                # Detect levels fed by earlier head rows (P3, P4) only need that row: their 1x1 conv + decode run as
-                # branches beside the remaining head rows and are joined at the end of the graph
-                per = (len(plan.launches) - n_before) // len(f)
+                        b["join_before"] = n0
+            if isinstance(m, Detect) and not isinstance(f, int):
+                per = (n1 - n0) // len(f)
                 for lvl, j in enumerate(f[:-1]):
-                    if per * len(f) != len(plan.launches) - n_before or last_launch[j] >= n_before - 1:
-                        continue
-                    bid = len(plan.branches) + 1
-                    for l in plan.launches[n_before + lvl * per:n_before + (lvl + 1) * per]:
-                        l.branch = bid
-                    plan.branches[bid] = {"after": last_launch[j], "join_before": None, "row": m.i}
-        plan.outputs = x
-        return plan
+                    if per * len(f) == n1 - n0 and spans[j][1] < n0:
+                        branch(n0 + lvl * per, n0 + (lvl + 1) * per, spans[j][1] - 1, m.i)
 
-    def forward_once(self, x, x2, profile=False):
+    def _check_eval(self):
         if self.training:
             raise NotImplementedError("icafusion_amd implements the eval-mode inference path only (call .eval())")
-        if not (x.is_cuda and x2.is_cuda):
+
+    @staticmethod
+    def _check_images(*images):
+        if not all(t.is_cuda for t in images):
             raise RuntimeError("icafusion_amd.Model runs on the MI355X only: move the model and inputs to cuda "
                                "(no CPU fallback exists; the CPU reference is oracle/icaf_oracle.py, test-only)")
-        if x.shape != x2.shape:
-            raise ValueError(f"RGB and IR batches must match, got {tuple(x.shape)} vs {tuple(x2.shape)}")
-        dt = self.compute_dtype or next(self.parameters()).dtype
-        B, _, H, W = x.shape
-        if H % 32 or W % 32:
-            raise ValueError(f"input size {H}x{W} must be a multiple of the max stride 32")
-        plan = self.plan_for(B, H, W, x.device, dt)
-        if x.data_ptr() != plan.inputs[0].data_ptr():
-            plan.inputs[0].copy_(x)
-        if x2.data_ptr() != plan.inputs[1].data_ptr():
-            plan.inputs[1].copy_(x2)
-        if profile:
+        if len(images) == 2 and images[0].shape != images[1].shape:
+            raise ValueError(f"RGB and IR batches must match, got {tuple(images[0].shape)} vs {tuple(images[1].shape)}")
+
+    @staticmethod
+    def _check_stride(H, W, gs=32):
+        if H % gs or W % gs:
+            raise ValueError(f"input size {H}x{W} must be a multiple of the max stride {gs}")
+
+    @staticmethod
+    def _feed(plan, *images):
+        for dst, t in zip(plan.inputs, images):
+            if t.data_ptr() != dst.data_ptr():
+                dst.copy_(t)
+
+    def _result(self, out):
+        """plan.outputs — the (z, logits, raws) triple, or a TTA plan's merged tensor — as views if `static_outputs`, else as clones."""
+        if self.static_outputs:
+            return out
+        return out.clone() if torch.is_tensor(out) else type(out)(self._result(t) for t in out)
+
+    def _forward_images(self, images, u8=False, augment=False, profile=False):
+        """The front end proper: check, find the plan (augment: the TTA plan, which checks the size itself), feed it, run it, hand out its outputs."""
+        self._check_eval()
+        self._check_images(*images)
+        B, _, H, W = images[0].shape
+        if not augment:
+            self._check_stride(H, W)
+        plan = (self.tta_plan_for if augment else self.plan_for)(B, H, W, images[0].device, u8=u8)
+        self._feed(plan, *images)
+        if profile and not augment:
             for name, ms, flops, nbytes in plan.timed_run():
                 logger.info(f"{ms:10.3f} ms {flops / 1e9:10.2f} GFLOP  {name}")
         else:
             plan.run()
-        z, logits, raws = plan.outputs
-        if self.static_outputs:
-            return z, logits, raws
-        return z.clone(), logits.clone(), [r.clone() for r in raws]
+        out = self._result(plan.outputs)
+        return (out, None) if augment else out
+
+    def forward_once(self, x, x2, profile=False):
+        return self._forward_images((x, x2), profile=profile)
 
     def forward_u8(self, img6, augment=False):
         """Forward from the dataloader's uint8 (B, 6, H, W) RGB+IR batch (reference test.py:116-128 does
         `.to(device).float() / 255`, splits `[:, :3]` / `[:, 3:]`, then `model(img_rgb, img_ir)`): same outputs as
         forward(), one quarter of the input bytes, no fp32 image ever materialised.  augment=True: as forward(augment=True),
         the scaled passes staged straight from the uint8 batch."""
-        if self.training:
-            raise NotImplementedError("icafusion_amd implements the eval-mode inference path only (call .eval())")
+        self._check_eval()
         if not img6.is_cuda or img6.dtype != torch.uint8 or img6.dim() != 4 or img6.shape[1] != 6:
             raise ValueError("forward_u8 expects a cuda uint8 tensor of shape (B, 6, H, W)")
-        if augment:
-            return self._forward_augment(img6)
-        B, _, H, W = img6.shape
-        if H % 32 or W % 32:
-            raise ValueError(f"input size {H}x{W} must be a multiple of the max stride 32")
-        plan = self.plan_for(B, H, W, img6.device, u8=True)
-        if img6.data_ptr() != plan.inputs[0].data_ptr():
-            plan.inputs[0].copy_(img6)
-        plan.run()
-        z, logits, raws = plan.outputs
-        if self.static_outputs:
-            return z, logits, raws
-        return z.clone(), logits.clone(), [r.clone() for r in raws]
+        return self._forward_images((img6,), u8=True, augment=augment)
 
     def forward_frames(self, rgb, ir, img_size=640, bgr=True, augment=False, val_size=None):
         """Forward from NATIVE camera frames: rgb / ir are cuda uint8 tensors (B, H0, W0, ch) in decoder layout (interleaved, ch = 3 or
@@ -637,8 +596,7 @@ class Model(HipModule):
         val_size (an int): the VALIDATION loader's geometry instead (PairedValSet; ops.val_geometry(shapes, val_size, img_size)) — longest
         side to val_size (pixel-area average when shrinking, utils.datasets.resize_area_scalar byte for byte; bilinear when growing), then
         padded into img_size, the batch's letterbox shape; .scale then holds test.py's ratio_pad rows."""
-        if self.training:
-            raise NotImplementedError("icafusion_amd implements the eval-mode inference path only (call .eval())")
+        self._check_eval()
         fr = [list(t) if isinstance(t, (list, tuple)) else [t[i] for i in range(t.shape[0])] if torch.is_tensor(t) and t.dim() == 4 else None
               for t in (rgb, ir)]
         if fr[0] is None or fr[1] is None or not fr[0] or len(fr[0]) != len(fr[1]):
@@ -651,29 +609,9 @@ class Model(HipModule):
         if shapes != [tuple(f.shape[:2]) for f in fr[1]]:
             raise ValueError("the RGB and IR frame of a pair must have the same size")
         H, W = (img_size, img_size) if isinstance(img_size, int) else img_size
-        gs = int(self.stride.max())
-        if H % gs or W % gs:
-            raise ValueError(f"input size {H}x{W} must be a multiple of the max stride {gs}")
-        device = fr[0][0].device
-        key = (H, W, tuple(shapes), tuple(int(f.shape[2]) for f in fr[0] + fr[1]), device, val_size)
-        states = self.__dict__.setdefault("_frame_states", {})
-        st = states.pop(key, None)
-        if st is None:
-            mode = None
-            if val_size is None:
-                geom1, scale = ops.frame_geometry(shapes, (H, W))
-            else:
-                geom1, mode1, scale = ops.val_geometry(shapes, val_size, (H, W))
-                mode = np.concatenate((mode1, mode1))
-            geom = np.concatenate((geom1, geom1))
-            nbytes = ops.pack_frames(geom, key[3])
-            st = {"geom": geom, "geom_dev": ops.geom_tensor(geom, device), "arena": torch.zeros((nbytes,), dtype=torch.uint8, device=device),
-                  "mode": mode, "mode_dev": None if mode is None else torch.from_numpy(mode).to(device),
-                  "info": ops.FrameGeometry(geom, scale, torch.from_numpy(scale).to(device)), "dst": None, "launch": None}
-            while len(states) >= 8:                       # a few sets of shapes stay resident (arena + table each)
-                states.pop(next(iter(states)))
-        states[key] = st
-        plan = (self.tta_plan_for if augment else self.plan_for)(B, H, W, device, u8=True)
+        self._check_stride(H, W, int(self.stride.max()))
+        st = self._frame_state(H, W, shapes, tuple(int(f.shape[2]) for f in fr[0] + fr[1]), fr[0][0].device, val_size)
+        plan = (self.tta_plan_for if augment else self.plan_for)(B, H, W, fr[0][0].device, u8=True)
         dst = plan.inputs[0]
         if st["dst"] is not dst:                          # the plan was rebuilt (evicted from the cache): bind the launch to its new input
             if st["mode"] is None:
@@ -687,12 +625,30 @@ class Model(HipModule):
         st["launch"].args = st["launch"].args[:-1] + (int(bool(bgr)),)
         st["launch"](ops.current_stream_ptr())
         plan.run()
-        if augment:
-            return ((plan.outputs if self.static_outputs else plan.outputs.clone()), None), st["info"]
-        z, logits, raws = plan.outputs
-        if self.static_outputs:
-            return (z, logits, raws), st["info"]
-        return (z.clone(), logits.clone(), [r.clone() for r in raws]), st["info"]
+        out = self._result(plan.outputs)
+        return ((out, None) if augment else out), st["info"]
+
+    def _frame_state(self, H, W, shapes, chans, device, val_size):
+        """forward_frames' geometry tables, arena and staging launch for one set of frame shapes: found, or made and kept (least recently used out)."""
+        key = (H, W, tuple(shapes), chans, device, val_size)
+        states = self.__dict__.setdefault("_frame_states", {})
+        st = states.pop(key, None)
+        if st is None:
+            mode = None
+            if val_size is None:
+                geom1, scale = ops.frame_geometry(shapes, (H, W))
+            else:
+                geom1, mode1, scale = ops.val_geometry(shapes, val_size, (H, W))
+                mode = np.concatenate((mode1, mode1))
+            geom = np.concatenate((geom1, geom1))
+            nbytes = ops.pack_frames(geom, chans)
+            st = {"geom": geom, "geom_dev": ops.geom_tensor(geom, device), "arena": torch.zeros((nbytes,), dtype=torch.uint8, device=device),
+                  "mode": mode, "mode_dev": None if mode is None else torch.from_numpy(mode).to(device),
+                  "info": ops.FrameGeometry(geom, scale, torch.from_numpy(scale).to(device)), "dst": None, "launch": None}
+            while len(states) >= 8:                       # a few sets of shapes stay resident (arena + table each)
+                states.pop(next(iter(states)))
+        states[key] = st
+        return st
 
     def plan_for(self, B, H, W, device="cuda", dtype=None, u8=False, slot=0, branches=True):
         """Pre-build (and return) the execution plan; its .inputs are the static RGB / IR staging buffers (u8: the one
@@ -703,15 +659,7 @@ class Model(HipModule):
         branches=False: the plan's hipGraph is one chain (no parallel DMFF / Detect branches, whatever `branch_dmff` says) — what a
         host-fed pipeline wants: a graph with branches runs them on streams of its own, and those share hardware queues with the
         pipeline's copy and NMS streams."""
-        dt = dtype or self.compute_dtype or next(self.parameters()).dtype
-        device = torch.device(device)
-        if device.type == "cuda" and device.index is None:
-            device = torch.device("cuda", torch.cuda.current_device())
-        key = (B, H, W, dt, device, "u8") if u8 else (B, H, W, dt, device)
-        if slot:                                    # further plans of the same shape (own buffers): batches in flight side by side
-            key = key + ("slot", slot)
-        if not branches:
-            key = key + ("chain",)
+        dt, device, key = self._plan_key(B, H, W, device, dtype, u8, slot, branches)
         plans = self.__dict__.setdefault("_plans", {})
         plan = plans.pop(key, None)
         if plan is None:
@@ -735,6 +683,16 @@ class Model(HipModule):
                     plans.pop(next(iter(plans)))
         plans[key] = plan                           # (re-)insert as most recently used
         return plan
+
+    def _plan_key(self, B, H, W, device, dtype, u8, slot, branches, tta=False):
+        """-> (dtype, device, cache key) of a plan: the defaults resolved (the parameters' dtype, the current cuda device), then what
+        else tells plans apart — slot: further plans of the same shape (own buffers) for batches in flight side by side."""
+        dt = dtype or self.compute_dtype or next(self.parameters()).dtype
+        device = torch.device(device)
+        if device.type == "cuda" and device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        tags = (("tta",) if tta else ()) + (("u8",) if u8 else ()) + (("slot", slot) if slot else ()) + (() if branches else ("chain",))
+        return dt, device, (B, H, W, dt, device) + tags
 
     @staticmethod
     def _plan_bytes_hint(plans, B, H, W, dt):

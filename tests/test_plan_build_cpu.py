@@ -244,3 +244,21 @@ def test_packed_cache_key_follows_every_argument():
     assert padded.shape[1] > base.shape[1] == 64 and torch.equal(padded[:, :64], base) and not padded[:, 64:].any()
     assert torch.equal(swapped[:, :32], base[:, 32:]) and torch.equal(swapped[:, 32:], base[:, :32]) and torch.equal(low[:, :32], base[:, :32])
     assert got[9][0].shape == (2,) + tuple(base.shape) and torch.equal(got[9][0][0], base) and got[9][2].shape == (2, base.shape[0])
+
+
+@pytest.mark.parametrize("only, rows", [("VGG16", 10), ("ResNet50", 9)])
+def test_plan_fingerprint_matrix_covers_the_backbones(only, rows):
+    """tools/plan_fingerprint.py fingerprints the working tree's VGG16 / ResNet50 rows of its matrix — per backbone two yamls in three dtypes,
+    the bf16 variants (u8, pair_streams=False, VGG16: fuse_stem=True) and the second, non-square shape: one '<name> <sha256>' line each."""
+    import os
+    import re
+    import subprocess
+    import sys
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    r = subprocess.run([sys.executable, os.path.join(repo, "tools", "plan_fingerprint.py"), repo, "--digest", "--only", only],
+                       capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = r.stdout.splitlines()
+    assert len(lines) == rows and len({l.split()[0] for l in lines}) == rows, r.stdout
+    assert all(re.fullmatch(rf"\S*{only}\S* [0-9a-f]{{64}}", l) for l in lines), r.stdout
+    assert {f"yolov5_{only}_Transfusion_kaist/bf16/{tag}" for tag in ("u8", "pair_streams=False", "352x416")} <= {l.split()[0] for l in lines}

@@ -86,25 +86,31 @@ if a.candidates:
     candidate_sweep()
     sys.exit(0)
 
-B, H, W = 2, 320, 352
+SHAPE, SHAPE2 = (2, 320, 352), (1, 352, 416)
 YAMLS = ["yolov5n_Transfusion_kaist.yaml", "yolov5s_Transfusion_kaist.yaml", "yolov5m_Transfusion_kaist.yaml", "yolov5l_Transfusion_VEDAI.yaml",
-         "yolov5s_Add_kaist.yaml", "yolov5n_NiNfusion_FLIR.yaml", "yolov5m_NiNfusion_kaist.yaml", "yolov5m_Transfusion_SeaDrone.yaml"]
+         "yolov5s_Add_kaist.yaml", "yolov5n_NiNfusion_FLIR.yaml", "yolov5m_NiNfusion_kaist.yaml", "yolov5m_Transfusion_SeaDrone.yaml",
+         "yolov5_VGG16_Transfusion_kaist.yaml", "yolov5_VGG16_NiNfusion_kaist.yaml", "yolov5_ResNet50_Transfusion_kaist.yaml",
+         "yolov5_ResNet50_NiNfusion_kaist.yaml", "yolov5s_Transfusion_kaist_loops3.yaml"]
 DTYPES = {"bf16": torch.bfloat16, "fp16": torch.float16, "fp32": torch.float32}
-S = "yolov5s_Transfusion_kaist.yaml"
+S, V, R = "yolov5s_Transfusion_kaist.yaml", "yolov5_VGG16_Transfusion_kaist.yaml", "yolov5_ResNet50_Transfusion_kaist.yaml"
 CTB = common.CrossTransformerBlock
-# (name, yaml, dtype, build_plan keywords, Model attributes, class-level switches, loops of the DMFF rows)
-MATRIX = [(f"{y[:-5]}/{d}", y, d, {}, {}, [], None) for y in YAMLS for d in DTYPES] + [
-    (f"{S[:-5]}/bf16/{tag}", S, "bf16", kw, attrs, sw, loops) for tag, kw, attrs, sw, loops in [
-        ("u8", {"u8": True}, {}, [], None),
-        ("fold_upsample", {}, {"fold_upsample": True}, [], None),
-        ("pair_streams=False", {}, {"pair_streams": False}, [], None),
-        ("fuse_stem2=False", {}, {}, [(common.Conv, "fuse_stem2", False)], None),
-        ("fuse_cv3=False", {}, {}, [(common.C3, "fuse_cv3", False)], None),
-        ("chain_bottlenecks=False", {}, {}, [(common.C3, "chain_bottlenecks", False)], None),
-        ("chain_tail=False", {}, {}, [(common.Conv, "chain_tail", False)], None),
-        ("fuse_max_c=128", {}, {}, [(CTB, "fuse_max_c", 128)], None),
-        ("fuse_wide=False", {}, {}, [(CTB, "fuse_wide", False)], None),
-        ("loops=3", {}, {}, [], 3)]]
+U8, UNPAIRED = ("u8", {"u8": True}, {}, [], None), ("pair_streams=False", {}, {"pair_streams": False}, [], None)
+# (name, yaml, dtype, (B, H, W), build_plan keywords, Model attributes, class-level switches, loops of the DMFF rows)
+MATRIX = [(f"{y[:-5]}/{d}", y, d, SHAPE, {}, {}, [], None) for y in YAMLS for d in DTYPES] + [
+    (f"{y[:-5]}/bf16/{tag}", y, "bf16", SHAPE, kw, attrs, sw, loops) for y, variants in [
+        (S, [U8,
+             ("fold_upsample", {}, {"fold_upsample": True}, [], None),
+             UNPAIRED,
+             ("fuse_stem2=False", {}, {}, [(common.Conv, "fuse_stem2", False)], None),
+             ("fuse_cv3=False", {}, {}, [(common.C3, "fuse_cv3", False)], None),
+             ("chain_bottlenecks=False", {}, {}, [(common.C3, "chain_bottlenecks", False)], None),
+             ("chain_tail=False", {}, {}, [(common.Conv, "chain_tail", False)], None),
+             ("fuse_max_c=128", {}, {}, [(CTB, "fuse_max_c", 128)], None),
+             ("fuse_wide=False", {}, {}, [(CTB, "fuse_wide", False)], None),
+             ("loops=3", {}, {}, [], 3)]),
+        (V, [U8, UNPAIRED, ("fuse_stem=True", {}, {}, [(common.VGGblock, "fuse_stem", True)], None)]),
+        (R, [U8, UNPAIRED])] for tag, kw, attrs, sw, loops in variants] + [
+    (f"{y[:-5]}/bf16/{SHAPE2[1]}x{SHAPE2[2]}", y, "bf16", SHAPE2, {}, {}, [], None) for y in (S, V, R)]
 
 
 @contextlib.contextmanager
@@ -225,7 +231,7 @@ def seed_parameters(m):
                 t.copy_(torch.rand(t.shape, generator=g) * 0.5 + 0.25)
 
 
-for name, y, d, kw, attrs, switches, loops in MATRIX:
+for name, y, d, (B, H, W), kw, attrs, switches, loops in MATRIX:
     if a.only not in name:
         continue
     torch.manual_seed(0)
