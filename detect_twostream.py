@@ -23,6 +23,7 @@ import torch
 from icafusion_amd import ops
 from icafusion_amd.models.experimental import attempt_load
 from icafusion_amd.models.yolo import Model
+from icafusion_amd.utils.confluence import confluence_process
 from icafusion_amd.utils.datasets import LoadImages, imwrite_bgr
 from icafusion_amd.utils.general import increment_path, non_max_suppression, scale_coords, xyxy2xywh
 from icafusion_amd.utils.torch_utils import select_device, time_synchronized
@@ -83,7 +84,14 @@ def detect(opt):
             pred = out[0]
         else:
             pred = (model.forward_u8(img6, augment=True) if getattr(opt, "augment", False) else model.forward_u8(img6))[0]
-        pred = non_max_suppression(pred, opt.conf_thres, opt.iou_thres, classes=opt.classes, agnostic=opt.agnostic_nms)
+        if getattr(opt, "confluence", None) is not None:               # the reference's one-line swap (test.py:139-140); --classes afterwards
+            det = confluence_process(pred, opt.conf_thres, opt.confluence)[0]
+            det = torch.zeros((0, 6), device=pred.device) if det is None else det
+            if opt.classes is not None:
+                det = det[(det[:, 5:6] == torch.tensor(opt.classes, device=det.device)).any(1)]
+            pred = [det]
+        else:
+            pred = non_max_suppression(pred, opt.conf_thres, opt.iou_thres, classes=opt.classes, agnostic=opt.agnostic_nms)
         t2 = time_synchronized()
         det = pred[0]
         p = Path(path)
@@ -138,6 +146,8 @@ def parse_opt(argv=None):
     ap.add_argument("--nosave", action="store_true")
     ap.add_argument("--classes", nargs="+", type=int)
     ap.add_argument("--agnostic-nms", action="store_true")
+    ap.add_argument("--confluence", type=float, default=None, metavar="P_THRES",
+                    help="suppress with confluence (normalised Manhattan proximity below P_THRES, utils/confluence.py) instead of NMS")
     ap.add_argument("--project", default="runs/detect")
     ap.add_argument("--name", default="exp")
     ap.add_argument("--exist-ok", action="store_true")

@@ -83,8 +83,10 @@ RESIZE_LDS_BYTES = 20480                    # ICAF_RESIZE_LDS_BYTES: the fp32 ro
 RESIZE_MAX_TAPS = 8                         # ICAF_RESIZE_MAX_TAPS: taps per output whose weights it tabulates
 MISSRATE_MAX_DET, MISSRATE_KEEP, MISSRATE_MAX_LABELS, MISSRATE_SETUPS = 1024, 1000, 256, 7     # ICAF_MISSRATE_*: store rows / maxDets / labels per image / set-ups
 
+CONFLUENCE_MAX_CAND = 4096                  # ICAF_CONFLUENCE_MAX_CAND: candidates per image whose class members fit the LDS of one CU
 
-_p, _i, _ll, _f, _sz = C.c_void_p, C.c_int, C.c_longlong, C.c_float, C.c_size_t
+
+_p, _i, _ll, _f, _sz =C.c_void_p, C.c_int, C.c_longlong, C.c_float, C.c_size_t
 # symbol -> (restype, argtypes); must list every function declared in include/icaf.h
 SIGNATURES = {
     "icaf_last_error": (C.c_char_p, []),
@@ -134,6 +136,9 @@ SIGNATURES = {
     "icaf_nms": (_i, [_p, _i, _ll, _i, _f, _f, _i, _i, C.POINTER(_i), _i, _i, _i, _f, _p, _p, _p, _p, _sz, _p]),
     "icaf_missrate_stage": (_i, [_p, _p, _p, _p, _i, _i, _p, _p, _i, _i, _p]),
     "icaf_missrate_match": (_i, [_p, _p, _p, _p, _p, _i, _i, _p, _p, _i, _p, _p, _p, _p, _p]),
+    "icaf_confluence_select": (_i, [_p, _p, _i, _i, _i, C.c_double, _p, _p, _p, _p]),
+    "icaf_confluence_workspace_bytes": (_i, [_i, _ll, _i, _i, C.POINTER(_sz)]),
+    "icaf_confluence": (_i, [_p, _i, _ll, _i, _f, C.c_double, _i, _p, _p, _p, _p, _sz, _p]),
     "icaf_graph_begin": (_i, [_p]),
     "icaf_graph_end": (_i, [_p, C.POINTER(_p)]),
     "icaf_graph_launch": (_i, [_p, _p]),

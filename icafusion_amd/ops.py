@@ -971,6 +971,54 @@ class NmsRunner:
         return self.det, self.count, self.keep
 
 
+CONFLUENCE_MAX_CAND = _lib.CONFLUENCE_MAX_CAND
+
+
+def confluence_select(cand, n, nc, p_thres, det=None, count=None, keep_idx=None, want_keep=True, stream_ptr=None):
+    """Confluence (reference utils/confluence.py:109-193) on candidate lists that already live on the device (icaf_confluence_select): cand
+    (B, max_cand, 6) fp32 [x1, y1, x2, y2, conf, cls], n (B,) int32.  Returns (det (B, max_cand, 6), count (B,) int32, keep_idx (B, max_cand)
+    int32 or None): the kept rows in ascending candidate index, zeros behind them.  conf > 2e-4 is the caller's to guarantee.  No host sync."""
+    assert cand.is_cuda and cand.dtype == torch.float32 and cand.is_contiguous() and cand.dim() == 3 and cand.shape[2] == 6
+    B, max_cand, _ = cand.shape
+    assert n.dtype == torch.int32 and n.is_contiguous() and n.shape == (B,) and n.device == cand.device
+    if det is None:
+        det = torch.zeros((B, max_cand, 6), dtype=torch.float32, device=cand.device)
+    if count is None:
+        count = torch.zeros((B,), dtype=torch.int32, device=cand.device)
+    if keep_idx is None and want_keep:
+        keep_idx = torch.zeros((B, max_cand), dtype=torch.int32, device=cand.device)
+    assert det.dtype == torch.float32 and det.is_contiguous() and det.shape == (B, max_cand, 6) and count.dtype == torch.int32 and count.shape == (B,)
+    assert keep_idx is None or (keep_idx.dtype == torch.int32 and keep_idx.is_contiguous() and keep_idx.shape == (B, max_cand))
+    st = lib().icaf_confluence_select(cand.data_ptr(), n.data_ptr(), B, max_cand, int(nc), float(p_thres), det.data_ptr(), count.data_ptr(),
+                                      keep_idx.data_ptr() if keep_idx is not None else None,
+                                      stream_ptr if stream_ptr is not None else current_stream_ptr())
+    check(st, "icaf_confluence_select")
+    return det, count, keep_idx
+
+
+class ConfluenceRunner:
+    """Pre-allocated confluence launch (icaf_confluence: candidate stage + select) for a fixed (B, rows, nc) — graph-capturable; results stay
+    on the device.  Owns the det / count / keep block and the workspace.  count[b] < 0: image b had -count[b] > max_cand candidates and was
+    refused (its rows are zero)."""
+
+    def __init__(self, B, rows, nc, device, max_cand=CONFLUENCE_MAX_CAND, want_keep=True):
+        self.B, self.rows, self.nc, self.max_cand = B, rows, nc, int(max_cand)
+        sz = C.c_size_t(0)
+        check(lib().icaf_confluence_workspace_bytes(B, rows, nc, self.max_cand, C.byref(sz)), "confluence_workspace")
+        self.ws = torch.empty((max(sz.value, 16),), dtype=torch.uint8, device=device)
+        from .dist import detection_block
+        self.block, self.det, self.count = detection_block(B, self.max_cand, device)
+        self.keep = torch.zeros((B, self.max_cand), dtype=torch.int32, device=device) if want_keep else None
+
+    def launch(self, pred, conf_thres, p_thres, stream_ptr=None):
+        assert pred.dtype == torch.float32 and pred.is_contiguous() and pred.shape == (self.B, self.rows, 5 + self.nc)
+        st = lib().icaf_confluence(pred.data_ptr(), self.B, self.rows, self.nc, float(conf_thres), float(p_thres), self.max_cand,
+                                   self.det.data_ptr(), self.count.data_ptr(), self.keep.data_ptr() if self.keep is not None else None,
+                                   self.ws.data_ptr(), self.ws.numel(), stream_ptr if stream_ptr is not None else current_stream_ptr())
+        check(st, "icaf_confluence")
+        return self.det, self.count, self.keep
+
+
 # ------------------------------------------------------------------------------------------------------------
 # native camera frames: device letterbox in, native-space boxes out
 # ------------------------------------------------------------------------------------------------------------

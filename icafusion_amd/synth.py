@@ -93,3 +93,45 @@ def synth_labels(batch, nc, seed=0, max_boxes=8):
         for i in range(n):
             rows.append([b, cls[i], xy[i, 0], xy[i, 1], wh[i, 0], wh[i, 1]])
     return torch.tensor(rows, dtype=torch.float32)
+
+
+def synth_crowd(n, nc=1, seed=0, per_cluster=8, width=640.0, height=512.0):
+    """A crowded scene for the suppression steps: n xywh boxes (float32) in ceil(n / per_cluster) clusters — pedestrian-shaped boxes jittered
+    around a cluster's own box, as a detector scatters its candidates around an object — with a confidence in (0.15, 0.95) and a class per
+    CLUSTER.  Returns (xywh (n, 4), conf (n,), cls (n,) int64), shuffled so that clusters interleave in candidate order."""
+    g = np.random.default_rng([seed, 0xC0F1, n, nc])
+    k = max(1, -(-n // per_cluster))
+    cxy = g.uniform((0.08 * width, 0.2 * height), (0.92 * width, 0.8 * height), (k, 2))
+    cwh = np.stack((g.uniform(24.0, 60.0, k), g.uniform(70.0, 150.0, k)), 1)
+    ccls = g.integers(0, nc, k)
+    owner = g.permutation(np.arange(n) % k)
+    wh = cwh[owner] * g.uniform(0.85, 1.15, (n, 2))
+    xy = cxy[owner] + cwh[owner] * g.normal(0.0, 0.08, (n, 2))
+    conf = g.uniform(0.15, 0.95, n)
+    return np.concatenate((xy, wh), 1).astype(np.float32), conf.astype(np.float32), ccls[owner].astype(np.int64)
+
+
+def synth_crowd_dets(n, nc=1, seed=0, per_cluster=8):
+    """synth_crowd as a confluence / NMS candidate list (n, 6) float32 [x1, y1, x2, y2, conf, cls] (xywh -> xyxy in fp32)."""
+    xywh, conf, cls = synth_crowd(n, nc, seed, per_cluster)
+    half = xywh[:, 2:] / np.float32(2)
+    return np.concatenate((xywh[:, :2] - half, xywh[:, :2] + half, conf[:, None], cls[:, None].astype(np.float32)), 1).astype(np.float32)
+
+
+def synth_crowd_prediction(batch, rows, n, nc=1, seed=0, per_cluster=8):
+    """A decoded prediction tensor (batch, rows, 5 + nc) float32 whose every image holds exactly n rows above any sensible threshold (obj in
+    (0.5, 1), the cluster's class at conf / obj, the other classes at 0.01) at seeded positions among rows of zero objectness — the boxes
+    of synth_crowd, so that the suppression step meets n candidates per image."""
+    assert n <= rows
+    out = np.zeros((batch, rows, 5 + nc), np.float32)
+    for b in range(batch):
+        g = np.random.default_rng([seed, 0xC0F2, b, rows, n])
+        xywh, conf, cls = synth_crowd(n, nc, seed * 1000 + b, per_cluster)
+        at = np.sort(g.choice(rows, n, replace=False))
+        obj = g.uniform(0.5, 1.0, n).astype(np.float32)
+        out[b, :, :4] = (320.0, 256.0, 40.0, 100.0)
+        out[b, at, :4] = xywh
+        out[b, at, 4] = obj
+        out[b, at, 5:] = 0.01
+        out[b, at, 5 + cls] = np.minimum(conf / obj, np.float32(1.0))
+    return out

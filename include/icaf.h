@@ -535,6 +535,41 @@ int icaf_missrate_match(const double* gt_box, const double* gt_height, const int
                         const int* gt_off, int I, int max_labels_per_image, const double* dt, const int* dt_count, int cap, int* order,
                         int* dt_gt, unsigned char* dt_ignore, unsigned char* gt_ignore, icaf_stream_t s);
 
+/* ---- Confluence suppression (utils/confluence.py:50-193; the reference's alternative to NMS, test.py:139-140) ----------------------
+ * confluence (:109-193), per class 0 .. nc-1 on a candidate list [x1, y1, x2, y2, conf, cls] (fp32 values, arithmetic in fp64), candidates of a
+ * class in their original order; while any is alive:
+ *   p(i, j) (:141-162): lo / hi = min / max of i.x1, i.x2, j.x1, j.x2, every value normalised on its own as (v - lo) / (hi - lo) (one
+ *     subtraction, one IEEE division), likewise y; p = ((|n(i.x1) - n(j.x1)| + |n(i.x2) - n(j.x2)|) + |n(i.y1) - n(j.y1)|) + |n(i.y2) - n(j.y2)|.
+ *     hi == lo gives NaN: such a pair is no neighbour and never suppresses.
+ *   value(i) (:166-173) = min over the alive j != i with p(i, j) < 2 of p(i, j) / conf_i, 0 when there is none.
+ *   pick (:133-178) = the first i whose value is below a running minimum starting at 10000; the reference crashes when no value is, hence
+ *     the PRECONDITION conf > 2e-4 on every candidate (p < 2, so p / conf < 10000).  Here a value that is not below 10000 counts as 10000
+ *     and the lowest alive index wins among those: the launch always ends.  conf must be positive.
+ *   remove (:180-190) the pick and every alive j with p(pick, j) < p_thres (strict; p_thres is the reference's Python float: a double).
+ * The result is the picked candidates in ascending candidate index (np.unique, :192).
+ * The select entry point — cand [B][max_cand][6] fp32, n [B] (device): det [B][max_cand][6] receives the kept rows in ascending candidate
+ *   index and zeros behind them, count [B] their number, keep_idx [B][max_cand] (may be NULL) their candidate indices and -1 behind them.  Rows
+ *   whose class is not an integer in [0, nc) are never kept (no class loop of the reference visits them).  n[b] < 0 counts as 0; n[b] > max_cand
+ *   refuses the image as below.  Rows of cand at or beyond n[b] are never read.  Two kernels on `s`: one workgroup per (image, class) with its
+ *   members in LDS, then one per image; det doubles as scratch in between.
+ * The whole path (confluence_process, :50-106) — pred [B][rows][5+nc] fp32 (cx, cy, w, h, obj, cls...): obj > conf_thres, conf = cls * obj
+ *   (fp32), xywh -> xyxy (fp32), one candidate per (box, class) with conf > conf_thres in row-major order (for nc == 1 the best-class branch
+ *   of :89-91 is the same list); no class offset, no max_nms, no max_det.  Then the select.  The reference has no cap and a silent top-k would
+ *   be another algorithm, so an image with more than max_cand candidates is REFUSED, not truncated: count[b] = -(its candidate number), its
+ *   det rows zero; the other images of the batch are unaffected and the host decides.  conf_thres < 2e-4 is ICAF_ERR_ARG (the precondition
+ *   above).  Workspace: icaf_confluence_workspace_bytes, 256-byte aligned, contents irrelevant on entry (the candidate list and the initial
+ *   sweep's minimum / neighbour per candidate).  Four kernels on `s`, no host synchronisation.
+ * ICAF_CONFLUENCE_MAX_CAND = 4096: a class's members stay in the LDS of one CU for all its picks at 35 bytes each (box 16, value 8, conf 4,
+ *   neighbour 2, candidate index 2, re-sweep list 2, alive 1): 140 KiB of the 160 KiB; candidate and member indices fit 16 bits.
+ * ICAF_ERR_ARG for null pointers, B / nc / rows < 1, max_cand outside [1, ICAF_CONFLUENCE_MAX_CAND], a NaN p_thres, a short or misaligned
+ *   workspace. */
+enum { ICAF_CONFLUENCE_MAX_CAND = 4096 };
+int icaf_confluence_select(const float* cand, const int* n, int B, int max_cand, int nc, double p_thres, float* det, int* count,
+                           int* keep_idx, icaf_stream_t s);
+int icaf_confluence_workspace_bytes(int B, long long rows, int nc, int max_cand, size_t* bytes);
+int icaf_confluence(const float* pred, int B, long long rows, int nc, float conf_thres, double p_thres, int max_cand, float* det,
+                    int* count, int* keep_idx, void* workspace, size_t workspace_bytes, icaf_stream_t s);
+
 /* ---- HIP graph capture / events (so the Python host never needs a tracing compiler) ------------------------ */
 int icaf_graph_begin(icaf_stream_t s);
 int icaf_graph_end(icaf_stream_t s, void** graph_exec);

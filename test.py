@@ -14,7 +14,9 @@ the input of the KAIST miss-rate evaluator; `<weights>_predictions.json`) under 
 `--miss-rate ANNOTATIONS` adds the KAIST log-average miss rate (the evaluator of the reference's `evaluation_script/`: matching on the
 device, FPPI sweep in numpy; icafusion_amd/utils/missrate.py) and returns its dict as a fourth element; `--task speed` ignores it.
 `--task speed` runs at conf 0.25 / IoU 0.45 as the reference does.  `--device-letterbox` uploads the frames as decoded: the loader's
-longest-side resize (pixel-area average when shrinking) and the padding run on the device (Model.forward_frames(val_size=...)).  Not carried over (all outside the metric): plots / wandb /
+longest-side resize (pixel-area average when shrinking) and the padding run on the device (Model.forward_frames(val_size=...)).
+`--confluence P_THRES` swaps the suppression step for the reference's confluence (its commented line test.py:140; utils/confluence.py) and leaves
+everything downstream as it is; an image whose candidates exceed the confluence cap, or that keeps more than 1024 boxes, raises.  Not carried over (all outside the metric): plots / wandb /
 `--save-hybrid` auto-labelling / `--task study` / the pycocotools call / MR curves and plots; `--augment` raises (test-time augmentation is not built)."""
 import argparse
 import os
@@ -30,9 +32,12 @@ from icafusion_amd.utils.datasets import create_dataloader_rgb_ir
 from icafusion_amd import ops
 from icafusion_amd.utils.general import check_img_size, increment_path, nms_device, scale_coords, xywh2xyxy
 from icafusion_amd.utils import missrate
+from icafusion_amd.utils.confluence import confluence_device
 from icafusion_amd.utils.results import ResultWriter, frame_index, label_listing
 from icafusion_amd.utils.metrics import ap_per_class
 from icafusion_amd.utils.torch_utils import select_device, time_synchronized
+
+MATCH_MAX_DET = 1024                                             # detections per image icaf_match_predictions takes (nms.hip)
 
 
 def summarize(stats, nc, names, seen, verbose=False):
@@ -105,7 +110,7 @@ class MissRate:
 @torch.no_grad()
 def test(data, weights=None, batch_size=32, imgsz=640, conf_thres=0.001, iou_thres=0.5, single_cls=False, model=None,
          dataloader=None, device="0", compute_dtype=None, cfg=None, verbose=False, save_json=False, save_txt=False, save_conf=True,
-         save_dir=None, augment=False, miss_rate=None, device_letterbox=False):
+         save_dir=None, augment=False, confluence=None, miss_rate=None, device_letterbox=False):
     if augment:
         raise NotImplementedError("test-time augmentation (models/yolo_test.py:116-132) is outside the inference hot path")
     if isinstance(data, str):
@@ -156,7 +161,16 @@ def test(data, weights=None, batch_size=32, imgsz=640, conf_thres=0.001, iou_thr
         targets = targets.clone()
         targets[:, 2:] *= torch.tensor([width, height, width, height])
         t = time_synchronized()
-        det, count, _ = nms_device(out, conf_thres, iou_thres, multi_label=True, agnostic=single_cls)
+        if confluence is not None:                               # the reference's one-line swap (test.py:139-140)
+            det, count, _ = confluence_device(out, conf_thres, confluence)
+            for si, n in enumerate(count.tolist()):              # the matching kernel takes MATCH_MAX_DET rows per image
+                if n < 0 or n > MATCH_MAX_DET:
+                    raise ValueError(f"{paths[si]}: confluence " + (f"met {-n} candidates, above its cap of {det.shape[1]}" if n < 0 else
+                                                                    f"kept {n} detections, the matching takes {MATCH_MAX_DET}") +
+                                     "; raise --conf-thres")
+            det = det[:, :MATCH_MAX_DET].contiguous()
+        else:
+            det, count, _ = nms_device(out, conf_thres, iou_thres, multi_label=True, agnostic=single_cls)
         t_nms += time_synchronized() - t
         # statistics per image (reference test.py:144-230) on the device: labels go up in native image space, one kernel
         # maps the detections there (scale_coords + clip_coords) and matches them; only flags / conf / cls come back
@@ -227,6 +241,8 @@ def parse_opt(argv=None):
                                                                      "shrinking) and the padding run on the device")
     ap_.add_argument("--miss-rate", type=str, default=None, metavar="ANNOTATIONS",
                      help="KAIST annotation JSON: also report the log-average miss rate (All / Day / Night, scale and occlusion subsets)")
+    ap_.add_argument("--confluence", type=float, default=None, metavar="P_THRES",
+                     help="suppress with confluence (normalised Manhattan proximity below P_THRES, utils/confluence.py) instead of NMS")
     ap_.add_argument("--save-txt", action="store_true", help="per-image result lines + result.txt under <project>/<name>/labels")
     ap_.add_argument("--save-conf", action="store_true", help="append the confidence to every --save-txt line")
     ap_.add_argument("--save-json", action="store_true", help="<project>/<name>/<weights>_predictions.json")
@@ -254,4 +270,4 @@ if __name__ == "__main__":
         save_dir = increment_path(os.path.join(o.project, o.name), exist_ok=o.exist_ok) if (o.save_txt or o.save_json) else None
         test(o.data, o.weights, o.batch_size, imgsz, o.conf_thres, o.iou_thres, o.single_cls, device=o.device, compute_dtype=dtype, cfg=o.cfg,
              verbose=o.verbose, save_json=o.save_json, save_txt=o.save_txt, save_conf=o.save_conf, save_dir=save_dir, augment=o.augment,
-             miss_rate=o.miss_rate, device_letterbox=o.device_letterbox)
+             miss_rate=o.miss_rate, device_letterbox=o.device_letterbox, confluence=o.confluence)
