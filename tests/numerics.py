@@ -853,3 +853,405 @@ MERGE_GEOMS = {
     "big":       (6, 80, 80, 128, 20, 20, True),    # 6 * 6400 * 2 * nv = 1,228,800 (16 bit) vectors > 2^20, 20 MB of output; x4: exact bits
 }
 
+
+
+# ====================================================================================================================================
+# DMFF block kernels (dmff_wide.hip: ln_qkv, proj_mlp, proj_mlp_split + reduce; dmff_fused.hip: ln_qkv, attn_mlp) — the builders,
+# references and the torch emulation behind tests/test_gpu_exact_dmff.py.  Tokens are (2, rows, C) with the modality in front.
+#
+# Exactness through the block comes from three constructions:
+#   1. rows x[r, c] = m_r +- s with exactly C / 2 channels on either side and eps = 1 - s^2: mean m_r, q / C + eps = 1, rstd = 1 — every
+#      step exact in fp32 in ANY summation order (all partial sums are multiples of a power of two far below 2^24 of them);
+#   2. a zeroed GEMM isolates the others (W2 = 0: the launch returns x_att; W_o = 0: the MLP sees the rows of 1.);
+#   3. a sparse W2 (32 non-zeros per output channel, one or more in every hidden chunk) keeps the fp32 accumulation error of the fc2 sum,
+#      whose operands are NOT on a lattice after GELU, at (nnz - 1) u sum |w h|.
+# ====================================================================================================================================
+LN_EPS_EXACT = 0.75                                  # 1 - s^2 for deviations of s = 0.5
+DMFF_ROWS = (64, 33, 154, 321)                       # one tile; one row in the second 32-row half; a last tile of 26 rows (second half empty);
+DMFF_ROWS_MAX = 321                                  # six tiles: a second group of eight workgroups, one tile per eight under ksplit = 4
+W2_NNZ = 32
+# (C, dtype, ksplit, r32): every build dispatch_wide_proj_mlp, dispatch_wide_split and launch_wide_reduce can reach
+DMFF_CELLS = ([(128, dt, 1, False) for dt in (BF16, F16, F32)] + [(C, dt, 1, False) for C in (256, 512) for dt in (BF16, F16)] +
+              [(C, dt, 1, True) for C in (128, 256) for dt in (BF16, F16)] +
+              [(C, dt, ks, False) for C in (256, 512) for dt in (BF16, F16) for ks in (2, 4)] +
+              [(C, dt, 2, True) for C in (256, 512) for dt in (BF16, F16)])
+DT_NAME = {F32: "f32", BF16: "bf16", F16: "f16"}
+
+
+def cell_id(cell):
+    C, dt, ks, r32 = cell
+    return f"C{C}-{DT_NAME[dt]}-ks{ks}-{'r32' if r32 else 'r16'}"
+
+
+def wide_pass(C):
+    """Output channels per pass of the dmff_wide build for width C (WG4 / WG8) — also the width of a hidden chunk."""
+    return 128 if C == 128 else 256
+
+
+def rne64(x64, dt):
+    """fp64 -> `dt` -> fp64 in ONE rounding to nearest even, for values that are not fp32 numbers (rne() asserts they are)."""
+    if dt == F32:
+        return x64.float().double()
+    u = ulp(x64, dt)
+    return torch.round(x64 / u) * u
+
+
+def fma32(a, b, c):
+    """fp32 fma(a, b, c) for a Python float a and fp32 tensors b, c: the product is exact in fp64, the sum rounds once more only at the
+    53rd bit."""
+    return (f32w(a) * b.double() + c.double()).float()
+
+
+def exact_ln_rows(rows, C, s, seed, kmax=16, big=None):
+    """Construction 1: x[r, c] = m_r +- s, exactly C / 2 channels of every row on the + side under a fresh random permutation per row;
+    m_r = k / 2 with |k| <= kmax.  big: every fourth row takes this mean instead (the fp32 stream: x * x is then inexact in fp32, so a
+    one-pass variance shows)."""
+    g = _gen(seed)
+    m = torch.randint(-kmax, kmax + 1, (rows,), generator=g).float() / 2.0
+    if big is not None:
+        m[3::4] = float(big)
+    sign = torch.ones((rows, C))
+    sign[:, C // 2:] = -1.0
+    order = torch.stack([torch.randperm(C, generator=g) for _ in range(rows)])
+    return m[:, None] + s * torch.gather(sign, 1, order)
+
+
+def assert_exact_ln(v, eps, dt=None, what=""):
+    """The lattice condition of construction 1 on the rows `v` (fp32, (..., C)) a LayerNorm with this eps is about to see: every row holds
+    two values m +- s, C / 2 channels each; fp32(eps) + s^2 is exactly 1; every element is a multiple of a power of two `unit` with
+    C max|v| / unit < 2^24, so every partial sum of the row — and of the squared deviations, C s^2 / unit^2 — is an fp32 number in any
+    order; and (dt given) the rows are representable in the storage type."""
+    C = v.shape[-1]
+    v64 = v.double().reshape(-1, C)
+    hi, lo = v64.amax(1, keepdim=True), v64.amin(1, keepdim=True)
+    s = (hi - lo) / 2.0
+    assert bool(((v64 == hi) | (v64 == lo)).all()) and bool(((v64 == hi).sum(1) == C // 2).all()), f"{what}: rows are not m +- s, half each"
+    assert bool((s > 0).all()) and bool((f32w(eps) + s * s == 1.0).all()), f"{what}: eps + s^2 != 1"
+    k = next((k for k in range(0, 16) if bool((v64 * 2.0 ** k == torch.round(v64 * 2.0 ** k)).all())), None)
+    assert k is not None and C * float(v64.abs().max()) * 2.0 ** k < 2.0 ** 24, f"{what}: the row sums are not exact in fp32"
+    assert C * float((s * s).max()) * 4.0 ** k < 2.0 ** 24
+    if dt is not None:
+        assert torch.equal(v.to(dt).float(), v), f"{what}: rows not representable in {dt}"
+
+
+def tile_layernorm32(x, gam, bet, eps, tpr, dt):
+    """wide_tile_layernorm / tile_layernorm (dmff_wide.hip, dmff_fused.hip) in fp32 with the device's association: `tpr` threads per row,
+    thread p summing the 16-byte vectors p, p + tpr, ... element by element, then the xor-shuffle tree over 1, 2 (, 4); two passes.
+    x (rows, C) fp32 holding `dt` values -> (mean, rstd, output in dt)."""
+    rows, C = x.shape
+    vec = VEC[dt]
+    xv = x.reshape(rows, C // vec // tpr, tpr, vec).permute(0, 2, 1, 3).reshape(rows, tpr, -1)      # [row][thread][its elements, in order]
+
+    def tree(t):
+        acc = torch.zeros((rows, tpr))
+        for j in range(t.shape[2]):
+            acc = acc + t[:, :, j]
+        step = 1
+        while step < tpr:
+            acc = acc + acc[:, torch.arange(tpr) ^ step]
+            step *= 2
+        return acc[:, :1]
+    mean = tree(xv) / torch.tensor(float(C), dtype=F32)
+    d = xv - mean[:, :, None]
+    rstd = 1.0 / torch.sqrt(tree(d * d) / torch.tensor(float(C), dtype=F32) + torch.tensor(eps, dtype=F32))
+    return mean, rstd, ((x - mean) * rstd * gam + bet).to(dt)
+
+
+def _ri(g, lo, hi, shape):
+    return torch.randint(lo, hi + 1, shape, generator=g).float()
+
+
+def _nonzero(g, hi, shape):
+    """integers in [-hi, hi] without 0"""
+    return _ri(g, 1, hi, shape) * (_ri(g, 0, 1, shape) * 2.0 - 1.0)
+
+
+def sparse_w2(C, hid, dt, seed, nnz=W2_NNZ):
+    """Construction 3: W2 (2, C, hid) with `nnz` non-zeros k / 2^s_w per output channel, one in each of the nnz column blocks of width
+    hid / nnz — so at least one in every hidden chunk and every hidden-split slice — placed by an affine map of the channel index, so
+    that every hidden column is used by C nnz / hid (= 8) output channels of its modality."""
+    g = _gen(seed)
+    sw = GRID[dt][0]
+    blk = hid // nnz
+    assert hid % nnz == 0 and C % blk == 0 and wide_pass(C) % blk == 0
+    w = torch.zeros((2, C, hid))
+    n = torch.arange(C)
+    for m in range(2):
+        for j in range(nnz):
+            a = 2 * int(torch.randint(0, blk // 2, (1,), generator=g)) + 1
+            b = int(torch.randint(0, blk, (1,), generator=g))
+            w[m, n, j * blk + (n * a + b) % blk] = _nonzero(g, 2 ** sw, (C,)) / 2 ** sw
+    nz = w != 0
+    assert bool((nz.sum(2) == nnz).all()) and bool((nz.sum(1) >= 2).all())
+    assert bool((nz.reshape(2, C, hid // wide_pass(C), -1).sum(3) >= 1).all()), "an output channel misses a hidden chunk"
+    return w
+
+
+def dmff_operands_a(C, dt, rows=DMFF_ROWS_MAX, seed=0):
+    """Test (a), out-projection and coefficient mix: att, W_o, b_o, x on the lattice of `dt`; x32 fp32 values that NEITHER 16-bit type
+    holds (odd multiples of 2^-10 in [2, 4)); the four attention coefficients distinct powers of two; W2 = b2 = 0 with c_res_mlp = 1, so
+    the launch returns x_att; W1, b1 and the MLP LayerNorm random and non-zero (the MLP runs on real data and must leave no trace).
+    Rows r % 16 == 5 of x_att are CONSTANT on purpose (att = 0, x = 1 / 4 - (c_acc / c_res) b_o): the LayerNorm then divides by sqrt(eps),
+    which stays finite — a variance clamped to zero without eps would show as Inf * 0."""
+    g = _gen(7000 + 10 * C + [F32, BF16, F16].index(dt) + seed)
+    sw, sf = GRID[dt]
+    hid = 4 * C
+    co = [1.0, 0.5, 2.0, 0.25, 1.0, 0.5, 1.0, 2.0]          # (res, acc) of the attention mix per modality, then of the MLP mix
+    d = dict(att=_ri(g, -8, 8, (2, rows, C)), wo=_ri(g, -2 ** sw, 2 ** sw, (2, C, C)) / 2 ** sw, bo=_ri(g, -64, 64, (2, C)) / 2 ** sf,
+             x=_ri(g, -64, 64, (2, rows, C)) / 2 ** sf, x32=(2049.0 + 2.0 * _ri(g, 0, 1023, (2, rows, C))) * (_ri(g, 0, 1, (2, rows, C)) * 2.0 - 1.0) / 1024.0,
+             w1=torch.randn((2, hid, C), generator=g) / math.sqrt(C), b1=torch.randn((2, hid), generator=g) * 0.3,
+             w2=torch.zeros((2, C, hid)), b2=torch.zeros((2, C)), co=co, eps=(1e-5, 1e-5, 1e-5), hidden=hid,
+             ln=dict(a1w=torch.ones(C), a1b=torch.zeros(C), a2w=torch.ones(C), a2b=torch.zeros(C),
+                     mw=1.0 + 0.3 * torch.randn((C,), generator=g), mb=0.2 * torch.randn((C,), generator=g)))
+    const = torch.arange(rows) % 16 == 5
+    for m in range(2):
+        d["att"][m, const] = 0.0
+        flat = 0.25 - (co[2 * m + 1] / co[2 * m]) * d["bo"][m]
+        d["x"][m, const] = flat
+        d["x32"][m, const] = flat
+    d["const"] = const
+    for name in ("att", "wo", "x"):
+        assert torch.equal(d[name].to(dt).float(), d[name]), f"lattice {name} is not representable in {dt}"
+    if dt != F32:
+        free = d["x32"][:, ~const]
+        assert not bool((free.to(BF16).float() == free).any()) and not bool((free.to(F16).float() == free).any())
+    return d
+
+
+def dmff_xatt64(d, use_x32=False):
+    """fp64 x_att = c_res x + c_acc (att W_o^T + b_o) of both modalities, asserted to be an fp32 number (on the lattice it is exact)."""
+    out = []
+    for m in range(2):
+        x = (d["x32"] if use_x32 else d["x"])[m].double()
+        acc = d["att"][m].double() @ d["wo"][m].double().T
+        assert torch.equal((d["att"][m] @ d["wo"][m].T).double(), acc), "fp32 and fp64 out-projection differ: not on an exact lattice"
+        z = f32w(d["co"][2 * m]) * x + f32w(d["co"][2 * m + 1]) * (acc + d["bo"][m].double())
+        assert is_f32(z), "x_att is not an fp32 number"
+        out.append(z)
+    return torch.stack(out)
+
+
+def dmff_operands_b(C, dt, rows=DMFF_ROWS_MAX, seed=0):
+    """Test (b), LayerNorm + MLP + final mix: W_o = b_o = 0, x the rows of construction 1 — modality 0 with c_res = 1 and s = 0.5,
+    modality 1 with c_res = 2 and s = 0.25, so both reach deviations of 0.5 under the one shared eps_mlp = 0.75; x32 (the fp32 stream of a
+    later iteration) is a DIFFERENT set of such rows, every fourth one around a mean of 4096; gamma / beta = j / 8, W1 = j / 128, b1 = j / 32
+    (pre-activations exact, most of them in |u| < 3), W2 sparse, b2 on the lattice.  The attention LayerNorm's parameters differ from the
+    MLP's; att is random (against the zero W_o it must leave no trace)."""
+    g = _gen(8000 + 10 * C + [F32, BF16, F16].index(dt) + seed)
+    sf = GRID[dt][1]
+    hid = 4 * C
+    co = [1.0, 0.5, 2.0, 0.25, 0.5, 2.0, 0.25, 4.0]
+    lat8 = lambda: _nonzero(g, 16, (C,)) / 8.0
+    d = dict(att=_ri(g, -8, 8, (2, rows, C)), wo=torch.zeros((2, C, C)), bo=torch.zeros((2, C)),
+             x=torch.stack((exact_ln_rows(rows, C, 0.5, 8100 + C), exact_ln_rows(rows, C, 0.25, 8200 + C, kmax=8))),
+             x32=torch.stack((exact_ln_rows(rows, C, 0.5, 8300 + C, big=4096.0), exact_ln_rows(rows, C, 0.25, 8400 + C, kmax=8, big=2048.0))),
+             w1=_ri(g, -8, 8, (2, hid, C)) / 128.0, b1=_ri(g, -32, 32, (2, hid)) / 32.0,
+             w2=sparse_w2(C, hid, dt, 8500 + C), b2=_ri(g, -64, 64, (2, C)) / 2 ** sf, co=co, eps=(1e-5, 1e-5, LN_EPS_EXACT), hidden=hid,
+             ln=dict(a1w=lat8(), a1b=lat8(), a2w=lat8(), a2b=lat8(), mw=lat8(), mb=_ri(g, -16, 16, (C,)) / 8.0))
+    assert not torch.equal(d["ln"]["a1w"], d["ln"]["mw"]) and not torch.equal(d["ln"]["a2w"], d["ln"]["mw"])
+    assert not torch.equal(d["b1"][:, :hid // 2], d["b1"][:, hid // 2:])
+    for name in ("att", "x", "w1", "w2"):
+        assert torch.equal(d[name].to(dt).float(), d[name]), f"lattice {name} is not representable in {dt}"
+    return d
+
+
+def dmff_ref_b(d, dt, use_x32=False):
+    """fp64 reference and COUNTED per-element bounds of test (b).  Returns dict(out, by, b32, known, share, u_std): the reference (2, rows, C),
+    the bound on the stored y, the bound on the fp32 stream y32, the outputs none of whose hidden operands is ambiguous (their bound is
+    the accumulation and the mix alone), the share of hidden elements whose rounding is ambiguous, the spread of u.
+
+    Everything up to the pre-activation u is exact (asserted).  From there, with u = 2^-24:
+      1. h = RNE_dt(gelu(u)): the device evaluates GELU within act_budget32 of the true value; where true value +- budget round to the SAME
+         number of the storage type, h is known exactly (h_ref); where they do not (`ambiguous`), h may be the neighbour: |W2[n, k]| ulp_dt(h_k).
+         The fp32 build stores h unrounded: sum |W2| budget instead.
+      2. the fc2 sum has nnz non-zero terms per output (products w h exact in fp32 for the 16-bit types: <= 7 + 11 bits): nnz - 1 roundings
+         of partial sums bounded by S = sum |w h| — the chunk and slice order does not matter, adding an exact zero is exact.  The fp32 build
+         rounds the nnz products as well: 2 nnz - 1.
+      3. the final mix  fma(c_res, x_att, (sum + b2) * c_acc): the addition of b2 (u |mlp|), the product (u |c_acc mlp|), the fma (u |out|).
+      4. the storage rounding of y (storage_bound); y32 and the fp32 build's y have none."""
+    C, hid = d["x"].shape[2], d["hidden"]
+    outs, bys, b32s, known, amb_n, ustd = [], [], [], [], 0, []
+    for m in range(2):
+        cr_a, cr_m, ca_m = f32w(d["co"][2 * m]), f32w(d["co"][4 + 2 * m]), f32w(d["co"][5 + 2 * m])
+        assert not bool(d["wo"][m].any()) and not bool(d["bo"][m].any())
+        xatt = cr_a * (d["x32"] if use_x32 else d["x"])[m].double()
+        assert_exact_ln(xatt.float(), d["eps"][2], None if use_x32 else dt, "x_att")
+        mean = (xatt.amax(1, keepdim=True) + xatt.amin(1, keepdim=True)) / 2.0
+        n2 = (xatt - mean) * d["ln"]["mw"].double() + d["ln"]["mb"].double()                # rstd = 1
+        assert torch.equal(n2.float().to(dt).double(), n2), "the normalised tile is not representable in the storage type"
+        u = n2 @ d["w1"][m].double().T + d["b1"][m].double()
+        assert torch.equal((n2.float() @ d["w1"][m].T + d["b1"][m]).double(), u), "the pre-activation is not exact in fp32"
+        g64 = act64(u, ACT_GELU)
+        bud = act_budget32(u, ACT_GELU, dt)
+        w2 = d["w2"][m].double()
+        if dt == F32:
+            h, t1 = g64, bud @ w2.abs().T
+            nround = 2 * W2_NNZ - 1
+        else:
+            h = rne64(g64, dt)
+            amb = rne64(g64 - bud, dt) != rne64(g64 + bud, dt)
+            amb_n += int(amb.sum())
+            t1 = (amb.double() * ulp(g64.abs() + bud, dt)) @ w2.abs().T
+            nround = W2_NNZ - 1
+        mlp = h @ w2.T + d["b2"][m].double()
+        t2 = nround * U32 * (h.abs() @ w2.abs().T)
+        out = cr_m * xatt + ca_m * mlp
+        b32 = (abs(ca_m) * (t1 + t2) + U32 * (mlp.abs() + (ca_m * mlp).abs() + out.abs())) * SECOND + SUB32
+        outs.append(out)
+        b32s.append(b32)
+        known.append(t1 == 0 if dt != F32 else torch.ones_like(t1, dtype=torch.bool))
+        bys.append(b32 if dt == F32 else storage_bound(out, b32, dt))
+        ustd.append(float(u.std()))
+    share = 0.0 if dt == F32 else amb_n / (2.0 * d["x"].shape[1] * hid)
+    return dict(out=torch.stack(outs), by=torch.stack(bys), b32=torch.stack(b32s), known=torch.stack(known), share=share, u_std=ustd)
+
+
+def proj_mlp64(d, dt, use_x32=False):
+    """Plain fp64 statement of one proj_mlp launch on ANY data (weights and 16-bit operands as the storage type holds them; no
+    intermediate rounding): what close() compared against in tests/test_gpu_dmff_fused.py's style of check."""
+    q = lambda t: t.to(dt).double()
+    outs = []
+    for m in range(2):
+        co = [f32w(c) for c in d["co"]]
+        x = d["x32"][m].double() if use_x32 else q(d["x"][m])
+        xatt = co[2 * m] * x + co[2 * m + 1] * (q(d["att"][m]) @ q(d["wo"][m]).T + d["bo"][m].double())
+        dev = xatt - xatt.mean(1, keepdim=True)
+        n2 = dev / torch.sqrt((dev * dev).mean(1, keepdim=True) + f32w(d["eps"][2])) * d["ln"]["mw"].double() + d["ln"]["mb"].double()
+        h = act64(n2 @ q(d["w1"][m]).T + d["b1"][m].double(), ACT_GELU)
+        outs.append(co[4 + 2 * m] * xatt + co[5 + 2 * m] * (h @ q(d["w2"][m]).T + d["b2"][m].double()))
+    return torch.stack(outs)
+
+
+PROJ_MLP_DEFECTS = ("trunc", "swap", "lastchunk", "b1off", "halfshift", "lnswap", "erf")
+
+
+def emulate_proj_mlp(d, dt, ksplit=1, r32=False, use_x32=False, defect=None):
+    """One icaf_dmff_wide_proj_mlp launch (ksplit > 1: proj_mlp_split + reduce) in torch fp32 with the rounding points of dmff_wide.hip:
+    x_att = fma(c_res, x, (acc + b_o) c_acc), rounded to the storage type unless the fp32 stream keeps it (r32); two-pass LayerNorm on
+    that value, its output rounded to the storage type; per hidden chunk of wide_pass(C) columns h = RNE(gelu(n2 W1^T + b1)) and
+    acc2 += h W2^T in fp32, the slices of a split added in slice order; y = RNE(fma(c_res2, x_att, (acc2 + b2) c_acc2)), y32 the same
+    unrounded.  Returns (y, y32 or None).
+    defect: None | "trunc" (x_att truncated instead of rounded) | "swap" (the two modalities' coefficients exchanged) | "lastchunk" (the last
+    hidden chunk skipped) | "b1off" (a hidden-split slice reads b1 from offset 0 instead of its own columns) | "halfshift" (the second
+    32-row half of every tile takes the row below) | "lnswap" (the MLP LayerNorm with gamma / beta of the attention LayerNorm) | "erf" (a3
+    of the erf polynomial changed, as emulate())."""
+    rows, C = d["x"].shape[1], d["x"].shape[2]
+    hid, wp = d["hidden"], wide_pass(C)
+    assert use_x32 <= r32 and (ksplit == 1 or (C >= 256 and dt != F32)) and hid % (wp * ksplit) == 0
+    q = lambda t: t.to(dt).float()
+    eps_m = torch.tensor(d["eps"][2], dtype=F32)
+    fC = torch.tensor(float(C), dtype=F32)
+    coef = ERF_COEF if defect != "erf" else (ERF_COEF[0], ERF_COEF[1], 1.421513741, ERF_COEF[3], ERF_COEF[4])
+    ys, y32s = [], []
+    for m in range(2):
+        mc = 1 - m if defect == "swap" else m
+        cr_a, ca_a, cr_m, ca_m = (d["co"][2 * mc], d["co"][2 * mc + 1], d["co"][4 + 2 * mc], d["co"][5 + 2 * mc])
+        xres = d["x32"][m] if use_x32 else q(d["x"][m])
+        acc = q(d["att"][m]) @ q(d["wo"][m]).T
+        v = fma32(cr_a, xres, (acc + d["bo"][m]) * torch.tensor(ca_a, dtype=F32))
+        xatt = v if r32 else _store(v, dt, defect).float()
+        mean = xatt.sum(1, keepdim=True) / fC
+        dev = xatt - mean
+        rstd = 1.0 / torch.sqrt((dev * dev).sum(1, keepdim=True) / fC + eps_m)
+        lw, lb = (d["ln"]["a2w" if m else "a1w"], d["ln"]["a2b" if m else "a1b"]) if defect == "lnswap" else (d["ln"]["mw"], d["ln"]["mb"])
+        n2 = q(dev * rstd * lw + lb)
+        w1, w2 = q(d["w1"][m]), q(d["w2"][m])
+        per = hid // wp // ksplit
+        total = None
+        for ks in range(ksplit):
+            acc2 = torch.zeros((rows, C))
+            for ch in range(per):
+                if defect == "lastchunk" and ks == ksplit - 1 and ch == per - 1:
+                    continue
+                c0 = (ks * per + ch) * wp
+                boff = ch * wp if defect == "b1off" else c0
+                u = n2 @ w1[c0:c0 + wp].T + d["b1"][m][boff:boff + wp]
+                h = torch.erf(u * 0.70710678118654752440).add(1.0).mul(0.5 * u) if dt == F32 else q(_gelu_fast32(u, coef))
+                acc2 = acc2 + h @ w2[:, c0:c0 + wp].T
+            total = acc2 if total is None else total + acc2
+        out = fma32(cr_m, xatt, (total + d["b2"][m]) * torch.tensor(ca_m, dtype=F32))
+        if defect == "halfshift":
+            r = torch.arange(rows)
+            out = out[torch.where(r % 64 >= 32, (r + 1).clamp(max=rows - 1), r)]
+        ys.append(out.to(dt))
+        y32s.append(out)
+    return torch.stack(ys), (torch.stack(y32s) if r32 else None)
+
+
+def check_proj_mlp_a(y, y32, z, dt, what):
+    """Test (a): y == RNE(x_att) bit for bit, y32 == x_att bit for bit (z: dmff_xatt64 of the rows the launch saw)."""
+    assert_same_bits(y, rne(z, dt) + 0.0, what + ": y")
+    if y32 is not None:
+        assert_same_bits(y32, z.float() + 0.0, what + ": y32")
+
+
+def check_proj_mlp_b(y, y32, ref, dt, what):
+    """Test (b): every element of y (and of y32) within its counted bound; returns the largest err / budget of each."""
+    n = y.shape[1]
+    r = assert_budget(y, ref["out"][:, :n], ref["by"][:, :n], what + ": y", signed=False)
+    r32 = assert_budget(y32, ref["out"][:, :n], ref["b32"][:, :n], what + ": y32", signed=False) if y32 is not None else 0.0
+    return r, r32
+
+
+def dmff_operands_qkv(C, dt, rows=DMFF_ROWS_MAX, seed=0):
+    """Test (d): the rows of construction 1 (s = 0.5, eps_attn = 0.75) in both modalities, gamma / beta = j / 8 DIFFERENT for the two
+    attention LayerNorms, W_qkv = k / 2^s_w and bias = j / 2^s_f different per modality.  Returns the operands and the exact fp64 qkv
+    (2, rows, 3C): normalised rows +-0.5 gamma + beta (representable), then an exact GEMM."""
+    g = _gen(9000 + 10 * C + [F32, BF16, F16].index(dt) + seed)
+    sw, sf = GRID[dt]
+    lat8 = lambda: _nonzero(g, 16, (C,)) / 8.0
+    d = dict(x=torch.stack((exact_ln_rows(rows, C, 0.5, 9100 + C), exact_ln_rows(rows, C, 0.5, 9200 + C))),
+             wqkv=_ri(g, -2 ** sw, 2 ** sw, (2, 3 * C, C)) / 2 ** sw, bqkv=_ri(g, -64, 64, (2, 3 * C)) / 2 ** sf,
+             ln=dict(a1w=lat8(), a1b=lat8(), a2w=lat8(), a2b=lat8(), mw=torch.ones(C), mb=torch.zeros(C)),
+             co=[1.0] * 8, eps=(LN_EPS_EXACT, LN_EPS_EXACT, 1e-5), hidden=4 * C)
+    assert not torch.equal(d["ln"]["a1w"], d["ln"]["a2w"]) and not torch.equal(d["ln"]["a1b"], d["ln"]["a2b"])
+    assert_exact_ln(d["x"], LN_EPS_EXACT, dt, "qkv rows")
+    zs = []
+    for m in range(2):
+        x = d["x"][m].double()
+        mean = (x.amax(1, keepdim=True) + x.amin(1, keepdim=True)) / 2.0
+        n = (x - mean) * d["ln"]["a2w" if m else "a1w"].double() + d["ln"]["a2b" if m else "a1b"].double()
+        assert torch.equal(n.float().to(dt).double(), n)
+        z = n @ d["wqkv"][m].double().T + d["bqkv"][m].double()
+        assert torch.equal((n.float() @ d["wqkv"][m].T + d["bqkv"][m]).double(), z), "the QKV sums are not exact in fp32"
+        zs.append(z)
+    return d, torch.stack(zs)
+
+
+def dmff_take_rows(d, rows):
+    """The operands of a case cut to its first `rows` token rows (rows are independent: references are built once at DMFF_ROWS_MAX)."""
+    out = dict(d)
+    for k in ("att", "x", "x32"):
+        if k in d:
+            out[k] = d[k][:, :rows].contiguous()
+    return out
+
+
+def dmff_operands_rnd(C, rows, seed=31):
+    """Gaussian operands of one proj_mlp launch in the style of tests/test_gpu_dmff_fused.py (tokens normal(0.2, 0.8), weights of a
+    trained block's size): the data on which the self-test records what a max-norm tolerance makes of each planted defect."""
+    hid = 4 * C
+    r = lambda shape, k, scale=1.0: rnd(shape, seed + k, scale)
+    return dict(att=r((2, rows, C), 0, 0.5), wo=r((2, C, C), 1, C ** -0.5), bo=r((2, C), 2, 0.1), x=0.2 + r((2, rows, C), 3, 0.8),
+                x32=0.2 + r((2, rows, C), 4, 0.8), w1=r((2, hid, C), 5, C ** -0.5), b1=r((2, hid), 6, 0.1), w2=r((2, C, hid), 7, hid ** -0.5),
+                b2=r((2, C), 8, 0.1), co=[0.9, 0.45, 0.8, 0.55, 0.85, 0.5, 0.95, 0.4], eps=(1e-5, 1e-5, 1e-5), hidden=hid,
+                ln=dict(a1w=1.0 + r((C,), 9, 0.1), a1b=r((C,), 10, 0.1), a2w=1.0 + r((C,), 11, 0.1), a2b=r((C,), 12, 0.1),
+                        mw=1.0 + r((C,), 13, 0.1), mb=r((C,), 14, 0.1)))
+
+
+def attn_known_qkv(B, N, C, dt, seed):
+    """Test (e): a qkv tensor (2, B * N, 3C) whose attention output is known exactly.  K = 0: every score is 0, every probability of an
+    image's N keys equal, so a query's output is the MEAN of V over the keys of its image — of the modality whose K / V the direction
+    reads, whatever Q holds (random integers).  V = a per-(modality, image, channel) integer in [-8, 8] plus per-key integer
+    perturbations in [-4, 4] that sum to zero over the image: the key sum is N times the constant, exact in fp32 in any order, and the
+    mean is representable in every type.  Returns (qkv, att (2, B * N, C): that mean on every row of the image)."""
+    g = _gen(seed)
+    base = _ri(g, -8, 8, (2, B, 1, C))
+    assert not torch.equal(base[0], base[1])
+    half = _ri(g, -4, 4, (2, B, N // 2, C))
+    pert = torch.cat((half, -half, torch.zeros((2, B, N % 2, C))), 2)
+    order = torch.stack([torch.randperm(N, generator=g) for _ in range(2 * B * C)]).reshape(2, B, C, N).permute(0, 1, 3, 2)
+    v = base + torch.gather(pert, 2, order)
+    assert torch.equal(v.sum(2, keepdim=True), N * base) and torch.equal(v.to(dt).float(), v)
+    qkv = torch.cat((_ri(g, -8, 8, (2, B, N, C)), torch.zeros((2, B, N, C)), v), 3).reshape(2, B * N, 3 * C)
+    return qkv, base.expand(2, B, N, C).reshape(2, B * N, C).contiguous()

@@ -10,8 +10,8 @@ cstream / ctile / stem and the shared epilogue of conv_common.h), and LayerNorm 
 (c) a subset re-runs with NaN-prefilled outputs and NaN / Inf-poisoned surroundings of every view.
 icaf_bottleneck, icaf_stem2 and the chained / C3-tail launches apply SiLU between their stages, so their second stage never sees exact
 operands; the existing "equals two launches" bit tests tie them to the single launches checked here.  The chained launch appears in (c)
-for its store paths (y2, chain_keep) and is compared there with the two launches it replaces.  The shared LayerNorm inside
-icaf_dmff_wide_proj_mlp has no observable output of its own and is not covered.
+for its store paths (y2, chain_keep) and is compared there with the two launches it replaces.  The DMFF block kernels — the shared LayerNorm
+inside icaf_dmff_wide_proj_mlp included, on rows whose statistics are exact by choice of eps — have their gate in tests/test_gpu_exact_dmff.py.
 The kernels around the convolutions — token pooling, bilinear merge, nearest resize, channel copy, axpby and the two staging kernels —
 have the same kind of gate in tests/test_gpu_exact_pool.py (every pooling instantiation read back through ops.dmff_pool_config, the
 second pass of the grid-stride loops, the 64-bit-index instantiations through the probe knob index64).
