@@ -78,12 +78,18 @@ class FrameGeom(C.Structure):
                 ("top", C.c_int), ("left", C.c_int), ("sx", C.c_float), ("sy", C.c_float)]
 
 
+class LossParams(C.Structure):
+    _fields_ = [("box", C.c_double), ("obj", C.c_double), ("cls", C.c_double), ("cls_pw", C.c_double), ("obj_pw", C.c_double),
+                ("anchor_t", C.c_double), ("gr", C.c_double), ("cp", C.c_double), ("cn", C.c_double), ("balance", C.c_double * 5)]
+
+
 LETTERBOX_LDS_BYTES = 20480                 # ICAF_LETTERBOX_LDS_BYTES (icaf.h): the staging budget of one letterbox workgroup
 RESIZE_LDS_BYTES = 20480                    # ICAF_RESIZE_LDS_BYTES: the fp32 rows one icaf_resize_frames workgroup keeps between its two passes
 RESIZE_MAX_TAPS = 8                         # ICAF_RESIZE_MAX_TAPS: taps per output whose weights it tabulates
 MISSRATE_MAX_DET, MISSRATE_KEEP, MISSRATE_MAX_LABELS, MISSRATE_SETUPS = 1024, 1000, 256, 7     # ICAF_MISSRATE_*: store rows / maxDets / labels per image / set-ups
 
 CONFLUENCE_MAX_CAND = 4096                  # ICAF_CONFLUENCE_MAX_CAND: candidates per image whose class members fit the LDS of one CU
+LOSS_MAX_LEVELS, LOSS_MAX_ANCHORS, LOSS_MAX_TARGETS, LOSS_SLOT_INTS = 5, 8, 4096, 10      # ICAF_LOSS_*: levels / anchors per level / targets per call / words of a slot record
 
 
 _p, _i, _ll, _f, _sz =C.c_void_p, C.c_int, C.c_longlong, C.c_float, C.c_size_t
@@ -139,6 +145,8 @@ SIGNATURES = {
     "icaf_confluence_select": (_i, [_p, _p, _i, _i, _i, C.c_double, _p, _p, _p, _p]),
     "icaf_confluence_workspace_bytes": (_i, [_i, _ll, _i, _i, C.POINTER(_sz)]),
     "icaf_confluence": (_i, [_p, _i, _ll, _i, _f, C.c_double, _i, _p, _p, _p, _p, _sz, _p]),
+    "icaf_loss_workspace_bytes": (_i, [_i, C.POINTER(_i), C.POINTER(_i), _i, _i, _i, C.POINTER(_sz), C.POINTER(_sz), C.POINTER(_sz)]),
+    "icaf_loss": (_i, [C.POINTER(_p), C.POINTER(_i), C.POINTER(_i), _i, _i, _i, _i, C.POINTER(_f), _p, _i, C.POINTER(LossParams), _p, _p, _p, _sz, _p]),
     "icaf_graph_begin": (_i, [_p]),
     "icaf_graph_end": (_i, [_p, C.POINTER(_p)]),
     "icaf_graph_launch": (_i, [_p, _p]),

@@ -1019,6 +1019,67 @@ class ConfluenceRunner:
         return self.det, self.count, self.keep
 
 
+LOSS_MAX_LEVELS, LOSS_MAX_ANCHORS, LOSS_MAX_TARGETS, LOSS_SLOT_INTS = _lib.LOSS_MAX_LEVELS, _lib.LOSS_MAX_ANCHORS, _lib.LOSS_MAX_TARGETS, _lib.LOSS_SLOT_INTS
+
+
+def loss_workspace(shapes, B, na, nt):
+    """icaf_loss_workspace_bytes for `nt` targets: (bytes, tobj_off [nl], slots_off [nl]) — byte offsets from the workspace's start; tobj_off
+    does not depend on nt."""
+    nl = len(shapes)
+    ny, nx = (C.c_int * max(nl, 1))(*[int(s[0]) for s in shapes]), (C.c_int * max(nl, 1))(*[int(s[1]) for s in shapes])
+    sz, toff, soff = C.c_size_t(0), (C.c_size_t * max(nl, 1))(), (C.c_size_t * max(nl, 1))()
+    check(lib().icaf_loss_workspace_bytes(nl, ny, nx, int(B), int(na), int(nt), C.byref(sz), toff, soff), "loss_workspace")
+    return sz.value, list(toff)[:nl], list(soff)[:nl]
+
+
+def loss_params_block(prm):
+    """dict (utils.loss.loss_params) -> icaf_loss_params"""
+    blk = _lib.LossParams(*[float(prm[k]) for k in ("box", "obj", "cls", "cls_pw", "obj_pw", "anchor_t", "gr", "cp", "cn")])
+    for i, b in enumerate(prm["balance"][:5]):
+        blk.balance[i] = float(b)
+    return blk
+
+
+def loss_launch(maps, shapes, B, na, nc, anchors, targets, prm, out, counts, ws, nl=None, ws_bytes=None, stream_ptr=None):
+    """The raw icaf_loss call, status returned unchecked (the refusal tests read it): maps a list of data pointers, anchors a host fp32
+    array (nl, na, 2), targets a device (nt, 6) fp32 tensor, out (4,) fp32 / counts (nl,) int32 / ws uint8 device tensors."""
+    nl = len(shapes) if nl is None else nl
+    ptrs = (C.c_void_p * 8)(*([int(m) if m else None for m in maps] + [None] * (8 - len(maps))))
+    ny, nx = (C.c_int * 8)(*([int(s[0]) for s in shapes] + [0] * (8 - len(shapes)))), (C.c_int * 8)(*([int(s[1]) for s in shapes] + [0] * (8 - len(shapes))))
+    anc = np.ascontiguousarray(anchors, np.float32)
+    blk = loss_params_block(prm)
+    return lib().icaf_loss(ptrs, ny, nx, int(nl), int(B), int(na), int(nc), anc.ctypes.data_as(C.POINTER(C.c_float)), targets.data_ptr(),
+                           int(targets.shape[0]), C.byref(blk), out.data_ptr(), counts.data_ptr(), ws.data_ptr(),
+                           ws.numel() if ws_bytes is None else int(ws_bytes), stream_ptr if stream_ptr is not None else current_stream_ptr())
+
+
+class LossRunner:
+    """Pre-allocated validation-loss launch (icaf_loss: the forward value of the reference's ComputeLoss, no gradients) for a fixed
+    (B, level shapes, na, nc): owns the workspace (sized for LOSS_MAX_TARGETS, so any batch's target table fits), the four output values and
+    the per-level match counts; results stay on the device, no host sync.  loss_workspace() says where the tobj maps and the slot tables
+    of the last launch lie in `ws`."""
+
+    def __init__(self, B, shapes, na, nc, anchors, device, max_targets=LOSS_MAX_TARGETS):
+        self.B, self.shapes, self.na, self.nc = int(B), [tuple(int(v) for v in s) for s in shapes], int(na), int(nc)
+        self.anchors = np.ascontiguousarray(anchors.numpy() if torch.is_tensor(anchors) else anchors, np.float32).reshape(len(self.shapes), self.na, 2)
+        self.max_targets = int(max_targets)
+        nbytes, self.tobj_off, _ = loss_workspace(self.shapes, self.B, self.na, self.max_targets)
+        self.ws = torch.empty((nbytes,), dtype=torch.uint8, device=device)
+        self.out = torch.zeros((4,), dtype=torch.float32, device=device)
+        self.counts = torch.zeros((len(self.shapes),), dtype=torch.int32, device=device)
+
+    def launch(self, maps, targets, prm, stream_ptr=None):
+        assert len(maps) == len(self.shapes) and targets.dtype == torch.float32 and targets.is_contiguous() and targets.dim() == 2 and targets.shape[1] == 6
+        for m, (ny, nx) in zip(maps, self.shapes):
+            assert m.dtype == torch.float32 and m.is_contiguous() and m.shape == (self.B, self.na, ny, nx, 5 + self.nc)
+        if targets.shape[0] > self.max_targets:
+            raise ValueError(f"LossRunner: {targets.shape[0]} targets, the workspace was sized for {self.max_targets}")
+        st = loss_launch([m.data_ptr() for m in maps], self.shapes, self.B, self.na, self.nc, self.anchors, targets, prm, self.out, self.counts,
+                         self.ws, stream_ptr=stream_ptr)
+        check(st, "icaf_loss")
+        return self.out, self.counts
+
+
 # ------------------------------------------------------------------------------------------------------------
 # native camera frames: device letterbox in, native-space boxes out
 # ------------------------------------------------------------------------------------------------------------

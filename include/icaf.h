@@ -570,6 +570,44 @@ int icaf_confluence_workspace_bytes(int B, long long rows, int nc, int max_cand,
 int icaf_confluence(const float* pred, int B, long long rows, int nc, float conf_thres, double p_thres, int max_cand, float* det,
                     int* count, int* keep_idx, void* workspace, size_t workspace_bytes, icaf_stream_t s);
 
+/* ---- Validation loss: the forward value of ComputeLoss (utils/loss.py:325-463; test.py:112,132-133,364-367) -------------------------
+ * The box / objectness / class loss of a batch from the raw Detect maps p[i] [B][na][ny_i][nx_i][5+nc] fp32 and the target table [nt][6] fp32
+ * (image, class, x, y, w, h; normalised) — the VALUE only: no gradient is computed and nothing is kept for one.
+ * Target assignment (build_targets, :409-463), level i, gain = [nx_i, ny_i, nx_i, ny_i] (p[i].shape[[3, 2, 3, 2]]), separate fp32 operations
+ *   in the reference's order: t = targets * gain; r = t.wh / anchors[i][a]; target t joins anchor a when max(r, 1 / r).max() < anchor_t (fp32);
+ *   gxy = t.xy, gxi = gain.xy - gxy; j, k = (gxy % 1. < 0.5) & (gxy > 1.), l, m likewise on gxi; the row is repeated for the offsets
+ *   off = {(0, 0), (0.5, 0), (0, 0.5), (-0.5, 0), (0, -0.5)} that hold (the first always); gij = (gxy - off).long() truncates.
+ * SLOT LAYOUT: level i has 5 * na * nt slots, slot index (off * na + a) * nt + t; a slot is valid or not.  The valid slots of a level in slot
+ *   order are the reference's rows in the reference's order (targets.repeat(na, 1, 1)[j] is (anchor, target)-major, t.repeat((5, 1, 1))[j]
+ *   puts the offset outermost).  A slot record is ICAF_LOSS_SLOT_INTS = 10 32-bit words {valid, b, a, gj, gi, tbox[4] (fp32 bits), tcls}, zeros
+ *   when not valid; level i's records start at slots_off[i] of the workspace.
+ * CLAMP TRAP: :457 clamps gj / gi in place on views of gij, so tbox = gxy - gij (:458) uses the CLAMPED indices (a centre at x or y = 1.0).
+ * Per valid slot (:362-388), in fp64 on the fp32 logits: pxy = sigmoid * 2 - 0.5, pwh = (sigmoid * 2)^2 * anchor, CIoU against tbox
+ *   (bbox_iou(x1y1x2y2=False, CIoU=True), utils/general.py:410-452, eps 1e-7); lbox = sum over levels with a match of mean(1 - iou); for nc > 1
+ *   lcls = sum over those levels of mean over matches x classes of BCE-with-logits(pos_weight cls_pw) against cn everywhere, cp at tcls.
+ * Objectness: tobj[b, a, gj, gi] = (1 - gr) + gr * max(iou, 0) (fp32).  DUPLICATE RULE: several slots may hit one cell; the reference sorts by
+ *   iou ascending before the scatter (:379-382), so the LARGEST value stays — here an integer atomic max on the float's bits into the zeroed
+ *   dense map, which needs non-negative values: gr outside [0, 1] is refused.  lobj = sum_i balance[i] * mean(BCE-with-logits(p_i[..., 4],
+ *   tobj_i; pos_weight obj_pw)); level i's tobj map [B][na][ny_i][nx_i] fp32 starts at tobj_off[i] of the workspace.
+ * out[4] = {lbox * box, lobj * obj, lcls * cls, 0} fp32 (the rank loss is never accumulated, :391), counts[nl] the matches per level.  Sums are
+ *   fp64, two-stage, in a fixed order (no float atomics): two calls on the same inputs give the same bits.  anchors [nl][na][2] (grid units) and
+ *   prm are HOST memory; maps is a host array of nl device pointers; everything else lives on the device.  anchor_t is compared in fp32.
+ * Departures: a target whose image index is outside [0, B) is skipped and a class outside [0, nc) marks no positive (the reference raises).
+ * REFUSALS, all before any launch, outputs and workspace untouched, nothing is ever truncated: ICAF_ERR_UNSUPPORTED for nl outside [1, 5], na
+ *   outside [1, 8], nt > ICAF_LOSS_MAX_TARGETS = 4096, a level of more than 2^31 cells; ICAF_ERR_ARG for null pointers (a null map included),
+ *   nc < 1, B < 1, nt < 0, an empty map, gr outside [0, 1] (NaN included), a short or misaligned workspace.  nt = 0 is valid (:444-446):
+ *   lbox = lcls = 0 and lobj against an all-zero tobj.  Workspace: icaf_loss_workspace_bytes (tobj_off / slots_off [nl], bytes from its start,
+ *   may be NULL; tobj_off does not depend on nt), 256-byte aligned, contents irrelevant on entry (the call zeroes its own tobj).  One memset
+ *   and three kernels on `s`, no host synchronisation. */
+enum { ICAF_LOSS_MAX_LEVELS = 5, ICAF_LOSS_MAX_ANCHORS = 8, ICAF_LOSS_MAX_TARGETS = 4096, ICAF_LOSS_SLOT_INTS = 10 };
+typedef struct icaf_loss_params {
+    double box, obj, cls, cls_pw, obj_pw, anchor_t, gr, cp, cn, balance[5];
+} icaf_loss_params;
+int icaf_loss_workspace_bytes(int nl, const int* ny, const int* nx, int B, int na, int nt, size_t* bytes, size_t* tobj_off, size_t* slots_off);
+int icaf_loss(const float* const* maps, const int* ny, const int* nx, int nl, int B, int na, int nc, const float* anchors,
+              const float* targets, int nt, const icaf_loss_params* prm, float* out, int* counts, void* workspace, size_t workspace_bytes,
+              icaf_stream_t s);
+
 /* ---- HIP graph capture / events (so the Python host never needs a tracing compiler) ------------------------ */
 int icaf_graph_begin(icaf_stream_t s);
 int icaf_graph_end(icaf_stream_t s, void** graph_exec);

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Validation loop (mAP@0.5, mAP@0.5:0.95) of the two-stream detector on MI355X — the reference's test.py:23-330 reduced
 to its metric path: paired RGB/IR loader -> forward -> NMS(multi_label) -> per-image TP matching at 10 IoU thresholds ->
-ap_per_class.  `test(...)` keeps the reference's return value ((mp, mr, map50, map, 0, 0, 0), maps, times).
+ap_per_class.  `test(...)` keeps the reference's return value ((mp, mr, map50, map, lbox, lobj, lcls), maps, times); the three losses are 0
+unless a loss is asked for (below).
 
     python test.py --data data/multispectral/kaist.yaml --weights best.pt --batch-size 32 --img-size 640
     python test.py --data ... --cfg models/transformer/yolov5s_Transfusion_kaist.yaml      (synthetic weights: plumbing)
@@ -16,7 +17,10 @@ device, FPPI sweep in numpy; icafusion_amd/utils/missrate.py) and returns its di
 `--task speed` runs at conf 0.25 / IoU 0.45 as the reference does.  `--device-letterbox` uploads the frames as decoded: the loader's
 longest-side resize (pixel-area average when shrinking) and the padding run on the device (Model.forward_frames(val_size=...)).
 `--confluence P_THRES` swaps the suppression step for the reference's confluence (its commented line test.py:140; utils/confluence.py) and leaves
-everything downstream as it is; an image whose candidates exceed the confluence cap, or that keeps more than 1024 boxes, raises.  Not carried over (all outside the metric): plots / wandb /
+everything downstream as it is; `--hyp PATH` (or `test(compute_loss=...)`, as the reference's train.py:257,393 calls it) adds the validation
+loss — the forward value of the reference's ComputeLoss on the raw Detect maps of every batch (utils/loss.py:325-463; icaf_loss, no gradients),
+averaged over the batches as test.py:132-133,364-367 do, with the hyp gains scaled as train.py:238-241 scales them — fills the three trailing
+values and prints one `Loss:` line; there is no default hyp file, and without the flag nothing changes.  An image whose candidates exceed the confluence cap, or that keeps more than 1024 boxes, raises.  Not carried over (all outside the metric): plots / wandb /
 `--save-hybrid` auto-labelling / `--task study` / the pycocotools call / MR curves and plots; `--augment` raises (test-time augmentation is not built)."""
 import argparse
 import os
@@ -33,6 +37,7 @@ from icafusion_amd import ops
 from icafusion_amd.utils.general import check_img_size, increment_path, nms_device, scale_coords, xywh2xyxy
 from icafusion_amd.utils import missrate
 from icafusion_amd.utils.confluence import confluence_device
+from icafusion_amd.utils.loss import ComputeLoss, scale_hyp
 from icafusion_amd.utils.results import ResultWriter, frame_index, label_listing
 from icafusion_amd.utils.metrics import ap_per_class
 from icafusion_amd.utils.torch_utils import select_device, time_synchronized
@@ -110,7 +115,7 @@ class MissRate:
 @torch.no_grad()
 def test(data, weights=None, batch_size=32, imgsz=640, conf_thres=0.001, iou_thres=0.5, single_cls=False, model=None,
          dataloader=None, device="0", compute_dtype=None, cfg=None, verbose=False, save_json=False, save_txt=False, save_conf=True,
-         save_dir=None, augment=False, confluence=None, miss_rate=None, device_letterbox=False):
+         save_dir=None, augment=False, compute_loss=None, confluence=None, miss_rate=None, device_letterbox=False):
     if augment:
         raise NotImplementedError("test-time augmentation (models/yolo_test.py:116-132) is outside the inference hot path")
     if isinstance(data, str):
@@ -120,17 +125,7 @@ def test(data, weights=None, batch_size=32, imgsz=640, conf_thres=0.001, iou_thr
     if miss_rate and nc > 1:
         raise ValueError(f"the KAIST miss rate is a one-class (person) metric: {nc} classes need --single-cls")
     if model is None:
-        dev = select_device(device)
-        if weights:
-            model = attempt_load(weights, map_location="cpu")
-        else:
-            from icafusion_amd.synth import synth_state_dict
-            model = Model(cfg, nc=nc).eval()
-            model.load_state_dict(synth_state_dict(model, seed=0))
-            model = model.fuse().eval()
-        model = model.to(dev)
-        model.compute_dtype = compute_dtype
-        model.use_graph = True
+        model = load_model(weights, cfg, nc, device, compute_dtype)
     dev = next(model.parameters()).device
     if dataloader is None:
         gs = int(max(float(model.stride.max()), 32))                      # grid size = max stride (test.py:68)
@@ -146,18 +141,22 @@ def test(data, weights=None, batch_size=32, imgsz=640, conf_thres=0.001, iou_thr
     iouv = np.linspace(0.5, 0.95, 10)
     names = data.get("names", [str(i) for i in range(nc)])
     stats, seen, t_inf, t_nms = [], 0, 0.0, 0.0
+    loss = torch.zeros(3, device=dev) if compute_loss else None          # box, obj, cls: summed on the device, read once after the loop
     for img, targets, paths, shapes in dataloader:
         if device_letterbox:                                     # native BGR frames as decoded: resized and padded on the device
             rgb, ir, (height, width) = img
             rgb, ir, nb = [f.to(dev, non_blocking=True) for f in rgb], [f.to(dev, non_blocking=True) for f in ir], len(rgb)
             t = time_synchronized()
-            out = model.forward_frames(rgb, ir, img_size=(height, width), val_size=imgsz)[0][0]
+            res = model.forward_frames(rgb, ir, img_size=(height, width), val_size=imgsz)[0]
         else:
             img = img.to(dev, non_blocking=True)                 # uint8 (B, 6, H, W): cat(rgb, ir), test.py:116-123
             nb, _, height, width = img.shape
             t = time_synchronized()
-            out = model.forward_u8(img)[0]
+            res = model.forward_u8(img)
+        out = res[0]
         t_inf += time_synchronized() - t
+        if compute_loss:                                         # on the raw maps, before the labels go to pixels (test.py:132-133)
+            loss += compute_loss(res[2], targets.to(dev))[1][:3]
         targets = targets.clone()
         targets[:, 2:] *= torch.tensor([width, height, width, height])
         t = time_synchronized()
@@ -213,11 +212,14 @@ def test(data, weights=None, batch_size=32, imgsz=640, conf_thres=0.001, iou_thr
     print("\n".join(lines))
     tt = tuple(x / max(seen, 1) * 1e3 for x in (t_inf, t_nms, t_inf + t_nms)) + (imgsz, imgsz, batch_size)
     print("Speed: %.1f/%.1f/%.1f ms inference/NMS/total per %gx%g image at batch-size %g" % tt)
+    lbox, lobj, lcls = (loss.cpu() / len(dataloader)).tolist() if compute_loss else (0.0, 0.0, 0.0)       # test.py:364-367
+    if compute_loss:
+        print("Loss: %.5g box, %.5g obj, %.5g cls (mean of %d batches)" % (lbox, lobj, lcls, len(dataloader)))
     if mr_eval:
         mr_dict = mr_eval.finish()
         print("\n".join(missrate.format_lines(mr_dict)))
-        return (mp, mr, map50, map_, 0.0, 0.0, 0.0), maps, tt, mr_dict
-    return (mp, mr, map50, map_, 0.0, 0.0, 0.0), maps, tt
+        return (mp, mr, map50, map_, lbox, lobj, lcls), maps, tt, mr_dict
+    return (mp, mr, map50, map_, lbox, lobj, lcls), maps, tt
 
 
 def parse_opt(argv=None):
@@ -243,6 +245,8 @@ def parse_opt(argv=None):
                      help="KAIST annotation JSON: also report the log-average miss rate (All / Day / Night, scale and occlusion subsets)")
     ap_.add_argument("--confluence", type=float, default=None, metavar="P_THRES",
                      help="suppress with confluence (normalised Manhattan proximity below P_THRES, utils/confluence.py) instead of NMS")
+    ap_.add_argument("--hyp", type=str, default=None, metavar="PATH",
+                     help="hyperparameter yaml: also report the validation loss (box / obj / cls, the forward value of ComputeLoss)")
     ap_.add_argument("--save-txt", action="store_true", help="per-image result lines + result.txt under <project>/<name>/labels")
     ap_.add_argument("--save-conf", action="store_true", help="append the confidence to every --save-txt line")
     ap_.add_argument("--save-json", action="store_true", help="<project>/<name>/<weights>_predictions.json")
@@ -251,6 +255,31 @@ def parse_opt(argv=None):
     ap_.add_argument("--name", default="exp")
     ap_.add_argument("--exist-ok", action="store_true")
     return ap_.parse_args(argv)
+
+
+def loss_from_hyp(path, model, nc, imgsz):
+    """`--hyp PATH`: the yaml with the gains scaled as train.py:238-241 scales them, set on the model as train.py:243-245 does (model.hyp,
+    model.gr = 1.0), and the ComputeLoss built from it."""
+    with open(path) as f:
+        hyp = yaml.safe_load(f)
+    model.hyp, model.gr = scale_hyp(hyp, model.model[-1].nl, nc, imgsz), 1.0
+    return ComputeLoss(model)
+
+
+def load_model(weights, cfg, nc, device, compute_dtype):
+    """The model test() would build itself — the CLI needs it beforehand when a ComputeLoss is to be made from it."""
+    dev = select_device(device)
+    if weights:
+        model = attempt_load(weights, map_location="cpu")
+    else:
+        from icafusion_amd.synth import synth_state_dict
+        model = Model(cfg, nc=nc).eval()
+        model.load_state_dict(synth_state_dict(model, seed=0))
+        model = model.fuse().eval()
+    model = model.to(dev)
+    model.compute_dtype = compute_dtype
+    model.use_graph = True
+    return model
 
 
 if __name__ == "__main__":
@@ -268,6 +297,12 @@ if __name__ == "__main__":
                  device_letterbox=o.device_letterbox)
     else:
         save_dir = increment_path(os.path.join(o.project, o.name), exist_ok=o.exist_ok) if (o.save_txt or o.save_json) else None
+        model, compute_loss = None, None
+        if o.hyp:
+            with open(o.data) as f:
+                nc = 1 if o.single_cls else int(yaml.safe_load(f)["nc"])
+            model = load_model(o.weights, o.cfg, nc, o.device, dtype)
+            compute_loss = loss_from_hyp(o.hyp, model, nc, imgsz)
         test(o.data, o.weights, o.batch_size, imgsz, o.conf_thres, o.iou_thres, o.single_cls, device=o.device, compute_dtype=dtype, cfg=o.cfg,
              verbose=o.verbose, save_json=o.save_json, save_txt=o.save_txt, save_conf=o.save_conf, save_dir=save_dir, augment=o.augment,
-             miss_rate=o.miss_rate, device_letterbox=o.device_letterbox, confluence=o.confluence)
+             miss_rate=o.miss_rate, device_letterbox=o.device_letterbox, confluence=o.confluence, model=model, compute_loss=compute_loss)
