@@ -1,169 +1,137 @@
-"""ctypes binding of libicaf.so (C ABI declared in include/icaf.h).
+"""ctypes binding of libicaf.so, derived from include/icaf.h: the header is the one definition of the C ABI.
 
+Nothing of the header is repeated here.  `parse_header` reads its enums, structs and prototypes; the module then builds from them the constants
+(ICAF_F32 -> F32), the C.Structure classes (icaf_conv_args -> ConvArgs) and SIGNATURES.  A new entry point is declared in icaf.h, with ICAF_HOST in
+front of every pointer parameter that is host memory, and nowhere else.
 The HIP library is the product: there is no CPU or PyTorch fallback.  `lib()` raises if the shared object is
 missing or does not export every symbol of the header, so a GPU box that silently lost the extension fails loudly.
 """
+import collections
 import ctypes as C
 import os
+import re
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("ICAF_LIB") or os.path.join(_HERE, "lib", "libicaf.so")   # ICAF_LIB: A/B a variant build (tools/)
-
-F32, BF16, F16 = 0, 1, 2
-ACT_NONE, ACT_SILU, ACT_GELU, ACT_RELU = 0, 1, 2, 3
-
-
-class ConvArgs(C.Structure):
-    _fields_ = [
-        ("x", C.c_void_p), ("w", C.c_void_p), ("bias", C.c_void_p), ("y", C.c_void_p), ("res", C.c_void_p),
-        ("x_gs", C.c_longlong), ("w_gs", C.c_longlong), ("bias_gs", C.c_longlong), ("y_gs", C.c_longlong),
-        ("res_gs", C.c_longlong),
-        ("groups", C.c_int),
-        ("B", C.c_int), ("H", C.c_int), ("W", C.c_int), ("Cin", C.c_int), ("ldx", C.c_int),
-        ("Ho", C.c_int), ("Wo", C.c_int), ("Cout", C.c_int), ("ldy", C.c_int),
-        ("kh", C.c_int), ("kw", C.c_int), ("sh", C.c_int), ("sw", C.c_int), ("ph", C.c_int), ("pw", C.c_int),
-        ("ldr", C.c_int), ("Kp", C.c_int), ("act", C.c_int), ("dtype", C.c_int), ("out_dtype", C.c_int),
-        ("alpha_acc", C.c_float * 2), ("alpha_res", C.c_float * 2),
-        ("tile", C.c_int),
-        ("pre", C.c_void_p), ("pre_h", C.c_int), ("pre_w", C.c_int), ("ldpre", C.c_int), ("pre_mode", C.c_int),
-        ("w2", C.c_void_p), ("bias2", C.c_void_p), ("y2", C.c_void_p),
-        ("w2_gs", C.c_longlong), ("bias2_gs", C.c_longlong), ("y2_gs", C.c_longlong),
-        ("Kp2", C.c_int), ("Cout2", C.c_int), ("ldy2", C.c_int), ("chain_keep", C.c_int),
-        ("wf", C.c_void_p), ("wf_gs", C.c_longlong),
-        ("x2", C.c_void_p), ("x2_gs", C.c_longlong), ("ldx2", C.c_int), ("res_mode", C.c_int),
-    ]
-
-
-class BneckArgs(C.Structure):
-    _fields_ = [("conv", ConvArgs), ("w1", C.c_void_p), ("bias1", C.c_void_p), ("w1_gs", C.c_longlong),
-                ("bias1_gs", C.c_longlong), ("Kp1", C.c_int), ("shape", C.c_int),
-                ("x2", C.c_void_p), ("x2_gs", C.c_longlong), ("ldx2", C.c_int), ("reserved", C.c_int)]
-
-
-class Stem2Args(C.Structure):
-    _fields_ = [("img", C.c_void_p), ("img_u8", C.c_int), ("ctot", C.c_int),
-                ("dtype", C.c_int), ("nstreams", C.c_int), ("B", C.c_int), ("H", C.c_int), ("W", C.c_int),
-                ("w0", C.c_void_p), ("bias0", C.c_void_p), ("w0_gs", C.c_longlong), ("bias0_gs", C.c_longlong),
-                ("Kp0", C.c_int), ("C0", C.c_int),
-                ("w1", C.c_void_p), ("bias1", C.c_void_p), ("w1_gs", C.c_longlong), ("bias1_gs", C.c_longlong),
-                ("Kp1", C.c_int), ("C1", C.c_int),
-                ("w2", C.c_void_p), ("bias2", C.c_void_p), ("w2_gs", C.c_longlong), ("bias2_gs", C.c_longlong),
-                ("Kp2", C.c_int), ("C2", C.c_int),
-                ("y", C.c_void_p), ("y_gs", C.c_longlong), ("ldy", C.c_int), ("reserved", C.c_int)]
-
-
-class DmffArgs(C.Structure):
-    _fields_ = [("x", C.c_void_p), ("qkv", C.c_void_p), ("y", C.c_void_p),
-                ("wqkv", C.c_void_p), ("bqkv", C.c_void_p), ("wo", C.c_void_p), ("bo", C.c_void_p),
-                ("w1", C.c_void_p), ("b1", C.c_void_p), ("w2", C.c_void_p), ("b2", C.c_void_p),
-                ("ln_attn_gamma", C.c_void_p * 2), ("ln_attn_beta", C.c_void_p * 2),
-                ("ln_mlp_gamma", C.c_void_p), ("ln_mlp_beta", C.c_void_p),
-                ("wqkv_gs", C.c_longlong), ("bqkv_gs", C.c_longlong), ("wo_gs", C.c_longlong), ("bo_gs", C.c_longlong),
-                ("w1_gs", C.c_longlong), ("b1_gs", C.c_longlong), ("w2_gs", C.c_longlong), ("b2_gs", C.c_longlong),
-                ("x_gs", C.c_longlong), ("y_gs", C.c_longlong),
-                ("dtype", C.c_int), ("B", C.c_int), ("N", C.c_int), ("C", C.c_int), ("heads", C.c_int), ("Kp", C.c_int),
-                ("Kp4", C.c_int), ("hidden", C.c_int), ("ldy", C.c_int), ("reserved", C.c_int),
-                ("eps_attn", C.c_float), ("eps_mlp", C.c_float),
-                ("coef_res_attn", C.c_float * 2), ("coef_acc_attn", C.c_float * 2),
-                ("coef_res_mlp", C.c_float * 2), ("coef_acc_mlp", C.c_float * 2), ("debug_clock", C.c_void_p),
-                ("x32", C.c_void_p), ("y32", C.c_void_p)]          # fp32 residual stream across iterations (icaf.h)
-
-
-class TtaPass(C.Structure):
-    _fields_ = [("dst", C.c_void_p), ("Hr", C.c_int), ("Wr", C.c_int), ("Hp", C.c_int), ("Wp", C.c_int), ("flip", C.c_int), ("reserved", C.c_int)]
-
-
-class FrameGeom(C.Structure):
-    _fields_ = [("offset", C.c_longlong), ("h0", C.c_int), ("w0", C.c_int), ("pitch", C.c_int), ("ch", C.c_int), ("nh", C.c_int), ("nw", C.c_int),
-                ("top", C.c_int), ("left", C.c_int), ("sx", C.c_float), ("sy", C.c_float)]
-
-
-class LossParams(C.Structure):
-    _fields_ = [("box", C.c_double), ("obj", C.c_double), ("cls", C.c_double), ("cls_pw", C.c_double), ("obj_pw", C.c_double),
-                ("anchor_t", C.c_double), ("gr", C.c_double), ("cp", C.c_double), ("cn", C.c_double), ("balance", C.c_double * 5)]
-
-
-LETTERBOX_LDS_BYTES = 20480                 # ICAF_LETTERBOX_LDS_BYTES (icaf.h): the staging budget of one letterbox workgroup
-RESIZE_LDS_BYTES = 20480                    # ICAF_RESIZE_LDS_BYTES: the fp32 rows one icaf_resize_frames workgroup keeps between its two passes
-RESIZE_MAX_TAPS = 8                         # ICAF_RESIZE_MAX_TAPS: taps per output whose weights it tabulates
-MISSRATE_MAX_DET, MISSRATE_KEEP, MISSRATE_MAX_LABELS, MISSRATE_SETUPS = 1024, 1000, 256, 7     # ICAF_MISSRATE_*: store rows / maxDets / labels per image / set-ups
-
-CONFLUENCE_MAX_CAND = 4096                  # ICAF_CONFLUENCE_MAX_CAND: candidates per image whose class members fit the LDS of one CU
-LOSS_MAX_LEVELS, LOSS_MAX_ANCHORS, LOSS_MAX_TARGETS, LOSS_SLOT_INTS = 5, 8, 4096, 10      # ICAF_LOSS_*: levels / anchors per level / targets per call / words of a slot record
-
-
-_p, _i, _ll, _f, _sz =C.c_void_p, C.c_int, C.c_longlong, C.c_float, C.c_size_t
-# symbol -> (restype, argtypes); must list every function declared in include/icaf.h
-SIGNATURES = {
-    "icaf_last_error": (C.c_char_p, []),
-    "icaf_set_option": (_i, [C.c_char_p, _i]),
-    "icaf_version": (_i, []),
-    "icaf_device_info": (_i, [C.POINTER(_i), C.POINTER(_i), C.c_char_p, _i]),
-    "icaf_preprocess_nchw": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _i, _p]),
-    "icaf_preprocess_u8": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p]),
-    "icaf_stem": (_i, [_p, _i, _i, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _ll, _ll, _ll, _p]),
-    "icaf_stem2": (_i, [C.POINTER(Stem2Args), _p]),
-    "icaf_vgg_stem": (_i, [_p, _i, _i, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _ll, _ll, _ll, _p]),
-    "icaf_conv2d": (_i, [C.POINTER(ConvArgs), _p]),
-    "icaf_bottleneck": (_i, [C.POINTER(BneckArgs), _p]),
-    "icaf_conv2d_kernel_name": (_i, [C.POINTER(ConvArgs), C.c_char_p, _i]),
-    "icaf_conv2d_config_ids": (_i, [C.POINTER(_i), _i]),
-    "icaf_sppf_pool": (_i, [_p, _i, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p]),
-    "icaf_sppf_config": (_i, [_i, _i, _i, _i, C.POINTER(_i)]),
-    "icaf_upsample_nearest": (_i, [_p, _i, _p, _i, _i, _i, _i, _i, _i, _i, _p]),
-    "icaf_maxpool2d": (_i, [_p, _i, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p]),
-    "icaf_copy_channels": (_i, [_p, _i, _p, _i, _i, _ll, _i, _p]),
-    "icaf_axpby": (_i, [_p, _i, _p, _i, _p, _i, _i, _ll, _i, _f, _f, _p]),
-    "icaf_dmff_pool_tokens": (_i, [_p, _i, _p, _i, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i,
-                                   _f, _f, _f, _f, _p]),
-    "icaf_layernorm": (_i, [_p, _p, _p, _p, _p, _p, _i, _ll, _i, _i, _f, _p]),
-    "icaf_cross_attention": (_i, [_p, _p, _i, _i, _i, _i, _i, _p]),
-    "icaf_dmff_pool_config": (_i, [_i] * 11 + [C.POINTER(_i)] * 4),
-    "icaf_cross_attention_config": (_i, [_i, _i, _i, _i, _i, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)]),
-    "icaf_cross_attention_form": (_i, [_i, _i, _i, _i, _i, C.POINTER(_i)]),
-    "icaf_dmff_ln_qkv": (_i, [C.POINTER(DmffArgs), _p]),
-    "icaf_dmff_attn_mlp": (_i, [C.POINTER(DmffArgs), _p]),
-    "icaf_dmff_wide_ln_qkv": (_i, [C.POINTER(DmffArgs), _p]),
-    "icaf_dmff_wide_proj_mlp": (_i, [C.POINTER(DmffArgs), _p, _p]),
-    "icaf_dmff_wide_proj_mlp_split": (_i, [C.POINTER(DmffArgs), _p, _p, _i, _p]),
-    "icaf_dmff_wide_reduce": (_i, [C.POINTER(DmffArgs), _p, _i, _p]),
-    "icaf_dmff_attn_mlp_lds_bytes": (_i, [_i, _i, _i, _i, C.POINTER(_sz)]),
-    "icaf_dmff_upsample_merge": (_i, [_p, _p, _i, _p, _i, _p, _i, _i, _i, _i, _i, _i, _i, _i, _p]),
-    "icaf_detect_decode": (_i, [_p, _i, _p, _p, _p, _i, _i, _i, _i, _i, _ll, _ll, _f, C.POINTER(_f), _p]),
-    "icaf_detect_decode_kernel": (_i, [_p, _i, _p, _p, _i, _i, _i, _i, _i, C.POINTER(_i)]),
-    "icaf_detect_conv": (_i, [C.POINTER(ConvArgs), _p, _p, _p, _i, _i, _ll, _ll, _f, C.POINTER(_f), _p]),
-    "icaf_tta_stage": (_i, [_p, _i, _i, _i, _i, _i, C.POINTER(TtaPass), _i, _p]),
-    "icaf_tta_merge": (_i, [C.POINTER(_p), C.POINTER(_ll), C.POINTER(_f), C.POINTER(_i), _i, _p, _i, _i, _f, _p]),
-    "icaf_letterbox_frames": (_i, [_p, _p, _i, _i, _p, _i, _i, _i, _i, _p]),
-    "icaf_resize_frames": (_i, [_p, _p, _p, _i, _i, _p, _i, _i, _i, _i, _p]),
-    "icaf_scale_detections": (_i, [_p, _p, _i, _i, _p, _i, _p, _p]),
-    "icaf_match_predictions": (_i, [_p, _p, _i, _i, _p, _p, _i, _p, _p, _i, _p, _p, _p]),
-    "icaf_nms_workspace_bytes": (_i, [_i, _ll, _i, _i, C.POINTER(_sz)]),
-    "icaf_nms": (_i, [_p, _i, _ll, _i, _f, _f, _i, _i, C.POINTER(_i), _i, _i, _i, _f, _p, _p, _p, _p, _sz, _p]),
-    "icaf_missrate_stage": (_i, [_p, _p, _p, _p, _i, _i, _p, _p, _i, _i, _p]),
-    "icaf_missrate_match": (_i, [_p, _p, _p, _p, _p, _i, _i, _p, _p, _i, _p, _p, _p, _p, _p]),
-    "icaf_confluence_select": (_i, [_p, _p, _i, _i, _i, C.c_double, _p, _p, _p, _p]),
-    "icaf_confluence_workspace_bytes": (_i, [_i, _ll, _i, _i, C.POINTER(_sz)]),
-    "icaf_confluence": (_i, [_p, _i, _ll, _i, _f, C.c_double, _i, _p, _p, _p, _p, _sz, _p]),
-    "icaf_loss_workspace_bytes": (_i, [_i, C.POINTER(_i), C.POINTER(_i), _i, _i, _i, C.POINTER(_sz), C.POINTER(_sz), C.POINTER(_sz)]),
-    "icaf_loss": (_i, [C.POINTER(_p), C.POINTER(_i), C.POINTER(_i), _i, _i, _i, _i, C.POINTER(_f), _p, _i, C.POINTER(LossParams), _p, _p, _p, _sz, _p]),
-    "icaf_graph_begin": (_i, [_p]),
-    "icaf_graph_end": (_i, [_p, C.POINTER(_p)]),
-    "icaf_graph_launch": (_i, [_p, _p]),
-    "icaf_graph_destroy": (_i, [_p]),
-    "icaf_event_create": (_i, [C.POINTER(_p)]),
-    "icaf_event_record": (_i, [_p, _p]),
-    "icaf_stream_wait_event": (_i, [_p, _p]),
-    "icaf_event_elapsed_ms": (_i, [_p, _p, C.POINTER(_f)]),
-    "icaf_event_destroy": (_i, [_p]),
-    "icaf_stream_sync": (_i, [_p]),
-}
-
-_LIB = None
+HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "icaf.h")
 
 
 class IcafError(RuntimeError):
     pass
+
+
+# consts {name: int}; structs {C name: [(field, base type, pointer depth, array length or None)]};
+# funcs {name: ((base type, pointer depth) of the result, [(parameter, base type, pointer depth, marked ICAF_HOST)])}
+Header = collections.namedtuple("Header", "consts structs funcs")
+_SCALARS = {"int": C.c_int, "long long": C.c_longlong, "float": C.c_float, "double": C.c_double, "size_t": C.c_size_t,
+            "unsigned char": C.c_ubyte, "char": C.c_char}
+_PREPROCESSOR = re.compile(r"#\s*(ifndef\s+\w+|endif|include\s*<[\w./]+>|define\s+\w+)")
+_word = re.compile(r"[A-Za-z_]\w*").fullmatch
+
+
+def parse_header(text):
+    """The declarations of a header in icaf.h's C subset as a Header; IcafError quoting the text for anything else (never skipped, never guessed)."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    text = re.sub(r'#ifdef\s+__cplusplus\s+(extern\s+"C"\s*\{|\})\s+#endif', " ", text)          # read as C
+    for line in re.findall(r"^[ \t]*(#.*?)\s*$", text, re.M):
+        if not _PREPROCESSOR.fullmatch(line):
+            raise IcafError(f"icaf.h: unsupported preprocessor line {line!r}")
+    rest = re.sub(r"^[ \t]*#.*$", " ", text, flags=re.M).strip()
+    typedefs, consts, structs, funcs = {}, {}, {}, {}
+
+    def decl(stmt, where):
+        """`ICAF_HOST const float* a[2], *b` -> base type, host mark, [(name, pointer depth, array length or None)]"""
+        tok = re.findall(r"\w+|\[\d+\]|\S", stmt)
+        n = 0
+        while n + 1 < len(tok) and _word(tok[n]) and (tok[n + 1] == "*" or _word(tok[n + 1])):
+            n += 1
+        base, depth0 = " ".join(w for w in tok[:n] if w not in ("const", "ICAF_HOST")), 0
+        base, depth0 = typedefs.get(base, (base, 0))
+        if base != "void" and base not in _SCALARS and base not in structs:
+            raise IcafError(f"icaf.h: unknown type {base!r} in {where!r}")
+        out = []
+        for d in " ".join(tok[n:]).split(","):
+            m = re.fullmatch(r"((?:\*|const\b|\s)*)([A-Za-z_]\w*)\s*(?:\[(\d+)\])?\s*", d)
+            if not m:
+                raise IcafError(f"icaf.h: cannot parse {where!r}")
+            out.append((m[2], depth0 + m[1].count("*"), int(m[3]) if m[3] else None))
+        return base, "ICAF_HOST" in tok[:n], out
+
+    while rest:
+        if m := re.match(r"enum\s*\{([^{}]*)\}\s*;", rest):
+            for item in m[1].split(","):
+                e = re.fullmatch(r"\s*(\w+)\s*=\s*(-?\d+)\s*", item)
+                if not e:
+                    raise IcafError(f"icaf.h: cannot parse the enumerator {item.strip()!r}")
+                consts[e[1]] = int(e[2])
+        elif m := re.match(r"typedef\s+struct\s+\w+\s*\{([^{}]*)\}\s*(\w+)\s*;", rest):
+            *stmts, tail = m[1].split(";")
+            if tail.strip():
+                raise IcafError(f"icaf.h: cannot parse {tail.strip()!r} at the end of struct {m[2]}")
+            fields = []
+            for stmt in stmts:
+                where = " ".join(stmt.split())
+                base, host, names = decl(stmt, where)
+                if host or (base == "void" and not all(depth for _, depth, _ in names)):
+                    raise IcafError(f"icaf.h: cannot parse {where!r}")
+                fields += [(name, base, depth, alen) for name, depth, alen in names]
+            structs[m[2]] = fields
+        elif m := re.match(r"typedef\s+void\s*\*\s*(\w+)\s*;", rest):
+            typedefs[m[1]] = ("void", 1)
+        elif m := re.match(r"([^;{}()]+)\(([^;{}()]*)\)\s*;", rest):
+            where = " ".join(m[0].split())
+            base, host, names = decl(m[1], where)
+            (name, depth, alen), params = names[0], []
+            if len(names) != 1 or alen is not None or host or not name.startswith("icaf_"):
+                raise IcafError(f"icaf.h: not a prototype of an icaf_ function: {where!r}")
+            for p in [] if m[2].strip() == "void" else m[2].split(","):
+                pbase, phost, pn = decl(p, where)
+                if pn[0][2] is not None or (pn[0][1] == 0 and (phost or pbase == "void")):
+                    raise IcafError(f"icaf.h: cannot parse the parameter {p.strip()!r} of {where!r}")
+                params.append((pn[0][0], pbase, pn[0][1], phost))
+            funcs[name] = ((base, depth), params)
+        else:
+            raise IcafError(f"icaf.h: cannot parse {' '.join(re.match(r'[^;]*;?', rest)[0].split())[:200]!r}")
+        rest = rest[m.end():].lstrip()
+    return Header(consts, structs, funcs)
+
+
+def _ctype(classes, base, depth, host=False, alen=None):
+    """Scalars and structs by type; char* -> c_char_p; ICAF_HOST T* -> POINTER(T), ICAF_HOST T** / void** -> POINTER(c_void_p); other pointers c_void_p"""
+    if depth == 0:
+        t = None if base == "void" else _SCALARS.get(base) or classes[base]
+    elif base == "char" and depth == 1:
+        t = C.c_char_p
+    elif host and (depth > 1 or base != "void"):
+        t = C.POINTER(_ctype(classes, base, 0) if depth == 1 else C.c_void_p)
+    else:
+        t = C.c_void_p
+    return t * alen if alen else t
+
+
+def _bind(header):
+    """Header -> ({C struct name: C.Structure class named in CamelCase without icaf_}, {function: (restype, argtypes)})"""
+    classes = {}
+    for cname, fields in header.structs.items():
+        pyname = "".join(w.capitalize() for w in cname[len("icaf_"):].split("_"))
+        classes[cname] = type(pyname, (C.Structure,), {"_fields_": [(name, _ctype(classes, base, depth, alen=alen)) for name, base, depth, alen in fields]})
+    return classes, {name: (_ctype(classes, *ret), [_ctype(classes, base, depth, host) for _, base, depth, host in params])
+                     for name, (ret, params) in header.funcs.items()}
+
+
+def _load_header():
+    if not os.path.exists(HEADER_PATH):
+        raise IcafError(f"{HEADER_PATH} not found — icafusion_amd derives its binding of libicaf.so from it; it has no hand-written copy of the ABI")
+    with open(HEADER_PATH) as f:
+        return parse_header(f.read())
+
+
+HEADER = _load_header()                              # once per process
+STRUCTS, SIGNATURES = _bind(HEADER)                  # SIGNATURES: symbol -> (restype, argtypes), every function of include/icaf.h
+globals().update({cls.__name__: cls for cls in STRUCTS.values()})                   # ConvArgs, BneckArgs, Stem2Args, DmffArgs, TtaPass, FrameGeom, LossParams
+globals().update({name[len("ICAF_"):]: value for name, value in HEADER.consts.items()})    # F32, ACT_SILU, LETTERBOX_LDS_BYTES, MISSRATE_MAX_DET, ...
+
+_LIB = None
 
 
 def lib():

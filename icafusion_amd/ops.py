@@ -16,6 +16,7 @@ import torch
 from . import _lib
 from .options import OPT
 from ._lib import BneckArgs, ConvArgs, DmffArgs, FrameGeom, Stem2Args, check, lib, F32, BF16, F16, ACT_NONE, ACT_SILU, ACT_GELU, ACT_RELU  # noqa: F401
+from ._lib import CONFLUENCE_MAX_CAND, LOSS_MAX_LEVELS, LOSS_MAX_ANCHORS, LOSS_MAX_TARGETS, LOSS_SLOT_INTS  # noqa: F401
 
 _DT = {torch.float32: F32, torch.bfloat16: BF16, torch.float16: F16}
 VEC = {torch.float32: 4, torch.bfloat16: 8, torch.float16: 8}     # elements per 16-byte vector
@@ -700,14 +701,19 @@ def cross_attention_form(dtype, B, N, Cc, heads):
 
 
 @contextlib.contextmanager
-def attn_stream(on=True):
-    """Force icaf_cross_attention onto its key-streaming form inside a `with` (icaf.h: icaf_cross_attention_form): an A/B knob of the
-    library for timings and tests.  Like letterbox_direct it is set by a caller, not by the options object."""
-    check(lib().icaf_set_option(b"attn_stream", int(bool(on))), "icaf_set_option(attn_stream)")
+def _caller_knob(name, on):
+    """A library knob that a caller sets, not the options object (icaf.h: icaf_set_option): `on` inside the `with`, back to 0 behind it."""
+    check(lib().icaf_set_option(name.encode(), int(bool(on))), f"icaf_set_option({name})")
     try:
         yield
     finally:
-        check(lib().icaf_set_option(b"attn_stream", 0), "icaf_set_option(attn_stream)")
+        check(lib().icaf_set_option(name.encode(), 0), f"icaf_set_option({name})")
+
+
+def attn_stream(on=True):
+    """Force icaf_cross_attention onto its key-streaming form inside a `with` (icaf.h: icaf_cross_attention_form): an A/B knob of the
+    library for timings and tests.  Like letterbox_direct it is set by a caller, not by the options object."""
+    return _caller_knob("attn_stream", on)
 
 
 def dmff_fused_lds_bytes(C_, N, heads, dt):
@@ -971,9 +977,6 @@ class NmsRunner:
         return self.det, self.count, self.keep
 
 
-CONFLUENCE_MAX_CAND = _lib.CONFLUENCE_MAX_CAND
-
-
 def confluence_select(cand, n, nc, p_thres, det=None, count=None, keep_idx=None, want_keep=True, stream_ptr=None):
     """Confluence (reference utils/confluence.py:109-193) on candidate lists that already live on the device (icaf_confluence_select): cand
     (B, max_cand, 6) fp32 [x1, y1, x2, y2, conf, cls], n (B,) int32.  Returns (det (B, max_cand, 6), count (B,) int32, keep_idx (B, max_cand)
@@ -1017,9 +1020,6 @@ class ConfluenceRunner:
                                    self.ws.data_ptr(), self.ws.numel(), stream_ptr if stream_ptr is not None else current_stream_ptr())
         check(st, "icaf_confluence")
         return self.det, self.count, self.keep
-
-
-LOSS_MAX_LEVELS, LOSS_MAX_ANCHORS, LOSS_MAX_TARGETS, LOSS_SLOT_INTS = _lib.LOSS_MAX_LEVELS, _lib.LOSS_MAX_ANCHORS, _lib.LOSS_MAX_TARGETS, _lib.LOSS_SLOT_INTS
 
 
 def loss_workspace(shapes, B, na, nt):
@@ -1084,8 +1084,7 @@ class LossRunner:
 # native camera frames: device letterbox in, native-space boxes out
 # ------------------------------------------------------------------------------------------------------------
 # one row per (modality, image): the layout of icaf_frame_geom (include/icaf.h)
-GEOM_DTYPE = np.dtype([("offset", "<i8"), ("h0", "<i4"), ("w0", "<i4"), ("pitch", "<i4"), ("ch", "<i4"), ("nh", "<i4"), ("nw", "<i4"),
-                       ("top", "<i4"), ("left", "<i4"), ("sx", "<f4"), ("sy", "<f4")])
+GEOM_DTYPE = np.dtype(FrameGeom)
 assert GEOM_DTYPE.itemsize == C.sizeof(FrameGeom) == 48
 FRAME_ALIGN = 256          # frames start on this boundary inside an arena (the kernel needs 16)
 # what a forward from frames hands back beside its result: the descriptor rows, the scale_coords rows, and those on the device
@@ -1410,24 +1409,14 @@ def missrate_evaluate(table, dt, dt_count, device="cuda"):
     return {"order": order, "dt_gt": dt_gt, "dt_ignore": dt_ignore, "gt_ignore": gt_ignore[:tab.labels]}
 
 
-@contextlib.contextmanager
 def letterbox_direct(on=True):
     """Force icaf_letterbox_frames onto its direct path (no LDS staging) inside a `with`: an A/B knob of the library, it changes no result."""
-    check(lib().icaf_set_option(b"letterbox_direct", int(bool(on))), "icaf_set_option(letterbox_direct)")
-    try:
-        yield
-    finally:
-        check(lib().icaf_set_option(b"letterbox_direct", 0), "icaf_set_option(letterbox_direct)")
+    return _caller_knob("letterbox_direct", on)
 
 
-@contextlib.contextmanager
 def area_direct(on=True):
     """Force the area rows of icaf_resize_frames onto their direct path (no LDS) inside a `with`: an A/B knob of the library, it changes no result."""
-    check(lib().icaf_set_option(b"area_direct", int(bool(on))), "icaf_set_option(area_direct)")
-    try:
-        yield
-    finally:
-        check(lib().icaf_set_option(b"area_direct", 0), "icaf_set_option(area_direct)")
+    return _caller_knob("area_direct", on)
 
 
 # ------------------------------------------------------------------------------------------------------------

@@ -9,7 +9,7 @@
  * and calls these functions through ctypes — see INTEGRATION.md for the binding stub.
  *
  * Conventions
- *   - every pointer named x/y/w/... is a DEVICE pointer unless the comment says "host";
+ *   - every pointer parameter is a DEVICE pointer unless it is marked ICAF_HOST (char* is always host memory);
  *   - activations are NHWC ("channels-last"): element (b,h,w,c) lives at ((b*H + h)*W + w)*ld + c, where the
  *     pixel stride `ld` >= C lets a tensor be a channel slice of a wider buffer (this is how Concat, C3's
  *     torch.cat and SPPF's torch.cat are eliminated);
@@ -29,6 +29,8 @@ extern "C" {
 #endif
 
 typedef void* icaf_stream_t; /* hipStream_t */
+/* marks a pointer parameter that is HOST memory (char* always is); every other pointer is a device pointer.  The Python binding reads it. */
+#define ICAF_HOST
 
 enum { ICAF_F32 = 0, ICAF_BF16 = 1, ICAF_F16 = 2 };
 enum { ICAF_ACT_NONE = 0, ICAF_ACT_SILU = 1, ICAF_ACT_GELU = 2, ICAF_ACT_RELU = 3 };
@@ -47,7 +49,7 @@ const char* icaf_last_error(void);
 int icaf_set_option(const char* name, int value);
 int icaf_version(void);
 /* device facts used by the host for grid sizing / reporting: CU count, LDS bytes per workgroup, gcnArchName */
-int icaf_device_info(int* cu_count, int* lds_bytes, char* arch, int arch_len);
+int icaf_device_info(ICAF_HOST int* cu_count, ICAF_HOST int* lds_bytes, char* arch, int arch_len);
 
 /* ---- input staging -------------------------------------------------------------------------------------
  * Reference: detect_twostream.py:70-80 / test.py:116-123 hand the model NCHW float tensors in [0,1].
@@ -90,7 +92,7 @@ typedef struct icaf_stem2_args {
     const void* w2; const float* bias2; long long w2_gs, bias2_gs; int Kp2, C2;
     void* y; long long y_gs; int ldy, reserved;
 } icaf_stem2_args;
-int icaf_stem2(const icaf_stem2_args* a, icaf_stream_t s);
+int icaf_stem2(ICAF_HOST const icaf_stem2_args* a, icaf_stream_t s);
 
 /* Image-fed first layer of a VGG block (models/common.py:109-128: Conv2d(3, 64, 3, padding=1) + ReLU, yaml rows 0 and 5 of the
  * yolov5_VGG16_* files) in one launch, both streams: y = ReLU(conv3x3 / s1 / p1 (img) + bias) computed straight from the NCHW images
@@ -209,7 +211,7 @@ typedef struct icaf_conv_args {
     int res_mode;
 } icaf_conv_args;
 
-int icaf_conv2d(const icaf_conv_args* a, icaf_stream_t s);
+int icaf_conv2d(ICAF_HOST const icaf_conv_args* a, icaf_stream_t s);
 
 /* Whole Bottleneck in one launch (models/common.py:184-194): y = [x +] SiLU(conv3x3(SiLU(conv1x1(x)))) for c_ -> c_ -> c_
  * channels with c_ in {32, 64}, 16-bit types.  `conv` describes the 3x3 / stride 1 / pad 1 layer (x = block input,
@@ -232,11 +234,11 @@ typedef struct icaf_bneck_args {
     long long x2_gs;
     int ldx2, reserved;
 } icaf_bneck_args;
-int icaf_bottleneck(const icaf_bneck_args* a, icaf_stream_t s);
+int icaf_bottleneck(ICAF_HOST const icaf_bneck_args* a, icaf_stream_t s);
 /* name of the kernel instantiation icaf_conv2d would launch for these args (host string, for profiling) */
-int icaf_conv2d_kernel_name(const icaf_conv_args* a, char* buf, int buf_len);
+int icaf_conv2d_kernel_name(ICAF_HOST const icaf_conv_args* a, char* buf, int buf_len);
 /* the launch configuration ids that are built, ascending: writes the first `cap` of them to ids (may be NULL), returns how many there are */
-int icaf_conv2d_config_ids(int* ids, int cap);
+int icaf_conv2d_config_ids(ICAF_HOST int* ids, int cap);
 
 /* ---- SPPF / upsample / copy ------------------------------------------------------------------------------
  * icaf_sppf_pool: the three chained k x k stride-1 max pools of SPPF.forward (models/common.py:262-267);
@@ -248,7 +250,7 @@ int icaf_sppf_pool(const void* x, int ldx, void* y1, void* y2, void* y3, int ldy
                    int C, int k, icaf_stream_t s);
 /* launch choice of icaf_sppf_pool for this geometry (SPPF.forward, models/common.py:262-267): *vpb = channel vectors per
  * workgroup of the LDS kernel (8 / 4 / 2 / 1, the probe knob "sppf_vpb" included), 0 = the global-memory kernel */
-int icaf_sppf_config(int dtype, int H, int W, int C, int* vpb);
+int icaf_sppf_config(int dtype, int H, int W, int C, ICAF_HOST int* vpb);
 int icaf_upsample_nearest(const void* x, int ldx, void* y, int ldy, int dtype, int B, int H, int W, int C,
                           int scale, icaf_stream_t s);
 /* nn.MaxPool2d(k, stride, pad) over an NHWC tensor (models/common.py:122: the 2 / 2 / 0 pool closing a VGGblock; 3 / 2 / 1 is ResNet's):
@@ -286,22 +288,22 @@ int icaf_dmff_pool_tokens(const void* fea_rgb, int ld_rgb, const void* fea_ir, i
 /* launch choice of icaf_dmff_pool_tokens for this geometry (same argument checks): *kernel = 0 (one thread per token element) / 1 (separable
  * rows kernel, overlapping windows whose token row fits the LDS); rows kernel: *R = input rows in flight per item (4 / 8 / 12), *TR = token rows
  * per workgroup (1 / 2), else 0; element kernel: *index64 = 1 when the 64-bit-index instantiation runs (the probe knob "index64" included) */
-int icaf_dmff_pool_config(int dtype, int B, int H, int W, int C, int th, int tw, int kh, int kw, int sh, int sw, int* kernel, int* R,
-                          int* TR, int* index64);
+int icaf_dmff_pool_config(int dtype, int B, int H, int W, int C, int th, int tw, int kh, int kw, int sh, int sw, ICAF_HOST int* kernel, ICAF_HOST int* R,
+                          ICAF_HOST int* TR, ICAF_HOST int* index64);
 int icaf_layernorm(const void* x, void* y, const float* gamma0, const float* beta0, const float* gamma1,
                    const float* beta1, int dtype, long long rows_per_group, int C, int groups, float eps,
                    icaf_stream_t s);
 int icaf_cross_attention(const void* qkv, void* out, int dtype, int B, int N, int C, int heads, icaf_stream_t s);
 /* launch choice of icaf_cross_attention (CrossAttention.forward :670-685): *dkp = padded head dimension of the kernel instance,
  * *qsplit = query splits per head (the probe knob "attn_qsplit" included), *remap = 1 when the one-dimensional XCD-grouped grid is used */
-int icaf_cross_attention_config(int dtype, int B, int N, int C, int heads, int* dkp, int* qsplit, int* remap);
+int icaf_cross_attention_config(int dtype, int B, int N, int C, int heads, ICAF_HOST int* dkp, ICAF_HOST int* qsplit, ICAF_HOST int* remap);
 /* Which kernel icaf_cross_attention launches for this shape (same argument checks): *form = 0, the resident form — K and V^T of a head stay in
  * LDS for the workgroup's lifetime: d_k <= 128 and at most 160 KiB, unchanged; *form = 1, the key-streaming form — K and V^T pass through LDS
  * in double-buffered 32-key tiles, same online softmax and key order: 128 < d_k <= 256 (a multiple of the 16-byte vector) and every shape whose
  * resident K / V^T exceed 160 KiB (fp32 at N = 256, d_k = 128), or everything with the probe knob "attn_stream".  For form 1
  * icaf_cross_attention_config reports the streaming instance's padded head dimension (64 / 128 / 256; d_k = 192 runs the 256 instance), its query
  * splits (a workgroup round is four query tiles, two at 256, where a pair of waves shares a query tile and splits the head's d rows) and remap. */
-int icaf_cross_attention_form(int dtype, int B, int N, int C, int heads, int* form);
+int icaf_cross_attention_form(int dtype, int B, int N, int C, int heads, ICAF_HOST int* form);
 int icaf_dmff_upsample_merge(const void* tokens, const void* fea_rgb, int ld_rgb, const void* fea_ir, int ld_ir,
                              void* out, int ldo, int dtype, int B, int H, int W, int C, int th, int tw,
                              icaf_stream_t s);
@@ -313,19 +315,19 @@ int icaf_dmff_upsample_merge(const void* tokens, const void* fea_rgb, int ld_rgb
  * anchors_px: host pointer to na*2 floats = anchor sizes in pixels (anchor_grid).
  */
 int icaf_detect_decode(const float* p, int ldp, float* z, float* logits, float* raw, int B, int ny, int nx, int na,
-                       int no, long long rows_total, long long row_offset, float stride, const float* anchors_px,
+                       int no, long long rows_total, long long row_offset, float stride, ICAF_HOST const float* anchors_px,
                        icaf_stream_t s);
 /* which kernel icaf_detect_decode launches for these arguments (models/yolo_test.py:43-65): *kernel = 0 one thread per pixel
  * (3 anchors, no in {6, 8, 14}, 8-byte aligned rows), 1 one thread per element (every other head, or the probe knob
  * "detect_elementwise").  Pointers, not shapes: their alignment is part of the choice; nothing is read through them. */
 int icaf_detect_decode_kernel(const float* p, int ldp, const float* z, const float* raw, int B, int ny, int nx, int na,
-                              int no, int* kernel);
+                              int no, ICAF_HOST int* kernel);
 /* A Detect level in ONE launch (16-bit feature maps, 3 anchors, no in {6, 8, 14}): the level's 1x1 output convolution
  * (models/yolo_test.py:50; `a` describes it as for icaf_conv2d: 1x1, no activation, groups 1, Cout = na * no; a->y is ignored)
  * with the decode above as the epilogue of the persistent streaming GEMM — the fp32 conv map is never written.  z / logits / raw
  * are bit-identical to icaf_conv2d (fp32 out) followed by icaf_detect_decode. */
-int icaf_detect_conv(const icaf_conv_args* a, float* z, float* logits, float* raw, int na, int no, long long rows_total,
-                     long long row_offset, float stride, const float* anchors_px, icaf_stream_t s);
+int icaf_detect_conv(ICAF_HOST const icaf_conv_args* a, float* z, float* logits, float* raw, int na, int no, long long rows_total,
+                     long long row_offset, float stride, ICAF_HOST const float* anchors_px, icaf_stream_t s);
 
 /* ---- fused DMFF block (16-bit token types) -------------------------------------------------------------------
  * One CrossTransformerBlock iteration (models/common.py:737-759) in two launches:
@@ -363,8 +365,8 @@ typedef struct icaf_dmff_args {
      * iteration's fp32 tokens instead of the 16-bit x (LayerNorm + QKV keep reading the 16-bit tokens).  16-bit dtypes, 16-byte aligned. */
     const float* x32; float* y32;
 } icaf_dmff_args;
-int icaf_dmff_ln_qkv(const icaf_dmff_args* a, icaf_stream_t s);
-int icaf_dmff_attn_mlp(const icaf_dmff_args* a, icaf_stream_t s);
+int icaf_dmff_ln_qkv(ICAF_HOST const icaf_dmff_args* a, icaf_stream_t s);
+int icaf_dmff_attn_mlp(ICAF_HOST const icaf_dmff_args* a, icaf_stream_t s);
 /* The block for the WIDE levels (C = 256 or 512, 16-bit types; dmff_wide.hip): one iteration = icaf_dmff_wide_ln_qkv,
  * icaf_cross_attention, icaf_dmff_wide_proj_mlp.
  *   icaf_dmff_wide_ln_qkv    as icaf_dmff_ln_qkv (LayerNorm :661-662 + the six projections :664-669);
@@ -374,17 +376,17 @@ int icaf_dmff_attn_mlp(const icaf_dmff_args* a, icaf_stream_t s);
  * DIFFERENT WEIGHT LAYOUT: a->wqkv / wo / w1 / w2 point at FRAGMENT-MAJOR copies of the packed [2][Np][Kp] matrices,
  * [2][Np/32][Kp/16][64][8] (lane (hi*32 + r) of block (nb, ks) = w[nb*32 + r][ks*16 + hi*8 .. +8], the layout of icaf_conv_args.wf;
  * same *_gs strides): each wavefront streams its MFMA weight operands straight from L2 into registers.  hidden % 256 == 0. */
-int icaf_dmff_wide_ln_qkv(const icaf_dmff_args* a, icaf_stream_t s);
-int icaf_dmff_wide_proj_mlp(const icaf_dmff_args* a, const void* att, icaf_stream_t s);
+int icaf_dmff_wide_ln_qkv(ICAF_HOST const icaf_dmff_args* a, icaf_stream_t s);
+int icaf_dmff_wide_proj_mlp(ICAF_HOST const icaf_dmff_args* a, const void* att, icaf_stream_t s);
 /* The same step with the MLP's hidden columns split over `ksplit` (2 or 4) workgroups per 64-row tile — for levels with fewer tiles
  * than CUs and more weight bytes than an XCD's L2 (P5: 100 tokens x 32 images at C = 512): every workgroup repeats out-projection +
  * LayerNorm (:682-685, :745-750), runs Linear(C, 4C) -> GELU -> Linear(4C, C) (:704-709) over ITS hidden slice, parks x_att in y and
  * writes fp32 partial sums into partial [ksplit][2][B*N][C].  icaf_dmff_wide_reduce (the next launch on the stream) adds them in slice
  * order (deterministic: no atomics, no in-kernel fences) and applies bias + the coefficient mix (:751-752) in place on y.  Same operands
  * and fragment-major weight layout as icaf_dmff_wide_proj_mlp; hidden % (256 * ksplit) == 0. */
-int icaf_dmff_wide_proj_mlp_split(const icaf_dmff_args* a, const void* att, float* partial, int ksplit, icaf_stream_t s);
-int icaf_dmff_wide_reduce(const icaf_dmff_args* a, const float* partial, int ksplit, icaf_stream_t s);
-int icaf_dmff_attn_mlp_lds_bytes(int C, int N, int heads, int dtype, size_t* bytes);
+int icaf_dmff_wide_proj_mlp_split(ICAF_HOST const icaf_dmff_args* a, const void* att, float* partial, int ksplit, icaf_stream_t s);
+int icaf_dmff_wide_reduce(ICAF_HOST const icaf_dmff_args* a, const float* partial, int ksplit, icaf_stream_t s);
+int icaf_dmff_attn_mlp_lds_bytes(int C, int N, int heads, int dtype, ICAF_HOST size_t* bytes);
 
 /* ---- test-time augmentation (models/yolo_test.py:116-131, utils/torch_utils.py:257-267) ---------------------
  * Model.forward(augment=True) runs three passes, (scale, flip) = (1, -), (0.83, left-right), (0.67, -), and concatenates their decoded
@@ -412,9 +414,9 @@ typedef struct icaf_tta_pass {
     int flip;          /* != 0: x.flip(3) before the resize */
     int reserved;
 } icaf_tta_pass;
-int icaf_tta_stage(const void* src, int src_u8, int ctot, int B, int H, int W, const icaf_tta_pass* passes, int npass,
+int icaf_tta_stage(const void* src, int src_u8, int ctot, int B, int H, int W, ICAF_HOST const icaf_tta_pass* passes, int npass,
                    icaf_stream_t s);
-int icaf_tta_merge(const float* const* z, const long long* rows, const float* scale, const int* flip, int npass, float* out,
+int icaf_tta_merge(ICAF_HOST const float* const* z, ICAF_HOST const long long* rows, ICAF_HOST const float* scale, ICAF_HOST const int* flip, int npass, float* out,
                    int B, int no, float width, icaf_stream_t s);
 
 /* ---- native camera frames (utils/datasets.py: letterbox; detect_twostream.py:70-80) ---------------------------------------
@@ -494,9 +496,9 @@ int icaf_resize_frames(const void* arena, const icaf_frame_geom* geom, const int
 int icaf_match_predictions(const float* det, const int* count, int B, int max_det, const float* labels, const int* label_off,
                            int max_labels_per_image, const float* scale, const float* iouv, int T, unsigned char* correct,
                            float* predn, icaf_stream_t s);
-int icaf_nms_workspace_bytes(int B, long long rows, int nc, int multi_label, size_t* bytes);
+int icaf_nms_workspace_bytes(int B, long long rows, int nc, int multi_label, ICAF_HOST size_t* bytes);
 int icaf_nms(const float* pred, int B, long long rows, int nc, float conf_thres, float iou_thres, int multi_label,
-             int agnostic, const int* classes_host, int n_classes, int max_det, int max_nms, float max_wh,
+             int agnostic, ICAF_HOST const int* classes_host, int n_classes, int max_det, int max_nms, float max_wh,
              float* det, int* count, int* keep_idx, void* workspace, size_t workspace_bytes, icaf_stream_t s);
 
 /* ---- KAIST log-average miss rate, per-image half (evaluation_script/evaluation_script.py:46-79, 119-179, 181-294, 478-497) ----------
@@ -566,7 +568,7 @@ int icaf_missrate_match(const double* gt_box, const double* gt_height, const int
 enum { ICAF_CONFLUENCE_MAX_CAND = 4096 };
 int icaf_confluence_select(const float* cand, const int* n, int B, int max_cand, int nc, double p_thres, float* det, int* count,
                            int* keep_idx, icaf_stream_t s);
-int icaf_confluence_workspace_bytes(int B, long long rows, int nc, int max_cand, size_t* bytes);
+int icaf_confluence_workspace_bytes(int B, long long rows, int nc, int max_cand, ICAF_HOST size_t* bytes);
 int icaf_confluence(const float* pred, int B, long long rows, int nc, float conf_thres, double p_thres, int max_cand, float* det,
                     int* count, int* keep_idx, void* workspace, size_t workspace_bytes, icaf_stream_t s);
 
@@ -603,20 +605,20 @@ enum { ICAF_LOSS_MAX_LEVELS = 5, ICAF_LOSS_MAX_ANCHORS = 8, ICAF_LOSS_MAX_TARGET
 typedef struct icaf_loss_params {
     double box, obj, cls, cls_pw, obj_pw, anchor_t, gr, cp, cn, balance[5];
 } icaf_loss_params;
-int icaf_loss_workspace_bytes(int nl, const int* ny, const int* nx, int B, int na, int nt, size_t* bytes, size_t* tobj_off, size_t* slots_off);
-int icaf_loss(const float* const* maps, const int* ny, const int* nx, int nl, int B, int na, int nc, const float* anchors,
-              const float* targets, int nt, const icaf_loss_params* prm, float* out, int* counts, void* workspace, size_t workspace_bytes,
+int icaf_loss_workspace_bytes(int nl, ICAF_HOST const int* ny, ICAF_HOST const int* nx, int B, int na, int nt, ICAF_HOST size_t* bytes, ICAF_HOST size_t* tobj_off, ICAF_HOST size_t* slots_off);
+int icaf_loss(ICAF_HOST const float* const* maps, ICAF_HOST const int* ny, ICAF_HOST const int* nx, int nl, int B, int na, int nc, ICAF_HOST const float* anchors,
+              const float* targets, int nt, ICAF_HOST const icaf_loss_params* prm, float* out, int* counts, void* workspace, size_t workspace_bytes,
               icaf_stream_t s);
 
 /* ---- HIP graph capture / events (so the Python host never needs a tracing compiler) ------------------------ */
 int icaf_graph_begin(icaf_stream_t s);
-int icaf_graph_end(icaf_stream_t s, void** graph_exec);
+int icaf_graph_end(icaf_stream_t s, ICAF_HOST void** graph_exec);
 int icaf_graph_launch(void* graph_exec, icaf_stream_t s);
 int icaf_graph_destroy(void* graph_exec);
-int icaf_event_create(void** ev);
+int icaf_event_create(ICAF_HOST void** ev);
 int icaf_event_record(void* ev, icaf_stream_t s);
 int icaf_stream_wait_event(icaf_stream_t s, void* ev);         /* hipStreamWaitEvent: fork / join of capture branches */
-int icaf_event_elapsed_ms(void* start, void* stop, float* ms); /* synchronises on `stop` */
+int icaf_event_elapsed_ms(void* start, void* stop, ICAF_HOST float* ms); /* synchronises on `stop` */
 int icaf_event_destroy(void* ev);
 int icaf_stream_sync(icaf_stream_t s);
 

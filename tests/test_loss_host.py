@@ -114,8 +114,8 @@ def test_cpu_statement_equals_the_reference(name):
 def test_header_declares_the_entry_points_with_their_citations():
     with open(os.path.join(REPO, "include", "icaf.h")) as f:
         header = f.read()
-    assert "int icaf_loss_workspace_bytes(int nl, const int* ny, const int* nx, int B, int na, int nt, size_t* bytes, size_t* tobj_off, size_t* slots_off);" in header
-    assert "int icaf_loss(const float* const* maps, const int* ny, const int* nx, int nl, int B, int na, int nc, const float* anchors," in header
+    assert "int icaf_loss_workspace_bytes(int nl, ICAF_HOST const int* ny, ICAF_HOST const int* nx, int B, int na, int nt, ICAF_HOST size_t* bytes, ICAF_HOST size_t* tobj_off, ICAF_HOST size_t* slots_off);" in header
+    assert "int icaf_loss(ICAF_HOST const float* const* maps, ICAF_HOST const int* ny, ICAF_HOST const int* nx, int nl, int B, int na, int nc, ICAF_HOST const float* anchors," in header
     assert "double box, obj, cls, cls_pw, obj_pw, anchor_t, gr, cp, cn, balance[5];" in header
     block = header[header.index("---- Validation loss"):header.index("int icaf_loss_workspace_bytes(")]
     for cite in ("utils/loss.py:325-463", ":409-463", ":362-388", ":379-382", ":457", ":458", "utils/general.py:410-452", "SLOT LAYOUT", "(off * na + a) * nt + t",
