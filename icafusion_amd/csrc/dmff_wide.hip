@@ -33,6 +33,7 @@
 #include <type_traits>
 #include "icaf_common.h"
 #include "conv_common.h"
+#include "wide_cursor.h"
 
 namespace icaf {
 
@@ -78,28 +79,31 @@ using WG8 = WG<8, 4>;
 using WG4 = WG<4, 2>;
 
 // One wave's weight stream.  A SEGMENT is one pass's fragments for this wave's 32 channels: n slices of WSL consecutive K steps,
-// 64 lanes x 16 bytes each, contiguous in the fragment-major copy.  `next` yields the segment after the current one.
-struct WCursor {
-    const u32x4* base;       // next slice (lane offset included)
-    int left, seg;
-};
-
-template <int WSL, class NEXT>
-__device__ __forceinline__ void wfetch(u32x4 (&w)[WSL], WCursor& c, const NEXT& next) {
-    if (c.left == 0) return;                         // end of the kernel's stream (wave-uniform)
+// 64 lanes x 16 bytes each, contiguous in the fragment-major copy.  Which segment follows which, and where its slices lie, is the
+// integer arithmetic of wide_cursor.h (checked on the host); `mats(m)` is the wave-uniform base of matrix m, the lane offset is added last.
+//
+// A refill is UNCONDITIONAL: WSL loads per slot, always, the cursor arithmetic behind them scalar code with no load in a branch.  With
+// the refill in a branch (`if (left == 0) return;`, the first form of this file) the compiler could not count the loads younger than a slot and waited
+// vmcnt(0) once per rotation — for the refill it had issued a few MFMAs earlier: a ring of four slices that held one (docs/HISTORY.md
+// section 21).  Now a slot is waited for with (WDEPTH - 1) * WSL + (WSL - 1 - k) loads still travelling.  Past the end of the kernel's
+// stream the cursor stays on its last valid slice: WDEPTH refills of an address already read, never consumed.
+template <int WSL, class SEGS, class MATS>
+__device__ __forceinline__ void wfetch(u32x4 (&w)[WSL], WCursor& c, const SEGS& segs, const MATS& mats) {
+    const u32x4* b = mats(c.mat) + c.frag * 64 + (threadIdx.x & 63);
 #pragma unroll
-    for (int k = 0; k < WSL; ++k) w[k] = c.base[k * 64];
-    c.base += WSL * 64;
-    if (--c.left == 0) { ++c.seg; next(c); }
+    for (int k = 0; k < WSL; ++k) w[k] = b[k * 64];
+    wcursor_advance(c, WSL, segs);
 }
 
 // acc[t] += W[32 wn + i][k] * A[32 t + j][k] over the next n slices (n % WDEPTH == 0) of the wave's stream; A: LDS tile, row stride SA
-template <int DT, int WSL, class NEXT>
-__device__ __forceinline__ void wpass(f32x16 (&acc)[2], const unsigned char* A, int SA, int n, u32x4 (&wq)[WDEPTH][WSL], WCursor& c, const NEXT& next) {
+template <int DT, int WSL, class SEGS, class MATS>
+__device__ __forceinline__ void wpass(f32x16 (&acc)[2], const unsigned char* A, int SA, int n, u32x4 (&wq)[WDEPTH][WSL], WCursor& c, const SEGS& segs, const MATS& mats) {
     const int lane = threadIdx.x & 63, l31 = lane & 31, hi = lane >> 5;
     const unsigned char* a0 = A + (size_t)l31 * SA + hi * 16;
     const unsigned char* a1 = a0 + (size_t)32 * SA;
-    for (int s = 0; s < n; s += WDEPTH) {
+    int s = 0;
+    do {                                         // (n >= WDEPTH: a loop that runs at least once tells the compiler that a load requested before the pass is
+                                                 //  older than WDEPTH * WSL refills when the pass ends — its wait there is counted, the ring stays full)
 #pragma unroll
         for (int u = 0; u < WDEPTH; ++u) {
 #pragma unroll
@@ -110,16 +114,18 @@ __device__ __forceinline__ void wpass(f32x16 (&acc)[2], const unsigned char* A, 
                 mma_step<DT>(acc[0], wq[u][k], x0);
                 mma_step<DT>(acc[1], wq[u][k], x1);
             }
-            wfetch<WSL>(wq[u], c, next);
+            wfetch<WSL>(wq[u], c, segs, mats);
             __builtin_amdgcn_sched_barrier(0);             // (left alone the scheduler hoists the token-fragment reads of all four slices: 128 registers)
         }
-    }
+        s += WDEPTH;
+    } while (s < n);
 }
 
 // LayerNorm of the 64 rows of an LDS tile in place: TPR (8 or 4) threads per row, two-pass statistics in fp32 on the stored values
-// (the arithmetic of layernorm_kernel, dmff.hip).
+// (the arithmetic of layernorm_kernel, dmff.hip).  gam / bet: C floats each IN LDS (the kernel's prologue fetched them with the tile: read from
+// global memory here, inside the third loop, they cost one dependent round trip per iteration).
 template <int DT, int TPR>
-__device__ __forceinline__ void wide_tile_layernorm(unsigned char* tile, int S, int C, const float* __restrict__ gam, const float* __restrict__ bet, float eps) {
+__device__ __forceinline__ void wide_tile_layernorm(unsigned char* tile, int S, int C, const float* gam, const float* bet, float eps) {
     using E = Elem<DT>;
     const int tid = threadIdx.x, row = tid / TPR, part = tid % TPR;
     const int nv = C / E::VEC;
@@ -169,7 +175,12 @@ template <int KS> __device__ __forceinline__ void wide_place_ks(int bid, int& g,
 // LayerNorm + QKV projection: a workgroup = 64 token rows x three passes (768 output channels with eight wavefronts, 384 with
 // four) of one modality.  grid = 8 * ceil(tiles * C / WPASS / 4)
 // ---------------------------------------------------------------------------------------------------------------
-template <int DT, class G = WG8>
+// NT: 16-byte vectors of the token tile per thread (64 rows x C elements over the workgroup's threads: 4, or 8 at C = 512 and in fp32) — a
+// compile-time count, so that the prologue is ONE batch of loads: the tile, then one quad of gamma | beta and one of this workgroup's biases
+// per thread (from clamped indices, stored to LDS under the predicate), then the first WDEPTH weight slices; the LDS writes follow, waiting
+// for the older loads only.  Read in a `for (i = tid; ...)` loop the tile cost one memory round trip per iteration, and the first of them
+// drained the weight prefetch issued "to travel meanwhile".
+template <int DT, class G = WG8, int NT = 4>
 __global__ __launch_bounds__(G::WT) void dmff_wide_ln_qkv_kernel(const WideP p) {
     using E = Elem<DT>;
     using T = typename E::type;
@@ -177,6 +188,8 @@ __global__ __launch_bounds__(G::WT) void dmff_wide_ln_qkv_kernel(const WideP p) 
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int C = p.C, SA = C * EB + 16;
     unsigned char* tile = smem;
+    float* lnp = (float*)(tile + (size_t)WROWS * SA);               // gamma [C], beta [C]
+    float* bs = lnp + 2 * C;                                        // bias of this workgroup's passes [npass][WPASS]
     const int tid = threadIdx.x, lane = tid & 63, l31 = lane & 31, hi = lane >> 5;
     const int wn = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int npass = p.qkv_npass;                                    // 3: a workgroup writes q, k AND v columns of its group; 1: one pass each
@@ -189,32 +202,44 @@ __global__ __launch_bounds__(G::WT) void dmff_wide_ln_qkv_kernel(const WideP p) 
     const long long r0 = (long long)tile_i * WROWS;
     const int ks_row = p.Kp / G::template kstep<DT>(), nsl = C / G::template ksl<DT>();
 
-    const u32x4* wf = (const u32x4*)((const T*)p.wqkv + g * p.wqkv_gs) + lane;
-    auto next = [&](WCursor& c) {
-        if (c.seg >= npass) { c.left = 0; return; }
-        c.base = wf + (long long)((grp * npass + c.seg) * G::NW + wn) * ks_row * 64;
-        c.left = nsl;
-    };
-    WCursor cur; cur.seg = 0; next(cur);
-    u32x4 wq[WDEPTH][G::SL];
-#pragma unroll
-    for (int u = 0; u < WDEPTH; ++u) wfetch<G::SL>(wq[u], cur, next);      // the first weight slices travel while the tokens are normalised
-
+    // ---- prologue: every global load of the workgroup's front in one batch, the weight ring last (youngest) ----
+    u32x4 tl[NT];
+    const int nv = C / VEC;
     {
         const T* xg = (const T*)p.x + g * p.x_gs;
-        const int nv = C / VEC;
-        for (int i = tid; i < WROWS * nv; i += G::WT) {               // raw tokens -> LDS (rows beyond the tensor: clamped, never stored)
-            const int row = i / nv, v = i - row * nv;
+#pragma unroll
+        for (int it = 0; it < NT; ++it) {                            // raw tokens (rows beyond the tensor: clamped, never stored)
+            const int i = tid + it * G::WT, row = i / nv, v = i - row * nv;
             long long r = r0 + row;
             r = r < p.rows ? r : p.rows - 1;
-            *(u32x4*)(tile + (size_t)row * SA + v * 16) = *(const u32x4*)(xg + r * C + v * VEC);
+            tl[it] = *(const u32x4*)(xg + r * C + v * VEC);
         }
     }
+    const int nlq = C / 2, nbq = npass * (G::WPASS / 4);             // quads of gamma | beta, of the workgroup's biases (both < threads)
+    const int lqi = tid < nlq ? tid : nlq - 1, bqi = tid < nbq ? tid : nbq - 1;
+    const f32x4 lq = *(const f32x4*)(lqi < C / 4 ? p.ln_a_g[g] + 4 * lqi : p.ln_a_b[g] + 4 * lqi - C);
+    const f32x4 bq = *(const f32x4*)(p.bqkv + g * p.bqkv_gs + grp * npass * G::WPASS + 4 * bqi);
+
+    const u32x4* wf = (const u32x4*)((const T*)p.wqkv + g * p.wqkv_gs);
+    const WQkvSegs segs{npass, grp, G::NW, wn, ks_row, nsl};
+    auto mats = [&](int) { return wf; };
+    WCursor cur;
+    wcursor_start(cur, G::SL, segs);
+    u32x4 wq[WDEPTH][G::SL];
+#pragma unroll
+    for (int u = 0; u < WDEPTH; ++u) wfetch<G::SL>(wq[u], cur, segs, mats);      // the first weight slices travel while the tokens are normalised
+
+#pragma unroll
+    for (int it = 0; it < NT; ++it) {
+        const int i = tid + it * G::WT, row = i / nv, v = i - row * nv;
+        *(u32x4*)(tile + (size_t)row * SA + v * 16) = tl[it];
+    }
+    if (tid < nlq) *(f32x4*)(lnp + 4 * tid) = lq;
+    if (tid < nbq) *(f32x4*)(bs + 4 * tid) = bq;
     lds_barrier();
-    wide_tile_layernorm<DT, G::TPR>(tile, SA, C, p.ln_a_g[g], p.ln_a_b[g], p.eps_a);
+    wide_tile_layernorm<DT, G::TPR>(tile, SA, C, lnp, lnp + C, p.eps_a);
     lds_barrier();
 
-    const float* bias = p.bqkv + g * p.bqkv_gs;
     const int nout = 3 * C;
     T* out = (T*)p.qkv + (long long)g * p.rows * nout;
     for (int j = 0; j < npass; ++j) {
@@ -223,19 +248,18 @@ __global__ __launch_bounds__(G::WT) void dmff_wide_ln_qkv_kernel(const WideP p) 
         for (int t = 0; t < 2; ++t)
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[t][r] = 0.0f;
-        wpass<DT, G::SL>(acc, tile, SA, nsl, wq, cur, next);
+        wpass<DT, G::SL>(acc, tile, SA, nsl, wq, cur, segs, mats);
         const int nb = (grp * npass + j) * G::WPASS + wn * 32;
 #pragma unroll
-        for (int t = 0; t < 2; ++t) {
-            const long long row = r0 + t * 32 + l31;
-            if (row < p.rows) {
+        for (int q = 0; q < 4; ++q) {
+            const int n = nb + 8 * q + 4 * hi;
+            const f32x4 b = *(const f32x4*)(bs + j * G::WPASS + wn * 32 + 8 * q + 4 * hi);      // (LDS: no global load inside the predicated store)
 #pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const int n = nb + 8 * q + 4 * hi;
-                    const f32x4 b = *(const f32x4*)(bias + n);
+            for (int t = 0; t < 2; ++t) {
+                const long long row = r0 + t * 32 + l31;
+                if (row < p.rows)
                     *(typename Quad<DT>::type*)(out + row * nout + n) =
                         pack4<DT>(acc[t][4 * q] + b[0], acc[t][4 * q + 1] + b[1], acc[t][4 * q + 2] + b[2], acc[t][4 * q + 3] + b[3]);
-                }
             }
         }
     }
@@ -259,7 +283,8 @@ __global__ __launch_bounds__(G::WT) void dmff_wide_proj_mlp_kernel(const WideP p
     unsigned char* T0 = smem;                                      // attention output -> later the LayerNorm'ed MLP input
     unsigned char* Hb = T0 + (size_t)WROWS * SA;                   // hidden chunk [64][256]
     float* red = (float*)(Hb + (size_t)WROWS * SH);                // [NW][64] row partial sums of the channel groups
-    float* b1s = red + G::NW * 64;                                     // fc1 bias (hid floats)
+    float* prm = red + G::NW * 64;                                 // ln_m gamma [C], ln_m beta [C], b_o [C], b2 [C]: fetched with the tile
+    constexpr int NT = WROWS * (NPW * WPASS / VEC) / WT;           // 16-byte vectors of the attention tile per thread (C = NPW * WPASS)
 
     const int tid = threadIdx.x, lane = tid & 63, l31 = lane & 31, hi = lane >> 5;
     const int wn = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -272,34 +297,40 @@ __global__ __launch_bounds__(G::WT) void dmff_wide_proj_mlp_kernel(const WideP p
     const int ks_row = p.Kp / KST, ks_row4 = p.Kp4 / KST, nsl = C / G::template ksl<DT>(), nchunk = p.hid / WPASS / KS, chunk0 = ksl * nchunk;
 
     // the wave's stream: NPW out-projection passes, then per hidden chunk one fc1 pass and NPW fc2 passes
-    const u32x4* wof = (const u32x4*)((const T*)p.wo + g * p.wo_gs) + lane;
-    const u32x4* w1f = (const u32x4*)((const T*)p.w1 + g * p.w1_gs) + lane;
-    const u32x4* w2f = (const u32x4*)((const T*)p.w2 + g * p.w2_gs) + lane;
-    auto next = [&](WCursor& c) {
-        const int s = c.seg;
-        if (s < NPW) { c.base = wof + (long long)(s * G::NW + wn) * ks_row * 64; c.left = nsl; return; }
-        const int m = s - NPW, chunk = m / (1 + NPW), r = m - chunk * (1 + NPW);
-        if (chunk >= nchunk) { c.left = 0; return; }
-        if (r == 0) { c.base = w1f + (long long)((chunk0 + chunk) * G::NW + wn) * ks_row * 64; c.left = nsl; }
-        else { c.base = w2f + ((long long)((r - 1) * G::NW + wn) * ks_row4 + (chunk0 + chunk) * (WPASS / KST)) * 64; c.left = NSL2; }
-    };
-    WCursor cur; cur.seg = 0; next(cur);
-    u32x4 wq[WDEPTH][G::SL];
-#pragma unroll
-    for (int u = 0; u < WDEPTH; ++u) wfetch<G::SL>(wq[u], cur, next);      // the first weight slices travel while the tile is loaded
-
+    // ---- prologue: the attention tile and one quad of the four parameter vectors per thread in ONE batch of loads (clamped indices,
+    //      stored to LDS under the predicate), then the first WDEPTH weight slices; the LDS writes wait for the older loads only ----
+    u32x4 tl[NT];
+    constexpr int NV = NPW * WPASS / VEC;
     {
         const T* att = (const T*)p.att + (long long)g * p.rows * C;
-        const int nv = C / VEC;
-        for (int i = tid; i < WROWS * nv; i += WT) {               // (rows beyond the tensor: clamped, never stored)
-            const int row = i / nv, v = i - row * nv;
+#pragma unroll
+        for (int it = 0; it < NT; ++it) {                          // (rows beyond the tensor: clamped, never stored)
+            const int i = tid + it * WT, row = i / NV, v = i - row * NV;
             long long r = r0 + row;
             r = r < p.rows ? r : p.rows - 1;
-            *(u32x4*)(T0 + (size_t)row * SA + v * 16) = *(const u32x4*)(att + r * C + v * VEC);
+            tl[it] = *(const u32x4*)(att + r * C + v * VEC);
         }
-        const float* b1 = p.b1 + g * p.b1_gs;
-        for (int i = tid; i < p.hid / KS; i += WT) b1s[i] = b1[chunk0 * WPASS + i];
     }
+    const int pqi = tid < C ? tid : C - 1, pw = pqi / (C / 4), po = 4 * pqi - pw * C;        // C quads (<= threads): vector pw, element po
+    const f32x4 pq = *(const f32x4*)((pw == 0 ? p.ln_m_g : pw == 1 ? p.ln_m_b : pw == 2 ? p.bo + g * p.bo_gs : p.b2 + g * p.b2_gs) + po);
+
+    const u32x4* wof = (const u32x4*)((const T*)p.wo + g * p.wo_gs);
+    const u32x4* w1f = (const u32x4*)((const T*)p.w1 + g * p.w1_gs);
+    const u32x4* w2f = (const u32x4*)((const T*)p.w2 + g * p.w2_gs);
+    const WMlpSegs segs{NPW, G::NW, wn, ks_row, ks_row4, nsl, NSL2, nchunk, chunk0, WPASS / KST};
+    auto mats = [&](int m) { return m == 0 ? wof : m == 1 ? w1f : w2f; };
+    WCursor cur;
+    wcursor_start(cur, G::SL, segs);
+    u32x4 wq[WDEPTH][G::SL];
+#pragma unroll
+    for (int u = 0; u < WDEPTH; ++u) wfetch<G::SL>(wq[u], cur, segs, mats);      // the first weight slices travel while the tile is stored
+
+#pragma unroll
+    for (int it = 0; it < NT; ++it) {
+        const int i = tid + it * WT, row = i / NV, v = i - row * NV;
+        *(u32x4*)(T0 + (size_t)row * SA + v * 16) = tl[it];
+    }
+    if (tid < C) *(f32x4*)(prm + 4 * tid) = pq;
     lds_barrier();
 
     bool rok[2];
@@ -314,9 +345,11 @@ __global__ __launch_bounds__(G::WT) void dmff_wide_proj_mlp_kernel(const WideP p
         const long long grow = rok[t] ? row : p.rows - 1;
         xres[t] = (const T*)p.x + g * p.x_gs + grow * C;
         yrow[t] = (T*)p.y + g * p.y_gs + grow * p.ldy;
-        x32row[t] = (R32 && p.x32) ? p.x32 + ((long long)g * p.rows + grow) * C : nullptr;
         y32row[t] = R32 ? p.y32 + ((long long)g * p.rows + grow) * C : nullptr;
+        // (first iteration, no x32: the fp32 residual load below still goes out — to this lane's row of y32, any mapped address — and is discarded)
+        x32row[t] = R32 ? (p.x32 ? p.x32 + ((long long)g * p.rows + grow) * C : y32row[t]) : nullptr;
     }
+    const bool has32 = R32 && p.x32 != nullptr;
     using XQ = typename std::conditional<R32, f32x4, typename Quad<DT>::type>::type;      // x_att per (pass, row half, channel quad): fp32, or rounded to the storage type
     auto xq_pack = [](float a, float b, float c, float d) -> XQ {
         if constexpr (R32) return f32x4{a, b, c, d};
@@ -331,16 +364,41 @@ __global__ __launch_bounds__(G::WT) void dmff_wide_proj_mlp_kernel(const WideP p
     constexpr bool PARK = NPW >= 2 || KS > 1;          // (hidden split: the reduce launch reads x_att from the output rows)
     XQ xatt[NPW][2][4];
     {
-        const float* bias = p.bo + g * p.bo_gs;
+        const float* bias = prm + 2 * C;                              // b_o (LDS)
         const float ca = p.c_acc_a[g], cr = p.c_res_a[g];
 #pragma unroll
         for (int i = 0; i < NPW; ++i) {
+            // the residual rows this pass's result meets: requested BEFORE the pass (unconditionally: the rows are clamped), so that they
+            // travel under its MFMAs and are older than its refills — the wait behind the pass leaves the weight ring alone
+            // (the fp32 stream at C = 512 has no 48 registers to spare across the pass: its rows are requested behind it, still as one batch)
+            constexpr bool AHEAD = !(R32 && NPW > 1);
+            typename Quad<DT>::type xr[2][4];
+            f32x4 xr32[R32 ? 2 : 1][R32 ? 4 : 1];
+            auto request = [&]() {
+#pragma unroll
+                for (int t = 0; t < 2; ++t)
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) {
+                        const int n = i * WPASS + wn * 32 + 8 * q + 4 * hi;
+                        xr[t][q] = *(const typename Quad<DT>::type*)(xres[t] + n);
+                        if constexpr (R32) xr32[t][q] = *(const f32x4*)(x32row[t] + n);
+                    }
+            };
+            if constexpr (AHEAD) request();
             f32x16 acc[2];
 #pragma unroll
             for (int t = 0; t < 2; ++t)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) acc[t][r] = 0.0f;
-            wpass<DT, G::SL>(acc, T0, SA, nsl, wq, cur, next);
+            wpass<DT, G::SL>(acc, T0, SA, nsl, wq, cur, segs, mats);
+            if constexpr (!AHEAD) request();
+#pragma unroll
+            for (int t = 0; t < 2; ++t)
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    asm volatile("" : "+v"(xr[t][q]));                // (consumed here, behind the pass: the loads stay where they were written)
+                    if constexpr (R32) asm volatile("" : "+v"(xr32[t][q]));
+                }
 #pragma unroll
             for (int t = 0; t < 2; ++t)
 #pragma unroll
@@ -348,8 +406,11 @@ __global__ __launch_bounds__(G::WT) void dmff_wide_proj_mlp_kernel(const WideP p
                     const int n = i * WPASS + wn * 32 + 8 * q + 4 * hi;
                     const f32x4 bv = *(const f32x4*)(bias + n);
                     float rv[4], v[4];
-                    if (R32 && x32row[t]) { const f32x4 r4 = *(const f32x4*)(x32row[t] + n); rv[0] = r4[0]; rv[1] = r4[1]; rv[2] = r4[2]; rv[3] = r4[3]; }
-                    else unpack4<DT>(*(const typename Quad<DT>::type*)(xres[t] + n), rv);
+                    unpack4<DT>(xr[t][q], rv);
+                    if constexpr (R32) {
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) rv[j] = has32 ? xr32[t][q][j] : rv[j];
+                    }
 #pragma unroll
                     for (int j = 0; j < 4; ++j) v[j] = __builtin_fmaf(cr, rv[j], (acc[t][4 * q + j] + bv[j]) * ca);
                     xatt[i][t][q] = xq_pack(v[0], v[1], v[2], v[3]);
@@ -416,7 +477,7 @@ __global__ __launch_bounds__(G::WT) void dmff_wide_proj_mlp_kernel(const WideP p
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 const int n = i * WPASS + wn * 32 + 8 * q + 4 * hi;
-                const f32x4 gv = *(const f32x4*)(p.ln_m_g + n), bv = *(const f32x4*)(p.ln_m_b + n);
+                const f32x4 gv = *(const f32x4*)(prm + n), bv = *(const f32x4*)(prm + C + n);          // (LDS)
 #pragma unroll
                 for (int t = 0; t < 2; ++t) {
                     float v[4], o[4];
@@ -444,27 +505,33 @@ __global__ __launch_bounds__(G::WT) void dmff_wide_proj_mlp_kernel(const WideP p
         for (int t = 0; t < 2; ++t)
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc2[i][t][r] = 0.0f;
+    const float* b1 = p.b1 + g * p.b1_gs + (long long)chunk0 * WPASS + wn * 32 + 4 * hi;
     for (int chunk = 0; chunk < nchunk; ++chunk) {
+        f32x4 b1q[4];                                              // this lane's fc1 biases of the chunk: requested before the pass, as the residual rows above
+#pragma unroll
+        for (int q = 0; q < 4; ++q) b1q[q] = *(const f32x4*)(b1 + chunk * WPASS + 8 * q);
         f32x16 acc[2];
 #pragma unroll
         for (int t = 0; t < 2; ++t)
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[t][r] = 0.0f;
-        wpass<DT, G::SL>(acc, T0, SA, nsl, wq, cur, next);
+        wpass<DT, G::SL>(acc, T0, SA, nsl, wq, cur, segs, mats);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) asm volatile("" : "+v"(b1q[q]));
         lds_barrier();                                             // every wave is done with the previous chunk's H
 #pragma unroll
         for (int t = 0; t < 2; ++t)
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 const int nl = wn * 32 + 8 * q + 4 * hi;
-                const f32x4 bv = *(const f32x4*)(b1s + chunk * WPASS + nl);
+                const f32x4 bv = b1q[q];
                 *(typename Quad<DT>::type*)(Hb + (size_t)(t * 32 + l31) * SH + nl * EB) =
                     pack4<DT>(apply_act<ICAF_ACT_GELU, DT>(acc[t][4 * q] + bv[0]), apply_act<ICAF_ACT_GELU, DT>(acc[t][4 * q + 1] + bv[1]),
                               apply_act<ICAF_ACT_GELU, DT>(acc[t][4 * q + 2] + bv[2]), apply_act<ICAF_ACT_GELU, DT>(acc[t][4 * q + 3] + bv[3]));
             }
         lds_barrier();
 #pragma unroll
-        for (int i = 0; i < NPW; ++i) wpass<DT, G::SL>(acc2[i], Hb, SH, NSL2, wq, cur, next);
+        for (int i = 0; i < NPW; ++i) wpass<DT, G::SL>(acc2[i], Hb, SH, NSL2, wq, cur, segs, mats);
     }
     // ---- output: x' = c_res2 * x_att + c_acc2 * (mlp + b2) ----
     if constexpr (KS > 1) {                            // hidden split: this workgroup's share of the fc2 sums, fp32; dmff_wide_reduce_kernel finishes
@@ -480,7 +547,7 @@ __global__ __launch_bounds__(G::WT) void dmff_wide_proj_mlp_kernel(const WideP p
                         *(f32x4*)(part + (r0 + t * 32 + l31) * C + n) = f32x4{acc2[i][t][4 * q], acc2[i][t][4 * q + 1], acc2[i][t][4 * q + 2], acc2[i][t][4 * q + 3]};
             }
     } else {
-        const float* b2 = p.b2 + g * p.b2_gs;
+        const float* b2 = prm + 3 * C;                            // (LDS)
         const float ca = p.c_acc_m[g], cr = p.c_res_m[g];
 #pragma unroll
         for (int i = 0; i < NPW; ++i)
@@ -573,24 +640,26 @@ static int wide_fill(const icaf_dmff_args* a, WideP& p, const char* who) {
     return ICAF_OK;
 }
 
-template <int DT, class G>
+template <int DT, class G, int NT>
 static int launch_wide_ln_qkv(const WideP& p, hipStream_t s) {
-    const size_t lds = (size_t)WROWS * (p.C * Elem<DT>::BYTES + 16);
-    ICAF_LDS_OPTIN((dmff_wide_ln_qkv_kernel<DT, G>), lds);        // (size checked on EVERY call, attribute raised per device as needed)
+    if (WROWS * (p.C / Elem<DT>::VEC) != NT * G::WT) return fail(ICAF_ERR_UNSUPPORTED, "icaf_dmff_wide_ln_qkv: C=%d is not the width this build loads its tile for", p.C);
+    const size_t lds = (size_t)WROWS * (p.C * Elem<DT>::BYTES + 16) + (size_t)(2 * p.C + 3 * G::WPASS) * sizeof(float);      // tile, gamma | beta, biases
+    ICAF_LDS_OPTIN((dmff_wide_ln_qkv_kernel<DT, G, NT>), lds);        // (size checked on EVERY call, attribute raised per device as needed)
     const long long work = ((p.rows + WROWS - 1) / WROWS) * (3 * (p.C / G::WPASS) / p.qkv_npass);
-    hipLaunchKernelGGL((dmff_wide_ln_qkv_kernel<DT, G>), dim3((unsigned)(8 * ((work + 3) / 4))), dim3(G::WT), lds, s, p);
+    hipLaunchKernelGGL((dmff_wide_ln_qkv_kernel<DT, G, NT>), dim3((unsigned)(8 * ((work + 3) / 4))), dim3(G::WT), lds, s, p);
     ICAF_LAUNCH_CHECK();
     return ICAF_OK;
 }
 
 template <class G>
-static size_t wide_proj_mlp_lds(int C, int hid, int eb = 2) {
-    return (size_t)WROWS * (C * eb + 16) + (size_t)WROWS * (G::WPASS * eb + 16) + G::NW * 64 * sizeof(float) + (size_t)hid * sizeof(float);
+static size_t wide_proj_mlp_lds(int C, int eb = 2) {          // tile, hidden chunk, row sums, the four parameter vectors
+    return (size_t)WROWS * (C * eb + 16) + (size_t)WROWS * (G::WPASS * eb + 16) + G::NW * 64 * sizeof(float) + (size_t)4 * C * sizeof(float);
 }
 
 template <int DT, int NPW, class G, bool R32 = false>
 static int launch_wide_proj_mlp(const WideP& p, hipStream_t s) {
-    const size_t lds = wide_proj_mlp_lds<G>(p.C, p.hid, Elem<DT>::BYTES);
+    if (p.C != NPW * G::WPASS) return fail(ICAF_ERR_UNSUPPORTED, "icaf_dmff_wide_proj_mlp: C=%d is not the width this build loads its tile for", p.C);
+    const size_t lds = wide_proj_mlp_lds<G>(p.C, Elem<DT>::BYTES);
     ICAF_LDS_OPTIN((dmff_wide_proj_mlp_kernel<DT, NPW, 1, G, R32>), lds);
     const long long ntiles = (p.rows + WROWS - 1) / WROWS;
     hipLaunchKernelGGL((dmff_wide_proj_mlp_kernel<DT, NPW, 1, G, R32>), dim3((unsigned)(8 * ((ntiles + 3) / 4))), dim3(G::WT), lds, s, p);
@@ -600,7 +669,8 @@ static int launch_wide_proj_mlp(const WideP& p, hipStream_t s) {
 
 template <int DT, int NPW, int KS, bool R32 = false>
 static int launch_wide_proj_mlp_split(const WideP& p, hipStream_t s) {
-    const size_t lds = wide_proj_mlp_lds<WG8>(p.C, p.hid / KS);
+    if (p.C != NPW * WG8::WPASS) return fail(ICAF_ERR_UNSUPPORTED, "icaf_dmff_wide_proj_mlp_split: C=%d is not the width this build loads its tile for", p.C);
+    const size_t lds = wide_proj_mlp_lds<WG8>(p.C);
     ICAF_LDS_OPTIN((dmff_wide_proj_mlp_kernel<DT, NPW, KS, WG8, R32>), lds);
     const long long ntiles = (p.rows + WROWS - 1) / WROWS, per = 4 / KS;
     hipLaunchKernelGGL((dmff_wide_proj_mlp_kernel<DT, NPW, KS, WG8, R32>), dim3((unsigned)(8 * ((ntiles + per - 1) / per))), dim3(WG8::WT), lds, s, p);
@@ -620,7 +690,8 @@ static int dispatch_wide_split(const WideP& p, int ksplit, hipStream_t s) {
 
 template <int DT>
 static int dispatch_wide_ln_qkv(const WideP& p, hipStream_t s) {
-    return p.C == 128 ? launch_wide_ln_qkv<DT, WG4>(p, s) : launch_wide_ln_qkv<DT, WG8>(p, s);
+    if (p.C == 128) return launch_wide_ln_qkv<DT, WG4, 4>(p, s);
+    return p.C == 256 ? launch_wide_ln_qkv<DT, WG8, 4>(p, s) : launch_wide_ln_qkv<DT, WG8, 8>(p, s);
 }
 
 template <int DT>
@@ -659,7 +730,7 @@ extern "C" int icaf_dmff_wide_ln_qkv(const icaf_dmff_args* a, icaf_stream_t s) {
     if (st) return st;
     if (!a->qkv || !a->wqkv || !a->bqkv || !a->ln_attn_gamma[0] || !a->ln_attn_gamma[1] || !a->ln_attn_beta[0] || !a->ln_attn_beta[1])
         return fail(ICAF_ERR_ARG, "icaf_dmff_wide_ln_qkv: null pointer");
-    if (a->dtype == ICAF_F32) return launch_wide_ln_qkv<ICAF_F32, WG4>(p, S(s));
+    if (a->dtype == ICAF_F32) return launch_wide_ln_qkv<ICAF_F32, WG4, 8>(p, S(s));
     return a->dtype == ICAF_BF16 ? dispatch_wide_ln_qkv<ICAF_BF16>(p, S(s)) : dispatch_wide_ln_qkv<ICAF_F16>(p, S(s));
 }
 
