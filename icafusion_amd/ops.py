@@ -1409,6 +1409,149 @@ def missrate_evaluate(table, dt, dt_count, device="cuda"):
     return {"order": order, "dt_gt": dt_gt, "dt_ignore": dt_ignore, "gt_ignore": gt_ignore[:tab.labels]}
 
 
+class StatsStore:
+    """Data-set-wide store of validation statistics on the device (icaf_stats_stage): one row per detection of the pass, in the order in
+    which test.py's host loop concatenates its per-image `stats` (image order, then row order).  mask (capacity,) int16 holds the TP flags
+    (bit t = threshold t), conf (capacity,) fp32, cls (capacity,) int32; the cursor and the any_tp flag live on the device, so staging a
+    batch reads nothing back.  `capacity` is the host's upper bound of the rows (images x max_det): the store cannot overflow."""
+
+    def __init__(self, capacity, T, device="cuda"):
+        capacity, T = int(capacity), int(T)
+        if T < 1 or T > _lib.STATS_MAX_T:                 # the library's own limits (it refuses them too), before anything is allocated
+            raise _lib.IcafError(f"icaf_stats_stage: T must be in [1, {_lib.STATS_MAX_T}] ({T})")
+        if capacity < 1 or capacity > _lib.STATS_MAX_ROWS:
+            raise _lib.IcafError(f"icaf_stats_stage: the store's capacity must be in [1, {_lib.STATS_MAX_ROWS}] rows ({capacity})")
+        if torch.device(device).type != "cuda":
+            raise ValueError("the statistics store lives on a cuda device (no CPU fallback exists)")
+        self.capacity, self.T = capacity, T
+        self.mask = torch.zeros((capacity,), dtype=torch.int16, device=device)
+        self.conf = torch.zeros((capacity,), dtype=torch.float32, device=device)
+        self.cls = torch.zeros((capacity,), dtype=torch.int32, device=device)
+        self.state = torch.zeros((2,), dtype=torch.int32, device=device)           # cursor, any_tp
+        self._rows = None
+
+    def stage(self, correct, det, count, stream_ptr=None):
+        """Append one batch: correct (B, max_det, T) uint8, det (B, max_det, 6) fp32, count (B,) int32.  One launch, nothing is read back."""
+        stats_stage(correct, det, count, self.mask, self.conf, self.cls, self.state[0:1], self.state[1:2])(
+            stream_ptr if stream_ptr is not None else current_stream_ptr())
+        self._rows = None
+
+    def rows(self):
+        """The number of rows staged so far (reads the cursor: one synchronisation); raises if a batch did not fit."""
+        if self._rows is None:
+            self._rows = int(self.state[0].item())
+        if self._rows > self.capacity:
+            raise _lib.IcafError(f"the statistics store holds {self.capacity} rows, {self._rows} were staged")
+        return self._rows
+
+    def any_tp(self):
+        return bool(self.state[1].item())
+
+    def to_host(self):
+        """(correct (n, T) bool, conf (n,) fp32, cls (n,) int32) as numpy: what the host loop's concatenated `stats` hold."""
+        n = self.rows()
+        mask = self.mask[:n].cpu().numpy().view(np.uint16)
+        return ((mask[:, None] >> np.arange(self.T, dtype=np.uint16)[None, :]) & 1).astype(bool), self.conf[:n].cpu().numpy(), self.cls[:n].cpu().numpy()
+
+
+def stats_stage(correct, det, count, store_mask, store_conf, store_cls, cursor, any_tp, name="stats_stage"):
+    """One validation batch into the statistics store (icaf_stats_stage).  Shapes and dtypes are validated here; T and the capacity are
+    refused by the library, before any launch."""
+    if det.dim() != 3 or det.shape[2] != 6 or det.dtype != torch.float32 or not det.is_contiguous() or not det.is_cuda:
+        raise ValueError("det must be a contiguous cuda float32 (B, max_det, 6) tensor")
+    B, max_det, _ = det.shape
+    if correct.dim() != 3 or tuple(correct.shape[:2]) != (B, max_det) or correct.dtype != torch.uint8 or not correct.is_contiguous() or correct.device != det.device:
+        raise ValueError("correct must be a contiguous cuda uint8 (B, max_det, T) tensor beside det")
+    if count.dtype != torch.int32 or count.numel() != B or not count.is_contiguous() or count.device != det.device:
+        raise ValueError("count must be a cuda int32 (B,) tensor")
+    cap = store_mask.numel()
+    for t, dtype, what in ((store_mask, torch.int16, "store_mask"), (store_conf, torch.float32, "store_conf"), (store_cls, torch.int32, "store_cls")):
+        if t.dim() != 1 or t.numel() != cap or t.dtype != dtype or not t.is_contiguous() or t.device != det.device:
+            raise ValueError(f"{what} must be a contiguous {dtype} (capacity,) tensor beside det")
+    for t, what in ((cursor, "cursor"), (any_tp, "any_tp")):
+        if t.numel() != 1 or t.dtype != torch.int32 or t.device != det.device:
+            raise ValueError(f"{what} must be one cuda int32 beside det")
+    return Launch(lib().icaf_stats_stage, (correct.data_ptr(), det.data_ptr(), count.data_ptr(), B, max_det, correct.shape[2], store_mask.data_ptr(),
+                                          store_conf.data_ptr(), store_cls.data_ptr(), cap, cursor.data_ptr(), any_tp.data_ptr()),
+                  keep=(correct, det, count, store_mask, store_conf, store_cls, cursor, any_tp), name=name,
+                  nbytes=B * max_det * (correct.shape[2] + 24 + 10))
+
+
+def ap_workspace(n, T, device):
+    """(workspace uint8 tensor, byte offset of the tpc table int32 [T][n]) for ap_per_class_device (icaf_ap_workspace_bytes)."""
+    nbytes, tpc_off = C.c_size_t(0), C.c_size_t(0)
+    check(lib().icaf_ap_workspace_bytes(int(n), int(T), C.byref(nbytes), C.byref(tpc_off)), "icaf_ap_workspace_bytes")
+    return torch.empty((nbytes.value + 256,), dtype=torch.uint8, device=device), tpc_off.value
+
+
+def ap_per_class_device(stats, unique_classes, n_l, T=None, want_perm=False, want_tpc=False, stream_ptr=None):
+    """ap_per_class on the device (icaf_ap_per_class; reference utils/metrics.py:18-82) with a DEFINED order: class ascending, confidence
+    descending, equal confidences in arrival order.  stats: a StatsStore, or (mask int16 (>= n,), conf fp32, cls int32, n) device tensors
+    with T given; unique_classes / n_l: the sorted classes of the labels and their label counts (host sequences or numpy).
+    Returns a dict of numpy arrays: ap (nc, T), p / r / f1 (nc, 1000) fp64, best (the argmax index), tp / fp / fn (nc,), and on request
+    perm (n,) (sorted position -> arrival index) and tpc (T, n) (inclusive TP count inside the class, by sorted position)."""
+    if isinstance(stats, StatsStore):
+        mask, conf, cls, n, T = stats.mask, stats.conf, stats.cls, stats.rows(), stats.T
+    else:
+        mask, conf, cls, n = stats
+        n = int(n)
+        if T is None:
+            raise ValueError("T (the number of IoU thresholds) must be given with plain tensors")
+    if mask.dtype != torch.int16 or conf.dtype != torch.float32 or cls.dtype != torch.int32 or not mask.is_cuda:
+        raise ValueError("mask / conf / cls must be cuda int16 / float32 / int32 tensors")
+    if n < 0 or min(mask.numel(), conf.numel(), cls.numel()) < n or not (mask.is_contiguous() and conf.is_contiguous() and cls.is_contiguous()):
+        raise ValueError(f"mask / conf / cls must be contiguous and hold the {n} rows")
+    dev = mask.device
+    uc = np.ascontiguousarray(np.asarray(unique_classes).astype(np.int32))
+    nl = np.ascontiguousarray(np.asarray(n_l).astype(np.int32))
+    nc = int(uc.shape[0])
+    if uc.ndim != 1 or nl.shape != uc.shape or (nc > 1 and (np.diff(uc) <= 0).any()):
+        raise ValueError("unique_classes must be ascending and distinct, n_l their label counts")
+    uc_d, nl_d = torch.from_numpy(uc).to(dev), torch.from_numpy(nl).to(dev)
+    T = int(T)
+    ws, tpc_off = ap_workspace(n, T, dev) if 1 <= T <= _lib.STATS_MAX_T and 0 <= n <= _lib.STATS_MAX_ROWS else (torch.empty((512,), dtype=torch.uint8, device=dev), 0)
+    shift = (-ws.data_ptr()) % 256
+    ap = torch.zeros((max(nc, 1), max(T, 1)), dtype=torch.float64, device=dev)
+    p, r, f1 = (torch.zeros((max(nc, 1), _lib.AP_CURVE_POINTS), dtype=torch.float64, device=dev) for _ in range(3))
+    best = torch.zeros((1,), dtype=torch.int32, device=dev)
+    report = torch.zeros((max(nc, 1), 3), dtype=torch.float64, device=dev)
+    perm = torch.zeros((max(n, 1),), dtype=torch.int32, device=dev) if want_perm else None
+    check(lib().icaf_ap_per_class(mask.data_ptr() or None, conf.data_ptr() or None, cls.data_ptr() or None, n, T, uc_d.data_ptr() or None,
+                                 nl_d.data_ptr() or None, nc, ap.data_ptr(), p.data_ptr(), r.data_ptr(), f1.data_ptr(), best.data_ptr(),
+                                 report.data_ptr(), perm.data_ptr() if perm is not None else None, ws.data_ptr() + shift, ws.numel() - shift,
+                                 stream_ptr if stream_ptr is not None else current_stream_ptr()), "icaf_ap_per_class")
+    rep = report[:nc].cpu().numpy()
+    out = {"ap": ap[:nc, :T].cpu().numpy(), "p": p[:nc].cpu().numpy(), "r": r[:nc].cpu().numpy(), "f1": f1[:nc].cpu().numpy(),
+           "best": int(best.item()), "tp": rep[:, 0].copy(), "fp": rep[:, 1].copy(), "fn": rep[:, 2].copy()}
+    if want_perm:
+        out["perm"] = perm[:n].cpu().numpy()
+    if want_tpc:
+        out["tpc"] = ws[shift + tpc_off:shift + tpc_off + 4 * T * max(n, 1)].view(torch.int32).view(T, max(n, 1))[:, :n].cpu().numpy()
+    return out
+
+
+def confusion_matrix(predn, det, count, labels, label_off, matrix, conf=0.25, iou_thres=0.45, name="confusion_matrix"):
+    """One batch into the confusion matrix (icaf_confusion_matrix; reference utils/metrics.py:121-159): predn (B, max_det, 4) native-space
+    boxes as match_predictions writes them, det (B, max_det, 6), count (B,) int32, labels (L, 5) fp32 [cls, x1, y1, x2, y2] sorted by image,
+    label_off (B + 1,) int32, matrix (nc + 1, nc + 1) int32 on the device (accumulated).  IoU ties: lowest label, then lowest detection."""
+    if det.dim() != 3 or det.shape[2] != 6 or det.dtype != torch.float32 or not det.is_contiguous() or not det.is_cuda:
+        raise ValueError("det must be a contiguous cuda float32 (B, max_det, 6) tensor")
+    B, max_det, _ = det.shape
+    if tuple(predn.shape) != (B, max_det, 4) or predn.dtype != torch.float32 or not predn.is_contiguous() or predn.device != det.device:
+        raise ValueError("predn must be a contiguous cuda float32 (B, max_det, 4) tensor beside det")
+    if count.dtype != torch.int32 or count.numel() != B or not count.is_contiguous() or count.device != det.device:
+        raise ValueError("count must be a cuda int32 (B,) tensor")
+    if label_off.dtype != torch.int32 or label_off.numel() != B + 1 or not label_off.is_contiguous() or label_off.device != det.device:
+        raise ValueError("label_off must be a cuda int32 (B + 1,) tensor")
+    if labels.dtype != torch.float32 or not labels.is_contiguous() or (labels.numel() and (labels.dim() != 2 or labels.shape[1] != 5 or labels.device != det.device)):
+        raise ValueError("labels must be a contiguous cuda float32 (L, 5) tensor")
+    if matrix.dim() != 2 or matrix.shape[0] != matrix.shape[1] or matrix.shape[0] < 2 or matrix.dtype != torch.int32 or not matrix.is_contiguous() or matrix.device != det.device:
+        raise ValueError("matrix must be a contiguous cuda int32 (nc + 1, nc + 1) tensor")
+    return Launch(lib().icaf_confusion_matrix, (predn.data_ptr(), det.data_ptr(), count.data_ptr(), B, max_det, labels.data_ptr() if labels.numel() else None,
+                                               label_off.data_ptr(), matrix.shape[0] - 1, float(conf), float(iou_thres), matrix.data_ptr()),
+                  keep=(predn, det, count, labels, label_off, matrix), name=name, nbytes=B * max_det * 40)
+
+
 def letterbox_direct(on=True):
     """Force icaf_letterbox_frames onto its direct path (no LDS staging) inside a `with`: an A/B knob of the library, it changes no result."""
     return _caller_knob("letterbox_direct", on)
@@ -1422,19 +1565,23 @@ def area_direct(on=True):
 # ------------------------------------------------------------------------------------------------------------
 # graph capture + events
 # ------------------------------------------------------------------------------------------------------------
-def match_predictions(det, count, labels, label_off, iouv, scale=None, predn=None, stream_ptr=None):
+def match_predictions(det, count, labels, label_off, iouv, scale=None, predn=None, stream_ptr=None, max_labels=None):
     """TP flags of every detection at every IoU threshold on the device (icaf_match_predictions; reference
     test.py:196-230).  det (B, max_det, 6) / count (B,) int32: the NMS output block; labels (L, 5) fp32 [cls, x1, y1,
     x2, y2] in native image space sorted by image, label_off (B + 1,) int32; scale (B, 5) fp32 [gain, pad_x, pad_y, w0,
-    h0] or None; iouv (T,) fp32.  Returns uint8 (B, max_det, T); rows >= count[b] are unspecified."""
+    h0] or None; iouv (T,) fp32.  Returns uint8 (B, max_det, T); rows >= count[b] are unspecified.  max_labels: the host's
+    maximum of labels per image (it built label_off); when given, label_off is not read back."""
     B, max_det, six = det.shape
     assert six == 6 and det.dtype == torch.float32 and det.is_contiguous() and count.dtype == torch.int32
     assert label_off.dtype == torch.int32 and label_off.numel() == B + 1 and iouv.dtype == torch.float32
     assert labels.dtype == torch.float32 and labels.is_contiguous() and (labels.numel() == 0 or labels.shape[1] == 5)
     T = iouv.numel()
     correct = torch.empty((B, max_det, T), dtype=torch.uint8, device=det.device)
-    off = label_off.cpu()
-    max_l = int((off[1:] - off[:-1]).max()) if B else 0
+    if max_labels is None:
+        off = label_off.cpu()
+        max_l = int((off[1:] - off[:-1]).max()) if B else 0
+    else:
+        max_l = int(max_labels)
     st = lib().icaf_match_predictions(det.data_ptr(), count.data_ptr(), B, max_det, labels.data_ptr() if labels.numel() else None,
                                       label_off.data_ptr(), max_l, scale.data_ptr() if scale is not None else None, iouv.data_ptr(), T,
                                       correct.data_ptr(), predn.data_ptr() if predn is not None else None,

@@ -610,6 +610,58 @@ int icaf_loss(ICAF_HOST const float* const* maps, ICAF_HOST const int* ny, ICAF_
               const float* targets, int nt, ICAF_HOST const icaf_loss_params* prm, float* out, int* counts, void* workspace, size_t workspace_bytes,
               icaf_stream_t s);
 
+/* ---- Validation statistics: store, ap_per_class, ConfusionMatrix (test.py:144-230, 287-321; utils/metrics.py:18-82, 85-110, 113-159) ---
+ * icaf_stats_stage (test.py:198-230, the `stats.append` of every image): one validation batch into a data-set-wide store.  correct [B][max_det][T]
+ *   uint8 as icaf_match_predictions leaves it, det [B][max_det][6], count [B].  Row i < min(max(count[b], 0), max_det) of image b lands at
+ *   cursor + (rows of the images before b) + i: image order, then row order.  store_mask [capacity] uint16 (bit t = correct[b][i][t] != 0),
+ *   store_conf [capacity] fp32 (det column 4), store_cls [capacity] int32 ((int) of det column 5); cursor [1] int32 is advanced by the batch's
+ *   rows, any_tp [1] int32 becomes 1 if any stored bit is set.  One launch of one workgroup: it forms the prefix, reads and advances the cursor,
+ *   so no atomic decides an order; calls on one stream append in call order.  Nothing is written at or beyond `capacity`: a batch that does not
+ *   fit still advances the cursor past the capacity (the host sees the overflow), after which every further call writes nothing.  Rows of
+ *   correct / det at or beyond count[b] are never read.  ICAF_ERR_UNSUPPORTED before any launch: T outside [1, ICAF_STATS_MAX_T], capacity
+ *   outside [1, ICAF_STATS_MAX_ROWS], B outside [1, ICAF_STATS_MAX_BATCH].
+ * icaf_ap_per_class (utils/metrics.py:18-82 with compute_ap, :85-110): mask / conf / cls [n] as the store holds them, unique_classes [nc] int32
+ *   (DEVICE; ascending, from the labels) and n_l [nc] int32 (DEVICE; their label counts); all arithmetic the reference does in float64 is fp64
+ *   without contraction, in its operation order.
+ *   ORDER (the reference's np.argsort(-conf) leaves ties to the numpy build): class ascending, confidence descending, equal confidences in
+ *     arrival order — a stable LSD radix sort over the bit pattern of the fp32 confidence and one 8-bit class pass, ICAF_STATS_SORT_TILE rows
+ *     per workgroup.  PRECONDITIONS: conf finite and >= 0, classes in [0, 256) (a class outside is sorted as 0 / 255).  perm [n] (may be NULL)
+ *     receives the arrival index of every sorted position.
+ *   Per class ci with predictions and labels: tpc[t][i] the inclusive count of bit t over the class's rows (workspace, at tpc_off: int32 [T][n]
+ *     indexed by sorted position; fpc = (row in class + 1) - tpc); recall = tpc / (n_l + 1e-16), precision = tpc / (tpc + fpc);
+ *     r[ci] = interp(-px, -conf, recall[:, 0], left = 0), p[ci] likewise with left = 1, px = linspace(0, 1, 1000); ap[ci][t] = trapezoid sum in
+ *     index order of interp(linspace(0, 1, 101), [0, recall, recall[-1] + 0.01], envelope([1, precision, 0])).  interp is np.interp: below xp[0]
+ *     `left`, above xp[-1] fp[-1], otherwise j = the LARGEST index with xp[j] <= x and fp[j] if j is the last index or xp[j] == x, else
+ *     ((fp[j+1] - fp[j]) / (xp[j+1] - xp[j])) * (x - xp[j]) + fp[j].  A class without predictions (or with n_l <= 0) keeps zero rows; predictions
+ *     of a class that is not in unique_classes are ignored.
+ *   f1 = 2 p r / (p + r + 1e-16); best [1] = the first argmax over the 1000 points of the class mean (classes summed in order, then divided);
+ *     report [nc][3] fp64 = {tp, fp, fn} at that index: tp = rint(r * n), fn = n - tp, fp = rint(tp / (p + 1e-16) - tp) with n = n_l[nc - 1]
+ *     for EVERY class (the reference's loop variable, :45, read after the loop, :78-80), rounding half to even.
+ *   Outputs ap [nc][T], p / r / f1 [nc][1000] fp64.  Integer scans and fixed-order sums: two calls give the same bits.  n = 0 is valid.
+ *   ICAF_ERR_UNSUPPORTED before any launch: nc > ICAF_STATS_MAX_CLASSES, T outside [1, ICAF_STATS_MAX_T], n > ICAF_STATS_MAX_ROWS;
+ *   ICAF_ERR_ARG for null pointers, nc < 1, a short or misaligned (256 bytes) workspace (icaf_ap_workspace_bytes; contents irrelevant on entry).
+ * icaf_confusion_matrix (ConfusionMatrix.process_batch, :121-159), one workgroup per image, integer atomics into matrix [(nc+1)][(nc+1)] int32
+ *   (accumulated, never cleared here; rows = predicted class, columns = true class, index nc = background).  predn [B][max_det][4] native-space
+ *   boxes as icaf_match_predictions writes them, det (conf column 4, class column 5), count, labels [L][5] (cls, x1, y1, x2, y2), label_off [B+1].
+ *   Detections with conf > `conf` (fp32) are kept, classes truncated to int; (label, detection) is a candidate when the fp32 box_iou
+ *   (utils/general.py:455-477: inter / (area_label + area_det - inter)) is > iou_thres; every detection keeps its highest-IoU label, every label
+ *   the highest-IoU detection among those that chose it; a matched label adds matrix[cls(det)][cls(label)], an unmatched one
+ *   matrix[nc][cls(label)]; ONLY IF the image has a match, every kept detection that matched no label adds matrix[cls(det)][nc] (the
+ *   reference's `if n:`).  IoU TIES: the reference's order comes from an unstable argsort; here the lowest label index wins, then the lowest
+ *   detection index.  An image with no detections or no labels contributes nothing (test.py never calls process_batch for it).  A class outside
+ *   [0, nc) adds nothing (the reference raises).  Bounds come from count / label_off only; rows at or beyond count[b] are never read.
+ *   max_det above 1024 is ICAF_ERR_UNSUPPORTED. */
+enum { ICAF_STATS_MAX_T = 16, ICAF_STATS_MAX_ROWS = 16777216, ICAF_STATS_MAX_CLASSES = 256, ICAF_STATS_MAX_BATCH = 4096,
+       ICAF_STATS_SORT_TILE = 4096, ICAF_AP_CURVE_POINTS = 1000 };
+int icaf_stats_stage(const unsigned char* correct, const float* det, const int* count, int B, int max_det, int T, void* store_mask,
+                     float* store_conf, int* store_cls, int capacity, int* cursor, int* any_tp, icaf_stream_t s);
+int icaf_ap_workspace_bytes(int n, int T, ICAF_HOST size_t* bytes, ICAF_HOST size_t* tpc_off);
+int icaf_ap_per_class(const void* mask, const float* conf, const int* cls, int n, int T, const int* unique_classes, const int* n_l, int nc,
+                      double* ap, double* p, double* r, double* f1, int* best, double* report, int* perm, void* workspace,
+                      size_t workspace_bytes, icaf_stream_t s);
+int icaf_confusion_matrix(const float* predn, const float* det, const int* count, int B, int max_det, const float* labels,
+                          const int* label_off, int nc, float conf, float iou_thres, int* matrix, icaf_stream_t s);
+
 /* ---- HIP graph capture / events (so the Python host never needs a tracing compiler) ------------------------ */
 int icaf_graph_begin(icaf_stream_t s);
 int icaf_graph_end(icaf_stream_t s, ICAF_HOST void** graph_exec);

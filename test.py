@@ -20,8 +20,14 @@ longest-side resize (pixel-area average when shrinking) and the padding run on t
 everything downstream as it is; `--hyp PATH` (or `test(compute_loss=...)`, as the reference's train.py:257,393 calls it) adds the validation
 loss — the forward value of the reference's ComputeLoss on the raw Detect maps of every batch (utils/loss.py:325-463; icaf_loss, no gradients),
 averaged over the batches as test.py:132-133,364-367 do, with the hyp gains scaled as train.py:238-241 scales them — fills the three trailing
-values and prints one `Loss:` line; there is no default hyp file, and without the flag nothing changes.  An image whose candidates exceed the confluence cap, or that keeps more than 1024 boxes, raises.  Not carried over (all outside the metric): plots / wandb /
-`--save-hybrid` auto-labelling / `--task study` / the pycocotools call / MR curves and plots; `--augment` raises (test-time augmentation is not built)."""
+values and prints one `Loss:` line; there is no default hyp file, and without the flag nothing changes.  An image whose candidates exceed the confluence cap, or that keeps more than 1024 boxes, raises.
+`--plots` builds the reference's ConfusionMatrix (test.py:103,205-206,320-321; conf 0.25 / IoU 0.45) on the device, one launch per batch, prints
+it and saves confusion_matrix.txt (and confusion_matrix.png when matplotlib is there); `--device-stats` keeps the statistics of the pass on the device: every batch is
+appended to an ops.StatsStore, nothing is read back per batch (result files excepted), the four synchronisations per batch become event pairs, and
+ap_per_class runs as kernels with a DEFINED order at equal confidences (arrival order; the host's np.argsort leaves it to the numpy build).  Without
+the two flags the loop runs the code it always ran.  Not carried over (all outside the metric): the PR / F1 / P / R curve images and `plot_images` /
+wandb / `--save-hybrid` auto-labelling / `--task study` / the pycocotools call / MR curves and plots; `--augment` raises (the help text says
+test-time augmentation is not built; Model.forward(augment=True) is by now — test() still refuses it)."""
 import argparse
 import os
 import time
@@ -39,21 +45,32 @@ from icafusion_amd.utils import missrate
 from icafusion_amd.utils.confluence import confluence_device
 from icafusion_amd.utils.loss import ComputeLoss, scale_hyp
 from icafusion_amd.utils.results import ResultWriter, frame_index, label_listing
-from icafusion_amd.utils.metrics import ap_per_class
+from icafusion_amd.utils.metrics import ConfusionMatrix, ap_per_class
 from icafusion_amd.utils.torch_utils import select_device, time_synchronized
 
 MATCH_MAX_DET = 1024                                             # detections per image icaf_match_predictions takes (nms.hip)
 
 
-def summarize(stats, nc, names, seen, verbose=False):
+def summarize(stats, nc, names, seen, verbose=False, store=None):
     """Statistics -> (mp, mr, map50, map, maps) + the reference's result table (test.py:287-313): for one class the columns are
     TP / FP / FN / F1 / P / R / mAP@.5 / mAP@.5:.95, otherwise P / R / mAP@.5 / mAP@.75 / mAP@.5:.95 with one row per class when
-    `verbose`.  stats: list of (correct (n, 10) bool, conf (n,), pcls (n,), tcls list) per image."""
+    `verbose`.  stats: list of (correct (n, 10) bool, conf (n,), pcls (n,), tcls list) per image — or, with `store` (an ops.StatsStore, the
+    `device_stats` path), the list of the images' label classes: the numbers then come from icaf_ap_per_class, and "no TP at all means
+    every metric is 0" reads the store's any_tp flag."""
     mp = mr = map50 = map75 = map_ = 0.0
     tp = fp = fn = f1 = np.zeros(1)
     p = r = np.zeros(0)
     ap, ap_class, nt = np.zeros((0, 10)), np.zeros(0, int), np.zeros(nc, int)
-    if stats:
+    if store is not None:
+        tcls = np.concatenate([np.asarray(t, np.float64) for t in stats]) if stats else np.zeros(0)
+        if store.rows() and store.any_tp():
+            ap_class, n_l = np.unique(tcls, return_counts=True)
+            res = ops.ap_per_class_device(store, ap_class, n_l)
+            i, ap, ap_class = res["best"], res["ap"], ap_class.astype("int32")
+            tp, fp, fn, p, r, f1 = res["tp"], res["fp"], res["fn"], res["p"][:, i], res["r"][:, i], res["f1"][:, i]
+            mp, mr, map50, map75, map_ = p.mean(), r.mean(), ap[:, 0].mean(), ap[:, 5].mean(), ap.mean()
+        nt = np.bincount(tcls.astype(np.int64), minlength=nc)
+    elif stats:
         cat = [np.concatenate([np.asarray(s[k]) for s in stats], 0) for k in range(4)]
         if len(cat[0]) and cat[0].any():
             tp, fp, fn, p, r, ap, f1, ap_class = ap_per_class(cat[0], cat[1], cat[2], cat[3])
@@ -115,7 +132,8 @@ class MissRate:
 @torch.no_grad()
 def test(data, weights=None, batch_size=32, imgsz=640, conf_thres=0.001, iou_thres=0.5, single_cls=False, model=None,
          dataloader=None, device="0", compute_dtype=None, cfg=None, verbose=False, save_json=False, save_txt=False, save_conf=True,
-         save_dir=None, augment=False, compute_loss=None, confluence=None, miss_rate=None, device_letterbox=False):
+         save_dir=None, augment=False, compute_loss=None, confluence=None, plots=False, device_stats=False, stats_out=None, miss_rate=None,
+         device_letterbox=False):
     if augment:
         raise NotImplementedError("test-time augmentation (models/yolo_test.py:116-132) is outside the inference hot path")
     if isinstance(data, str):
@@ -141,25 +159,34 @@ def test(data, weights=None, batch_size=32, imgsz=640, conf_thres=0.001, iou_thr
     iouv = np.linspace(0.5, 0.95, 10)
     names = data.get("names", [str(i) for i in range(nc)])
     stats, seen, t_inf, t_nms = [], 0, 0.0, 0.0
+    cmatrix = ConfusionMatrix(nc, device=dev) if plots else None          # test.py:103
+    store, events = None, []                                             # device_stats: the statistics stay on the device until the pass is over
+
+    def clock():                                                         # device_stats: an event on the stream instead of a synchronisation
+        if not device_stats:
+            return time_synchronized()
+        events.append(ops.Event())
+        events[-1].record(ops.current_stream_ptr())
+        return 0.0
     loss = torch.zeros(3, device=dev) if compute_loss else None          # box, obj, cls: summed on the device, read once after the loop
     for img, targets, paths, shapes in dataloader:
         if device_letterbox:                                     # native BGR frames as decoded: resized and padded on the device
             rgb, ir, (height, width) = img
             rgb, ir, nb = [f.to(dev, non_blocking=True) for f in rgb], [f.to(dev, non_blocking=True) for f in ir], len(rgb)
-            t = time_synchronized()
+            t = clock()
             res = model.forward_frames(rgb, ir, img_size=(height, width), val_size=imgsz)[0]
         else:
             img = img.to(dev, non_blocking=True)                 # uint8 (B, 6, H, W): cat(rgb, ir), test.py:116-123
             nb, _, height, width = img.shape
-            t = time_synchronized()
+            t = clock()
             res = model.forward_u8(img)
         out = res[0]
-        t_inf += time_synchronized() - t
+        t_inf += clock() - t
         if compute_loss:                                         # on the raw maps, before the labels go to pixels (test.py:132-133)
             loss += compute_loss(res[2], targets.to(dev))[1][:3]
         targets = targets.clone()
         targets[:, 2:] *= torch.tensor([width, height, width, height])
-        t = time_synchronized()
+        t = clock()
         if confluence is not None:                               # the reference's one-line swap (test.py:139-140)
             det, count, _ = confluence_device(out, conf_thres, confluence)
             for si, n in enumerate(count.tolist()):              # the matching kernel takes MATCH_MAX_DET rows per image
@@ -170,7 +197,7 @@ def test(data, weights=None, batch_size=32, imgsz=640, conf_thres=0.001, iou_thr
             det = det[:, :MATCH_MAX_DET].contiguous()
         else:
             det, count, _ = nms_device(out, conf_thres, iou_thres, multi_label=True, agnostic=single_cls)
-        t_nms += time_synchronized() - t
+        t_nms += clock() - t
         # statistics per image (reference test.py:144-230) on the device: labels go up in native image space, one kernel
         # maps the detections there (scale_coords + clip_coords) and matches them; only flags / conf / cls come back
         if single_cls:
@@ -185,12 +212,27 @@ def test(data, weights=None, batch_size=32, imgsz=640, conf_thres=0.001, iou_thr
             off.append(off[-1] + len(labels))
             (h0, w0), ((gain, _), (padw, padh)) = shapes[si][0], shapes[si][1]
             scale.append([gain, padw, padh, w0, h0])
-        predn = torch.zeros((nb, det.shape[1], 4), dtype=torch.float32, device=dev) if writer or mr_eval else None     # native-space boxes
-        correct = ops.match_predictions(det, count, torch.cat(lab_rows).float().contiguous().to(dev),
-                                        torch.tensor(off, dtype=torch.int32, device=dev), torch.from_numpy(iouv.astype(np.float32)).to(dev),
-                                        scale=torch.tensor(scale, dtype=torch.float32, device=dev), predn=predn)
+        predn = torch.zeros((nb, det.shape[1], 4), dtype=torch.float32, device=dev) if writer or mr_eval or cmatrix else None     # native-space boxes
+        lab_dev, off_dev = torch.cat(lab_rows).float().contiguous().to(dev), torch.tensor(off, dtype=torch.int32, device=dev)
+        correct = ops.match_predictions(det, count, lab_dev, off_dev, torch.from_numpy(iouv.astype(np.float32)).to(dev),
+                                        scale=torch.tensor(scale, dtype=torch.float32, device=dev), predn=predn,
+                                        **({"max_labels": max(len(t) for t in tcls_all)} if device_stats else {}))     # no label_off read-back
         if mr_eval:
             mr_eval.stage(predn, det, count, paths)
+        if cmatrix:                                              # test.py:205-206, every image of the batch in one launch
+            cmatrix.process_images(predn, det, count, lab_dev, off_dev)
+        if device_stats:                                         # nothing comes back: the rows go to the store in the host loop's order
+            if store is None:                                    # images x max_det rows: an upper bound of the cursor, it cannot overflow
+                store = ops.StatsStore(len(dataloader.dataset) * det.shape[1], len(iouv), dev)
+            store.stage(correct, det, count)
+            stats += tcls_all
+            seen += nb
+            if writer:                                           # the result files are written on the host: their rows still come back
+                cnt, cc, pn = count.cpu().numpy(), det[..., 4:6].cpu().numpy(), predn.cpu().numpy()
+                for si in range(nb):
+                    if cnt[si]:
+                        writer.add(paths[si], pn[si, :cnt[si]], cc[si, :cnt[si], 0], cc[si, :cnt[si], 1])
+            continue
         correct, cc, count = correct.cpu().numpy().astype(bool), det[..., 4:6].cpu().numpy(), count.cpu().numpy()
         predn = predn.cpu().numpy() if writer else None
         for si in range(nb):
@@ -208,8 +250,18 @@ def test(data, weights=None, batch_size=32, imgsz=640, conf_thres=0.001, iou_thr
         for f in (result_txt, pred_json):
             if f is not None:
                 print(f"saved {f}")
-    (mp, mr, map50, map_), maps, lines = summarize(stats, nc, names, seen, verbose)
+    if device_stats:                                             # the event pairs of every batch, read once the pass is over
+        ms = [a.elapsed_ms(b) for a, b in zip(events[0::2], events[1::2])]
+        t_inf, t_nms = sum(ms[0::2]) / 1e3, sum(ms[1::2]) / 1e3
+    if isinstance(stats_out, list):
+        stats_out.append(store) if device_stats else stats_out.extend(stats)
+    (mp, mr, map50, map_), maps, lines = summarize(stats, nc, names, seen, verbose, store=store)
     print("\n".join(lines))
+    if cmatrix:                                                  # test.py:320-321
+        cmatrix.print()
+        plot_dir = str(save_dir) if save_dir is not None else str(increment_path("runs/test/exp"))
+        os.makedirs(plot_dir, exist_ok=True)
+        cmatrix.plot(save_dir=plot_dir, names=list(names))
     tt = tuple(x / max(seen, 1) * 1e3 for x in (t_inf, t_nms, t_inf + t_nms)) + (imgsz, imgsz, batch_size)
     print("Speed: %.1f/%.1f/%.1f ms inference/NMS/total per %gx%g image at batch-size %g" % tt)
     lbox, lobj, lcls = (loss.cpu() / len(dataloader)).tolist() if compute_loss else (0.0, 0.0, 0.0)       # test.py:364-367
@@ -247,6 +299,10 @@ def parse_opt(argv=None):
                      help="suppress with confluence (normalised Manhattan proximity below P_THRES, utils/confluence.py) instead of NMS")
     ap_.add_argument("--hyp", type=str, default=None, metavar="PATH",
                      help="hyperparameter yaml: also report the validation loss (box / obj / cls, the forward value of ComputeLoss)")
+    ap_.add_argument("--plots", action="store_true", help="confusion matrix of the pass (conf 0.25 / IoU 0.45): printed, and saved as "
+                                                          "confusion_matrix.txt (+ .png with matplotlib) under <project>/<name>")
+    ap_.add_argument("--device-stats", action="store_true", help="keep the statistics on the device: nothing is read back per batch, "
+                                                                 "ap_per_class runs as kernels with a stable order at equal confidences")
     ap_.add_argument("--save-txt", action="store_true", help="per-image result lines + result.txt under <project>/<name>/labels")
     ap_.add_argument("--save-conf", action="store_true", help="append the confidence to every --save-txt line")
     ap_.add_argument("--save-json", action="store_true", help="<project>/<name>/<weights>_predictions.json")
@@ -296,7 +352,7 @@ if __name__ == "__main__":
             test(o.data, [w] if w else None, o.batch_size, imgsz, 0.25, 0.45, o.single_cls, device=o.device, compute_dtype=dtype, cfg=o.cfg,
                  device_letterbox=o.device_letterbox)
     else:
-        save_dir = increment_path(os.path.join(o.project, o.name), exist_ok=o.exist_ok) if (o.save_txt or o.save_json) else None
+        save_dir = increment_path(os.path.join(o.project, o.name), exist_ok=o.exist_ok) if (o.save_txt or o.save_json or o.plots) else None
         model, compute_loss = None, None
         if o.hyp:
             with open(o.data) as f:
@@ -305,4 +361,5 @@ if __name__ == "__main__":
             compute_loss = loss_from_hyp(o.hyp, model, nc, imgsz)
         test(o.data, o.weights, o.batch_size, imgsz, o.conf_thres, o.iou_thres, o.single_cls, device=o.device, compute_dtype=dtype, cfg=o.cfg,
              verbose=o.verbose, save_json=o.save_json, save_txt=o.save_txt, save_conf=o.save_conf, save_dir=save_dir, augment=o.augment,
-             miss_rate=o.miss_rate, device_letterbox=o.device_letterbox, confluence=o.confluence, model=model, compute_loss=compute_loss)
+             miss_rate=o.miss_rate, device_letterbox=o.device_letterbox, confluence=o.confluence, model=model, compute_loss=compute_loss,
+             plots=o.plots, device_stats=o.device_stats)
