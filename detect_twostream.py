@@ -58,6 +58,8 @@ def load_model(opt, device):
 
 @torch.no_grad()
 def detect(opt):
+    if getattr(opt, "merge_nms", False) and getattr(opt, "confluence", None) is not None:
+        raise ValueError("--merge-nms is a mode of NMS: it does not go with --confluence")
     device = select_device(opt.device)
     save_img = not opt.nosave
     save_dir = increment_path(Path(opt.project) / opt.name, exist_ok=opt.exist_ok)
@@ -91,7 +93,8 @@ def detect(opt):
                 det = det[(det[:, 5:6] == torch.tensor(opt.classes, device=det.device)).any(1)]
             pred = [det]
         else:
-            pred = non_max_suppression(pred, opt.conf_thres, opt.iou_thres, classes=opt.classes, agnostic=opt.agnostic_nms)
+            pred = non_max_suppression(pred, opt.conf_thres, opt.iou_thres, classes=opt.classes, agnostic=opt.agnostic_nms,
+                                       merge=getattr(opt, "merge_nms", False))
         t2 = time_synchronized()
         det = pred[0]
         p = Path(path)
@@ -148,6 +151,8 @@ def parse_opt(argv=None):
     ap.add_argument("--agnostic-nms", action="store_true")
     ap.add_argument("--confluence", type=float, default=None, metavar="P_THRES",
                     help="suppress with confluence (normalised Manhattan proximity below P_THRES, utils/confluence.py) instead of NMS")
+    ap.add_argument("--merge-nms", action="store_true", help="merge-NMS (utils/general.py:594-600): every kept box becomes the score-weighted mean "
+                    "of the candidates overlapping it; goes with --augment and ensembles, whose passes repeat every box")
     ap.add_argument("--project", default="runs/detect")
     ap.add_argument("--name", default="exp")
     ap.add_argument("--exist-ok", action="store_true")

@@ -29,6 +29,11 @@
 //   3. nms_rank_kernel         (only when keep_idx is requested) converts the kept slots into torchvision's indices: the
 //                              rank of the slot among the image's candidates = chunk counts before it + candidates before
 //                              it inside its chunk.
+//   icaf_nms_ex adds the two modes of the reference that icaf_nms cannot express (both described at their kernels below):
+//   1b. nms_label_keys_kernel  (apriori labels, :545-552) one workgroup per image behind the keys kernel: the label rows as candidates
+//                              behind the prediction rows.  The walk, rank and merge kernels then read such a slot's box from the label
+//                              table (decode_slot<true>); the plain path runs the <false> instantiations — the code it always ran.
+//   4.  nms_merge_kernel       (merge-NMS, :594-600) one workgroup per image behind the walk and the rank kernel.
 // All box arithmetic is fp32 with contraction disabled, in the reference's operation order, so kept indices are
 // bit-identical to the CPU algorithm on the same prediction tensor.
 #pragma clang fp contract(off)
@@ -202,10 +207,22 @@ struct WalkSmem {
     int mode_b_bin;
 };
 
-// decode the box of candidate slot `slot`: xywh -> xyxy exactly as the reference (utils/general.py:332-339)
+// decode the box of candidate slot `slot`: xywh -> xyxy exactly as the reference (utils/general.py:332-339).  LAB: rows at or beyond `rows` are
+// the image's apriori labels (lb = its first label row, [cls, cx, cy, w, h]): obj = 1, one-hot class confidence (:548-551), read where they lie
+template <bool LAB>
 __device__ __forceinline__ void decode_slot(const float* __restrict__ pb, const unsigned short* __restrict__ cb, int nc, int multi,
-                                            unsigned int slot, float& x1, float& y1, float& x2, float& y2, float& sc, int& cl) {
+                                            unsigned int slot, const float* __restrict__ lb, long long rows, float& x1, float& y1, float& x2,
+                                            float& y2, float& sc, int& cl) {
     const unsigned int row = multi ? slot / (unsigned)nc : slot;
+    if (LAB && (long long)row >= rows) {
+        const float* l = lb + ((long long)row - rows) * 5;
+        const int lc = (int)l[0];
+        cl = multi ? (int)(slot - row * (unsigned)nc) : lc;
+        const float hw = l[3] / 2.0f, hh = l[4] / 2.0f;
+        x1 = l[1] - hw; y1 = l[2] - hh; x2 = l[1] + hw; y2 = l[2] + hh;
+        sc = (cl == lc ? 1.0f : 0.0f) * 1.0f;
+        return;
+    }
     cl = multi ? (int)(slot - row * (unsigned)nc) : (int)cb[row];
     const float* p = pb + (long long)row * (5 + nc);
     const float hw = p[2] / 2.0f, hh = p[3] / 2.0f;
@@ -218,7 +235,9 @@ __device__ __forceinline__ void decode_slot(const float* __restrict__ pb, const 
 #else
 #define NMS_STAMP(i) do { } while (0)
 #endif
+template <bool LAB>
 __global__ __launch_bounds__(WALK_THREADS) void nms_walk_kernel(const float* __restrict__ pred, long long rows, int nc, int multi,
+                                                                const float* __restrict__ labels, const int* __restrict__ label_off,
                                                                 long long cap, const unsigned int* __restrict__ key32,
                                                                 const unsigned short* __restrict__ cls16,
                                                                 const unsigned int* __restrict__ ghist,
@@ -231,6 +250,7 @@ __global__ __launch_bounds__(WALK_THREADS) void nms_walk_kernel(const float* __r
     const float* pb = pred + (long long)b * rows * (5 + nc);
     const unsigned int* kb = key32 + (long long)b * cap;
     const unsigned short* cb = cls16 + (long long)b * rows;
+    const float* lb = LAB ? labels + (long long)label_off[b] * 5 : nullptr;
 #ifdef ICAF_NMS_DEBUG
     __shared__ long long stamps[16];
     for (int i = tid; i < 16; i += WALK_THREADS) stamps[i] = 0;
@@ -394,7 +414,7 @@ __global__ __launch_bounds__(WALK_THREADS) void nms_walk_kernel(const float* __r
                     const unsigned int slot = 0xffffffffu - (unsigned)(sm.keys[pos] & 0xffffffffull);
                     float x1, y1, x2, y2, sc;
                     int cl;
-                    decode_slot(pb, cb, nc, multi, slot, x1, y1, x2, y2, sc, cl);
+                    decode_slot<LAB>(pb, cb, nc, multi, slot, lb, rows, x1, y1, x2, y2, sc, cl);
                     const float off = (float)cl * cls_off;                 // boxes + cls * max_wh (reference :589-590)
                     x1 = x1 + off; y1 = y1 + off; x2 = x2 + off; y2 = y2 + off;
                     sm.cx1[tid] = x1; sm.cy1[tid] = y1; sm.cx2[tid] = x2; sm.cy2[tid] = y2;
@@ -479,7 +499,7 @@ __global__ __launch_bounds__(WALK_THREADS) void nms_walk_kernel(const float* __r
     for (unsigned int k = tid; k < nkept; k += WALK_THREADS) {
         float x1, y1, x2, y2, sc;
         int cl;
-        decode_slot(pb, cb, nc, multi, sm.kslot[k], x1, y1, x2, y2, sc, cl);
+        decode_slot<LAB>(pb, cb, nc, multi, sm.kslot[k], lb, rows, x1, y1, x2, y2, sc, cl);
         float* o = det + ((long long)b * max_det + k) * 6;
         o[0] = x1; o[1] = y1; o[2] = x2; o[3] = y2; o[4] = sc; o[5] = (float)cl;
         if (keep_idx) keep_idx[(long long)b * max_det + k] = (int)(reordered ? sm.kpos[k] : sm.kslot[k]);
@@ -507,6 +527,179 @@ __global__ __launch_bounds__(256) void nms_rank_kernel(const unsigned int* __res
     if (lane == 0) keep_idx[(long long)b * max_det + k] = (int)r;
 }
 
+// Apriori labels (utils/general.py:545-552) as a second candidate source: label row r of image b is candidate row rows + r, behind the
+// prediction rows, with obj = 1 and a one-hot class confidence, so conf = 1 for its class and 0 for the others.  Runs after nms_keys_kernel
+// on the same stream and fills the key words of ALL max_labels label rows (0 behind the image's labels), adding its candidates to the
+// histogram, the candidate counter and the chunk counts that kernel wrote.  Integer atomics only: the sums do not depend on their order.
+__global__ __launch_bounds__(256) void nms_label_keys_kernel(const float* __restrict__ labels, const int* __restrict__ label_off,
+                                                             int max_labels, long long rows, int nc, float conf, int multi, ClassMask cm,
+                                                             int use_cm, long long cap, int nchunks, unsigned int* __restrict__ key32,
+                                                             unsigned int* __restrict__ ghist, unsigned int* __restrict__ ncand,
+                                                             unsigned int* __restrict__ chunk_cnt) {
+    const int b = blockIdx.x;
+    const int l0 = label_off[b];
+    int nl = label_off[b + 1] - l0;
+    nl = nl < 0 ? 0 : (nl > max_labels ? max_labels : nl);
+    unsigned int* kb = key32 + (long long)b * cap;
+    for (int r = threadIdx.x; r < max_labels; r += 256) {
+        const long long row = rows + r;
+        int lc = -1;
+        if (r < nl) {
+            const float c = labels[(long long)(l0 + r) * 5];
+            if (c >= 0.0f && c < (float)nc) lc = (int)c;                 // (the host wrapper refuses other classes; never index with one)
+        }
+        const unsigned int chunk = (unsigned)(row / NMS_CHUNK_ROWS);
+        for (int j = 0; j < (multi ? nc : 1); ++j) {
+            unsigned int k = 0;
+            if (lc >= 0) {
+                const int cj = multi ? j : lc;                           // best class of a one-hot row: the label's
+                const float c = (cj == lc ? 1.0f : 0.0f) * 1.0f;
+                if (c > conf && class_ok(cm, use_cm, cj)) k = ordered_bits(c);
+            }
+            kb[multi ? row * nc + j : row] = k;
+            if (k) {
+                atomicAdd(&ghist[(long long)b * NMS_NB + bin_of(k)], 1u);
+                atomicAdd(&ncand[b], 1u);
+                atomicAdd(&chunk_cnt[(long long)b * nchunks + chunk], 1u);
+            }
+        }
+    }
+}
+
+// Merge-NMS (utils/general.py:594-600), one workgroup per image, after the walk (and the rank kernel).  An image whose candidate count n
+// (after the class filter, before max_nms) is not inside 1 < n < 3000 returns at once: its plain result stands.  Otherwise
+//   1. the image's candidates are compacted into LDS in slot (= candidate) order: un-offset xyxy, score, class offset;
+//   2. one wavefront per kept box i: hit(i, j) = box_iou(boxes[i], boxes[j]) > iou_thres on the class-offset boxes, fp32, contraction off,
+//      the operation order of :455-477 (areas, clamp(0), inter / (a1 + a2 - inter), an IEEE division).  THE SUMMATION ORDER: lane l adds
+//      the products score_j * xyxy_j (exact in fp64) and the scores of its hits j = l, l + 64, l + 128, ... in ascending j into fp64
+//      accumulators that start at 0; the 64 lanes are then combined by the butterfly v += shfl_xor(v, o), o = 32, 16, 8, 4, 2, 1 (fp64 adds
+//      commute, so every lane holds the same bits).  Each of the five sums is rounded to fp32 once, the quotient is an fp32 division;
+//   3. with `redundant` the kept boxes with fewer than two hits are dropped: one prefix scan, det / keep_idx / count compacted in order.
+//      Only rows below the new count are written; the rows at or behind it keep what the walk left there.
+// A zero-area box has IoU NaN with everything, itself included: no hit, 0 / 0 coordinates — as the reference.
+constexpr int MERGE_N = ICAF_NMS_MERGE_LIMIT;
+struct MergeSmem {
+    float x1[MERGE_N], y1[MERGE_N], x2[MERGE_N], y2[MERGE_N], sc[MERGE_N], off[MERGE_N];
+    float res[MAX_KEEP][4];
+    unsigned int hits[MAX_KEEP];
+    unsigned int cnt[4][16];
+    unsigned int wsum[16];
+};
+
+template <bool LAB>
+__global__ __launch_bounds__(WALK_THREADS) void nms_merge_kernel(const float* __restrict__ pred, long long rows, int nc, int multi,
+                                                                 const float* __restrict__ labels, const int* __restrict__ label_off,
+                                                                 long long cap, const unsigned int* __restrict__ key32,
+                                                                 const unsigned short* __restrict__ cls16,
+                                                                 const unsigned int* __restrict__ ncand, float iou_thr, float cls_off,
+                                                                 int max_det, int redundant, float* __restrict__ det, int* __restrict__ count,
+                                                                 int* __restrict__ keep_idx) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char merge_smem_raw[];
+    MergeSmem& sm = *reinterpret_cast<MergeSmem*>(merge_smem_raw);
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const unsigned int n = ncand[b];
+    if (!(n > 1u && n < (unsigned)MERGE_N)) return;                       // workgroup-uniform
+    const int nk = min(count[b], max_det);
+    const float* pb = pred + (long long)b * rows * (5 + nc);
+    const unsigned int* kb = key32 + (long long)b * cap;
+    const unsigned short* cb = cls16 + (long long)b * rows;
+    const float* lb = LAB ? labels + (long long)label_off[b] * 5 : nullptr;
+    // ------------------------------------------------------------------ 1. candidates into LDS, slot order
+    unsigned int base = 0;
+    for (long long i0 = 0; i0 < cap; i0 += 4 * WALK_THREADS) {
+        unsigned int k32[4];
+        unsigned long long m[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const long long i = i0 + u * WALK_THREADS + tid;
+            k32[u] = i < cap ? kb[i] : 0u;
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            m[u] = __ballot(k32[u] != 0u);
+            if (lane == 0) sm.cnt[u][wave] = (unsigned)__popcll(m[u]);
+        }
+        __syncthreads();
+        unsigned int before[4] = {0, 0, 0, 0}, total = 0;
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+#pragma unroll
+            for (int w = 0; w < 16; ++w) {
+                const unsigned int c = sm.cnt[u][w];
+#pragma unroll
+                for (int v = 0; v < 4; ++v)
+                    if (u < v || (u == v && w < wave)) before[v] += c;
+                total += c;
+            }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            if (k32[u] == 0u) continue;
+            const unsigned int pos = base + before[u] + (unsigned)__popcll(m[u] & ((1ull << lane) - 1ull));
+            if (pos >= (unsigned)MERGE_N) continue;                        // (cannot happen: n < MERGE_N keys exist)
+            float x1, y1, x2, y2, sc;
+            int cl;
+            decode_slot<LAB>(pb, cb, nc, multi, (unsigned)(i0 + u * WALK_THREADS + tid), lb, rows, x1, y1, x2, y2, sc, cl);
+            sm.x1[pos] = x1; sm.y1[pos] = y1; sm.x2[pos] = x2; sm.y2[pos] = y2; sm.sc[pos] = sc; sm.off[pos] = (float)cl * cls_off;
+        }
+        __syncthreads();
+        base += total;
+    }
+    const unsigned int nc_lds = base < (unsigned)MERGE_N ? base : (unsigned)MERGE_N;       // == n
+    // ------------------------------------------------------------------ 2. one wavefront per kept box
+    for (int k = wave; k < nk; k += 16) {
+        const float* d = det + ((long long)b * max_det + k) * 6;
+        const float ko = d[5] * cls_off;                                   // boxes + cls * max_wh (:589-590), as the walk offset them
+        const float kx1 = d[0] + ko, ky1 = d[1] + ko, kx2 = d[2] + ko, ky2 = d[3] + ko;
+        const float karea = (kx2 - kx1) * (ky2 - ky1);
+        double sw = 0.0, a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
+        unsigned int hits = 0;
+        for (unsigned int j = lane; j < nc_lds; j += 64) {
+            const float ux1 = sm.x1[j], uy1 = sm.y1[j], ux2 = sm.x2[j], uy2 = sm.y2[j], o = sm.off[j];
+            const float cx1 = ux1 + o, cy1 = uy1 + o, cx2 = ux2 + o, cy2 = uy2 + o;
+            const float carea = (cx2 - cx1) * (cy2 - cy1);
+            const float w = fmaxf(fminf(kx2, cx2) - fmaxf(kx1, cx1), 0.0f), h = fmaxf(fminf(ky2, cy2) - fmaxf(ky1, cy1), 0.0f);
+            const float inter = w * h;
+            const float iou = inter / (karea + carea - inter);
+            if (iou > iou_thr) {
+                const double s = (double)sm.sc[j];
+                sw += s;
+                a0 += s * (double)ux1; a1 += s * (double)uy1; a2 += s * (double)ux2; a3 += s * (double)uy2;
+                ++hits;
+            }
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            sw += __shfl_xor(sw, o); a0 += __shfl_xor(a0, o); a1 += __shfl_xor(a1, o); a2 += __shfl_xor(a2, o); a3 += __shfl_xor(a3, o);
+            hits += __shfl_xor(hits, o);
+        }
+        if (lane == 0) {
+            const float fw = (float)sw;
+            sm.res[k][0] = (float)a0 / fw; sm.res[k][1] = (float)a1 / fw; sm.res[k][2] = (float)a2 / fw; sm.res[k][3] = (float)a3 / fw;
+            sm.hits[k] = hits;
+        }
+    }
+    __syncthreads();
+    // ------------------------------------------------------------------ 3. write back, compacted when `redundant`
+    float sc = 0.0f, cl = 0.0f;
+    int ki = 0;
+    unsigned int flag = 0;
+    if (tid < nk) {
+        const float* d = det + ((long long)b * max_det + tid) * 6;
+        sc = d[4]; cl = d[5];
+        if (keep_idx) ki = keep_idx[(long long)b * max_det + tid];
+        flag = (!redundant || sm.hits[tid] > 1u) ? 1u : 0u;
+    }
+    unsigned int total;
+    const unsigned int incl = block_incl_scan_1024(flag, sm.wsum, total);      // (its barriers order the reads above before the writes below)
+    if (flag) {
+        const unsigned int pos = incl - 1u;
+        float* o = det + ((long long)b * max_det + pos) * 6;
+        o[0] = sm.res[tid][0]; o[1] = sm.res[tid][1]; o[2] = sm.res[tid][2]; o[3] = sm.res[tid][3]; o[4] = sc; o[5] = cl;
+        if (keep_idx) keep_idx[(long long)b * max_det + pos] = ki;
+    }
+    if (tid == 0) count[b] = (int)total;
+}
+
 struct NmsWs {
     unsigned int* key32; unsigned short* cls16; unsigned int* ghist; unsigned int* ncand; unsigned int* chunk_cnt;
     size_t zero_bytes; int nchunks; size_t total;
@@ -514,15 +707,17 @@ struct NmsWs {
 
 static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
-static int nms_layout(int B, long long rows, int nc, int multi, void* base, NmsWs& ws) {
+// max_labels: label rows per image behind the prediction rows (0: the layout of icaf_nms)
+static int nms_layout(int B, long long rows, int nc, int multi, int max_labels, void* base, NmsWs& ws) {
     if (B < 1 || rows < 1 || nc < 1) return fail(ICAF_ERR_ARG, "icaf_nms: bad B/rows/nc");
     if (nc > 65535) return fail(ICAF_ERR_UNSUPPORTED, "icaf_nms: at most 65535 classes");
-    const long long cap = rows * ((multi && nc > 1) ? nc : 1);
+    if (max_labels < 0 || max_labels > ICAF_NMS_MAX_LABELS) return fail(ICAF_ERR_ARG, "icaf_nms: max_labels must be in [0, %d]", (int)ICAF_NMS_MAX_LABELS);
+    const long long cap = (rows + max_labels) * ((multi && nc > 1) ? nc : 1);
     if (cap > 0xfffffff0LL || (long long)B > 65535) return fail(ICAF_ERR_UNSUPPORTED, "icaf_nms: rows*nc exceeds 2^32 candidate slots per image");
     size_t off = 0;
     unsigned char* p = (unsigned char*)base;
     auto take = [&](size_t bytes) { unsigned char* r = p ? p + off : nullptr; off = align_up(off + bytes, 256); return r; };
-    ws.nchunks = (int)((rows + NMS_CHUNK_ROWS - 1) / NMS_CHUNK_ROWS);
+    ws.nchunks = (int)((rows + max_labels + NMS_CHUNK_ROWS - 1) / NMS_CHUNK_ROWS);
     ws.ghist = (unsigned int*)take((size_t)B * NMS_NB * 4 + (size_t)B * 4);       // histograms + candidate counters: cleared per call
     ws.ncand = ws.ghist ? ws.ghist + (size_t)B * NMS_NB : nullptr;
     ws.zero_bytes = (size_t)B * NMS_NB * 4 + (size_t)B * 4;
@@ -622,61 +817,106 @@ __global__ __launch_bounds__(256) void match_predictions_kernel(const float* __r
 
 using namespace icaf;
 
-extern "C" int icaf_nms_workspace_bytes(int B, long long rows, int nc, int multi_label, size_t* bytes) {
-    if (!bytes) return fail(ICAF_ERR_ARG, "icaf_nms_workspace_bytes: null pointer");
+// labels without a table or without room count as none: the layout, the launches and the results are icaf_nms'
+static inline int nms_label_rows(const icaf_nms_args* a) { return (a->labels && a->max_labels > 0) ? a->max_labels : 0; }
+
+extern "C" int icaf_nms_ex_workspace_bytes(const icaf_nms_args* a, size_t* bytes) {
+    if (!a || !bytes) return fail(ICAF_ERR_ARG, "icaf_nms_workspace_bytes: null pointer");
     NmsWs ws;
-    int st = nms_layout(B, rows, nc, multi_label, nullptr, ws);
+    int st = nms_layout(a->B, a->rows, a->nc, a->multi_label, a->max_labels, nullptr, ws);      // (sized for max_labels whether or not a table is set yet)
     if (st) return st;
     *bytes = ws.total;
     return ICAF_OK;
 }
 
-extern "C" int icaf_nms(const float* pred, int B, long long rows, int nc, float conf_thres, float iou_thres, int multi_label, int agnostic,
-                        const int* classes_host, int n_classes, int max_det, int max_nms, float max_wh, float* det, int* count,
-                        int* keep_idx, void* workspace, size_t workspace_bytes, icaf_stream_t s) {
-    if (!pred || !det || !count || !workspace) return fail(ICAF_ERR_ARG, "icaf_nms: null pointer");
-    if (max_det < 1 || max_det > MAX_KEEP) return fail(ICAF_ERR_ARG, "icaf_nms: max_det must be in [1, %d]", MAX_KEEP);
-    if (max_nms < 1) return fail(ICAF_ERR_ARG, "icaf_nms: max_nms must be positive");
-    if (n_classes < 0 || (n_classes > 0 && !classes_host)) return fail(ICAF_ERR_ARG, "icaf_nms: class filter of %d ids without a list", n_classes);
-    if (((uintptr_t)workspace & 255) != 0) return fail(ICAF_ERR_ARG, "icaf_nms: workspace must be 256-byte aligned");
-    const int multi = multi_label && nc > 1;
-    NmsWs ws;
-    int st = nms_layout(B, rows, nc, multi, workspace, ws);
-    if (st) return st;
-    if (ws.total > workspace_bytes) return fail(ICAF_ERR_ARG, "icaf_nms: workspace too small (%zu < %zu)", workspace_bytes, ws.total);
-    ClassMask cm;
-    memset(&cm, 0, sizeof(cm));
-    for (int i = 0; i < n_classes; ++i) {
-        const int c = classes_host[i];
-        if (c < 0 || c > 255) return fail(ICAF_ERR_UNSUPPORTED, "icaf_nms: class filter supports ids 0..255");
-        cm.w[c >> 5] |= 1u << (c & 31);
-    }
-    const long long cap = rows * (multi ? nc : 1);
-    hipStream_t hs = S(s);
-    static std::atomic<bool> attr_set[ICAF_MAX_DEVICES];      // hipFuncSetAttribute is per device
+extern "C" int icaf_nms_workspace_bytes(int B, long long rows, int nc, int multi_label, size_t* bytes) {
+    icaf_nms_args a;
+    memset(&a, 0, sizeof(a));
+    a.B = B; a.rows = rows; a.nc = nc; a.multi_label = multi_label;
+    return icaf_nms_ex_workspace_bytes(&a, bytes);
+}
+
+template <bool LAB>
+static int nms_launch(const icaf_nms_args* a, const NmsWs& ws, const ClassMask& cm, int multi, int ml, hipStream_t hs) {
+    const long long rows = a->rows, cap = (rows + ml) * (multi ? a->nc : 1);
+    const int B = a->B, nc = a->nc, use_cm = a->n_classes > 0 ? 1 : 0;
+    const float cls_off = a->agnostic ? 0.0f : a->max_wh;
+    static std::atomic<bool> attr_set[ICAF_MAX_DEVICES];      // hipFuncSetAttribute is per device (and per instantiation)
     int dev = 0;
     ICAF_HIP(hipGetDevice(&dev));
     if (dev < 0 || dev >= ICAF_MAX_DEVICES) return fail(ICAF_ERR_UNSUPPORTED, "icaf_nms: device ordinal %d", dev);
     if (!attr_set[dev]) {
-        ICAF_HIP(hipFuncSetAttribute((const void*)nms_walk_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(WalkSmem)));
+        ICAF_HIP(hipFuncSetAttribute((const void*)nms_walk_kernel<LAB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(WalkSmem)));
+        ICAF_HIP(hipFuncSetAttribute((const void*)nms_merge_kernel<LAB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(MergeSmem)));
         attr_set[dev] = true;
     }
     ICAF_HIP(hipMemsetAsync(ws.ghist, 0, ws.zero_bytes, hs));
-    nms_keys_kernel<<<dim3((unsigned)ws.nchunks, (unsigned)B), dim3(256), 0, hs>>>(pred, rows, nc, conf_thres, multi, cm, n_classes > 0 ? 1 : 0,
-                                                                                   cap, ws.nchunks, ws.key32, ws.cls16, ws.ghist, ws.ncand,
+    nms_keys_kernel<<<dim3((unsigned)ws.nchunks, (unsigned)B), dim3(256), 0, hs>>>(a->pred, rows, nc, a->conf_thres, multi, cm, use_cm, cap,
+                                                                                   ws.nchunks, ws.key32, ws.cls16, ws.ghist, ws.ncand,
                                                                                    ws.chunk_cnt);
     ICAF_LAUNCH_CHECK();
-    nms_walk_kernel<<<dim3((unsigned)B), dim3(WALK_THREADS), sizeof(WalkSmem), hs>>>(pred, rows, nc, multi, cap, ws.key32, ws.cls16, ws.ghist,
-                                                                                     ws.ncand, iou_thres, agnostic ? 0.0f : max_wh, max_det,
-                                                                                     max_nms, det, count, keep_idx);
+    if (LAB) {
+        nms_label_keys_kernel<<<dim3((unsigned)B), dim3(256), 0, hs>>>(a->labels, a->label_off, ml, rows, nc, a->conf_thres, multi, cm, use_cm, cap,
+                                                                       ws.nchunks, ws.key32, ws.ghist, ws.ncand, ws.chunk_cnt);
+        ICAF_LAUNCH_CHECK();
+    }
+    nms_walk_kernel<LAB><<<dim3((unsigned)B), dim3(WALK_THREADS), sizeof(WalkSmem), hs>>>(a->pred, rows, nc, multi, a->labels, a->label_off, cap,
+                                                                                          ws.key32, ws.cls16, ws.ghist, ws.ncand, a->iou_thres,
+                                                                                          cls_off, a->max_det, a->max_nms, a->det, a->count,
+                                                                                          a->keep_idx);
     ICAF_LAUNCH_CHECK();
-    if (keep_idx) {
-        nms_rank_kernel<<<dim3((unsigned)((max_det + 3) / 4), (unsigned)B), dim3(256), 0, hs>>>(ws.key32, cap, multi ? nc : 1, ws.nchunks,
-                                                                                              ws.chunk_cnt, ws.ncand, count, max_det, max_nms,
-                                                                                              keep_idx);
+    if (a->keep_idx) {
+        nms_rank_kernel<<<dim3((unsigned)((a->max_det + 3) / 4), (unsigned)B), dim3(256), 0, hs>>>(ws.key32, cap, multi ? nc : 1, ws.nchunks,
+                                                                                                 ws.chunk_cnt, ws.ncand, a->count, a->max_det,
+                                                                                                 a->max_nms, a->keep_idx);
+        ICAF_LAUNCH_CHECK();
+    }
+    if (a->merge) {
+        nms_merge_kernel<LAB><<<dim3((unsigned)B), dim3(WALK_THREADS), sizeof(MergeSmem), hs>>>(a->pred, rows, nc, multi, a->labels, a->label_off,
+                                                                                                cap, ws.key32, ws.cls16, ws.ncand, a->iou_thres,
+                                                                                                cls_off, a->max_det, a->redundant ? 1 : 0, a->det,
+                                                                                                a->count, a->keep_idx);
         ICAF_LAUNCH_CHECK();
     }
     return ICAF_OK;
+}
+
+extern "C" int icaf_nms_ex(const icaf_nms_args* a, icaf_stream_t s) {
+    if (!a) return fail(ICAF_ERR_ARG, "icaf_nms: null pointer");
+    if (!a->pred || !a->det || !a->count || !a->workspace) return fail(ICAF_ERR_ARG, "icaf_nms: null pointer");
+    if (a->max_det < 1 || a->max_det > MAX_KEEP) return fail(ICAF_ERR_ARG, "icaf_nms: max_det must be in [1, %d]", MAX_KEEP);
+    if (a->max_nms < 1) return fail(ICAF_ERR_ARG, "icaf_nms: max_nms must be positive");
+    if (a->n_classes < 0 || (a->n_classes > 0 && !a->classes)) return fail(ICAF_ERR_ARG, "icaf_nms: class filter of %d ids without a list", a->n_classes);
+    if (((uintptr_t)a->workspace & 255) != 0) return fail(ICAF_ERR_ARG, "icaf_nms: workspace must be 256-byte aligned");
+    if (a->merge && a->max_nms < MERGE_N)
+        return fail(ICAF_ERR_ARG, "icaf_nms: merge needs max_nms >= %d (the reference would merge over a truncated candidate list)", MERGE_N);
+    if (a->labels && a->max_labels > 0 && !a->label_off) return fail(ICAF_ERR_ARG, "icaf_nms: labels without label_off");
+    const int multi = a->multi_label && a->nc > 1;
+    const int ml = nms_label_rows(a);
+    NmsWs ws;
+    int st = nms_layout(a->B, a->rows, a->nc, multi, ml, a->workspace, ws);
+    if (st) return st;
+    if (ws.total > a->workspace_bytes) return fail(ICAF_ERR_ARG, "icaf_nms: workspace too small (%zu < %zu)", a->workspace_bytes, ws.total);
+    ClassMask cm;
+    memset(&cm, 0, sizeof(cm));
+    for (int i = 0; i < a->n_classes; ++i) {
+        const int c = a->classes[i];
+        if (c < 0 || c > 255) return fail(ICAF_ERR_UNSUPPORTED, "icaf_nms: class filter supports ids 0..255");
+        cm.w[c >> 5] |= 1u << (c & 31);
+    }
+    return ml ? nms_launch<true>(a, ws, cm, multi, ml, S(s)) : nms_launch<false>(a, ws, cm, multi, 0, S(s));
+}
+
+extern "C" int icaf_nms(const float* pred, int B, long long rows, int nc, float conf_thres, float iou_thres, int multi_label, int agnostic,
+                        const int* classes_host, int n_classes, int max_det, int max_nms, float max_wh, float* det, int* count,
+                        int* keep_idx, void* workspace, size_t workspace_bytes, icaf_stream_t s) {
+    icaf_nms_args a;
+    memset(&a, 0, sizeof(a));
+    a.pred = pred; a.B = B; a.rows = rows; a.nc = nc; a.conf_thres = conf_thres; a.iou_thres = iou_thres;
+    a.multi_label = multi_label; a.agnostic = agnostic; a.classes = classes_host; a.n_classes = n_classes;
+    a.max_det = max_det; a.max_nms = max_nms; a.max_wh = max_wh; a.det = det; a.count = count; a.keep_idx = keep_idx;
+    a.workspace = workspace; a.workspace_bytes = workspace_bytes;
+    return icaf_nms_ex(&a, s);
 }
 
 extern "C" int icaf_match_predictions(const float* det, const int* count, int B, int max_det, const float* labels, const int* label_off,

@@ -943,14 +943,24 @@ def tta_merge(zs, scales, flips, out, width, name="tta_merge"):
 class NmsRunner:
     """Pre-allocated NMS launch for a fixed (B, rows, nc) — graph-capturable; results stay on the device."""
 
-    def __init__(self, B, rows, nc, device, multi_label=False, max_det=300, want_keep=True, block=None):
+    def __init__(self, B, rows, nc, device, multi_label=False, max_det=300, want_keep=True, block=None, max_labels=0, merge=False):
         """want_keep=False skips the kept-index output (torchvision's return value; one more small launch) — the serving
         pipeline only needs the detection rows.  `block`: a flat fp32 tensor of B * max_det * 6 + B elements to use as the detection block
-        (the pipeline lays the blocks of consecutive steps side by side so that ONE collective moves all of them)."""
+        (the pipeline lays the blocks of consecutive steps side by side so that ONE collective moves all of them).
+        max_labels: room for that many apriori label rows per image behind the prediction rows (launch(labels=...), icaf_nms_ex); merge: the
+        reference's merge-NMS (utils/general.py:594-600) follows the walk.  With both at their defaults the runner calls icaf_nms as ever."""
         self.B, self.rows, self.nc, self.max_det = B, rows, nc, max_det
         self.multi_label = bool(multi_label) and nc > 1
+        self.max_labels, self.merge = int(max_labels), bool(merge)
+        if self.max_labels < 0:
+            raise ValueError("NmsRunner: max_labels must not be negative")
         sz = C.c_size_t(0)
-        check(lib().icaf_nms_workspace_bytes(B, rows, nc, int(self.multi_label), C.byref(sz)), "nms_workspace")
+        if self.max_labels:
+            a = _lib.NmsArgs()
+            a.B, a.rows, a.nc, a.multi_label, a.max_labels = B, rows, nc, int(self.multi_label), self.max_labels
+            check(lib().icaf_nms_ex_workspace_bytes(C.byref(a), C.byref(sz)), "nms_workspace")
+        else:
+            check(lib().icaf_nms_workspace_bytes(B, rows, nc, int(self.multi_label), C.byref(sz)), "nms_workspace")
         self.ws = torch.empty((max(sz.value, 16),), dtype=torch.uint8, device=device)
         from .dist import detection_block            # det + count in ONE allocation: the block the all-gather sends as it is
         if block is None:
@@ -962,19 +972,67 @@ class NmsRunner:
         self.keep = torch.zeros((B, max_det), dtype=torch.int32, device=device) if want_keep else None
 
     def launch(self, pred, conf_thres, iou_thres, agnostic=False, classes=None, max_nms=30000, max_wh=4096.0,
-               stream_ptr=None):
+               stream_ptr=None, labels=None, label_off=None, redundant=True):
+        """labels (L, 5) fp32 [cls, cx, cy, w, h] in pixels and label_off (B + 1,) int32 on the device (nms_label_table builds and checks them):
+        image b's apriori labels are rows label_off[b] .. label_off[b + 1], at most the runner's max_labels."""
         assert pred.dtype == torch.float32 and pred.is_contiguous() and pred.shape == (self.B, self.rows, 5 + self.nc)
         cls_arr, ncls = None, 0
         if classes is not None:
             ncls = len(classes)
             cls_arr = (C.c_int * max(ncls, 1))(*[int(c) for c in classes])
-        st = lib().icaf_nms(pred.data_ptr(), self.B, self.rows, self.nc, float(conf_thres), float(iou_thres),
-                            int(self.multi_label), int(bool(agnostic)), cls_arr, ncls, self.max_det, int(max_nms),
-                            float(max_wh), self.det.data_ptr(), self.count.data_ptr(), self.keep.data_ptr() if self.keep is not None else None,
-                            self.ws.data_ptr(), self.ws.numel(),
-                            stream_ptr if stream_ptr is not None else current_stream_ptr())
-        check(st, "icaf_nms")
+        stream = stream_ptr if stream_ptr is not None else current_stream_ptr()
+        keep_ptr = self.keep.data_ptr() if self.keep is not None else None
+        if labels is None and not self.merge:
+            st = lib().icaf_nms(pred.data_ptr(), self.B, self.rows, self.nc, float(conf_thres), float(iou_thres),
+                                int(self.multi_label), int(bool(agnostic)), cls_arr, ncls, self.max_det, int(max_nms),
+                                float(max_wh), self.det.data_ptr(), self.count.data_ptr(), keep_ptr,
+                                self.ws.data_ptr(), self.ws.numel(), stream)
+            check(st, "icaf_nms")
+            return self.det, self.count, self.keep
+        if self.merge and int(max_nms) < _lib.NMS_MERGE_LIMIT:
+            raise ValueError(f"merge-NMS needs max_nms >= {_lib.NMS_MERGE_LIMIT}: the reference would merge over a truncated candidate list")
+        a = _lib.NmsArgs()
+        a.pred, a.B, a.rows, a.nc = pred.data_ptr(), self.B, self.rows, self.nc
+        a.conf_thres, a.iou_thres, a.multi_label, a.agnostic = float(conf_thres), float(iou_thres), int(self.multi_label), int(bool(agnostic))
+        a.classes, a.n_classes = (C.addressof(cls_arr) if cls_arr is not None else None), ncls
+        a.max_det, a.max_nms, a.max_wh = self.max_det, int(max_nms), float(max_wh)
+        a.det, a.count, a.keep_idx = self.det.data_ptr(), self.count.data_ptr(), keep_ptr
+        a.workspace, a.workspace_bytes = self.ws.data_ptr(), self.ws.numel()
+        a.merge, a.redundant = int(self.merge), int(bool(redundant))
+        if labels is not None:
+            if label_off is None:
+                raise ValueError("NmsRunner.launch: labels need label_off")
+            if not self.max_labels:
+                raise ValueError("NmsRunner.launch: the runner was built with max_labels=0")
+            assert labels.dtype == torch.float32 and labels.is_contiguous() and labels.dim() == 2 and labels.shape[1] == 5 and labels.device == pred.device
+            assert label_off.dtype == torch.int32 and label_off.is_contiguous() and label_off.shape == (self.B + 1,) and label_off.device == pred.device
+            if labels.shape[0]:                                     # an empty table: no label anywhere, the plain candidate stage
+                a.labels, a.label_off, a.max_labels = labels.data_ptr(), label_off.data_ptr(), self.max_labels
+        check(lib().icaf_nms_ex(C.byref(a), stream), "icaf_nms_ex")
         return self.det, self.count, self.keep
+
+
+def nms_label_table(labels, B, nc, max_labels=None, device=None):
+    """The per-image apriori label lists of non_max_suppression(labels=...) -> (table (L, 5) fp32, label_off (B + 1,) int32, longest list), built
+    and CHECKED on the host from the small tensors: every class an id in [0, nc), at most max_labels rows per image (when given).  `labels`: a
+    sequence of B (n_i, 5) tensors / arrays [cls, cx, cy, w, h] in pixels, empty entries allowed.  The tensors go to `device` when it is given."""
+    if len(labels) != B:
+        raise ValueError(f"apriori labels for {len(labels)} images, the batch holds {B}")
+    rows, off = [], [0]
+    for i, l in enumerate(labels):
+        l = torch.as_tensor(l, dtype=torch.float32).detach().cpu().reshape(-1, 5) if len(l) else torch.zeros((0, 5))
+        if len(l):
+            c = l[:, 0]
+            if not bool(((c >= 0) & (c < nc)).all()):
+                raise ValueError(f"apriori labels of image {i}: class ids must be in [0, {nc})")
+        if max_labels is not None and len(l) > max_labels:
+            raise ValueError(f"apriori labels of image {i}: {len(l)} rows, max_labels is {max_labels}")
+        rows.append(l)
+        off.append(off[-1] + len(l))
+    table, off_t = torch.cat(rows).contiguous(), torch.tensor(off, dtype=torch.int32)
+    if device is not None:
+        table, off_t = table.to(device), off_t.to(device)
+    return table, off_t, max(b - a for a, b in zip(off, off[1:]))
 
 
 def confluence_select(cand, n, nc, p_thres, det=None, count=None, keep_idx=None, want_keep=True, stream_ptr=None):

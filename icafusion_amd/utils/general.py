@@ -102,38 +102,59 @@ def box_iou(box1, box2):
 
 
 def nms_device(prediction, conf_thres=0.25, iou_thres=0.45, classes=None, agnostic=False, multi_label=False,
-               max_det=300, max_nms=30000, max_wh=4096.0, stream_ptr=None, runner=None):
+               max_det=300, max_nms=30000, max_wh=4096.0, stream_ptr=None, runner=None, labels=None, merge=False, redundant=True):
     """Device-resident NMS: returns (det (B,max_det,6), count (B,), keep_idx (B,max_det)) without any host sync.
     The three tensors are the runner's STATIC output buffers: with the default (shared, per-shape) runner they are
     overwritten by the next call of the same shape — consume or clone them first, or pass an own `runner`
-    (ops.NmsRunner) as DetectionPipeline does for each of its two in-flight slots."""
+    (ops.NmsRunner) as DetectionPipeline does for each of its two in-flight slots.
+    labels: the reference's apriori labels (utils/general.py:545-552) — a sequence of B per-image (n_i, 5) tensors [cls, x, y, w, h] in pixels
+    (empty entries allowed), or the (table, label_off) pair of ops.nms_label_table already on the device; they join the image's candidates
+    behind its prediction rows, and keep_idx indexes that concatenated list.  merge: the reference's merge-NMS (:594-600) — every kept box
+    becomes the score-weighted mean of the candidates overlapping it, for images with 1 < n < 3000 candidates; `redundant` drops the kept
+    boxes that nothing else overlaps (icaf_nms_ex in include/icaf.h states the summation order)."""
+    B, rows, no = prediction.shape
+    nc = no - 5
+    if merge and int(max_nms) < ops._lib.NMS_MERGE_LIMIT:
+        raise ValueError(f"merge-NMS needs max_nms >= {ops._lib.NMS_MERGE_LIMIT}: the reference would merge over a truncated candidate list")
+    table = off = None
+    need = 0
+    if labels is not None and len(labels):
+        if isinstance(labels, tuple) and len(labels) == 2 and isinstance(labels[1], torch.Tensor) and labels[1].dtype == torch.int32:
+            table, off = labels
+            need = runner.max_labels if runner is not None else int((off[1:] - off[:-1]).max())
+        else:
+            table, off, need = ops.nms_label_table(labels, B, nc, runner.max_labels if runner is not None else None)
     if not prediction.is_cuda:
         raise RuntimeError("non_max_suppression runs on the MI355X only (no CPU fallback; see oracle/ for the "
                            "CPU reference used by the tests)")
     pred = prediction.float().contiguous()
-    B, rows, no = pred.shape
-    nc = no - 5
     ml = bool(multi_label) and nc > 1
+    cap = 0 if not need else max(16, 1 << (need - 1).bit_length())             # label room in powers of two: few runners for many batches
     if runner is None:
-        key = (B, rows, nc, ml, max_det, pred.device)
+        key = (B, rows, nc, ml, max_det, pred.device, cap, bool(merge))
         runner = _RUNNERS.pop(key, None)
         if runner is None:
             while len(_RUNNERS) >= _MAX_RUNNERS:          # rectangular validation batches meet many (B, rows): bound the workspaces
                 _RUNNERS.pop(next(iter(_RUNNERS)))
-            runner = ops.NmsRunner(B, rows, nc, pred.device, ml, max_det)
+            runner = ops.NmsRunner(B, rows, nc, pred.device, ml, max_det, max_labels=cap, merge=merge)
         _RUNNERS[key] = runner
     elif (runner.B, runner.rows, runner.nc, runner.multi_label, runner.max_det) != (B, rows, nc, ml, max_det):
         raise ValueError("nms_device: the runner was built for another (B, rows, nc, multi_label, max_det)")
-    return runner.launch(pred, conf_thres, iou_thres, agnostic, classes, max_nms, max_wh, stream_ptr)
+    elif runner.merge != bool(merge) or runner.max_labels < need:
+        raise ValueError("nms_device: the runner was built for another merge mode or fewer labels")
+    if table is None or not need:
+        return runner.launch(pred, conf_thres, iou_thres, agnostic, classes, max_nms, max_wh, stream_ptr, redundant=redundant)
+    return runner.launch(pred, conf_thres, iou_thres, agnostic, classes, max_nms, max_wh, stream_ptr,
+                         labels=table.to(pred.device), label_off=off.to(pred.device), redundant=redundant)
 
 
 def non_max_suppression(prediction, conf_thres=0.25, iou_thres=0.45, classes=None, agnostic=False, multi_label=False,
-                        labels=()):
+                        labels=(), merge=False):
     """Drop-in for the reference's non_max_suppression (utils/general.py:518-607): list of (n,6) tensors
     [x1, y1, x2, y2, conf, cls] per image.  The 10 s wall-clock bail-out of the reference (:603-605) does not exist
-    here; apriori `labels` (autolabelling) are outside the inference hot path."""
-    if labels:
-        raise NotImplementedError("apriori labels (autolabelling) are outside the inference hot path")
-    det, count, _ = nms_device(prediction, conf_thres, iou_thres, classes, agnostic, multi_label)
+    here.  `labels` are the reference's apriori labels (:545-552): one (n_i, 5) tensor [cls, x, y, w, h] in pixels per image;
+    `merge` is its `merge = True` (:594-600, with redundant = True as there) — nms_device says what each does."""
+    det, count, _ = nms_device(prediction, conf_thres, iou_thres, classes, agnostic, multi_label, labels=labels if len(labels) else None,
+                               merge=merge)
     counts = count.tolist()                           # the one device->host sync of post-processing
     return [det[i, :n].clone() for i, n in enumerate(counts)]

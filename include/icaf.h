@@ -500,6 +500,51 @@ int icaf_nms_workspace_bytes(int B, long long rows, int nc, int multi_label, ICA
 int icaf_nms(const float* pred, int B, long long rows, int nc, float conf_thres, float iou_thres, int multi_label,
              int agnostic, ICAF_HOST const int* classes_host, int n_classes, int max_det, int max_nms, float max_wh,
              float* det, int* count, int* keep_idx, void* workspace, size_t workspace_bytes, icaf_stream_t s);
+/* icaf_nms_ex: icaf_nms with the two modes of the reference that it cannot express; with labels = NULL (or max_labels = 0) and merge = 0 it
+ * enqueues exactly what icaf_nms enqueues (icaf_nms is this call with those values) and the workspace is icaf_nms_workspace_bytes'.
+ * APRIORI LABELS (utils/general.py:545-552; test.py --save-hybrid): labels [L][5] fp32 rows cls, cx, cy, w, h in the prediction's pixel space,
+ *   label_off [B+1] int32 (both device memory): image b owns rows [label_off[b], label_off[b+1]), the convention of icaf_match_predictions, at
+ *   most max_labels of them (the host-known capacity that sizes the workspace; rows beyond it are not read).  A label row is a candidate with
+ *   obj = 1 and class confidence 1 for (int)cls, 0 for the other classes: it passes the obj test by construction (:543 runs before :546), then
+ *   conf = obj * cls > conf_thres and the class filter like any row.  The label rows FOLLOW the image's prediction rows in candidate order —
+ *   candidate row rows + r, slot (rows + r) * ncm + class with ncm = nc under multi_label and 1 otherwise — so "descending score, ties by
+ *   ascending candidate index" holds unchanged and keep_idx indexes the concatenated candidate list.  The boxes are read where they lie; no
+ *   concatenated tensor is built.  cls must be in [0, nc) (the host wrapper checks; the kernels skip such a row rather than index with it).
+ * MERGE-NMS (:594-600, the reference's `merge = True`), after the walk, per image.  n = the image's candidates after the class filter and
+ *   before the max_nms cap.  Unless 1 < n < 3000 the image's plain result stands, silently, as in the reference; merge with max_nms < 3000 is
+ *   ICAF_ERR_ARG (the reference would merge over a truncated list).  For every kept box i and candidate j: hit = box_iou(boxes[i], boxes[j])
+ *   > iou_thres on the class-offset boxes, fp32 without contraction in the order of :455-477 (areas, clamp(0), inter / (a1 + a2 - inter)), so
+ *   every decision is bit-exact.  New box = sum_j hit * score_j * xyxy_j / sum_j hit * score_j over the un-offset xyxy.  THE SUMMATION RULE (the
+ *   reference leaves the order to its BLAS): products and sums in fp64 (fp32 x fp32 is exact there); partial sum l, l = 0..63, takes the hits
+ *   j = l, l + 64, l + 128, ... in ascending j from 0.0; the 64 partial sums are combined by v[l] += v[l ^ o] for o = 32, 16, 8, 4, 2, 1; each of
+ *   the five sums is rounded to fp32 once and the division is fp32.  Two calls give the same bits.  redundant != 0 (:599-600): a kept box with
+ *   fewer than two hits is removed; det, keep_idx and count are compacted in order, and the rows at or behind the new count hold what
+ *   icaf_nms leaves there (the walk's plain rows up to its count, untouched memory behind).  No special case for degenerate boxes: a
+ *   zero-area box has IoU NaN with every box, itself included, hence no hit and 0 / 0 = NaN coordinates, exactly as the reference.
+ * `classes` is HOST memory (n_classes ints); every other pointer is device memory.  One more small kernel per mode on `s`. */
+enum { ICAF_NMS_MERGE_LIMIT = 3000, ICAF_NMS_MAX_LABELS = 65536 };
+typedef struct icaf_nms_args {
+    const float* pred;        /* [B][rows][5+nc] */
+    const int* classes;       /* HOST: class filter, n_classes ids in 0..255, or NULL */
+    const float* labels;      /* [L][5] cls, cx, cy, w, h; NULL: none */
+    const int* label_off;     /* [B+1] */
+    float* det;               /* [B][max_det][6] */
+    int* count;               /* [B] */
+    int* keep_idx;            /* [B][max_det] or NULL */
+    void* workspace;          /* icaf_nms_ex_workspace_bytes, 256-byte aligned */
+    size_t workspace_bytes;
+    long long rows;
+    int B, nc;
+    float conf_thres, iou_thres;
+    int multi_label, agnostic;
+    int n_classes, max_det;
+    int max_nms, max_labels;
+    float max_wh;
+    int merge, redundant;
+    int reserved;
+} icaf_nms_args;
+int icaf_nms_ex_workspace_bytes(ICAF_HOST const icaf_nms_args* a, ICAF_HOST size_t* bytes);
+int icaf_nms_ex(ICAF_HOST const icaf_nms_args* a, icaf_stream_t s);
 
 /* ---- KAIST log-average miss rate, per-image half (evaluation_script/evaluation_script.py:46-79, 119-179, 181-294, 478-497) ----------
  * The reference evaluator's nine passes (All / Day / Night on set-up 0, near / medium / far / none / partial / heavy on set-ups 1-6) share

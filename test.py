@@ -21,12 +21,15 @@ everything downstream as it is; `--hyp PATH` (or `test(compute_loss=...)`, as th
 loss — the forward value of the reference's ComputeLoss on the raw Detect maps of every batch (utils/loss.py:325-463; icaf_loss, no gradients),
 averaged over the batches as test.py:132-133,364-367 do, with the hyp gains scaled as train.py:238-241 scales them — fills the three trailing
 values and prints one `Loss:` line; there is no default hyp file, and without the flag nothing changes.  An image whose candidates exceed the confluence cap, or that keeps more than 1024 boxes, raises.
+`--save-hybrid` (test.py:137-139, 414) hands every batch's pixel-space labels to NMS as apriori candidates at conf 1 and forces `--save-txt`;
+`--merge-nms` runs the reference's merge-NMS (utils/general.py:594-600: score-weighted mean of the overlapping candidates, images with
+1 < n < 3000 candidates, fp64 sums in the fixed order of include/icaf.h); neither goes with `--confluence`.
 `--plots` builds the reference's ConfusionMatrix (test.py:103,205-206,320-321; conf 0.25 / IoU 0.45) on the device, one launch per batch, prints
 it and saves confusion_matrix.txt (and confusion_matrix.png when matplotlib is there); `--device-stats` keeps the statistics of the pass on the device: every batch is
 appended to an ops.StatsStore, nothing is read back per batch (result files excepted), the four synchronisations per batch become event pairs, and
 ap_per_class runs as kernels with a DEFINED order at equal confidences (arrival order; the host's np.argsort leaves it to the numpy build).  Without
 the two flags the loop runs the code it always ran.  Not carried over (all outside the metric): the PR / F1 / P / R curve images and `plot_images` /
-wandb / `--save-hybrid` auto-labelling / `--task study` / the pycocotools call / MR curves and plots; `--augment` raises (the help text says
+wandb / `--task study` / the pycocotools call / MR curves and plots; `--augment` raises (the help text says
 test-time augmentation is not built; Model.forward(augment=True) is by now — test() still refuses it)."""
 import argparse
 import os
@@ -132,10 +135,13 @@ class MissRate:
 @torch.no_grad()
 def test(data, weights=None, batch_size=32, imgsz=640, conf_thres=0.001, iou_thres=0.5, single_cls=False, model=None,
          dataloader=None, device="0", compute_dtype=None, cfg=None, verbose=False, save_json=False, save_txt=False, save_conf=True,
-         save_dir=None, augment=False, compute_loss=None, confluence=None, plots=False, device_stats=False, stats_out=None, miss_rate=None,
-         device_letterbox=False):
+         save_dir=None, augment=False, compute_loss=None, confluence=None, plots=False, device_stats=False, stats_out=None, save_hybrid=False,
+         merge_nms=False, miss_rate=None, device_letterbox=False):
     if augment:
         raise NotImplementedError("test-time augmentation (models/yolo_test.py:116-132) is outside the inference hot path")
+    if confluence is not None and (save_hybrid or merge_nms):
+        raise ValueError("--save-hybrid and --merge-nms are modes of NMS: they do not go with --confluence")
+    save_txt = save_txt or save_hybrid                                   # reference test.py:414
     if isinstance(data, str):
         with open(data) as f:
             data = yaml.safe_load(f)
@@ -196,7 +202,9 @@ def test(data, weights=None, batch_size=32, imgsz=640, conf_thres=0.001, iou_thr
                                      "; raise --conf-thres")
             det = det[:, :MATCH_MAX_DET].contiguous()
         else:
-            det, count, _ = nms_device(out, conf_thres, iou_thres, multi_label=True, agnostic=single_cls)
+            # --save-hybrid: the batch's pixel-space targets join the candidates as apriori labels (reference test.py:137-139)
+            lb = [targets[targets[:, 0] == si, 1:] for si in range(nb)] if save_hybrid else None
+            det, count, _ = nms_device(out, conf_thres, iou_thres, multi_label=True, agnostic=single_cls, labels=lb, merge=merge_nms)
         t_nms += clock() - t
         # statistics per image (reference test.py:144-230) on the device: labels go up in native image space, one kernel
         # maps the detections there (scale_coords + clip_coords) and matches them; only flags / conf / cls come back
@@ -306,7 +314,9 @@ def parse_opt(argv=None):
     ap_.add_argument("--save-txt", action="store_true", help="per-image result lines + result.txt under <project>/<name>/labels")
     ap_.add_argument("--save-conf", action="store_true", help="append the confidence to every --save-txt line")
     ap_.add_argument("--save-json", action="store_true", help="<project>/<name>/<weights>_predictions.json")
-    ap_.add_argument("--save-hybrid", action="store_true", help="auto-labelling: not built, raises")
+    ap_.add_argument("--save-hybrid", action="store_true", help="auto-labelling: the labels join the NMS candidates at conf 1 (implies --save-txt)")
+    ap_.add_argument("--merge-nms", action="store_true", help="merge-NMS: every kept box becomes the score-weighted mean of the candidates "
+                                                              "overlapping it (images with fewer than 3000 candidates)")
     ap_.add_argument("--project", default="runs/test")
     ap_.add_argument("--name", default="exp")
     ap_.add_argument("--exist-ok", action="store_true")
@@ -341,8 +351,7 @@ def load_model(weights, cfg, nc, device, compute_dtype):
 if __name__ == "__main__":
     o = parse_opt()
     print(o)
-    if o.save_hybrid:
-        raise NotImplementedError("--save-hybrid (label + prediction auto-labelling, test.py:134-135) is outside the inference hot path")
+    o.save_txt |= o.save_hybrid                                             # reference test.py:414
     if o.task not in ("val", "test", "train", "speed"):
         raise NotImplementedError(f"--task {o.task}: only val / test / train / speed are built (study = image-size sweep + plots)")
     dtype = torch.float16 if o.half else torch.bfloat16 if o.bf16 else None
@@ -362,4 +371,4 @@ if __name__ == "__main__":
         test(o.data, o.weights, o.batch_size, imgsz, o.conf_thres, o.iou_thres, o.single_cls, device=o.device, compute_dtype=dtype, cfg=o.cfg,
              verbose=o.verbose, save_json=o.save_json, save_txt=o.save_txt, save_conf=o.save_conf, save_dir=save_dir, augment=o.augment,
              miss_rate=o.miss_rate, device_letterbox=o.device_letterbox, confluence=o.confluence, model=model, compute_loss=compute_loss,
-             plots=o.plots, device_stats=o.device_stats)
+             plots=o.plots, device_stats=o.device_stats, save_hybrid=o.save_hybrid, merge_nms=o.merge_nms)
