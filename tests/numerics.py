@@ -1255,3 +1255,296 @@ def attn_known_qkv(B, N, C, dt, seed):
     assert torch.equal(v.sum(2, keepdim=True), N * base) and torch.equal(v.to(dt).float(), v)
     qkv = torch.cat((_ri(g, -8, 8, (2, B, N, C)), torch.zeros((2, B, N, C)), v), 3).reshape(2, B * N, 3 * C)
     return qkv, base.expand(2, B, N, C).reshape(2, B * N, C).contiguous()
+
+
+# ====================================================================================================================================
+# cross attention (dmff.hip: cross_attn_kernel, cross_attn_stream_kernel; attn_core.h: AttnCore, also inside dmff_attn_mlp_kernel).
+# qkv is (2, B * N, 3C) = [Q | K | V], heads head-major inside each third; direction `dir` reads K / V of modality dir and Q of the OTHER
+# modality:  out[dir] = softmax(Q[1 - dir] K[dir]^T / sqrt(d_k)) V[dir]  per (image, head).
+# ====================================================================================================================================
+LOG2E = 1.4426950408889634
+EXP2_REL = 2.0 * U32             # v_exp_f32: 1 ulp — the figure silu_budget32 above takes from the ISA guide (the guide's text is not part of
+                                 # this repository; tests/test_gpu_exact_attn.py records what the fp32 builds show against fp64 beside it)
+ATTN_HEADS = 8
+ATTN_RES_DK = (16, 32, 40, 64, 72, 128)              # resident form: DKP 16 / 32 / 48 / 64 / 96 / 128
+ATTN_STREAM_DK = (64, 128, 192, 256)                 # streaming form: 64 and 128 through the knob attn_stream, 192 and 256 by the library's choice
+ATTN_CELLS = [(0, dk) for dk in ATTN_RES_DK] + [(1, dk) for dk in ATTN_STREAM_DK]
+ATTN_TOKENS = ((1, 77), (4, 77), (1, 130), (4, 130), (1, 32))       # (B, N)
+ATTN_DEFER = 6.0                                     # AttnCore::DEFER (16-bit builds)
+ATTN_UNDERFLOW = 149.0 + ATTN_DEFER + 8.0            # exponent distance below which a probability is 0 in fp32 whatever maximum is held
+ATTN_DEFECTS = ("nomask", "vtperm", "scale_dkp", "l_norescale", "dirswap", "headoff", "lastq")
+
+
+def attn_dkp(dk, form):
+    """Padded head dimension of the instantiation (attn_select in dmff.hip)."""
+    return next(p for p in ((64, 128, 256) if form else (16, 32, 48, 64, 96, 128)) if p >= dk)
+
+
+def attn_resident_lds(dk, N, dt):
+    """LDS bytes of the resident form (attn_resident_lds in dmff.hip): above 160 KiB the library streams the shape instead."""
+    eb, NP, dkp = (4 if dt == F32 else 2), (N + 31) // 32 * 32, attn_dkp(dk, 0)
+    return NP * (dkp * eb + 16) + (dkp + (1 if dt != F32 and dkp % 32 == 16 else 0)) * (NP * eb + 16)
+
+
+def attn_form(dk, N, dt, form):
+    """The form a cell's launch really takes: a resident cell whose K / V^T do not fit the LDS (fp32, d_k = 128, N = 130) streams."""
+    return 1 if form or dk > 128 or attn_resident_lds(dk, N, dt) > 160 * 1024 else 0
+
+
+def attn_den(dk, form, dt):
+    """Where the instantiation forms the softmax denominator: "free" (a ones row of V^T in the unused rows of the last O^T tile), "xtra" (one
+    more MFMA with an all-ones A operand) — both sum the ROUNDED probabilities — or "valu" (fp32 adds of the unrounded ones)."""
+    if dt == F32 or form:
+        return "valu"
+    dkp = attn_dkp(dk, form)
+    return "free" if dkp % 32 == 16 else "xtra" if dkp == 32 else "valu"
+
+
+def attn_scale(dk):
+    """scale_l2e as the launch computes it: fp32(log2(e) / sqrt(d_k)), as an fp64 number."""
+    return f32w((1.0 / math.sqrt(dk)) * LOG2E)
+
+
+def _attn_split(qkv, B, N, C, heads):
+    """(2, B * N, 3C) -> q, k, v as (2, B, heads, N, dk) of the modality that STORES them."""
+    f = qkv.reshape(2, B, N, 3, heads, C // heads)
+    return tuple(f[:, :, :, i].permute(0, 1, 3, 2, 4) for i in range(3))
+
+
+def _attn_join(o):
+    """(2, B, heads, N, dk) -> (2, B * N, C)"""
+    G, B, H, N, dk = o.shape
+    return o.permute(0, 1, 3, 2, 4).reshape(G, B * N, H * dk).contiguous()
+
+
+def attn_select_qkv(B, N, dk, seed, heads=ATTN_HEADS, vmax=127):
+    """Family `select`: query i of (direction, image, head) has ONE winning key pi(i); every other probability is exactly 0 in fp32.
+    Dimension 0 of a head holds q = -d_k a_q and k = a_k, dimensions 1 .. d_k - 1 hold a_q / a_k times a +-1 code word; a_q a_k = A is a power
+    of two.  A key's code word is an 8-bit number (a random permutation of 0 .. 255 per group, cut to N) with bit (d mod 8) on code dimension d,
+    the dimensions shuffled and sign-flipped per (direction, image, head); the query carries the word of its winner.  Hence
+        score(i, j) = A ((d_k - 1) - 2 hamming(i, j)) - A d_k:   -A for the winner, <= -A (1 + 2 dmin) for every other key, dmin = (d_k - 1) // 8,
+    every term a multiple of A below 2^24: an exact integer in fp32 in any order.  All scores are negative, so a zero-filled padding key
+    that is not masked, or a zero K row, BEATS the winner by A c >= ATTN_UNDERFLOW / (2 dmin) in the exponent domain and the output
+    collapses to 0.  A is the smallest power of two with 2 A dmin c >= ATTN_UNDERFLOW = 149 + 6 + 8: a loser's probability is at most
+    2^-(149 + 8) relative to whatever maximum the deferred loop holds (at most 6 below the true one) — 0 in fp32 — and once the winner has
+    been seen the rescale factor of everything before it is 0 as well.  V: non-zero integers in [-vmax, vmax], rows distinct.
+    Returns (qkv (2, B * N, 3C), expected (2, B * N, C) = V[pi(i)] of the direction's own modality, pi (2, B, heads, N))."""
+    g = _gen(seed)
+    L, C = dk - 1, heads * dk
+    dmin = L // 8
+    c = LOG2E / math.sqrt(dk)
+    A = 2.0 ** math.ceil(math.log2(ATTN_UNDERFLOW / (2.0 * dmin * c)))
+    aq = 2.0 ** math.ceil(math.log2(A) / 2.0)
+    ak = A / aq
+    assert 2.0 * A * dk < 2.0 ** 24 and N <= 256 and dmin >= 1
+    G = (2, B, heads)
+    word = torch.stack([torch.randperm(256, generator=g)[:N] for _ in range(2 * B * heads)]).reshape(*G, N)
+    dimp = torch.stack([torch.randperm(L, generator=g) for _ in range(2 * B * heads)]).reshape(*G, 1, L)
+    sign = _ri(g, 0, 1, (*G, 1, L)) * 2.0 - 1.0
+    code = (1.0 - 2.0 * ((word[..., None] >> (dimp % 8)) & 1).float()) * sign                  # (2, B, heads, N, L)
+    pi = torch.randint(0, N, (*G, N), generator=g)
+    qcode = torch.gather(code, 3, pi[..., None].expand(*G, N, L))                                # query i carries the word of key pi(i) ...
+    k = torch.cat((torch.full((*G, N, 1), ak), ak * code), 4)
+    q = torch.cat((torch.full((*G, N, 1), -dk * aq), aq * qcode), 4).flip(0)                     # ... and is stored in the OTHER modality
+    v = _nonzero(g, vmax, (*G, N, dk))
+    want = torch.gather(v, 3, pi[..., None].expand(*G, N, dk))
+    qkv = torch.cat((_attn_join(q), _attn_join(k), _attn_join(v)), 2)
+    # ---- the construction, asserted in fp64 ----
+    s = q.flip(0).double() @ k.double().transpose(-1, -2)
+    assert torch.equal(s, s.round()) and float(s.abs().max()) < 2.0 ** 24 and float(s.max()) < 0.0, "select: scores must be negative integers below 2^24"
+    win = torch.gather(s, 4, pi[..., None])
+    assert torch.equal(win, s.amax(4, keepdim=True)) and bool((win == -A).all())
+    gap = (win - s) * c
+    gap.scatter_(4, pi[..., None], float("inf"))
+    assert float(gap.min()) >= ATTN_UNDERFLOW, f"select: a losing key lies only {float(gap.min()):.1f} below its winner"
+    assert A * c < 2.0 ** 11                         # |m c| < 2^11: the fma's residual exponent is below 2^-13, P of the winner rounds to 1 in 16 bit
+    chosen = torch.zeros(N, dtype=torch.bool)
+    chosen[pi.reshape(-1)] = True
+    assert bool(chosen.all()), "select: some key index is nobody's winner in any group"
+    assert all(len(torch.unique(pi.reshape(-1, N)[i])) < N for i in range(2 * B * heads)), "select: pi must not be a bijection"
+    rows = v.reshape(-1, dk)
+    assert len(torch.unique(rows, dim=0)) == len(rows), "select: V rows must be distinct"
+    for t in (qkv, want):
+        assert torch.equal(t.to(BF16).float(), t) and torch.equal(t.to(F16).float(), t)
+    return qkv, _attn_join(want), pi
+
+
+def attn_select_bound(want, dt):
+    """|out - V[pi(i)]| of family select, from attn_core.h.  m is the winner's score exactly once its tile has run (first tile: m = the tile
+    maximum; later: the winner exceeds any held maximum by more than the slack, so the cold path runs and alpha = exp2(<= -155) = 0 wipes O
+    and l).  The winner's exponent fma(s, c, -fl(m c)) is the rounding error of m c, below 2^-24 * 2^11; P = exp2 of it is 1 + O(2^-13):
+      16 bit: P rounds to 1; O = v exactly.  free / xtra: l = 1, the result is v.  valu: l = 1 + O(2^-13) unrounded, o / l is within 2^-13 of v,
+              less than a quarter unit of either type — RNE returns v.  None: BIT FOR BIT in all three forms.
+      fp32:   O = fl(v P) (<= 2u, MFMA rounding not assumed to be RNE), l = P, 1 / l (<= 2u), the product (u): 5u |v|."""
+    if dt != F32:
+        return None
+    return 5.0 * U32 * SECOND * want.double().abs() + SUB32
+
+
+# (key, height in the exponent domain above the background's mean) of the dominant keys of family graded, per N
+ATTN_STAIRS = {32: ((10, 12.0), (30, 20.0)),
+               77: ((25, 12.0), (44, 16.0), (70, 46.0), (76, 50.0)),
+               130: ((25, 12.0), (44, 16.0), (80, 22.0), (120, 50.0), (129, 54.0))}
+
+
+def attn_graded_qkv(B, N, dk, seed, heads=ATTN_HEADS):
+    """Family `graded`: real softmax weights with the cold path forced.  Q integers in {0, 1, 2}, background K integers in [-2, 2] (scores
+    exact integers, about +-2.6 sigma wide in the exponent domain at every d_k), V = j / 4 with |j| <= 32.  ATTN_STAIRS[N] places dominant keys
+    late in the key order: K = t on a random subset S of the head's dimensions and 0 elsewhere, t |S| ~ height / c, so a query's score is
+    t sum_S q — the height holds on average and varies by a few units from query to query.  After the first tile the held maximum is about
+    12; the step to 16 stays below the slack of 6 (no rescale, p up to 2^6, for most lanes), the step to 22 lies just above it, the steps
+    to 46 / 50 far above (O and the denominator rescaled by 2^-30), the last one sits on the last key — in the ragged last tile, again less
+    than the slack above the maximum held there.  |s - m| c stays below about 70."""
+    g = _gen(seed)
+    G = (2, B, heads)
+    q = _ri(g, 0, 2, (*G, N, dk))
+    k = _ri(g, -2, 2, (*G, N, dk))
+    v = _ri(g, -32, 32, (*G, N, dk)) / 4.0
+    c = LOG2E / math.sqrt(dk)
+    for key, h in ATTN_STAIRS[N]:
+        t = math.ceil(h / c / dk)
+        ns = max(1, min(dk, round(h / c / t)))
+        sel = torch.stack([torch.randperm(dk, generator=g) < ns for _ in range(2 * B * heads)]).reshape(*G, dk)
+        k[:, :, :, key] = sel.float() * t
+    qkv = torch.cat((_attn_join(q.flip(0)), _attn_join(k), _attn_join(v)), 2)
+    assert torch.equal(qkv.to(BF16).float(), qkv) and torch.equal(qkv.to(F16).float(), qkv)
+    return qkv
+
+
+def attn_ref64(qkv, B, N, C, heads=ATTN_HEADS, dk_scale=None):
+    """fp64 softmax(q k^T / sqrt(d_k)) v with the true d_k, and what the counted bound needs, each (2, B * N, C):
+      out   the reference;
+      dev   sqrt(sum_k w_k (v_k - out)^2) >= sum_k w_k |v_k - out| (Jensen): what a relative perturbation of the WEIGHTS multiplies;
+      a1    sum_k w_k |v_k|: what a relative perturbation of the numerator alone, or of the accumulation, multiplies;
+      sc    max_k |s_k| c of the query's row, repeated over the head's channels."""
+    dk = C // heads
+    q, k, v = (t.double() for t in _attn_split(qkv, B, N, C, heads))
+    s = q.flip(0) @ k.transpose(-1, -2)
+    w = torch.softmax(s / math.sqrt(dk_scale or dk), -1)
+    out = w @ v
+    dev = torch.sqrt(torch.clamp(w @ (v * v) - out * out, min=0.0)) + 2.0 ** -40
+    sc = (s.abs().amax(-1, keepdim=True) * (LOG2E / math.sqrt(dk))).expand_as(out)
+    return dict(out=_attn_join(out), dev=_attn_join(dev), a1=_attn_join(w @ v.abs()), sc=_attn_join(sc), vmax=float(v.abs().max()))
+
+
+def attn_graded_bound(ref, N, dk, form, dt):
+    """Per-element bound on |device - ref['out']| of one launch, counted from attn_core.h (u = 2^-24, nkt = key tiles, first order):
+      exponent   fma(s, c, -fl(m c)): the rounding of c (u |s - m| c), of m c (u |m| c) and of the fma (u |s - m| c); alpha on the cold path:
+                 fl((m - m') c) with the rounded c, 2u |m - m'| c, at most once per tile.  All at most (5 + 4 nkt) u max|s| c, times ln 2
+                 as a relative error of the probability;
+      exp2       EXP2_REL per probability and per alpha: (1 + nkt) EXP2_REL;
+                 — both reach numerator and denominator alike (alpha scales O and the denominator together in every form), so they perturb
+                 the WEIGHTS: times dev;
+      P          RNE to the storage type, 2^-(MANT + 1) per probability: numerator and denominator alike in free / xtra (times dev, and
+                 1 + 2 eta for the perturbed denominator), the numerator only in valu (times a1); fp16: a probability below 2^-14 is rounded
+                 absolutely, 2^-25 each against a denominator >= 1: N 2^-25 max|v|;
+      sums       fp32 accumulation over the keys in the MFMA (or the VALU adds of the denominator) and the rescales: (N + nkt + 2) roundings
+                 of 3u each (product, add, no RNE assumed), in numerator and denominator: 2 (N + nkt + 2) 3u a1;
+      1 / l      2u, the product u: 3u |out|;
+      storage    half a unit of the type where the value lies (storage_bound)."""
+    nkt = (N + 31) // 32
+    out = ref["out"]
+    eta_w = math.log(2.0) * U32 * ref["sc"] * (5.0 + 4.0 * nkt) + (1.0 + nkt) * EXP2_REL
+    b32 = eta_w * ref["dev"] + 2.0 * (N + nkt + 2) * 3.0 * U32 * ref["a1"] + 3.0 * U32 * out.abs() + SUB32
+    if dt != F32:
+        eta_p = 2.0 ** -(MANT[dt] + 1)
+        b32 = b32 + (eta_p * (1.0 + 2.0 * eta_p) * ref["dev"] if attn_den(dk, form, dt) != "valu" else eta_p * ref["a1"])
+        if dt == F16:
+            b32 = b32 + N * 2.0 ** -25 * ref["vmax"]
+    return storage_bound(out, SECOND * b32, dt)
+
+
+def attn_uniform_bound(att, N, dt):
+    """Family uniform (attn_known_qkv: K = 0): p = exp2(0) = 1 for the N keys, O = N mean exactly, l = N; o * fl(1 / l) carries 2u + u.
+    16 bit: the mean is representable and 3u is far inside a quarter unit: BIT FOR BIT (None).  fp32: 3u |mean| (exact at a power of two)."""
+    if dt != F32:
+        return None
+    return 3.0 * U32 * SECOND * att.double().abs() + SUB32
+
+
+def attn_gauss_qkv(B, N, C, seed=41):
+    """The Gaussian data of test_cross_attention (tests/test_gpu_kernels.py), for the record of what close(factor=2) accepts."""
+    qkv = rnd((2, B * N, 3 * C), seed, 1.0)
+    qkv[:, :, :2 * C] *= 1.5
+    return qkv
+
+
+def emulate_attention(qkv, B, N, C, heads, dt, form, defect=None):
+    """fp32 restatement of the tile loop of attn_core.h / cross_attn_stream_kernel for one launch: 32-key tiles, 32-query tiles (one wave
+    each: the cold-path vote __any is taken over the tile's 32 queries, padding queries — zero Q rows — included), the deferred maximum
+    with slack DEFER / c (none in fp32), P rounded to `dt` for the numerator, the denominator from the rounded P (free / xtra) or from the
+    unrounded one (valu), the rescale of O and the denominator, o * (1 / l), RNE to `dt`.  qkv: CPU tensor holding `dt` values.
+    defect: None or one of ATTN_DEFECTS —
+      nomask       padding keys keep their score 0;                       vtperm    keys 21 and 26 (one 16-key group) trade places in V^T;
+      scale_dkp    c = log2e / sqrt(DKP);                                 l_norescale  the denominator is not rescaled on the cold path;
+      dirswap      queries taken from the direction's own modality;       headoff   K of head h against V of head h + 1;
+      lastq        the last row of a ragged query tile is not written (stays NaN)."""
+    assert defect is None or defect in ATTN_DEFECTS
+    dk = C // heads
+    dkp = attn_dkp(dk, form)
+    den = attn_den(dk, form, dt)
+    cf = torch.tensor(attn_scale(dkp if defect == "scale_dkp" else dk), dtype=F32)
+    defer = torch.tensor(ATTN_DEFER, dtype=F32) / cf if dt != F32 else torch.tensor(0.0)
+    q, k, v = (t.to(dt).float() for t in _attn_split(qkv, B, N, C, heads))
+    if defect != "dirswap":
+        q = q.flip(0)
+    if defect == "headoff":
+        v = v.roll(-1, 2)
+    if defect == "vtperm":
+        v = v.clone()
+        v[:, :, :, [21, 26]] = v[:, :, :, [26, 21]]
+    NP = (N + 31) // 32 * 32
+    nkt = NP // 32
+    pad = lambda t: torch.cat((t, torch.zeros((*t.shape[:3], NP - N, dk))), 3)
+    q, k, v = pad(q), pad(k), pad(v)
+    s = q @ k.transpose(-1, -2)                                    # (2, B, heads, NP, NP); exact on integer data in any order
+    if defect != "nomask":
+        s[..., N:] = float("-inf")
+    m = torch.full((2, B, heads, NP, 1), float("-inf"))
+    l = torch.zeros_like(m)
+    acc = torch.zeros((2, B, heads, NP, dk))
+    for kt in range(nkt):
+        st, vt = s[..., kt * 32:(kt + 1) * 32], v[:, :, :, kt * 32:(kt + 1) * 32]
+        tmax = st.amax(-1, keepdim=True)
+        vote = (tmax > m + defer).reshape(2, B, heads, nkt, 32).any(-1, keepdim=True).expand(2, B, heads, nkt, 32).reshape(m.shape)
+        m_new = torch.where(vote, torch.maximum(m, tmax), m)
+        alpha = torch.where(vote, torch.exp2((m - m_new) * cf), torch.ones_like(m))
+        if defect != "l_norescale":
+            l = l * alpha
+        acc = acc * alpha
+        m = m_new
+        mc = m * cf
+        p = torch.exp2(fma32(float(cf), st, -mc.expand_as(st)))
+        pr = p.to(dt).float()
+        acc = acc + pr @ vt
+        l = l + (p if den == "valu" else pr).sum(-1, keepdim=True)
+    out = (acc * (1.0 / l))[:, :, :, :N].to(dt)
+    if defect == "lastq" and N % 32:
+        out[:, :, :, N - 1] = float("nan")
+    return _attn_join(out)
+
+
+def attn_bound(family, ref, N, dk, form, dt):
+    """(fp64 reference, per-element bound or None for "bit for bit") of one launch of `family`."""
+    if family == "graded":
+        return ref["out"], attn_graded_bound(ref, N, dk, form, dt)
+    return ref.double(), attn_select_bound(ref, dt) if family == "select" else attn_uniform_bound(ref, N, dt)
+
+
+def attn_ratio(family, got, ref, N, dk, form, dt):
+    """Largest err / budget of one launch, for the record; where the check is bit for bit the budget is half a unit of the type, so anything
+    but 0 fails."""
+    r64, bound = attn_bound(family, ref, N, dk, form, dt)
+    return budget_ratio(got, r64, bound if bound is not None else 0.5 * ulp(r64, dt))
+
+
+def check_attention(family, got, ref, N, dk, form, dt, what):
+    """The check of one launch of `family` ("select": ref = expected tensor; "uniform": ref = the mean; "graded": ref = attn_ref64()).
+    Returns the largest err / budget (0 stands for bit-identical)."""
+    if family == "graded":
+        return assert_budget(got, ref["out"], attn_graded_bound(ref, N, dk, form, dt), what, signed=False)
+    bound = attn_select_bound(ref, dt) if family == "select" else attn_uniform_bound(ref, N, dt)
+    if bound is None:
+        assert_same_bits(got, rne(ref.double(), dt) + 0.0, what)
+        return 0.0
+    return assert_budget(got, ref.double(), bound, what, signed=False)

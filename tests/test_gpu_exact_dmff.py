@@ -17,14 +17,16 @@ the others, a sparse W2 keeps the fc2 accumulation error counted.
     for bit; the wide kernel in both forms (three passes per workgroup, and one: OPT.dmff_qkv_npass = 1), which must also agree with each other.
 (e) the two-launch kernel icaf_dmff_attn_mlp with an attention output known exactly (K = 0, V with a representable per-image mean:
     numerics.attn_known_qkv), then (a) and (b) on it: all three softmax-denominator forms of attn_core.h (d_k = 16, 32, 64), N = 64 and
-    N = 77 (a second tile of 13 rows per image), both workgroup placements (2 B a multiple of 8 or not).
+    N = 77 (a second tile of 13 rows per image), both workgroup placements (2 B a multiple of 8 or not).  The 16-bit builds again with
+    the select family (numerics.attn_select_qkv: one winning key per query, the tile is V of that key), which moves under a wrong key
+    order in V^T, a wrong Q offset, a wrong maximum and a denominator the cold path skipped — all of which leave the mean where it is.
 
 Known limitation: on rows m +- s that a 16-bit type represents, x * x is exact as well, so this gate does not tell a one-pass variance
 E[x^2] - mean^2 from the two-pass one.  In the fp32-stream builds it does: every fourth row of the x32 case of (b) lies around m = 4096, where
 x * x is not an fp32 number.  For the 16-bit stream the protection is the `ln_rows` kinds of tests/test_gpu_exact.py (icaf_layernorm and the
 identity-Q test of the fused LayerNorm + QKV kernels).
 
-Every test prints the largest err / budget it saw before it asserts (`-s`); docs/HISTORY.md section 20 records them."""
+Every test prints the largest err / budget it saw before it asserts (`-s`); docs/HISTORY.md sections 20 and 22 record them."""
 import pytest
 import torch
 
@@ -290,8 +292,12 @@ def test_attn_mlp_with_known_attention_tile(C, heads, dt, B, N):
     itself is representable (tests/test_numerics_selftest.py checks both statements); the fp32 build stores the tile unrounded and is
     therefore run at the power-of-two count only.  With the tile known, (a) (W2 = 0: y == RNE(x_att) bit for bit) and (b) (W_o = 0: counted
     bound) run as for the three-launch kernels, into a NaN-prefilled strided y whose gaps must stay untouched."""
+    attn_mlp_on_known_tile(*nm.attn_known_qkv(B, N, C, dt, 100 * C + N), "", C, heads, dt, B, N)
+
+
+def attn_mlp_on_known_tile(qkv_c, att, tag, C, heads, dt, B, N):
+    """One icaf_dmff_attn_mlp launch per check (a) / (b) on a qkv whose attention tile `att` is known exactly after the store to `dt`."""
     rows = B * N
-    qkv_c, att = nm.attn_known_qkv(B, N, C, dt, 100 * C + N)
     qkv = nm.PoisonedFlat((2, rows, 3 * C), dt, DEV, nm.NAN_BITS[dt], qkv_c.to(dt).to(DEV), 6 * C)
     failures = []
     for kind in ("a", "b"):
@@ -301,7 +307,7 @@ def test_attn_mlp_with_known_attention_tile(C, heads, dt, B, N):
         blk = Block(d, dt)
         x = nm.PoisonedFlat((2, rows, C), dt, DEV, nm.INF_BITS[dt], blk.tok["x"], 2 * C)
         y = StridedOut(rows, C, dt)
-        what = f"icaf_dmff_attn_mlp ({kind}) C={C} heads={heads} {nm.DT_NAME[dt]} B={B} N={N}"
+        what = f"icaf_dmff_attn_mlp{tag} ({kind}) C={C} heads={heads} {nm.DT_NAME[dt]} B={B} N={N}"
         ops.dmff_attn_mlp(x.view, qkv.view, y.view, blk.packs, blk.ln, blk.coef, d["eps"], B, N, heads)(ops.current_stream_ptr())
         torch.cuda.synchronize()
         try:
@@ -314,9 +320,25 @@ def test_attn_mlp_with_known_attention_tile(C, heads, dt, B, N):
             else:
                 assert want["share"] <= 0.05
                 r = nm.budget_ratio(got, want["out"], want["by"])
-                RATIOS[("(e) y", f"C{C}-h{heads}-{nm.DT_NAME[dt]}-N{N}")] = r
+                RATIOS[("(e) y" + tag, f"C{C}-h{heads}-{nm.DT_NAME[dt]}-N{N}")] = r
                 print(f"\n[dmff e] {what}: err / budget {r:.3f}, ambiguous share {want['share']:.4f}")
                 nm.check_proj_mlp_b(got, None, want, dt, what)
         except AssertionError as e:
             failures.append(str(e)[:400])
     assert not failures, "\n".join(failures)
+
+
+# The select family of tests/numerics.py ("cross attention"): one winning key per query, every other probability exactly 0, all scores
+# negative — the attention tile is V[pi(i)] of the modality the direction reads, which a wrong key order in V^T, a wrong head or direction
+# offset, an unmasked padding key or a skipped rescale of the denominator all change (the K = 0 mean above is invariant under a key
+# permutation, under whatever Q holds and under a wrong maximum or rescale).  Stage A of dmff_attn_mlp_kernel stores the tile with pack4<DT>(o * inv): the bf16 and f16 builds round it to the storage type
+# there, and RNE(v (1 + O(2^-13))) = v (numerics.attn_select_bound); the fp32 build stores o * inv unrounded, v (1 + 5 u) at best, so checks
+# (a) and (b), which need the tile on the lattice, do not apply to it and it is left to the K = 0 cases.
+SELECT_CASES = [(C, h, dt, B, N) for C, h in ATTN_HEADS for dt in (BF16, F16) for B, N in ATTN_TOKENS]
+
+
+@pytest.mark.parametrize("C,heads,dt,B,N", SELECT_CASES, ids=[f"C{C}-h{h}-{nm.DT_NAME[dt]}-B{B}-N{N}" for C, h, dt, B, N in SELECT_CASES])
+def test_attn_mlp_with_selected_attention_tile(C, heads, dt, B, N):
+    """(e) with the select family (V = non-zero integers in [-8, 8], the lattice of (a)): d_k = 16 / 32 / 64, N = 64 / 77, the 16-bit builds."""
+    qkv_c, att, _ = nm.attn_select_qkv(B, N, C // heads, 300 * C + N, heads=heads, vmax=8)
+    attn_mlp_on_known_tile(qkv_c, att, " select", C, heads, dt, B, N)

@@ -540,3 +540,131 @@ def test_close_verdicts_of_the_block_defects_are_recorded():
         print("run with test_proj_mlp_defects_are_rejected (same process): nothing was recorded")
     for k in sorted(mine):
         print(f"close() on {k[0]} {k[1]}: {'ACCEPTS' if mine[k] else 'rejects'}")
+
+
+# ====================================================================================================================================
+# cross attention: the helpers behind tests/test_gpu_exact_attn.py, shown to fail
+# ====================================================================================================================================
+# nm.emulate_attention (an fp32 restatement of the tile loop of attn_core.h) stands in for the kernels.  What close(factor=2) of
+# tests/test_gpu_kernels.py makes of each planted defect on the Gaussian data of test_cross_attention is recorded beside the verdict of the
+# new families (docs/HISTORY.md section 22).
+D3 = [F32, BF16, F16]
+D3_IDS = ["f32", "bf16", "f16"]
+ATTN_FAMILIES = ("select", "uniform", "graded")
+_ATTN = {}
+
+
+def attn_case(family, B, N, dk):
+    """(qkv, reference) of one family, built once per shape (every value is representable in all three types)."""
+    key = (family, B, N, dk)
+    if key not in _ATTN:
+        C = nm.ATTN_HEADS * dk
+        if family == "select":
+            qkv, want, _ = nm.attn_select_qkv(B, N, dk, 7000 + 10 * dk + N)
+        elif family == "uniform":
+            qkv, want = nm.attn_known_qkv(B, N, C, F16, 100 * C + N)
+        else:
+            qkv = nm.attn_graded_qkv(B, N, dk, 9000 + 10 * dk + N)
+            want = nm.attn_ref64(qkv, B, N, C)
+        _ATTN[key] = (qkv, want)
+    return _ATTN[key]
+
+
+def attn_checks(form, dk, dt, B, N, defect=None, families=ATTN_FAMILIES):
+    """The emulation of one cell through the check of every family: {family: (error text or None, err / budget)}."""
+    res = {}
+    for fam in families:
+        qkv, want = attn_case(fam, B, N, dk)
+        got = nm.emulate_attention(qkv, B, N, nm.ATTN_HEADS * dk, nm.ATTN_HEADS, dt, form, defect)
+        ratio = nm.attn_ratio(fam, got, want, N, dk, form, dt)
+        try:
+            nm.check_attention(fam, got, want, N, dk, form, dt, fam)
+            res[fam] = (None, ratio)
+        except AssertionError as e:
+            res[fam] = (str(e)[:200], ratio)
+    return res
+
+
+@pytest.mark.parametrize("dt", D3, ids=D3_IDS)
+@pytest.mark.parametrize("form,dk", nm.ATTN_CELLS, ids=[f"{'stream' if f else 'resident'}-dk{d}" for f, d in nm.ATTN_CELLS])
+def test_attention_clean_emulation_is_accepted_at_every_cell(form, dk, dt):
+    """The clean emulation passes select, uniform and graded at N = 77, 130 and 32 in every (form, d_k, dtype) cell; graded really
+    exercises rounding; at the power-of-two count the uniform family is exact in fp32 as well."""
+    for N in (77, 130, 32):
+        res = attn_checks(form, dk, dt, 1, N)
+        assert all(v[0] is None for v in res.values()), f"N={N}: {res}"
+        nm.assert_rounding_exercised(attn_case("graded", 1, N, dk)[1]["out"], dt, f"graded dk={dk} N={N}")
+        print(f"clean attention form={form} dk={dk} N={N} {nm.DT_NAME[dt]} ({nm.attn_den(dk, form, dt)}): err / budget " +
+              ", ".join(f"{k} {v[1]:.3f}" for k, v in res.items()))
+        assert dt != F32 or N != 32 or res["uniform"][1] == 0.0
+
+
+@pytest.mark.parametrize("N", [77, 130, 32])
+@pytest.mark.parametrize("dk", sorted(set(nm.ATTN_RES_DK + nm.ATTN_STREAM_DK)))
+def test_select_construction_holds_for_every_shape(dk, N):
+    """attn_select_qkv asserts its own construction (negative integer scores below 2^24, every loser ATTN_UNDERFLOW below its winner in
+    fp64, every key index somebody's winner, pi no bijection, distinct V rows, all three types hold every value); here for every
+    (d_k, N) of the GPU module, at B = 1 and — the largest d_k of either form — B = 4, and against the fp64 softmax: the expected tensor IS
+    the reference to 2^-150."""
+    for B in ((1, 4) if dk in (128, 256) and N == 130 else (1,)):
+        qkv, want, pi = nm.attn_select_qkv(B, N, dk, 7000 + 10 * dk + N)
+        ref = nm.attn_ref64(qkv, B, N, nm.ATTN_HEADS * dk)
+        assert float((ref["out"] - want.double()).abs().max()) <= 127.0 * N * 2.0 ** -150
+        assert float(ref["dev"].max()) < 1e-9
+
+
+# defect -> (the family that must reject it, the cells it is planted in: free, xtra, valu with a padded d_k, streaming with a padded d_k)
+ATTN_DEFECT_CELLS = [(0, 16), (0, 32), (0, 72), (1, 192)]
+ATTN_DEFECT_MUST = {"nomask": ("select", ATTN_DEFECT_CELLS), "vtperm": ("select", ATTN_DEFECT_CELLS), "scale_dkp": ("graded", [(0, 40), (0, 72), (1, 192)]),
+                    "l_norescale": ("graded", ATTN_DEFECT_CELLS), "dirswap": ("select", ATTN_DEFECT_CELLS), "headoff": ("select", ATTN_DEFECT_CELLS),
+                    "lastq": ("select", ATTN_DEFECT_CELLS)}
+
+
+@pytest.mark.parametrize("dt", D3, ids=D3_IDS)
+@pytest.mark.parametrize("defect", nm.ATTN_DEFECTS)
+def test_attention_defects_are_rejected(defect, dt):
+    """Every planted defect is rejected by the family built for it, in every denominator form; the wrong scale of a padded head dimension
+    exceeds the graded budget by a wide factor (>= 10).  The same defect on the Gaussian data of test_cross_attention goes to
+    close(factor=2) for the record."""
+    must, cells = ATTN_DEFECT_MUST[defect]
+    B, N = 1, 77
+    for form, dk in cells:
+        res = attn_checks(form, dk, dt, B, N, defect)
+        caught = sorted(k for k, v in res.items() if v[0] is not None)
+        assert must in caught, f"{defect} form={form} dk={dk}: {must} accepted it ({res})"
+        assert defect != "scale_dkp" or res["graded"][1] >= 10.0, f"scale_dkp at dk={dk}: only {res['graded'][1]:.2f} x the budget"
+        print(f"{defect} form={form} dk={dk} {nm.DT_NAME[dt]}: rejected by {caught}; err / budget " + ", ".join(f"{k} {v[1]:.3g}" for k, v in res.items()))
+        C = nm.ATTN_HEADS * dk
+        g = nm.attn_gauss_qkv(B, N, C).to(dt).float()
+        got = torch.nan_to_num(nm.emulate_attention(g, B, N, C, nm.ATTN_HEADS, dt, form, defect).float(), nan=0.0)     # (close() ran on zero-filled outputs)
+        ref = nm.attn_ref64(g, B, N, C)["out"]
+        scale = max(float(ref.abs().max()), 1e-6)
+        record(f"attention:{defect}:{'stream' if form else 'resident'}-dk{dk}", dt, float((got.double() - ref).abs().max()) / scale <= 2.0 * OLD_TOL[dt])
+
+
+@pytest.mark.parametrize("dt", D16, ids=D16_IDS)
+@pytest.mark.parametrize("C,heads,B,N", [(64, 4, 4, 64), (128, 4, 3, 77), (128, 2, 3, 77)])
+def test_selected_attention_tile_of_the_two_launch_kernel_cases(C, heads, B, N, dt):
+    """Test (e) of tests/test_gpu_exact_dmff.py with the select family: the operands build (their construction asserts hold at 2 and 4
+    heads and V in [-8, 8]), the emulated attention returns the expected tile bit for bit, a wrong key order in V^T does not, and the
+    clean block emulation passes (a) and (b) with that tile in place of att."""
+    qkv, att, _ = nm.attn_select_qkv(B, N, C // heads, 300 * C + N, heads=heads, vmax=8)
+    nm.assert_same_bits(nm.emulate_attention(qkv, B, N, C, heads, dt, 0), att.to(dt), "select tile")
+    assert not nm.same_bits(nm.emulate_attention(qkv, B, N, C, heads, dt, 0, "vtperm"), att.to(dt))
+    for kind in ("a", "b"):
+        d = (nm.dmff_operands_a if kind == "a" else nm.dmff_operands_b)(C, dt, B * N)
+        d["att"] = att
+        y, _ = nm.emulate_proj_mlp(d, dt)
+        if kind == "a":
+            nm.check_proj_mlp_a(y, None, nm.dmff_xatt64(d), dt, "(e select, a)")
+        else:
+            nm.check_proj_mlp_b(y, None, nm.dmff_ref_b(d, dt), dt, "(e select, b)")
+
+
+def test_close_verdicts_of_the_attention_defects_are_recorded():
+    """Closing: what close(factor=2) accepted among the attention defects above (docs/HISTORY.md section 22)."""
+    mine = {k: v for k, v in VERDICTS.items() if k[0].startswith("attention:")}
+    if not mine:
+        print("run with test_attention_defects_are_rejected (same process): nothing was recorded")
+    for k in sorted(mine):
+        print(f"close(factor=2) on {k[0]} {k[1]}: {'ACCEPTS' if mine[k] else 'rejects'}")
