@@ -34,3 +34,19 @@ def attempt_load(weights, map_location=None):
     for k in ("names", "stride"):
         setattr(model, k, getattr(model[-1], k))
     return model
+
+
+def load_detector(weights, cfg, device, compute_dtype, nc=None):
+    """The model of the front ends (test.py, detect_twostream.py) on `device`, set to replay hipGraphs in `compute_dtype`: the checkpoint(s)
+    `weights`, or — without any — the network of the yaml `cfg` with deterministic synthetic weights, fused."""
+    if weights:
+        model = attempt_load(weights, map_location="cpu")
+    else:
+        from ..synth import synth_state_dict
+        model = Model(cfg, nc=nc).eval()
+        model.load_state_dict(synth_state_dict(model, seed=0))
+        model = model.fuse().eval()
+    model = model.to(device)
+    model.compute_dtype = compute_dtype
+    model.use_graph = True
+    return model

@@ -2,7 +2,7 @@
 """Validation loop (mAP@0.5, mAP@0.5:0.95) of the two-stream detector on MI355X — the reference's test.py:23-330 reduced
 to its metric path: paired RGB/IR loader -> forward -> NMS(multi_label) -> per-image TP matching at 10 IoU thresholds ->
 ap_per_class.  `test(...)` keeps the reference's return value ((mp, mr, map50, map, lbox, lobj, lcls), maps, times); the three losses are 0
-unless a loss is asked for (below).
+unless a loss is asked for (ValLoss).
 
     python test.py --data data/multispectral/kaist.yaml --weights best.pt --batch-size 32 --img-size 640
     python test.py --data ... --cfg models/transformer/yolov5s_Transfusion_kaist.yaml      (synthetic weights: plumbing)
@@ -10,37 +10,27 @@ unless a loss is asked for (below).
 Protocol as the reference's: rectangular batches with pad 0.5 (test.py:100 — KAIST's 512x640 frames become 544x672
 batches), conf 0.001 / IoU 0.5 multi-label NMS, boxes mapped back to native image space before matching.  Every distinct
 batch shape compiles its own execution plan (hipGraph); Model keeps them in a byte-capped LRU (Model.plan_cache_bytes).
-`--save-txt` / `--save-conf` / `--save-json` leave the reference's result files (per-image `frame,x,y,w,h[,conf]` lines + `result.txt`,
-the input of the KAIST miss-rate evaluator; `<weights>_predictions.json`) under `--project/--name` (icafusion_amd/utils/results.py);
-`--miss-rate ANNOTATIONS` adds the KAIST log-average miss rate (the evaluator of the reference's `evaluation_script/`: matching on the
-device, FPPI sweep in numpy; icafusion_amd/utils/missrate.py) and returns its dict as a fourth element; `--task speed` ignores it.
-`--task speed` runs at conf 0.25 / IoU 0.45 as the reference does.  `--device-letterbox` uploads the frames as decoded: the loader's
-longest-side resize (pixel-area average when shrinking) and the padding run on the device (Model.forward_frames(val_size=...)).
-`--confluence P_THRES` swaps the suppression step for the reference's confluence (its commented line test.py:140; utils/confluence.py) and leaves
-everything downstream as it is; `--hyp PATH` (or `test(compute_loss=...)`, as the reference's train.py:257,393 calls it) adds the validation
-loss — the forward value of the reference's ComputeLoss on the raw Detect maps of every batch (utils/loss.py:325-463; icaf_loss, no gradients),
-averaged over the batches as test.py:132-133,364-367 do, with the hyp gains scaled as train.py:238-241 scales them — fills the three trailing
-values and prints one `Loss:` line; there is no default hyp file, and without the flag nothing changes.  An image whose candidates exceed the confluence cap, or that keeps more than 1024 boxes, raises.
-`--save-hybrid` (test.py:137-139, 414) hands every batch's pixel-space labels to NMS as apriori candidates at conf 1 and forces `--save-txt`;
-`--merge-nms` runs the reference's merge-NMS (utils/general.py:594-600: score-weighted mean of the overlapping candidates, images with
-1 < n < 3000 candidates, fp64 sums in the fixed order of include/icaf.h); neither goes with `--confluence`.
-`--plots` builds the reference's ConfusionMatrix (test.py:103,205-206,320-321; conf 0.25 / IoU 0.45) on the device, one launch per batch, prints
-it and saves confusion_matrix.txt (and confusion_matrix.png when matplotlib is there); `--device-stats` keeps the statistics of the pass on the device: every batch is
-appended to an ops.StatsStore, nothing is read back per batch (result files excepted), the four synchronisations per batch become event pairs, and
-ap_per_class runs as kernels with a DEFINED order at equal confidences (arrival order; the host's np.argsort leaves it to the numpy build).  Without
-the two flags the loop runs the code it always ran.  Not carried over (all outside the metric): the PR / F1 / P / R curve images and `plot_images` /
-wandb / `--task study` / the pycocotools call / MR curves and plots; `--augment` raises (the help text says
-test-time augmentation is not built; Model.forward(augment=True) is by now — test() still refuses it)."""
+`--task speed` runs at conf 0.25 / IoU 0.45 as the reference does and saves nothing.
+
+test() is a set-up, one loop — forward, loss, suppress, labels, match, record, consumers — and the finish.  Each step of the loop is a
+function below (to_device / forward, suppress, native_labels, match); what the matching leaves goes into one ValBatch, and every output of
+the pass is a consumer of those records with `add(batch)` per batch and `finish()` after the loop, built only when its flag asks for it:
+MissRate, Confusion, HostStats or DeviceStats, ResultFiles (they see a batch in this order) and ValLoss, which is fed the raw maps before
+the labels go to pixels.  Each one's docstring describes its flag.  Without a flag the loop runs the code it always ran.
+
+Not carried over (all outside the metric): the PR / F1 / P / R curve images and `plot_images` / wandb / `--task study` / the pycocotools
+call / MR curves and plots; `--augment` raises (the help text says test-time augmentation is not built; Model.forward(augment=True) is by
+now — test() still refuses it)."""
 import argparse
+import collections
+import functools
 import os
-import time
 
 import numpy as np
 import torch
 import yaml
 
-from icafusion_amd.models.experimental import attempt_load
-from icafusion_amd.models.yolo import Model
+from icafusion_amd.models.experimental import load_detector
 from icafusion_amd.utils.datasets import create_dataloader_rgb_ir
 from icafusion_amd import ops
 from icafusion_amd.utils.general import check_img_size, increment_path, nms_device, scale_coords, xywh2xyxy
@@ -52,33 +42,49 @@ from icafusion_amd.utils.metrics import ConfusionMatrix, ap_per_class
 from icafusion_amd.utils.torch_utils import select_device, time_synchronized
 
 MATCH_MAX_DET = 1024                                             # detections per image icaf_match_predictions takes (nms.hip)
+IOUV = np.linspace(0.5, 0.95, 10)                                # the IoU thresholds of mAP@0.5:0.95
+
+
+# ---- the statistics of a pass -> numbers and the result table -----------------------------------------------------------------------------------
+def _numbers(nt, tp=None, fp=None, fn=None, p=None, r=None, f1=None, ap=None, ap_class=None):
+    """-> tp, fp, fn, p, r, f1, ap, ap_class, nt, (mp, mr, map50, map75, map): what summarize() formats.  Without the curves — no
+    detection, or no TP at all — every metric is 0."""
+    if ap is None:
+        return np.zeros(1), np.zeros(1), np.zeros(1), np.zeros(0), np.zeros(0), np.zeros(1), np.zeros((0, 10)), np.zeros(0, int), nt, (0.0,) * 5
+    return tp, fp, fn, p, r, f1, ap, ap_class, nt, (p.mean(), r.mean(), ap[:, 0].mean(), ap[:, 5].mean(), ap.mean())
+
+
+def host_numbers(stats, nc):
+    """The numbers of the host lists: numpy ap_per_class (utils/metrics.py) on the concatenated rows."""
+    if not stats:
+        return _numbers(np.zeros(nc, int))
+    cat = [np.concatenate([np.asarray(s[k]) for s in stats], 0) for k in range(4)]
+    nt = np.bincount(cat[3].astype(np.int64), minlength=nc)
+    if not (len(cat[0]) and cat[0].any()):
+        return _numbers(nt)
+    tp, fp, fn, p, r, ap, f1, ap_class = ap_per_class(cat[0], cat[1], cat[2], cat[3])
+    return _numbers(nt, tp, fp, fn, p, r, f1, ap, ap_class)
+
+
+def store_numbers(tcls_all, store, nc):
+    """The numbers of an ops.StatsStore: icaf_ap_per_class on the device; "no TP at all" reads the store's any_tp flag."""
+    tcls = np.concatenate([np.asarray(t, np.float64) for t in tcls_all]) if tcls_all else np.zeros(0)
+    nt = np.bincount(tcls.astype(np.int64), minlength=nc)
+    if not (store.rows() and store.any_tp()):
+        return _numbers(nt)
+    ap_class, n_l = np.unique(tcls, return_counts=True)
+    res = ops.ap_per_class_device(store, ap_class, n_l)
+    i = res["best"]
+    return _numbers(nt, res["tp"], res["fp"], res["fn"], res["p"][:, i], res["r"][:, i], res["f1"][:, i], res["ap"], ap_class.astype("int32"))
 
 
 def summarize(stats, nc, names, seen, verbose=False, store=None):
     """Statistics -> (mp, mr, map50, map, maps) + the reference's result table (test.py:287-313): for one class the columns are
     TP / FP / FN / F1 / P / R / mAP@.5 / mAP@.5:.95, otherwise P / R / mAP@.5 / mAP@.75 / mAP@.5:.95 with one row per class when
     `verbose`.  stats: list of (correct (n, 10) bool, conf (n,), pcls (n,), tcls list) per image — or, with `store` (an ops.StatsStore, the
-    `device_stats` path), the list of the images' label classes: the numbers then come from icaf_ap_per_class, and "no TP at all means
-    every metric is 0" reads the store's any_tp flag."""
-    mp = mr = map50 = map75 = map_ = 0.0
-    tp = fp = fn = f1 = np.zeros(1)
-    p = r = np.zeros(0)
-    ap, ap_class, nt = np.zeros((0, 10)), np.zeros(0, int), np.zeros(nc, int)
-    if store is not None:
-        tcls = np.concatenate([np.asarray(t, np.float64) for t in stats]) if stats else np.zeros(0)
-        if store.rows() and store.any_tp():
-            ap_class, n_l = np.unique(tcls, return_counts=True)
-            res = ops.ap_per_class_device(store, ap_class, n_l)
-            i, ap, ap_class = res["best"], res["ap"], ap_class.astype("int32")
-            tp, fp, fn, p, r, f1 = res["tp"], res["fp"], res["fn"], res["p"][:, i], res["r"][:, i], res["f1"][:, i]
-            mp, mr, map50, map75, map_ = p.mean(), r.mean(), ap[:, 0].mean(), ap[:, 5].mean(), ap.mean()
-        nt = np.bincount(tcls.astype(np.int64), minlength=nc)
-    elif stats:
-        cat = [np.concatenate([np.asarray(s[k]) for s in stats], 0) for k in range(4)]
-        if len(cat[0]) and cat[0].any():
-            tp, fp, fn, p, r, ap, f1, ap_class = ap_per_class(cat[0], cat[1], cat[2], cat[3])
-            mp, mr, map50, map75, map_ = p.mean(), r.mean(), ap[:, 0].mean(), ap[:, 5].mean(), ap.mean()
-        nt = np.bincount(cat[3].astype(np.int64), minlength=nc)
+    `device_stats` path), the list of the images' label classes."""
+    tp, fp, fn, p, r, f1, ap, ap_class, nt, (mp, mr, map50, map75, map_) = (host_numbers(stats, nc) if store is None else
+                                                                            store_numbers(stats, store, nc))
     lines = []
     if nc == 1:
         lines.append(("%20s" + "%12s" * 10) % ("Class", "Images", "Labels", "TP", "FP", "FN", "F1", "P", "R", "mAP@.5", "mAP@.5:.95"))
@@ -97,10 +103,128 @@ def summarize(stats, nc, names, seen, verbose=False, store=None):
     return (mp, mr, map50, map_), maps, lines
 
 
+# ---- one batch after the matching, and the consumers of a pass ------------------------------------------------------------------------------------
+class ValBatch:
+    """What the matching step leaves of one batch, built once and read by every consumer: paths, shapes, nb; on the device det (nb, max_det, 6),
+    count (nb,), predn (the native-space boxes; None when no consumer reads them), correct (nb, max_det, 10), lab_dev (native-space label
+    rows) and off_dev (their offsets per image); tcls_all, the label classes per image, on the host.  The host copies are taken on first
+    use and kept, so each block is read back at most once per batch however many consumers ask — and not at all when none does."""
+
+    def __init__(self, paths, shapes, nb, det, count, predn, correct, lab_dev, off_dev, tcls_all):
+        self.paths, self.shapes, self.nb, self.tcls_all = paths, shapes, nb, tcls_all
+        self.det, self.count, self.predn, self.correct, self.lab_dev, self.off_dev = det, count, predn, correct, lab_dev, off_dev
+
+    @functools.cached_property
+    def count_host(self):
+        return self.count.cpu().numpy()
+
+    @functools.cached_property
+    def conf_cls_host(self):
+        return self.det[..., 4:6].cpu().numpy()
+
+    @functools.cached_property
+    def predn_host(self):
+        return self.predn.cpu().numpy()
+
+    @functools.cached_property
+    def correct_host(self):
+        return self.correct.cpu().numpy().astype(bool)
+
+
+class HostStats:
+    """The default statistics: flags / conf / cls of every image come back and join the list summarize() hands to numpy's ap_per_class
+    (reference test.py:144-230).  `out` (test(stats_out=[...])) receives the list."""
+    store = None
+
+    def __init__(self, out):
+        self.rows, self.out = [], out
+
+    def match_options(self, tcls_all):
+        return {}
+
+    def add(self, b):
+        correct, cc, count = b.correct_host, b.conf_cls_host, b.count_host
+        for si, tcls in enumerate(b.tcls_all):
+            n = int(count[si])
+            if n:
+                self.rows.append((correct[si, :n] if tcls else np.zeros((n, 10), bool), cc[si, :n, 0], cc[si, :n, 1], tcls))
+            elif tcls:
+                self.rows.append((np.zeros((0, 10), bool), np.zeros(0), np.zeros(0), tcls))
+
+    def finish(self):
+        if isinstance(self.out, list):
+            self.out.extend(self.rows)
+
+
+class DeviceStats:
+    """`--device-stats` keeps the statistics of the pass on the device: every batch is appended to an ops.StatsStore in the host loop's
+    order, nothing is read back per batch (result files excepted), the four synchronisations per batch become event pairs (EventStopwatch),
+    and ap_per_class runs as kernels with a DEFINED order at equal confidences (arrival order; the host's np.argsort leaves it to the numpy
+    build).  `rows` holds the label classes per image; `out` (test(stats_out=[...])) receives the store."""
+
+    def __init__(self, dataloader, dev, out):
+        self.rows, self.store, self.dataloader, self.dev, self.out = [], None, dataloader, dev, out
+
+    def match_options(self, tcls_all):
+        return {"max_labels": max(len(t) for t in tcls_all)}             # spares the matching its label_off read-back
+
+    def add(self, b):
+        if self.store is None:                                           # images x max_det rows: an upper bound of the cursor, it cannot overflow
+            self.store = ops.StatsStore(len(self.dataloader.dataset) * b.det.shape[1], len(IOUV), self.dev)
+        self.store.stage(b.correct, b.det, b.count)
+        self.rows += b.tcls_all
+
+    def finish(self):
+        if isinstance(self.out, list):
+            self.out.append(self.store)
+
+
+class ResultFiles:
+    """`--save-txt` / `--save-conf` / `--save-json` leave the reference's result files (per-image `frame,x,y,w,h[,conf]` lines + `result.txt`,
+    the input of the KAIST miss-rate evaluator; `<weights>_predictions.json`) under `--project/--name` (icafusion_amd/utils/results.py).
+    They are written on the host: count, conf / cls and the native-space boxes of every batch come back for them."""
+
+    def __init__(self, dataset, save_dir, save_txt, save_conf, save_json, weights):
+        listing = label_listing(os.path.dirname(dataset.label_files[0])) if save_txt else None
+        self.writer = ResultWriter(save_dir if save_dir is not None else increment_path("runs/test/exp"), save_txt=save_txt, save_conf=save_conf,
+                                   save_json=save_json, label_names=listing, weights=weights)
+
+    def add(self, b):
+        count, cc, predn = b.count_host, b.conf_cls_host, b.predn_host
+        for si in range(b.nb):
+            n = int(count[si])
+            if n:
+                self.writer.add(b.paths[si], predn[si, :n], cc[si, :n, 0], cc[si, :n, 1])
+
+    def finish(self):
+        for f in self.writer.close():
+            if f is not None:
+                print(f"saved {f}")
+
+
+class Confusion:
+    """`--plots` builds the reference's ConfusionMatrix (test.py:103,205-206,320-321; conf 0.25 / IoU 0.45) on the device, every image of a
+    batch in one launch, prints it and saves confusion_matrix.txt (and confusion_matrix.png when matplotlib is there)."""
+
+    def __init__(self, nc, dev, names, save_dir):
+        self.matrix, self.names, self.save_dir = ConfusionMatrix(nc, device=dev), names, save_dir
+
+    def add(self, b):
+        self.matrix.process_images(b.predn, b.det, b.count, b.lab_dev, b.off_dev)
+
+    def finish(self):
+        self.matrix.print()
+        plot_dir = str(self.save_dir) if self.save_dir is not None else str(increment_path("runs/test/exp"))
+        os.makedirs(plot_dir, exist_ok=True)
+        self.matrix.plot(save_dir=plot_dir, names=list(self.names))
+
+
 class MissRate:
-    """KAIST log-average miss rate of one validation pass (`miss_rate=` / `--miss-rate`): every batch's native-space boxes are staged on
-    the device into the store the matching kernel reads (icaf_missrate_stage, at the image's position in the sorted label directory:
-    the `frame - 1` of result.txt), one icaf_missrate_match launch follows the loop, and utils.missrate.summarize runs the FPPI sweep."""
+    """KAIST log-average miss rate of one validation pass (`miss_rate=` / `--miss-rate ANNOTATIONS`; the evaluator of the reference's
+    `evaluation_script/`): every batch's native-space boxes are staged on the device into the store the matching kernel reads
+    (icaf_missrate_stage, at the image's position in the sorted label directory: the `frame - 1` of result.txt), one icaf_missrate_match
+    launch follows the loop, and utils.missrate.summarize runs the FPPI sweep in numpy.  test() returns the dict as a fourth element;
+    `--task speed` ignores the flag."""
 
     def __init__(self, ann_path, dataset, dev):
         self.table = missrate.load_annotations(ann_path)
@@ -114,12 +238,12 @@ class MissRate:
             raise ValueError(f"frame {bad + 1} is {stems[bad]} in the label directory and {self.table['im_name'][bad]} in {ann_path}")
         self.dev, self.tab, self.dt, self.count = dev, ops.missrate_table(self.table, dev), None, None
 
-    def stage(self, predn, det, count, paths):
+    def add(self, b):
         if self.dt is None:                                                     # cap = NMS's max_det
-            self.dt = torch.zeros((self.tab.images, det.shape[1], 5), dtype=torch.float64, device=self.dev)
+            self.dt = torch.zeros((self.tab.images, b.det.shape[1], 5), dtype=torch.float64, device=self.dev)
             self.count = torch.zeros((self.tab.images,), dtype=torch.int32, device=self.dev)
-        index = [frame_index(self.listing, os.path.splitext(os.path.basename(p))[0]) for p in paths]
-        ops.missrate_stage(predn, det, count, index, torch.tensor(index, dtype=torch.int32, device=self.dev), self.dt,
+        index = [frame_index(self.listing, os.path.splitext(os.path.basename(p))[0]) for p in b.paths]
+        ops.missrate_stage(b.predn, b.det, b.count, index, torch.tensor(index, dtype=torch.int32, device=self.dev), self.dt,
                            self.count)(ops.current_stream_ptr())
 
     def finish(self):
@@ -129,7 +253,132 @@ class MissRate:
         ops.missrate_match(self.tab, self.dt, self.count, *outs)(ops.current_stream_ptr())
         order, dt_gt, dt_ignore, gt_ignore = (o.cpu().numpy() for o in outs)
         dt, count = self.dt.cpu().numpy(), self.count.cpu().numpy()
-        return missrate.summarize(self.table, count, missrate.sorted_scores(dt, order, count), dt_gt, dt_ignore, gt_ignore[:self.tab.labels])
+        res = missrate.summarize(self.table, count, missrate.sorted_scores(dt, order, count), dt_gt, dt_ignore, gt_ignore[:self.tab.labels])
+        print("\n".join(missrate.format_lines(res)))
+        return res
+
+
+class ValLoss:
+    """`--hyp PATH` (or `test(compute_loss=...)`, as the reference's train.py:257,393 calls it) adds the validation loss — the forward value
+    of the reference's ComputeLoss on the raw Detect maps of every batch (utils/loss.py:325-463; icaf_loss, no gradients), averaged over the
+    batches as test.py:132-133,364-367 do, with the hyp gains scaled as train.py:238-241 scales them (loss_from_hyp) — fills the three
+    trailing values and prints one `Loss:` line; there is no default hyp file, and without the flag nothing changes.  It is fed the raw
+    maps and the unscaled targets, so it is the one consumer with a call site of its own."""
+
+    def __init__(self, compute_loss, dev, batches):
+        self.compute_loss, self.dev, self.batches = compute_loss, dev, batches
+        self.sum = torch.zeros(3, device=dev)                            # box, obj, cls: summed on the device, read once after the loop
+
+    def add(self, maps, targets):
+        self.sum += self.compute_loss(maps, targets.to(self.dev))[1][:3]
+
+    def finish(self):
+        lbox, lobj, lcls = (self.sum.cpu() / self.batches).tolist()      # test.py:364-367
+        print("Loss: %.5g box, %.5g obj, %.5g cls (mean of %d batches)" % (lbox, lobj, lcls, self.batches))
+        return lbox, lobj, lcls
+
+
+# ---- timing ------------------------------------------------------------------------------------------------------------------------------------
+class Stopwatch:
+    """Synchronised host time: start() and stop(bucket) each synchronise the device and read the host clock; totals() -> seconds per bucket."""
+
+    def __init__(self):
+        self.laps = []
+
+    def mark(self):
+        return time_synchronized()
+
+    def seconds(self, a, b):
+        return b - a
+
+    def start(self):
+        self.t0 = self.mark()
+
+    def stop(self, bucket):
+        self.laps.append((bucket, self.t0, self.mark()))
+
+    def totals(self):
+        out = collections.defaultdict(float)
+        for bucket, a, b in self.laps:
+            out[bucket] += self.seconds(a, b)
+        return out
+
+
+class EventStopwatch(Stopwatch):
+    """The same laps as events on the stream: nothing synchronises during the pass, totals() reads the pairs once it is over."""
+
+    def mark(self):
+        e = ops.Event()
+        e.record(ops.current_stream_ptr())
+        return e
+
+    def seconds(self, a, b):
+        return a.elapsed_ms(b) / 1e3
+
+
+# ---- the steps of the loop body -------------------------------------------------------------------------------------------------------------------
+def to_device(img, dev, native):
+    """One loader item on the device -> (what forward() takes, images in the batch, (height, width) of the network's input).  `native`
+    (`--device-letterbox`): the frames go up as decoded, as lists of uint8 BGR images."""
+    if native:
+        rgb, ir, (height, width) = img
+        return ([f.to(dev, non_blocking=True) for f in rgb], [f.to(dev, non_blocking=True) for f in ir]), len(rgb), (height, width)
+    img = img.to(dev, non_blocking=True)                         # uint8 (B, 6, H, W): cat(rgb, ir), test.py:116-123
+    return img, img.shape[0], (img.shape[2], img.shape[3])
+
+
+def forward(model, x, net_hw, imgsz):
+    """-> the model's outputs ([0] predictions, [2] raw Detect maps).  Native frames (`--device-letterbox`): the loader's longest-side resize
+    (pixel-area average when shrinking) and the padding run on the device (Model.forward_frames(val_size=...))."""
+    if isinstance(x, tuple):
+        return model.forward_frames(x[0], x[1], img_size=net_hw, val_size=imgsz)[0]
+    return model.forward_u8(x)
+
+
+def suppress(out, targets, nb, paths, conf_thres, iou_thres, agnostic=False, confluence=None, save_hybrid=False, merge_nms=False):
+    """Predictions -> det (nb, max_det, 6), count (nb,) on the device.  NMS, with two modes: `--save-hybrid` (test.py:137-139, 414) hands the
+    batch's pixel-space labels (`targets`) to it as apriori candidates at conf 1 and forces `--save-txt`; `--merge-nms` runs the reference's
+    merge-NMS (utils/general.py:594-600: score-weighted mean of the overlapping candidates, images with 1 < n < 3000 candidates, fp64 sums in
+    the fixed order of include/icaf.h).  `--confluence P_THRES` swaps the step for the reference's confluence (its commented line
+    test.py:140; utils/confluence.py) and leaves everything downstream as it is; neither NMS mode goes with it.  An image whose candidates
+    exceed the confluence cap, or that keeps more than MATCH_MAX_DET boxes, raises."""
+    if confluence is None:
+        lb = [targets[targets[:, 0] == si, 1:] for si in range(nb)] if save_hybrid else None
+        det, count, _ = nms_device(out, conf_thres, iou_thres, multi_label=True, agnostic=agnostic, labels=lb, merge=merge_nms)
+        return det, count
+    det, count, _ = confluence_device(out, conf_thres, confluence)
+    for si, n in enumerate(count.tolist()):                      # the matching kernel takes MATCH_MAX_DET rows per image
+        if n < 0 or n > MATCH_MAX_DET:
+            raise ValueError(f"{paths[si]}: confluence " + (f"met {-n} candidates, above its cap of {det.shape[1]}" if n < 0 else
+                                                            f"kept {n} detections, the matching takes {MATCH_MAX_DET}") +
+                             "; raise --conf-thres")
+    return det[:, :MATCH_MAX_DET].contiguous(), count
+
+
+def native_labels(targets, nb, net_hw, shapes, dev):
+    """Pixel-space targets of a batch -> lab_dev (rows of class + xyxy in native image space), off_dev (nb + 1 row offsets), scale (nb, 5:
+    gain, padw, padh, w0, h0 — what maps a detection to native space), all on the device, and tcls_all (the classes per image, host)."""
+    lab_rows, off, scale, tcls_all = [], [0], [], []
+    for si in range(nb):
+        labels = targets[targets[:, 0] == si, 1:]
+        tcls_all.append(labels[:, 0].tolist())
+        tbox = xywh2xyxy(labels[:, 1:5])
+        scale_coords(net_hw, tbox, shapes[si][0], shapes[si][1])
+        lab_rows.append(torch.cat((labels[:, :1], tbox), 1))
+        off.append(off[-1] + len(labels))
+        (h0, w0), ((gain, _), (padw, padh)) = shapes[si][0], shapes[si][1]
+        scale.append([gain, padw, padh, w0, h0])
+    return (torch.cat(lab_rows).float().contiguous().to(dev), torch.tensor(off, dtype=torch.int32, device=dev),
+            torch.tensor(scale, dtype=torch.float32, device=dev), tcls_all)
+
+
+def match(det, count, lab_dev, off_dev, scale, want_predn, **options):
+    """Statistics per image (reference test.py:144-230) on the device: one kernel maps the detections to native space (scale_coords +
+    clip_coords) and matches them against the labels -> predn (nb, max_det, 4) when a consumer wants the boxes, correct (nb, max_det, 10)."""
+    predn = torch.zeros((det.shape[0], det.shape[1], 4), dtype=torch.float32, device=det.device) if want_predn else None
+    correct = ops.match_predictions(det, count, lab_dev, off_dev, torch.from_numpy(IOUV.astype(np.float32)).to(det.device), scale=scale,
+                                    predn=predn, **options)
+    return predn, correct
 
 
 @torch.no_grad()
@@ -156,129 +405,49 @@ def test(data, weights=None, batch_size=32, imgsz=640, conf_thres=0.001, iou_thr
         # the reference passes `opt` (test.py:100), whose single_cls makes the dataset zero the label classes (utils/datasets.py:465-466)
         dataloader = create_dataloader_rgb_ir(data["val_rgb"], data["val_ir"], imgsz, batch_size, gs, argparse.Namespace(single_cls=single_cls),
                                               pad=0.5, rect=True, native=device_letterbox)[0]
-    writer = None
-    if save_txt or save_json:                                           # result files of the reference (utils/results.py)
-        listing = label_listing(os.path.dirname(dataloader.dataset.label_files[0])) if save_txt else None
-        writer = ResultWriter(save_dir if save_dir is not None else increment_path("runs/test/exp"), save_txt=save_txt, save_conf=save_conf,
-                              save_json=save_json, label_names=listing, weights=weights)
-    mr_eval = MissRate(miss_rate, dataloader.dataset, dev) if miss_rate else None
-    iouv = np.linspace(0.5, 0.95, 10)
     names = data.get("names", [str(i) for i in range(nc)])
-    stats, seen, t_inf, t_nms = [], 0, 0.0, 0.0
-    cmatrix = ConfusionMatrix(nc, device=dev) if plots else None          # test.py:103
-    store, events = None, []                                             # device_stats: the statistics stay on the device until the pass is over
-
-    def clock():                                                         # device_stats: an event on the stream instead of a synchronisation
-        if not device_stats:
-            return time_synchronized()
-        events.append(ops.Event())
-        events[-1].record(ops.current_stream_ptr())
-        return 0.0
-    loss = torch.zeros(3, device=dev) if compute_loss else None          # box, obj, cls: summed on the device, read once after the loop
+    files = ResultFiles(dataloader.dataset, save_dir, save_txt, save_conf, save_json, weights) if save_txt or save_json else None
+    mr_eval = MissRate(miss_rate, dataloader.dataset, dev) if miss_rate else None
+    cmatrix = Confusion(nc, dev, names, save_dir) if plots else None     # test.py:103
+    stats = DeviceStats(dataloader, dev, stats_out) if device_stats else HostStats(stats_out)
+    watch = EventStopwatch() if device_stats else Stopwatch()
+    loss = ValLoss(compute_loss, dev, len(dataloader)) if compute_loss else None
+    consumers = [c for c in (mr_eval, cmatrix, stats, files) if c is not None]
+    want_predn = bool(files or mr_eval or cmatrix)
+    seen = 0
     for img, targets, paths, shapes in dataloader:
-        if device_letterbox:                                     # native BGR frames as decoded: resized and padded on the device
-            rgb, ir, (height, width) = img
-            rgb, ir, nb = [f.to(dev, non_blocking=True) for f in rgb], [f.to(dev, non_blocking=True) for f in ir], len(rgb)
-            t = clock()
-            res = model.forward_frames(rgb, ir, img_size=(height, width), val_size=imgsz)[0]
-        else:
-            img = img.to(dev, non_blocking=True)                 # uint8 (B, 6, H, W): cat(rgb, ir), test.py:116-123
-            nb, _, height, width = img.shape
-            t = clock()
-            res = model.forward_u8(img)
-        out = res[0]
-        t_inf += clock() - t
-        if compute_loss:                                         # on the raw maps, before the labels go to pixels (test.py:132-133)
-            loss += compute_loss(res[2], targets.to(dev))[1][:3]
+        x, nb, (height, width) = to_device(img, dev, device_letterbox)
+        watch.start()
+        res = forward(model, x, (height, width), imgsz)
+        watch.stop("inference")
+        if loss:                                                 # on the raw maps, before the labels go to pixels (test.py:132-133)
+            loss.add(res[2], targets)
         targets = targets.clone()
         targets[:, 2:] *= torch.tensor([width, height, width, height])
-        t = clock()
-        if confluence is not None:                               # the reference's one-line swap (test.py:139-140)
-            det, count, _ = confluence_device(out, conf_thres, confluence)
-            for si, n in enumerate(count.tolist()):              # the matching kernel takes MATCH_MAX_DET rows per image
-                if n < 0 or n > MATCH_MAX_DET:
-                    raise ValueError(f"{paths[si]}: confluence " + (f"met {-n} candidates, above its cap of {det.shape[1]}" if n < 0 else
-                                                                    f"kept {n} detections, the matching takes {MATCH_MAX_DET}") +
-                                     "; raise --conf-thres")
-            det = det[:, :MATCH_MAX_DET].contiguous()
-        else:
-            # --save-hybrid: the batch's pixel-space targets join the candidates as apriori labels (reference test.py:137-139)
-            lb = [targets[targets[:, 0] == si, 1:] for si in range(nb)] if save_hybrid else None
-            det, count, _ = nms_device(out, conf_thres, iou_thres, multi_label=True, agnostic=single_cls, labels=lb, merge=merge_nms)
-        t_nms += clock() - t
-        # statistics per image (reference test.py:144-230) on the device: labels go up in native image space, one kernel
-        # maps the detections there (scale_coords + clip_coords) and matches them; only flags / conf / cls come back
+        watch.start()
+        det, count = suppress(res[0], targets, nb, paths, conf_thres, iou_thres, single_cls, confluence, save_hybrid, merge_nms)
+        watch.stop("nms")
         if single_cls:
             det[..., 5] = 0
-        lab_rows, off, scale, tcls_all = [], [0], [], []
-        for si in range(nb):
-            labels = targets[targets[:, 0] == si, 1:]
-            tcls_all.append(labels[:, 0].tolist())
-            tbox = xywh2xyxy(labels[:, 1:5])
-            scale_coords((height, width), tbox, shapes[si][0], shapes[si][1])                 # native-space labels
-            lab_rows.append(torch.cat((labels[:, :1], tbox), 1))
-            off.append(off[-1] + len(labels))
-            (h0, w0), ((gain, _), (padw, padh)) = shapes[si][0], shapes[si][1]
-            scale.append([gain, padw, padh, w0, h0])
-        predn = torch.zeros((nb, det.shape[1], 4), dtype=torch.float32, device=dev) if writer or mr_eval or cmatrix else None     # native-space boxes
-        lab_dev, off_dev = torch.cat(lab_rows).float().contiguous().to(dev), torch.tensor(off, dtype=torch.int32, device=dev)
-        correct = ops.match_predictions(det, count, lab_dev, off_dev, torch.from_numpy(iouv.astype(np.float32)).to(dev),
-                                        scale=torch.tensor(scale, dtype=torch.float32, device=dev), predn=predn,
-                                        **({"max_labels": max(len(t) for t in tcls_all)} if device_stats else {}))     # no label_off read-back
-        if mr_eval:
-            mr_eval.stage(predn, det, count, paths)
-        if cmatrix:                                              # test.py:205-206, every image of the batch in one launch
-            cmatrix.process_images(predn, det, count, lab_dev, off_dev)
-        if device_stats:                                         # nothing comes back: the rows go to the store in the host loop's order
-            if store is None:                                    # images x max_det rows: an upper bound of the cursor, it cannot overflow
-                store = ops.StatsStore(len(dataloader.dataset) * det.shape[1], len(iouv), dev)
-            store.stage(correct, det, count)
-            stats += tcls_all
-            seen += nb
-            if writer:                                           # the result files are written on the host: their rows still come back
-                cnt, cc, pn = count.cpu().numpy(), det[..., 4:6].cpu().numpy(), predn.cpu().numpy()
-                for si in range(nb):
-                    if cnt[si]:
-                        writer.add(paths[si], pn[si, :cnt[si]], cc[si, :cnt[si], 0], cc[si, :cnt[si], 1])
-            continue
-        correct, cc, count = correct.cpu().numpy().astype(bool), det[..., 4:6].cpu().numpy(), count.cpu().numpy()
-        predn = predn.cpu().numpy() if writer else None
-        for si in range(nb):
-            n, tcls = int(count[si]), tcls_all[si]
-            seen += 1
-            if writer and n:
-                writer.add(paths[si], predn[si, :n], cc[si, :n, 0], cc[si, :n, 1])
-            if n == 0:
-                if tcls:
-                    stats.append((np.zeros((0, 10), bool), np.zeros(0), np.zeros(0), tcls))
-                continue
-            stats.append((correct[si, :n] if tcls else np.zeros((n, 10), bool), cc[si, :n, 0], cc[si, :n, 1], tcls))
-    if writer:
-        result_txt, pred_json = writer.close()
-        for f in (result_txt, pred_json):
-            if f is not None:
-                print(f"saved {f}")
-    if device_stats:                                             # the event pairs of every batch, read once the pass is over
-        ms = [a.elapsed_ms(b) for a, b in zip(events[0::2], events[1::2])]
-        t_inf, t_nms = sum(ms[0::2]) / 1e3, sum(ms[1::2]) / 1e3
-    if isinstance(stats_out, list):
-        stats_out.append(store) if device_stats else stats_out.extend(stats)
-    (mp, mr, map50, map_), maps, lines = summarize(stats, nc, names, seen, verbose, store=store)
+        lab_dev, off_dev, scale, tcls_all = native_labels(targets, nb, (height, width), shapes, dev)
+        predn, correct = match(det, count, lab_dev, off_dev, scale, want_predn, **stats.match_options(tcls_all))
+        batch = ValBatch(paths, shapes, nb, det, count, predn, correct, lab_dev, off_dev, tcls_all)
+        seen += nb
+        for c in consumers:
+            c.add(batch)
+    if files:
+        files.finish()
+    stats.finish()
+    (mp, mr, map50, map_), maps, lines = summarize(stats.rows, nc, names, seen, verbose, store=stats.store)
     print("\n".join(lines))
     if cmatrix:                                                  # test.py:320-321
-        cmatrix.print()
-        plot_dir = str(save_dir) if save_dir is not None else str(increment_path("runs/test/exp"))
-        os.makedirs(plot_dir, exist_ok=True)
-        cmatrix.plot(save_dir=plot_dir, names=list(names))
-    tt = tuple(x / max(seen, 1) * 1e3 for x in (t_inf, t_nms, t_inf + t_nms)) + (imgsz, imgsz, batch_size)
+        cmatrix.finish()
+    t = watch.totals()
+    tt = tuple(x / max(seen, 1) * 1e3 for x in (t["inference"], t["nms"], t["inference"] + t["nms"])) + (imgsz, imgsz, batch_size)
     print("Speed: %.1f/%.1f/%.1f ms inference/NMS/total per %gx%g image at batch-size %g" % tt)
-    lbox, lobj, lcls = (loss.cpu() / len(dataloader)).tolist() if compute_loss else (0.0, 0.0, 0.0)       # test.py:364-367
-    if compute_loss:
-        print("Loss: %.5g box, %.5g obj, %.5g cls (mean of %d batches)" % (lbox, lobj, lcls, len(dataloader)))
+    lbox, lobj, lcls = loss.finish() if loss else (0.0, 0.0, 0.0)
     if mr_eval:
-        mr_dict = mr_eval.finish()
-        print("\n".join(missrate.format_lines(mr_dict)))
-        return (mp, mr, map50, map_, lbox, lobj, lcls), maps, tt, mr_dict
+        return (mp, mr, map50, map_, lbox, lobj, lcls), maps, tt, mr_eval.finish()
     return (mp, mr, map50, map_, lbox, lobj, lcls), maps, tt
 
 
@@ -334,24 +503,12 @@ def loss_from_hyp(path, model, nc, imgsz):
 
 def load_model(weights, cfg, nc, device, compute_dtype):
     """The model test() would build itself — the CLI needs it beforehand when a ComputeLoss is to be made from it."""
-    dev = select_device(device)
-    if weights:
-        model = attempt_load(weights, map_location="cpu")
-    else:
-        from icafusion_amd.synth import synth_state_dict
-        model = Model(cfg, nc=nc).eval()
-        model.load_state_dict(synth_state_dict(model, seed=0))
-        model = model.fuse().eval()
-    model = model.to(dev)
-    model.compute_dtype = compute_dtype
-    model.use_graph = True
-    return model
+    return load_detector(weights, cfg, select_device(device), compute_dtype, nc=nc)
 
 
 if __name__ == "__main__":
     o = parse_opt()
     print(o)
-    o.save_txt |= o.save_hybrid                                             # reference test.py:414
     if o.task not in ("val", "test", "train", "speed"):
         raise NotImplementedError(f"--task {o.task}: only val / test / train / speed are built (study = image-size sweep + plots)")
     dtype = torch.float16 if o.half else torch.bfloat16 if o.bf16 else None
@@ -361,7 +518,7 @@ if __name__ == "__main__":
             test(o.data, [w] if w else None, o.batch_size, imgsz, 0.25, 0.45, o.single_cls, device=o.device, compute_dtype=dtype, cfg=o.cfg,
                  device_letterbox=o.device_letterbox)
     else:
-        save_dir = increment_path(os.path.join(o.project, o.name), exist_ok=o.exist_ok) if (o.save_txt or o.save_json or o.plots) else None
+        save_dir = increment_path(os.path.join(o.project, o.name), exist_ok=o.exist_ok)      # a name only: test() makes it when a flag saves
         model, compute_loss = None, None
         if o.hyp:
             with open(o.data) as f:

@@ -10,6 +10,19 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(REPO, "tests", "golden")
 
 
+def val_module():
+    """The repository's test.py as a module (`import test` would find the standard library's): a fresh one per call, so the names a test
+    replaces on it stay with that test."""
+    import importlib.util
+    import sys
+    if REPO not in sys.path:
+        sys.path.insert(0, REPO)
+    spec = importlib.util.spec_from_file_location("icaf_root_test", os.path.join(REPO, "test.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
 def sample_idx(numel, tag, n=2048):
     """Same seeded sampling as tests/golden/make_golden.py."""
     g = np.random.default_rng([0x5A3917, tag])

@@ -13,20 +13,6 @@ SETS = {"MLPD": "KAIST_annotation.json.gz", "MBNet": "KAIST_annotation.json.gz",
         "synth": "synth_annotation.json.gz"}
 
 
-@functools.lru_cache(maxsize=None)
-def val_module():
-    """The repository's test.py as a module (`import test` would find the standard library's)."""
-    import importlib.util
-    import sys
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    if root not in sys.path:
-        sys.path.insert(0, root)
-    spec = importlib.util.spec_from_file_location("icaf_root_test_mr", os.path.join(root, "test.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
-
-
 def _freeze(x):
     if isinstance(x, np.ndarray):
         x.setflags(write=False)

@@ -1,16 +1,14 @@
 """Confluence without a GPU: the CPU statement of the rules (tests/confluence_ref.py) against every result recorded from the reference
 (tests/golden/confluence, README_confluence.md), the C ABI's declaration, the wrapper's refusals before any device call and the opt-in flag
 of test.py (without it the loop still calls nms_device)."""
-import importlib.util
 import json
 import os
-import sys
 
 import numpy as np
 import pytest
 import torch
 
-from helpers import REPO
+from helpers import REPO, val_module
 import confluence_ref
 from icafusion_amd import _lib, ops
 from icafusion_amd.utils import confluence as cf
@@ -32,14 +30,6 @@ def process_cases():
         none = g[n + "__none"]
         out[n] = (g[n + "__pred"], float(g[n + "__conf"]), float(g[n + "__p"]), [None if none[i] else g[f"{n}__out{i}"] for i in range(len(none))])
     return out
-
-
-def load_test_py(tag):
-    sys.path.insert(0, REPO)
-    spec = importlib.util.spec_from_file_location("icaf_root_test_" + tag, os.path.join(REPO, "test.py"))
-    val = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(val)
-    return val
 
 
 def test_fixture_set_is_complete():
@@ -124,7 +114,7 @@ def test_wrapper_refuses_cpu_tensors_and_small_conf_before_any_device_call(monke
 
 
 def test_front_ends_parse_the_flag():
-    val = load_test_py("cf_parse")
+    val = val_module()
     assert val.parse_opt([]).confluence is None and val.parse_opt(["--confluence", "0.5"]).confluence == 0.5
     import inspect
     assert inspect.signature(val.test).parameters["confluence"].default is None
@@ -145,7 +135,7 @@ class FakeModel:
 
 @pytest.mark.parametrize("flag", [None, 0.5])
 def test_validation_loop_calls_nms_unless_the_flag_is_given(monkeypatch, flag):
-    val = load_test_py("cf_loop")
+    val = val_module()
     calls = {"nms": 0, "confluence": 0}
 
     def fake_nms(out, conf_thres, iou_thres, **kw):
@@ -170,7 +160,7 @@ def test_validation_loop_calls_nms_unless_the_flag_is_given(monkeypatch, flag):
 
 
 def test_validation_loop_names_the_image_it_refuses(monkeypatch):
-    val = load_test_py("cf_refuse")
+    val = val_module()
     for bad, words in ((-5000, "met 5000 candidates"), (1025, "kept 1025 detections")):
         def fake_confluence(out, conf_thres, p_thres, bad=bad):
             return torch.zeros((2, 4096, 6)), torch.tensor([3, bad], dtype=torch.int32), None

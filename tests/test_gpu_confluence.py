@@ -10,9 +10,9 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
-from helpers import REPO, load_cfg                                         # noqa: E402
+from helpers import REPO, load_cfg, val_module                             # noqa: E402
 import confluence_ref                                                      # noqa: E402
-from test_confluence_host import load_test_py, process_cases, select_cases  # noqa: E402
+from test_confluence_host import process_cases, select_cases  # noqa: E402
 from icafusion_amd import ops                                              # noqa: E402
 from icafusion_amd.synth import synth_crowd_prediction, synth_state_dict   # noqa: E402
 from icafusion_amd.utils import confluence as cf                           # noqa: E402
@@ -175,7 +175,7 @@ def test_validation_loop_with_confluence(tmp_path, monkeypatch):
     matched equal the CPU statement applied to the decoded rows of the same forward"""
     from test_frontends import make_dataset
     from icafusion_amd.models.yolo import Model
-    val = load_test_py("cf_gpu")
+    val = val_module()
     rgb_dir, ir_dir = make_dataset(str(tmp_path / "set"), n=5, size=(96, 128), nc=2, seed=3)
     data = {"val_rgb": rgb_dir, "val_ir": ir_dir, "nc": 2, "names": ["person", "car"]}
     model = Model(load_cfg("yolov5s_Add_kaist.yaml")).eval()

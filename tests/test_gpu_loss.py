@@ -174,8 +174,8 @@ def test_validation_loop_reports_the_loss(tmp_path, device_letterbox):
     equal the mean over the batches of the CPU statement on the maps each batch produced; precision, recall, mAP and maps are those of a
     run without the loss"""
     from test_frontends import make_dataset
-    from test_confluence_host import load_test_py
-    val = load_test_py("loss_gpu")
+    from helpers import val_module
+    val = val_module()
     rgb_dir, ir_dir = make_dataset(str(tmp_path / "set"), n=4, size=(120, 128), nc=1, seed=3)
     data = {"val_rgb": rgb_dir, "val_ir": ir_dir, "nc": 1, "names": ["person"]}
     model = kaist_model()

@@ -12,7 +12,8 @@ pytestmark = pytest.mark.gpu
 import missrate_ref                                                        # noqa: E402
 from icafusion_amd import _lib, ops                                        # noqa: E402
 from icafusion_amd.utils import missrate                                   # noqa: E402
-from missrate_helpers import MR_DIR, assert_matches_golden, assert_numbers, case, table, val_module      # noqa: E402
+from helpers import val_module                                             # noqa: E402
+from missrate_helpers import MR_DIR, assert_matches_golden, assert_numbers, case, table      # noqa: E402
 
 DEV = "cuda:0"
 GUARD = 4096

@@ -192,12 +192,12 @@ def _label_boxes(root, stem, w0, h0):
 def test_validation_loop_with_save_hybrid_and_merge(tmp_path, monkeypatch):
     """test(save_hybrid=True) on two 96 x 128 pairs: the result files hold every label box at conf 1 and every label is matched at IoU 0.5
     (recall 1.0 by construction: no two labels of a class overlap beyond the NMS threshold); test(merge_nms=True) returns finite metrics"""
-    from test_confluence_host import load_test_py
+    from helpers import val_module
     from test_frontends import make_dataset
     from icafusion_amd.models.yolo import Model
     from icafusion_amd.synth import synth_state_dict
     from oracle import icaf_oracle as oracle
-    val = load_test_py("nms_modes_gpu")
+    val = val_module()
     root = str(tmp_path / "set")
     rgb_dir, ir_dir = make_dataset(root, n=2, size=(96, 128), nc=1, seed=7, mixed=False)          # five labels, IoU up to 0.33 between two of an image
     labels = {}

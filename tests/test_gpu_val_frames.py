@@ -1,7 +1,6 @@
 """Validation from native frames on the MI355X: icaf_resize_frames against resize_area_scalar + padding byte for byte (staged and direct
 path), a batch that mixes area, bilinear and copied frames in one launch against icaf_letterbox_frames, forward_frames(val_size=...)
 against forward_u8 of the batch composed on the host, and test(device_letterbox=True) against test().  Every comparison is exact."""
-import os
 import sys
 
 import numpy as np
@@ -10,7 +9,7 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
-from helpers import REPO, load_cfg                                         # noqa: E402
+from helpers import REPO, load_cfg, val_module                             # noqa: E402
 from icafusion_amd import ops                                              # noqa: E402
 from icafusion_amd.models.yolo import Model                                # noqa: E402
 from icafusion_amd.synth import synth_state_dict                           # noqa: E402
@@ -178,11 +177,8 @@ def test_validation_loop_from_native_frames_equals_the_host_loop(tmp_path, capsy
     and 96 x 64, a ragged last batch; tests/test_val_frames_host.py shows this set's bytes equal between the two area statements): the
     same return tuple, the same maps, the same --save-txt / --save-json files."""
     sys.path.insert(0, REPO)
-    import importlib.util
     from test_frontends import make_dataset
-    spec = importlib.util.spec_from_file_location("icaf_root_test_gpu_val", os.path.join(REPO, "test.py"))
-    val = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(val)
+    val = val_module()
     rgb_dir, ir_dir = make_dataset(str(tmp_path / "set"), n=5, size=(96, 128), nc=2, seed=3)
     data = {"val_rgb": rgb_dir, "val_ir": ir_dir, "nc": 2, "names": ["person", "car"]}
     model = build("yolov5s_Add_kaist.yaml", torch.bfloat16)

@@ -13,11 +13,10 @@ pytestmark = pytest.mark.gpu
 import ap_ref                                                              # noqa: E402
 import confusion_ref                                                       # noqa: E402
 import val_stats_helpers as H                                              # noqa: E402
-from helpers import load_cfg                                               # noqa: E402
+from helpers import load_cfg, val_module                                   # noqa: E402
 from icafusion_amd import _lib, ops                                        # noqa: E402
 from icafusion_amd.synth import synth_state_dict                           # noqa: E402
 from icafusion_amd.utils import metrics                                    # noqa: E402
-from missrate_helpers import val_module                                    # noqa: E402
 
 DEV = "cuda:0"
 GUARD = 4096
@@ -385,3 +384,30 @@ def test_validation_loop_on_the_device(tmp_path, monkeypatch, capsys):
         confusion_ref.process_images(m, 2, predn, det, count, labels, off)
     assert np.array_equal(made[0].matrix, m.astype(np.float64))
     assert (tmp_path / "run" / "confusion_matrix.txt").exists() or (tmp_path / "run" / "confusion_matrix.png").exists()
+
+
+def test_result_files_are_the_same_bytes_with_and_without_device_stats(tmp_path):
+    """test(save_txt, save_conf, save_json) with device_stats off and on, on the inputs of test_validation_loop_on_the_device: both write
+    the same set of files — every per-image label file, result.txt, the predictions JSON — with the same bytes, and result.txt is not
+    empty (equal empty files would prove nothing)."""
+    from test_frontends import make_dataset
+    from icafusion_amd.models.yolo import Model
+    val = val_module()
+    rgb_dir, ir_dir = make_dataset(str(tmp_path / "set"), n=5, size=(96, 128), nc=2, seed=3)
+    data = {"val_rgb": rgb_dir, "val_ir": ir_dir, "nc": 2, "names": ["person", "car"]}
+    model = Model(load_cfg("yolov5s_Add_kaist.yaml")).eval()
+    model.load_state_dict(synth_state_dict(model, 0))
+    model = model.to(DEV)
+    model.compute_dtype, model.autotune, model.use_graph = torch.bfloat16, False, True
+    files = {}
+    for device_stats in (False, True):
+        run = tmp_path / ("device" if device_stats else "host")
+        val.test(data, batch_size=2, imgsz=64, conf_thres=0.05, model=model, save_txt=True, save_conf=True, save_json=True, save_dir=run,
+                 device_stats=device_stats)
+        files[device_stats] = {str(f.relative_to(run)): f.read_bytes() for f in sorted(run.rglob("*")) if f.is_file()}
+    host, dev = files[False], files[True]
+    print({k: len(v) for k, v in host.items()})
+    assert len(host["labels/result.txt"]) > 0 and "_predictions.json" in host and len(host) >= 3
+    assert sorted(host) == sorted(dev)
+    for name in host:
+        assert host[name] == dev[name], name

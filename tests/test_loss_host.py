@@ -13,7 +13,7 @@ import pytest
 import torch
 import yaml
 
-from helpers import REPO
+from helpers import REPO, val_module
 import loss_ref
 from icafusion_amd import _lib, ops
 from icafusion_amd.utils import loss as L
@@ -171,13 +171,8 @@ def test_compute_loss_refusals_come_before_any_device_call(monkeypatch):
     assert L.loss_params(FakeLossModel().hyp, 1.0, 2)["balance"] == [4.0, 1.0] and len(L.loss_params(FakeLossModel().hyp, 1.0, 5)["balance"]) == 5
 
 
-def load_test_py(tag):
-    from test_confluence_host import load_test_py as load
-    return load(tag)
-
-
 def test_hyp_flag_and_its_scaling():
-    val = load_test_py("loss_parse")
+    val = val_module()
     assert val.parse_opt([]).hyp is None and val.parse_opt(["--hyp", "h.yaml"]).hyp == "h.yaml"
     assert inspect.signature(val.test).parameters["compute_loss"].default is None
     with open(os.path.join(GOLDEN, "hyp.scratch.yaml")) as f:
@@ -203,7 +198,6 @@ def test_validation_loop_on_cpu_reports_the_loss_of_the_cpu_statement(tmp_path, 
     mean over the batches of the statement's items on the very maps and (still normalised) targets of each batch; without compute_loss they
     are 0.0 and the metrics are the same."""
     from test_frontends import make_dataset
-    from test_result_files import _root_test_module
     from icafusion_amd.models.yolo import Model
     from icafusion_amd.synth import synth_state_dict
     from icafusion_amd.utils import datasets as D
@@ -211,7 +205,7 @@ def test_validation_loop_on_cpu_reports_the_loss_of_the_cpu_statement(tmp_path, 
     from icafusion_amd.utils.metrics import match_predictions
     sys.path.insert(0, REPO)
     from oracle import icaf_oracle as oracle
-    val = _root_test_module()
+    val = val_module()
     rgb_dir, ir_dir = make_dataset(str(tmp_path / "set"), n=3, size=(120, 128), nc=3, seed=5)
     cfg = yaml.safe_load(open(os.path.join(REPO, "models", "transformer", "yolov5s_Transfusion_FLIR.yaml")))
     model = Model(cfg)

@@ -10,10 +10,10 @@ import numpy as np
 import pytest
 
 import missrate_ref
-from helpers import REPO
+from helpers import REPO, val_module
 from icafusion_amd import _lib
 from icafusion_amd.utils import missrate
-from missrate_helpers import MR_DIR, SETS, assert_matches_golden, assert_numbers, case, table, val_module
+from missrate_helpers import MR_DIR, SETS, assert_matches_golden, assert_numbers, case, table
 
 NAMES = sorted(SETS)
 

@@ -7,7 +7,7 @@ import os
 import numpy as np
 import pytest
 
-from helpers import load_golden
+from helpers import load_golden, val_module
 from icafusion_amd.utils.general import check_img_size, increment_path, xyxy2xywh2
 from icafusion_amd.utils.results import ResultWriter, frame_index, label_listing
 
@@ -69,17 +69,9 @@ def test_path_helpers(tmp_path, capsys):
     np.testing.assert_array_equal(xyxy2xywh2(np.array([[1.0, 2.0, 5.0, 9.0]])), [[1.0, 2.0, 4.0, 7.0]])
 
 
-def _root_test_module():
-    import importlib.util
-    spec = importlib.util.spec_from_file_location("icaf_root_test", os.path.join(os.path.dirname(HERE), "test.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
-
-
 def test_summary_table_and_metrics():
     """test.py's statistics -> metrics + the reference's table layout (test.py:287-313), including the empty cases."""
-    val = _root_test_module()
+    val = val_module()
     g = np.random.default_rng(3)
     iouv_n = 10
 
@@ -121,7 +113,7 @@ def test_summary_table_and_metrics():
 
 
 def test_root_test_rejects_what_is_not_built():
-    val = _root_test_module()
+    val = val_module()
     with pytest.raises(NotImplementedError):
         val.test({"nc": 1}, augment=True)
 
@@ -142,7 +134,7 @@ def test_validation_loop_on_cpu_with_the_oracle_behind_it(tmp_path, monkeypatch)
     from icafusion_amd.utils.general import scale_coords, xywh2xyxy
     from icafusion_amd.utils.metrics import match_predictions
     from oracle import icaf_oracle as oracle
-    val = _root_test_module()
+    val = val_module()
     rgb_dir, ir_dir = make_dataset(str(tmp_path / "set"), n=3, size=(120, 128), nc=3, seed=5)
     cfg = yaml.safe_load(open(os.path.join(REPO, "models", "transformer", "yolov5s_Transfusion_FLIR.yaml")))
     sd = synth_state_dict(Model(cfg), seed=0)
@@ -289,7 +281,7 @@ def test_single_cls_reaches_the_dataset(tmp_path, monkeypatch):
     from icafusion_amd.utils.general import scale_coords
     from icafusion_amd.utils.metrics import match_predictions
     from oracle import icaf_oracle as oracle
-    val = _root_test_module()
+    val = val_module()
     rgb_dir, ir_dir = make_dataset(str(tmp_path / "set"), n=2, size=(120, 128), nc=3, seed=8)
     cfg = yaml.safe_load(open(os.path.join(REPO, "models", "transformer", "yolov5s_Transfusion_kaist.yaml")))       # nc = 1 head
     om = oracle.OracleModel(cfg, synth_state_dict(Model(cfg), seed=0))

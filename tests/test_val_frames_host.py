@@ -8,7 +8,7 @@ import numpy as np
 import pytest
 import torch
 
-from helpers import REPO, load_cfg
+from helpers import REPO, load_cfg, val_module
 from icafusion_amd import _lib, ops
 from icafusion_amd.models.yolo import Model
 from icafusion_amd.utils import datasets as D
@@ -196,10 +196,7 @@ def test_header_signature_and_flags():
     assert "utils/datasets.py:1116-1122" in block and "ICAF_RESIZE_LDS_BYTES = 20480" in block
     assert len(_lib.SIGNATURES["icaf_resize_frames"][1]) == 11
     sys.path.insert(0, REPO)
-    import importlib.util
-    spec = importlib.util.spec_from_file_location("icaf_root_test_val", os.path.join(REPO, "test.py"))
-    val = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(val)
+    val = val_module()
     assert val.parse_opt([]).device_letterbox is False and val.parse_opt(["--device-letterbox"]).device_letterbox is True
     import inspect
     assert list(inspect.signature(val.test).parameters)[-1] == "device_letterbox"

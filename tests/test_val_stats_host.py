@@ -8,7 +8,7 @@ import confusion_ref
 import val_stats_helpers as H
 from icafusion_amd import _lib
 from icafusion_amd.utils.metrics import ap_per_class
-from missrate_helpers import val_module
+from helpers import val_module
 
 
 @pytest.mark.parametrize("name", H.names("ap"))

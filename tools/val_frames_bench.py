@@ -14,7 +14,6 @@ One process, items interleaved round by round in a rotating order, medians repor
       on one CPU thread), upload of the native pair against upload of the resized batch item, kernel."""
 import argparse
 import contextlib
-import importlib.util
 import io
 import json
 import os
@@ -24,10 +23,12 @@ import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
 import numpy as np   # noqa: E402
 import torch         # noqa: E402
 import yaml          # noqa: E402
 
+from helpers import val_module                                    # noqa: E402
 from icafusion_amd import ops                                     # noqa: E402
 from icafusion_amd.models.yolo import Model                       # noqa: E402
 from icafusion_amd.synth import synth_state_dict                  # noqa: E402
@@ -114,9 +115,7 @@ def main():
 
     # ---- (b): the validation loop -----------------------------------------------------------------------------------------------------
     if not a.no_loop:
-        spec = importlib.util.spec_from_file_location("icaf_root_test_bench", os.path.join(ROOT, "test.py"))
-        val = importlib.util.module_from_spec(spec)
-        spec.loader.exec_module(val)
+        val = val_module()
         torch.set_num_threads(1)
         with tempfile.TemporaryDirectory() as td:
             g = np.random.default_rng(0)

@@ -91,13 +91,11 @@ def call_bench(dev, repeats, groups):
 
 
 def loop_bench(dev, rounds):
-    import importlib.util
+    from helpers import val_module
     from test_frontends import make_dataset
     from icafusion_amd.models.yolo import Model
     from icafusion_amd.synth import synth_state_dict
-    spec = importlib.util.spec_from_file_location("icaf_root_test_bench", os.path.join(REPO, "test.py"))
-    val = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(val)
+    val = val_module()
     with open(os.path.join(REPO, "models", "transformer", "yolov5s_Transfusion_kaist.yaml")) as f:
         cfg = yaml.safe_load(f)
     model = Model(cfg).eval()
