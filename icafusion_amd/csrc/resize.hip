@@ -1,7 +1,7 @@
 // Device resize of native VALIDATION frames (utils/datasets.py:1116-1122, load_image_rgb_ir: longest side to img_size — INTER_AREA when
 // shrinking, INTER_LINEAR when growing — then letterbox's padding), byte for byte: one launch serves a batch that mixes frames that
-// shrink (mode 1: the pixel-area average of utils.datasets.resize_area_scalar), frames that grow and frames that are copied (mode 0: the
-// bilinear arithmetic of icaf_letterbox_frames, the same device functions).  Built with fp contraction off (build.py): every product and
+// shrink (mode 1: the pixel-area average of utils.datasets.resize_area_scalar), frames that grow and frames that are copied (mode 0:
+// lb_tile of frames_core.h, the tile icaf_letterbox_frames runs).  Built with fp contraction off (build.py): every product and
 // sum rounds on its own, in the order resize_area_scalar fixes (vertical taps first, ascending, fp32 accumulator from 0).
 #include "frames_core.h"
 
@@ -9,7 +9,7 @@ namespace icaf {
 
 constexpr int RS_LDS = ICAF_RESIZE_LDS_BYTES;      // the fp32 v rows of a mode-1 sub-tile, or the source rectangle of a mode-0 tile
 constexpr int RS_NT = ICAF_RESIZE_MAX_TAPS;        // taps per output row / column whose weights are tabulated in LDS
-constexpr int RS_THREADS = LB_TX * LB_TH;          // 128: the letterbox's block (lb_rows indexes by it), two waves
+constexpr int RS_THREADS = LB_TX * LB_TH;          // 128: the letterbox's block (lb_tile and lb_rows index by it), two waves
 static_assert(RS_LDS >= LB_LDS && RS_LDS % 16 == 0, "mode-0 tiles stage their source rectangle in the same bytes");
 
 // resize_area.weights in fp64, one element: output index j covers [j s, j s + s); the weight of source pixel px is its overlap with
@@ -263,44 +263,7 @@ __global__ __launch_bounds__(RS_THREADS) void resize_frames_kernel(const unsigne
         area_tile(frame, g, lds, wy, wx, py0, px0, d, plane_stride, H, W, swap_rb, area_direct);
         return;
     }
-    // mode 0: the tile of letterbox_frames_kernel (frames.hip), statement for statement
-    const int ra = max((int)blockIdx.y * LB_TH, g.top) - g.top, rb = min(min((int)blockIdx.y * LB_TH + LB_TH, H), g.top + g.nh) - 1 - g.top;
-    const int ca = max((int)blockIdx.x * LB_TW, g.left) - g.left, cb = min(min((int)blockIdx.x * LB_TW + LB_TW, W), g.left + g.nw) - 1 - g.left;
-    LbTile t{0, 0, 0, 0};
-    bool staged = false;
-    int rows_cap, cols_cap, nvec;
-    if (ra <= rb && ca <= cb && !lb_direct && lb_budget(g, rows_cap, cols_cap, nvec)) {
-        int i0, i1, hi0, hi1;
-        float f;
-        lb_tap(ra, g.sy, g.h0, i0, i1, f);
-        lb_tap(rb, g.sy, g.h0, hi0, hi1, f);
-        t.y_lo = i0; t.nrows = hi1 - i0 + 1;
-        lb_tap(ca, g.sx, g.w0, i0, i1, f);
-        lb_tap(cb, g.sx, g.w0, hi0, hi1, f);
-        t.x_lo = i0; t.ncols = hi1 - i0 + 1;
-        staged = t.nrows <= rows_cap && t.ncols <= cols_cap;
-    }
-    if (staged) {
-        const int tid = threadIdx.y * LB_TX + threadIdx.x, lstride = nvec * 16;
-        const long long frame_bytes = (long long)g.h0 * g.pitch;
-        for (int idx = tid; idx < t.nrows * nvec; idx += RS_THREADS) {
-            const int row = idx / nvec, v = idx - row * nvec;
-            const long long a = ((((long long)(t.y_lo + row) * g.pitch + (long long)t.x_lo * g.ch) >> 4) + v) << 4;
-            u32x4 q = {0u, 0u, 0u, 0u};
-            if (a + 16 <= frame_bytes) {
-                q = *(const u32x4*)(frame + a);
-            } else {
-#pragma unroll
-                for (int k = 0; k < 16; ++k)
-                    if (a + k < frame_bytes) q[k >> 2] |= (unsigned int)frame[a + k] << (8 * (k & 3));
-            }
-            *(u32x4*)(lds + (long long)row * lstride + v * 16) = q;
-        }
-        __syncthreads();
-        lb_rows<true>(frame, g, lds, lstride, t, d, plane_stride, H, W, swap_rb);
-    } else {
-        lb_rows<false>(frame, g, lds, 0, t, d, plane_stride, H, W, swap_rb);
-    }
+    lb_tile(frame, g, lds, d, plane_stride, H, W, swap_rb, lb_direct);     // mode 0
 }
 
 }  // namespace icaf
@@ -309,15 +272,9 @@ using namespace icaf;
 
 extern "C" int icaf_resize_frames(const void* arena, const icaf_frame_geom* geom, const int* mode, int nstreams, int B, void* dst, int ctot, int H,
                                   int W, int swap_rb, icaf_stream_t s) {
-    if (!arena || !geom || !dst) return fail(ICAF_ERR_ARG, "icaf_resize_frames: null pointer");
-    if (((uintptr_t)arena & 15) || ((uintptr_t)dst & 15) || ((uintptr_t)geom & 7) || ((uintptr_t)mode & 3))
-        return fail(ICAF_ERR_ARG, "icaf_resize_frames: arena and dst must be 16-byte aligned, the geometry table 8-byte, the mode table 4-byte aligned");
-    if (nstreams < 1 || B < 1 || H < 1 || W < 1 || W % LB_PX) return fail(ICAF_ERR_ARG, "icaf_resize_frames: bad geometry (W %% 16 == 0)");
-    if (ctot < 3 * nstreams) return fail(ICAF_ERR_ARG, "icaf_resize_frames: %d modalities need ctot >= %d, got %d", nstreams, 3 * nstreams, ctot);
-    const long long gz = (long long)nstreams * B, gy = (H + LB_TH - 1) / LB_TH;
-    if (gz > 65535 || gy > 65535) return fail(ICAF_ERR_UNSUPPORTED, "icaf_resize_frames: grid %lld x %lld too large", gy, gz);
-    dim3 grid((unsigned)((W + LB_TW - 1) / LB_TW), (unsigned)gy, (unsigned)gz), block(LB_TX, LB_TH);
-    hipLaunchKernelGGL(resize_frames_kernel, grid, block, 0, S(s), (const unsigned char*)arena, geom, mode, B, ctot, H, W, (unsigned char*)dst,
+    dim3 grid;
+    if (const int rc = frames_launch_prepare("icaf_resize_frames", arena, geom, mode, dst, nstreams, B, ctot, H, W, grid)) return rc;
+    hipLaunchKernelGGL(resize_frames_kernel, grid, dim3(LB_TX, LB_TH), 0, S(s), (const unsigned char*)arena, geom, mode, B, ctot, H, W, (unsigned char*)dst,
                        swap_rb ? 1 : 0, g_opt.letterbox_direct ? 1 : 0, g_opt.area_direct ? 1 : 0);
     ICAF_LAUNCH_CHECK();
     return ICAF_OK;

@@ -597,17 +597,13 @@ class Model(HipModule):
         side to val_size (pixel-area average when shrinking, utils.datasets.resize_area_scalar byte for byte; bilinear when growing), then
         padded into img_size, the batch's letterbox shape; .scale then holds test.py's ratio_pad rows."""
         self._check_eval()
-        fr = [list(t) if isinstance(t, (list, tuple)) else [t[i] for i in range(t.shape[0])] if torch.is_tensor(t) and t.dim() == 4 else None
-              for t in (rgb, ir)]
-        if fr[0] is None or fr[1] is None or not fr[0] or len(fr[0]) != len(fr[1]):
-            raise ValueError("forward_frames expects two (B, H0, W0, ch) tensors or two equally long lists of (H0, W0, ch) tensors")
-        for f in fr[0] + fr[1]:
-            if not torch.is_tensor(f) or not f.is_cuda or f.dtype != torch.uint8 or f.dim() != 3 or f.shape[2] not in (1, 3):
-                raise ValueError("forward_frames expects cuda uint8 frames of shape (H0, W0, ch), ch = 3 or 1")
+        try:
+            *fr, shapes, _ = ops.frame_lists(rgb, ir)
+        except ValueError as e:
+            raise ValueError(f"forward_frames expects cuda uint8 frames: {e}") from None
+        if not all(f.is_cuda for f in fr[0] + fr[1]):
+            raise ValueError("forward_frames expects cuda uint8 frames (no CPU fallback exists)")
         B = len(fr[0])
-        shapes = [tuple(f.shape[:2]) for f in fr[0]]
-        if shapes != [tuple(f.shape[:2]) for f in fr[1]]:
-            raise ValueError("the RGB and IR frame of a pair must have the same size")
         H, W = (img_size, img_size) if isinstance(img_size, int) else img_size
         self._check_stride(H, W, int(self.stride.max()))
         st = self._frame_state(H, W, shapes, tuple(int(f.shape[2]) for f in fr[0] + fr[1]), fr[0][0].device, val_size)

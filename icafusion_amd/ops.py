@@ -1149,6 +1149,22 @@ FRAME_ALIGN = 256          # frames start on this boundary inside an arena (the 
 FrameGeometry = collections.namedtuple("FrameGeometry", "geom scale_host scale")
 
 
+def _geom_row(g, i, shape, fit, how):
+    """Fill descriptor row `g` for frame i of native `shape`: h0, w0, nh, nw, top, left and the fp32 tap scales sx = w0 / nw, sy = h0 / nh
+    (offset / pitch / ch stay 0 for pack_frames); returns (h0, w0).  fit(h0, w0) -> (nh, nw, place) is the caller's resize rule, `how` its
+    name in the refusal; place() -> (top, left) runs only once the resized block is known to hold a pixel."""
+    h0, w0 = (int(v) for v in shape)
+    if h0 < 1 or w0 < 1:
+        raise ValueError(f"frame {i}: empty shape {h0}x{w0}")
+    nh, nw, place = fit(h0, w0)
+    if nw < 1 or nh < 1:
+        raise ValueError(f"frame {i}: {h0}x{w0} {how} leaves no pixel ({nh}x{nw})")
+    top, left = place()
+    g["h0"], g["w0"], g["nh"], g["nw"], g["top"], g["left"] = h0, w0, nh, nw, top, left
+    g["sx"], g["sy"] = np.float32(w0 / nw), np.float32(h0 / nh)
+    return h0, w0
+
+
 def frame_geometry(shapes, new_shape, scaleup=True):
     """The letterbox of native (h0, w0) frames to `new_shape` as numbers (utils.datasets.letterbox_geometry is the one definition of r,
     new_unpad, dw / dh and the round(d -+ 0.1) split): returns (geom, scale).  geom: GEOM_DTYPE rows, one per shape — h0, w0, nh, nw,
@@ -1161,16 +1177,12 @@ def frame_geometry(shapes, new_shape, scaleup=True):
     H, W = int(new_shape[0]), int(new_shape[1])
     geom = np.zeros((len(shapes),), GEOM_DTYPE)
     scale = np.zeros((len(shapes), 5), np.float32)
-    for i, (h0, w0) in enumerate(shapes):
-        h0, w0 = int(h0), int(w0)
-        if h0 < 1 or w0 < 1:
-            raise ValueError(f"frame {i}: empty shape {h0}x{w0}")
+
+    def fit(h0, w0):
         _, (nw, nh), _, (top, _, left, _) = letterbox_geometry((h0, w0), (H, W), scaleup)
-        if nw < 1 or nh < 1:
-            raise ValueError(f"frame {i}: {h0}x{w0} letterboxed to {H}x{W} leaves no pixel ({nh}x{nw})")
-        g = geom[i]
-        g["h0"], g["w0"], g["nh"], g["nw"], g["top"], g["left"] = h0, w0, nh, nw, top, left
-        g["sx"], g["sy"] = np.float32(w0 / nw), np.float32(h0 / nh)
+        return nh, nw, lambda: (top, left)
+    for i, shape in enumerate(shapes):
+        h0, w0 = _geom_row(geom[i], i, shape, fit, f"letterboxed to {H}x{W}")
         gain = min(H / h0, W / w0)
         scale[i] = (gain, (W - w0 * gain) / 2, (H - h0 * gain) / 2, w0, h0)
     return geom, scale
@@ -1229,81 +1241,26 @@ def geom_tensor(geom, device=None, pin=False):
     return t.pin_memory() if pin else t
 
 
-def letterbox_frames(arena, geom, geom_dev, dst, swap_rb=True, c0=0, name="letterbox_frames"):
-    """Letterbox the frames of a byte arena into the uint8 (B, ctot, H, W) plan input (icaf_letterbox_frames).  arena: flat cuda uint8;
-    geom: the HOST descriptor rows (nstreams * B, entry modality * B + image) the device table `geom_dev` holds — or will hold by the
-    time the launch runs, for a table refreshed per step (validate_frames each refresh) — validated here, before any device call;
-    modality m fills channels [3m, 3m + 3)."""
-    if arena.dtype != torch.uint8 or not arena.is_contiguous() or arena.dim() != 1:
-        raise ValueError("the arena must be a flat contiguous uint8 tensor")
-    if dst.dtype != torch.uint8 or not dst.is_contiguous() or dst.dim() != 4:
-        raise ValueError("dst must be a contiguous uint8 (B, ctot, H, W) tensor")
-    B, ctot, H, W = dst.shape
-    n = len(geom)
-    if n % B or n == 0 or 3 * (n // B) > ctot:
-        raise ValueError(f"{n} descriptors for a batch of {B} images with {ctot} channels")
-    if W % 16:
-        raise ValueError(f"output width {W} must be a multiple of 16")
-    if geom_dev.numel() * geom_dev.element_size() < n * GEOM_DTYPE.itemsize:
-        raise ValueError("the device table is smaller than the descriptor rows")
-    validate_frames(geom, arena.numel(), H, W)
-    if not (arena.is_cuda and dst.is_cuda and geom_dev.is_cuda):
-        raise ValueError("arena, table and dst must be cuda tensors (no CPU fallback exists)")
-    nb = sum(int(g["h0"]) * int(g["w0"]) * int(g["ch"]) for g in geom) + n * 3 * H * W       # frames read once, planes written once
-    return Launch(lib().icaf_letterbox_frames, (arena.data_ptr(), geom_dev.data_ptr(), n // B, B, dst.data_ptr(), ctot, H, W, int(bool(swap_rb))),
-                  keep=(arena, geom_dev, dst), name=name, nbytes=nb)
+def frame_lists(rgb, ir):
+    """Native frames as callers hand them over — per modality one uint8 (B, H0, W0, ch) tensor or a list of (H0_i, W0_i, ch) tensors, ch = 3
+    or 1, a pair sharing its size — as (frames_rgb, frames_ir, shapes, uniform): the two lists of B frames, their (h0, w0), and per modality
+    whether it came as one 4-D tensor.  Anything else raises ValueError; device, batch size and channel counts are the caller's to check."""
+    uniform = tuple(torch.is_tensor(t) and t.dim() == 4 for t in (rgb, ir))
+    fr = [[t[i] for i in range(t.shape[0])] if u else list(t) if isinstance(t, (list, tuple)) else None for t, u in zip((rgb, ir), uniform)]
+    if fr[0] is None or fr[1] is None or not fr[0] or len(fr[0]) != len(fr[1]):
+        raise ValueError("native frames come as two (B, H0, W0, ch) tensors or two equally long lists of (H0, W0, ch) tensors")
+    for f in fr[0] + fr[1]:
+        if not torch.is_tensor(f) or f.dtype != torch.uint8 or f.dim() != 3 or f.shape[2] not in (1, 3):
+            raise ValueError("frames must be uint8 tensors of shape (H0, W0, ch), ch = 3 or 1")
+    shapes = [tuple(f.shape[:2]) for f in fr[0]]
+    if shapes != [tuple(f.shape[:2]) for f in fr[1]]:
+        raise ValueError("the RGB and IR frame of a pair must have the same size")
+    return fr[0], fr[1], shapes, uniform
 
 
-def val_geometry(shapes, img_size, batch_shape):
-    """The validation loader's two steps for native (h0, w0) frames as numbers (PairedValSet.__getitem__; reference utils/datasets.py:
-    1116-1122 + letterbox): returns (geom, mode, scale).  Step 1, the loader's own numbers: r = img_size / max(h0, w0), (nw, nh) =
-    (int(w0 r), int(h0 r)) unless r == 1; mode 1 (pixel-area average) for r < 1, mode 0 for r > 1 (bilinear up-scale) and r == 1 (copy).
-    Step 2, letterbox_geometry((nh, nw), batch_shape, scaleup=False), must be pure padding — what the loader's rectangular batch shapes
-    and a square img_size batch give; a frame it would resize a second time raises ValueError.  geom: GEOM_DTYPE rows as frame_geometry's
-    (offset / pitch / ch left for pack_frames); mode: int32 per row; scale: float32 (n, 5) rows {nh / h0, dw, dh, w0, h0} — scale_coords'
-    ratio_pad form, the rows test.py builds from the loader's `shapes`."""
-    from .utils.datasets import letterbox_geometry
-    if isinstance(batch_shape, int):
-        batch_shape = (batch_shape, batch_shape)
-    H, W = int(batch_shape[0]), int(batch_shape[1])
-    n = len(shapes)
-    geom, mode, scale = np.zeros((n,), GEOM_DTYPE), np.zeros((n,), np.int32), np.zeros((n, 5), np.float32)
-    for i, (h0, w0) in enumerate(shapes):
-        h0, w0 = int(h0), int(w0)
-        if h0 < 1 or w0 < 1:
-            raise ValueError(f"frame {i}: empty shape {h0}x{w0}")
-        r = img_size / max(h0, w0)
-        nh, nw = (int(h0 * r), int(w0 * r)) if r != 1 else (h0, w0)
-        if nw < 1 or nh < 1:
-            raise ValueError(f"frame {i}: {h0}x{w0} with its longest side at {img_size} leaves no pixel ({nh}x{nw})")
-        _, new_unpad, (dw, dh), (top, _, left, _) = letterbox_geometry((nh, nw), (H, W), scaleup=False)
-        if new_unpad != (nw, nh):
-            raise ValueError(f"frame {i}: {h0}x{w0} -> {nh}x{nw} does not fit the {H}x{W} batch by padding alone (letterbox would resize it to "
-                             f"{new_unpad[1]}x{new_unpad[0]})")
-        g = geom[i]
-        g["h0"], g["w0"], g["nh"], g["nw"], g["top"], g["left"] = h0, w0, nh, nw, top, left
-        g["sx"], g["sy"] = np.float32(w0 / nw), np.float32(h0 / nh)
-        mode[i] = 1 if r < 1 else 0
-        scale[i] = (nh / h0, dw, dh, w0, h0)
-    return geom, mode, scale
-
-
-def area_staged(g):
-    """The budget rule of icaf_resize_frames for one mode-1 descriptor row (include/icaf.h): True = its tiles tabulate their weights and keep
-    the fp32 rows of the vertical pass in LDS, at least two output rows at a time; False = direct path (a shrink of 7 x and more on an axis, or
-    source spans too wide for two rows)."""
-    h0, w0, nh, nw, ch = (int(g[k]) for k in ("h0", "w0", "nh", "nw", "ch"))
-    sy, sx = h0 / nh, w0 / nw
-    if int(sy) + 2 > _lib.RESIZE_MAX_TAPS or int(sx) + 2 > _lib.RESIZE_MAX_TAPS:
-        return False
-    floats = ((min(w0, int(64.0 * sx) + 2) * ch + 3) & ~3) + 4
-    return min(32, _lib.RESIZE_LDS_BYTES // (4 * floats)) >= 2
-
-
-def resize_frames(arena, geom, mode_dev, geom_dev, dst, swap_rb=True, mode=None, name="resize_frames"):
-    """letterbox_frames with a resize mode per descriptor (icaf_resize_frames): mode 0 rows are letterbox_frames' bilinear resize, mode 1
-    rows the pixel-area average of utils.datasets.resize_area_scalar, byte for byte.  mode: the HOST int rows the device table `mode_dev`
-    (int32) holds; both None = every row mode 0.  Validated here, before any device call: validate_frames, and nh <= h0, nw <= w0 for mode 1."""
+def _frames_launch(fn, arena, geom, geom_dev, dst, swap_rb, name, mode=None, mode_dev=None):
+    """The Launch of a frame kernel (`fn`: the entry point's name; icaf_resize_frames takes the mode table behind the descriptors), everything
+    validated before any device call: the tensors' layout, the tables' sizes, validate_frames, the mode rows, and last that all live on the device."""
     if arena.dtype != torch.uint8 or not arena.is_contiguous() or arena.dim() != 1:
         raise ValueError("the arena must be a flat contiguous uint8 tensor")
     if dst.dtype != torch.uint8 or not dst.is_contiguous() or dst.dim() != 4:
@@ -1331,9 +1288,68 @@ def resize_frames(arena, geom, mode_dev, geom_dev, dst, swap_rb=True, mode=None,
     if not (arena.is_cuda and dst.is_cuda and geom_dev.is_cuda and (mode_dev is None or mode_dev.is_cuda)):
         raise ValueError("arena, tables and dst must be cuda tensors (no CPU fallback exists)")
     nb = sum(int(g["h0"]) * int(g["w0"]) * int(g["ch"]) for g in geom) + n * 3 * H * W       # frames read once, planes written once
-    return Launch(lib().icaf_resize_frames, (arena.data_ptr(), geom_dev.data_ptr(), mode_dev.data_ptr() if mode_dev is not None else None,
-                                             n // B, B, dst.data_ptr(), ctot, H, W, int(bool(swap_rb))),
+    tables = (geom_dev.data_ptr(),) + ((mode_dev.data_ptr() if mode_dev is not None else None,) if fn == "icaf_resize_frames" else ())
+    return Launch(getattr(lib(), fn), (arena.data_ptr(),) + tables + (n // B, B, dst.data_ptr(), ctot, H, W, int(bool(swap_rb))),
                   keep=(arena, geom_dev, mode_dev, dst), name=name, nbytes=nb)
+
+
+def letterbox_frames(arena, geom, geom_dev, dst, swap_rb=True, c0=0, name="letterbox_frames"):
+    """Letterbox the frames of a byte arena into the uint8 (B, ctot, H, W) plan input (icaf_letterbox_frames).  arena: flat cuda uint8;
+    geom: the HOST descriptor rows (nstreams * B, entry modality * B + image) the device table `geom_dev` holds — or will hold by the
+    time the launch runs, for a table refreshed per step (validate_frames each refresh) — validated here, before any device call;
+    modality m fills channels [3m, 3m + 3)."""
+    return _frames_launch("icaf_letterbox_frames", arena, geom, geom_dev, dst, swap_rb, name)
+
+
+def val_geometry(shapes, img_size, batch_shape):
+    """The validation loader's two steps for native (h0, w0) frames as numbers (PairedValSet.__getitem__; reference utils/datasets.py:
+    1116-1122 + letterbox): returns (geom, mode, scale).  Step 1, the loader's own numbers: r = img_size / max(h0, w0), (nw, nh) =
+    (int(w0 r), int(h0 r)) unless r == 1; mode 1 (pixel-area average) for r < 1, mode 0 for r > 1 (bilinear up-scale) and r == 1 (copy).
+    Step 2, letterbox_geometry((nh, nw), batch_shape, scaleup=False), must be pure padding — what the loader's rectangular batch shapes
+    and a square img_size batch give; a frame it would resize a second time raises ValueError.  geom: GEOM_DTYPE rows as frame_geometry's
+    (offset / pitch / ch left for pack_frames); mode: int32 per row; scale: float32 (n, 5) rows {nh / h0, dw, dh, w0, h0} — scale_coords'
+    ratio_pad form, the rows test.py builds from the loader's `shapes`."""
+    from .utils.datasets import letterbox_geometry
+    if isinstance(batch_shape, int):
+        batch_shape = (batch_shape, batch_shape)
+    H, W = int(batch_shape[0]), int(batch_shape[1])
+    n = len(shapes)
+    geom, mode, scale = np.zeros((n,), GEOM_DTYPE), np.zeros((n,), np.int32), np.zeros((n, 5), np.float32)
+    for i, shape in enumerate(shapes):
+        def fit(h0, w0):
+            r = img_size / max(h0, w0)
+            nh, nw = (int(h0 * r), int(w0 * r)) if r != 1 else (h0, w0)
+
+            def place():
+                _, new_unpad, (dw, dh), (top, _, left, _) = letterbox_geometry((nh, nw), (H, W), scaleup=False)
+                if new_unpad != (nw, nh):
+                    raise ValueError(f"frame {i}: {h0}x{w0} -> {nh}x{nw} does not fit the {H}x{W} batch by padding alone (letterbox would "
+                                     f"resize it to {new_unpad[1]}x{new_unpad[0]})")
+                mode[i] = 1 if r < 1 else 0
+                scale[i] = (nh / h0, dw, dh, w0, h0)
+                return top, left
+            return nh, nw, place
+        _geom_row(geom[i], i, shape, fit, f"with its longest side at {img_size}")
+    return geom, mode, scale
+
+
+def area_staged(g):
+    """The budget rule of icaf_resize_frames for one mode-1 descriptor row (include/icaf.h): True = its tiles tabulate their weights and keep
+    the fp32 rows of the vertical pass in LDS, at least two output rows at a time; False = direct path (a shrink of 7 x and more on an axis, or
+    source spans too wide for two rows)."""
+    h0, w0, nh, nw, ch = (int(g[k]) for k in ("h0", "w0", "nh", "nw", "ch"))
+    sy, sx = h0 / nh, w0 / nw
+    if int(sy) + 2 > _lib.RESIZE_MAX_TAPS or int(sx) + 2 > _lib.RESIZE_MAX_TAPS:
+        return False
+    floats = ((min(w0, int(64.0 * sx) + 2) * ch + 3) & ~3) + 4
+    return min(32, _lib.RESIZE_LDS_BYTES // (4 * floats)) >= 2
+
+
+def resize_frames(arena, geom, mode_dev, geom_dev, dst, swap_rb=True, mode=None, name="resize_frames"):
+    """letterbox_frames with a resize mode per descriptor (icaf_resize_frames): mode 0 rows are letterbox_frames' bilinear resize, mode 1
+    rows the pixel-area average of utils.datasets.resize_area_scalar, byte for byte.  mode: the HOST int rows the device table `mode_dev`
+    (int32) holds; both None = every row mode 0.  Validated here, before any device call: validate_frames, and nh <= h0, nw <= w0 for mode 1."""
+    return _frames_launch("icaf_resize_frames", arena, geom, geom_dev, dst, swap_rb, name, mode, mode_dev)
 
 
 def scale_detections(det, count, scale, out=None, round=False, name="scale_detections"):

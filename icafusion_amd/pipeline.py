@@ -196,20 +196,15 @@ class DetectionPipeline:
         if f is None:
             raise ValueError("DetectionPipeline(frames=(max_h0, max_w0)) takes native frames")
         B, chans = f["B"], f["chans"]
+        *lists, shapes, uniform = ops.frame_lists(rgb, ir)
+        if len(shapes) != B:
+            raise ValueError(f"submit_frames expects a batch of {B} pairs, got {len(shapes)}")
         mods, contiguous = [], []
-        for m, t in enumerate((rgb, ir)):
-            uniform = torch.is_tensor(t) and t.dim() == 4
-            fr = [t[i] for i in range(t.shape[0])] if uniform else list(t) if isinstance(t, (list, tuple)) else None
-            if fr is None or len(fr) != B:
-                raise ValueError(f"submit_frames expects (B, H0, W0, ch) tensors or lists of (H0, W0, ch) tensors for a batch of {B}")
-            for x in fr:
-                if not torch.is_tensor(x) or x.dtype != torch.uint8 or x.dim() != 3 or x.shape[2] != chans[m]:
-                    raise ValueError(f"modality {m}: frames must be uint8 (H0, W0, {chans[m]}) tensors")
-            contiguous.append(bool(uniform and t.is_contiguous() and (t[0].numel() % 16 == 0)))
+        for m, (t, fr) in enumerate(zip((rgb, ir), lists)):
+            if any(x.shape[2] != chans[m] for x in fr):
+                raise ValueError(f"modality {m}: frames must be uint8 (H0, W0, {chans[m]}) tensors")
+            contiguous.append(bool(uniform[m] and t.is_contiguous() and (t[0].numel() % 16 == 0)))
             mods.append((t, fr))
-        shapes = [tuple(x.shape[:2]) for x in mods[0][1]]
-        if shapes != [tuple(x.shape[:2]) for x in mods[1][1]]:
-            raise ValueError("the RGB and IR frame of a pair must have the same size")
         table, geom = self._frame_table(shapes, tuple(contiguous))        # raises before anything is enqueued
         pi = self.n % self.nplans
         fs = self.fwd_streams[pi % self.depth]

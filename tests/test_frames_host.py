@@ -137,6 +137,38 @@ def test_forward_frames_rejects_what_forward_u8_rejects():
         m.forward_frames(f[0], f[0], 64)                                  # not a batch
 
 
+def test_frame_lists_parses_and_refuses():
+    """ops.frame_lists, the one parser of forward_frames and submit_frames: a 4-D pair and a ragged list come back as frame lists with their
+    shapes and the per-modality `uniform` flag; every other form of input is a ValueError."""
+    def u8(*shape):
+        return torch.zeros(shape, dtype=torch.uint8)
+    rgb, ir = u8(2, 48, 64, 3), u8(2, 48, 64, 1)
+    fr, fi, shapes, uniform = ops.frame_lists(rgb, ir)
+    assert shapes == [(48, 64), (48, 64)] and uniform == (True, True)
+    assert [tuple(f.shape) for f in fr] == [(48, 64, 3)] * 2 and [tuple(f.shape) for f in fi] == [(48, 64, 1)] * 2
+    assert fr[1].data_ptr() == rgb[1].data_ptr() and fi[1].data_ptr() == ir[1].data_ptr()          # views, not copies
+    ragged = [u8(48, 64, 3), u8(9, 31, 3)]
+    fr, fi, shapes, uniform = ops.frame_lists(ragged, (u8(48, 64, 1), u8(9, 31, 1)))
+    assert shapes == [(48, 64), (9, 31)] and uniform == (False, False) and fr[1] is ragged[1] and len(fi) == 2
+    assert ops.frame_lists(rgb, [ir[0], ir[1]])[3] == (True, False)                                # one modality as a tensor, one as a list
+    for bad_rgb, bad_ir, match in [
+            (rgb[0], ir[0], "two"),                                   # 3-D tensors: not a batch
+            (rgb, None, "two"),
+            ([], [], "two"),                                          # empty lists
+            (u8(0, 48, 64, 3), u8(0, 48, 64, 1), "two"),              # an empty batch
+            (rgb, [ir[0]], "equally long"),
+            (ragged, ragged[:1], "equally long"),
+            (rgb.float(), ir, "uint8"),
+            ([u8(48, 64, 3), np.zeros((48, 64, 3), np.uint8)], ragged, "uint8"),       # not a tensor
+            ([u8(48, 64)], [u8(48, 64)], r"\(H0, W0, ch\)"),          # a frame without its channel axis
+            (u8(2, 48, 64, 2), ir, "ch = 3 or 1"),
+            (u8(2, 48, 64, 4), ir, "ch = 3 or 1"),
+            (rgb, u8(2, 48, 60, 1), "same size"),
+            (ragged, ragged[::-1], "same size")]:
+        with pytest.raises(ValueError, match=match):
+            ops.frame_lists(bad_rgb, bad_ir)
+
+
 def test_device_letterbox_flag_parses():
     sys.path.insert(0, REPO)
     import detect_twostream as dt

@@ -7,7 +7,9 @@ One process, items interleaved round by round in a rotating order, medians repor
   (a) letterbox_staged / letterbox_direct   icaf_letterbox_frames alone on its two paths (HIP event pairs around --inner launches), with
       its algorithmic bytes (frames read once, planes written once) over the time; the same pair for frames that really are resized
       (--resize-frame, default 384x480: the KAIST frame at 640 is a copy between pads); upsample_nearest at a comparable byte volume is
-      the project's streaming yardstick
+      the project's streaming yardstick.  Each of the four has two companions on the same arena and descriptors: `<item>_again`, a second
+      copy of the launch (the A/A spread), and `resize_null_<path>[_resize]`, icaf_resize_frames without a mode table — the other kernel
+      that runs the same tile (`tile_ab`: is its median within the letterbox's median plus that spread?)
   (b) scale_detections alone
   (c) the host-fed pipeline at depth 2: submit_frames from pinned native frames against submit_u8 from pinned host-letterboxed batches,
       and a SECOND copy of the submit_u8 configuration for the A/A spread of the call (wall clock around --steps submits + synchronize)
@@ -37,15 +39,20 @@ def median(v):
 
 
 def letterbox_launch(B, shape, size, dev, seed):
-    """(launch, geom) of a two-modality batch of B random BGR frames of one shape, in a tight arena."""
+    """((letterbox, letterbox again, resize without a mode table), geom) of a two-modality batch of B random BGR frames of one shape, in a
+    tight arena: three launches on the same arena and device table, each into planes of its own."""
     h0, w0 = shape
     geom1, _ = ops.frame_geometry([shape] * B, size)
     geom = np.concatenate((geom1, geom1))
     end = ops.pack_frames(geom, 3)
     g = torch.Generator().manual_seed(seed)
     arena = torch.randint(0, 256, (end,), dtype=torch.uint8, generator=g).to(dev)
-    dst = torch.zeros((B, 6, size, size), dtype=torch.uint8, device=dev)
-    return ops.letterbox_frames(arena, geom, ops.geom_tensor(geom, dev), dst, swap_rb=True), geom
+    tab = ops.geom_tensor(geom, dev)
+
+    def planes():
+        return torch.zeros((B, 6, size, size), dtype=torch.uint8, device=dev)
+    return (ops.letterbox_frames(arena, geom, tab, planes(), swap_rb=True), ops.letterbox_frames(arena, geom, tab, planes(), swap_rb=True),
+            ops.resize_frames(arena, geom, None, tab, planes(), swap_rb=True)), geom
 
 
 def main():
@@ -68,8 +75,8 @@ def main():
     sp = ops.current_stream_ptr()
 
     # ---- (a) + (b): kernels alone -------------------------------------------------------------------------------------------------
-    lb, geom = letterbox_launch(B, frame, S, dev, 1)
-    lbr, geomr = letterbox_launch(B, rframe, S, dev, 2)
+    (lb, lb2, rn), geom = letterbox_launch(B, frame, S, dev, 1)
+    (lbr, lbr2, rnr), geomr = letterbox_launch(B, rframe, S, dev, 2)
     up = ops.upsample_nearest(torch.randn((B, 80, 80, 64), device=dev).to(dt), torch.empty((B, 160, 160, 64), dtype=dt, device=dev), 2)
     det = torch.rand((B, 300, 6), device=dev) * S
     count = torch.full((B,), 300, dtype=torch.int32, device=dev)
@@ -84,6 +91,12 @@ def main():
              "upsample_nearest": up, "scale_detections": sd}
     nbytes = {"letterbox_staged": lb.bytes, "letterbox_direct": lb.bytes, "letterbox_staged_resize": lbr.bytes, "letterbox_direct_resize": lbr.bytes,
               "upsample_nearest": up.bytes, "scale_detections": sd.bytes}
+    cells = {"letterbox_staged": ("resize_null_staged", lb2, rn), "letterbox_direct": ("resize_null_direct", direct(lb2), direct(rn)),
+             "letterbox_staged_resize": ("resize_null_staged_resize", lbr2, rnr),
+             "letterbox_direct_resize": ("resize_null_direct_resize", direct(lbr2), direct(rnr))}
+    for cell, (null, again, other) in cells.items():
+        items[cell + "_again"], items[null] = again, other
+        nbytes[cell + "_again"] = nbytes[null] = nbytes[cell]
     names = list(items)
     e0, e1 = ops.Event(), ops.Event()
     times = {n: [] for n in names}
@@ -100,11 +113,16 @@ def main():
     kern = {n: {"ms": median(v), "ms_min_max": [min(v), max(v)], "algorithmic_bytes": int(nbytes[n]),
                 "GB_per_s": nbytes[n] / (median(v) * 1e-3) / 1e9} for n, v in times.items()}
     yard = kern["upsample_nearest"]["GB_per_s"]
+    tile_ab = {}
+    for cell, (null, _, _) in cells.items():
+        ms, again, other = kern[cell]["ms"], kern[cell + "_again"]["ms"], kern[null]["ms"]
+        tile_ab[cell] = {"letterbox_ms": ms, "letterbox_again_ms": again, "resize_null_ms": other, "limit_ms": ms + abs(ms - again),
+                         "within": bool(other <= ms + abs(ms - again))}
     res = {"model": f"yolov5{a.model}_Transfusion_kaist", "dtype": a.dtype, "batch": B, "size": S, "frame": list(frame), "resize_frame": list(rframe),
            "device": ops.device_info(),
            "timing": f"kernels: HIP events around {a.inner} launches, median of {a.rounds} interleaved rounds after {a.warmup}; pipelines: wall clock "
                      f"around {a.steps} submits + synchronize, same rounds, interleaved",
-           "kernels": kern, "staged_default_by_budget_rule": [bool(ops.letterbox_staged(geom[0])), bool(ops.letterbox_staged(geomr[0]))],
+           "kernels": kern, "tile_ab": tile_ab, "staged_default_by_budget_rule": [bool(ops.letterbox_staged(geom[0])), bool(ops.letterbox_staged(geomr[0]))],
            "staged_over_direct": kern["letterbox_direct"]["ms"] / kern["letterbox_staged"]["ms"],
            "staged_over_direct_resize": kern["letterbox_direct_resize"]["ms"] / kern["letterbox_staged_resize"]["ms"],
            "letterbox_over_yardstick": kern["letterbox_staged"]["GB_per_s"] / yard,
