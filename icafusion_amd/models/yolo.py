@@ -585,7 +585,7 @@ class Model(HipModule):
             raise ValueError("forward_u8 expects a cuda uint8 tensor of shape (B, 6, H, W)")
         return self._forward_images((img6,), u8=True, augment=augment)
 
-    def forward_frames(self, rgb, ir, img_size=640, bgr=True, augment=False, val_size=None):
+    def forward_frames(self, rgb, ir, img_size=640, bgr=True, augment=False, val_size=None, formats=None, yuv_matrix="bt601"):
         """Forward from NATIVE camera frames: rgb / ir are cuda uint8 tensors (B, H0, W0, ch) in decoder layout (interleaved, ch = 3 or
         1) or lists of (H0_i, W0_i, ch) tensors for ragged sizes; a pair shares its size.  The letterbox to img_size (an int or (H, W);
         utils.datasets.letterbox, byte for byte) runs on the device straight into the uint8 plan's input, then the plan (or the TTA plan)
@@ -595,8 +595,15 @@ class Model(HipModule):
         copied into an arena owned by the model; after the first call of a set of shapes nothing is allocated.
         val_size (an int): the VALIDATION loader's geometry instead (PairedValSet; ops.val_geometry(shapes, val_size, img_size)) — longest
         side to val_size (pixel-area average when shrinking, utils.datasets.resize_area_scalar byte for byte; bilinear when growing), then
-        padded into img_size, the batch's letterbox shape; .scale then holds test.py's ratio_pad rows."""
+        padded into img_size, the batch's letterbox shape; .scale then holds test.py's ratio_pad rows.
+        formats=(fmt_rgb, fmt_ir): a modality that arrives as YUV 4:2:0 names its layout, "nv12" | "nv21" | "i420" | "yv12" (None: the
+        interleaved frames above), and is handed over as the contiguous buffer a decoder returns — one uint8 (B, 3 * H0 // 2, W0) tensor
+        or a list of (3 * H0_i // 2, W0_i) tensors, H0 and W0 even; the frame size comes from the other modality, or from the buffers when
+        both are YUV.  yuv_matrix: "bt601" | "bt709" | "bt601-full" (or 0 / 1 / 2).  The colour conversion runs inside the letterbox
+        (icaf_letterbox_yuv_frames); the result is bit-identical to forward_u8 of letterbox(utils.datasets.yuv420_to_bgr(...))."""
         self._check_eval()
+        if formats is not None and any(f is not None for f in formats):
+            return self._forward_yuv_frames(rgb, ir, img_size, bgr, augment, val_size, formats, yuv_matrix)
         try:
             *fr, shapes, _ = ops.frame_lists(rgb, ir)
         except ValueError as e:
@@ -618,6 +625,45 @@ class Model(HipModule):
         for g, f in zip(st["geom"], fr[0] + fr[1]):
             o, n = int(g["offset"]), f.numel()
             st["arena"][o:o + n].view(f.shape).copy_(f)
+        st["launch"].args = st["launch"].args[:-1] + (int(bool(bgr)),)
+        st["launch"](ops.current_stream_ptr())
+        plan.run()
+        out = self._result(plan.outputs)
+        return ((out, None) if augment else out), st["info"]
+
+    def _forward_yuv_frames(self, rgb, ir, img_size, bgr, augment, val_size, formats, yuv_matrix):
+        """forward_frames with at least one YUV 4:2:0 modality: the same steps around icaf_letterbox_yuv_frames and its 80-byte rows."""
+        if val_size is not None:
+            raise ValueError("forward_frames: YUV 4:2:0 frames have no validation geometry (val_size); the area down-scale reads interleaved frames")
+        matrix = ops.yuv_matrix_code(yuv_matrix)
+        try:
+            *fr, shapes, _ = ops.yuv_frame_lists(rgb, ir, formats)
+        except ValueError as e:
+            raise ValueError(f"forward_frames expects cuda uint8 frames: {e}") from None
+        if not all(f.is_cuda for f in fr[0] + fr[1]):
+            raise ValueError("forward_frames expects cuda uint8 frames (no CPU fallback exists)")
+        B, device = len(fr[0]), fr[0][0].device
+        H, W = (img_size, img_size) if isinstance(img_size, int) else img_size
+        self._check_stride(H, W, int(self.stride.max()))
+        layouts = tuple(fmt if fmt is not None else int(f.shape[2]) for fmt, frames in zip(formats, fr) for f in frames)
+        key = (H, W, tuple(shapes), layouts, matrix, device)
+        states = self.__dict__.setdefault("_frame_states", {})
+        st = states.pop(key, None)
+        if st is None:
+            geom1, scale = ops.frame_geometry(shapes, (H, W))
+            geom, nbytes = ops.pack_yuv_frames(np.concatenate((geom1, geom1)), layouts, matrix=matrix)
+            st = {"geom": geom, "geom_dev": ops.geom_tensor(geom, device), "arena": torch.zeros((nbytes,), dtype=torch.uint8, device=device),
+                  "info": ops.FrameGeometry(geom, scale, torch.from_numpy(scale).to(device)), "dst": None, "launch": None}
+            while len(states) >= 8:
+                states.pop(next(iter(states)))
+        states[key] = st
+        plan = (self.tta_plan_for if augment else self.plan_for)(B, H, W, device, u8=True)
+        dst = plan.inputs[0]
+        if st["dst"] is not dst:
+            st["launch"] = ops.letterbox_yuv_frames(st["arena"], st["geom"], st["geom_dev"], dst, swap_rb=bgr)
+            st["dst"] = dst
+        for o, f in zip(st["geom"]["g"]["offset"], fr[0] + fr[1]):        # a YUV buffer is one run of bytes: luma rows, then its chroma
+            st["arena"][int(o):int(o) + f.numel()].view(f.shape).copy_(f)
         st["launch"].args = st["launch"].args[:-1] + (int(bool(bgr)),)
         st["launch"](ops.current_stream_ptr())
         plan.run()

@@ -15,7 +15,7 @@ import torch
 
 from . import _lib
 from .options import OPT
-from ._lib import BneckArgs, ConvArgs, DmffArgs, FrameGeom, Stem2Args, check, lib, F32, BF16, F16, ACT_NONE, ACT_SILU, ACT_GELU, ACT_RELU  # noqa: F401
+from ._lib import BneckArgs, ConvArgs, DmffArgs, FrameGeom, Stem2Args, YuvGeom, check, lib, F32, BF16, F16, ACT_NONE, ACT_SILU, ACT_GELU, ACT_RELU  # noqa: F401
 from ._lib import CONFLUENCE_MAX_CAND, LOSS_MAX_LEVELS, LOSS_MAX_ANCHORS, LOSS_MAX_TARGETS, LOSS_SLOT_INTS  # noqa: F401
 
 _DT = {torch.float32: F32, torch.bfloat16: BF16, torch.float16: F16}
@@ -1258,21 +1258,27 @@ def frame_lists(rgb, ir):
     return fr[0], fr[1], shapes, uniform
 
 
-def _frames_launch(fn, arena, geom, geom_dev, dst, swap_rb, name, mode=None, mode_dev=None):
-    """The Launch of a frame kernel (`fn`: the entry point's name; icaf_resize_frames takes the mode table behind the descriptors), everything
-    validated before any device call: the tensors' layout, the tables' sizes, validate_frames, the mode rows, and last that all live on the device."""
+def _frames_tensors(arena, dst, n, geom_dev, row_bytes):
+    """What every frame kernel asks of its tensors, for `n` descriptor rows of `row_bytes` each: returns dst's (B, ctot, H, W)."""
     if arena.dtype != torch.uint8 or not arena.is_contiguous() or arena.dim() != 1:
         raise ValueError("the arena must be a flat contiguous uint8 tensor")
     if dst.dtype != torch.uint8 or not dst.is_contiguous() or dst.dim() != 4:
         raise ValueError("dst must be a contiguous uint8 (B, ctot, H, W) tensor")
     B, ctot, H, W = dst.shape
-    n = len(geom)
     if n % B or n == 0 or 3 * (n // B) > ctot:
         raise ValueError(f"{n} descriptors for a batch of {B} images with {ctot} channels")
     if W % 16:
         raise ValueError(f"output width {W} must be a multiple of 16")
-    if geom_dev.numel() * geom_dev.element_size() < n * GEOM_DTYPE.itemsize:
+    if geom_dev.numel() * geom_dev.element_size() < n * row_bytes:
         raise ValueError("the device table is smaller than the descriptor rows")
+    return B, ctot, H, W
+
+
+def _frames_launch(fn, arena, geom, geom_dev, dst, swap_rb, name, mode=None, mode_dev=None):
+    """The Launch of a frame kernel (`fn`: the entry point's name; icaf_resize_frames takes the mode table behind the descriptors), everything
+    validated before any device call: the tensors' layout, the tables' sizes, validate_frames, the mode rows, and last that all live on the device."""
+    n = len(geom)
+    B, ctot, H, W = _frames_tensors(arena, dst, n, geom_dev, GEOM_DTYPE.itemsize)
     if (mode is None) != (mode_dev is None):
         raise ValueError("the mode table needs its host rows and its device copy, or neither (all rows mode 0)")
     if mode is not None:
@@ -1299,6 +1305,161 @@ def letterbox_frames(arena, geom, geom_dev, dst, swap_rb=True, c0=0, name="lette
     time the launch runs, for a table refreshed per step (validate_frames each refresh) — validated here, before any device call;
     modality m fills channels [3m, 3m + 3)."""
     return _frames_launch("icaf_letterbox_frames", arena, geom, geom_dev, dst, swap_rb, name)
+
+
+# native YUV 4:2:0 frames: one row per (modality, image) in the layout of icaf_yuv_geom (include/icaf.h) — field "g" is a GEOM_DTYPE row
+YUV_GEOM_DTYPE = np.dtype(YuvGeom)
+assert YUV_GEOM_DTYPE.itemsize == C.sizeof(YuvGeom) == 80 and YUV_GEOM_DTYPE["g"] == GEOM_DTYPE
+YUV_LAYOUTS = {"nv12": (2, 0), "nv21": (2, 1), "i420": (1, 0), "yv12": (1, 1)}      # layout -> (c_step, Cr stored first)
+YUV_MATRICES = {"bt601": 0, "bt709": 1, "bt601-full": 2}
+
+
+def yuv_matrix_code(matrix):
+    """0 / 1 / 2 of icaf_yuv_geom.matrix from the value itself or its name (bt601, bt709, bt601-full); ValueError for anything else."""
+    code = YUV_MATRICES.get(matrix, matrix) if isinstance(matrix, str) else matrix
+    if code not in (0, 1, 2) or isinstance(code, bool):
+        raise ValueError(f"unknown YUV matrix {matrix!r} (0 / 'bt601', 1 / 'bt709', 2 / 'bt601-full')")
+    return int(code)
+
+
+def pack_yuv_frames(geom, layouts, pitch=None, c_pitch=None, matrix=0, base=0):
+    """pack_frames for tables that hold YUV 4:2:0 surfaces: returns (rows, end) — YUV_GEOM_DTYPE rows around `geom` (frame_geometry's
+    GEOM_DTYPE rows, or YUV rows whose "g" is filled) and the first free byte behind the frames.  layouts: per row, or one for all,
+    "nv12" | "nv21" | "i420" | "yv12" (a kind-1 row) or 3 / 1 (a kind-0 row, laid out exactly as pack_frames lays it out).  A YUV frame
+    is laid out as a decoder hands it over: h0 luma rows of `pitch` bytes (default w0), directly behind them ceil(h0 / 2) chroma rows of
+    `c_pitch` bytes (default: ceil(w0 / 2) samples, tight) — one plane of CbCr / CrCb pairs, or the Cb and the Cr plane (i420) / Cr and
+    Cb (yv12) one behind the other.  Frames start on FRAME_ALIGN boundaries from `base` on."""
+    n = len(geom)
+    rows = np.zeros((n,), YUV_GEOM_DTYPE)
+    rows["g"] = geom if geom.dtype == GEOM_DTYPE else geom["g"]
+    per_row = lambda v: [v] * n if v is None or isinstance(v, (int, str)) else list(v)
+    code = yuv_matrix_code(matrix)
+    off = int(base)
+    for i, (q, lay, p, cp) in enumerate(zip(rows, per_row(layouts), per_row(pitch), per_row(c_pitch))):
+        g = q["g"]
+        off = -(-off // FRAME_ALIGN) * FRAME_ALIGN
+        h0, w0 = int(g["h0"]), int(g["w0"])
+        if lay in (1, 3):
+            g["offset"], g["ch"], g["pitch"] = off, lay, w0 * lay if p is None else int(p)
+            off += h0 * int(g["pitch"])
+            continue
+        if lay not in YUV_LAYOUTS:
+            raise ValueError(f"frame {i}: unknown layout {lay!r} (3, 1 or one of {', '.join(YUV_LAYOUTS)})")
+        step, cr_first = YUV_LAYOUTS[lay]
+        chh, cw = (h0 + 1) // 2, (w0 + 1) // 2
+        g["offset"], g["ch"], g["pitch"] = off, 1, w0 if p is None else int(p)
+        q["kind"], q["matrix"], q["c_step"], q["c_pitch"] = 1, code, step, cw * step if cp is None else int(cp)
+        first = off + h0 * int(g["pitch"])
+        second = first + 1 if step == 2 else first + chh * int(q["c_pitch"])
+        q["cb_offset"], q["cr_offset"] = (second, first) if cr_first else (first, second)
+        off = first + (1 if step == 2 else 2) * chh * int(q["c_pitch"])
+    return rows, off
+
+
+def yuv_letterbox_staged(q):
+    """The budget rule of icaf_letterbox_yuv_frames for one table row (include/icaf.h): True = its tiles stage the luma rectangle and the
+    chroma samples under it in LDS, False = they tap global memory.  A kind-0 row follows letterbox_staged."""
+    g = q["g"]
+    if int(q["kind"]) == 0:
+        return letterbox_staged(g)
+    sx, sy = np.float32(g["sx"]), np.float32(g["sy"])
+    if not (sx < 1024 and sy < 1024):
+        return False
+    h0, w0, step = int(g["h0"]), int(g["w0"]), int(q["c_step"])
+    rows = min(h0, int(np.float32(32) * sy) + 4)
+    cols = min(w0, int(np.float32(64) * sx) + 4)
+    crows, ccols = min((h0 + 1) // 2, rows // 2 + 1), min((w0 + 1) // 2, cols // 2 + 1)
+    vectors = rows * ((cols + 30) >> 4) + (1 if step == 2 else 2) * crows * ((ccols * step + 30) >> 4)
+    return vectors * 16 <= _lib.YUV_LDS_BYTES
+
+
+def validate_yuv_frames(geom, arena_bytes, H, W):
+    """validate_frames for YUV_GEOM_DTYPE rows: raises ValueError with the row and the reason — everything validate_frames refuses of
+    "g", an unknown kind, and for kind-1 rows a ch that is not 1, a c_step that is not 1 or 2, an unknown matrix, a c_pitch too small for
+    ceil(w0 / 2) samples, interleaved chroma whose offsets are not one byte apart, chroma planes that leave the arena.  The kernel trusts
+    the table — nothing reaches the device before this has passed."""
+    for i, q in enumerate(geom):
+        if int(q["kind"]) not in (0, 1):
+            raise ValueError(f"frame {i}: kind {int(q['kind'])} (0 = interleaved row, 1 = YUV 4:2:0)")
+    validate_frames(geom["g"], arena_bytes, H, W)
+    for i, q in enumerate(geom):
+        if int(q["kind"]) == 0:
+            continue
+        g = q["g"]
+        cb, cr, cp, step, matrix = (int(q[k]) for k in ("cb_offset", "cr_offset", "c_pitch", "c_step", "matrix"))
+        chh, cw = (int(g["h0"]) + 1) // 2, (int(g["w0"]) + 1) // 2
+        if int(g["ch"]) != 1:
+            raise ValueError(f"frame {i}: a YUV 4:2:0 row describes its Y plane with ch 1, got {int(g['ch'])}")
+        if step not in (1, 2):
+            raise ValueError(f"frame {i}: c_step {step} (2 = interleaved chroma, 1 = planar)")
+        if matrix not in (0, 1, 2):
+            raise ValueError(f"frame {i}: matrix {matrix} (0 = BT.601, 1 = BT.709, 2 = BT.601 full range)")
+        if cp < cw * step:
+            raise ValueError(f"frame {i}: c_pitch {cp} is less than a chroma row of {cw} samples x {step} bytes")
+        if step == 2 and abs(cb - cr) != 1:
+            raise ValueError(f"frame {i}: interleaved chroma needs cb_offset and cr_offset one byte apart, got {cb} / {cr}")
+        for name, o in (("Cb", cb), ("Cr", cr)):
+            end = o + (chh - 1) * cp + (cw - 1) * step + 1
+            if o < 0 or end > arena_bytes:
+                raise ValueError(f"frame {i}: {name} bytes [{o}, {end}) leave the arena of {arena_bytes} bytes")
+
+
+def letterbox_yuv_frames(arena, geom, geom_dev, dst, swap_rb=True, name="letterbox_yuv_frames"):
+    """letterbox_frames for tables with YUV 4:2:0 rows (icaf_letterbox_yuv_frames): kind-1 rows are converted at the bilinear taps and
+    equal letterbox(yuv420_to_bgr(...)) byte for byte (planes R, G, B; swap_rb is not read for them), kind-0 rows are letterbox_frames'
+    own.  geom: the HOST YUV_GEOM_DTYPE rows the device table `geom_dev` holds, validated here, before any device call."""
+    if geom.dtype != YUV_GEOM_DTYPE:
+        raise ValueError("the descriptor rows must be YUV_GEOM_DTYPE rows (pack_yuv_frames)")
+    n = len(geom)
+    B, ctot, H, W = _frames_tensors(arena, dst, n, geom_dev, YUV_GEOM_DTYPE.itemsize)
+    validate_yuv_frames(geom, arena.numel(), H, W)
+    if not (arena.is_cuda and dst.is_cuda and geom_dev.is_cuda):
+        raise ValueError("arena, table and dst must be cuda tensors (no CPU fallback exists)")
+    nb = n * 3 * H * W                                          # frames read once (luma and both chroma), planes written once
+    for q in geom:
+        h0, w0 = int(q["g"]["h0"]), int(q["g"]["w0"])
+        nb += h0 * w0 + 2 * ((h0 + 1) // 2) * ((w0 + 1) // 2) if int(q["kind"]) else h0 * w0 * int(q["g"]["ch"])
+    return Launch(lib().icaf_letterbox_yuv_frames, (arena.data_ptr(), geom_dev.data_ptr(), n // B, B, dst.data_ptr(), ctot, H, W, int(bool(swap_rb))),
+                  keep=(arena, geom_dev, dst), name=name, nbytes=nb)
+
+
+def yuv_frame_lists(rgb, ir, formats):
+    """frame_lists for modalities that may arrive as YUV 4:2:0: formats = (fmt_rgb, fmt_ir), each None (an interleaved modality, as
+    frame_lists takes it) or "nv12" | "nv21" | "i420" | "yv12" — then one uint8 (B, 3 * H0 // 2, W0) tensor or a list of (3 * H0_i // 2,
+    W0_i) tensors, the contiguous buffer a decoder binding returns, H0 and W0 even.  The frame sizes come from the interleaved modality,
+    or from the buffers themselves when both are YUV.  Returns (frames_rgb, frames_ir, shapes, uniform) like frame_lists."""
+    formats = tuple(formats)
+    if len(formats) != 2 or any(f is not None and f not in YUV_LAYOUTS for f in formats):
+        raise ValueError(f"formats=(fmt_rgb, fmt_ir), each None or one of {', '.join(YUV_LAYOUTS)}, got {formats!r}")
+    nd = [3 if f else 4 for f in formats]
+    uniform = tuple(torch.is_tensor(t) and t.dim() == d for t, d in zip((rgb, ir), nd))
+    fr = [[t[i] for i in range(t.shape[0])] if u else list(t) if isinstance(t, (list, tuple)) else None for t, u in zip((rgb, ir), uniform)]
+    if fr[0] is None or fr[1] is None or not fr[0] or len(fr[0]) != len(fr[1]):
+        raise ValueError("native frames come as two batch tensors or two equally long lists of frames")
+    shapes = [None, None]
+    for m, fmt in enumerate(formats):
+        for f in fr[m]:
+            if not torch.is_tensor(f) or f.dtype != torch.uint8 or f.dim() != nd[m] - 1 or (fmt is None and f.shape[2] not in (1, 3)):
+                raise ValueError("frames must be uint8 tensors of shape (H0, W0, ch), ch = 3 or 1" if fmt is None else
+                                 f"{fmt} frames must be uint8 tensors of shape (3 * H0 // 2, W0)")
+        if fmt is None:
+            shapes[m] = [tuple(f.shape[:2]) for f in fr[m]]
+    if shapes[0] is None and shapes[1] is None:                  # both YUV: the buffers state their own size
+        for f in fr[0]:
+            if f.shape[0] % 3:
+                raise ValueError(f"a YUV 4:2:0 buffer has 3 * H0 // 2 rows, got {f.shape[0]}")
+        shapes[0] = [(2 * f.shape[0] // 3, f.shape[1]) for f in fr[0]]
+    size = shapes[0] if shapes[0] is not None else shapes[1]
+    for h0, w0 in size if any(formats) else ():
+        if h0 % 2 or w0 % 2:
+            raise ValueError(f"a YUV 4:2:0 buffer needs even H0 and W0, got {h0}x{w0} (odd sizes: ops.pack_yuv_frames)")
+    for m, fmt in enumerate(formats):
+        if fmt is not None and [tuple(f.shape) for f in fr[m]] != [(3 * h0 // 2, w0) for h0, w0 in size]:
+            raise ValueError(f"a {fmt} buffer of a frame of H0 x W0 has shape (3 * H0 // 2, W0): expected {[(3 * h0 // 2, w0) for h0, w0 in size]}, "
+                             f"got {[tuple(f.shape) for f in fr[m]]}")
+    if shapes[0] is not None and shapes[1] is not None and shapes[0] != shapes[1]:
+        raise ValueError("the RGB and IR frame of a pair must have the same size")
+    return fr[0], fr[1], [tuple(int(v) for v in s) for s in size], uniform
 
 
 def val_geometry(shapes, img_size, batch_shape):

@@ -47,11 +47,15 @@ HOST_FED_BRANCHES = OPT.pipe_branches             # keep the hipGraph's parallel
 class DetectionPipeline:
     def __init__(self, model, batch, height, width, device, conf_thres=0.25, iou_thres=0.45, classes=None,
                  agnostic=False, multi_label=False, max_det=300, world=1, overlap=True, force_gather=False, depth=1, u8=False, augment=False,
-                 frames=None, frame_channels=(3, 3), frames_bgr=True, round_boxes=False):
+                 frames=None, frame_channels=(3, 3), frames_bgr=True, round_boxes=False, frame_formats=(None, None), yuv_matrix="bt601"):
         """frames=(max_h0, max_w0): the pipeline also takes NATIVE camera frames (`submit_frames`; implies u8): every plan owns a frame arena
         for `batch` pairs of up to that size (frame_channels: interleaved channels of the RGB / IR frames, 3 or 1) and a geometry table;
         the letterbox runs on the device in front of the plan and the boxes come back in native image space (round_boxes: torch.round
         applied, as detect_twostream.py:80).  frames_bgr: the frames are BGR (planes become RGB).
+        frame_formats=(fmt_rgb, fmt_ir): a modality that arrives as YUV 4:2:0 names its layout ("nv12" | "nv21" | "i420" | "yv12"; None:
+        interleaved frames of frame_channels) and is submitted as the decoder's contiguous buffer, (B, 3 * H0 // 2, W0) or a list of (3 * H0_i
+        // 2, W0_i); its half of the arena holds 1.5 bytes per pixel and the conversion (yuv_matrix: "bt601" | "bt709" | "bt601-full") runs
+        inside the letterbox, equal to utils.datasets.yuv420_to_bgr in front of the host letterbox byte for byte.
         augment=True: every step is a test-time-augmentation step (Model.forward(augment=True), reference models/yolo_test.py:116-131:
         the plans are engine.TtaPlan objects) and NMS runs over the merged rows of the three passes (55,755 per image at 640 x 640).
         u8=True: the plans take the dataloader's uint8 (B, 6, H, W) RGB+IR batch (Model.forward_u8: `/255`, split and cast in the
@@ -124,26 +128,40 @@ class DetectionPipeline:
         self.n = 0
         self.last = None
         self.frames = None
+        if frames is None and any(f is not None for f in frame_formats):
+            raise ValueError("frame_formats describes native frames: pass frames=(max_h0, max_w0) with it")
         if frames is not None:
-            self._init_frames(batch, height, width, frames, frame_channels, frames_bgr, round_boxes)
+            self._init_frames(batch, height, width, frames, frame_channels, frames_bgr, round_boxes, frame_formats, yuv_matrix)
 
-    def _init_frames(self, B, H, W, frames, chans, bgr, round_boxes):
+    def _init_frames(self, B, H, W, frames, chans, bgr, round_boxes, formats=(None, None), yuv_matrix="bt601"):
         """Per plan: a byte arena (RGB frames in its first half, IR frames in its second) and ONE table allocation — 2B descriptor rows
         for the letterbox, then B scale_coords rows for scale_detections — with a pinned host twin it is copied from."""
         max_h0, max_w0 = int(frames[0]), int(frames[1])
         chans = tuple(int(c) for c in chans)
         if max_h0 < 1 or max_w0 < 1 or len(chans) != 2 or any(c not in (1, 3) for c in chans):
             raise ValueError(f"frames=(max_h0, max_w0) with frame_channels of 1 or 3 each, got {frames} / {chans}")
+        formats = tuple(formats)
+        if len(formats) != 2 or any(f is not None and f not in ops.YUV_LAYOUTS for f in formats):
+            raise ValueError(f"frame_formats=(fmt_rgb, fmt_ir), each None or one of {', '.join(ops.YUV_LAYOUTS)}, got {formats!r}")
+        yuv = any(formats)                                                       # then the table holds icaf_yuv_geom rows
         A = ops.FRAME_ALIGN
-        cap = [B * (-(-(max_h0 * max_w0 * c) // A) * A) for c in chans]          # bytes per modality
-        gb = 2 * B * ops.GEOM_DTYPE.itemsize
+        # bytes per modality: interleaved frames of c channels, or 1.5 bytes per pixel (luma + 4:2:0 chroma of the even sizes buffers come in)
+        per_frame = [max_h0 * max_w0 * c if fmt is None else max_h0 * max_w0 + 2 * ((max_h0 + 1) // 2) * ((max_w0 + 1) // 2) for c, fmt in zip(chans, formats)]
+        cap = [B * (-(-n // A) * A) for n in per_frame]
         probe, _ = ops.frame_geometry([(max_h0, max_w0)] * B, (H, W))
         probe = np.concatenate((probe, probe))
-        ops.pack_frames(probe[:B], chans[0])
-        ops.pack_frames(probe[B:], chans[1], base=cap[0])
+        if yuv:
+            matrix = ops.yuv_matrix_code(yuv_matrix)
+            lay = [fmt if fmt is not None else c for c, fmt in zip(chans, formats)]
+            probe = np.concatenate((ops.pack_yuv_frames(probe[:B], lay[0], matrix=matrix)[0], ops.pack_yuv_frames(probe[B:], lay[1], matrix=matrix, base=cap[0])[0]))
+        else:
+            matrix, lay = 0, list(chans)
+            ops.pack_frames(probe[:B], chans[0])
+            ops.pack_frames(probe[B:], chans[1], base=cap[0])
+        gb = 2 * B * probe.dtype.itemsize
         self.frames = {"B": B, "H": H, "W": W, "max": (max_h0, max_w0), "chans": chans, "cap": cap, "geom_bytes": gb, "cache": {},
                        "arena": [], "tab_dev": [], "tab_host": [], "letterbox": [], "scale_rows": [], "scale_launch": {}, "pending": None,
-                       "round": bool(round_boxes)}
+                       "round": bool(round_boxes), "formats": formats, "yuv": yuv, "matrix": matrix, "layouts": lay}
         f = self.frames
         for plan in self.plans:
             arena = torch.zeros((sum(cap),), dtype=torch.uint8, device=self.device)
@@ -152,7 +170,7 @@ class DetectionPipeline:
             f["tab_dev"].append(tab)
             f["tab_host"].append(torch.zeros((gb + B * 20,), dtype=torch.uint8).pin_memory())
             f["scale_rows"].append(tab[gb:].view(torch.float32).view(B, 5))
-            f["letterbox"].append(ops.letterbox_frames(arena, probe, tab, plan.inputs[0], swap_rb=bgr))
+            f["letterbox"].append((ops.letterbox_yuv_frames if yuv else ops.letterbox_frames)(arena, probe, tab, plan.inputs[0], swap_rb=bgr))
 
     def _frame_table(self, shapes, contiguous):
         """(table bytes, descriptor rows) of one step's frames, cached per set of shapes: the geometry, the arena layout (a uniform
@@ -168,26 +186,48 @@ class DetectionPipeline:
                     raise ValueError(f"a {h0}x{w0} frame exceeds the pipeline's frames={f['max']}")
             geom1, scale = ops.frame_geometry(shapes, (f["H"], f["W"]))
             geom = np.concatenate((geom1, geom1))
-            for m, base in ((0, 0), (1, cap[0])):
-                rows = geom[m * B:(m + 1) * B]
-                if contiguous[m]:
-                    ops.pack_frames(rows, chans[m])
-                    fb = int(rows[0]["h0"]) * int(rows[0]["pitch"])
-                    rows["offset"] = base + fb * np.arange(B)
-                else:
-                    end = ops.pack_frames(rows, chans[m], base=base)
-                    if end - base > cap[m]:
-                        raise ValueError(f"the frames of modality {m} need {end - base} bytes of the arena's {cap[m]}")
-            ops.validate_frames(geom, sum(cap), f["H"], f["W"])
+            if f["yuv"]:
+                geom = self._yuv_rows(geom, contiguous)
+            else:
+                for m, base in ((0, 0), (1, cap[0])):
+                    rows = geom[m * B:(m + 1) * B]
+                    if contiguous[m]:
+                        ops.pack_frames(rows, chans[m])
+                        fb = int(rows[0]["h0"]) * int(rows[0]["pitch"])
+                        rows["offset"] = base + fb * np.arange(B)
+                    else:
+                        end = ops.pack_frames(rows, chans[m], base=base)
+                        if end - base > cap[m]:
+                            raise ValueError(f"the frames of modality {m} need {end - base} bytes of the arena's {cap[m]}")
+            (ops.validate_yuv_frames if f["yuv"] else ops.validate_frames)(geom, sum(cap), f["H"], f["W"])
             table = np.concatenate((geom.view(np.uint8).reshape(-1), scale.view(np.uint8).reshape(-1)))
             if len(f["cache"]) >= 64:
                 f["cache"].pop(next(iter(f["cache"])))
             hit = f["cache"][key] = (torch.from_numpy(table), geom)
         return hit
 
+    def _yuv_rows(self, geom, contiguous):
+        """_frame_table's arena layout for a pipeline with a YUV modality: icaf_yuv_geom rows.  A uniform batch in one contiguous tensor
+        whose frames are whole 16-byte multiples keeps its layout (frame b of the modality at b frame sizes: ONE copy moves it), other
+        frames start on FRAME_ALIGN boundaries."""
+        f = self.frames
+        B, cap, halves = f["B"], f["cap"], []
+        for m, base in ((0, 0), (1, cap[0])):
+            rows, end = ops.pack_yuv_frames(geom[m * B:(m + 1) * B], f["layouts"][m], matrix=f["matrix"], base=base)
+            if contiguous[m]:
+                fb = (end - int(rows[B - 1]["g"]["offset"]))                        # bytes of one frame, chroma included
+                for k in ("cb_offset", "cr_offset"):
+                    rows[k] += (rows["kind"] != 0) * (base + fb * np.arange(B) - rows["g"]["offset"])
+                rows["g"]["offset"] = base + fb * np.arange(B)
+            elif end - base > cap[m]:
+                raise ValueError(f"the frames of modality {m} need {end - base} bytes of the arena's {cap[m]}")
+            halves.append(rows)
+        return np.concatenate(halves)
+
     def submit_frames(self, rgb, ir):
         """One batch of NATIVE frames through the pipeline: rgb / ir are uint8 (B, H0, W0, ch) tensors or lists of (H0_i, W0_i, ch) tensors,
-        in pinned host memory or on the device; a pair shares its size, sizes may change from step to step.  The frames and the step's
+        in pinned host memory or on the device (a modality with a frame_formats layout: (B, 3 * H0 // 2, W0) or a list of (3 * H0_i // 2,
+        W0_i) buffers, H0 and W0 even); a pair shares its size, sizes may change from step to step.  The frames and the step's
         geometry table are copied on the copy stream(s) under the events submit_u8 uses, the letterbox runs on the plan's forward stream in
         front of its graph, scale_detections on the NMS stream behind NMS: the (det, count) step() returns hold NATIVE-space boxes (rows >=
         count zeroed), and so does the gathered block of a process group.  Host buffers must stay untouched until their copy has run
@@ -196,12 +236,12 @@ class DetectionPipeline:
         if f is None:
             raise ValueError("DetectionPipeline(frames=(max_h0, max_w0)) takes native frames")
         B, chans = f["B"], f["chans"]
-        *lists, shapes, uniform = ops.frame_lists(rgb, ir)
+        *lists, shapes, uniform = ops.yuv_frame_lists(rgb, ir, f["formats"]) if f["yuv"] else ops.frame_lists(rgb, ir)
         if len(shapes) != B:
             raise ValueError(f"submit_frames expects a batch of {B} pairs, got {len(shapes)}")
         mods, contiguous = [], []
         for m, (t, fr) in enumerate(zip((rgb, ir), lists)):
-            if any(x.shape[2] != chans[m] for x in fr):
+            if f["formats"][m] is None and any(x.shape[2] != chans[m] for x in fr):
                 raise ValueError(f"modality {m}: frames must be uint8 (H0, W0, {chans[m]}) tensors")
             contiguous.append(bool(uniform[m] and t.is_contiguous() and (t[0].numel() % 16 == 0)))
             mods.append((t, fr))
@@ -231,7 +271,7 @@ class DetectionPipeline:
                 if k == 0:
                     f["tab_dev"][pi].copy_(f["tab_host"][pi], non_blocking=True)
                 for m, (t, fr) in enumerate(mods):
-                    rows = geom[m * B:(m + 1) * B]
+                    rows = geom[m * B:(m + 1) * B]["g"] if f["yuv"] else geom[m * B:(m + 1) * B]
                     if contiguous[m]:
                         o, fb = int(rows[lo]["offset"]), t[0].numel()
                         arena[o:o + (hi - lo) * fb].view(t[lo:hi].shape).copy_(t[lo:hi], non_blocking=True)

@@ -142,6 +142,58 @@ def letterbox(img, new_shape=(640, 640), color=(114, 114, 114), auto=True, scale
     return out, (r, r), (dw, dh)
 
 
+YUV_LAYOUTS = ("nv12", "nv21", "i420", "yv12")
+
+
+def yuv420_planes(buf, h0, w0, layout):
+    """The planes of one YUV 4:2:0 frame as a decoder hands it over — `buf`: uint8, h0 * w0 luma bytes followed by the chroma of
+    ceil(h0 / 2) x ceil(w0 / 2) samples, interleaved CbCr (nv12) / CrCb (nv21) or as two planes Cb, Cr (i420) / Cr, Cb (yv12); for even
+    sizes that is the (3 * h0 // 2, w0) array every decoder binding returns.  Returns views (y, cb, cr)."""
+    if layout not in YUV_LAYOUTS:
+        raise ValueError(f"unknown YUV 4:2:0 layout {layout!r} (one of {', '.join(YUV_LAYOUTS)})")
+    ch, cw = (h0 + 1) // 2, (w0 + 1) // 2
+    flat = np.asarray(buf).reshape(-1)
+    if flat.dtype != np.uint8 or flat.size != h0 * w0 + 2 * ch * cw:
+        raise ValueError(f"a {h0}x{w0} {layout} frame is {h0 * w0 + 2 * ch * cw} uint8 bytes, got {flat.size} of {flat.dtype}")
+    y, c = flat[:h0 * w0].reshape(h0, w0), flat[h0 * w0:]
+    if layout in ("nv12", "nv21"):
+        c = c.reshape(ch, cw, 2)
+        first, second = c[:, :, 0], c[:, :, 1]
+    else:
+        first, second = c[:ch * cw].reshape(ch, cw), c[ch * cw:].reshape(ch, cw)
+    return (y, first, second) if layout in ("nv12", "i420") else (y, second, first)
+
+
+def yuv420_to_bgr(y, cb, cr, matrix=0):
+    """THE colour conversion of native YUV 4:2:0 frames (icaf_letterbox_yuv_frames equals letterbox() of this image byte for byte): y
+    (h0, w0) uint8, cb / cr (ceil(h0 / 2), ceil(w0 / 2)) uint8 -> (h0, w0, 3) uint8 BGR.  Pixel (i, j) takes chroma sample (i >> 1,
+    j >> 1): nearest replication, no chroma filtering.  32-bit integer arithmetic, `>>` flooring, results clamped to 0..255; with
+    c = Y - 16, d = Cb - 128, e = Cr - 128:
+      matrix 0, BT.601 limited range:      R = (298c + 409e + 128) >> 8, G = (298c - 100d - 208e + 128) >> 8, B = (298c + 516d + 128) >> 8
+      matrix 1, BT.709 limited range:      R = (298c + 459e + 128) >> 8, G = (298c - 55d - 136e + 128) >> 8,  B = (298c + 541d + 128) >> 8
+      matrix 2, BT.601 full range (JFIF):  R = Y + ((91881e + 32768) >> 16), G = Y + ((-22554d - 46802e + 32768) >> 16),
+                                           B = Y + ((116130d + 32768) >> 16)"""
+    y, cb, cr = (np.asarray(a) for a in (y, cb, cr))
+    h0, w0 = y.shape
+    if any(a.dtype != np.uint8 for a in (y, cb, cr)) or cb.shape != ((h0 + 1) // 2, (w0 + 1) // 2) or cr.shape != cb.shape:
+        raise ValueError(f"a {h0}x{w0} luma plane takes uint8 chroma planes of {(h0 + 1) // 2}x{(w0 + 1) // 2}, got {cb.shape} / {cr.shape}")
+    if matrix not in (0, 1, 2):
+        raise ValueError(f"unknown YUV matrix {matrix!r} (0 = BT.601, 1 = BT.709, 2 = BT.601 full range)")
+    rows, cols = np.arange(h0) >> 1, np.arange(w0) >> 1
+    Y = y.astype(np.int32)
+    d = cb.astype(np.int32)[rows][:, cols] - 128
+    e = cr.astype(np.int32)[rows][:, cols] - 128
+    if matrix == 2:
+        r = Y + ((91881 * e + 32768) >> 16)
+        g = Y + ((-22554 * d - 46802 * e + 32768) >> 16)
+        b = Y + ((116130 * d + 32768) >> 16)
+    else:
+        c = 298 * (Y - 16) + 128
+        rv, gu, gv, bu = (409, -100, -208, 516) if matrix == 0 else (459, -55, -136, 541)
+        r, g, b = (c + rv * e) >> 8, (c + gu * d + gv * e) >> 8, (c + bu * d) >> 8
+    return np.clip(np.stack((b, g, r), axis=2), 0, 255).astype(np.uint8)
+
+
 def _list_images(path):
     p = str(Path(path).absolute())
     if "*" in p:

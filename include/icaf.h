@@ -40,7 +40,7 @@ const char* icaf_last_error(void);
 /* Probe knobs of the library, set by the host's one options object (icafusion_amd/options.py) when the library is loaded — the library reads no
  * environment variable: "detect_elementwise" (!= 0: icaf_detect_decode by the one-thread-per-element kernel), "attn_qsplit" (n > 0: query splits per
  * head of icaf_cross_attention), "sppf_vpb" (n > 0: cap on the channel vectors per workgroup of icaf_sppf_pool), "letterbox_direct" (!= 0:
- * icaf_letterbox_frames taps global memory in every tile instead of staging in LDS; set by a caller for an A/B, not by the options object),
+ * icaf_letterbox_frames and icaf_letterbox_yuv_frames tap global memory in every tile instead of staging in LDS; set by a caller for an A/B, not by the options object),
  * "index64" (!= 0: the element kernel of icaf_dmff_pool_tokens and icaf_upsample_nearest launch the 64-bit-index instantiations they otherwise
  * keep for 2^31 vectors and more), "attn_stream" (!= 0: icaf_cross_attention launches the key-streaming form for every shape, for A/B timings
  * and tests; set by a caller, not by the options object), "area_direct" (!= 0: the area rows of icaf_resize_frames recompute their vertical
@@ -453,7 +453,48 @@ int icaf_letterbox_frames(const void* arena, const icaf_frame_geom* geom, int ns
 int icaf_scale_detections(const float* det, const int* count, int B, int max_det, const float* scale, int round, float* out,
                           icaf_stream_t s);
 
-/* ---- native validation frames (utils/datasets.py:1116-1122, load_image_rgb_ir: longest side to img_size, then letterbox's padding) ----
+/* ---- native YUV 4:2:0 camera frames (utils/datasets.py: yuv420_to_bgr, then letterbox) ----------------------------------------
+ * icaf_letterbox_yuv_frames: icaf_letterbox_frames for the surfaces a video decoder delivers (NV12 / NV21: a Y plane and one plane of
+ *   interleaved chroma; I420 / YV12: three planes), byte for byte equal to letterbox(yuv420_to_bgr(y, cb, cr, matrix)) followed by the
+ *   BGR -> RGB planes: CONVERT AT NATIVE RESOLUTION, THEN LETTERBOX.  arena, dst, nstreams, B, ctot, H, W, the grid, the 32 x 64 tile, the
+ *   alignment rules, the refusals and "every byte of the planes written exactly once, 114 outside the block" are icaf_letterbox_frames';
+ *   geom: DEVICE table of nstreams * B 80-byte rows, entry modality * B + image.
+ *   kind 0: g is exactly icaf_letterbox_frames' row (ch 3 or 1) and the tile produces exactly its bytes, swap_rb included; the other
+ *     fields are not read.  A thermal stream that arrives as NV12 is such a row on its Y plane (offset, pitch, ch 1): luma taken as is.
+ *   kind 1: g.offset / g.pitch describe the Y plane (h0 rows, g.ch is 1); the chroma planes hold ceil(h0 / 2) rows of ceil(w0 / 2) samples,
+ *     sample (i, j) of Cb at arena byte cb_offset + i * c_pitch + j * c_step, of Cr likewise from cr_offset; c_step 2 is interleaved
+ *     chroma (the two offsets one byte apart), c_step 1 planar.  Pixel (y, x) uses chroma sample (y >> 1, x >> 1): nearest replication,
+ *     no chroma filtering; odd h0 / w0 are legal.  swap_rb is not read: planes [3m, 3m + 3) are always R, G, B.
+ *     Each of the four bilinear taps of an output pixel is converted to three bytes, then icaf_letterbox_frames' fp32 tap arithmetic
+ *     (s, i0, frac, top, bot, out, floor(out + 0.5f), clip) runs on those bytes per channel.  Conversion in 32-bit integers, >> an
+ *     arithmetic (flooring) shift, clip8 clamping to 0..255, c = Y - 16, d = Cb - 128, e = Cr - 128:
+ *       matrix 0, BT.601 limited range:  R = clip8((298 c + 409 e + 128) >> 8)   G = clip8((298 c - 100 d - 208 e + 128) >> 8)
+ *                                        B = clip8((298 c + 516 d + 128) >> 8)
+ *       matrix 1, BT.709 limited range:  R = clip8((298 c + 459 e + 128) >> 8)   G = clip8((298 c - 55 d - 136 e + 128) >> 8)
+ *                                        B = clip8((298 c + 541 d + 128) >> 8)
+ *       matrix 2, BT.601 full range (JFIF):  R = clip8(Y + ((91881 e + 32768) >> 16))   G = clip8(Y + ((-22554 d - 46802 e + 32768) >> 16))
+ *                                            B = clip8(Y + ((116130 d + 32768) >> 16))
+ *   Budget rule of a kind-1 row: with rows = (int)(32 sy) + 4 capped at h0 and cols = (int)(64 sx) + 4 capped at w0 (the luma rectangle a
+ *   tile can tap), crows = rows / 2 + 1 capped at ceil(h0 / 2) and ccols = cols / 2 + 1 capped at ceil(w0 / 2) (the chroma samples under
+ *   it), a tile stages rows luma rows of (cols + 30) / 16 vectors and, for c_step 2, crows rows of (2 ccols + 30) / 16 vectors, for c_step 1
+ *   twice crows rows of (ccols + 30) / 16 vectors (16-byte vectors, integer divisions) if that fits ICAF_YUV_LDS_BYTES and sx, sy < 1024;
+ *   otherwise, or with the probe knob "letterbox_direct", every tap is three clamped global byte loads.  Staging reads aligned 16-byte
+ *   vectors where they lie inside a plane and single bytes where a vector crosses a plane's first or last byte (chroma planes need no
+ *   alignment).  No load leaves the h0 * pitch bytes of the Y plane or the bytes from a chroma plane's first sample to its last.
+ *   The host guarantees (icafusion_amd/ops.py validate_yuv_frames): everything icaf_letterbox_frames asks of g; for kind 1 also ch == 1,
+ *   c_step 1 or 2, c_pitch >= ceil(w0 / 2) * c_step, both chroma planes inside the arena, |cb_offset - cr_offset| == 1 for c_step 2,
+ *   matrix 0..2. */
+enum { ICAF_YUV_LDS_BYTES = 40960 };     /* a 1080 x 1920 NV12 frame letterboxed to 640 (3 x) stages: (100 * 14 + 51 * 14) vectors = 33,824 bytes */
+typedef struct icaf_yuv_geom {
+    icaf_frame_geom g;     /* kind 0: exactly icaf_letterbox_frames' row (ch 3 or 1).  kind 1: offset / pitch describe the Y plane, ch is 1 */
+    long long cb_offset, cr_offset;   /* first Cb / Cr byte in the arena */
+    int c_pitch, c_step;   /* bytes per chroma row; bytes between chroma samples: 2 = interleaved (NV12: cr = cb + 1, NV21: cb = cr + 1), 1 = planar (I420 / YV12) */
+    int matrix, kind;
+} icaf_yuv_geom;           /* 80 bytes */
+int icaf_letterbox_yuv_frames(const void* arena, const icaf_yuv_geom* geom, int nstreams, int B, void* dst, int ctot, int H, int W,
+                              int swap_rb, icaf_stream_t s);
+
+/* ---- native validation frames(utils/datasets.py:1116-1122, load_image_rgb_ir: longest side to img_size, then letterbox's padding) ----
  * icaf_resize_frames: icaf_letterbox_frames with a resize mode per descriptor, so that one launch serves a rectangular validation batch
  *   that mixes frames that shrink, frames that grow and frames that are copied.  arena, geom (DEVICE table, 48-byte rows), dst, swap_rb
  *   and the rule "every byte of the planes written exactly once, 114 outside the block" are icaf_letterbox_frames'.  mode: DEVICE int
