@@ -11,6 +11,10 @@ Per pair: letterbox to --img-size (utils/datasets.py), uint8 -> device, one forw
 boxes scaled back to the original image, optional YOLO-format txt / annotated images.  `--augment` runs the reference's test-time
 augmentation (three passes per pair, merged before NMS).  `--device-letterbox` hands the decoded frames over as they are: the letterbox and the
 mapping of the boxes back to the image then run on the device (Model.forward_frames, ops.scale_detections), same outputs.  The per-frame
+`--align-ir FILE|stretch` serves a calibrated rig whose thermal camera differs in size and pose from the visible one: FILE holds the 3 x 3 matrix
+that maps visible (aligned) pixel coordinates to thermal pixel coordinates (utils.datasets.load_alignment; --align-inverse: the file maps thermal to
+visible), `stretch` is "same field of view, other resolution".  With --device-letterbox the matrix goes to Model.forward_frames(align=...) and the
+thermal frame is registered at the letterbox's taps; without it the host calls utils.datasets.warp_perspective in front of letterbox.  Same outputs.
 `Done. (…s, …Hz)` and final `Average Speed` lines are the reference's (:160,198).  Webcam / video sources, the
 second-stage classifier and --view-img need OpenCV and are out of scope."""
 import argparse
@@ -23,7 +27,7 @@ import torch
 from icafusion_amd import ops
 from icafusion_amd.models.experimental import load_detector
 from icafusion_amd.utils.confluence import confluence_process
-from icafusion_amd.utils.datasets import LoadImages, imwrite_bgr
+from icafusion_amd.utils.datasets import LoadImages, imwrite_bgr, letterbox, load_alignment, stretch_alignment, warp_perspective
 from icafusion_amd.utils.general import increment_path, non_max_suppression, scale_coords, xyxy2xywh
 from icafusion_amd.utils.torch_utils import select_device, time_synchronized
 
@@ -57,12 +61,26 @@ def detect(opt):
     stride = int(model.stride.max())
     names = model.names
     on_device = bool(getattr(opt, "device_letterbox", False))      # native frames in, native boxes out: no host letterbox / scale_coords
-    dataset, dataset2 = (LoadImages(src, opt.img_size, stride, native=on_device) for src in (opt.source1, opt.source2))
+    align = getattr(opt, "align_ir", None)                         # a calibrated rig: the thermal frame is registered onto the visible one
+    border = int(getattr(opt, "align_border", 0))
+    if align is not None and align != "stretch":
+        align = load_alignment(align, inverse=bool(getattr(opt, "align_inverse", False)))
+    dataset = LoadImages(opt.source1, opt.img_size, stride, native=on_device)
+    dataset2 = LoadImages(opt.source2, opt.img_size, stride, native=on_device or align is not None)
     if len(dataset) != len(dataset2):
         raise ValueError(f"{len(dataset)} visible images vs {len(dataset2)} infrared images")
     t0, img_num, fps_sum = time.time(), 0, 0.0
     for (path, img, im0, _), (path2, img2, im0_, _) in zip(dataset, dataset2):
-        if on_device:
+        if align is not None:
+            M = stretch_alignment(im0_.shape[:2], im0.shape[:2]) if isinstance(align, str) else align
+            if not on_device or save_img:                              # the registered thermal frame on the host: the network's input, or only the picture
+                ir_src, im0_ = im0_, warp_perspective(im0_, M, im0.shape[:2], border)
+            if not on_device:
+                img2 = np.ascontiguousarray(letterbox(im0_, opt.img_size, stride=stride)[0][:, :, ::-1].transpose(2, 0, 1))
+        if on_device and align is not None:
+            frames = [torch.from_numpy(np.ascontiguousarray(x)).unsqueeze(0).to(device) for x in (im0, ir_src if save_img else im0_)]
+            net_shape = (opt.img_size, opt.img_size)
+        elif on_device:
             frames = [torch.from_numpy(x).unsqueeze(0).to(device) for x in (im0, im0_)]      # uint8 (1, H0, W0, 3) BGR, as decoded
             net_shape = (opt.img_size, opt.img_size)
         else:
@@ -71,7 +89,8 @@ def detect(opt):
         t1 = time_synchronized()
         # /255, RGB/IR split and the cast happen in the staging kernel; --augment: the three passes of models/yolo_test.py:116-131
         if on_device:
-            out, geometry = model.forward_frames(frames[0], frames[1], opt.img_size, bgr=True, augment=getattr(opt, "augment", False))
+            out, geometry = model.forward_frames(frames[0], frames[1], opt.img_size, bgr=True, augment=getattr(opt, "augment", False),
+                                                 **({} if align is None else {"align": (None, M), "align_border": border}))
             pred = out[0]
         else:
             pred = (model.forward_u8(img6, augment=True) if getattr(opt, "augment", False) else model.forward_u8(img6))[0]
@@ -153,6 +172,11 @@ def parse_opt(argv=None):
                     "the 0.83 pass flipped left-right; needs --img-size >= 448")
     ap.add_argument("--device-letterbox", action="store_true", help="hand the native frames to the device: letterbox and the mapping of the "
                     "boxes back to the image run as HIP kernels (Model.forward_frames, ops.scale_detections) instead of numpy / torch on the host")
+    ap.add_argument("--align-ir", type=str, default=None, metavar="FILE|stretch", help="calibrated rig: the 3 x 3 matrix (nine numbers, text or .npy) "
+                    "that maps visible pixel coordinates to thermal pixel coordinates, or `stretch` (same field of view, other resolution); the "
+                    "thermal frame is registered onto the visible one, boxes are in the visible frame")
+    ap.add_argument("--align-inverse", action="store_true", help="the --align-ir file maps thermal to visible coordinates (findHomography(ir, visible)): invert it")
+    ap.add_argument("--align-border", type=int, default=0, metavar="N", help="grey level 0..255 of registered pixels the thermal frame does not cover")
     return ap.parse_args(argv)
 
 

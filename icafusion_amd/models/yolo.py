@@ -585,7 +585,8 @@ class Model(HipModule):
             raise ValueError("forward_u8 expects a cuda uint8 tensor of shape (B, 6, H, W)")
         return self._forward_images((img6,), u8=True, augment=augment)
 
-    def forward_frames(self, rgb, ir, img_size=640, bgr=True, augment=False, val_size=None, formats=None, yuv_matrix="bt601"):
+    def forward_frames(self, rgb, ir, img_size=640, bgr=True, augment=False, val_size=None, formats=None, yuv_matrix="bt601", align=None,
+                       align_border=0):
         """Forward from NATIVE camera frames: rgb / ir are cuda uint8 tensors (B, H0, W0, ch) in decoder layout (interleaved, ch = 3 or
         1) or lists of (H0_i, W0_i, ch) tensors for ragged sizes; a pair shares its size.  The letterbox to img_size (an int or (H, W);
         utils.datasets.letterbox, byte for byte) runs on the device straight into the uint8 plan's input, then the plan (or the TTA plan)
@@ -600,8 +601,18 @@ class Model(HipModule):
         interleaved frames above), and is handed over as the contiguous buffer a decoder returns — one uint8 (B, 3 * H0 // 2, W0) tensor
         or a list of (3 * H0_i // 2, W0_i) tensors, H0 and W0 even; the frame size comes from the other modality, or from the buffers when
         both are YUV.  yuv_matrix: "bt601" | "bt709" | "bt601-full" (or 0 / 1 / 2).  The colour conversion runs inside the letterbox
-        (icaf_letterbox_yuv_frames); the result is bit-identical to forward_u8 of letterbox(utils.datasets.yuv420_to_bgr(...))."""
+        (icaf_letterbox_yuv_frames); the result is bit-identical to forward_u8 of letterbox(utils.datasets.yuv420_to_bgr(...)).
+        align=(A_rgb, A_ir): a CALIBRATED pair whose cameras differ in size and pose.  Exactly one entry is not None: a (3, 3) array (one
+        rig, every pair), a (B, 3, 3) array (per pair) or "stretch" (same field of view, other resolution), mapping ALIGNED pixel
+        coordinates to that modality's SOURCE pixel coordinates (utils.datasets.warp_perspective; cv2's WARP_INVERSE_MAP matrix).  That
+        modality may have any size per frame; the OTHER modality's frame size is the aligned size and its letterbox the pair's, so boxes
+        and FrameGeometry are in the un-warped modality's native space.  The homography is applied at the letterbox's taps
+        (icaf_letterbox_warp_frames; pixels the source does not cover are align_border, 0..255): bit-identical to forward_u8 of
+        letterbox(warp_perspective(frame, M, (h0, w0), align_border)) beside the plain letterbox of the other frame.  The matrices live in
+        the device table and are rewritten per call: a rig that re-calibrates rebuilds nothing."""
         self._check_eval()
+        if align is not None:
+            return self._forward_warp_frames(rgb, ir, img_size, bgr, augment, val_size, formats, align, align_border)
         if formats is not None and any(f is not None for f in formats):
             return self._forward_yuv_frames(rgb, ir, img_size, bgr, augment, val_size, formats, yuv_matrix)
         try:
@@ -663,6 +674,57 @@ class Model(HipModule):
             st["launch"] = ops.letterbox_yuv_frames(st["arena"], st["geom"], st["geom_dev"], dst, swap_rb=bgr)
             st["dst"] = dst
         for o, f in zip(st["geom"]["g"]["offset"], fr[0] + fr[1]):        # a YUV buffer is one run of bytes: luma rows, then its chroma
+            st["arena"][int(o):int(o) + f.numel()].view(f.shape).copy_(f)
+        st["launch"].args = st["launch"].args[:-1] + (int(bool(bgr)),)
+        st["launch"](ops.current_stream_ptr())
+        plan.run()
+        out = self._result(plan.outputs)
+        return ((out, None) if augment else out), st["info"]
+
+    def _forward_warp_frames(self, rgb, ir, img_size, bgr, augment, val_size, formats, align, border):
+        """forward_frames of a calibrated pair: the same steps around icaf_letterbox_warp_frames and its 104-byte rows.  The state is keyed
+        by the shapes; the matrices and the border are written into the table on every call."""
+        if val_size is not None:
+            raise ValueError("forward_frames: align= has no validation geometry (val_size); validation sets are registered offline")
+        if formats is not None and any(f is not None for f in formats):
+            raise ValueError("forward_frames: align= takes interleaved frames; a YUV 4:2:0 modality (formats) cannot be combined with it yet")
+        border = int(border)
+        if not 0 <= border <= 255:
+            raise ValueError(f"forward_frames: align_border {border} outside 0..255")
+        *fr, shapes, _, m, src_shapes, mats = ops.warp_frame_lists(rgb, ir, align)
+        if not all(f.is_cuda for f in fr[0] + fr[1]):
+            raise ValueError("forward_frames expects cuda uint8 frames (no CPU fallback exists)")
+        B, device = len(fr[0]), fr[0][0].device
+        H, W = (img_size, img_size) if isinstance(img_size, int) else img_size
+        self._check_stride(H, W, int(self.stride.max()))
+        chans = tuple(int(f.shape[2]) for f in fr[0] + fr[1])
+        key = (H, W, tuple(shapes), "align", m, tuple(src_shapes), chans, device)
+        states = self.__dict__.setdefault("_frame_states", {})
+        st = states.pop(key, None)
+        if st is None:
+            geom1, scale = ops.frame_geometry(shapes, (H, W))
+            warped = [(hs, ws, c) for (hs, ws), c in zip(src_shapes, chans[m * B:(m + 1) * B])]
+            plain = list(chans[(1 - m) * B:(2 - m) * B])
+            sources = warped + plain if m == 0 else plain + warped
+            placeholder = [np.eye(3, dtype=np.float32)] * B
+            geom, nbytes = ops.pack_warp_frames(np.concatenate((geom1, geom1)), sources, placeholder + [None] * B if m == 0 else [None] * B + placeholder)
+            st = {"geom": geom, "geom_dev": ops.geom_tensor(geom, device), "arena": torch.zeros((nbytes,), dtype=torch.uint8, device=device),
+                  "info": ops.FrameGeometry(geom, scale, torch.from_numpy(scale).to(device)), "dst": None, "launch": None}
+            while len(states) >= 8:
+                states.pop(next(iter(states)))
+        states[key] = st
+        geom = st["geom"]
+        geom["m"][m * B:(m + 1) * B] = mats.reshape(B, 9)
+        geom["border"][m * B:(m + 1) * B] = border
+        plan = (self.tta_plan_for if augment else self.plan_for)(B, H, W, device, u8=True)
+        dst = plan.inputs[0]
+        if st["dst"] is not dst:
+            st["launch"] = ops.letterbox_warp_frames(st["arena"], geom, st["geom_dev"], dst, swap_rb=bgr)
+            st["dst"] = dst
+        else:
+            ops.validate_warp_frames(geom, st["arena"].numel(), H, W)
+        st["geom_dev"].copy_(ops.geom_tensor(geom))               # this call's matrices, in stream order in front of the launch
+        for o, f in zip(geom["g"]["offset"], fr[0] + fr[1]):
             st["arena"][int(o):int(o) + f.numel()].view(f.shape).copy_(f)
         st["launch"].args = st["launch"].args[:-1] + (int(bool(bgr)),)
         st["launch"](ops.current_stream_ptr())

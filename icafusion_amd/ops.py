@@ -15,7 +15,7 @@ import torch
 
 from . import _lib
 from .options import OPT
-from ._lib import BneckArgs, ConvArgs, DmffArgs, FrameGeom, Stem2Args, YuvGeom, check, lib, F32, BF16, F16, ACT_NONE, ACT_SILU, ACT_GELU, ACT_RELU  # noqa: F401
+from ._lib import BneckArgs, ConvArgs, DmffArgs, FrameGeom, Stem2Args, WarpGeom, YuvGeom, check, lib, F32, BF16, F16, ACT_NONE, ACT_SILU, ACT_GELU, ACT_RELU  # noqa: F401
 from ._lib import CONFLUENCE_MAX_CAND, LOSS_MAX_LEVELS, LOSS_MAX_ANCHORS, LOSS_MAX_TARGETS, LOSS_SLOT_INTS  # noqa: F401
 
 _DT = {torch.float32: F32, torch.bfloat16: BF16, torch.float16: F16}
@@ -1254,7 +1254,7 @@ def frame_lists(rgb, ir):
             raise ValueError("frames must be uint8 tensors of shape (H0, W0, ch), ch = 3 or 1")
     shapes = [tuple(f.shape[:2]) for f in fr[0]]
     if shapes != [tuple(f.shape[:2]) for f in fr[1]]:
-        raise ValueError("the RGB and IR frame of a pair must have the same size")
+        raise ValueError("the RGB and IR frame of a pair must have the same size (a calibrated pair of unequal sizes: pass align=)")
     return fr[0], fr[1], shapes, uniform
 
 
@@ -1460,6 +1460,195 @@ def yuv_frame_lists(rgb, ir, formats):
     if shapes[0] is not None and shapes[1] is not None and shapes[0] != shapes[1]:
         raise ValueError("the RGB and IR frame of a pair must have the same size")
     return fr[0], fr[1], [tuple(int(v) for v in s) for s in size], uniform
+
+
+# calibrated RGB / IR pairs: one row per (modality, image) in the layout of icaf_warp_geom (include/icaf.h) — field "g" is a GEOM_DTYPE row
+WARP_GEOM_DTYPE = np.dtype(WarpGeom)
+assert WARP_GEOM_DTYPE.itemsize == C.sizeof(WarpGeom) == 104 and WARP_GEOM_DTYPE["g"] == GEOM_DTYPE
+
+
+def alignment_matrices(align, src_shapes, shapes):
+    """One modality's alignment as float32 (B, 3, 3) ALIGNED -> SOURCE matrices (utils.datasets.warp_perspective's convention): `align`
+    is a (3, 3) array (one rig, every pair), a (B, 3, 3) array (per pair) or "stretch" (utils.datasets.stretch_alignment of each pair's
+    source and aligned size).  ValueError for any other shape and for a non-finite entry."""
+    from .utils.datasets import stretch_alignment
+    B = len(shapes)
+    if isinstance(align, str):
+        if align != "stretch":
+            raise ValueError(f"an alignment is a (3, 3) or ({B}, 3, 3) matrix or 'stretch', got {align!r}")
+        return np.stack([stretch_alignment(s, a) for s, a in zip(src_shapes, shapes)])
+    a = align.detach().cpu().numpy() if torch.is_tensor(align) else np.asarray(align)
+    if a.dtype.kind not in "fiu" or a.shape not in ((3, 3), (B, 3, 3)):
+        raise ValueError(f"an alignment is a (3, 3) or ({B}, 3, 3) matrix or 'stretch', got shape {a.shape} of {a.dtype}")
+    a = np.ascontiguousarray(np.broadcast_to(a.astype(np.float64).astype(np.float32), (B, 3, 3)))
+    if not np.isfinite(a).all():
+        raise ValueError("an alignment matrix has a non-finite entry")
+    return a
+
+
+def pack_warp_frames(geom, sources, matrices=None, borders=0, pitch=None, base=0):
+    """pack_frames for tables of calibrated pairs: returns (rows, end) — WARP_GEOM_DTYPE rows around `geom` (frame_geometry's GEOM_DTYPE
+    rows, or WARP rows whose "g" is filled) and the first free byte behind the frames.  sources: a list with one entry per row, or one
+    entry (an int or a tuple) for all rows — 3 / 1 (a
+    kind-0 row: the frame has its row's h0 x w0 and that many channels, laid out exactly as pack_frames lays it out) or (hs, ws, ch) (a
+    kind-1 row: h0 x w0 is the ALIGNED size, the frame in the arena is the hs x ws source).  matrices: per row (or one for all) the 3 x 3
+    aligned -> source matrix of a kind-1 row, None for kind 0; borders: 0..255 per row or one for all; pitch: bytes per source row (default
+    tight).  Frames start on FRAME_ALIGN boundaries from `base` on."""
+    n = len(geom)
+    rows = np.zeros((n,), WARP_GEOM_DTYPE)
+    rows["g"] = geom if geom.dtype == GEOM_DTYPE else geom["g"]
+    srcs = [sources] * n if isinstance(sources, int) or (isinstance(sources, tuple) and len(sources) == 3 and isinstance(sources[0], int)) else list(sources)
+    mats = [None] * n if matrices is None else [matrices] * n if getattr(matrices, "shape", None) == (3, 3) else list(matrices)
+    bords = [borders] * n if isinstance(borders, int) else list(borders)
+    pitches = [pitch] * n if pitch is None or isinstance(pitch, int) else list(pitch)
+    if not (len(srcs) == len(mats) == len(bords) == len(pitches) == n):
+        raise ValueError(f"{n} rows need {n} sources, matrices, borders and pitches (or one for all)")
+    off = int(base)
+    for i, (q, src, mat, bd, p) in enumerate(zip(rows, srcs, mats, bords, pitches)):
+        g = q["g"]
+        off = -(-off // FRAME_ALIGN) * FRAME_ALIGN
+        if isinstance(src, (int, np.integer)):
+            if mat is not None:
+                raise ValueError(f"frame {i}: a matrix needs a (hs, ws, ch) source; {src} alone describes an unwarped frame")
+            g["offset"], g["ch"], g["pitch"] = off, int(src), int(g["w0"]) * int(src) if p is None else int(p)
+            off += int(g["h0"]) * int(g["pitch"])
+            continue
+        if len(src) != 3:
+            raise ValueError(f"frame {i}: a source is 3, 1 or (hs, ws, ch), got {src!r}")
+        hs, ws, ch = (int(v) for v in src)
+        if mat is None:
+            raise ValueError(f"frame {i}: a (hs, ws, ch) source needs its 3 x 3 matrix")
+        m = np.asarray(mat, np.float64).astype(np.float32)
+        if m.shape != (3, 3):
+            raise ValueError(f"frame {i}: an alignment matrix is 3 x 3, got shape {m.shape}")
+        q["kind"], q["hs"], q["ws"], q["border"], q["m"] = 1, hs, ws, int(bd), m.reshape(9)
+        g["offset"], g["ch"], g["pitch"] = off, ch, ws * ch if p is None else int(p)
+        off += hs * int(g["pitch"])
+    return rows, off
+
+
+def validate_warp_frames(geom, arena_bytes, H, W):
+    """validate_frames for WARP_GEOM_DTYPE rows: raises ValueError with the row and the reason — an unknown kind, for kind-0 rows
+    everything validate_frames refuses, for kind-1 rows the same of the SOURCE frame (hs x ws x ch at offset / pitch) and of the aligned
+    block, a border outside 0..255 and a non-finite matrix entry.  The kernel trusts the table — nothing reaches the device before this
+    has passed."""
+    for i, q in enumerate(geom):
+        kind = int(q["kind"])
+        if kind not in (0, 1):
+            raise ValueError(f"frame {i}: kind {kind} (0 = plain row, 1 = warped)")
+        g = q["g"]
+        if kind == 0:
+            try:
+                validate_frames(geom["g"][i:i + 1], arena_bytes, H, W)
+            except ValueError as e:
+                raise ValueError(f"frame {i}:" + str(e).split(":", 1)[1]) from None
+            continue
+        off, h0, w0, pitch, ch, nh, nw, top, left = (int(g[k]) for k in ("offset", "h0", "w0", "pitch", "ch", "nh", "nw", "top", "left"))
+        hs, ws, border = int(q["hs"]), int(q["ws"]), int(q["border"])
+        if ch not in (1, 3):
+            raise ValueError(f"frame {i}: {ch} interleaved channels (1 or 3)")
+        if hs < 1 or ws < 1:
+            raise ValueError(f"frame {i}: empty source frame ({hs}x{ws})")
+        if h0 < 1 or w0 < 1 or nh < 1 or nw < 1:
+            raise ValueError(f"frame {i}: empty aligned frame or resized block ({h0}x{w0} -> {nh}x{nw})")
+        if pitch < ws * ch:
+            raise ValueError(f"frame {i}: pitch {pitch} is less than a source row of {ws} pixels x {ch} channels")
+        if off < 0 or off % 16:
+            raise ValueError(f"frame {i}: offset {off} must be a non-negative multiple of 16")
+        if off + hs * pitch > arena_bytes:
+            raise ValueError(f"frame {i}: bytes [{off}, {off + hs * pitch}) leave the arena of {arena_bytes} bytes")
+        if top < 0 or left < 0 or top + nh > H or left + nw > W:
+            raise ValueError(f"frame {i}: resized block {nh}x{nw} at ({top}, {left}) leaves the {H}x{W} output")
+        if not (g["sx"] > 0 and g["sy"] > 0):
+            raise ValueError(f"frame {i}: tap scales must be positive")
+        if not 0 <= border <= 255:
+            raise ValueError(f"frame {i}: border {border} outside 0..255")
+        if not np.isfinite(q["m"]).all():
+            raise ValueError(f"frame {i}: the alignment matrix has a non-finite entry")
+
+
+def warp_letterbox_staged(q, tile):
+    """The stage rule of icaf_letterbox_warp_frames for one table row and one 32 x 64 output tile (include/icaf.h), tile = (tile row, tile
+    column): True = the tile copies a box of the source frame into LDS and taps it, False = it taps global memory (a tile of padding
+    only, a corner behind the horizon or with non-finite coordinates, a box outside the frame or beyond the budget).  The device's own
+    fp32 operations, one by one.  A kind-0 row follows letterbox_staged."""
+    g = q["g"]
+    if int(q["kind"]) == 0:
+        return letterbox_staged(g)
+    f32 = np.float32
+    by, bx = (int(v) for v in tile)
+    top, left, nh, nw = (int(g[k]) for k in ("top", "left", "nh", "nw"))
+    ra, rb = max(by * 32, top) - top, min(by * 32 + 32, top + nh) - 1 - top
+    ca, cb = max(bx * 64, left) - left, min(bx * 64 + 64, left + nw) - 1 - left
+    if ra > rb or ca > cb:
+        return False
+
+    def tap(j, scale, n):
+        s = (f32(j) + f32(0.5)) * f32(scale)
+        i = int(np.floor(s - f32(0.5)))
+        return min(max(i, 0), n - 1), min(max(i + 1, 0), n - 1)
+    (ylo, _), (_, yhi) = tap(ra, g["sy"], int(g["h0"])), tap(rb, g["sy"], int(g["h0"]))
+    (xlo, _), (_, xhi) = tap(ca, g["sx"], int(g["w0"])), tap(cb, g["sx"], int(g["w0"]))
+    m = np.asarray(q["m"], f32)
+    x, y = np.array([xlo, xhi, xlo, xhi], f32), np.array([ylo, ylo, yhi, yhi], f32)
+    with np.errstate(all="ignore"):
+        Z = (m[6] * x + m[7] * y) + m[8]
+        u, v = ((m[0] * x + m[1] * y) + m[2]) / Z, ((m[3] * x + m[4] * y) + m[5]) / Z
+    if not ((Z > 0).all() and np.isfinite(u).all() and np.isfinite(v).all()):
+        return False
+    ilo, ihi = max(np.floor(u.min()) - f32(1), f32(0)), min(np.floor(u.max()) + f32(2), f32(int(q["ws"]) - 1))
+    jlo, jhi = max(np.floor(v.min()) - f32(1), f32(0)), min(np.floor(v.max()) + f32(2), f32(int(q["hs"]) - 1))
+    if not (ilo <= ihi and jlo <= jhi):
+        return False
+    ncols, nrows = int(ihi) - int(ilo) + 1, int(jhi) - int(jlo) + 1
+    return nrows * ((ncols * int(g["ch"]) + 30) >> 4) * 16 <= _lib.WARP_LDS_BYTES
+
+
+def letterbox_warp_frames(arena, geom, geom_dev, dst, swap_rb=True, name="letterbox_warp_frames"):
+    """letterbox_frames for tables of calibrated pairs (icaf_letterbox_warp_frames): kind-1 rows are seen through their homography at the
+    bilinear taps and equal letterbox(utils.datasets.warp_perspective(...)) byte for byte, kind-0 rows are letterbox_frames' own.  geom:
+    the HOST WARP_GEOM_DTYPE rows the device table `geom_dev` holds — or will hold by the time the launch runs, for a table refreshed per
+    step (validate_warp_frames each refresh) — validated here, before any device call."""
+    if geom.dtype != WARP_GEOM_DTYPE:
+        raise ValueError("the descriptor rows must be WARP_GEOM_DTYPE rows (pack_warp_frames)")
+    n = len(geom)
+    B, ctot, H, W = _frames_tensors(arena, dst, n, geom_dev, WARP_GEOM_DTYPE.itemsize)
+    validate_warp_frames(geom, arena.numel(), H, W)
+    if not (arena.is_cuda and dst.is_cuda and geom_dev.is_cuda):
+        raise ValueError("arena, table and dst must be cuda tensors (no CPU fallback exists)")
+    nb = n * 3 * H * W                                          # at most: source frames read once, planes written once
+    for q in geom:
+        g = q["g"]
+        nb += (int(q["hs"]) * int(q["ws"]) if int(q["kind"]) else int(g["h0"]) * int(g["w0"])) * int(g["ch"])
+    return Launch(lib().icaf_letterbox_warp_frames, (arena.data_ptr(), geom_dev.data_ptr(), n // B, B, dst.data_ptr(), ctot, H, W, int(bool(swap_rb))),
+                  keep=(arena, geom_dev, dst), name=name, nbytes=nb)
+
+
+def warp_frame_lists(rgb, ir, align):
+    """frame_lists for a calibrated pair: align = (A_rgb, A_ir), exactly one of them not None — that modality is seen through its
+    alignment (alignment_matrices: a (3, 3) or (B, 3, 3) aligned -> source matrix, or "stretch") and may have any size per frame; the
+    OTHER modality's frame sizes are the aligned sizes.  Returns (frames_rgb, frames_ir, shapes, uniform, m, src_shapes, matrices): the two
+    lists of B frames, the aligned (h0, w0), per modality whether it came as one 4-D tensor, the aligned modality's index, its frames'
+    (hs, ws) and the float32 (B, 3, 3) matrices.  Anything else raises ValueError."""
+    try:
+        a_rgb, a_ir = align
+    except (TypeError, ValueError):
+        raise ValueError("align=(A_rgb, A_ir): one entry per modality, None for the modality that is not warped") from None
+    if a_rgb is not None and a_ir is not None:
+        raise ValueError("align=(A_rgb, A_ir): both modalities carry an alignment; one of them defines the aligned space and stays None")
+    if a_rgb is None and a_ir is None:
+        raise ValueError("align=(A_rgb, A_ir): neither modality carries an alignment (plain pairs: leave align=None)")
+    m = 0 if a_rgb is not None else 1
+    uniform = tuple(torch.is_tensor(t) and t.dim() == 4 for t in (rgb, ir))
+    fr = [[t[i] for i in range(t.shape[0])] if u else list(t) if isinstance(t, (list, tuple)) else None for t, u in zip((rgb, ir), uniform)]
+    if fr[0] is None or fr[1] is None or not fr[0] or len(fr[0]) != len(fr[1]):
+        raise ValueError("native frames come as two (B, H0, W0, ch) tensors or two equally long lists of (H0, W0, ch) tensors")
+    for f in fr[0] + fr[1]:
+        if not torch.is_tensor(f) or f.dtype != torch.uint8 or f.dim() != 3 or f.shape[2] not in (1, 3) or f.shape[0] < 1 or f.shape[1] < 1:
+            raise ValueError("frames must be uint8 tensors of shape (H0, W0, ch), ch = 3 or 1")
+    shapes = [tuple(int(v) for v in f.shape[:2]) for f in fr[1 - m]]
+    src_shapes = [tuple(int(v) for v in f.shape[:2]) for f in fr[m]]
+    return fr[0], fr[1], shapes, uniform, m, src_shapes, alignment_matrices(a_rgb if m == 0 else a_ir, src_shapes, shapes)
 
 
 def val_geometry(shapes, img_size, batch_shape):

@@ -47,7 +47,8 @@ HOST_FED_BRANCHES = OPT.pipe_branches             # keep the hipGraph's parallel
 class DetectionPipeline:
     def __init__(self, model, batch, height, width, device, conf_thres=0.25, iou_thres=0.45, classes=None,
                  agnostic=False, multi_label=False, max_det=300, world=1, overlap=True, force_gather=False, depth=1, u8=False, augment=False,
-                 frames=None, frame_channels=(3, 3), frames_bgr=True, round_boxes=False, frame_formats=(None, None), yuv_matrix="bt601"):
+                 frames=None, frame_channels=(3, 3), frames_bgr=True, round_boxes=False, frame_formats=(None, None), yuv_matrix="bt601",
+                 frame_align=(None, None), align_frames=None, align_border=0):
         """frames=(max_h0, max_w0): the pipeline also takes NATIVE camera frames (`submit_frames`; implies u8): every plan owns a frame arena
         for `batch` pairs of up to that size (frame_channels: interleaved channels of the RGB / IR frames, 3 or 1) and a geometry table;
         the letterbox runs on the device in front of the plan and the boxes come back in native image space (round_boxes: torch.round
@@ -56,6 +57,10 @@ class DetectionPipeline:
         interleaved frames of frame_channels) and is submitted as the decoder's contiguous buffer, (B, 3 * H0 // 2, W0) or a list of (3 * H0_i
         // 2, W0_i); its half of the arena holds 1.5 bytes per pixel and the conversion (yuv_matrix: "bt601" | "bt709" | "bt601-full") runs
         inside the letterbox, equal to utils.datasets.yuv420_to_bgr in front of the host letterbox byte for byte.
+        frame_align=(None, True) (or (True, None)): a CALIBRATED rig — the marked modality is seen through a homography that
+        `submit_frames(..., align=M)` takes per submit (Model.forward_frames' align=); its frames may have any size up to align_frames=
+        (max_hs, max_ws), which sizes its half of every arena, while frames= stays the other, the aligned, modality's maximum.  Pixels
+        the source does not cover are align_border.  Boxes come back in the un-warped modality's native space.
         augment=True: every step is a test-time-augmentation step (Model.forward(augment=True), reference models/yolo_test.py:116-131:
         the plans are engine.TtaPlan objects) and NMS runs over the merged rows of the three passes (55,755 per image at 640 x 640).
         u8=True: the plans take the dataloader's uint8 (B, 6, H, W) RGB+IR batch (Model.forward_u8: `/255`, split and cast in the
@@ -130,10 +135,14 @@ class DetectionPipeline:
         self.frames = None
         if frames is None and any(f is not None for f in frame_formats):
             raise ValueError("frame_formats describes native frames: pass frames=(max_h0, max_w0) with it")
+        if frames is None and (any(frame_align) or align_frames is not None):
+            raise ValueError("frame_align / align_frames describe native frames: pass frames=(max_h0, max_w0) with them")
         if frames is not None:
-            self._init_frames(batch, height, width, frames, frame_channels, frames_bgr, round_boxes, frame_formats, yuv_matrix)
+            self._init_frames(batch, height, width, frames, frame_channels, frames_bgr, round_boxes, frame_formats, yuv_matrix,
+                              frame_align, align_frames, align_border)
 
-    def _init_frames(self, B, H, W, frames, chans, bgr, round_boxes, formats=(None, None), yuv_matrix="bt601"):
+    def _init_frames(self, B, H, W, frames, chans, bgr, round_boxes, formats=(None, None), yuv_matrix="bt601", frame_align=(None, None),
+                     align_frames=None, align_border=0):
         """Per plan: a byte arena (RGB frames in its first half, IR frames in its second) and ONE table allocation — 2B descriptor rows
         for the letterbox, then B scale_coords rows for scale_detections — with a pinned host twin it is copied from."""
         max_h0, max_w0 = int(frames[0]), int(frames[1])
@@ -144,9 +153,22 @@ class DetectionPipeline:
         if len(formats) != 2 or any(f is not None and f not in ops.YUV_LAYOUTS for f in formats):
             raise ValueError(f"frame_formats=(fmt_rgb, fmt_ir), each None or one of {', '.join(ops.YUV_LAYOUTS)}, got {formats!r}")
         yuv = any(formats)                                                       # then the table holds icaf_yuv_geom rows
+        frame_align = tuple(bool(a) for a in frame_align)
+        if len(frame_align) != 2 or all(frame_align):
+            raise ValueError("frame_align=(None, True) or (True, None): one modality is aligned, the other defines the aligned space")
+        warp = frame_align.index(True) if any(frame_align) else None            # then the table holds icaf_warp_geom rows
+        if (warp is None) != (align_frames is None):
+            raise ValueError("frame_align marks the aligned modality and align_frames=(max_hs, max_ws) sizes its frames: pass both or neither")
+        if warp is not None and yuv:
+            raise ValueError("frame_align takes interleaved frames; a YUV 4:2:0 modality (frame_formats) cannot be combined with it yet")
+        smax, border = (max_h0, max_w0), int(align_border)
+        if warp is not None:
+            smax = (int(align_frames[0]), int(align_frames[1]))
+            if min(smax) < 1 or not 0 <= border <= 255:
+                raise ValueError(f"align_frames=(max_hs, max_ws) and align_border in 0..255, got {align_frames} / {align_border}")
         A = ops.FRAME_ALIGN
         # bytes per modality: interleaved frames of c channels, or 1.5 bytes per pixel (luma + 4:2:0 chroma of the even sizes buffers come in)
-        per_frame = [max_h0 * max_w0 * c if fmt is None else max_h0 * max_w0 + 2 * ((max_h0 + 1) // 2) * ((max_w0 + 1) // 2) for c, fmt in zip(chans, formats)]
+        per_frame = [smax[0] * smax[1] * c if m == warp else max_h0 * max_w0 * c if fmt is None else max_h0 * max_w0 + 2 * ((max_h0 + 1) // 2) * ((max_w0 + 1) // 2) for m, (c, fmt) in enumerate(zip(chans, formats))]
         cap = [B * (-(-n // A) * A) for n in per_frame]
         probe, _ = ops.frame_geometry([(max_h0, max_w0)] * B, (H, W))
         probe = np.concatenate((probe, probe))
@@ -154,6 +176,11 @@ class DetectionPipeline:
             matrix = ops.yuv_matrix_code(yuv_matrix)
             lay = [fmt if fmt is not None else c for c, fmt in zip(chans, formats)]
             probe = np.concatenate((ops.pack_yuv_frames(probe[:B], lay[0], matrix=matrix)[0], ops.pack_yuv_frames(probe[B:], lay[1], matrix=matrix, base=cap[0])[0]))
+        elif warp is not None:
+            matrix, lay = 0, list(chans)
+            src = [(smax[0], smax[1], chans[m]) if m == warp else chans[m] for m in (0, 1)]
+            mat = [np.eye(3, dtype=np.float32) if m == warp else None for m in (0, 1)]
+            probe = np.concatenate((ops.pack_warp_frames(probe[:B], src[0], mat[0], border)[0], ops.pack_warp_frames(probe[B:], src[1], mat[1], border, base=cap[0])[0]))
         else:
             matrix, lay = 0, list(chans)
             ops.pack_frames(probe[:B], chans[0])
@@ -161,7 +188,8 @@ class DetectionPipeline:
         gb = 2 * B * probe.dtype.itemsize
         self.frames = {"B": B, "H": H, "W": W, "max": (max_h0, max_w0), "chans": chans, "cap": cap, "geom_bytes": gb, "cache": {},
                        "arena": [], "tab_dev": [], "tab_host": [], "letterbox": [], "scale_rows": [], "scale_launch": {}, "pending": None,
-                       "round": bool(round_boxes), "formats": formats, "yuv": yuv, "matrix": matrix, "layouts": lay}
+                       "round": bool(round_boxes), "formats": formats, "yuv": yuv, "matrix": matrix, "layouts": lay,
+                       "warp": warp, "smax": smax, "border": border}
         f = self.frames
         for plan in self.plans:
             arena = torch.zeros((sum(cap),), dtype=torch.uint8, device=self.device)
@@ -170,14 +198,15 @@ class DetectionPipeline:
             f["tab_dev"].append(tab)
             f["tab_host"].append(torch.zeros((gb + B * 20,), dtype=torch.uint8).pin_memory())
             f["scale_rows"].append(tab[gb:].view(torch.float32).view(B, 5))
-            f["letterbox"].append((ops.letterbox_yuv_frames if yuv else ops.letterbox_frames)(arena, probe, tab, plan.inputs[0], swap_rb=bgr))
+            launch = ops.letterbox_yuv_frames if yuv else ops.letterbox_warp_frames if warp is not None else ops.letterbox_frames
+            f["letterbox"].append(launch(arena, probe, tab, plan.inputs[0], swap_rb=bgr))
 
-    def _frame_table(self, shapes, contiguous):
+    def _frame_table(self, shapes, contiguous, src_shapes=None):
         """(table bytes, descriptor rows) of one step's frames, cached per set of shapes: the geometry, the arena layout (a uniform
         batch whose frames are whole 16-byte multiples keeps its layout, so ONE copy per modality moves it; other frames start on
         FRAME_ALIGN boundaries) and the validation against this pipeline's arena and output size."""
         f = self.frames
-        key = (tuple(shapes), contiguous)
+        key = (tuple(shapes), contiguous) + ((tuple(src_shapes),) if src_shapes is not None else ())
         hit = f["cache"].get(key)
         if hit is None:
             B, chans, cap = f["B"], f["chans"], f["cap"]
@@ -188,6 +217,8 @@ class DetectionPipeline:
             geom = np.concatenate((geom1, geom1))
             if f["yuv"]:
                 geom = self._yuv_rows(geom, contiguous)
+            elif f["warp"] is not None:
+                geom = self._warp_rows(geom, contiguous, src_shapes)
             else:
                 for m, base in ((0, 0), (1, cap[0])):
                     rows = geom[m * B:(m + 1) * B]
@@ -199,7 +230,7 @@ class DetectionPipeline:
                         end = ops.pack_frames(rows, chans[m], base=base)
                         if end - base > cap[m]:
                             raise ValueError(f"the frames of modality {m} need {end - base} bytes of the arena's {cap[m]}")
-            (ops.validate_yuv_frames if f["yuv"] else ops.validate_frames)(geom, sum(cap), f["H"], f["W"])
+            (ops.validate_yuv_frames if f["yuv"] else ops.validate_warp_frames if f["warp"] is not None else ops.validate_frames)(geom, sum(cap), f["H"], f["W"])
             table = np.concatenate((geom.view(np.uint8).reshape(-1), scale.view(np.uint8).reshape(-1)))
             if len(f["cache"]) >= 64:
                 f["cache"].pop(next(iter(f["cache"])))
@@ -224,19 +255,51 @@ class DetectionPipeline:
             halves.append(rows)
         return np.concatenate(halves)
 
-    def submit_frames(self, rgb, ir):
+    def _warp_rows(self, geom, contiguous, src_shapes):
+        """_frame_table's arena layout for a calibrated rig: icaf_warp_geom rows, the aligned modality's around its SOURCE frames (identity
+        matrices: submit_frames writes the step's into the pinned table).  A uniform batch in one contiguous tensor whose frames are whole
+        16-byte multiples keeps its layout, other frames start on FRAME_ALIGN boundaries."""
+        f = self.frames
+        B, cap, chans, halves = f["B"], f["cap"], f["chans"], []
+        for hs, ws in src_shapes:
+            if hs > f["smax"][0] or ws > f["smax"][1]:
+                raise ValueError(f"a {hs}x{ws} frame exceeds the pipeline's align_frames={f['smax']}")
+        for m, base in ((0, 0), (1, cap[0])):
+            if m == f["warp"]:
+                rows, end = ops.pack_warp_frames(geom[m * B:(m + 1) * B], [(hs, ws, chans[m]) for hs, ws in src_shapes], [np.eye(3, dtype=np.float32)] * B,
+                                                 f["border"], base=base)
+                fb = int(rows[0]["hs"]) * int(rows[0]["g"]["pitch"])
+            else:
+                rows, end = ops.pack_warp_frames(geom[m * B:(m + 1) * B], chans[m], base=base)
+                fb = int(rows[0]["g"]["h0"]) * int(rows[0]["g"]["pitch"])
+            if contiguous[m]:
+                rows["g"]["offset"] = base + fb * np.arange(B)
+            elif end - base > cap[m]:
+                raise ValueError(f"the frames of modality {m} need {end - base} bytes of the arena's {cap[m]}")
+            halves.append(rows)
+        return np.concatenate(halves)
+
+    def submit_frames(self, rgb, ir, align=None):
         """One batch of NATIVE frames through the pipeline: rgb / ir are uint8 (B, H0, W0, ch) tensors or lists of (H0_i, W0_i, ch) tensors,
         in pinned host memory or on the device (a modality with a frame_formats layout: (B, 3 * H0 // 2, W0) or a list of (3 * H0_i // 2,
         W0_i) buffers, H0 and W0 even); a pair shares its size, sizes may change from step to step.  The frames and the step's
         geometry table are copied on the copy stream(s) under the events submit_u8 uses, the letterbox runs on the plan's forward stream in
         front of its graph, scale_detections on the NMS stream behind NMS: the (det, count) step() returns hold NATIVE-space boxes (rows >=
         count zeroed), and so does the gathered block of a process group.  Host buffers must stay untouched until their copy has run
-        (`pipe.copied[n % pipe.nplans]`, as for submit_u8)."""
+        (`pipe.copied[n % pipe.nplans]`, as for submit_u8).
+        align: for a pipeline built with frame_align, the step's alignment of the marked modality — a (3, 3) array, a (B, 3, 3) array or
+        "stretch" (aligned -> source, Model.forward_frames' align=); it travels in the pinned geometry table with the rest of the rows."""
         f = self.frames
         if f is None:
             raise ValueError("DetectionPipeline(frames=(max_h0, max_w0)) takes native frames")
         B, chans = f["B"], f["chans"]
-        *lists, shapes, uniform = ops.yuv_frame_lists(rgb, ir, f["formats"]) if f["yuv"] else ops.frame_lists(rgb, ir)
+        if (align is None) != (f["warp"] is None):
+            raise ValueError("submit_frames(align=...) goes with DetectionPipeline(frame_align=..., align_frames=...): both or neither")
+        src_shapes = mats = None
+        if f["warp"] is not None:
+            *lists, shapes, uniform, _, src_shapes, mats = ops.warp_frame_lists(rgb, ir, (align, None) if f["warp"] == 0 else (None, align))
+        else:
+            *lists, shapes, uniform = ops.yuv_frame_lists(rgb, ir, f["formats"]) if f["yuv"] else ops.frame_lists(rgb, ir)
         if len(shapes) != B:
             raise ValueError(f"submit_frames expects a batch of {B} pairs, got {len(shapes)}")
         mods, contiguous = [], []
@@ -245,7 +308,7 @@ class DetectionPipeline:
                 raise ValueError(f"modality {m}: frames must be uint8 (H0, W0, {chans[m]}) tensors")
             contiguous.append(bool(uniform[m] and t.is_contiguous() and (t[0].numel() % 16 == 0)))
             mods.append((t, fr))
-        table, geom = self._frame_table(shapes, tuple(contiguous))        # raises before anything is enqueued
+        table, geom = self._frame_table(shapes, tuple(contiguous), src_shapes)        # raises before anything is enqueued
         pi = self.n % self.nplans
         fs = self.fwd_streams[pi % self.depth]
         arena, ncs = f["arena"][pi], len(self.copy_streams)
@@ -253,6 +316,9 @@ class DetectionPipeline:
         if self.n >= self.nplans:
             self.copied[pi][0].synchronize()                                # the last copy OUT of this plan's pinned table (nplans steps ago) has run
         f["tab_host"][pi].copy_(table)
+        if mats is not None:                                                # this step's matrices, into the pinned rows of the aligned modality
+            rows = f["tab_host"][pi].numpy()[:f["geom_bytes"]].view(ops.WARP_GEOM_DTYPE)
+            rows["m"][f["warp"] * B:(f["warp"] + 1) * B] = mats.reshape(B, 9)
         cur = torch.cuda.current_stream(self.device)
         for k, cs in enumerate(self.copy_streams):                          # the batch in `ncs` slices of images, one copy stream each
             lo, hi = B * k // ncs, B * (k + 1) // ncs
@@ -271,7 +337,7 @@ class DetectionPipeline:
                 if k == 0:
                     f["tab_dev"][pi].copy_(f["tab_host"][pi], non_blocking=True)
                 for m, (t, fr) in enumerate(mods):
-                    rows = geom[m * B:(m + 1) * B]["g"] if f["yuv"] else geom[m * B:(m + 1) * B]
+                    rows = geom[m * B:(m + 1) * B]["g"] if f["yuv"] or f["warp"] is not None else geom[m * B:(m + 1) * B]
                     if contiguous[m]:
                         o, fb = int(rows[lo]["offset"]), t[0].numel()
                         arena[o:o + (hi - lo) * fb].view(t[lo:hi].shape).copy_(t[lo:hi], non_blocking=True)

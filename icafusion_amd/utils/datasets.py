@@ -194,6 +194,91 @@ def yuv420_to_bgr(y, cb, cr, matrix=0):
     return np.clip(np.stack((b, g, r), axis=2), 0, 255).astype(np.uint8)
 
 
+def warp_perspective(img, M, out_hw, border=0):
+    """THE registration of a calibrated RGB / IR pair (icaf_letterbox_warp_frames equals letterbox() of this image byte for byte): img
+    (hs, ws) or (hs, ws, ch) uint8 -> (h, w, ch) uint8, the source frame seen through the homography M.  M (3 x 3, rounded to float32
+    once) maps ALIGNED pixel coordinates to SOURCE pixel coordinates — x right, y down, an integer is a pixel centre: the matrix
+    cv2.warpPerspective takes with WARP_INVERSE_MAP, the inverse of findHomography(src_pts, aligned_pts).  All float32, every operation
+    rounded on its own, for aligned pixel (x, y):
+      X = (m00 x + m01 y) + m02, Y = (m10 x + m11 y) + m12, Z = (m20 x + m21 y) + m22, u = X / Z, v = Y / Z (IEEE divisions);
+      ok = Z > 0 and -1 < u < ws and -1 < v < hs (false on NaN: the far side of a horizon is not ok); not ok: `border` in every channel;
+      i0 = floor(u), fu = u - i0, j0 / fv likewise from v; a tap (j, i) inside the frame is its byte, outside it `border` (constant
+      border, no clamping); top = a00 (1 - fu) + a01 fu, bot likewise, out = top (1 - fv) + bot fv, result floor(out + 0.5) clipped to 0..255."""
+    img = np.asarray(img)
+    if img.dtype != np.uint8 or img.ndim not in (2, 3):
+        raise ValueError(f"warp_perspective takes a uint8 (hs, ws) or (hs, ws, ch) frame, got {img.dtype} {img.shape}")
+    if img.ndim == 2:
+        img = img[:, :, None]
+    hs, ws, ch = img.shape
+    h, w = int(out_hw[0]), int(out_hw[1])
+    border = int(border)
+    if hs < 1 or ws < 1 or h < 1 or w < 1 or not 0 <= border <= 255:
+        raise ValueError(f"warp_perspective: empty frame ({hs}x{ws} -> {h}x{w}) or border {border} outside 0..255")
+    m = np.asarray(M, np.float64).astype(np.float32)
+    if m.shape != (3, 3):
+        raise ValueError(f"warp_perspective takes a 3 x 3 matrix, got shape {m.shape}")
+    f32 = np.float32
+    x, y = np.arange(w, dtype=f32)[None, :], np.arange(h, dtype=f32)[:, None]
+    with np.errstate(all="ignore"):
+        X = (m[0, 0] * x + m[0, 1] * y) + m[0, 2]
+        Y = (m[1, 0] * x + m[1, 1] * y) + m[1, 2]
+        Z = (m[2, 0] * x + m[2, 1] * y) + m[2, 2]
+        u, v = X / Z, Y / Z
+        ok = (Z > 0) & (u > f32(-1)) & (u < f32(ws)) & (v > f32(-1)) & (v < f32(hs))
+    u, v = np.where(ok, u, f32(0)), np.where(ok, v, f32(0))
+    fi, fj = np.floor(u), np.floor(v)
+    fu, fv = (u - fi)[:, :, None], (v - fj)[:, :, None]
+    i0, j0 = fi.astype(np.int64), fj.astype(np.int64)
+    src = img.astype(f32)
+
+    def tap(j, i):
+        inside = ((j >= 0) & (j < hs) & (i >= 0) & (i < ws))[:, :, None]
+        return np.where(inside, src[np.clip(j, 0, hs - 1), np.clip(i, 0, ws - 1)], f32(border))
+    top = tap(j0, i0) * (f32(1) - fu) + tap(j0, i0 + 1) * fu
+    bot = tap(j0 + 1, i0) * (f32(1) - fu) + tap(j0 + 1, i0 + 1) * fu
+    out = top * (f32(1) - fv) + bot * fv
+    out = np.clip(np.floor(out + f32(0.5)), 0, 255).astype(np.uint8)
+    return np.where(ok[:, :, None], out, np.uint8(border))
+
+
+def stretch_alignment(src_hw, aligned_hw):
+    """The alignment matrix of "same field of view, other resolution" (half-pixel centres): a (hs, ws) source under an (h0, w0) aligned
+    frame, u = (x + 0.5) ws / w0 - 0.5 and v likewise, computed in float64 and rounded to float32.  Equal sizes give the identity."""
+    (hs, ws), (h0, w0) = (int(v) for v in src_hw), (int(v) for v in aligned_hw)
+    if min(hs, ws, h0, w0) < 1:
+        raise ValueError(f"stretch_alignment: empty size {hs}x{ws} / {h0}x{w0}")
+    return np.array([[ws / w0, 0.0, 0.5 * ws / w0 - 0.5], [0.0, hs / h0, 0.5 * hs / h0 - 0.5], [0.0, 0.0, 1.0]], np.float64).astype(np.float32)
+
+
+def load_alignment(path, inverse=False):
+    """A rig's 3 x 3 alignment matrix from a .npy file or a text file of nine numbers separated by white space and / or commas, as
+    float32.  The file holds the ALIGNED -> SOURCE matrix warp_perspective takes; inverse=True: it holds SOURCE -> aligned
+    (findHomography(src_pts, aligned_pts)) and is inverted in float64 first.  ValueError for a wrong count, a non-finite entry and,
+    under inverse, a singular matrix."""
+    path = str(path)
+    if path.endswith(".npy"):
+        a = np.asarray(np.load(path, allow_pickle=False), np.float64).reshape(-1)
+    else:
+        with open(path) as f:
+            words = f.read().replace(",", " ").split()
+        try:
+            a = np.array([float(t) for t in words], np.float64)
+        except ValueError:
+            raise ValueError(f"{path}: an alignment file holds nine numbers, got {words[:12]!r}") from None
+    if a.size != 9:
+        raise ValueError(f"{path}: an alignment matrix has nine entries, got {a.size}")
+    if not np.isfinite(a).all():
+        raise ValueError(f"{path}: the alignment matrix has a non-finite entry")
+    a = a.reshape(3, 3)
+    if inverse:
+        if not abs(np.linalg.det(a)) > 0 or not np.isfinite(np.linalg.cond(a)) or np.linalg.cond(a) > 1e15:
+            raise ValueError(f"{path}: the matrix is singular and has no inverse (--align-inverse / inverse=True)")
+        a = np.linalg.inv(a)
+        if not np.isfinite(a).all():
+            raise ValueError(f"{path}: the matrix is singular and has no inverse (--align-inverse / inverse=True)")
+    return a.astype(np.float32)
+
+
 def _list_images(path):
     p = str(Path(path).absolute())
     if "*" in p:

@@ -40,7 +40,7 @@ const char* icaf_last_error(void);
 /* Probe knobs of the library, set by the host's one options object (icafusion_amd/options.py) when the library is loaded — the library reads no
  * environment variable: "detect_elementwise" (!= 0: icaf_detect_decode by the one-thread-per-element kernel), "attn_qsplit" (n > 0: query splits per
  * head of icaf_cross_attention), "sppf_vpb" (n > 0: cap on the channel vectors per workgroup of icaf_sppf_pool), "letterbox_direct" (!= 0:
- * icaf_letterbox_frames and icaf_letterbox_yuv_frames tap global memory in every tile instead of staging in LDS; set by a caller for an A/B, not by the options object),
+ * icaf_letterbox_frames, icaf_letterbox_yuv_frames and icaf_letterbox_warp_frames tap global memory in every tile instead of staging in LDS; set by a caller for an A/B, not by the options object),
  * "index64" (!= 0: the element kernel of icaf_dmff_pool_tokens and icaf_upsample_nearest launch the 64-bit-index instantiations they otherwise
  * keep for 2^31 vectors and more), "attn_stream" (!= 0: icaf_cross_attention launches the key-streaming form for every shape, for A/B timings
  * and tests; set by a caller, not by the options object), "area_direct" (!= 0: the area rows of icaf_resize_frames recompute their vertical
@@ -493,6 +493,47 @@ typedef struct icaf_yuv_geom {
 } icaf_yuv_geom;           /* 80 bytes */
 int icaf_letterbox_yuv_frames(const void* arena, const icaf_yuv_geom* geom, int nstreams, int B, void* dst, int ctot, int H, int W,
                               int swap_rb, icaf_stream_t s);
+
+/* ---- calibrated RGB / IR pairs (utils/datasets.py: warp_perspective, then letterbox) -----------------------------------------
+ * icaf_letterbox_warp_frames: icaf_letterbox_frames for a pair whose two cameras are registered by a homography, byte for byte equal
+ *   to letterbox(warp_perspective(frame, m, (h0, w0), border)): WARP AT THE TAPS, the aligned frame never exists in memory.  arena, dst,
+ *   nstreams, B, ctot, H, W, the grid, the 32 x 64 tile, the alignment rules, the refusals and "every byte of the planes written exactly
+ *   once, 114 outside the block" are icaf_letterbox_frames'; geom: DEVICE table of nstreams * B 104-byte rows, entry modality * B + image.
+ *   kind 0: g is exactly icaf_letterbox_frames' row and the tile produces exactly its bytes (the same device function), swap_rb
+ *     included; the other fields are not read.
+ *   kind 1: g.h0 / g.w0 are the ALIGNED size (the other modality's native size) and nh / nw / top / left / sx / sy its letterbox;
+ *     g.offset / g.pitch / g.ch describe the SOURCE frame of hs x ws pixels.  The letterbox's four taps of an output pixel are ALIGNED
+ *     pixels (y, x), its clamped tap indices; each is evaluated from the source and rounded to a byte per channel, then
+ *     icaf_letterbox_frames' fp32 tap arithmetic runs on those bytes.  Aligned pixel (x, y), all fp32, every operation rounded on its
+ *     own (built with fp contraction off), m row-major and mapping aligned -> source pixel coordinates (integers are pixel centres):
+ *       X = (m[0] x + m[1] y) + m[2], Y = (m[3] x + m[4] y) + m[5], Z = (m[6] x + m[7] y) + m[8], u = X / Z, v = Y / Z (IEEE divisions);
+ *       ok = Z > 0 && u > -1 && u < ws && v > -1 && v < hs (false on NaN); not ok: the pixel is `border` in every channel;
+ *       i0 = floor(u), fu = u - i0, j0 / fv likewise; a tap (j, i) inside the source frame is its byte, a tap outside is `border`;
+ *       top = a00 (1 - fu) + a01 fu, bot likewise, out = top (1 - fv) + bot fv, the byte floor(out + 0.5f) clipped to 0..255.
+ *     A pixel's coordinates are computed once for its channels; a letterbox tap whose weight is +0 is not evaluated (it adds +0).
+ *     `border` fills aligned pixels the source does not cover; the padding outside the resized block stays 114.
+ *   Stage rule of a kind-1 tile: the aligned rectangle the tile's resized pixels tap (lb_tap at its first and last resized row and
+ *   column: first index of the first, second index of the last) has four corners; each is warped by the rule above.  If all four have
+ *   Z > 0 and finite u, v, the box [floor(min u) - 1, floor(max u) + 2] x [floor(min v) - 1, floor(max v) + 2] (fp32), cut to the frame,
+ *   is not empty and its rows of (ncols * ch + 30) / 16 16-byte vectors fit ICAF_WARP_LDS_BYTES, the box is staged in LDS with aligned
+ *   16-byte loads (single bytes in the frame's last, partial vector) and taps read LDS; a tap outside the box reads global memory, so the
+ *   bytes do not depend on the box.  Otherwise, or with the probe knob "letterbox_direct", every in-frame tap is a global byte load.  No
+ *   load leaves the source frame's hs * pitch bytes.
+ *   The host guarantees (icafusion_amd/ops.py validate_warp_frames): kind 0 rows as icaf_letterbox_frames asks; kind 1: ch 1 or 3,
+ *   hs, ws, h0, w0, nh, nw >= 1, pitch >= ws * ch, offset % 16 == 0, offset + hs * pitch inside the arena, the block inside H x W,
+ *   sx, sy > 0, border 0..255, nine finite matrix entries. */
+enum { ICAF_WARP_LDS_BYTES = 20480 };    /* a 512 x 640 grey source under a 1080 x 1920 aligned frame letterboxed to 640 stages about 52 rows of 6 vectors: 5 KB */
+typedef struct icaf_warp_geom {
+    icaf_frame_geom g;     /* kind 0: exactly icaf_letterbox_frames' row.  kind 1: h0 / w0 = the ALIGNED size, nh / nw / top / left / sx / sy its
+                              letterbox; offset / pitch / ch describe the SOURCE frame */
+    int kind;              /* 0 plain, 1 warped */
+    int hs, ws;            /* source size (kind 1) */
+    int border;            /* 0..255 */
+    float m[9];            /* row-major, aligned -> source */
+    int reserved;
+} icaf_warp_geom;          /* 104 bytes */
+int icaf_letterbox_warp_frames(const void* arena, const icaf_warp_geom* geom, int nstreams, int B, void* dst, int ctot, int H, int W,
+                               int swap_rb, icaf_stream_t s);
 
 /* ---- native validation frames(utils/datasets.py:1116-1122, load_image_rgb_ir: longest side to img_size, then letterbox's padding) ----
  * icaf_resize_frames: icaf_letterbox_frames with a resize mode per descriptor, so that one launch serves a rectangular validation batch
