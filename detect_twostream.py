@@ -15,6 +15,11 @@ mapping of the boxes back to the image then run on the device (Model.forward_fra
 that maps visible (aligned) pixel coordinates to thermal pixel coordinates (utils.datasets.load_alignment; --align-inverse: the file maps thermal to
 visible), `stretch` is "same field of view, other resolution".  With --device-letterbox the matrix goes to Model.forward_frames(align=...) and the
 thermal frame is registered at the letterbox's taps; without it the host calls utils.datasets.warp_perspective in front of letterbox.  Same outputs.
+`--ir-16bit` reads --source2 as 16-bit greyscale PNG / TIFF files of raw thermal counts (utils.datasets.imread_u16).  Automatic gain control maps them
+to the 8-bit image the network was trained on: a percentile window per frame (`--ir-agc-clip LO_PCT HI_PCT`, default 1 1) or a fixed one
+(`--ir-window LO HI`, raw counts).  With --device-letterbox the counts go to Model.forward_frames(formats=(None, "y16")) and are mapped at the
+letterbox's taps; without it the host calls utils.datasets.agc_window / agc_u16_to_u8 in front of letterbox.  Same outputs; the annotated thermal
+picture is the host-mapped frame on either path.
 `Done. (…s, …Hz)` and final `Average Speed` lines are the reference's (:160,198).  Webcam / video sources, the
 second-stage classifier and --view-img need OpenCV and are out of scope."""
 import argparse
@@ -27,7 +32,7 @@ import torch
 from icafusion_amd import ops
 from icafusion_amd.models.experimental import load_detector
 from icafusion_amd.utils.confluence import confluence_process
-from icafusion_amd.utils.datasets import LoadImages, imwrite_bgr, letterbox, load_alignment, stretch_alignment, warp_perspective
+from icafusion_amd.utils.datasets import LoadImages, agc_u16_to_u8, agc_window, imwrite_bgr, letterbox, load_alignment, stretch_alignment, warp_perspective
 from icafusion_amd.utils.general import increment_path, non_max_suppression, scale_coords, xyxy2xywh
 from icafusion_amd.utils.torch_utils import select_device, time_synchronized
 
@@ -65,12 +70,35 @@ def detect(opt):
     border = int(getattr(opt, "align_border", 0))
     if align is not None and align != "stretch":
         align = load_alignment(align, inverse=bool(getattr(opt, "align_inverse", False)))
+    raw16 = bool(getattr(opt, "ir_16bit", False))                  # --source2 holds raw 16-bit thermal counts: gain control in front of the network
+    ir_window = getattr(opt, "ir_window", None)
+    ir_clip = getattr(opt, "ir_agc_clip", None)
+    if not raw16 and (ir_window is not None or ir_clip is not None):
+        raise ValueError("--ir-window / --ir-agc-clip describe 16-bit thermal frames: pass --ir-16bit with them")
+    if raw16 and align is not None:
+        raise ValueError("--ir-16bit does not go with --align-ir yet: the registration reads 8-bit frames")
+    if ir_window is not None and ir_clip is not None:
+        raise ValueError("--ir-window fixes the gain-control window, --ir-agc-clip picks it per frame: pass one of them")
+    if ir_window is not None and not 0 <= ir_window[0] <= ir_window[1] <= 65535:
+        raise ValueError(f"--ir-window LO HI must satisfy 0 <= LO <= HI <= 65535, got {ir_window}")
+    ir_clip = (100, 100) if ir_clip is None else tuple(int(round(100 * p)) for p in ir_clip)      # per cent -> basis points
+    if not all(0 <= c <= 4999 for c in ir_clip):
+        raise ValueError("--ir-agc-clip LO_PCT HI_PCT: each between 0 and 49.99 per cent")
     dataset = LoadImages(opt.source1, opt.img_size, stride, native=on_device)
-    dataset2 = LoadImages(opt.source2, opt.img_size, stride, native=on_device or align is not None)
+    dataset2 = LoadImages(opt.source2, opt.img_size, stride, native=on_device or align is not None, raw16=raw16)
     if len(dataset) != len(dataset2):
         raise ValueError(f"{len(dataset)} visible images vs {len(dataset2)} infrared images")
     t0, img_num, fps_sum = time.time(), 0, 0.0
     for (path, img, im0, _), (path2, img2, im0_, _) in zip(dataset, dataset2):
+        if raw16:
+            raw = im0_
+            if raw.shape != im0.shape[:2]:
+                raise ValueError(f"{path2}: the thermal frame is {raw.shape}, the visible one {im0.shape[:2]}")
+            if not on_device or save_img:                              # the mapped thermal frame on the host: the network's input, or only the picture
+                lo, hi = tuple(ir_window) if ir_window is not None else agc_window(raw, ir_clip)
+                im0_ = np.repeat(agc_u16_to_u8(raw, lo, hi)[:, :, None], 3, axis=2)
+            if not on_device:
+                img2 = np.ascontiguousarray(letterbox(im0_, opt.img_size, stride=stride)[0][:, :, ::-1].transpose(2, 0, 1))
         if align is not None:
             M = stretch_alignment(im0_.shape[:2], im0.shape[:2]) if isinstance(align, str) else align
             if not on_device or save_img:                              # the registered thermal frame on the host: the network's input, or only the picture
@@ -79,6 +107,10 @@ def detect(opt):
                 img2 = np.ascontiguousarray(letterbox(im0_, opt.img_size, stride=stride)[0][:, :, ::-1].transpose(2, 0, 1))
         if on_device and align is not None:
             frames = [torch.from_numpy(np.ascontiguousarray(x)).unsqueeze(0).to(device) for x in (im0, ir_src if save_img else im0_)]
+            net_shape = (opt.img_size, opt.img_size)
+        elif on_device and raw16:                                      # the counts as their bytes, (1, H0, 2 * W0): every torch release has uint8
+            frames = [torch.from_numpy(im0).unsqueeze(0).to(device),
+                      torch.from_numpy(np.ascontiguousarray(raw).view(np.uint8).reshape(raw.shape[0], 2 * raw.shape[1])).unsqueeze(0).to(device)]
             net_shape = (opt.img_size, opt.img_size)
         elif on_device:
             frames = [torch.from_numpy(x).unsqueeze(0).to(device) for x in (im0, im0_)]      # uint8 (1, H0, W0, 3) BGR, as decoded
@@ -90,7 +122,8 @@ def detect(opt):
         # /255, RGB/IR split and the cast happen in the staging kernel; --augment: the three passes of models/yolo_test.py:116-131
         if on_device:
             out, geometry = model.forward_frames(frames[0], frames[1], opt.img_size, bgr=True, augment=getattr(opt, "augment", False),
-                                                 **({} if align is None else {"align": (None, M), "align_border": border}))
+                                                 **({} if align is None else {"align": (None, M), "align_border": border}),
+                                                 **({} if not raw16 else {"formats": (None, "y16"), "agc_clip": ir_clip, "agc_window": ir_window}))
             pred = out[0]
         else:
             pred = (model.forward_u8(img6, augment=True) if getattr(opt, "augment", False) else model.forward_u8(img6))[0]
@@ -176,6 +209,11 @@ def parse_opt(argv=None):
                     "that maps visible pixel coordinates to thermal pixel coordinates, or `stretch` (same field of view, other resolution); the "
                     "thermal frame is registered onto the visible one, boxes are in the visible frame")
     ap.add_argument("--align-inverse", action="store_true", help="the --align-ir file maps thermal to visible coordinates (findHomography(ir, visible)): invert it")
+    ap.add_argument("--ir-16bit", action="store_true", help="--source2 holds 16-bit greyscale PNG / TIFF files of raw thermal counts; automatic gain "
+                    "control maps them to 8 bits (on the device with --device-letterbox)")
+    ap.add_argument("--ir-agc-clip", type=float, nargs=2, default=None, metavar=("LO_PCT", "HI_PCT"), help="per cent of the pixels clipped at the "
+                    "low / high end of each thermal frame's histogram (default 1 1)")
+    ap.add_argument("--ir-window", type=int, nargs=2, default=None, metavar=("LO", "HI"), help="a fixed gain-control window in raw counts instead of the per-frame percentiles")
     ap.add_argument("--align-border", type=int, default=0, metavar="N", help="grey level 0..255 of registered pixels the thermal frame does not cover")
     return ap.parse_args(argv)
 

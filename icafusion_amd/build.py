@@ -3,11 +3,11 @@
     python -m icafusion_amd.build [--force]
 
 One object per .hip file (parallel), then one shared library exporting the C ABI of include/icaf.h.
-detect.hip / nms.hip / tta.hip / frames.hip / frames_yuv.hip / frames_warp.hip / resize.hip / missrate.hip / confluence.hip / loss.hip / valstats.hip are built with fp contraction off: their arithmetic must
+detect.hip / nms.hip / tta.hip / frames.hip / frames_yuv.hip / frames_warp.hip / frames_y16.hip / resize.hip / missrate.hip / confluence.hip / loss.hip / valstats.hip are built with fp contraction off: their arithmetic must
 round like the reference's separate fp32 torch ops so that NMS keep-indices are bit-exact (missrate.hip: the fp64 IoU of the KAIST miss-rate
 matching rounds like the evaluator's Python floats; confluence.hip: the fp64 proximity of a box pair rounds like the reference's numpy; tta.hip: the bilinear resize and the box de-scale of test-time
 augmentation mirror torch's CPU expressions operation by operation; frames.hip: the device letterbox equals the numpy
-resize_bilinear of utils/datasets.py byte for byte, and frames_yuv.hip runs the same tap arithmetic on converted YUV 4:2:0 taps, frames_warp.hip on taps seen through a homography (utils.datasets.warp_perspective, IEEE divisions, nothing fused); resize.hip: the validation loader's area down-scale equals resize_area_scalar byte for
+resize_bilinear of utils/datasets.py byte for byte, and frames_yuv.hip runs the same tap arithmetic on converted YUV 4:2:0 taps, frames_warp.hip on taps seen through a homography (utils.datasets.warp_perspective, IEEE divisions, nothing fused), frames_y16.hip on 16-bit thermal taps mapped to bytes by the integer gain-control rule (utils.datasets.agc_u16_to_u8); resize.hip: the validation loader's area down-scale equals resize_area_scalar byte for
 byte; loss.hip: the target assignment of the validation loss compares like the reference's separate fp32 torch ops; valstats.hip: the fp64
 curves of ap_per_class round like numpy's, np.interp's slope expression included).
 
@@ -70,7 +70,7 @@ VGPR_FORM = ["-mllvm", "-amdgpu-mfma-vgpr-form"]
 # (ctile.hip, round 6: the fused Bottleneck + cv3 kernel issues 112 v_accvgpr_read per wave for its seven accumulators and sits at VALU issue 0.70:
 #  115 registers and no AGPRs instead of 100 + 64, 135 -> 133 us; the other convolution files already compile to VGPR accumulators or do not move)
 PER_FILE = {"detect.hip": ["-ffp-contract=off"], "nms.hip": ["-ffp-contract=off"], "tta.hip": ["-ffp-contract=off"],
-            "frames.hip": ["-ffp-contract=off"], "frames_yuv.hip": ["-ffp-contract=off"], "frames_warp.hip": ["-ffp-contract=off"], "resize.hip": ["-ffp-contract=off"], "missrate.hip": ["-ffp-contract=off"],
+            "frames.hip": ["-ffp-contract=off"], "frames_yuv.hip": ["-ffp-contract=off"], "frames_warp.hip": ["-ffp-contract=off"], "frames_y16.hip": ["-ffp-contract=off"], "resize.hip": ["-ffp-contract=off"], "missrate.hip": ["-ffp-contract=off"],
             "confluence.hip": ["-ffp-contract=off"], "loss.hip": ["-ffp-contract=off"], "valstats.hip": ["-ffp-contract=off"], "dmff.hip": VGPR_FORM, "dmff_fused.hip": VGPR_FORM, "ctile.hip": VGPR_FORM}
 _VF = os.environ.get("ICAF_VGPR_FORM", "")             # A/B builds (tools/build_variant.py): "all" = the whole library in that form, "none" = no file
 if _VF == "all":                                       # (the file list IS the source directory: a new .hip file is never left out)

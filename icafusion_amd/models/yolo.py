@@ -586,7 +586,7 @@ class Model(HipModule):
         return self._forward_images((img6,), u8=True, augment=augment)
 
     def forward_frames(self, rgb, ir, img_size=640, bgr=True, augment=False, val_size=None, formats=None, yuv_matrix="bt601", align=None,
-                       align_border=0):
+                       align_border=0, agc_clip=(100, 100), agc_window=None):
         """Forward from NATIVE camera frames: rgb / ir are cuda uint8 tensors (B, H0, W0, ch) in decoder layout (interleaved, ch = 3 or
         1) or lists of (H0_i, W0_i, ch) tensors for ragged sizes; a pair shares its size.  The letterbox to img_size (an int or (H, W);
         utils.datasets.letterbox, byte for byte) runs on the device straight into the uint8 plan's input, then the plan (or the TTA plan)
@@ -609,8 +609,17 @@ class Model(HipModule):
         and FrameGeometry are in the un-warped modality's native space.  The homography is applied at the letterbox's taps
         (icaf_letterbox_warp_frames; pixels the source does not cover are align_border, 0..255): bit-identical to forward_u8 of
         letterbox(warp_perspective(frame, M, (h0, w0), align_border)) beside the plain letterbox of the other frame.  The matrices live in
-        the device table and are rewritten per call: a rig that re-calibrates rebuilds nothing."""
+        the device table and are rewritten per call: a rig that re-calibrates rebuilds nothing.
+        formats=(None, "y16") (either or both modalities): a 16-BIT THERMAL modality, raw counts as a torch.uint16 / torch.int16 (B, H0,
+        W0) tensor, its uint8 bytes (B, H0, 2 * W0), or a list of per-frame tensors.  Automatic gain control runs on the device:
+        agc_clip=(clip_lo, clip_hi), basis points clipped at either end of each frame's histogram (utils.datasets.agc_window), or
+        agc_window=(lo, hi) / a (B, 2) array, a window given by the caller; the counts are mapped to bytes at the letterbox's taps
+        (utils.datasets.agc_u16_to_u8; icaf_y16_window + icaf_letterbox_y16_frames), bit-identical to forward_u8 of the host-mapped,
+        host-letterboxed batch.  FrameGeometry.window holds, per modality, None or the cuda int32 (B, 2) windows this call used (a view
+        of the model's table: the next call of the same shapes overwrites it), so that a caller can feed a damped copy back as agc_window."""
         self._check_eval()
+        if formats is not None and any(f == "y16" for f in formats):
+            return self._forward_y16_frames(rgb, ir, img_size, bgr, augment, val_size, formats, align, agc_clip, agc_window)
         if align is not None:
             return self._forward_warp_frames(rgb, ir, img_size, bgr, augment, val_size, formats, align, align_border)
         if formats is not None and any(f is not None for f in formats):
@@ -676,6 +685,61 @@ class Model(HipModule):
         for o, f in zip(st["geom"]["g"]["offset"], fr[0] + fr[1]):        # a YUV buffer is one run of bytes: luma rows, then its chroma
             st["arena"][int(o):int(o) + f.numel()].view(f.shape).copy_(f)
         st["launch"].args = st["launch"].args[:-1] + (int(bool(bgr)),)
+        st["launch"](ops.current_stream_ptr())
+        plan.run()
+        out = self._result(plan.outputs)
+        return ((out, None) if augment else out), st["info"]
+
+    def _forward_y16_frames(self, rgb, ir, img_size, bgr, augment, val_size, formats, align, clip, window):
+        """forward_frames with at least one 16-bit thermal modality: the same steps around icaf_y16_window, icaf_letterbox_y16_frames and
+        their 72-byte rows.  The state is keyed by the shapes; clip and window are written into the table on every call."""
+        if val_size is not None:
+            raise ValueError("forward_frames: 16-bit thermal frames ('y16') have no validation geometry (val_size); the validation sets are 8-bit")
+        if align is not None:
+            raise ValueError("forward_frames: align= takes interleaved 8-bit frames; a 16-bit thermal modality ('y16') cannot be combined with it yet")
+        try:
+            *fr, shapes, _ = ops.y16_frame_lists(rgb, ir, formats)
+        except ValueError as e:
+            raise ValueError(f"forward_frames expects cuda frames: {e}") from None
+        if not all(f.is_cuda for f in fr[0] + fr[1]):
+            raise ValueError("forward_frames expects cuda frames (no CPU fallback exists)")
+        B, device = len(fr[0]), fr[0][0].device
+        H, W = (img_size, img_size) if isinstance(img_size, int) else img_size
+        self._check_stride(H, W, int(self.stride.max()))
+        layouts = tuple(fmt if fmt is not None else int(f.shape[2]) for fmt, frames in zip(formats, fr) for f in frames)
+        key = (H, W, tuple(shapes), layouts, "y16", device)
+        states = self.__dict__.setdefault("_frame_states", {})
+        st = states.pop(key, None)
+        if st is None:
+            geom1, scale = ops.frame_geometry(shapes, (H, W))
+            geom, nbytes = ops.pack_y16_frames(np.concatenate((geom1, geom1)), layouts)
+            wtab = torch.zeros((2 * B, 2), dtype=torch.int32, device=device)
+            st = {"geom": geom, "geom_dev": ops.geom_tensor(geom, device), "arena": torch.zeros((nbytes,), dtype=torch.uint8, device=device),
+                  "window": wtab, "dst": None, "launch": None, "select": None,
+                  "info": ops.FrameGeometry(geom, scale, torch.from_numpy(scale).to(device),
+                                            tuple(wtab[m * B:(m + 1) * B] if fmt else None for m, fmt in enumerate(formats)))}
+            while len(states) >= 8:
+                states.pop(next(iter(states)))
+        states[key] = st
+        # this call's clip and windows: the rows are packed again around the same geometry (same offsets), validated, and copied in stream order
+        wins = None
+        if window is not None:
+            per = ops._y16_windows(window, B)
+            wins = [w if fmt else None for fmt in formats for w in per]
+        geom, _ = ops.pack_y16_frames(st["geom"], layouts, clip=clip, window=wins)
+        ops.validate_y16_frames(geom, st["arena"].numel(), H, W)
+        st["geom"][:] = geom
+        plan = (self.tta_plan_for if augment else self.plan_for)(B, H, W, device, u8=True)
+        dst = plan.inputs[0]
+        if st["dst"] is not dst:
+            st["select"] = ops.y16_window(st["arena"], st["geom"], st["geom_dev"], st["window"], B, H, W)
+            st["launch"] = ops.letterbox_y16_frames(st["arena"], st["geom"], st["geom_dev"], st["window"], dst, swap_rb=bgr)
+            st["dst"] = dst
+        st["geom_dev"].copy_(ops.geom_tensor(st["geom"]))
+        for o, f in zip(st["geom"]["g"]["offset"], fr[0] + fr[1]):        # tight rows: a frame is one run of bytes
+            st["arena"][int(o):int(o) + f.numel()].view(f.shape).copy_(f)
+        st["launch"].args = st["launch"].args[:-1] + (int(bool(bgr)),)
+        st["select"](ops.current_stream_ptr())
         st["launch"](ops.current_stream_ptr())
         plan.run()
         out = self._result(plan.outputs)

@@ -15,7 +15,7 @@ import torch
 
 from . import _lib
 from .options import OPT
-from ._lib import BneckArgs, ConvArgs, DmffArgs, FrameGeom, Stem2Args, WarpGeom, YuvGeom, check, lib, F32, BF16, F16, ACT_NONE, ACT_SILU, ACT_GELU, ACT_RELU  # noqa: F401
+from ._lib import BneckArgs, ConvArgs, DmffArgs, FrameGeom, Stem2Args, WarpGeom, Y16Geom, YuvGeom, check, lib, F32, BF16, F16, ACT_NONE, ACT_SILU, ACT_GELU, ACT_RELU  # noqa: F401
 from ._lib import CONFLUENCE_MAX_CAND, LOSS_MAX_LEVELS, LOSS_MAX_ANCHORS, LOSS_MAX_TARGETS, LOSS_SLOT_INTS  # noqa: F401
 
 _DT = {torch.float32: F32, torch.bfloat16: BF16, torch.float16: F16}
@@ -1146,7 +1146,8 @@ GEOM_DTYPE = np.dtype(FrameGeom)
 assert GEOM_DTYPE.itemsize == C.sizeof(FrameGeom) == 48
 FRAME_ALIGN = 256          # frames start on this boundary inside an arena (the kernel needs 16)
 # what a forward from frames hands back beside its result: the descriptor rows, the scale_coords rows, and those on the device
-FrameGeometry = collections.namedtuple("FrameGeometry", "geom scale_host scale")
+# (window: per modality None or, for a 16-bit thermal modality, the cuda int32 (B, 2) gain-control windows the step used)
+FrameGeometry = collections.namedtuple("FrameGeometry", "geom scale_host scale window", defaults=(None,))
 
 
 def _geom_row(g, i, shape, fit, how):
@@ -1651,6 +1652,189 @@ def warp_frame_lists(rgb, ir, align):
     return fr[0], fr[1], shapes, uniform, m, src_shapes, alignment_matrices(a_rgb if m == 0 else a_ir, src_shapes, shapes)
 
 
+# 16-bit thermal frames: one row per (modality, image) in the layout of icaf_y16_geom (include/icaf.h) — field "g" is a GEOM_DTYPE row
+Y16_GEOM_DTYPE = np.dtype(Y16Geom)
+assert Y16_GEOM_DTYPE.itemsize == C.sizeof(Y16Geom) == 72 and Y16_GEOM_DTYPE["g"] == GEOM_DTYPE
+Y16_DTYPES = tuple(getattr(torch, n) for n in ("uint16", "int16") if hasattr(torch, n))      # the same bits either way
+
+
+def _y16_windows(window, n):
+    """pack_y16_frames' `window` as a list of n entries, each None (mode 1) or an (lo, hi) pair of ints (mode 0)."""
+    if window is None:
+        return [None] * n
+    if torch.is_tensor(window):
+        window = window.detach().cpu().numpy()
+    if not isinstance(window, np.ndarray) and any(w is None for w in window):
+        rows = list(window)
+    else:
+        w = np.asarray(window)
+        if w.shape == (2,):
+            rows = [w] * n
+        elif w.ndim == 2 and w.shape[1] == 2:
+            rows = list(w)
+        else:
+            raise ValueError(f"a gain-control window is (lo, hi) or one (lo, hi) row per frame, got shape {w.shape}")
+    if len(rows) != n:
+        raise ValueError(f"{len(rows)} gain-control windows for {n} frames")
+    out = []
+    for w in rows:
+        if w is not None and any(int(v) != v for v in w):
+            raise ValueError(f"a gain-control window holds integers, got {tuple(w)!r}")
+        out.append(None if w is None else (int(w[0]), int(w[1])))
+    return out
+
+
+def pack_y16_frames(geom, layouts, pitch=None, clip=None, window=None, base=0):
+    """pack_frames for tables that hold 16-bit thermal frames: returns (rows, end) — Y16_GEOM_DTYPE rows around `geom` (frame_geometry's
+    GEOM_DTYPE rows, or Y16 rows whose "g" is filled) and the first free byte behind the frames.  layouts: per row, or one for all, "y16"
+    (a kind-1 row: h0 rows of little-endian uint16, `pitch` BYTES each, default 2 * w0) or 3 / 1 (a kind-0 row, laid out exactly as
+    pack_frames lays it out).  clip: (clip_lo, clip_hi) in basis points for the percentile window (mode 1; default
+    utils.datasets.AGC_CLIP); window: None, or (lo, hi) for every Y16 row, or one entry per row of the table, None or (lo, hi) — a row
+    with a window is a mode-0 row.  Frames start on FRAME_ALIGN boundaries from `base` on."""
+    from .utils.datasets import AGC_CLIP, agc_clip
+    n = len(geom)
+    rows = np.zeros((n,), Y16_GEOM_DTYPE)
+    rows["g"] = geom if geom.dtype == GEOM_DTYPE else geom["g"]
+    per_row = lambda v: [v] * n if v is None or isinstance(v, (int, str)) else list(v)
+    clip_lo, clip_hi = agc_clip(AGC_CLIP if clip is None else clip)
+    off = int(base)
+    for i, (q, lay, p, win) in enumerate(zip(rows, per_row(layouts), per_row(pitch), _y16_windows(window, n))):
+        g = q["g"]
+        off = -(-off // FRAME_ALIGN) * FRAME_ALIGN
+        h0, w0 = int(g["h0"]), int(g["w0"])
+        if lay in (1, 3):
+            g["offset"], g["ch"], g["pitch"] = off, lay, w0 * lay if p is None else int(p)
+        elif lay == "y16":
+            g["offset"], g["ch"], g["pitch"] = off, 1, 2 * w0 if p is None else int(p)
+            q["kind"], q["mode"], q["clip_lo"], q["clip_hi"] = 1, 1 if win is None else 0, clip_lo, clip_hi
+            if win is not None:
+                q["lo"], q["hi"] = win
+        else:
+            raise ValueError(f"frame {i}: unknown layout {lay!r} (3, 1 or 'y16')")
+        off += h0 * int(g["pitch"])
+    return rows, off
+
+
+def y16_letterbox_staged(q):
+    """The budget rule of icaf_letterbox_y16_frames for one table row (include/icaf.h): True = its tiles stage the MAPPED bytes of their
+    source rectangle in LDS, False = they tap global memory.  A kind-0 row follows letterbox_staged; a kind-1 row the same rule for one
+    byte per pixel under ICAF_Y16_LDS_BYTES."""
+    g = q["g"]
+    if int(q["kind"]) == 0:
+        return letterbox_staged(g)
+    sx, sy = np.float32(g["sx"]), np.float32(g["sy"])
+    if not (sx < 1024 and sy < 1024):
+        return False
+    rows = min(int(g["h0"]), int(np.float32(32) * sy) + 4)
+    cols = min(int(g["w0"]), int(np.float32(64) * sx) + 4)
+    return rows * ((cols + 30) >> 4) * 16 <= _lib.Y16_LDS_BYTES
+
+
+def validate_y16_frames(geom, arena_bytes, H, W):
+    """validate_frames for Y16_GEOM_DTYPE rows: raises ValueError with the row and the reason — everything validate_frames refuses of
+    "g" (the 16-byte alignment, the frame inside the arena, the block inside the output), an unknown kind, and for kind-1 rows a ch that
+    is not 1, an odd pitch or one below 2 * w0 bytes, an unknown mode, a clip outside 0..4999 basis points, a window that is not 0 <= lo
+    <= hi <= 65535.  The kernels trust the table — nothing reaches the device before this has passed."""
+    for i, q in enumerate(geom):
+        if int(q["kind"]) not in (0, 1):
+            raise ValueError(f"frame {i}: kind {int(q['kind'])} (0 = interleaved row, 1 = 16-bit thermal)")
+    validate_frames(geom["g"], arena_bytes, H, W)
+    for i, q in enumerate(geom):
+        if int(q["kind"]) == 0:
+            continue
+        g = q["g"]
+        pitch, w0, mode, lo, hi, clip_lo, clip_hi = (int(v) for v in (g["pitch"], g["w0"], q["mode"], q["lo"], q["hi"], q["clip_lo"], q["clip_hi"]))
+        if int(g["ch"]) != 1:
+            raise ValueError(f"frame {i}: a 16-bit thermal row has ch 1, got {int(g['ch'])}")
+        if pitch % 2 or pitch < 2 * w0:
+            raise ValueError(f"frame {i}: pitch {pitch} must be an even number of bytes, at least 2 * w0 = {2 * w0}")
+        if mode not in (0, 1):
+            raise ValueError(f"frame {i}: mode {mode} (0 = window given, 1 = percentile)")
+        if not (0 <= clip_lo <= 4999 and 0 <= clip_hi <= 4999):
+            raise ValueError(f"frame {i}: clip ({clip_lo}, {clip_hi}) must lie in 0..4999 basis points each")
+        if mode == 0 and not 0 <= lo <= hi <= 65535:
+            raise ValueError(f"frame {i}: window ({lo}, {hi}) must satisfy 0 <= lo <= hi <= 65535")
+
+
+def _y16_tables(arena, geom, geom_dev, window_dev, n):
+    if geom.dtype != Y16_GEOM_DTYPE:
+        raise ValueError("the descriptor rows must be Y16_GEOM_DTYPE rows (pack_y16_frames)")
+    if window_dev.dtype != torch.int32 or not window_dev.is_contiguous() or window_dev.numel() < 2 * n:
+        raise ValueError(f"the window table must be a contiguous int32 tensor of {n} (lo, hi) rows")
+
+
+def y16_window(arena, geom, geom_dev, window_dev, B, H, W, name="y16_window"):
+    """The gain-control windows of a table's 16-bit thermal rows (icaf_y16_window): window_dev, int32 (n, 2) on the device, takes (lo, hi)
+    of every kind-1 row — utils.datasets.agc_window of the frame for a mode-1 row, the row's own pair for a mode-0 row; rows of kind 0
+    keep what they hold.  geom: the HOST rows the device table `geom_dev` holds, validated here (against an H x W output) before any
+    device call; B: images per modality.  Nothing is read back."""
+    n = len(geom)
+    _y16_tables(arena, geom, geom_dev, window_dev, n)
+    if arena.dtype != torch.uint8 or not arena.is_contiguous() or arena.dim() != 1:
+        raise ValueError("the arena must be a flat contiguous uint8 tensor")
+    if n == 0 or n % B or geom_dev.numel() * geom_dev.element_size() < n * Y16_GEOM_DTYPE.itemsize:
+        raise ValueError(f"{n} descriptors for a batch of {B} images, or a device table smaller than the rows")
+    validate_y16_frames(geom, arena.numel(), H, W)
+    if not (arena.is_cuda and geom_dev.is_cuda and window_dev.is_cuda):
+        raise ValueError("arena and tables must be cuda tensors (no CPU fallback exists)")
+    nb = sum(2 * 2 * int(q["g"]["h0"]) * int(q["g"]["w0"]) for q in geom if int(q["kind"]) and int(q["mode"]))       # two passes over a frame
+    return Launch(lib().icaf_y16_window, (arena.data_ptr(), geom_dev.data_ptr(), n // B, B, window_dev.data_ptr()),
+                  keep=(arena, geom_dev, window_dev), name=name, nbytes=nb)
+
+
+def letterbox_y16_frames(arena, geom, geom_dev, window_dev, dst, swap_rb=True, name="letterbox_y16_frames"):
+    """letterbox_frames for tables with 16-bit thermal rows (icaf_letterbox_y16_frames): kind-1 rows are mapped to bytes at the bilinear
+    taps with their row of `window_dev` (y16_window fills it; it runs first) and equal letterbox(agc_u16_to_u8(frame, lo, hi)) byte for
+    byte in all three planes, kind-0 rows are letterbox_frames' own.  geom: the HOST Y16_GEOM_DTYPE rows the device table `geom_dev`
+    holds, validated here, before any device call."""
+    n = len(geom)
+    _y16_tables(arena, geom, geom_dev, window_dev, n)
+    B, ctot, H, W = _frames_tensors(arena, dst, n, geom_dev, Y16_GEOM_DTYPE.itemsize)
+    validate_y16_frames(geom, arena.numel(), H, W)
+    if not (arena.is_cuda and dst.is_cuda and geom_dev.is_cuda and window_dev.is_cuda):
+        raise ValueError("arena, tables and dst must be cuda tensors (no CPU fallback exists)")
+    nb = n * 3 * H * W + sum(int(q["g"]["h0"]) * int(q["g"]["w0"]) * (2 if int(q["kind"]) else int(q["g"]["ch"])) for q in geom)
+    return Launch(lib().icaf_letterbox_y16_frames, (arena.data_ptr(), geom_dev.data_ptr(), window_dev.data_ptr(), n // B, B, dst.data_ptr(), ctot, H, W,
+                                                    int(bool(swap_rb))), keep=(arena, geom_dev, window_dev, dst), name=name, nbytes=nb)
+
+
+def y16_bytes(t):
+    """A 16-bit thermal modality as bytes: a torch.uint16 / torch.int16 tensor (..., H0, W0) becomes its uint8 view (..., H0, 2 * W0)
+    (little-endian, as the kernels read it), a uint8 tensor is taken as that view already, a list or tuple is converted frame by frame."""
+    if isinstance(t, (list, tuple)):
+        return [y16_bytes(f) for f in t]
+    if torch.is_tensor(t) and t.dtype in Y16_DTYPES and t.dim() >= 2:
+        return (t if t.stride(-1) == 1 else t.contiguous()).view(torch.uint8)
+    return t
+
+
+def y16_frame_lists(rgb, ir, formats):
+    """frame_lists for modalities that may arrive as 16-bit thermal frames: formats = (fmt_rgb, fmt_ir), each None (an interleaved
+    modality, as frame_lists takes it) or "y16" — then a torch.uint16 / torch.int16 (B, H0, W0) tensor, or its uint8 byte buffer (B, H0,
+    2 * W0), or a list of per-frame (H0_i, W0_i) / (H0_i, 2 * W0_i) tensors.  Returns (frames_rgb, frames_ir, shapes, uniform) like
+    frame_lists; the frames of a Y16 modality come back as uint8 (H0, 2 * W0) views."""
+    formats = tuple(formats)
+    if len(formats) != 2 or any(f not in (None, "y16") for f in formats):
+        raise ValueError(f"formats=(fmt_rgb, fmt_ir), each None or 'y16', got {formats!r}")
+    mods = [y16_bytes(t) if f else t for t, f in zip((rgb, ir), formats)]
+    nd = [3 if f else 4 for f in formats]
+    uniform = tuple(torch.is_tensor(t) and t.dim() == d for t, d in zip(mods, nd))
+    fr = [[t[i] for i in range(t.shape[0])] if u else list(t) if isinstance(t, (list, tuple)) else None for t, u in zip(mods, uniform)]
+    if fr[0] is None or fr[1] is None or not fr[0] or len(fr[0]) != len(fr[1]):
+        raise ValueError("native frames come as two batch tensors or two equally long lists of frames")
+    shapes = []
+    for m, fmt in enumerate(formats):
+        for f in fr[m]:
+            if not torch.is_tensor(f) or f.dtype != torch.uint8 or f.dim() != nd[m] - 1 or (fmt is None and f.shape[2] not in (1, 3)) or \
+                    (fmt is not None and (f.shape[1] % 2 or f.shape[1] < 2 or f.shape[0] < 1)):
+                raise ValueError("frames must be uint8 tensors of shape (H0, W0, ch), ch = 3 or 1" if fmt is None else
+                                 "y16 frames must be 16-bit tensors of shape (H0, W0) or their uint8 bytes (H0, 2 * W0)")
+        shapes.append([(int(f.shape[0]), int(f.shape[1]) // 2 if fmt else int(f.shape[1])) for f in fr[m]])
+    if shapes[0] != shapes[1]:
+        raise ValueError("the RGB and IR frame of a pair must have the same size")
+    return fr[0], fr[1], shapes[0], uniform
+
+
 def val_geometry(shapes, img_size, batch_shape):
     """The validation loader's two steps for native (h0, w0) frames as numbers (PairedValSet.__getitem__; reference utils/datasets.py:
     1116-1122 + letterbox): returns (geom, mode, scale).  Step 1, the loader's own numbers: r = img_size / max(h0, w0), (nw, nh) =
@@ -1977,7 +2161,7 @@ def confusion_matrix(predn, det, count, labels, label_off, matrix, conf=0.25, io
 
 
 def letterbox_direct(on=True):
-    """Force icaf_letterbox_frames onto its direct path (no LDS staging) inside a `with`: an A/B knob of the library, it changes no result."""
+    """Force icaf_letterbox_frames (and its YUV, warp and Y16 siblings) onto its direct path (no LDS staging) inside a `with`: an A/B knob of the library, it changes no result."""
     return _caller_knob("letterbox_direct", on)
 
 

@@ -26,6 +26,7 @@ import torch
 from . import dist as D
 from . import ops
 from .options import OPT
+from .utils.datasets import agc_clip as agc_clip_checked
 from .utils.general import nms_device
 
 
@@ -48,7 +49,7 @@ class DetectionPipeline:
     def __init__(self, model, batch, height, width, device, conf_thres=0.25, iou_thres=0.45, classes=None,
                  agnostic=False, multi_label=False, max_det=300, world=1, overlap=True, force_gather=False, depth=1, u8=False, augment=False,
                  frames=None, frame_channels=(3, 3), frames_bgr=True, round_boxes=False, frame_formats=(None, None), yuv_matrix="bt601",
-                 frame_align=(None, None), align_frames=None, align_border=0):
+                 frame_align=(None, None), align_frames=None, align_border=0, agc_clip=(100, 100)):
         """frames=(max_h0, max_w0): the pipeline also takes NATIVE camera frames (`submit_frames`; implies u8): every plan owns a frame arena
         for `batch` pairs of up to that size (frame_channels: interleaved channels of the RGB / IR frames, 3 or 1) and a geometry table;
         the letterbox runs on the device in front of the plan and the boxes come back in native image space (round_boxes: torch.round
@@ -61,11 +62,22 @@ class DetectionPipeline:
         `submit_frames(..., align=M)` takes per submit (Model.forward_frames' align=); its frames may have any size up to align_frames=
         (max_hs, max_ws), which sizes its half of every arena, while frames= stays the other, the aligned, modality's maximum.  Pixels
         the source does not cover are align_border.  Boxes come back in the un-warped modality's native space.
+        frame_formats=(None, "y16") (either or both modalities): a 16-BIT THERMAL modality, raw counts submitted as a torch.uint16 /
+        torch.int16 (B, H0, W0) tensor, its uint8 bytes (B, H0, 2 * W0) or a list of per-frame tensors; its half of the arena holds 2
+        bytes per pixel.  Gain control runs on the device in front of the letterbox (Model.forward_frames' formats="y16"): agc_clip=
+        (clip_lo, clip_hi) basis points per frame, or the window `submit_frames(..., agc_window=)` gives for a step; the windows a
+        step used stay on the device in `pipe.frames["window"][plan index]`, int32 (2B, 2), rows modality * B + image.
         augment=True: every step is a test-time-augmentation step (Model.forward(augment=True), reference models/yolo_test.py:116-131:
         the plans are engine.TtaPlan objects) and NMS runs over the merged rows of the three passes (55,755 per image at 640 x 640).
         u8=True: the plans take the dataloader's uint8 (B, 6, H, W) RGB+IR batch (Model.forward_u8: `/255`, split and cast in the
         staging kernel, reference test.py:116-123) — `submit_u8` then feeds them from (pinned) host memory with the H2D copy on its own
         stream, overlapped with the forwards in flight."""
+        if "y16" in tuple(frame_formats):                                        # refused before anything is built
+            if any(f in ops.YUV_LAYOUTS for f in frame_formats):
+                raise ValueError("a 16-bit thermal modality ('y16') beside a YUV 4:2:0 modality is not supported yet: one table holds one kind of row")
+            if any(frame_align):
+                raise ValueError("frame_align takes interleaved 8-bit frames; a 16-bit thermal modality ('y16') cannot be combined with it yet")
+            agc_clip_checked(agc_clip)
         self.model, self.device, self.world = model, torch.device(device), world
         self.u8, self.augment = bool(u8) or frames is not None, bool(augment)
         self.gather = world > 1 or bool(force_gather)       # force_gather: run the all-gather even with one rank (hardware test of the RCCL path)
@@ -139,10 +151,10 @@ class DetectionPipeline:
             raise ValueError("frame_align / align_frames describe native frames: pass frames=(max_h0, max_w0) with them")
         if frames is not None:
             self._init_frames(batch, height, width, frames, frame_channels, frames_bgr, round_boxes, frame_formats, yuv_matrix,
-                              frame_align, align_frames, align_border)
+                              frame_align, align_frames, align_border, agc_clip)
 
     def _init_frames(self, B, H, W, frames, chans, bgr, round_boxes, formats=(None, None), yuv_matrix="bt601", frame_align=(None, None),
-                     align_frames=None, align_border=0):
+                     align_frames=None, align_border=0, agc_clip=(100, 100)):
         """Per plan: a byte arena (RGB frames in its first half, IR frames in its second) and ONE table allocation — 2B descriptor rows
         for the letterbox, then B scale_coords rows for scale_detections — with a pinned host twin it is copied from."""
         max_h0, max_w0 = int(frames[0]), int(frames[1])
@@ -150,9 +162,10 @@ class DetectionPipeline:
         if max_h0 < 1 or max_w0 < 1 or len(chans) != 2 or any(c not in (1, 3) for c in chans):
             raise ValueError(f"frames=(max_h0, max_w0) with frame_channels of 1 or 3 each, got {frames} / {chans}")
         formats = tuple(formats)
-        if len(formats) != 2 or any(f is not None and f not in ops.YUV_LAYOUTS for f in formats):
-            raise ValueError(f"frame_formats=(fmt_rgb, fmt_ir), each None or one of {', '.join(ops.YUV_LAYOUTS)}, got {formats!r}")
-        yuv = any(formats)                                                       # then the table holds icaf_yuv_geom rows
+        if len(formats) != 2 or any(f is not None and f != "y16" and f not in ops.YUV_LAYOUTS for f in formats):
+            raise ValueError(f"frame_formats=(fmt_rgb, fmt_ir), each None, 'y16' or one of {', '.join(ops.YUV_LAYOUTS)}, got {formats!r}")
+        y16 = "y16" in formats                                                   # then the table holds icaf_y16_geom rows (__init__ checked its company)
+        yuv = any(formats) and not y16                                           # then the table holds icaf_yuv_geom rows
         frame_align = tuple(bool(a) for a in frame_align)
         if len(frame_align) != 2 or all(frame_align):
             raise ValueError("frame_align=(None, True) or (True, None): one modality is aligned, the other defines the aligned space")
@@ -168,7 +181,7 @@ class DetectionPipeline:
                 raise ValueError(f"align_frames=(max_hs, max_ws) and align_border in 0..255, got {align_frames} / {align_border}")
         A = ops.FRAME_ALIGN
         # bytes per modality: interleaved frames of c channels, or 1.5 bytes per pixel (luma + 4:2:0 chroma of the even sizes buffers come in)
-        per_frame = [smax[0] * smax[1] * c if m == warp else max_h0 * max_w0 * c if fmt is None else max_h0 * max_w0 + 2 * ((max_h0 + 1) // 2) * ((max_w0 + 1) // 2) for m, (c, fmt) in enumerate(zip(chans, formats))]
+        per_frame = [smax[0] * smax[1] * c if m == warp else max_h0 * max_w0 * c if fmt is None else max_h0 * max_w0 * 2 if fmt == "y16" else max_h0 * max_w0 + 2 * ((max_h0 + 1) // 2) * ((max_w0 + 1) // 2) for m, (c, fmt) in enumerate(zip(chans, formats))]
         cap = [B * (-(-n // A) * A) for n in per_frame]
         probe, _ = ops.frame_geometry([(max_h0, max_w0)] * B, (H, W))
         probe = np.concatenate((probe, probe))
@@ -176,6 +189,9 @@ class DetectionPipeline:
             matrix = ops.yuv_matrix_code(yuv_matrix)
             lay = [fmt if fmt is not None else c for c, fmt in zip(chans, formats)]
             probe = np.concatenate((ops.pack_yuv_frames(probe[:B], lay[0], matrix=matrix)[0], ops.pack_yuv_frames(probe[B:], lay[1], matrix=matrix, base=cap[0])[0]))
+        elif y16:
+            matrix, lay = 0, [fmt if fmt is not None else c for c, fmt in zip(chans, formats)]
+            probe = np.concatenate((ops.pack_y16_frames(probe[:B], lay[0], clip=agc_clip)[0], ops.pack_y16_frames(probe[B:], lay[1], clip=agc_clip, base=cap[0])[0]))
         elif warp is not None:
             matrix, lay = 0, list(chans)
             src = [(smax[0], smax[1], chans[m]) if m == warp else chans[m] for m in (0, 1)]
@@ -189,7 +205,7 @@ class DetectionPipeline:
         self.frames = {"B": B, "H": H, "W": W, "max": (max_h0, max_w0), "chans": chans, "cap": cap, "geom_bytes": gb, "cache": {},
                        "arena": [], "tab_dev": [], "tab_host": [], "letterbox": [], "scale_rows": [], "scale_launch": {}, "pending": None,
                        "round": bool(round_boxes), "formats": formats, "yuv": yuv, "matrix": matrix, "layouts": lay,
-                       "warp": warp, "smax": smax, "border": border}
+                       "warp": warp, "smax": smax, "border": border, "y16": y16, "clip": agc_clip, "window": [], "select": []}
         f = self.frames
         for plan in self.plans:
             arena = torch.zeros((sum(cap),), dtype=torch.uint8, device=self.device)
@@ -198,6 +214,11 @@ class DetectionPipeline:
             f["tab_dev"].append(tab)
             f["tab_host"].append(torch.zeros((gb + B * 20,), dtype=torch.uint8).pin_memory())
             f["scale_rows"].append(tab[gb:].view(torch.float32).view(B, 5))
+            if y16:                                                              # two launches: the windows, then the letterbox that reads them
+                f["window"].append(torch.zeros((2 * B, 2), dtype=torch.int32, device=self.device))
+                f["select"].append(ops.y16_window(arena, probe, tab, f["window"][-1], B, H, W))
+                f["letterbox"].append(ops.letterbox_y16_frames(arena, probe, tab, f["window"][-1], plan.inputs[0], swap_rb=bgr))
+                continue
             launch = ops.letterbox_yuv_frames if yuv else ops.letterbox_warp_frames if warp is not None else ops.letterbox_frames
             f["letterbox"].append(launch(arena, probe, tab, plan.inputs[0], swap_rb=bgr))
 
@@ -217,6 +238,8 @@ class DetectionPipeline:
             geom = np.concatenate((geom1, geom1))
             if f["yuv"]:
                 geom = self._yuv_rows(geom, contiguous)
+            elif f["y16"]:
+                geom = self._y16_rows(geom, contiguous)
             elif f["warp"] is not None:
                 geom = self._warp_rows(geom, contiguous, src_shapes)
             else:
@@ -230,7 +253,7 @@ class DetectionPipeline:
                         end = ops.pack_frames(rows, chans[m], base=base)
                         if end - base > cap[m]:
                             raise ValueError(f"the frames of modality {m} need {end - base} bytes of the arena's {cap[m]}")
-            (ops.validate_yuv_frames if f["yuv"] else ops.validate_warp_frames if f["warp"] is not None else ops.validate_frames)(geom, sum(cap), f["H"], f["W"])
+            (ops.validate_yuv_frames if f["yuv"] else ops.validate_y16_frames if f["y16"] else ops.validate_warp_frames if f["warp"] is not None else ops.validate_frames)(geom, sum(cap), f["H"], f["W"])
             table = np.concatenate((geom.view(np.uint8).reshape(-1), scale.view(np.uint8).reshape(-1)))
             if len(f["cache"]) >= 64:
                 f["cache"].pop(next(iter(f["cache"])))
@@ -250,6 +273,21 @@ class DetectionPipeline:
                 for k in ("cb_offset", "cr_offset"):
                     rows[k] += (rows["kind"] != 0) * (base + fb * np.arange(B) - rows["g"]["offset"])
                 rows["g"]["offset"] = base + fb * np.arange(B)
+            elif end - base > cap[m]:
+                raise ValueError(f"the frames of modality {m} need {end - base} bytes of the arena's {cap[m]}")
+            halves.append(rows)
+        return np.concatenate(halves)
+
+    def _y16_rows(self, geom, contiguous):
+        """_frame_table's arena layout for a pipeline with a 16-bit thermal modality: icaf_y16_geom rows in percentile mode (submit_frames
+        writes a step's windows into the pinned table).  A uniform batch in one contiguous tensor whose frames are whole 16-byte multiples
+        keeps its layout, other frames start on FRAME_ALIGN boundaries."""
+        f = self.frames
+        B, cap, halves = f["B"], f["cap"], []
+        for m, base in ((0, 0), (1, cap[0])):
+            rows, end = ops.pack_y16_frames(geom[m * B:(m + 1) * B], f["layouts"][m], clip=f["clip"], base=base)
+            if contiguous[m]:
+                rows["g"]["offset"] = base + int(rows[0]["g"]["h0"]) * int(rows[0]["g"]["pitch"]) * np.arange(B)
             elif end - base > cap[m]:
                 raise ValueError(f"the frames of modality {m} need {end - base} bytes of the arena's {cap[m]}")
             halves.append(rows)
@@ -279,7 +317,7 @@ class DetectionPipeline:
             halves.append(rows)
         return np.concatenate(halves)
 
-    def submit_frames(self, rgb, ir, align=None):
+    def submit_frames(self, rgb, ir, align=None, agc_window=None):
         """One batch of NATIVE frames through the pipeline: rgb / ir are uint8 (B, H0, W0, ch) tensors or lists of (H0_i, W0_i, ch) tensors,
         in pinned host memory or on the device (a modality with a frame_formats layout: (B, 3 * H0 // 2, W0) or a list of (3 * H0_i // 2,
         W0_i) buffers, H0 and W0 even); a pair shares its size, sizes may change from step to step.  The frames and the step's
@@ -288,18 +326,31 @@ class DetectionPipeline:
         count zeroed), and so does the gathered block of a process group.  Host buffers must stay untouched until their copy has run
         (`pipe.copied[n % pipe.nplans]`, as for submit_u8).
         align: for a pipeline built with frame_align, the step's alignment of the marked modality — a (3, 3) array, a (B, 3, 3) array or
-        "stretch" (aligned -> source, Model.forward_frames' align=); it travels in the pinned geometry table with the rest of the rows."""
+        "stretch" (aligned -> source, Model.forward_frames' align=); it travels in the pinned geometry table with the rest of the rows.
+        agc_window: for a pipeline with a "y16" modality, this step's gain-control window, (lo, hi) or a (B, 2) array, instead of the
+        percentile window of each frame; it travels in the pinned table too."""
         f = self.frames
         if f is None:
             raise ValueError("DetectionPipeline(frames=(max_h0, max_w0)) takes native frames")
         B, chans = f["B"], f["chans"]
+        wins = None
+        if agc_window is not None:
+            if not f["y16"]:
+                raise ValueError("submit_frames(agc_window=...) goes with DetectionPipeline(frame_formats=(..., 'y16'))")
+            wins = ops._y16_windows(agc_window, B)
+            for lo_, hi_ in wins:
+                if not 0 <= lo_ <= hi_ <= 65535:
+                    raise ValueError(f"agc_window ({lo_}, {hi_}) must satisfy 0 <= lo <= hi <= 65535")
+        if f["y16"]:
+            rgb, ir = (ops.y16_bytes(t) if fmt else t for t, fmt in zip((rgb, ir), f["formats"]))
         if (align is None) != (f["warp"] is None):
             raise ValueError("submit_frames(align=...) goes with DetectionPipeline(frame_align=..., align_frames=...): both or neither")
         src_shapes = mats = None
         if f["warp"] is not None:
             *lists, shapes, uniform, _, src_shapes, mats = ops.warp_frame_lists(rgb, ir, (align, None) if f["warp"] == 0 else (None, align))
         else:
-            *lists, shapes, uniform = ops.yuv_frame_lists(rgb, ir, f["formats"]) if f["yuv"] else ops.frame_lists(rgb, ir)
+            *lists, shapes, uniform = ops.yuv_frame_lists(rgb, ir, f["formats"]) if f["yuv"] else \
+                ops.y16_frame_lists(rgb, ir, f["formats"]) if f["y16"] else ops.frame_lists(rgb, ir)
         if len(shapes) != B:
             raise ValueError(f"submit_frames expects a batch of {B} pairs, got {len(shapes)}")
         mods, contiguous = [], []
@@ -319,6 +370,13 @@ class DetectionPipeline:
         if mats is not None:                                                # this step's matrices, into the pinned rows of the aligned modality
             rows = f["tab_host"][pi].numpy()[:f["geom_bytes"]].view(ops.WARP_GEOM_DTYPE)
             rows["m"][f["warp"] * B:(f["warp"] + 1) * B] = mats.reshape(B, 9)
+        if wins is not None:                                                # this step's windows, into the pinned rows of the Y16 modalities
+            rows = f["tab_host"][pi].numpy()[:f["geom_bytes"]].view(ops.Y16_GEOM_DTYPE)
+            for m, fmt in enumerate(f["formats"]):
+                if fmt:
+                    rows["mode"][m * B:(m + 1) * B] = 0
+                    rows["lo"][m * B:(m + 1) * B] = [w[0] for w in wins]
+                    rows["hi"][m * B:(m + 1) * B] = [w[1] for w in wins]
         cur = torch.cuda.current_stream(self.device)
         for k, cs in enumerate(self.copy_streams):                          # the batch in `ncs` slices of images, one copy stream each
             lo, hi = B * k // ncs, B * (k + 1) // ncs
@@ -337,7 +395,7 @@ class DetectionPipeline:
                 if k == 0:
                     f["tab_dev"][pi].copy_(f["tab_host"][pi], non_blocking=True)
                 for m, (t, fr) in enumerate(mods):
-                    rows = geom[m * B:(m + 1) * B]["g"] if f["yuv"] or f["warp"] is not None else geom[m * B:(m + 1) * B]
+                    rows = geom[m * B:(m + 1) * B]["g"] if f["yuv"] or f["y16"] or f["warp"] is not None else geom[m * B:(m + 1) * B]
                     if contiguous[m]:
                         o, fb = int(rows[lo]["offset"]), t[0].numel()
                         arena[o:o + (hi - lo) * fb].view(t[lo:hi].shape).copy_(t[lo:hi], non_blocking=True)
@@ -352,6 +410,8 @@ class DetectionPipeline:
                             x.record_stream(cs)
             self.copied[pi][k].record(cs)
             fs.wait_event(self.copied[pi][k])
+        if f["y16"]:
+            f["select"][pi](fs.cuda_stream)
         f["letterbox"][pi](fs.cuda_stream)
         f["pending"] = pi
         try:

@@ -194,6 +194,67 @@ def yuv420_to_bgr(y, cb, cr, matrix=0):
     return np.clip(np.stack((b, g, r), axis=2), 0, 255).astype(np.uint8)
 
 
+AGC_CLIP = (100, 100)        # basis points clipped at the low / high end of a 16-bit thermal frame's histogram: 1 % each
+
+
+def _u16_frame(frame):
+    f = np.asarray(frame)
+    if f.dtype == np.int16:                       # torch has no uint16 on older releases: the same bits
+        f = f.view(np.uint16)
+    if f.dtype != np.uint16 or f.ndim != 2 or f.size == 0:
+        raise ValueError(f"a 16-bit thermal frame is a non-empty (h0, w0) uint16 array, got {f.dtype} {f.shape}")
+    return f
+
+
+def agc_clip(clip):
+    """(clip_lo, clip_hi) as two ints in basis points, each 0..4999; ValueError names the limit."""
+    try:
+        lo, hi = clip
+        ok = all(isinstance(v, (int, np.integer)) and not isinstance(v, bool) and 0 <= v <= 4999 for v in (lo, hi))
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError(f"the gain-control clip is (clip_lo, clip_hi) in basis points, integers in 0..4999 each, got {clip!r}")
+    return int(lo), int(hi)
+
+
+def agc_window(frame, clip=AGC_CLIP):
+    """THE gain-control window of a 16-bit thermal frame (icaf_y16_window equals it): (lo, hi) with n = h0 * w0, C(v) = pixels <= v,
+    D(v) = pixels >= v, lo the smallest v with 10000 * C(v) > clip_lo * n and hi the largest v with 10000 * D(v) > clip_hi * n.  Integers
+    only, 64-bit products, both inequalities strict; clip in basis points, 0..4999 each; (0, 0) gives the frame's minimum and maximum."""
+    f = _u16_frame(frame)
+    clip_lo, clip_hi = agc_clip(clip)
+    n = f.size
+    hist = np.bincount(f.reshape(-1), minlength=65536).astype(np.int64)
+    c = np.cumsum(hist)                           # C(v)
+    d = n - c + hist                              # D(v)
+    lo = int(np.argmax(10000 * c > clip_lo * n))
+    hi = 65535 - int(np.argmax((10000 * d > clip_hi * n)[::-1]))
+    return lo, hi
+
+
+def agc_u16_to_u8(frame, lo, hi):
+    """THE 16-to-8-bit mapping of a thermal frame (icaf_letterbox_y16_frames equals letterbox() of this image byte for byte): d =
+    max(hi - lo, 1), out(v) = min(255, ((max(v, lo) - lo) * 255 + (d >> 1)) // d).  Integers only, no special cases: v <= lo gives 0,
+    v >= hi gives 255 when hi > lo, a flat frame maps to 0."""
+    f = _u16_frame(frame)
+    lo, hi = int(lo), int(hi)
+    if not 0 <= lo <= hi <= 65535:
+        raise ValueError(f"a gain-control window is 0 <= lo <= hi <= 65535, got ({lo}, {hi})")
+    d = max(hi - lo, 1)
+    x = (np.maximum(f.astype(np.int64), lo) - lo) * 255 + (d >> 1)
+    return np.minimum(x // d, 255).astype(np.uint8)
+
+
+def imread_u16(path):
+    """A 16-bit single-channel PNG or TIFF (raw thermal counts) as an (h0, w0) uint16 array."""
+    from PIL import Image
+    with Image.open(path) as im:
+        if im.mode not in ("I;16", "I;16L", "I;16B", "I;16N"):
+            raise ValueError(f"{path}: expected a 16-bit greyscale image (mode I;16), got mode {im.mode}")
+        return np.ascontiguousarray(np.asarray(im).astype(np.uint16))
+
+
 def warp_perspective(img, M, out_hw, border=0):
     """THE registration of a calibrated RGB / IR pair (icaf_letterbox_warp_frames equals letterbox() of this image byte for byte): img
     (hs, ws) or (hs, ws, ch) uint8 -> (h, w, ch) uint8, the source frame seen through the homography M.  M (3 x 3, rounded to float32
@@ -296,10 +357,13 @@ class LoadImages:
     """Iterate the image files of a folder / glob / single path: yields (path, CHW RGB uint8 letterboxed, BGR original,
     None) like the reference's LoadImages.__next__ (utils/datasets.py:205-241).  Video files are out of scope.
     native=True: no host letterbox — the second item is None and the consumer letterboxes the BGR original on the device
-    (Model.forward_frames)."""
+    (Model.forward_frames).  raw16=True: the files are 16-bit greyscale PNG / TIFF (raw thermal counts, imread_u16): the third item
+    is the (h0, w0) uint16 original, the second None — the consumer picks the gain-control window (agc_window / agc_u16_to_u8 on the
+    host, or Model.forward_frames(formats=(None, "y16")) on the device)."""
 
-    def __init__(self, path, img_size=640, stride=32, native=False):
+    def __init__(self, path, img_size=640, stride=32, native=False, raw16=False):
         self.native = bool(native)
+        self.raw16 = bool(raw16)
         self.files = _list_images(path)
         self.nf = len(self.files)
         self.img_size, self.stride, self.mode, self.cap = img_size, stride, "image", None
@@ -318,6 +382,8 @@ class LoadImages:
             raise StopIteration
         path = self.files[self.count]
         self.count += 1
+        if self.raw16:
+            return path, None, imread_u16(path), self.cap
         img0 = imread_bgr(path)
         if self.native:
             return path, None, img0, self.cap

@@ -40,7 +40,7 @@ const char* icaf_last_error(void);
 /* Probe knobs of the library, set by the host's one options object (icafusion_amd/options.py) when the library is loaded — the library reads no
  * environment variable: "detect_elementwise" (!= 0: icaf_detect_decode by the one-thread-per-element kernel), "attn_qsplit" (n > 0: query splits per
  * head of icaf_cross_attention), "sppf_vpb" (n > 0: cap on the channel vectors per workgroup of icaf_sppf_pool), "letterbox_direct" (!= 0:
- * icaf_letterbox_frames, icaf_letterbox_yuv_frames and icaf_letterbox_warp_frames tap global memory in every tile instead of staging in LDS; set by a caller for an A/B, not by the options object),
+ * icaf_letterbox_frames, icaf_letterbox_yuv_frames, icaf_letterbox_warp_frames and icaf_letterbox_y16_frames tap global memory in every tile instead of staging in LDS; set by a caller for an A/B, not by the options object),
  * "index64" (!= 0: the element kernel of icaf_dmff_pool_tokens and icaf_upsample_nearest launch the 64-bit-index instantiations they otherwise
  * keep for 2^31 vectors and more), "attn_stream" (!= 0: icaf_cross_attention launches the key-streaming form for every shape, for A/B timings
  * and tests; set by a caller, not by the options object), "area_direct" (!= 0: the area rows of icaf_resize_frames recompute their vertical
@@ -534,6 +534,54 @@ typedef struct icaf_warp_geom {
 } icaf_warp_geom;          /* 104 bytes */
 int icaf_letterbox_warp_frames(const void* arena, const icaf_warp_geom* geom, int nstreams, int B, void* dst, int ctot, int H, int W,
                                int swap_rb, icaf_stream_t s);
+
+/* ---- 16-bit thermal frames (utils/datasets.py: agc_window, agc_u16_to_u8, then letterbox) ---------------------------------------
+ * Uncooled LWIR cameras deliver 14- or 16-bit raw counts (Y16).  Automatic gain control picks a window [lo, hi] from the frame's
+ * histogram and maps it linearly onto 0..255; both steps are stated here in integers, no floating point anywhere in them.
+ *   Frame: h0 x w0 little-endian uint16; g.pitch in BYTES, even, >= 2 * w0; g.offset 16-byte aligned; g.ch is 1.
+ *   Window (mode 1), clip_lo / clip_hi in basis points, 0..4999: n = h0 * w0, C(v) = pixels <= v, D(v) = pixels >= v;
+ *     lo = the smallest v with 10000 * C(v) > clip_lo * n, hi = the largest v with 10000 * D(v) > clip_hi * n (64-bit products, both
+ *     inequalities strict; clip (0, 0) gives the frame's minimum and maximum; clip_lo + clip_hi < 10000 implies lo <= hi).  Row padding
+ *     never enters the histogram.  Mode 0: the caller's (lo, hi), 0 <= lo <= hi <= 65535, taken as is.
+ *   Mapping: d = max(hi - lo, 1), out(v) = min(255, ((max(v, lo) - lo) * 255 + (d >> 1)) / d), a flooring integer division, no special
+ *     cases: v <= lo gives 0, v >= hi gives 255 when hi > lo, a flat frame maps to 0.  The numerator x is at most 65535 * 255 + 32767 <
+ *     2^24.  The kernels multiply instead of dividing: with m = 2^40 / d + 1 (flooring), m * d = 2^40 + e with 1 <= e <= d, so
+ *     x * m / 2^40 = x / d + x * e / (d * 2^40); x = q * d + r with r <= d - 1 leaves a gap of at least 1 / d to q + 1, and
+ *     x * e / (d * 2^40) < 1 / d because x * e < 2^24 * 2^16: (x * m) >> 40 == x / d for every numerator and divisor in range, and
+ *     x * m < 2^24 * (2^40 + 1) fits 64 bits.
+ *   Composition: MAP AT NATIVE RESOLUTION, THEN LETTERBOX — the output equals letterbox(grey -> 3 planes of agc_u16_to_u8(frame, lo,
+ *     hi)); each of the four bilinear taps of an output pixel is mapped to a byte, then icaf_letterbox_frames' fp32 tap arithmetic runs
+ *     on those bytes.  The 8-bit thermal frame never exists in memory.
+ * icaf_y16_window: fills window[nstreams * B][2] (DEVICE int32 lo, hi; entry modality * B + image) for every kind-1 row of geom: mode 0
+ *   copies the row's lo / hi, mode 1 runs the select above.  Rows of kind 0 leave their entry untouched.  One workgroup per frame, two
+ *   passes over it: 256 bins of v >> 8, then 256 bins of v & 255 inside the high byte that holds the lo rank and inside the one that
+ *   holds the hi rank; every wave counts into its own LDS copy and equal values of a wave are counted with one addition.  Counts are
+ *   integers: the result does not depend on the order of the additions.  No host synchronisation, nothing read back.
+ * icaf_letterbox_y16_frames: icaf_letterbox_frames for tables that hold Y16 rows.  arena, dst, nstreams, B, ctot, H, W, the grid, the
+ *   32 x 64 tile, the alignment rules, the refusals and "every byte of the planes written exactly once, 114 outside the block" are
+ *   icaf_letterbox_frames'; geom: DEVICE table of nstreams * B 72-byte rows; window: the table icaf_y16_window filled (4-byte aligned).
+ *   kind 0: g is exactly icaf_letterbox_frames' row (ch 3 or 1) and the tile produces exactly its bytes (the same device function),
+ *     swap_rb included; the other fields and `window` are not read.
+ *   kind 1: a Y16 frame, mapped with its row of `window` whatever its mode; the three planes hold the same bytes, swap_rb is not read.
+ *   Budget rule of a kind-1 row: the MAPPED bytes are staged, so the rule is icaf_letterbox_frames' for a grey frame — with rows =
+ *   (int)(32 sy) + 4 capped at h0 and cols = (int)(64 sx) + 4 capped at w0, a tile stages rows rows of (cols + 30) / 16 16-byte vectors
+ *   if that fits ICAF_Y16_LDS_BYTES and sx, sy < 1024.  A staged vector is 16 pixels from a pixel index (row * pitch / 2 + column) that is
+ *   a multiple of 16: two aligned 16-byte loads (single pixels where a load would cross the frame's last byte), each pixel mapped
+ *   once while it is written to LDS.  Otherwise, or with the probe knob "letterbox_direct", every tap is one clamped 2-byte load plus
+ *   the mapping.  No load leaves the frame's h0 * pitch bytes.
+ *   The host guarantees (icafusion_amd/ops.py validate_y16_frames): everything icaf_letterbox_frames asks of g of a kind-0 row; for
+ *   kind 1 ch == 1, offset % 16 == 0, pitch even and >= 2 * w0, offset + h0 * pitch inside the arena, the block inside H x W, mode 0 or
+ *   1, clip_lo and clip_hi in 0..4999, 0 <= lo <= hi <= 65535 for mode 0. */
+enum { ICAF_Y16_LDS_BYTES = 20480 };     /* the mapped bytes of a grey frame: icaf_letterbox_frames' own budget */
+typedef struct icaf_y16_geom {
+    icaf_frame_geom g;     /* kind 0: exactly icaf_letterbox_frames' row (ch 3 or 1).  kind 1: ch is 1, pitch in bytes over 2-byte pixels */
+    int kind, mode;        /* kind 0 plain, 1 Y16; mode 0 = window (lo, hi) given, 1 = percentile */
+    int lo, hi;            /* mode 0: the window */
+    int clip_lo, clip_hi;  /* mode 1: basis points clipped at either end */
+} icaf_y16_geom;           /* 72 bytes */
+int icaf_y16_window(const void* arena, const icaf_y16_geom* geom, int nstreams, int B, int* window, icaf_stream_t s);
+int icaf_letterbox_y16_frames(const void* arena, const icaf_y16_geom* geom, const int* window, int nstreams, int B, void* dst, int ctot,
+                              int H, int W, int swap_rb, icaf_stream_t s);
 
 /* ---- native validation frames(utils/datasets.py:1116-1122, load_image_rgb_ir: longest side to img_size, then letterbox's padding) ----
  * icaf_resize_frames: icaf_letterbox_frames with a resize mode per descriptor, so that one launch serves a rectangular validation batch
