@@ -1,7 +1,7 @@
 // Device letterbox of native camera frames (utils/datasets.py: letterbox = resize_bilinear to new_unpad + grey padding), byte for byte:
 // decoder-layout frames (H0 x W0 x ch interleaved uint8, own row pitch) -> the plan's uint8 [B][ctot][H][W] input planes.  Built with fp
 // contraction off (build.py): every product and sum rounds like resize_bilinear's separate fp32 numpy operations.  The tile itself
-// (lb_tile) and the entry point's checks (frames_launch_prepare) are in frames_core.h, shared with resize.hip; this kernel stays beside
+// (lb_tile) and the entry point's checks and launch (frames_launch) are in frames_core.h, shared with resize.hip; this kernel stays beside
 // resize_frames_kernel's mode-0 branch because it is the faster of the two on staged tiles (profiles/frames_tile_ab.json).
 #include "frames_core.h"
 
@@ -25,10 +25,5 @@ using namespace icaf;
 
 extern "C" int icaf_letterbox_frames(const void* arena, const icaf_frame_geom* geom, int nstreams, int B, void* dst, int ctot, int H, int W,
                                      int swap_rb, icaf_stream_t s) {
-    dim3 grid;
-    if (const int rc = frames_launch_prepare("icaf_letterbox_frames", arena, geom, nullptr, dst, nstreams, B, ctot, H, W, grid)) return rc;
-    hipLaunchKernelGGL(letterbox_frames_kernel, grid, dim3(LB_TX, LB_TH), 0, S(s), (const unsigned char*)arena, geom, B, ctot, H, W, (unsigned char*)dst,
-                       swap_rb ? 1 : 0, g_opt.letterbox_direct ? 1 : 0);
-    ICAF_LAUNCH_CHECK();
-    return ICAF_OK;
+    return frames_launch("icaf_letterbox_frames", letterbox_frames_kernel, arena, geom, nullptr, dst, nstreams, B, ctot, H, W, swap_rb, s);
 }

@@ -80,88 +80,42 @@ __device__ __forceinline__ void warp_px(const unsigned char* __restrict__ src, c
     }
 }
 
-// One thread: 16 output columns of one output row, three planes: lb_rows with its four byte fetches replaced by warp_px.  STAGED: source
-// bytes come from the LDS box of `t` where it holds them.
+// The tap of lb_rows_taps: aligned pixel (yy[i], x) — lb_rows with its four byte fetches replaced by warp_px.  STAGED: source bytes come
+// from the LDS box of `t` where it holds them.
 template <bool STAGED>
-__device__ __forceinline__ void warp_rows(const unsigned char* __restrict__ src, const icaf_warp_geom& q, const unsigned char* lds, const WarpTile& t,
-                                          unsigned char* __restrict__ dst, long long plane_stride, int H, int W, int swap_rb) {
-    const icaf_frame_geom& g = q.g;
-    const int x = blockIdx.x * LB_TW + threadIdx.x * LB_PX, r = blockIdx.y * LB_TH + threadIdx.y;
-    if (x >= W || r >= H) return;
-    unsigned char* o = dst + (long long)r * W + x;
-    const u32x4 padv = {0x72727272u, 0x72727272u, 0x72727272u, 0x72727272u};
-    const int jr = r - g.top;
-    if (jr < 0 || jr >= g.nh || x + LB_PX <= g.left || x >= g.left + g.nw) {
-#pragma unroll
-        for (int c = 0; c < 3; ++c) *(u32x4*)(o + c * plane_stride) = padv;
-        return;
+struct WarpTap {
+    const unsigned char* __restrict__ src;
+    const icaf_warp_geom& q;
+    const unsigned char* lds;
+    const WarpTile& t;
+    int swap_rb, yy[2];
+
+    __device__ __forceinline__ WarpTap(const unsigned char* src, const icaf_warp_geom& q, const unsigned char* lds, const WarpTile& t, int swap_rb)
+        : src(src), q(q), lds(lds), t(t), swap_rb(swap_rb) {}
+    __device__ __forceinline__ void rows(const int* y) { yy[0] = y[0]; yy[1] = y[1]; }
+    __device__ __forceinline__ void operator()(int i, int x, float* out) const {
+        const bool rgb = q.g.ch == 3;
+        const int nplanes = rgb ? 3 : 1;
+        const int sc[3] = {rgb && swap_rb ? 2 : 0, rgb ? 1 : 0, rgb && !swap_rb ? 2 : 0};
+        warp_px<STAGED>(src, q, lds, t, yy[i], x, nplanes, sc, out);
     }
-    int yy[2];
-    float fy;
-    lb_tap(jr, g.sy, g.h0, yy[0], yy[1], fy);
-    const float gy = 1.0f - fy;
-    const bool rgb = g.ch == 3;
-    const int nplanes = rgb ? 3 : 1;
-    const int sc[3] = {rgb && swap_rb ? 2 : 0, rgb ? 1 : 0, rgb && !swap_rb ? 2 : 0};
-    u32x4 out[3] = {padv, padv, padv};
-#pragma unroll
-    for (int j = 0; j < LB_PX; ++j) {
-        const int jx = x + j - g.left;
-        if (jx < 0 || jx >= g.nw) continue;
-        int xx[2];
-        float fx;
-        lb_tap(jx, g.sx, g.w0, xx[0], xx[1], fx);
-        const float gx = 1.0f - fx;
-        // [row][column][plane] of the four taps.  A tap whose weight is +0 is not evaluated: it takes its neighbour's finite bytes and adds
-        // +0 to the lerp, the same bits (an aligned frame copied between pads evaluates one pixel, not four)
-        float a[2][2][3];
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                if ((i == 0 || fy != 0.0f) && (h == 0 || fx != 0.0f)) {
-                    warp_px<STAGED>(src, q, lds, t, yy[i], xx[h], nplanes, sc, a[i][h]);
-                } else {
-#pragma unroll
-                    for (int c = 0; c < 3; ++c) a[i][h][c] = h ? a[i][0][c] : a[0][0][c];
-                }
-            }
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            const float top = a[0][0][c] * gx + a[0][1][c] * fx;
-            const float bot = a[1][0][c] * gx + a[1][1][c] * fx;
-            float v = top * gy + bot * fy;
-            v = floorf(v + 0.5f);
-            v = fminf(fmaxf(v, 0.0f), 255.0f);
-            const int sh = 8 * (j & 3);
-            out[c][j >> 2] = (out[c][j >> 2] & ~(0xffu << sh)) | ((unsigned int)v << sh);
-        }
-    }
-#pragma unroll
-    for (int c = 0; c < 3; ++c) *(u32x4*)(o + c * plane_stride) = out[c];
-}
+};
 
 // One workgroup: the 32 x 64 output tile of a kind-1 row.  The stage rule (include/icaf.h; ops.warp_letterbox_staged states the same on the
 // host): the four corners of the aligned rectangle the tile taps are warped; if all have Z > 0 and finite coordinates, their bounding box,
 // widened by one pixel on the low and two on the high side and cut to the frame, is not empty and fits WARP_LDS, it is copied into LDS
-// with lb_tile's aligned 16-byte row copies.  Z is affine in (x, y), so it is positive on the whole rectangle and the rectangle's image is
+// with aligned 16-byte row copies (lb_stage).  Z is affine in (x, y), so it is positive on the whole rectangle and the rectangle's image is
 // the convex hull of the corners' images; the widening covers the floor / + 1 of the taps and the rounding of the fp32 coordinates, and a
 // tap that still falls outside the box reads the frame (warp_byte).  The choice is workgroup-uniform: every thread reaches the barrier.
 __device__ __forceinline__ void warp_tile(const unsigned char* __restrict__ src, const icaf_warp_geom& q, unsigned char* lds, unsigned char* __restrict__ d,
                                           long long plane_stride, int H, int W, int swap_rb, int force_direct) {
     const icaf_frame_geom& g = q.g;
-    const int ra = max((int)blockIdx.y * LB_TH, g.top) - g.top, rb = min(min((int)blockIdx.y * LB_TH + LB_TH, H), g.top + g.nh) - 1 - g.top;
-    const int ca = max((int)blockIdx.x * LB_TW, g.left) - g.left, cb = min(min((int)blockIdx.x * LB_TW + LB_TW, W), g.left + g.nw) - 1 - g.left;
     WarpTile t{0, 0, 0, 0, 0};
+    LbTile al{0, 0, 0, 0};                                         // the aligned rectangle the tile taps
     bool staged = false;
     int nvec = 0;
-    if (ra <= rb && ca <= cb && !force_direct) {
-        int ylo, yhi, xlo, xhi, other;
-        float f;
-        lb_tap(ra, g.sy, g.h0, ylo, other, f);
-        lb_tap(rb, g.sy, g.h0, other, yhi, f);
-        lb_tap(ca, g.sx, g.w0, xlo, other, f);
-        lb_tap(cb, g.sx, g.w0, other, xhi, f);
+    if (!force_direct && lb_extent(g, H, W, al)) {
+        const int ylo = al.y_lo, yhi = al.y_lo + al.nrows - 1, xlo = al.x_lo, xhi = al.x_lo + al.ncols - 1;
         float umin = INFINITY, umax = -INFINITY, vmin = INFINITY, vmax = -INFINITY;
         bool ok = true;
 #pragma unroll
@@ -184,27 +138,16 @@ __device__ __forceinline__ void warp_tile(const unsigned char* __restrict__ src,
         }
     }
     if (staged) {
-        const int tid = threadIdx.y * LB_TX + threadIdx.x;
         t.lstride = nvec * 16;
-        const long long frame_bytes = (long long)q.hs * g.pitch;
-        for (int idx = tid; idx < t.nrows * nvec; idx += LB_TX * LB_TH) {
-            const int row = idx / nvec, v = idx - row * nvec;
-            // g.offset is 16-byte aligned, so rounding a row's first byte down to a vector boundary never leaves the frame
-            const long long a = ((((long long)(t.j_lo + row) * g.pitch + (long long)t.i_lo * g.ch) >> 4) + v) << 4;
-            u32x4 w = {0u, 0u, 0u, 0u};
-            if (a + 16 <= frame_bytes) {
-                w = *(const u32x4*)(src + a);
-            } else {                                               // the frame's last, partial vector: byte by byte, nothing past hs * pitch
-#pragma unroll
-                for (int k = 0; k < 16; ++k)
-                    if (a + k < frame_bytes) w[k >> 2] |= (unsigned int)src[a + k] << (8 * (k & 3));
-            }
-            *(u32x4*)(lds + (long long)row * t.lstride + v * 16) = w;
-        }
+        // g.offset is 16-byte aligned, so rounding a row's first byte down to a vector boundary never leaves the frame; the frame's last,
+        // partial vector goes byte by byte, nothing past hs * pitch
+        lb_stage(src, 0, (long long)q.hs * g.pitch, (long long)t.j_lo * g.pitch + (long long)t.i_lo * g.ch, g.pitch, t.nrows, nvec, lds);
         __syncthreads();
-        warp_rows<true>(src, q, lds, t, d, plane_stride, H, W, swap_rb);
+        WarpTap<true> tap(src, q, lds, t, swap_rb);
+        lb_rows_taps(g, tap, d, plane_stride, H, W);
     } else {
-        warp_rows<false>(src, q, lds, t, d, plane_stride, H, W, swap_rb);
+        WarpTap<false> tap(src, q, lds, t, swap_rb);
+        lb_rows_taps(g, tap, d, plane_stride, H, W);
     }
 }
 
@@ -212,14 +155,10 @@ __global__ __launch_bounds__(LB_TX * LB_TH) void letterbox_warp_frames_kernel(co
                                                                              const icaf_warp_geom* __restrict__ geom, int B, int ctot, int H, int W,
                                                                              unsigned char* __restrict__ dst, int swap_rb, int force_direct) {
     __shared__ __attribute__((aligned(16))) unsigned char lds[WARP_LDS_ALLOC];
-    const int img = blockIdx.z, m = img / B, b = img - m * B;      // img = modality * B + b
-    const icaf_warp_geom q = geom[img];
-    const long long plane_stride = (long long)H * W;
-    unsigned char* d = dst + ((long long)b * ctot + 3 * m) * plane_stride;
-    if (q.kind == 0)                                               // workgroup-uniform: icaf_letterbox_frames' row, its tile, its bytes
-        lb_tile(arena + q.g.offset, q.g, lds, d, plane_stride, H, W, swap_rb, force_direct);
-    else
-        warp_tile(arena + q.g.offset, q, lds, d, plane_stride, H, W, swap_rb, force_direct);
+    icaf_warp_geom q;
+    unsigned char* d;
+    if (lb_table_row(arena, geom, B, ctot, H, W, dst, lds, swap_rb, force_direct, q, d))
+        warp_tile(arena + q.g.offset, q, lds, d, (long long)H * W, H, W, swap_rb, force_direct);
 }
 
 }  // namespace icaf
@@ -229,11 +168,5 @@ using namespace icaf;
 extern "C" int icaf_letterbox_warp_frames(const void* arena, const icaf_warp_geom* geom, int nstreams, int B, void* dst, int ctot, int H, int W,
                                           int swap_rb, icaf_stream_t s) {
     static_assert(sizeof(icaf_warp_geom) == 104, "icaf_warp_geom is 104 bytes (include/icaf.h)");
-    dim3 grid;
-    if (const int rc = frames_launch_prepare("icaf_letterbox_warp_frames", arena, (const icaf_frame_geom*)geom, nullptr, dst, nstreams, B, ctot, H, W, grid))
-        return rc;
-    hipLaunchKernelGGL(letterbox_warp_frames_kernel, grid, dim3(LB_TX, LB_TH), 0, S(s), (const unsigned char*)arena, geom, B, ctot, H, W,
-                       (unsigned char*)dst, swap_rb ? 1 : 0, g_opt.letterbox_direct ? 1 : 0);
-    ICAF_LAUNCH_CHECK();
-    return ICAF_OK;
+    return frames_launch("icaf_letterbox_warp_frames", letterbox_warp_frames_kernel, arena, geom, nullptr, dst, nstreams, B, ctot, H, W, swap_rb, s);
 }

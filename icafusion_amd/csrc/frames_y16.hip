@@ -230,24 +230,13 @@ __device__ __forceinline__ void y16_rows_direct(const unsigned char* __restrict_
 // aligned) frame: two aligned 16-byte loads.  The choice between the paths is workgroup-uniform.
 __device__ __forceinline__ void y16_tile(const unsigned char* __restrict__ frame, const icaf_frame_geom& g, const Y16Map& k, unsigned char* lds,
                                          unsigned char* __restrict__ d, long long plane_stride, int H, int W, int force_direct) {
-    const int ra = max((int)blockIdx.y * LB_TH, g.top) - g.top, rb = min(min((int)blockIdx.y * LB_TH + LB_TH, H), g.top + g.nh) - 1 - g.top;
-    const int ca = max((int)blockIdx.x * LB_TW, g.left) - g.left, cb = min(min((int)blockIdx.x * LB_TW + LB_TW, W), g.left + g.nw) - 1 - g.left;
     icaf_frame_geom m8 = g;
     m8.pitch = g.pitch >> 1;
     LbTile t{0, 0, 0, 0};
     bool staged = false;
     int rows_cap, cols_cap, nvec;
-    if (ra <= rb && ca <= cb && !force_direct && lb_budget(m8, rows_cap, cols_cap, nvec)) {      // LB_LDS == Y16_LDS (asserted below)
-        int i0, i1, hi0, hi1;
-        float f;
-        lb_tap(ra, g.sy, g.h0, i0, i1, f);
-        lb_tap(rb, g.sy, g.h0, hi0, hi1, f);
-        t.y_lo = i0; t.nrows = hi1 - i0 + 1;
-        lb_tap(ca, g.sx, g.w0, i0, i1, f);
-        lb_tap(cb, g.sx, g.w0, hi0, hi1, f);
-        t.x_lo = i0; t.ncols = hi1 - i0 + 1;
+    if (!force_direct && lb_budget(m8, rows_cap, cols_cap, nvec) && lb_extent(g, H, W, t))      // LB_LDS == Y16_LDS (asserted below)
         staged = t.nrows <= rows_cap && t.ncols <= cols_cap;
-    }
     if (staged) {
         const int tid = threadIdx.y * LB_TX + threadIdx.x, lstride = nvec * 16;
         const long long frame_bytes = (long long)g.h0 * g.pitch;
@@ -284,19 +273,16 @@ __device__ __forceinline__ void y16_tile(const unsigned char* __restrict__ frame
 static_assert(Y16_LDS == LB_LDS, "y16_tile states its budget through lb_budget: the two limits are one number");
 
 __global__ __launch_bounds__(LB_TX * LB_TH) void letterbox_y16_frames_kernel(const unsigned char* __restrict__ arena,
-                                                                            const icaf_y16_geom* __restrict__ geom, const int* __restrict__ window,
-                                                                            int B, int ctot, int H, int W, unsigned char* __restrict__ dst, int swap_rb,
-                                                                            int force_direct) {
+                                                                            const icaf_y16_geom* __restrict__ geom, int B, int ctot, int H, int W,
+                                                                            unsigned char* __restrict__ dst, int swap_rb, int force_direct,
+                                                                            const int* __restrict__ window) {
     __shared__ __attribute__((aligned(16))) unsigned char lds[Y16_LDS_ALLOC];
-    const int img = blockIdx.z, m = img / B, b = img - m * B;      // img = modality * B + b
-    const icaf_y16_geom q = geom[img];
-    const long long plane_stride = (long long)H * W;
-    unsigned char* d = dst + ((long long)b * ctot + 3 * m) * plane_stride;
-    if (q.kind == 0) {                                             // workgroup-uniform: icaf_letterbox_frames' row, its tile, its bytes
-        lb_tile(arena + q.g.offset, q.g, lds, d, plane_stride, H, W, swap_rb, force_direct);
-    } else {
+    icaf_y16_geom q;
+    unsigned char* d;
+    if (lb_table_row(arena, geom, B, ctot, H, W, dst, lds, swap_rb, force_direct, q, d)) {
+        const int img = blockIdx.z;
         const Y16Map k = y16_map_of(window[2 * img], window[2 * img + 1]);
-        y16_tile(arena + q.g.offset, q.g, k, lds, d, plane_stride, H, W, force_direct);
+        y16_tile(arena + q.g.offset, q.g, k, lds, d, (long long)H * W, H, W, force_direct);
     }
 }
 
@@ -317,12 +303,6 @@ extern "C" int icaf_y16_window(const void* arena, const icaf_y16_geom* geom, int
 
 extern "C" int icaf_letterbox_y16_frames(const void* arena, const icaf_y16_geom* geom, const int* window, int nstreams, int B, void* dst, int ctot,
                                          int H, int W, int swap_rb, icaf_stream_t s) {
-    dim3 grid;
-    if (const int rc = frames_launch_prepare("icaf_letterbox_y16_frames", arena, (const icaf_frame_geom*)geom, window, dst, nstreams, B, ctot, H, W, grid))
-        return rc;
     if (!window) return fail(ICAF_ERR_ARG, "icaf_letterbox_y16_frames: null window table");
-    hipLaunchKernelGGL(letterbox_y16_frames_kernel, grid, dim3(LB_TX, LB_TH), 0, S(s), (const unsigned char*)arena, geom, window, B, ctot, H, W,
-                       (unsigned char*)dst, swap_rb ? 1 : 0, g_opt.letterbox_direct ? 1 : 0);
-    ICAF_LAUNCH_CHECK();
-    return ICAF_OK;
+    return frames_launch("icaf_letterbox_y16_frames", letterbox_y16_frames_kernel, arena, geom, window, dst, nstreams, B, ctot, H, W, swap_rb, s, window);
 }

@@ -618,201 +618,63 @@ class Model(HipModule):
         host-letterboxed batch.  FrameGeometry.window holds, per modality, None or the cuda int32 (B, 2) windows this call used (a view
         of the model's table: the next call of the same shapes overwrites it), so that a caller can feed a damped copy back as agc_window."""
         self._check_eval()
-        if formats is not None and any(f == "y16" for f in formats):
-            return self._forward_y16_frames(rgb, ir, img_size, bgr, augment, val_size, formats, align, agc_clip, agc_window)
-        if align is not None:
-            return self._forward_warp_frames(rgb, ir, img_size, bgr, augment, val_size, formats, align, align_border)
-        if formats is not None and any(f is not None for f in formats):
-            return self._forward_yuv_frames(rgb, ir, img_size, bgr, augment, val_size, formats, yuv_matrix)
+        kind = ops.frame_kind(formats, align, val_size)                    # the table's kind (ops.KINDS); refuses what cannot be combined
+        formats = (None, None) if formats is None else tuple(formats)
+        matrix = ops.yuv_matrix_code(yuv_matrix) if kind.name == "yuv" else 0
         try:
-            *fr, shapes, _ = ops.frame_lists(rgb, ir)
+            *fr, shapes, _, m, _, mats = kind.lists(rgb, ir, formats, align)
         except ValueError as e:
-            raise ValueError(f"forward_frames expects cuda uint8 frames: {e}") from None
-        if not all(f.is_cuda for f in fr[0] + fr[1]):
-            raise ValueError("forward_frames expects cuda uint8 frames (no CPU fallback exists)")
-        B = len(fr[0])
+            raise ValueError(f"forward_frames expects cuda {kind.noun}: {e}") from None
+        frames = fr[0] + fr[1]
+        if not all(f.is_cuda for f in frames):
+            raise ValueError(f"forward_frames expects cuda {kind.noun} (no CPU fallback exists)")
+        B, device = len(fr[0]), frames[0].device
         H, W = (img_size, img_size) if isinstance(img_size, int) else img_size
         self._check_stride(H, W, int(self.stride.max()))
-        st = self._frame_state(H, W, shapes, tuple(int(f.shape[2]) for f in fr[0] + fr[1]), fr[0][0].device, val_size)
-        plan = (self.tta_plan_for if augment else self.plan_for)(B, H, W, fr[0][0].device, u8=True)
-        dst = plan.inputs[0]
-        if st["dst"] is not dst:                          # the plan was rebuilt (evicted from the cache): bind the launch to its new input
-            if st["mode"] is None:
-                st["launch"] = ops.letterbox_frames(st["arena"], st["geom"], st["geom_dev"], dst, swap_rb=bgr)
-            else:
-                st["launch"] = ops.resize_frames(st["arena"], st["geom"], st["mode_dev"], st["geom_dev"], dst, swap_rb=bgr, mode=st["mode"])
-            st["dst"] = dst
-        for g, f in zip(st["geom"], fr[0] + fr[1]):
-            o, n = int(g["offset"]), f.numel()
-            st["arena"][o:o + n].view(f.shape).copy_(f)
-        st["launch"].args = st["launch"].args[:-1] + (int(bool(bgr)),)
-        st["launch"](ops.current_stream_ptr())
-        plan.run()
-        out = self._result(plan.outputs)
-        return ((out, None) if augment else out), st["info"]
-
-    def _forward_yuv_frames(self, rgb, ir, img_size, bgr, augment, val_size, formats, yuv_matrix):
-        """forward_frames with at least one YUV 4:2:0 modality: the same steps around icaf_letterbox_yuv_frames and its 80-byte rows."""
-        if val_size is not None:
-            raise ValueError("forward_frames: YUV 4:2:0 frames have no validation geometry (val_size); the area down-scale reads interleaved frames")
-        matrix = ops.yuv_matrix_code(yuv_matrix)
-        try:
-            *fr, shapes, _ = ops.yuv_frame_lists(rgb, ir, formats)
-        except ValueError as e:
-            raise ValueError(f"forward_frames expects cuda uint8 frames: {e}") from None
-        if not all(f.is_cuda for f in fr[0] + fr[1]):
-            raise ValueError("forward_frames expects cuda uint8 frames (no CPU fallback exists)")
-        B, device = len(fr[0]), fr[0][0].device
-        H, W = (img_size, img_size) if isinstance(img_size, int) else img_size
-        self._check_stride(H, W, int(self.stride.max()))
-        layouts = tuple(fmt if fmt is not None else int(f.shape[2]) for fmt, frames in zip(formats, fr) for f in frames)
-        key = (H, W, tuple(shapes), layouts, matrix, device)
-        states = self.__dict__.setdefault("_frame_states", {})
-        st = states.pop(key, None)
-        if st is None:
-            geom1, scale = ops.frame_geometry(shapes, (H, W))
-            geom, nbytes = ops.pack_yuv_frames(np.concatenate((geom1, geom1)), layouts, matrix=matrix)
-            st = {"geom": geom, "geom_dev": ops.geom_tensor(geom, device), "arena": torch.zeros((nbytes,), dtype=torch.uint8, device=device),
-                  "info": ops.FrameGeometry(geom, scale, torch.from_numpy(scale).to(device)), "dst": None, "launch": None}
-            while len(states) >= 8:
-                states.pop(next(iter(states)))
-        states[key] = st
-        plan = (self.tta_plan_for if augment else self.plan_for)(B, H, W, device, u8=True)
-        dst = plan.inputs[0]
-        if st["dst"] is not dst:
-            st["launch"] = ops.letterbox_yuv_frames(st["arena"], st["geom"], st["geom_dev"], dst, swap_rb=bgr)
-            st["dst"] = dst
-        for o, f in zip(st["geom"]["g"]["offset"], fr[0] + fr[1]):        # a YUV buffer is one run of bytes: luma rows, then its chroma
-            st["arena"][int(o):int(o) + f.numel()].view(f.shape).copy_(f)
-        st["launch"].args = st["launch"].args[:-1] + (int(bool(bgr)),)
-        st["launch"](ops.current_stream_ptr())
-        plan.run()
-        out = self._result(plan.outputs)
-        return ((out, None) if augment else out), st["info"]
-
-    def _forward_y16_frames(self, rgb, ir, img_size, bgr, augment, val_size, formats, align, clip, window):
-        """forward_frames with at least one 16-bit thermal modality: the same steps around icaf_y16_window, icaf_letterbox_y16_frames and
-        their 72-byte rows.  The state is keyed by the shapes; clip and window are written into the table on every call."""
-        if val_size is not None:
-            raise ValueError("forward_frames: 16-bit thermal frames ('y16') have no validation geometry (val_size); the validation sets are 8-bit")
-        if align is not None:
-            raise ValueError("forward_frames: align= takes interleaved 8-bit frames; a 16-bit thermal modality ('y16') cannot be combined with it yet")
-        try:
-            *fr, shapes, _ = ops.y16_frame_lists(rgb, ir, formats)
-        except ValueError as e:
-            raise ValueError(f"forward_frames expects cuda frames: {e}") from None
-        if not all(f.is_cuda for f in fr[0] + fr[1]):
-            raise ValueError("forward_frames expects cuda frames (no CPU fallback exists)")
-        B, device = len(fr[0]), fr[0][0].device
-        H, W = (img_size, img_size) if isinstance(img_size, int) else img_size
-        self._check_stride(H, W, int(self.stride.max()))
-        layouts = tuple(fmt if fmt is not None else int(f.shape[2]) for fmt, frames in zip(formats, fr) for f in frames)
-        key = (H, W, tuple(shapes), layouts, "y16", device)
-        states = self.__dict__.setdefault("_frame_states", {})
-        st = states.pop(key, None)
-        if st is None:
-            geom1, scale = ops.frame_geometry(shapes, (H, W))
-            geom, nbytes = ops.pack_y16_frames(np.concatenate((geom1, geom1)), layouts)
-            wtab = torch.zeros((2 * B, 2), dtype=torch.int32, device=device)
-            st = {"geom": geom, "geom_dev": ops.geom_tensor(geom, device), "arena": torch.zeros((nbytes,), dtype=torch.uint8, device=device),
-                  "window": wtab, "dst": None, "launch": None, "select": None,
-                  "info": ops.FrameGeometry(geom, scale, torch.from_numpy(scale).to(device),
-                                            tuple(wtab[m * B:(m + 1) * B] if fmt else None for m, fmt in enumerate(formats)))}
-            while len(states) >= 8:
-                states.pop(next(iter(states)))
-        states[key] = st
-        # this call's clip and windows: the rows are packed again around the same geometry (same offsets), validated, and copied in stream order
-        wins = None
-        if window is not None:
-            per = ops._y16_windows(window, B)
-            wins = [w if fmt else None for fmt in formats for w in per]
-        geom, _ = ops.pack_y16_frames(st["geom"], layouts, clip=clip, window=wins)
-        ops.validate_y16_frames(geom, st["arena"].numel(), H, W)
-        st["geom"][:] = geom
-        plan = (self.tta_plan_for if augment else self.plan_for)(B, H, W, device, u8=True)
-        dst = plan.inputs[0]
-        if st["dst"] is not dst:
-            st["select"] = ops.y16_window(st["arena"], st["geom"], st["geom_dev"], st["window"], B, H, W)
-            st["launch"] = ops.letterbox_y16_frames(st["arena"], st["geom"], st["geom_dev"], st["window"], dst, swap_rb=bgr)
-            st["dst"] = dst
-        st["geom_dev"].copy_(ops.geom_tensor(st["geom"]))
-        for o, f in zip(st["geom"]["g"]["offset"], fr[0] + fr[1]):        # tight rows: a frame is one run of bytes
-            st["arena"][int(o):int(o) + f.numel()].view(f.shape).copy_(f)
-        st["launch"].args = st["launch"].args[:-1] + (int(bool(bgr)),)
-        st["select"](ops.current_stream_ptr())
-        st["launch"](ops.current_stream_ptr())
-        plan.run()
-        out = self._result(plan.outputs)
-        return ((out, None) if augment else out), st["info"]
-
-    def _forward_warp_frames(self, rgb, ir, img_size, bgr, augment, val_size, formats, align, border):
-        """forward_frames of a calibrated pair: the same steps around icaf_letterbox_warp_frames and its 104-byte rows.  The state is keyed
-        by the shapes; the matrices and the border are written into the table on every call."""
-        if val_size is not None:
-            raise ValueError("forward_frames: align= has no validation geometry (val_size); validation sets are registered offline")
-        if formats is not None and any(f is not None for f in formats):
-            raise ValueError("forward_frames: align= takes interleaved frames; a YUV 4:2:0 modality (formats) cannot be combined with it yet")
-        border = int(border)
-        if not 0 <= border <= 255:
-            raise ValueError(f"forward_frames: align_border {border} outside 0..255")
-        *fr, shapes, _, m, src_shapes, mats = ops.warp_frame_lists(rgb, ir, align)
-        if not all(f.is_cuda for f in fr[0] + fr[1]):
-            raise ValueError("forward_frames expects cuda uint8 frames (no CPU fallback exists)")
-        B, device = len(fr[0]), fr[0][0].device
-        H, W = (img_size, img_size) if isinstance(img_size, int) else img_size
-        self._check_stride(H, W, int(self.stride.max()))
-        chans = tuple(int(f.shape[2]) for f in fr[0] + fr[1])
-        key = (H, W, tuple(shapes), "align", m, tuple(src_shapes), chans, device)
-        states = self.__dict__.setdefault("_frame_states", {})
-        st = states.pop(key, None)
-        if st is None:
-            geom1, scale = ops.frame_geometry(shapes, (H, W))
-            warped = [(hs, ws, c) for (hs, ws), c in zip(src_shapes, chans[m * B:(m + 1) * B])]
-            plain = list(chans[(1 - m) * B:(2 - m) * B])
-            sources = warped + plain if m == 0 else plain + warped
-            placeholder = [np.eye(3, dtype=np.float32)] * B
-            geom, nbytes = ops.pack_warp_frames(np.concatenate((geom1, geom1)), sources, placeholder + [None] * B if m == 0 else [None] * B + placeholder)
-            st = {"geom": geom, "geom_dev": ops.geom_tensor(geom, device), "arena": torch.zeros((nbytes,), dtype=torch.uint8, device=device),
-                  "info": ops.FrameGeometry(geom, scale, torch.from_numpy(scale).to(device)), "dst": None, "launch": None}
-            while len(states) >= 8:
-                states.pop(next(iter(states)))
-        states[key] = st
+        st = self._frame_state(kind, H, W, shapes, ops.frame_specs(formats, fr, m), matrix, device, val_size)
         geom = st["geom"]
-        geom["m"][m * B:(m + 1) * B] = mats.reshape(B, 9)
-        geom["border"][m * B:(m + 1) * B] = border
+        if kind.update is not None:      # this call's matrices / border / clip / windows: written into the rows, validated, copied in stream order below
+            kind.update(geom, B, formats, m, mats=mats, border=align_border, clip=agc_clip, wins=None if agc_window is None else ops._y16_windows(agc_window, B))
+            kind.validate(geom, st["arena"].numel(), H, W)
         plan = (self.tta_plan_for if augment else self.plan_for)(B, H, W, device, u8=True)
         dst = plan.inputs[0]
-        if st["dst"] is not dst:
-            st["launch"] = ops.letterbox_warp_frames(st["arena"], geom, st["geom_dev"], dst, swap_rb=bgr)
+        if st["dst"] is not dst:                          # the plan was rebuilt (evicted from the cache): bind the launches to its new input
+            st["launches"] = kind.launches(st["arena"], geom, st["geom_dev"], dst, bgr, B, window=st["window"], mode=st["mode"], mode_dev=st["mode_dev"])
             st["dst"] = dst
-        else:
-            ops.validate_warp_frames(geom, st["arena"].numel(), H, W)
-        st["geom_dev"].copy_(ops.geom_tensor(geom))               # this call's matrices, in stream order in front of the launch
-        for o, f in zip(geom["g"]["offset"], fr[0] + fr[1]):
+        if kind.update is not None:
+            st["geom_dev"].copy_(ops.geom_tensor(geom))
+        for o, f in zip(ops.frame_rows(geom)["offset"], frames):          # tight rows (a YUV buffer: luma rows, then its chroma): a frame is one run of bytes
             st["arena"][int(o):int(o) + f.numel()].view(f.shape).copy_(f)
-        st["launch"].args = st["launch"].args[:-1] + (int(bool(bgr)),)
-        st["launch"](ops.current_stream_ptr())
+        last = st["launches"][-1]
+        last.args = last.args[:-1] + (int(bool(bgr)),)
+        for launch in st["launches"]:
+            launch(ops.current_stream_ptr())
         plan.run()
         out = self._result(plan.outputs)
         return ((out, None) if augment else out), st["info"]
 
-    def _frame_state(self, H, W, shapes, chans, device, val_size):
-        """forward_frames' geometry tables, arena and staging launch for one set of frame shapes: found, or made and kept (least recently used out)."""
-        key = (H, W, tuple(shapes), chans, device, val_size)
+    def _frame_state(self, kind, H, W, shapes, specs, matrix, device, val_size):
+        """forward_frames' table, arena and launches for one kind of table and one set of frame shapes: found, or made and kept (least
+        recently used out).  specs (ops.frame_specs) holds each frame's format, channels or source size."""
+        key = (kind.name, H, W, tuple(shapes), specs, matrix, device, val_size)
         states = self.__dict__.setdefault("_frame_states", {})
         st = states.pop(key, None)
         if st is None:
-            mode = None
+            mode = window = None
             if val_size is None:
                 geom1, scale = ops.frame_geometry(shapes, (H, W))
-            else:
+            else:                                         # (ops.frame_kind: the plain kind alone has the validation geometry)
                 geom1, mode1, scale = ops.val_geometry(shapes, val_size, (H, W))
                 mode = np.concatenate((mode1, mode1))
-            geom = np.concatenate((geom1, geom1))
-            nbytes = ops.pack_frames(geom, chans)
+            geom, nbytes = kind.pack(np.concatenate((geom1, geom1)), specs, matrix=matrix)
+            B = len(shapes)
+            if kind.window:                               # rows modality * B + image; FrameGeometry.window: the views of the 16-bit modalities
+                window = torch.zeros((2 * B, 2), dtype=torch.int32, device=device)
             st = {"geom": geom, "geom_dev": ops.geom_tensor(geom, device), "arena": torch.zeros((nbytes,), dtype=torch.uint8, device=device),
-                  "mode": mode, "mode_dev": None if mode is None else torch.from_numpy(mode).to(device),
-                  "info": ops.FrameGeometry(geom, scale, torch.from_numpy(scale).to(device)), "dst": None, "launch": None}
+                  "mode": mode, "mode_dev": None if mode is None else torch.from_numpy(mode).to(device), "window": window,
+                  "info": ops.FrameGeometry(geom, scale, torch.from_numpy(scale).to(device),
+                                            None if window is None else tuple(window[m * B:(m + 1) * B] if s == "y16" else None for m, s in enumerate(specs[::B]))),
+                  "dst": None, "launches": None}
             while len(states) >= 8:                       # a few sets of shapes stay resident (arena + table each)
                 states.pop(next(iter(states)))
         states[key] = st

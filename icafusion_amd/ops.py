@@ -1192,46 +1192,87 @@ def frame_geometry(shapes, new_shape, scaleup=True):
 def pack_frames(geom, channels, pitch=None, base=0):
     """Lay frames out back to back in a byte arena: fills offset / pitch / ch of the rows (pitch: bytes per row, default w0 * ch; frames
     start on FRAME_ALIGN boundaries from `base` on) and returns the first free byte behind them."""
-    chans = [channels] * len(geom) if isinstance(channels, int) else list(channels)
-    pitches = [pitch] * len(geom) if pitch is None or isinstance(pitch, int) else list(pitch)
     off = int(base)
-    for g, ch, p in zip(geom, chans, pitches):
-        off = -(-off // FRAME_ALIGN) * FRAME_ALIGN
-        g["offset"], g["ch"], g["pitch"] = off, int(ch), int(g["w0"]) * int(ch) if p is None else int(p)
-        off += int(g["h0"]) * int(g["pitch"])
+    for g, ch, p in zip(geom, _per_row(channels, len(geom)), _per_row(pitch, len(geom))):
+        off = _place(g, off, ch, int(g["w0"]) * int(ch) if p is None else p)
     return off
+
+
+def _per_row(v, n, single=lambda v: False):
+    """An argument of a pack function as a list of n: one value for all rows (None, an int, a string, or what `single` takes for one), or
+    one value per row."""
+    return [v] * n if v is None or isinstance(v, (int, str)) or single(v) else list(v)
+
+
+def _place(g, off, ch, pitch, nrows=None):
+    """The frame of descriptor row `g` at the first FRAME_ALIGN boundary from `off` on: sets offset / ch / pitch and returns the first byte
+    behind its `nrows` (default h0) rows."""
+    off = -(-int(off) // FRAME_ALIGN) * FRAME_ALIGN
+    g["offset"], g["ch"], g["pitch"] = off, int(ch), int(pitch)
+    return off + (int(g["h0"]) if nrows is None else int(nrows)) * int(pitch)
+
+
+def _table_rows(geom, dtype):
+    """Zeroed rows of a table kind around `geom`: frame_geometry's GEOM_DTYPE rows, or rows of the kind whose "g" is filled."""
+    rows = np.zeros((len(geom),), dtype)
+    rows["g"] = frame_rows(geom)
+    return rows
+
+
+def frame_rows(rows):
+    """The icaf_frame_geom rows of a table of any kind: GEOM_DTYPE rows themselves, or field "g" of the rows that embed them."""
+    return rows if rows.dtype == GEOM_DTYPE else rows["g"]
+
+
+def _tap_caps(g):
+    """The caps of the staging rules (include/icaf.h): the (rows, columns) a 32 x 64 tile of descriptor row `g` can tap at most, or None for
+    a tap scale of 1024 and more (such frames are never staged)."""
+    sx, sy = np.float32(g["sx"]), np.float32(g["sy"])
+    if not (sx < 1024 and sy < 1024):
+        return None
+    return min(int(g["h0"]), int(np.float32(32) * sy) + 4), min(int(g["w0"]), int(np.float32(64) * sx) + 4)
+
+
+def _rect_staged(g, ch, budget):
+    """One rectangle of `ch` bytes a pixel under `budget`: rows of whole 16-byte vectors, up to 15 bytes of alignment phase each."""
+    caps = _tap_caps(g)
+    return caps is not None and caps[0] * ((caps[1] * ch + 30) >> 4) * 16 <= budget
 
 
 def letterbox_staged(g):
     """The budget rule of icaf_letterbox_frames for one descriptor row (include/icaf.h): True = its tiles stage their source rectangle
     in LDS, False = they tap global memory (frames scaled down so far that a 32 x 64 tile's rectangle exceeds the budget)."""
-    sx, sy = np.float32(g["sx"]), np.float32(g["sy"])
-    if not (sx < 1024 and sy < 1024):
-        return False
-    rows = min(int(g["h0"]), int(np.float32(32) * sy) + 4)
-    cols = min(int(g["w0"]), int(np.float32(64) * sx) + 4)
-    return rows * ((cols * int(g["ch"]) + 30) >> 4) * 16 <= _lib.LETTERBOX_LDS_BYTES
+    return _rect_staged(g, int(g["ch"]), _lib.LETTERBOX_LDS_BYTES)
+
+
+def _validate_row(i, g, arena_bytes, H, W, src=None):
+    """validate_frames' checks of descriptor row i.  src = (hs, ws): the frame in the arena is that SOURCE (a calibrated pair's warped
+    modality) and h0 x w0 the aligned frame seen through it."""
+    off, h0, w0, pitch, ch, nh, nw, top, left = (int(g[k]) for k in ("offset", "h0", "w0", "pitch", "ch", "nh", "nw", "top", "left"))
+    hs, ws = (h0, w0) if src is None else src
+    if ch not in (1, 3):
+        raise ValueError(f"frame {i}: {ch} interleaved channels (1 or 3)")
+    if hs < 1 or ws < 1:
+        raise ValueError(f"frame {i}: empty source frame ({hs}x{ws})" if src else f"frame {i}: empty frame or resized block ({h0}x{w0} -> {nh}x{nw})")
+    if h0 < 1 or w0 < 1 or nh < 1 or nw < 1:
+        raise ValueError(f"frame {i}: empty {'aligned ' if src else ''}frame or resized block ({h0}x{w0} -> {nh}x{nw})")
+    if pitch < ws * ch:
+        raise ValueError(f"frame {i}: pitch {pitch} is less than a {'source ' if src else ''}row of {ws} pixels x {ch} channels")
+    if off < 0 or off % 16:
+        raise ValueError(f"frame {i}: offset {off} must be a non-negative multiple of 16")
+    if off + hs * pitch > arena_bytes:
+        raise ValueError(f"frame {i}: bytes [{off}, {off + hs * pitch}) leave the arena of {arena_bytes} bytes")
+    if top < 0 or left < 0 or top + nh > H or left + nw > W:
+        raise ValueError(f"frame {i}: resized block {nh}x{nw} at ({top}, {left}) leaves the {H}x{W} output")
+    if not (g["sx"] > 0 and g["sy"] > 0):
+        raise ValueError(f"frame {i}: tap scales must be positive")
 
 
 def validate_frames(geom, arena_bytes, H, W):
     """Host check of descriptor rows against an arena of `arena_bytes` and an H x W output: raises ValueError with the reason.  The
     kernel trusts the table — nothing reaches the device before this has passed."""
     for i, g in enumerate(geom):
-        off, h0, w0, pitch, ch, nh, nw, top, left = (int(g[k]) for k in ("offset", "h0", "w0", "pitch", "ch", "nh", "nw", "top", "left"))
-        if ch not in (1, 3):
-            raise ValueError(f"frame {i}: {ch} interleaved channels (1 or 3)")
-        if h0 < 1 or w0 < 1 or nh < 1 or nw < 1:
-            raise ValueError(f"frame {i}: empty frame or resized block ({h0}x{w0} -> {nh}x{nw})")
-        if pitch < w0 * ch:
-            raise ValueError(f"frame {i}: pitch {pitch} is less than a row of {w0} pixels x {ch} channels")
-        if off < 0 or off % 16:
-            raise ValueError(f"frame {i}: offset {off} must be a non-negative multiple of 16")
-        if off + h0 * pitch > arena_bytes:
-            raise ValueError(f"frame {i}: bytes [{off}, {off + h0 * pitch}) leave the arena of {arena_bytes} bytes")
-        if top < 0 or left < 0 or top + nh > H or left + nw > W:
-            raise ValueError(f"frame {i}: resized block {nh}x{nw} at ({top}, {left}) leaves the {H}x{W} output")
-        if not (g["sx"] > 0 and g["sy"] > 0):
-            raise ValueError(f"frame {i}: tap scales must be positive")
+        _validate_row(i, g, arena_bytes, H, W)
 
 
 def geom_tensor(geom, device=None, pin=False):
@@ -1246,10 +1287,7 @@ def frame_lists(rgb, ir):
     """Native frames as callers hand them over — per modality one uint8 (B, H0, W0, ch) tensor or a list of (H0_i, W0_i, ch) tensors, ch = 3
     or 1, a pair sharing its size — as (frames_rgb, frames_ir, shapes, uniform): the two lists of B frames, their (h0, w0), and per modality
     whether it came as one 4-D tensor.  Anything else raises ValueError; device, batch size and channel counts are the caller's to check."""
-    uniform = tuple(torch.is_tensor(t) and t.dim() == 4 for t in (rgb, ir))
-    fr = [[t[i] for i in range(t.shape[0])] if u else list(t) if isinstance(t, (list, tuple)) else None for t, u in zip((rgb, ir), uniform)]
-    if fr[0] is None or fr[1] is None or not fr[0] or len(fr[0]) != len(fr[1]):
-        raise ValueError("native frames come as two (B, H0, W0, ch) tensors or two equally long lists of (H0, W0, ch) tensors")
+    fr, uniform = _pair_lists((rgb, ir), (4, 4))
     for f in fr[0] + fr[1]:
         if not torch.is_tensor(f) or f.dtype != torch.uint8 or f.dim() != 3 or f.shape[2] not in (1, 3):
             raise ValueError("frames must be uint8 tensors of shape (H0, W0, ch), ch = 3 or 1")
@@ -1259,45 +1297,67 @@ def frame_lists(rgb, ir):
     return fr[0], fr[1], shapes, uniform
 
 
-def _frames_tensors(arena, dst, n, geom_dev, row_bytes):
-    """What every frame kernel asks of its tensors, for `n` descriptor rows of `row_bytes` each: returns dst's (B, ctot, H, W)."""
+def _pair_lists(mods, dims, what="(B, H0, W0, ch) tensors or two equally long lists of (H0, W0, ch) tensors"):
+    """The two modalities as handed over -> ([frames of modality 0, of modality 1], uniform): a tensor of dims[m] dimensions is a uniform
+    batch and split along its first axis, a list or tuple is taken frame by frame; both hold the same number of frames, one at least."""
+    uniform = tuple(torch.is_tensor(t) and t.dim() == d for t, d in zip(mods, dims))
+    fr = [[t[i] for i in range(t.shape[0])] if u else list(t) if isinstance(t, (list, tuple)) else None for t, u in zip(mods, uniform)]
+    if fr[0] is None or fr[1] is None or not fr[0] or len(fr[0]) != len(fr[1]):
+        raise ValueError(f"native frames come as two {what}")
+    return fr, uniform
+
+
+def _frames_checked(kind, arena, geom, geom_dev, dst, B=None, HW=None, window=None, mode=None, mode_dev=None):
+    """What every frame launch of a table `kind` asks before any device call, for its host rows `geom`: the tensors' layout, the tables'
+    sizes (window: the int32 window table of a 16-bit kind; mode / mode_dev: icaf_resize_frames' host rows and device table), the kind's
+    validator against the arena and the H x W output, the mode rows, and last that all live on the device.  The output is dst's
+    (B, ctot, H, W), or — for a launch without one — B and HW = (H, W).  Returns (n, B, ctot, H, W)."""
+    n = len(geom)
+    if kind.dtype != GEOM_DTYPE and geom.dtype != kind.dtype:
+        raise ValueError(f"the descriptor rows must be {kind.rows}_GEOM_DTYPE rows (pack_{kind.rows.lower()}_frames)")
+    if window is not None and (window.dtype != torch.int32 or not window.is_contiguous() or window.numel() < 2 * n):
+        raise ValueError(f"the window table must be a contiguous int32 tensor of {n} (lo, hi) rows")
     if arena.dtype != torch.uint8 or not arena.is_contiguous() or arena.dim() != 1:
         raise ValueError("the arena must be a flat contiguous uint8 tensor")
-    if dst.dtype != torch.uint8 or not dst.is_contiguous() or dst.dim() != 4:
-        raise ValueError("dst must be a contiguous uint8 (B, ctot, H, W) tensor")
-    B, ctot, H, W = dst.shape
-    if n % B or n == 0 or 3 * (n // B) > ctot:
-        raise ValueError(f"{n} descriptors for a batch of {B} images with {ctot} channels")
-    if W % 16:
-        raise ValueError(f"output width {W} must be a multiple of 16")
-    if geom_dev.numel() * geom_dev.element_size() < n * row_bytes:
+    ctot = None
+    if dst is not None:
+        if dst.dtype != torch.uint8 or not dst.is_contiguous() or dst.dim() != 4:
+            raise ValueError("dst must be a contiguous uint8 (B, ctot, H, W) tensor")
+        B, ctot, H, W = dst.shape
+        if W % 16:
+            raise ValueError(f"output width {W} must be a multiple of 16")
+    else:
+        H, W = HW
+    if n % B or n == 0 or (ctot is not None and 3 * (n // B) > ctot):
+        raise ValueError(f"{n} descriptors for a batch of {B} images" + (f" with {ctot} channels" if ctot is not None else ""))
+    if geom_dev.numel() * geom_dev.element_size() < n * kind.dtype.itemsize:
         raise ValueError("the device table is smaller than the descriptor rows")
-    return B, ctot, H, W
-
-
-def _frames_launch(fn, arena, geom, geom_dev, dst, swap_rb, name, mode=None, mode_dev=None):
-    """The Launch of a frame kernel (`fn`: the entry point's name; icaf_resize_frames takes the mode table behind the descriptors), everything
-    validated before any device call: the tensors' layout, the tables' sizes, validate_frames, the mode rows, and last that all live on the device."""
-    n = len(geom)
-    B, ctot, H, W = _frames_tensors(arena, dst, n, geom_dev, GEOM_DTYPE.itemsize)
     if (mode is None) != (mode_dev is None):
         raise ValueError("the mode table needs its host rows and its device copy, or neither (all rows mode 0)")
     if mode is not None:
         if len(mode) != n or mode_dev.dtype != torch.int32 or not mode_dev.is_contiguous() or mode_dev.numel() < n:
             raise ValueError(f"the mode table must hold one int32 per descriptor ({n}), host and device")
-    validate_frames(geom, arena.numel(), H, W)
+    kind.validate(geom, arena.numel(), H, W)
     for i in range(n if mode is not None else 0):
         md, g = int(mode[i]), geom[i]
         if md not in (0, 1):
             raise ValueError(f"frame {i}: mode {md} (0 = bilinear, 1 = area)")
         if md == 1 and (int(g["nh"]) > int(g["h0"]) or int(g["nw"]) > int(g["w0"])):
             raise ValueError(f"frame {i}: the area mode only shrinks ({int(g['h0'])}x{int(g['w0'])} -> {int(g['nh'])}x{int(g['nw'])})")
-    if not (arena.is_cuda and dst.is_cuda and geom_dev.is_cuda and (mode_dev is None or mode_dev.is_cuda)):
+    if not all(t.is_cuda for t in (arena, dst, geom_dev, window, mode_dev) if t is not None):
         raise ValueError("arena, tables and dst must be cuda tensors (no CPU fallback exists)")
-    nb = sum(int(g["h0"]) * int(g["w0"]) * int(g["ch"]) for g in geom) + n * 3 * H * W       # frames read once, planes written once
-    tables = (geom_dev.data_ptr(),) + ((mode_dev.data_ptr() if mode_dev is not None else None,) if fn == "icaf_resize_frames" else ())
+    return n, B, ctot, H, W
+
+
+def _frames_launch(fn, kind, arena, geom, geom_dev, dst, swap_rb, name, extra=(), **tables):
+    """The Launch of a frame kernel, everything checked before any device call (_frames_checked).  fn: the entry point's name; kind: the
+    record of its table; extra: the device table the entry point takes behind the descriptors — icaf_resize_frames' modes (None: all rows
+    mode 0), icaf_letterbox_y16_frames' windows; tables: the same as _frames_checked's window= or mode= / mode_dev=."""
+    n, B, ctot, H, W = _frames_checked(kind, arena, geom, geom_dev, dst, **tables)
+    nb = sum(kind.read(q) for q in geom) + n * 3 * H * W         # frames read once (at most, for a warped source), planes written once
+    tables = (geom_dev.data_ptr(),) + tuple(t.data_ptr() if t is not None else None for t in extra)
     return Launch(getattr(lib(), fn), (arena.data_ptr(),) + tables + (n // B, B, dst.data_ptr(), ctot, H, W, int(bool(swap_rb))),
-                  keep=(arena, geom_dev, mode_dev, dst), name=name, nbytes=nb)
+                  keep=(arena, geom_dev, dst) + tuple(extra), name=name, nbytes=nb)
 
 
 def letterbox_frames(arena, geom, geom_dev, dst, swap_rb=True, c0=0, name="letterbox_frames"):
@@ -1305,7 +1365,7 @@ def letterbox_frames(arena, geom, geom_dev, dst, swap_rb=True, c0=0, name="lette
     geom: the HOST descriptor rows (nstreams * B, entry modality * B + image) the device table `geom_dev` holds — or will hold by the
     time the launch runs, for a table refreshed per step (validate_frames each refresh) — validated here, before any device call;
     modality m fills channels [3m, 3m + 3)."""
-    return _frames_launch("icaf_letterbox_frames", arena, geom, geom_dev, dst, swap_rb, name)
+    return _frames_launch("icaf_letterbox_frames", KINDS["plain"], arena, geom, geom_dev, dst, swap_rb, name)
 
 
 # native YUV 4:2:0 frames: one row per (modality, image) in the layout of icaf_yuv_geom (include/icaf.h) — field "g" is a GEOM_DTYPE row
@@ -1331,26 +1391,21 @@ def pack_yuv_frames(geom, layouts, pitch=None, c_pitch=None, matrix=0, base=0):
     `c_pitch` bytes (default: ceil(w0 / 2) samples, tight) — one plane of CbCr / CrCb pairs, or the Cb and the Cr plane (i420) / Cr and
     Cb (yv12) one behind the other.  Frames start on FRAME_ALIGN boundaries from `base` on."""
     n = len(geom)
-    rows = np.zeros((n,), YUV_GEOM_DTYPE)
-    rows["g"] = geom if geom.dtype == GEOM_DTYPE else geom["g"]
-    per_row = lambda v: [v] * n if v is None or isinstance(v, (int, str)) else list(v)
+    rows = _table_rows(geom, YUV_GEOM_DTYPE)
     code = yuv_matrix_code(matrix)
     off = int(base)
-    for i, (q, lay, p, cp) in enumerate(zip(rows, per_row(layouts), per_row(pitch), per_row(c_pitch))):
+    for i, (q, lay, p, cp) in enumerate(zip(rows, _per_row(layouts, n), _per_row(pitch, n), _per_row(c_pitch, n))):
         g = q["g"]
-        off = -(-off // FRAME_ALIGN) * FRAME_ALIGN
         h0, w0 = int(g["h0"]), int(g["w0"])
         if lay in (1, 3):
-            g["offset"], g["ch"], g["pitch"] = off, lay, w0 * lay if p is None else int(p)
-            off += h0 * int(g["pitch"])
+            off = _place(g, off, lay, w0 * lay if p is None else p)
             continue
         if lay not in YUV_LAYOUTS:
             raise ValueError(f"frame {i}: unknown layout {lay!r} (3, 1 or one of {', '.join(YUV_LAYOUTS)})")
         step, cr_first = YUV_LAYOUTS[lay]
         chh, cw = (h0 + 1) // 2, (w0 + 1) // 2
-        g["offset"], g["ch"], g["pitch"] = off, 1, w0 if p is None else int(p)
+        first = _place(g, off, 1, w0 if p is None else p)
         q["kind"], q["matrix"], q["c_step"], q["c_pitch"] = 1, code, step, cw * step if cp is None else int(cp)
-        first = off + h0 * int(g["pitch"])
         second = first + 1 if step == 2 else first + chh * int(q["c_pitch"])
         q["cb_offset"], q["cr_offset"] = (second, first) if cr_first else (first, second)
         off = first + (1 if step == 2 else 2) * chh * int(q["c_pitch"])
@@ -1363,12 +1418,10 @@ def yuv_letterbox_staged(q):
     g = q["g"]
     if int(q["kind"]) == 0:
         return letterbox_staged(g)
-    sx, sy = np.float32(g["sx"]), np.float32(g["sy"])
-    if not (sx < 1024 and sy < 1024):
+    caps = _tap_caps(g)
+    if caps is None:
         return False
-    h0, w0, step = int(g["h0"]), int(g["w0"]), int(q["c_step"])
-    rows = min(h0, int(np.float32(32) * sy) + 4)
-    cols = min(w0, int(np.float32(64) * sx) + 4)
+    (rows, cols), h0, w0, step = caps, int(g["h0"]), int(g["w0"]), int(q["c_step"])
     crows, ccols = min((h0 + 1) // 2, rows // 2 + 1), min((w0 + 1) // 2, cols // 2 + 1)
     vectors = rows * ((cols + 30) >> 4) + (1 if step == 2 else 2) * crows * ((ccols * step + 30) >> 4)
     return vectors * 16 <= _lib.YUV_LDS_BYTES
@@ -1409,19 +1462,7 @@ def letterbox_yuv_frames(arena, geom, geom_dev, dst, swap_rb=True, name="letterb
     """letterbox_frames for tables with YUV 4:2:0 rows (icaf_letterbox_yuv_frames): kind-1 rows are converted at the bilinear taps and
     equal letterbox(yuv420_to_bgr(...)) byte for byte (planes R, G, B; swap_rb is not read for them), kind-0 rows are letterbox_frames'
     own.  geom: the HOST YUV_GEOM_DTYPE rows the device table `geom_dev` holds, validated here, before any device call."""
-    if geom.dtype != YUV_GEOM_DTYPE:
-        raise ValueError("the descriptor rows must be YUV_GEOM_DTYPE rows (pack_yuv_frames)")
-    n = len(geom)
-    B, ctot, H, W = _frames_tensors(arena, dst, n, geom_dev, YUV_GEOM_DTYPE.itemsize)
-    validate_yuv_frames(geom, arena.numel(), H, W)
-    if not (arena.is_cuda and dst.is_cuda and geom_dev.is_cuda):
-        raise ValueError("arena, table and dst must be cuda tensors (no CPU fallback exists)")
-    nb = n * 3 * H * W                                          # frames read once (luma and both chroma), planes written once
-    for q in geom:
-        h0, w0 = int(q["g"]["h0"]), int(q["g"]["w0"])
-        nb += h0 * w0 + 2 * ((h0 + 1) // 2) * ((w0 + 1) // 2) if int(q["kind"]) else h0 * w0 * int(q["g"]["ch"])
-    return Launch(lib().icaf_letterbox_yuv_frames, (arena.data_ptr(), geom_dev.data_ptr(), n // B, B, dst.data_ptr(), ctot, H, W, int(bool(swap_rb))),
-                  keep=(arena, geom_dev, dst), name=name, nbytes=nb)
+    return _frames_launch("icaf_letterbox_yuv_frames", KINDS["yuv"], arena, geom, geom_dev, dst, swap_rb, name)
 
 
 def yuv_frame_lists(rgb, ir, formats):
@@ -1433,10 +1474,7 @@ def yuv_frame_lists(rgb, ir, formats):
     if len(formats) != 2 or any(f is not None and f not in YUV_LAYOUTS for f in formats):
         raise ValueError(f"formats=(fmt_rgb, fmt_ir), each None or one of {', '.join(YUV_LAYOUTS)}, got {formats!r}")
     nd = [3 if f else 4 for f in formats]
-    uniform = tuple(torch.is_tensor(t) and t.dim() == d for t, d in zip((rgb, ir), nd))
-    fr = [[t[i] for i in range(t.shape[0])] if u else list(t) if isinstance(t, (list, tuple)) else None for t, u in zip((rgb, ir), uniform)]
-    if fr[0] is None or fr[1] is None or not fr[0] or len(fr[0]) != len(fr[1]):
-        raise ValueError("native frames come as two batch tensors or two equally long lists of frames")
+    fr, uniform = _pair_lists((rgb, ir), nd, "batch tensors or two equally long lists of frames")
     shapes = [None, None]
     for m, fmt in enumerate(formats):
         for f in fr[m]:
@@ -1496,23 +1534,18 @@ def pack_warp_frames(geom, sources, matrices=None, borders=0, pitch=None, base=0
     aligned -> source matrix of a kind-1 row, None for kind 0; borders: 0..255 per row or one for all; pitch: bytes per source row (default
     tight).  Frames start on FRAME_ALIGN boundaries from `base` on."""
     n = len(geom)
-    rows = np.zeros((n,), WARP_GEOM_DTYPE)
-    rows["g"] = geom if geom.dtype == GEOM_DTYPE else geom["g"]
-    srcs = [sources] * n if isinstance(sources, int) or (isinstance(sources, tuple) and len(sources) == 3 and isinstance(sources[0], int)) else list(sources)
-    mats = [None] * n if matrices is None else [matrices] * n if getattr(matrices, "shape", None) == (3, 3) else list(matrices)
-    bords = [borders] * n if isinstance(borders, int) else list(borders)
-    pitches = [pitch] * n if pitch is None or isinstance(pitch, int) else list(pitch)
+    rows = _table_rows(geom, WARP_GEOM_DTYPE)
+    srcs = _per_row(sources, n, lambda s: isinstance(s, tuple) and len(s) == 3 and isinstance(s[0], int))
+    mats, bords, pitches = _per_row(matrices, n, lambda m: getattr(m, "shape", None) == (3, 3)), _per_row(borders, n), _per_row(pitch, n)
     if not (len(srcs) == len(mats) == len(bords) == len(pitches) == n):
         raise ValueError(f"{n} rows need {n} sources, matrices, borders and pitches (or one for all)")
     off = int(base)
     for i, (q, src, mat, bd, p) in enumerate(zip(rows, srcs, mats, bords, pitches)):
         g = q["g"]
-        off = -(-off // FRAME_ALIGN) * FRAME_ALIGN
         if isinstance(src, (int, np.integer)):
             if mat is not None:
                 raise ValueError(f"frame {i}: a matrix needs a (hs, ws, ch) source; {src} alone describes an unwarped frame")
-            g["offset"], g["ch"], g["pitch"] = off, int(src), int(g["w0"]) * int(src) if p is None else int(p)
-            off += int(g["h0"]) * int(g["pitch"])
+            off = _place(g, off, src, int(g["w0"]) * int(src) if p is None else p)
             continue
         if len(src) != 3:
             raise ValueError(f"frame {i}: a source is 3, 1 or (hs, ws, ch), got {src!r}")
@@ -1523,8 +1556,7 @@ def pack_warp_frames(geom, sources, matrices=None, borders=0, pitch=None, base=0
         if m.shape != (3, 3):
             raise ValueError(f"frame {i}: an alignment matrix is 3 x 3, got shape {m.shape}")
         q["kind"], q["hs"], q["ws"], q["border"], q["m"] = 1, hs, ws, int(bd), m.reshape(9)
-        g["offset"], g["ch"], g["pitch"] = off, ch, ws * ch if p is None else int(p)
-        off += hs * int(g["pitch"])
+        off = _place(g, off, ch, ws * ch if p is None else p, nrows=hs)
     return rows, off
 
 
@@ -1537,31 +1569,11 @@ def validate_warp_frames(geom, arena_bytes, H, W):
         kind = int(q["kind"])
         if kind not in (0, 1):
             raise ValueError(f"frame {i}: kind {kind} (0 = plain row, 1 = warped)")
-        g = q["g"]
         if kind == 0:
-            try:
-                validate_frames(geom["g"][i:i + 1], arena_bytes, H, W)
-            except ValueError as e:
-                raise ValueError(f"frame {i}:" + str(e).split(":", 1)[1]) from None
+            _validate_row(i, q["g"], arena_bytes, H, W)
             continue
-        off, h0, w0, pitch, ch, nh, nw, top, left = (int(g[k]) for k in ("offset", "h0", "w0", "pitch", "ch", "nh", "nw", "top", "left"))
-        hs, ws, border = int(q["hs"]), int(q["ws"]), int(q["border"])
-        if ch not in (1, 3):
-            raise ValueError(f"frame {i}: {ch} interleaved channels (1 or 3)")
-        if hs < 1 or ws < 1:
-            raise ValueError(f"frame {i}: empty source frame ({hs}x{ws})")
-        if h0 < 1 or w0 < 1 or nh < 1 or nw < 1:
-            raise ValueError(f"frame {i}: empty aligned frame or resized block ({h0}x{w0} -> {nh}x{nw})")
-        if pitch < ws * ch:
-            raise ValueError(f"frame {i}: pitch {pitch} is less than a source row of {ws} pixels x {ch} channels")
-        if off < 0 or off % 16:
-            raise ValueError(f"frame {i}: offset {off} must be a non-negative multiple of 16")
-        if off + hs * pitch > arena_bytes:
-            raise ValueError(f"frame {i}: bytes [{off}, {off + hs * pitch}) leave the arena of {arena_bytes} bytes")
-        if top < 0 or left < 0 or top + nh > H or left + nw > W:
-            raise ValueError(f"frame {i}: resized block {nh}x{nw} at ({top}, {left}) leaves the {H}x{W} output")
-        if not (g["sx"] > 0 and g["sy"] > 0):
-            raise ValueError(f"frame {i}: tap scales must be positive")
+        _validate_row(i, q["g"], arena_bytes, H, W, src=(int(q["hs"]), int(q["ws"])))
+        border = int(q["border"])
         if not 0 <= border <= 255:
             raise ValueError(f"frame {i}: border {border} outside 0..255")
         if not np.isfinite(q["m"]).all():
@@ -1610,27 +1622,11 @@ def letterbox_warp_frames(arena, geom, geom_dev, dst, swap_rb=True, name="letter
     bilinear taps and equal letterbox(utils.datasets.warp_perspective(...)) byte for byte, kind-0 rows are letterbox_frames' own.  geom:
     the HOST WARP_GEOM_DTYPE rows the device table `geom_dev` holds — or will hold by the time the launch runs, for a table refreshed per
     step (validate_warp_frames each refresh) — validated here, before any device call."""
-    if geom.dtype != WARP_GEOM_DTYPE:
-        raise ValueError("the descriptor rows must be WARP_GEOM_DTYPE rows (pack_warp_frames)")
-    n = len(geom)
-    B, ctot, H, W = _frames_tensors(arena, dst, n, geom_dev, WARP_GEOM_DTYPE.itemsize)
-    validate_warp_frames(geom, arena.numel(), H, W)
-    if not (arena.is_cuda and dst.is_cuda and geom_dev.is_cuda):
-        raise ValueError("arena, table and dst must be cuda tensors (no CPU fallback exists)")
-    nb = n * 3 * H * W                                          # at most: source frames read once, planes written once
-    for q in geom:
-        g = q["g"]
-        nb += (int(q["hs"]) * int(q["ws"]) if int(q["kind"]) else int(g["h0"]) * int(g["w0"])) * int(g["ch"])
-    return Launch(lib().icaf_letterbox_warp_frames, (arena.data_ptr(), geom_dev.data_ptr(), n // B, B, dst.data_ptr(), ctot, H, W, int(bool(swap_rb))),
-                  keep=(arena, geom_dev, dst), name=name, nbytes=nb)
+    return _frames_launch("icaf_letterbox_warp_frames", KINDS["align"], arena, geom, geom_dev, dst, swap_rb, name)
 
 
-def warp_frame_lists(rgb, ir, align):
-    """frame_lists for a calibrated pair: align = (A_rgb, A_ir), exactly one of them not None — that modality is seen through its
-    alignment (alignment_matrices: a (3, 3) or (B, 3, 3) aligned -> source matrix, or "stretch") and may have any size per frame; the
-    OTHER modality's frame sizes are the aligned sizes.  Returns (frames_rgb, frames_ir, shapes, uniform, m, src_shapes, matrices): the two
-    lists of B frames, the aligned (h0, w0), per modality whether it came as one 4-D tensor, the aligned modality's index, its frames'
-    (hs, ws) and the float32 (B, 3, 3) matrices.  Anything else raises ValueError."""
+def _aligned_modality(align):
+    """align=(A_rgb, A_ir) -> (index of the one modality that carries an alignment, that alignment); ValueError for any other form."""
     try:
         a_rgb, a_ir = align
     except (TypeError, ValueError):
@@ -1639,17 +1635,23 @@ def warp_frame_lists(rgb, ir, align):
         raise ValueError("align=(A_rgb, A_ir): both modalities carry an alignment; one of them defines the aligned space and stays None")
     if a_rgb is None and a_ir is None:
         raise ValueError("align=(A_rgb, A_ir): neither modality carries an alignment (plain pairs: leave align=None)")
-    m = 0 if a_rgb is not None else 1
-    uniform = tuple(torch.is_tensor(t) and t.dim() == 4 for t in (rgb, ir))
-    fr = [[t[i] for i in range(t.shape[0])] if u else list(t) if isinstance(t, (list, tuple)) else None for t, u in zip((rgb, ir), uniform)]
-    if fr[0] is None or fr[1] is None or not fr[0] or len(fr[0]) != len(fr[1]):
-        raise ValueError("native frames come as two (B, H0, W0, ch) tensors or two equally long lists of (H0, W0, ch) tensors")
+    return (0, a_rgb) if a_rgb is not None else (1, a_ir)
+
+
+def warp_frame_lists(rgb, ir, align):
+    """frame_lists for a calibrated pair: align = (A_rgb, A_ir), exactly one of them not None — that modality is seen through its
+    alignment (alignment_matrices: a (3, 3) or (B, 3, 3) aligned -> source matrix, or "stretch") and may have any size per frame; the
+    OTHER modality's frame sizes are the aligned sizes.  Returns (frames_rgb, frames_ir, shapes, uniform, m, src_shapes, matrices): the two
+    lists of B frames, the aligned (h0, w0), per modality whether it came as one 4-D tensor, the aligned modality's index, its frames'
+    (hs, ws) and the float32 (B, 3, 3) matrices.  Anything else raises ValueError."""
+    m, a = _aligned_modality(align)
+    fr, uniform = _pair_lists((rgb, ir), (4, 4))
     for f in fr[0] + fr[1]:
         if not torch.is_tensor(f) or f.dtype != torch.uint8 or f.dim() != 3 or f.shape[2] not in (1, 3) or f.shape[0] < 1 or f.shape[1] < 1:
             raise ValueError("frames must be uint8 tensors of shape (H0, W0, ch), ch = 3 or 1")
     shapes = [tuple(int(v) for v in f.shape[:2]) for f in fr[1 - m]]
     src_shapes = [tuple(int(v) for v in f.shape[:2]) for f in fr[m]]
-    return fr[0], fr[1], shapes, uniform, m, src_shapes, alignment_matrices(a_rgb if m == 0 else a_ir, src_shapes, shapes)
+    return fr[0], fr[1], shapes, uniform, m, src_shapes, alignment_matrices(a, src_shapes, shapes)
 
 
 # 16-bit thermal frames: one row per (modality, image) in the layout of icaf_y16_geom (include/icaf.h) — field "g" is a GEOM_DTYPE row
@@ -1693,25 +1695,21 @@ def pack_y16_frames(geom, layouts, pitch=None, clip=None, window=None, base=0):
     with a window is a mode-0 row.  Frames start on FRAME_ALIGN boundaries from `base` on."""
     from .utils.datasets import AGC_CLIP, agc_clip
     n = len(geom)
-    rows = np.zeros((n,), Y16_GEOM_DTYPE)
-    rows["g"] = geom if geom.dtype == GEOM_DTYPE else geom["g"]
-    per_row = lambda v: [v] * n if v is None or isinstance(v, (int, str)) else list(v)
+    rows = _table_rows(geom, Y16_GEOM_DTYPE)
     clip_lo, clip_hi = agc_clip(AGC_CLIP if clip is None else clip)
     off = int(base)
-    for i, (q, lay, p, win) in enumerate(zip(rows, per_row(layouts), per_row(pitch), _y16_windows(window, n))):
+    for i, (q, lay, p, win) in enumerate(zip(rows, _per_row(layouts, n), _per_row(pitch, n), _y16_windows(window, n))):
         g = q["g"]
-        off = -(-off // FRAME_ALIGN) * FRAME_ALIGN
-        h0, w0 = int(g["h0"]), int(g["w0"])
+        w0 = int(g["w0"])
         if lay in (1, 3):
-            g["offset"], g["ch"], g["pitch"] = off, lay, w0 * lay if p is None else int(p)
+            off = _place(g, off, lay, w0 * lay if p is None else p)
         elif lay == "y16":
-            g["offset"], g["ch"], g["pitch"] = off, 1, 2 * w0 if p is None else int(p)
+            off = _place(g, off, 1, 2 * w0 if p is None else p)
             q["kind"], q["mode"], q["clip_lo"], q["clip_hi"] = 1, 1 if win is None else 0, clip_lo, clip_hi
             if win is not None:
                 q["lo"], q["hi"] = win
         else:
             raise ValueError(f"frame {i}: unknown layout {lay!r} (3, 1 or 'y16')")
-        off += h0 * int(g["pitch"])
     return rows, off
 
 
@@ -1722,12 +1720,7 @@ def y16_letterbox_staged(q):
     g = q["g"]
     if int(q["kind"]) == 0:
         return letterbox_staged(g)
-    sx, sy = np.float32(g["sx"]), np.float32(g["sy"])
-    if not (sx < 1024 and sy < 1024):
-        return False
-    rows = min(int(g["h0"]), int(np.float32(32) * sy) + 4)
-    cols = min(int(g["w0"]), int(np.float32(64) * sx) + 4)
-    return rows * ((cols + 30) >> 4) * 16 <= _lib.Y16_LDS_BYTES
+    return _rect_staged(g, 1, _lib.Y16_LDS_BYTES)
 
 
 def validate_y16_frames(geom, arena_bytes, H, W):
@@ -1756,27 +1749,12 @@ def validate_y16_frames(geom, arena_bytes, H, W):
             raise ValueError(f"frame {i}: window ({lo}, {hi}) must satisfy 0 <= lo <= hi <= 65535")
 
 
-def _y16_tables(arena, geom, geom_dev, window_dev, n):
-    if geom.dtype != Y16_GEOM_DTYPE:
-        raise ValueError("the descriptor rows must be Y16_GEOM_DTYPE rows (pack_y16_frames)")
-    if window_dev.dtype != torch.int32 or not window_dev.is_contiguous() or window_dev.numel() < 2 * n:
-        raise ValueError(f"the window table must be a contiguous int32 tensor of {n} (lo, hi) rows")
-
-
 def y16_window(arena, geom, geom_dev, window_dev, B, H, W, name="y16_window"):
     """The gain-control windows of a table's 16-bit thermal rows (icaf_y16_window): window_dev, int32 (n, 2) on the device, takes (lo, hi)
     of every kind-1 row — utils.datasets.agc_window of the frame for a mode-1 row, the row's own pair for a mode-0 row; rows of kind 0
     keep what they hold.  geom: the HOST rows the device table `geom_dev` holds, validated here (against an H x W output) before any
     device call; B: images per modality.  Nothing is read back."""
-    n = len(geom)
-    _y16_tables(arena, geom, geom_dev, window_dev, n)
-    if arena.dtype != torch.uint8 or not arena.is_contiguous() or arena.dim() != 1:
-        raise ValueError("the arena must be a flat contiguous uint8 tensor")
-    if n == 0 or n % B or geom_dev.numel() * geom_dev.element_size() < n * Y16_GEOM_DTYPE.itemsize:
-        raise ValueError(f"{n} descriptors for a batch of {B} images, or a device table smaller than the rows")
-    validate_y16_frames(geom, arena.numel(), H, W)
-    if not (arena.is_cuda and geom_dev.is_cuda and window_dev.is_cuda):
-        raise ValueError("arena and tables must be cuda tensors (no CPU fallback exists)")
+    n = _frames_checked(KINDS["y16"], arena, geom, geom_dev, None, B=B, HW=(H, W), window=window_dev)[0]
     nb = sum(2 * 2 * int(q["g"]["h0"]) * int(q["g"]["w0"]) for q in geom if int(q["kind"]) and int(q["mode"]))       # two passes over a frame
     return Launch(lib().icaf_y16_window, (arena.data_ptr(), geom_dev.data_ptr(), n // B, B, window_dev.data_ptr()),
                   keep=(arena, geom_dev, window_dev), name=name, nbytes=nb)
@@ -1787,15 +1765,7 @@ def letterbox_y16_frames(arena, geom, geom_dev, window_dev, dst, swap_rb=True, n
     taps with their row of `window_dev` (y16_window fills it; it runs first) and equal letterbox(agc_u16_to_u8(frame, lo, hi)) byte for
     byte in all three planes, kind-0 rows are letterbox_frames' own.  geom: the HOST Y16_GEOM_DTYPE rows the device table `geom_dev`
     holds, validated here, before any device call."""
-    n = len(geom)
-    _y16_tables(arena, geom, geom_dev, window_dev, n)
-    B, ctot, H, W = _frames_tensors(arena, dst, n, geom_dev, Y16_GEOM_DTYPE.itemsize)
-    validate_y16_frames(geom, arena.numel(), H, W)
-    if not (arena.is_cuda and dst.is_cuda and geom_dev.is_cuda and window_dev.is_cuda):
-        raise ValueError("arena, tables and dst must be cuda tensors (no CPU fallback exists)")
-    nb = n * 3 * H * W + sum(int(q["g"]["h0"]) * int(q["g"]["w0"]) * (2 if int(q["kind"]) else int(q["g"]["ch"])) for q in geom)
-    return Launch(lib().icaf_letterbox_y16_frames, (arena.data_ptr(), geom_dev.data_ptr(), window_dev.data_ptr(), n // B, B, dst.data_ptr(), ctot, H, W,
-                                                    int(bool(swap_rb))), keep=(arena, geom_dev, window_dev, dst), name=name, nbytes=nb)
+    return _frames_launch("icaf_letterbox_y16_frames", KINDS["y16"], arena, geom, geom_dev, dst, swap_rb, name, extra=(window_dev,), window=window_dev)
 
 
 def y16_bytes(t):
@@ -1818,10 +1788,7 @@ def y16_frame_lists(rgb, ir, formats):
         raise ValueError(f"formats=(fmt_rgb, fmt_ir), each None or 'y16', got {formats!r}")
     mods = [y16_bytes(t) if f else t for t, f in zip((rgb, ir), formats)]
     nd = [3 if f else 4 for f in formats]
-    uniform = tuple(torch.is_tensor(t) and t.dim() == d for t, d in zip(mods, nd))
-    fr = [[t[i] for i in range(t.shape[0])] if u else list(t) if isinstance(t, (list, tuple)) else None for t, u in zip(mods, uniform)]
-    if fr[0] is None or fr[1] is None or not fr[0] or len(fr[0]) != len(fr[1]):
-        raise ValueError("native frames come as two batch tensors or two equally long lists of frames")
+    fr, uniform = _pair_lists(mods, nd, "batch tensors or two equally long lists of frames")
     shapes = []
     for m, fmt in enumerate(formats):
         for f in fr[m]:
@@ -1883,7 +1850,133 @@ def resize_frames(arena, geom, mode_dev, geom_dev, dst, swap_rb=True, mode=None,
     """letterbox_frames with a resize mode per descriptor (icaf_resize_frames): mode 0 rows are letterbox_frames' bilinear resize, mode 1
     rows the pixel-area average of utils.datasets.resize_area_scalar, byte for byte.  mode: the HOST int rows the device table `mode_dev`
     (int32) holds; both None = every row mode 0.  Validated here, before any device call: validate_frames, and nh <= h0, nw <= w0 for mode 1."""
-    return _frames_launch("icaf_resize_frames", arena, geom, geom_dev, dst, swap_rb, name, mode, mode_dev)
+    return _frames_launch("icaf_resize_frames", KINDS["plain"], arena, geom, geom_dev, dst, swap_rb, name, extra=(mode_dev,), mode=mode, mode_dev=mode_dev)
+
+
+# One record per kind of table — what Model.forward_frames and DetectionPipeline ask of it:
+#   name      "plain" | "yuv" | "align" | "y16" (part of forward_frames' state key)
+#   rows      the kind's prefix of its *_GEOM_DTYPE / pack_*_frames names ("" for plain), noun: what its frames are called in a refusal
+#   dtype     the row dtype (frame_rows gives the embedded icaf_frame_geom rows of any of them)
+#   lists     (rgb, ir, formats, align) -> (frames_rgb, frames_ir, shapes, uniform, aligned modality, its source shapes, its matrices)
+#   pack      (geom, specs, base, matrix=, clip=, border=) -> (rows, end); specs: one entry per row, see frame_specs
+#   validate  (rows, arena_bytes, H, W)
+#   read      row -> bytes of its frame (frame_bytes states the same for a maximum size, before any row exists)
+#   window    True: the kind's step writes an int32 (n, 2) window table that its letterbox reads
+#   launches  (arena, rows, rows_dev, dst, swap_rb, B, window=, mode=, mode_dev=) -> the Launches of a step, in order; swap_rb is the
+#             last argument of the last
+#   update    None, or (rows, B, formats, aligned modality, mats=, border=, clip=, wins=): the row fields rewritten per call / per submit
+FrameKind = collections.namedtuple("FrameKind", "name rows noun dtype lists pack validate read window launches update")
+
+
+def _update_warp(rows, B, formats, m, mats=None, border=None, **_):
+    """This call's matrices (float32 (B, 3, 3)) and border into the aligned modality's rows; None leaves the field."""
+    if mats is not None:
+        rows["m"][m * B:(m + 1) * B] = mats.reshape(B, 9)
+    if border is not None:
+        rows["border"][m * B:(m + 1) * B] = int(border)
+
+
+def _update_y16(rows, B, formats, m, clip=None, wins=None, **_):
+    """This call's gain control into the rows of the Y16 modalities: wins, None or B entries (_y16_windows), gives a frame its window
+    (mode 0) or None (mode 1, the percentile window of clip_lo / clip_hi); clip=None leaves the clip."""
+    from .utils.datasets import agc_clip
+    for mod, fmt in enumerate(formats):
+        if fmt != "y16":
+            continue
+        sl = slice(mod * B, (mod + 1) * B)
+        if clip is not None:
+            rows["clip_lo"][sl], rows["clip_hi"][sl] = agc_clip(clip)
+        win = [None] * B if wins is None else wins
+        rows["mode"][sl] = [w is None for w in win]
+        rows["lo"][sl], rows["hi"][sl] = [0 if w is None else w[0] for w in win], [0 if w is None else w[1] for w in win]
+
+
+def _y16_launches(arena, rows, rows_dev, dst, swap_rb, B, window=None, **_):
+    H, W = dst.shape[2:]
+    return [y16_window(arena, rows, rows_dev, window, B, H, W), letterbox_y16_frames(arena, rows, rows_dev, window, dst, swap_rb)]
+
+
+def _yuv_read(q):
+    h0, w0 = int(q["g"]["h0"]), int(q["g"]["w0"])
+    return h0 * w0 + 2 * ((h0 + 1) // 2) * ((w0 + 1) // 2) if int(q["kind"]) else h0 * w0 * int(q["g"]["ch"])
+
+
+KINDS = {k.name: k for k in (
+    FrameKind("plain", "", "uint8 frames", GEOM_DTYPE, lambda rgb, ir, formats, align: frame_lists(rgb, ir) + (None, None, None),
+              lambda geom, specs, base=0, **_: (geom, pack_frames(geom, specs, base=base)), validate_frames,
+              lambda g: int(g["h0"]) * int(g["w0"]) * int(g["ch"]), False,
+              lambda arena, rows, rows_dev, dst, swap_rb, B, mode=None, mode_dev=None, **_:
+              [letterbox_frames(arena, rows, rows_dev, dst, swap_rb) if mode is None else resize_frames(arena, rows, mode_dev, rows_dev, dst, swap_rb, mode)], None),
+    FrameKind("yuv", "YUV", "uint8 frames", YUV_GEOM_DTYPE, lambda rgb, ir, formats, align: yuv_frame_lists(rgb, ir, formats) + (None, None, None),
+              lambda geom, specs, base=0, matrix=0, **_: pack_yuv_frames(geom, specs, matrix=matrix, base=base), validate_yuv_frames, _yuv_read, False,
+              lambda arena, rows, rows_dev, dst, swap_rb, B, **_: [letterbox_yuv_frames(arena, rows, rows_dev, dst, swap_rb)], None),
+    FrameKind("align", "WARP", "uint8 frames", WARP_GEOM_DTYPE, lambda rgb, ir, formats, align: warp_frame_lists(rgb, ir, align),
+              lambda geom, specs, base=0, border=0, **_:
+              pack_warp_frames(geom, list(specs), [np.eye(3, dtype=np.float32) if isinstance(s, tuple) else None for s in specs], border, base=base),
+              validate_warp_frames, lambda q: (int(q["hs"]) * int(q["ws"]) if int(q["kind"]) else int(q["g"]["h0"]) * int(q["g"]["w0"])) * int(q["g"]["ch"]),
+              False, lambda arena, rows, rows_dev, dst, swap_rb, B, **_: [letterbox_warp_frames(arena, rows, rows_dev, dst, swap_rb)], _update_warp),
+    FrameKind("y16", "Y16", "frames", Y16_GEOM_DTYPE, lambda rgb, ir, formats, align: y16_frame_lists(rgb, ir, formats) + (None, None, None),
+              lambda geom, specs, base=0, clip=None, **_: pack_y16_frames(geom, specs, clip=clip, base=base), validate_y16_frames,
+              lambda q: int(q["g"]["h0"]) * int(q["g"]["w0"]) * (2 if int(q["kind"]) else int(q["g"]["ch"])), True, _y16_launches, _update_y16))}
+
+
+def frame_kind(formats, align, val_size=None, who="forward_frames: ", align_arg="align=", formats_arg="formats"):
+    """The record of the table kind that serves formats=(fmt_rgb, fmt_ir) (None, or each None, "y16" or a YUV 4:2:0 layout) and align
+    (None, or (A_rgb, A_ir) with exactly one entry not None).  The ONE place that refuses what cannot be combined yet: a table holds
+    one kind of row, and only plain tables have the validation geometry (val_size).  who / align_arg / formats_arg: how the caller's
+    arguments are called in the refusal."""
+    formats = tuple(formats) if formats is not None else (None, None)
+    y16, yuv = "y16" in formats, any(f is not None and f != "y16" for f in formats)
+    if y16 and yuv:
+        raise ValueError("a 16-bit thermal modality ('y16') beside a YUV 4:2:0 modality is not supported yet: one table holds one kind of row")
+    if y16 and val_size is not None:
+        raise ValueError(f"{who}16-bit thermal frames ('y16') have no validation geometry (val_size); the validation sets are 8-bit")
+    if y16 and align is not None:
+        raise ValueError(f"{who}{align_arg} takes interleaved 8-bit frames; a 16-bit thermal modality ('y16') cannot be combined with it yet")
+    if align is not None and val_size is not None:
+        raise ValueError(f"{who}{align_arg} has no validation geometry (val_size); validation sets are registered offline")
+    if align is not None and yuv:
+        raise ValueError(f"{who}{align_arg} takes interleaved frames; a YUV 4:2:0 modality ({formats_arg}) cannot be combined with it yet")
+    if align is not None:
+        _aligned_modality(align)
+    if yuv and val_size is not None:
+        raise ValueError(f"{who}YUV 4:2:0 frames have no validation geometry (val_size); the area down-scale reads interleaved frames")
+    return KINDS["y16" if y16 else "align" if align is not None else "yuv" if yuv else "plain"]
+
+
+def frame_specs(formats, frames, aligned=None):
+    """What a pack function takes per row, for the frame lists of the two modalities: the format's name ("y16", "nv12", ...), the source's
+    (hs, ws, ch) for a frame of the aligned modality, else the interleaved channels."""
+    return tuple(fmt if fmt is not None else tuple(int(v) for v in f.shape) if m == aligned else int(f.shape[2])
+                 for m, (fmt, fs) in enumerate(zip(formats, frames)) for f in fs)
+
+
+def frame_bytes(spec, h0, w0):
+    """Bytes of the arena one frame of `spec` (frame_specs) occupies when it is h0 x w0 (an aligned modality's source: its own hs x ws):
+    2 a pixel for "y16", 1.5 for YUV 4:2:0 (luma + the chroma of sizes rounded up), else the interleaved channels."""
+    if isinstance(spec, tuple):
+        return spec[0] * spec[1] * spec[2]
+    if spec == "y16":
+        return 2 * h0 * w0
+    if spec in YUV_LAYOUTS:
+        return h0 * w0 + 2 * ((h0 + 1) // 2) * ((w0 + 1) // 2)
+    return h0 * w0 * int(spec)
+
+
+def layout_modality(rows, end, base, cap, contiguous, m=0):
+    """The arena layout of ONE modality's rows as a pack function laid them out from `base` on (`end`: the first free byte behind them), in
+    place: a uniform batch that arrives as one contiguous tensor (`contiguous`) keeps its layout — frame b at base + b frame sizes, so
+    ONE copy moves the batch — the chroma offsets of YUV rows moving with their frame; other frames stay on their FRAME_ALIGN starts and
+    must fit the modality's `cap` bytes (ValueError).  Returns rows."""
+    g, B = frame_rows(rows), len(rows)
+    if contiguous:
+        at = base + (end - int(g[B - 1]["offset"])) * np.arange(B)           # (end - last offset: the bytes of one frame, chroma included)
+        for k in ("cb_offset", "cr_offset") if "cb_offset" in (rows.dtype.names or ()) else ():
+            rows[k] += (rows["kind"] != 0) * (at - g["offset"])
+        g["offset"] = at
+    elif end - base > cap:
+        raise ValueError(f"the frames of modality {m} need {end - base} bytes of the arena's {cap}")
+    return rows
 
 
 def scale_detections(det, count, scale, out=None, round=False, name="scale_detections"):

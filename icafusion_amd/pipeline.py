@@ -72,11 +72,10 @@ class DetectionPipeline:
         u8=True: the plans take the dataloader's uint8 (B, 6, H, W) RGB+IR batch (Model.forward_u8: `/255`, split and cast in the
         staging kernel, reference test.py:116-123) — `submit_u8` then feeds them from (pinned) host memory with the H2D copy on its own
         stream, overlapped with the forwards in flight."""
-        if "y16" in tuple(frame_formats):                                        # refused before anything is built
-            if any(f in ops.YUV_LAYOUTS for f in frame_formats):
-                raise ValueError("a 16-bit thermal modality ('y16') beside a YUV 4:2:0 modality is not supported yet: one table holds one kind of row")
-            if any(frame_align):
-                raise ValueError("frame_align takes interleaved 8-bit frames; a 16-bit thermal modality ('y16') cannot be combined with it yet")
+        # the kind of table the frames need (ops.KINDS): what cannot be combined is refused here, before anything is built
+        kind = ops.frame_kind(frame_formats, tuple(a or None for a in frame_align) if any(frame_align) else None, who="", align_arg="frame_align",
+                              formats_arg="frame_formats")
+        if kind.window:
             agc_clip_checked(agc_clip)
         self.model, self.device, self.world = model, torch.device(device), world
         self.u8, self.augment = bool(u8) or frames is not None, bool(augment)
@@ -150,13 +149,13 @@ class DetectionPipeline:
         if frames is None and (any(frame_align) or align_frames is not None):
             raise ValueError("frame_align / align_frames describe native frames: pass frames=(max_h0, max_w0) with them")
         if frames is not None:
-            self._init_frames(batch, height, width, frames, frame_channels, frames_bgr, round_boxes, frame_formats, yuv_matrix,
+            self._init_frames(kind, batch, height, width, frames, frame_channels, frames_bgr, round_boxes, frame_formats, yuv_matrix,
                               frame_align, align_frames, align_border, agc_clip)
 
-    def _init_frames(self, B, H, W, frames, chans, bgr, round_boxes, formats=(None, None), yuv_matrix="bt601", frame_align=(None, None),
+    def _init_frames(self, kind, B, H, W, frames, chans, bgr, round_boxes, formats=(None, None), yuv_matrix="bt601", frame_align=(None, None),
                      align_frames=None, align_border=0, agc_clip=(100, 100)):
         """Per plan: a byte arena (RGB frames in its first half, IR frames in its second) and ONE table allocation — 2B descriptor rows
-        for the letterbox, then B scale_coords rows for scale_detections — with a pinned host twin it is copied from."""
+        of `kind` (ops.KINDS) for the letterbox, then B scale_coords rows for scale_detections — with a pinned host twin it is copied from."""
         max_h0, max_w0 = int(frames[0]), int(frames[1])
         chans = tuple(int(c) for c in chans)
         if max_h0 < 1 or max_w0 < 1 or len(chans) != 2 or any(c not in (1, 3) for c in chans):
@@ -164,48 +163,26 @@ class DetectionPipeline:
         formats = tuple(formats)
         if len(formats) != 2 or any(f is not None and f != "y16" and f not in ops.YUV_LAYOUTS for f in formats):
             raise ValueError(f"frame_formats=(fmt_rgb, fmt_ir), each None, 'y16' or one of {', '.join(ops.YUV_LAYOUTS)}, got {formats!r}")
-        y16 = "y16" in formats                                                   # then the table holds icaf_y16_geom rows (__init__ checked its company)
-        yuv = any(formats) and not y16                                           # then the table holds icaf_yuv_geom rows
-        frame_align = tuple(bool(a) for a in frame_align)
-        if len(frame_align) != 2 or all(frame_align):
-            raise ValueError("frame_align=(None, True) or (True, None): one modality is aligned, the other defines the aligned space")
-        warp = frame_align.index(True) if any(frame_align) else None            # then the table holds icaf_warp_geom rows
+        warp = [bool(a) for a in frame_align].index(True) if any(frame_align) else None      # the aligned modality of a calibrated rig
         if (warp is None) != (align_frames is None):
             raise ValueError("frame_align marks the aligned modality and align_frames=(max_hs, max_ws) sizes its frames: pass both or neither")
-        if warp is not None and yuv:
-            raise ValueError("frame_align takes interleaved frames; a YUV 4:2:0 modality (frame_formats) cannot be combined with it yet")
         smax, border = (max_h0, max_w0), int(align_border)
         if warp is not None:
             smax = (int(align_frames[0]), int(align_frames[1]))
             if min(smax) < 1 or not 0 <= border <= 255:
                 raise ValueError(f"align_frames=(max_hs, max_ws) and align_border in 0..255, got {align_frames} / {align_border}")
         A = ops.FRAME_ALIGN
-        # bytes per modality: interleaved frames of c channels, or 1.5 bytes per pixel (luma + 4:2:0 chroma of the even sizes buffers come in)
-        per_frame = [smax[0] * smax[1] * c if m == warp else max_h0 * max_w0 * c if fmt is None else max_h0 * max_w0 * 2 if fmt == "y16" else max_h0 * max_w0 + 2 * ((max_h0 + 1) // 2) * ((max_w0 + 1) // 2) for m, (c, fmt) in enumerate(zip(chans, formats))]
-        cap = [B * (-(-n // A) * A) for n in per_frame]
-        probe, _ = ops.frame_geometry([(max_h0, max_w0)] * B, (H, W))
-        probe = np.concatenate((probe, probe))
-        if yuv:
-            matrix = ops.yuv_matrix_code(yuv_matrix)
-            lay = [fmt if fmt is not None else c for c, fmt in zip(chans, formats)]
-            probe = np.concatenate((ops.pack_yuv_frames(probe[:B], lay[0], matrix=matrix)[0], ops.pack_yuv_frames(probe[B:], lay[1], matrix=matrix, base=cap[0])[0]))
-        elif y16:
-            matrix, lay = 0, [fmt if fmt is not None else c for c, fmt in zip(chans, formats)]
-            probe = np.concatenate((ops.pack_y16_frames(probe[:B], lay[0], clip=agc_clip)[0], ops.pack_y16_frames(probe[B:], lay[1], clip=agc_clip, base=cap[0])[0]))
-        elif warp is not None:
-            matrix, lay = 0, list(chans)
-            src = [(smax[0], smax[1], chans[m]) if m == warp else chans[m] for m in (0, 1)]
-            mat = [np.eye(3, dtype=np.float32) if m == warp else None for m in (0, 1)]
-            probe = np.concatenate((ops.pack_warp_frames(probe[:B], src[0], mat[0], border)[0], ops.pack_warp_frames(probe[B:], src[1], mat[1], border, base=cap[0])[0]))
-        else:
-            matrix, lay = 0, list(chans)
-            ops.pack_frames(probe[:B], chans[0])
-            ops.pack_frames(probe[B:], chans[1], base=cap[0])
+        # what a pack function takes for a frame of each modality (ops.frame_specs) and the bytes it holds at the maximum size
+        specs = [fmt if fmt is not None else (smax[0], smax[1], c) if m == warp else c for m, (c, fmt) in enumerate(zip(chans, formats))]
+        cap = [B * (-(-ops.frame_bytes(s, max_h0, max_w0) // A) * A) for s in specs]
+        opts = {"matrix": ops.yuv_matrix_code(yuv_matrix) if kind.name == "yuv" else 0, "clip": agc_clip, "border": border}
+        probe1, _ = ops.frame_geometry([(max_h0, max_w0)] * B, (H, W))
+        probe = np.concatenate([kind.pack(probe1.copy(), [specs[m]] * B, base=base, **opts)[0] for m, base in ((0, 0), (1, cap[0]))])
         gb = 2 * B * probe.dtype.itemsize
         self.frames = {"B": B, "H": H, "W": W, "max": (max_h0, max_w0), "chans": chans, "cap": cap, "geom_bytes": gb, "cache": {},
                        "arena": [], "tab_dev": [], "tab_host": [], "letterbox": [], "scale_rows": [], "scale_launch": {}, "pending": None,
-                       "round": bool(round_boxes), "formats": formats, "yuv": yuv, "matrix": matrix, "layouts": lay,
-                       "warp": warp, "smax": smax, "border": border, "y16": y16, "clip": agc_clip, "window": [], "select": []}
+                       "round": bool(round_boxes), "formats": formats, "kind": kind, "specs": specs, "opts": opts,
+                       "warp": warp, "smax": smax, "window": []}
         f = self.frames
         for plan in self.plans:
             arena = torch.zeros((sum(cap),), dtype=torch.uint8, device=self.device)
@@ -214,108 +191,39 @@ class DetectionPipeline:
             f["tab_dev"].append(tab)
             f["tab_host"].append(torch.zeros((gb + B * 20,), dtype=torch.uint8).pin_memory())
             f["scale_rows"].append(tab[gb:].view(torch.float32).view(B, 5))
-            if y16:                                                              # two launches: the windows, then the letterbox that reads them
-                f["window"].append(torch.zeros((2 * B, 2), dtype=torch.int32, device=self.device))
-                f["select"].append(ops.y16_window(arena, probe, tab, f["window"][-1], B, H, W))
-                f["letterbox"].append(ops.letterbox_y16_frames(arena, probe, tab, f["window"][-1], plan.inputs[0], swap_rb=bgr))
-                continue
-            launch = ops.letterbox_yuv_frames if yuv else ops.letterbox_warp_frames if warp is not None else ops.letterbox_frames
-            f["letterbox"].append(launch(arena, probe, tab, plan.inputs[0], swap_rb=bgr))
+            f["window"].append(torch.zeros((2 * B, 2), dtype=torch.int32, device=self.device) if kind.window else None)
+            f["letterbox"].append(kind.launches(arena, probe, tab, plan.inputs[0], bgr, B, window=f["window"][-1]))     # a step's launches, in order
 
     def _frame_table(self, shapes, contiguous, src_shapes=None):
-        """(table bytes, descriptor rows) of one step's frames, cached per set of shapes: the geometry, the arena layout (a uniform
-        batch whose frames are whole 16-byte multiples keeps its layout, so ONE copy per modality moves it; other frames start on
-        FRAME_ALIGN boundaries) and the validation against this pipeline's arena and output size."""
+        """(table bytes, descriptor rows) of one step's frames, cached per set of shapes: the geometry, the arena layout
+        (ops.layout_modality: a uniform batch whose frames are whole 16-byte multiples keeps its layout, so ONE copy per modality moves it;
+        other frames start on FRAME_ALIGN boundaries) and the validation against this pipeline's arena and output size.  The rows of an
+        aligned modality lie around its SOURCE frames, with identity matrices, those of a 16-bit modality are in percentile mode:
+        submit_frames writes a step's matrices and windows into the pinned table."""
         f = self.frames
         key = (tuple(shapes), contiguous) + ((tuple(src_shapes),) if src_shapes is not None else ())
         hit = f["cache"].get(key)
         if hit is None:
-            B, chans, cap = f["B"], f["chans"], f["cap"]
+            B, cap, kind = f["B"], f["cap"], f["kind"]
             for h0, w0 in shapes:
                 if h0 > f["max"][0] or w0 > f["max"][1]:
                     raise ValueError(f"a {h0}x{w0} frame exceeds the pipeline's frames={f['max']}")
+            for hs, ws in src_shapes or ():
+                if hs > f["smax"][0] or ws > f["smax"][1]:
+                    raise ValueError(f"a {hs}x{ws} frame exceeds the pipeline's align_frames={f['smax']}")
             geom1, scale = ops.frame_geometry(shapes, (f["H"], f["W"]))
-            geom = np.concatenate((geom1, geom1))
-            if f["yuv"]:
-                geom = self._yuv_rows(geom, contiguous)
-            elif f["y16"]:
-                geom = self._y16_rows(geom, contiguous)
-            elif f["warp"] is not None:
-                geom = self._warp_rows(geom, contiguous, src_shapes)
-            else:
-                for m, base in ((0, 0), (1, cap[0])):
-                    rows = geom[m * B:(m + 1) * B]
-                    if contiguous[m]:
-                        ops.pack_frames(rows, chans[m])
-                        fb = int(rows[0]["h0"]) * int(rows[0]["pitch"])
-                        rows["offset"] = base + fb * np.arange(B)
-                    else:
-                        end = ops.pack_frames(rows, chans[m], base=base)
-                        if end - base > cap[m]:
-                            raise ValueError(f"the frames of modality {m} need {end - base} bytes of the arena's {cap[m]}")
-            (ops.validate_yuv_frames if f["yuv"] else ops.validate_y16_frames if f["y16"] else ops.validate_warp_frames if f["warp"] is not None else ops.validate_frames)(geom, sum(cap), f["H"], f["W"])
+            halves = []
+            for m, base in ((0, 0), (1, cap[0])):
+                specs = [(hs, ws, f["chans"][m]) for hs, ws in src_shapes] if m == f["warp"] else [f["specs"][m]] * B
+                rows, end = kind.pack(geom1.copy(), specs, base=base, **f["opts"])
+                halves.append(ops.layout_modality(rows, end, base, cap[m], contiguous[m], m))
+            geom = np.concatenate(halves)
+            kind.validate(geom, sum(cap), f["H"], f["W"])
             table = np.concatenate((geom.view(np.uint8).reshape(-1), scale.view(np.uint8).reshape(-1)))
             if len(f["cache"]) >= 64:
                 f["cache"].pop(next(iter(f["cache"])))
             hit = f["cache"][key] = (torch.from_numpy(table), geom)
         return hit
-
-    def _yuv_rows(self, geom, contiguous):
-        """_frame_table's arena layout for a pipeline with a YUV modality: icaf_yuv_geom rows.  A uniform batch in one contiguous tensor
-        whose frames are whole 16-byte multiples keeps its layout (frame b of the modality at b frame sizes: ONE copy moves it), other
-        frames start on FRAME_ALIGN boundaries."""
-        f = self.frames
-        B, cap, halves = f["B"], f["cap"], []
-        for m, base in ((0, 0), (1, cap[0])):
-            rows, end = ops.pack_yuv_frames(geom[m * B:(m + 1) * B], f["layouts"][m], matrix=f["matrix"], base=base)
-            if contiguous[m]:
-                fb = (end - int(rows[B - 1]["g"]["offset"]))                        # bytes of one frame, chroma included
-                for k in ("cb_offset", "cr_offset"):
-                    rows[k] += (rows["kind"] != 0) * (base + fb * np.arange(B) - rows["g"]["offset"])
-                rows["g"]["offset"] = base + fb * np.arange(B)
-            elif end - base > cap[m]:
-                raise ValueError(f"the frames of modality {m} need {end - base} bytes of the arena's {cap[m]}")
-            halves.append(rows)
-        return np.concatenate(halves)
-
-    def _y16_rows(self, geom, contiguous):
-        """_frame_table's arena layout for a pipeline with a 16-bit thermal modality: icaf_y16_geom rows in percentile mode (submit_frames
-        writes a step's windows into the pinned table).  A uniform batch in one contiguous tensor whose frames are whole 16-byte multiples
-        keeps its layout, other frames start on FRAME_ALIGN boundaries."""
-        f = self.frames
-        B, cap, halves = f["B"], f["cap"], []
-        for m, base in ((0, 0), (1, cap[0])):
-            rows, end = ops.pack_y16_frames(geom[m * B:(m + 1) * B], f["layouts"][m], clip=f["clip"], base=base)
-            if contiguous[m]:
-                rows["g"]["offset"] = base + int(rows[0]["g"]["h0"]) * int(rows[0]["g"]["pitch"]) * np.arange(B)
-            elif end - base > cap[m]:
-                raise ValueError(f"the frames of modality {m} need {end - base} bytes of the arena's {cap[m]}")
-            halves.append(rows)
-        return np.concatenate(halves)
-
-    def _warp_rows(self, geom, contiguous, src_shapes):
-        """_frame_table's arena layout for a calibrated rig: icaf_warp_geom rows, the aligned modality's around its SOURCE frames (identity
-        matrices: submit_frames writes the step's into the pinned table).  A uniform batch in one contiguous tensor whose frames are whole
-        16-byte multiples keeps its layout, other frames start on FRAME_ALIGN boundaries."""
-        f = self.frames
-        B, cap, chans, halves = f["B"], f["cap"], f["chans"], []
-        for hs, ws in src_shapes:
-            if hs > f["smax"][0] or ws > f["smax"][1]:
-                raise ValueError(f"a {hs}x{ws} frame exceeds the pipeline's align_frames={f['smax']}")
-        for m, base in ((0, 0), (1, cap[0])):
-            if m == f["warp"]:
-                rows, end = ops.pack_warp_frames(geom[m * B:(m + 1) * B], [(hs, ws, chans[m]) for hs, ws in src_shapes], [np.eye(3, dtype=np.float32)] * B,
-                                                 f["border"], base=base)
-                fb = int(rows[0]["hs"]) * int(rows[0]["g"]["pitch"])
-            else:
-                rows, end = ops.pack_warp_frames(geom[m * B:(m + 1) * B], chans[m], base=base)
-                fb = int(rows[0]["g"]["h0"]) * int(rows[0]["g"]["pitch"])
-            if contiguous[m]:
-                rows["g"]["offset"] = base + fb * np.arange(B)
-            elif end - base > cap[m]:
-                raise ValueError(f"the frames of modality {m} need {end - base} bytes of the arena's {cap[m]}")
-            halves.append(rows)
-        return np.concatenate(halves)
 
     def submit_frames(self, rgb, ir, align=None, agc_window=None):
         """One batch of NATIVE frames through the pipeline: rgb / ir are uint8 (B, H0, W0, ch) tensors or lists of (H0_i, W0_i, ch) tensors,
@@ -332,25 +240,19 @@ class DetectionPipeline:
         f = self.frames
         if f is None:
             raise ValueError("DetectionPipeline(frames=(max_h0, max_w0)) takes native frames")
-        B, chans = f["B"], f["chans"]
+        B, chans, kind = f["B"], f["chans"], f["kind"]
         wins = None
         if agc_window is not None:
-            if not f["y16"]:
+            if not kind.window:
                 raise ValueError("submit_frames(agc_window=...) goes with DetectionPipeline(frame_formats=(..., 'y16'))")
             wins = ops._y16_windows(agc_window, B)
             for lo_, hi_ in wins:
                 if not 0 <= lo_ <= hi_ <= 65535:
                     raise ValueError(f"agc_window ({lo_}, {hi_}) must satisfy 0 <= lo <= hi <= 65535")
-        if f["y16"]:
-            rgb, ir = (ops.y16_bytes(t) if fmt else t for t, fmt in zip((rgb, ir), f["formats"]))
+        rgb, ir = (ops.y16_bytes(t) if fmt == "y16" else t for t, fmt in zip((rgb, ir), f["formats"]))
         if (align is None) != (f["warp"] is None):
             raise ValueError("submit_frames(align=...) goes with DetectionPipeline(frame_align=..., align_frames=...): both or neither")
-        src_shapes = mats = None
-        if f["warp"] is not None:
-            *lists, shapes, uniform, _, src_shapes, mats = ops.warp_frame_lists(rgb, ir, (align, None) if f["warp"] == 0 else (None, align))
-        else:
-            *lists, shapes, uniform = ops.yuv_frame_lists(rgb, ir, f["formats"]) if f["yuv"] else \
-                ops.y16_frame_lists(rgb, ir, f["formats"]) if f["y16"] else ops.frame_lists(rgb, ir)
+        *lists, shapes, uniform, _, src_shapes, mats = kind.lists(rgb, ir, f["formats"], None if align is None else (align, None) if f["warp"] == 0 else (None, align))
         if len(shapes) != B:
             raise ValueError(f"submit_frames expects a batch of {B} pairs, got {len(shapes)}")
         mods, contiguous = [], []
@@ -367,16 +269,8 @@ class DetectionPipeline:
         if self.n >= self.nplans:
             self.copied[pi][0].synchronize()                                # the last copy OUT of this plan's pinned table (nplans steps ago) has run
         f["tab_host"][pi].copy_(table)
-        if mats is not None:                                                # this step's matrices, into the pinned rows of the aligned modality
-            rows = f["tab_host"][pi].numpy()[:f["geom_bytes"]].view(ops.WARP_GEOM_DTYPE)
-            rows["m"][f["warp"] * B:(f["warp"] + 1) * B] = mats.reshape(B, 9)
-        if wins is not None:                                                # this step's windows, into the pinned rows of the Y16 modalities
-            rows = f["tab_host"][pi].numpy()[:f["geom_bytes"]].view(ops.Y16_GEOM_DTYPE)
-            for m, fmt in enumerate(f["formats"]):
-                if fmt:
-                    rows["mode"][m * B:(m + 1) * B] = 0
-                    rows["lo"][m * B:(m + 1) * B] = [w[0] for w in wins]
-                    rows["hi"][m * B:(m + 1) * B] = [w[1] for w in wins]
+        if kind.update is not None:                                         # this step's matrices / windows, into the pinned rows they belong to
+            kind.update(f["tab_host"][pi].numpy()[:f["geom_bytes"]].view(kind.dtype), B, f["formats"], f["warp"], mats=mats, wins=wins)
         cur = torch.cuda.current_stream(self.device)
         for k, cs in enumerate(self.copy_streams):                          # the batch in `ncs` slices of images, one copy stream each
             lo, hi = B * k // ncs, B * (k + 1) // ncs
@@ -395,7 +289,7 @@ class DetectionPipeline:
                 if k == 0:
                     f["tab_dev"][pi].copy_(f["tab_host"][pi], non_blocking=True)
                 for m, (t, fr) in enumerate(mods):
-                    rows = geom[m * B:(m + 1) * B]["g"] if f["yuv"] or f["y16"] or f["warp"] is not None else geom[m * B:(m + 1) * B]
+                    rows = ops.frame_rows(geom[m * B:(m + 1) * B])
                     if contiguous[m]:
                         o, fb = int(rows[lo]["offset"]), t[0].numel()
                         arena[o:o + (hi - lo) * fb].view(t[lo:hi].shape).copy_(t[lo:hi], non_blocking=True)
@@ -410,9 +304,8 @@ class DetectionPipeline:
                             x.record_stream(cs)
             self.copied[pi][k].record(cs)
             fs.wait_event(self.copied[pi][k])
-        if f["y16"]:
-            f["select"][pi](fs.cuda_stream)
-        f["letterbox"][pi](fs.cuda_stream)
+        for launch in f["letterbox"][pi]:
+            launch(fs.cuda_stream)
         f["pending"] = pi
         try:
             return self.step()

@@ -129,6 +129,39 @@ def test_forward_from_frames_equals_forward_from_the_host_letterbox(dtype):
     assert torch.equal(z, ref.forward_u8(host_batch(flipped, flipped, 320).to(DEV))[0])
 
 
+def test_forward_frames_of_every_kind_from_one_state_cache():
+    """One yolov5s bf16 model at 320 x 320, the smallest size its DMFF blocks take (20 x 20 tokens at stride 16), two pairs of 48 x 80 and
+    60 x 44 (one padded above and below, the other left and right): forward_frames as plain, NV12 visible, 16-bit thermal, a 36 x 50 thermal
+    source through a rotation, plain again, then the four in reverse.  The four kinds of table (ops.KINDS) share ONE cache of states and
+    rebind their launches to one plan input: every result is forward_u8 of the host-prepared batch bit for bit, and the second visit of a
+    kind equals its first."""
+    m, ref = build("yolov5s_Transfusion_kaist.yaml", torch.bfloat16), build("yolov5s_Transfusion_kaist.yaml", torch.bfloat16)
+    new, shapes = 320, [(48, 80), (60, 44)]
+    g = np.random.default_rng(70)
+    rgb, grey, src = frames_of(shapes, 3, 71), frames_of(shapes, 1, 72), frames_of([(36, 50)] * 2, 1, 73)
+    planes = [(g.integers(0, 256, (h, w), dtype=np.uint8), g.integers(0, 256, (h // 2, w // 2), dtype=np.uint8),
+               g.integers(0, 256, (h // 2, w // 2), dtype=np.uint8)) for h, w in shapes]
+    nv12 = [np.concatenate((y, np.stack((cb, cr), -1).reshape(y.shape[0] // 2, y.shape[1]))) for y, cb, cr in planes]
+    raw = [g.integers(28000, 34000, s).astype(np.uint16) for s in shapes]
+    M = np.array([[0.6 * np.cos(0.1), -0.6 * np.sin(0.1), 3.0], [0.6 * np.sin(0.1), 0.6 * np.cos(0.1), 1.5], [0.0, 0.0, 1.0]], np.float32)
+    dev = lambda frames: [torch.from_numpy(f).to(DEV) for f in frames]
+    calls = {"plain": (rgb, grey, {}, (rgb, grey)),
+             "yuv": (nv12, grey, {"formats": ("nv12", None)}, ([D.yuv420_to_bgr(*p) for p in planes], grey)),
+             "y16": (rgb, [f.view(np.int16) for f in raw], {"formats": (None, "y16")}, (rgb, [D.agc_u16_to_u8(f, *D.agc_window(f))[:, :, None] for f in raw])),
+             "align": (rgb, src, {"align": (None, M), "align_border": 7}, (rgb, [D.warp_perspective(f, M, s, 7) for f, s in zip(src, shapes)]))}
+    want = {k: ref.forward_u8(host_batch(*host, new).to(DEV)) for k, (_, _, _, host) in calls.items()}
+    assert not torch.equal(want["plain"][0], want["y16"][0]) and not torch.equal(want["plain"][0], want["align"][0])
+    first = {}
+    for k in ("plain", "yuv", "y16", "align", "plain", "align", "y16", "yuv", "plain"):
+        a, b, kw, _ = calls[k]
+        (z, logits, raws), info = m.forward_frames(dev(a), dev(b), new, **kw)
+        wz, wlogits, wraws = want[k]
+        assert torch.equal(z, wz) and torch.equal(logits, wlogits) and all(torch.equal(x, y) for x, y in zip(raws, wraws)), k
+        assert np.array_equal(info.scale.cpu().numpy(), ops.frame_geometry(shapes, new)[1]) and info.geom.dtype == ops.KINDS[k].dtype
+        assert torch.equal(z, first.setdefault(k, z.clone())), k
+    assert sorted(key[0] for key in m._frame_states) == ["align", "plain", "y16", "yuv"]
+
+
 def test_tta_from_frames_equals_tta_from_the_host_letterbox():
     m = build("yolov5s_Transfusion_kaist.yaml", torch.bfloat16)
     ref = build("yolov5s_Transfusion_kaist.yaml", torch.bfloat16)
