@@ -24,6 +24,7 @@
 #include "icaf_common.h"
 #include "conv_common.h"
 #include "attn_core.h"
+#include "dmff_args.h"
 
 namespace icaf {
 
@@ -675,110 +676,114 @@ static size_t attn_mlp_lds(int C, int N, int dkp, int eb) {      // (eb = 4: alw
     const size_t ks = dkp * eb == 32 ? 32 : dkp * eb + 16;
     const bool ones = eb == 2 && dkp % 32 == 16;                            // AttnCore<>::ones_row(): one all-ones V^T row per head
     const size_t kv2 = 2 * ((size_t)NP * ks + (size_t)(dkp + (ones ? 1 : 0)) * (NP * eb + 16));
-    const bool dma = eb == 2 && slice_bytes(C) == 128 && C > 128;         // = attn_mlp_dma<>() of the instantiation dispatch_np2 picks
+    const bool dma = eb == 2 && slice_bytes(C) == 128 && C > 128;         // = attn_mlp_dma<>() of the instantiation launch_np2 picks
     const size_t ring = dma ? (size_t)DMFF_NSD * 128 * 128 : (eb == 4 || slice_bytes(C) == 128) ? Ring<128>::BYTES : Ring<64>::BYTES;
     const size_t chain = hb + ring + 2 * 64 * sizeof(float);
     return tile + (kv2 > chain ? kv2 : chain);
 }
 
+// What the two launches run for a shape — THE statement of which instantiations exist: the launches, icaf_dmff_attn_mlp_lds_bytes and
+// icaf_dmff_block_forms (dmff_wide.hip) all go through fused_resolve.
+struct FusedForm {
+    int slb;          // bytes of K per weight slice (both kernels)
+    int dkp;          // head dimension padded to an instantiation of the attention core
+    int np2;          // 128-channel passes per C-wide product in the instantiation (C = 320 at 64-byte slices runs the four-pass build)
+    size_t lds;       // dynamic LDS of dmff_attn_mlp_kernel; set as soon as every rule before the 160 KiB limit holds
+};
+
+// attn_mlp = false: the rules of icaf_dmff_ln_qkv alone (it reaches C = 1024 and reads neither hidden nor the padded head dimension)
+static int fused_resolve(const char* who, int dtype, int C, int N, int heads, int hidden, FusedForm& f, bool attn_mlp = true) {
+    f = FusedForm{};
+    const bool f32 = dtype == ICAF_F32;
+    if (dtype != ICAF_BF16 && dtype != ICAF_F16 && !f32) return fail(ICAF_ERR_ARG, "%s: bad dtype %d", who, dtype);
+    if (f32 && C > 128) return fail(ICAF_ERR_UNSUPPORTED, "%s: the fp32 instantiation covers C <= 128 (wider fp32 blocks use the per-layer launches)", who);
+    if (N < 1 || heads < 1 || C < 1 || C % heads) return fail(ICAF_ERR_ARG, "%s: bad N/heads", who);
+    if (C % 64 || C > 1024) return fail(ICAF_ERR_UNSUPPORTED, "%s: C=%d must be a multiple of 64 and <= 1024", who, C);
+    const int dk = C / heads;
+    if (dk % 8) return fail(ICAF_ERR_UNSUPPORTED, "%s: head dim %d must be a multiple of 8", who, dk);
+    f.slb = f32 ? 128 : slice_bytes(C);                    // (fp32: 32 K elements per slice, C % 64 == 0 gives an even count)
+    if (!attn_mlp) return ICAF_OK;
+    if (hidden % 128 || hidden < 128) return fail(ICAF_ERR_UNSUPPORTED, "%s: hidden width %d must be a multiple of 128", who, hidden);
+    // fp32 (parity build of the same template): head dims 8 .. 32 — what fits the LDS plan with 4-byte tiles
+    if (dk > (f32 ? 32 : 128)) return fail(ICAF_ERR_UNSUPPORTED, "%s: head dim %d > %d", who, dk, f32 ? 32 : 128);
+    f.dkp = dk <= 16 ? 16 : dk <= 32 ? 32 : dk <= 48 ? 48 : dk <= 64 ? 64 : dk <= 96 ? 96 : 128;
+    if (C > 512) return fail(ICAF_ERR_UNSUPPORTED, "%s: C=%d > 512 (the [64 x C] token tile and K / V^T of two heads exceed the LDS)", who, C);
+    f.np2 = (C + 127) / 128;
+    if (f.slb == 64 && f.np2 == 3) f.np2 = 4;              // C = 320: 64-byte slices are built for 1, 2 and 4 passes
+    f.lds = attn_mlp_lds(C, N, f.dkp, f32 ? 4 : 2);
+    if (f.lds > 160 * 1024) return fail(ICAF_ERR_UNSUPPORTED, "%s: %zu bytes of LDS (C=%d, N=%d, dk=%d) exceed 160 KiB", who, f.lds, C, N, dk);
+    return ICAF_OK;
+}
+
+bool dmff_fused_covered(int dtype, int C, int N, int heads, int hidden) {
+    FusedForm f;
+    return fused_resolve("icaf_dmff_block_forms", dtype, C, N, heads, hidden, f) == ICAF_OK;
+}
+
 template <int DT, int DKP, int NP2, int SLB>
-static int launch_attn_mlp(const DmffP& p, hipStream_t s) {
-    const size_t lds = attn_mlp_lds(p.C, p.N, DKP, Elem<DT>::BYTES);
-    if (lds > 160 * 1024) return fail(ICAF_ERR_UNSUPPORTED, "icaf_dmff_attn_mlp: %zu bytes of LDS (C=%d, N=%d, dk=%d) exceed 160 KiB", lds, p.C, p.N, p.dk);
-    static std::atomic<bool> attr_set[ICAF_MAX_DEVICES];
-    int dev = 0;
-    ICAF_HIP(hipGetDevice(&dev));
-    if (dev < 0 || dev >= ICAF_MAX_DEVICES) return fail(ICAF_ERR_UNSUPPORTED, "device ordinal %d", dev);
-    if (!attr_set[dev]) {
-        ICAF_HIP(hipFuncSetAttribute((const void*)dmff_attn_mlp_kernel<DT, DKP, NP2, SLB>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        attr_set[dev] = true;
-    }
+static int launch_attn_mlp(const DmffP& p, const FusedForm& f, hipStream_t s) {
+    ICAF_LDS_OPTIN((dmff_attn_mlp_kernel<DT, DKP, NP2, SLB>), f.lds);
     dim3 grid((unsigned)(((p.N + TMROWS - 1) / TMROWS) * p.B * 2));
-    hipLaunchKernelGGL((dmff_attn_mlp_kernel<DT, DKP, NP2, SLB>), grid, dim3(FT), lds, s, p);
+    hipLaunchKernelGGL((dmff_attn_mlp_kernel<DT, DKP, NP2, SLB>), grid, dim3(FT), f.lds, s, p);
     ICAF_LAUNCH_CHECK();
     return ICAF_OK;
 }
 
+// resolved values -> template arguments (no rule lives here: fused_resolve returns nothing these switches lack)
 template <int DT, int DKP>
-static int dispatch_np2(const DmffP& p, hipStream_t s) {
-    const int np2 = (p.C + 127) / 128;
-    if (slice_bytes(p.C) == 128) {
-        if (np2 <= 1) return launch_attn_mlp<DT, DKP, 1, 128>(p, s);
-        if (np2 <= 2) return launch_attn_mlp<DT, DKP, 2, 128>(p, s);
-        if (np2 <= 3) return launch_attn_mlp<DT, DKP, 3, 128>(p, s);
-        if (np2 <= 4) return launch_attn_mlp<DT, DKP, 4, 128>(p, s);
-    } else {                                    // C = 64, 192, 320, 448: 64-byte slices
-        if (np2 <= 1) return launch_attn_mlp<DT, DKP, 1, 64>(p, s);
-        if (np2 <= 2) return launch_attn_mlp<DT, DKP, 2, 64>(p, s);
-        if (np2 <= 4) return launch_attn_mlp<DT, DKP, 4, 64>(p, s);
+static int launch_np2(const DmffP& p, const FusedForm& f, hipStream_t s) {
+    switch (f.slb * 8 + f.np2) {
+        case 128 * 8 + 1: return launch_attn_mlp<DT, DKP, 1, 128>(p, f, s);
+        case 128 * 8 + 2: return launch_attn_mlp<DT, DKP, 2, 128>(p, f, s);
+        case 128 * 8 + 3: return launch_attn_mlp<DT, DKP, 3, 128>(p, f, s);
+        case 128 * 8 + 4: return launch_attn_mlp<DT, DKP, 4, 128>(p, f, s);
+        case 64 * 8 + 1: return launch_attn_mlp<DT, DKP, 1, 64>(p, f, s);          // C = 64, 192, 320, 448: 64-byte slices
+        case 64 * 8 + 2: return launch_attn_mlp<DT, DKP, 2, 64>(p, f, s);
+        case 64 * 8 + 4: return launch_attn_mlp<DT, DKP, 4, 64>(p, f, s);
     }
-    return fail(ICAF_ERR_UNSUPPORTED, "icaf_dmff_attn_mlp: C=%d > 512 (the [64 x C] token tile and K / V^T of two heads exceed the LDS)", p.C);
-}
-
-// fp32 (parity build of the same template): C <= 128, head dims 8 .. 32 — what fits the LDS plan with 4-byte tiles
-static int dispatch_attn_mlp_f32(const DmffP& p, hipStream_t s) {
-    if (p.C > 128 || p.dk > 32) return fail(ICAF_ERR_UNSUPPORTED, "icaf_dmff_attn_mlp: the fp32 instantiation covers C <= 128, head dim <= 32 (C=%d, dk=%d)", p.C, p.dk);
-    if (p.dk <= 16) return launch_attn_mlp<ICAF_F32, 16, 1, 128>(p, s);
-    return launch_attn_mlp<ICAF_F32, 32, 1, 128>(p, s);
+    return fail(ICAF_ERR_UNSUPPORTED, "icaf_dmff_attn_mlp: no instantiation with %d passes of %d-byte slices", f.np2, f.slb);
 }
 
 template <int DT>
-static int dispatch_attn_mlp(const DmffP& p, hipStream_t s) {
-    if (p.dk <= 16) return dispatch_np2<DT, 16>(p, s);
-    if (p.dk <= 32) return dispatch_np2<DT, 32>(p, s);
-    if (p.dk <= 48) return dispatch_np2<DT, 48>(p, s);
-    if (p.dk <= 64) return dispatch_np2<DT, 64>(p, s);
-    if (p.dk <= 96) return dispatch_np2<DT, 96>(p, s);
-    if (p.dk <= 128) return dispatch_np2<DT, 128>(p, s);
-    return fail(ICAF_ERR_UNSUPPORTED, "icaf_dmff_attn_mlp: head dim %d > 128", p.dk);
+static int launch_dkp(const DmffP& p, const FusedForm& f, hipStream_t s) {
+    switch (f.dkp) {
+        case 16: return launch_np2<DT, 16>(p, f, s);
+        case 32: return launch_np2<DT, 32>(p, f, s);
+        case 48: return launch_np2<DT, 48>(p, f, s);
+        case 64: return launch_np2<DT, 64>(p, f, s);
+        case 96: return launch_np2<DT, 96>(p, f, s);
+        case 128: return launch_np2<DT, 128>(p, f, s);
+    }
+    return fail(ICAF_ERR_UNSUPPORTED, "icaf_dmff_attn_mlp: no instantiation for head dim %d", f.dkp);
+}
+
+// fp32 (parity build of the same template): one pass, head dims padded to 16 / 32.  (Ahead of the entry points on purpose: its two kernels stay the
+// first of the device module — WIDE_KERNEL_ORDER in dmff_wide.hip says why the order is kept.)
+static int launch_attn_mlp_f32(const DmffP& p, const FusedForm& f, hipStream_t s) {
+    return f.dkp == 16 ? launch_attn_mlp<ICAF_F32, 16, 1, 128>(p, f, s) : launch_attn_mlp<ICAF_F32, 32, 1, 128>(p, f, s);
 }
 
 template <int DT, int SLB>
-static int launch_ln_qkv_t(const DmffP& p, hipStream_t s) {
+static int launch_ln_qkv(const DmffP& p, hipStream_t s) {
     const size_t lds = (size_t)TMROWS * (p.C * Elem<DT>::BYTES + 16) + Ring<SLB>::BYTES;
-    if (lds > 160 * 1024) return fail(ICAF_ERR_UNSUPPORTED, "icaf_dmff_ln_qkv: C=%d too wide", p.C);
-    static std::atomic<bool> attr_set[ICAF_MAX_DEVICES];
-    int dev = 0;
-    ICAF_HIP(hipGetDevice(&dev));
-    if (dev < 0 || dev >= ICAF_MAX_DEVICES) return fail(ICAF_ERR_UNSUPPORTED, "device ordinal %d", dev);
-    if (!attr_set[dev]) {
-        ICAF_HIP(hipFuncSetAttribute((const void*)dmff_ln_qkv_kernel<DT, SLB>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        attr_set[dev] = true;
-    }
+    ICAF_LDS_OPTIN((dmff_ln_qkv_kernel<DT, SLB>), lds);
     const long long rows = (long long)p.B * p.N;
     dim3 grid((unsigned)((rows + TMROWS - 1) / TMROWS), (unsigned)((3 * p.C + QKV_GROUP - 1) / QKV_GROUP), 2u);
     hipLaunchKernelGGL((dmff_ln_qkv_kernel<DT, SLB>), grid, dim3(FT), lds, s, p);
     ICAF_LAUNCH_CHECK();
     return ICAF_OK;
 }
-template <int DT>
-static int launch_ln_qkv(const DmffP& p, hipStream_t s) {
-    if constexpr (DT == ICAF_F32) return launch_ln_qkv_t<DT, 128>(p, s);                  // (32 K elements per slice: C % 64 == 0 gives an even count)
-    else return slice_bytes(p.C) == 128 ? launch_ln_qkv_t<DT, 128>(p, s) : launch_ln_qkv_t<DT, 64>(p, s);
-}
 
-static int fill(const icaf_dmff_args* a, DmffP& p, const char* who) {
+static int fill(const icaf_dmff_args* a, DmffP& p, FusedForm& f, bool attn_mlp, const char* who) {
     if (!a || !a->x || !a->qkv || !a->wqkv || !a->bqkv) return fail(ICAF_ERR_ARG, "%s: null pointer", who);
-    if (a->dtype != ICAF_BF16 && a->dtype != ICAF_F16 && a->dtype != ICAF_F32) return fail(ICAF_ERR_ARG, "%s: bad dtype %d", who, a->dtype);
-    if (a->dtype == ICAF_F32 && a->C > 128) return fail(ICAF_ERR_UNSUPPORTED, "%s: the fp32 instantiation covers C <= 128 (wider fp32 blocks use the per-layer launches)", who);
-    if (a->B < 1 || a->N < 1 || a->heads < 1 || a->C % a->heads || a->B > 65535) return fail(ICAF_ERR_ARG, "%s: bad B/N/heads", who);
-    if (a->C % 64 || a->C > 1024) return fail(ICAF_ERR_UNSUPPORTED, "%s: C=%d must be a multiple of 64 and <= 1024", who, a->C);
-    if ((a->C / a->heads) % 8) return fail(ICAF_ERR_UNSUPPORTED, "%s: head dim %d must be a multiple of 8", who, a->C / a->heads);
+    if (a->B < 1 || a->B > 65535) return fail(ICAF_ERR_ARG, "%s: bad B", who);
+    const int st = fused_resolve(who, a->dtype, a->C, a->N, a->heads, a->hidden, f, attn_mlp);
+    if (st) return st;
     if (a->Kp < a->C || a->Kp % (a->dtype == ICAF_F32 ? 32 : 64)) return fail(ICAF_ERR_ARG, "%s: Kp=%d", who, a->Kp);
-    p.x = a->x; p.qkv = a->qkv; p.y = a->y;
-    p.wqkv = a->wqkv; p.bqkv = a->bqkv; p.wo = a->wo; p.bo = a->bo; p.w1 = a->w1; p.b1 = a->b1; p.w2 = a->w2; p.b2 = a->b2;
-    p.ln_a_g[0] = a->ln_attn_gamma[0]; p.ln_a_g[1] = a->ln_attn_gamma[1]; p.ln_a_b[0] = a->ln_attn_beta[0]; p.ln_a_b[1] = a->ln_attn_beta[1];
-    p.ln_m_g = a->ln_mlp_gamma; p.ln_m_b = a->ln_mlp_beta;
-    p.wqkv_gs = a->wqkv_gs; p.bqkv_gs = a->bqkv_gs; p.wo_gs = a->wo_gs; p.bo_gs = a->bo_gs; p.w1_gs = a->w1_gs; p.b1_gs = a->b1_gs;
-    p.w2_gs = a->w2_gs; p.b2_gs = a->b2_gs; p.x_gs = a->x_gs; p.y_gs = a->y_gs;
-    p.B = a->B; p.N = a->N; p.C = a->C; p.heads = a->heads; p.dk = a->C / a->heads; p.Kp = a->Kp; p.Kp4 = a->Kp4; p.hid = a->hidden; p.ldy = a->ldy;
-    p.eps_a = a->eps_attn; p.eps_m = a->eps_mlp;
+    dmff_fill_common(a, p);
+    p.B = a->B; p.N = a->N; p.heads = a->heads; p.dk = a->C / a->heads;
     p.scale_l2e = (float)((1.0 / sqrt((double)p.dk)) * 1.4426950408889634);
     p.dbg = (long long*)a->debug_clock;
-    for (int g = 0; g < 2; ++g) {
-        p.c_res_a[g] = a->coef_res_attn[g]; p.c_acc_a[g] = a->coef_acc_attn[g];
-        p.c_res_m[g] = a->coef_res_mlp[g]; p.c_acc_m[g] = a->coef_acc_mlp[g];
-    }
     return ICAF_OK;
 }
 
@@ -788,33 +793,32 @@ using namespace icaf;
 
 extern "C" int icaf_dmff_attn_mlp_lds_bytes(int C, int N, int heads, int dtype, size_t* bytes) {
     if (!bytes || heads < 1 || C % heads) return fail(ICAF_ERR_ARG, "icaf_dmff_attn_mlp_lds_bytes: bad arguments");
-    const int dk = C / heads;
-    const int dkp = dk <= 16 ? 16 : dk <= 32 ? 32 : dk <= 48 ? 48 : dk <= 64 ? 64 : dk <= 96 ? 96 : 128;
-    if (dtype == ICAF_F32) {
-        const size_t need = C % 64 == 0 && C <= 128 && dk % 8 == 0 && dk <= 32 ? attn_mlp_lds(C, N, dkp, 4) : (size_t)-1;
-        *bytes = need <= 160 * 1024 ? need : (size_t)-1;
-        return ICAF_OK;
-    }
-    *bytes = (dtype == ICAF_BF16 || dtype == ICAF_F16) && C % 64 == 0 && C <= 512 && dk % 8 == 0 && dk <= 128 ? attn_mlp_lds(C, N, dkp, 2) : (size_t)-1;
+    FusedForm f;
+    const int st = fused_resolve("icaf_dmff_attn_mlp_lds_bytes", dtype, C, N, heads, 128, f);      // (the hidden width is not this query's business)
+    // 16-bit types: the need is reported beyond 160 KiB too, as it always was (callers compare); fp32 and every other refusal: (size_t)-1
+    *bytes = st == ICAF_OK || (f.lds && dtype != ICAF_F32) ? f.lds : (size_t)-1;
     return ICAF_OK;
 }
 
 extern "C" int icaf_dmff_ln_qkv(const icaf_dmff_args* a, icaf_stream_t s) {
     DmffP p{};
-    int st = fill(a, p, "icaf_dmff_ln_qkv");
+    FusedForm f;
+    int st = fill(a, p, f, false, "icaf_dmff_ln_qkv");
     if (st) return st;
     if (!a->ln_attn_gamma[0] || !a->ln_attn_gamma[1] || !a->ln_attn_beta[0] || !a->ln_attn_beta[1]) return fail(ICAF_ERR_ARG, "icaf_dmff_ln_qkv: LayerNorm parameters missing");
-    if (a->dtype == ICAF_F32) return launch_ln_qkv<ICAF_F32>(p, S(s));
-    return a->dtype == ICAF_BF16 ? launch_ln_qkv<ICAF_BF16>(p, S(s)) : launch_ln_qkv<ICAF_F16>(p, S(s));
+    if (a->dtype == ICAF_F32) return launch_ln_qkv<ICAF_F32, 128>(p, S(s));
+    if (a->dtype == ICAF_BF16) return f.slb == 128 ? launch_ln_qkv<ICAF_BF16, 128>(p, S(s)) : launch_ln_qkv<ICAF_BF16, 64>(p, S(s));
+    return f.slb == 128 ? launch_ln_qkv<ICAF_F16, 128>(p, S(s)) : launch_ln_qkv<ICAF_F16, 64>(p, S(s));
 }
 
 extern "C" int icaf_dmff_attn_mlp(const icaf_dmff_args* a, icaf_stream_t s) {
     DmffP p{};
-    int st = fill(a, p, "icaf_dmff_attn_mlp");
+    FusedForm f;
+    int st = fill(a, p, f, true, "icaf_dmff_attn_mlp");
     if (st) return st;
     if (!a->y || !a->wo || !a->bo || !a->w1 || !a->b1 || !a->w2 || !a->b2 || !a->ln_mlp_gamma || !a->ln_mlp_beta) return fail(ICAF_ERR_ARG, "icaf_dmff_attn_mlp: null pointer");
-    if (a->hidden % 128 || a->hidden < 128 || a->Kp4 < a->hidden || a->Kp4 % (a->dtype == ICAF_F32 ? 32 : 64)) return fail(ICAF_ERR_UNSUPPORTED, "icaf_dmff_attn_mlp: hidden width %d must be a multiple of 128", a->hidden);
+    if (a->Kp4 < a->hidden || a->Kp4 % (a->dtype == ICAF_F32 ? 32 : 64)) return fail(ICAF_ERR_UNSUPPORTED, "icaf_dmff_attn_mlp: Kp4=%d for hidden width %d", a->Kp4, a->hidden);
     if (a->ldy < a->C || a->ldy % 4) return fail(ICAF_ERR_ARG, "icaf_dmff_attn_mlp: ldy=%d", a->ldy);
-    if (a->dtype == ICAF_F32) return dispatch_attn_mlp_f32(p, S(s));
-    return a->dtype == ICAF_BF16 ? dispatch_attn_mlp<ICAF_BF16>(p, S(s)) : dispatch_attn_mlp<ICAF_F16>(p, S(s));
+    if (a->dtype == ICAF_F32) return launch_attn_mlp_f32(p, f, S(s));
+    return a->dtype == ICAF_BF16 ? launch_dkp<ICAF_BF16>(p, f, S(s)) : launch_dkp<ICAF_F16>(p, f, S(s));
 }

@@ -9,6 +9,7 @@ classes still duck-type as nn.Modules taking/returning NCHW-shaped tensors.
 There is deliberately no PyTorch / CPU fallback: calling a module with CPU tensors, in training mode, or without
 libicaf.so raises.
 """
+import collections
 import functools
 import math
 
@@ -987,25 +988,31 @@ class CrossTransformerBlock(HipModule):
     # form at C <= fuse_max_c <= 128, and (round 5) the THREE-launch form every yolov5s level runs by default, at C = 128 (dmff_wide.hip)
     fuse_fp32 = OPT.dmff_fuse_fp32
 
-    def fusable(self, plan, C, N):
-        hid, h = self.mlp_vis[0].out_features, self.crossatt.h
-        types = (torch.bfloat16, torch.float16, torch.float32) if (self.fuse_fp32 and C <= 128) else (torch.bfloat16, torch.float16)
-        return (self.fuse_block and C <= self.fuse_max_c and plan.dtype in types and C % 64 == 0 and (C // h) % 8 == 0
-                and hid % 128 == 0 and self.mlp_vis[2].in_features == hid
-                and (plan.device.type != "cuda" or ops.dmff_fused_lds_bytes(C, N, h, plan.dtype) is not None)
-                and (plan.device.type == "cuda" or C <= 512))
-
     # wide levels, 16-bit types: three launches per iteration (ICAF_DMFF_WIDE=0: the seven per-layer launches, A/B switch)
     fuse_wide = OPT.dmff_wide
     res32 = OPT.dmff_res32        # loops > 1: the token stream between iterations in fp32 (A/B switch)
     wide_max_c = OPT.dmff_wide_max_c
 
-    def wide_fusable(self, plan, C):
-        hid, h = self.mlp_vis[0].out_features, self.crossatt.h
-        if plan.dtype == torch.float32 and not self.fuse_fp32:         # fp32 plans keep the per-layer launches unless the parity instantiation is asked for
-            return False
-        return (self.fuse_wide and self.fuse_block and self.fuse_max_c < C <= self.wide_max_c and ops.dmff_wide_ok(C, hid, plan.dtype)
-                and (C // h) % 8 == 0 and self.mlp_vis[2].in_features == hid)
+    BlockForm = collections.namedtuple("BlockForm", "form ksplit stream32")     # form: "two-launch" / "three-launch" / "per-layer"
+
+    def block_form(self, plan, C, N):
+        """THE decision how an iteration of this block runs at a level: the class switches above say what is wanted, ops.dmff_wide_ksplit which
+        hidden split is preferred, and the library (ops.dmff_block_forms, on every device) what is built.  A preferred or forced split that is
+        not built falls back to none; the fp32 token stream (loops > 1) is dropped where it is not built for the split."""
+        hid, h, dt = self.mlp_vis[0].out_features, self.crossatt.h, plan.dtype
+        per_layer = self.BlockForm("per-layer", 1, False)
+        # (fp32 plans keep the per-layer launches unless the parity instantiations are asked for)
+        if not self.fuse_block or self.mlp_vis[2].in_features != hid or (dt == torch.float32 and not self.fuse_fp32):
+            return per_layer
+        if C <= self.fuse_max_c:
+            return self.BlockForm("two-launch", 1, False) if ops.dmff_block_forms(dt, C, N, h, hid)[0] else per_layer
+        if self.fuse_wide and C <= self.wide_max_c:
+            ks = ops.dmff_wide_ksplit(N, C)                # few tokens per image, weights beyond an XCD's L2: hidden columns split over ks workgroups
+            s32 = bool(self.res32 and int(self.loops) > 1 and dt != torch.float32)
+            for form in dict.fromkeys(((ks, s32), (ks, False), (1, s32), (1, False))):
+                if ops.dmff_block_forms(dt, C, N, h, hid, *form)[1]:
+                    return self.BlockForm("three-launch", *form)
+        return per_layer
 
     def emit_tokens(self, plan, tok, B, N, final_out=None):
         """tok: (2, B*N, C) [0]=RGB [1]=IR -> same shape after `loops` shared-weight iterations.  final_out: optional
@@ -1014,67 +1021,56 @@ class CrossTransformerBlock(HipModule):
         C = tok.shape[2]
         rows = tok.shape[1]
         co, ln = p["co"], p["ln"]
-        hid = self.mlp_vis[0].out_features
+        hid, heads = self.mlp_vis[0].out_features, self.crossatt.h
         nloops = int(self.loops)
-        if self.fusable(plan, C, N):
-            # fused block (dmff_fused.hip): LayerNorm + QKV, then attention + out-projection + LayerNorm + MLP; attention output,
-            # x_att, the normalised tile and the hidden activations never reach HBM
-            coef = dict(co=co, hidden=hid)
+        form, ks, r32 = self.block_form(plan, C, N)
+        coef = dict(co=co, hidden=hid)
+        if nloops > 1 and (plan.dtype != torch.float32 or form == "three-launch"):
+            plan.notes.setdefault("dmff_fp32_token_stream", {})[f"C={C}"] = r32
+
+        def out(it):
+            return final_out if (final_out is not None and it == nloops - 1) else plan.tokens(2, rows, C)
+        # the buffers a fused form keeps across its iterations; x_att, the normalised tile and the hidden activations never reach HBM in either
+        if form != "per-layer":
             qkv = plan.tokens(2, rows, 3 * C)
-            for it in range(nloops):
-                plan.add(ops.dmff_ln_qkv(tok, qkv, p, ln, coef, p["eps"], B, N, self.crossatt.h))
-                nxt = final_out if (final_out is not None and it == nloops - 1) else plan.tokens(2, rows, C)
-                plan.add(ops.dmff_attn_mlp(tok, qkv, nxt, p, ln, coef, p["eps"], B, N, self.crossatt.h))
-                tok = nxt
-            if nloops > 1 and plan.dtype != torch.float32:
-                plan.notes.setdefault("dmff_fp32_token_stream", {})[f"C={C}"] = False
-            return tok
-        if self.wide_fusable(plan, C):
-            # wide levels (C = 256 / 512): LayerNorm + QKV, attention, out-projection + LayerNorm + MLP — three launches; x_att, the
-            # normalised tile and the hidden activations never reach HBM (dmff_wide.hip)
-            coef = dict(co=co, hidden=hid)
-            qkv = plan.tokens(2, rows, 3 * C)
+        if form == "three-launch":
             att = plan.tokens(2, rows, C)
-            ks = ops.dmff_wide_ksplit(N, C, hid)                   # few tokens per image, weights beyond an XCD's L2: hidden columns split over ks workgroups
             part = plan.empty((ks, 2, rows, C), torch.float32) if ks > 1 else None
             # several iterations: the residual chain x -> x_att -> x' is carried in FP32 from one iteration to the next (two ping-pong buffers); the
             # 16-bit tokens are still written (LayerNorm + QKV read them).  Rounding the stream to 16 bits twice per iteration had used up the parity
             # margin of the 3-iteration configuration (0.91 x the reference's own bf16 error)
-            r32 = self.res32 and nloops > 1 and plan.dtype != torch.float32 and ks in (1, 2) and not (C == 512 and ks == 1)      # (not built: dmff_wide.hip)
             t32 = [plan.empty((2, rows, C), torch.float32) for _ in range(2)] if r32 else None
-            if nloops > 1:
-                plan.notes.setdefault("dmff_fp32_token_stream", {})[f"C={C}"] = bool(r32)
-            # (the LAST iteration writes y32 too although nothing reads it — 2 * rows * C * 4 bytes, 3 % of the launch's traffic at P3: the kernels' R32
-            #  instantiation writes both token streams or neither, and a third instantiation for one launch in `loops` was not worth its compile time)
-            for it in range(nloops):
-                plan.add(ops.dmff_wide_ln_qkv(tok, qkv, p, ln, coef, p["eps"], B, N, self.crossatt.h))
-                plan.add(ops.cross_attention(qkv, att, B, N, self.crossatt.h))
-                nxt = final_out if (final_out is not None and it == nloops - 1) else plan.tokens(2, rows, C)
-                ls = ops.dmff_wide_proj_mlp(tok, att, nxt, p, ln, coef, p["eps"], B, N, self.crossatt.h, partial=part, ksplit=ks,
-                                            x32=(t32[(it - 1) & 1] if (r32 and it > 0) else None), y32=(t32[it & 1] if r32 else None))
-                for l in (ls if isinstance(ls, list) else [ls]):
-                    plan.add(l)
-                tok = nxt
-            return tok
-        if nloops > 1 and plan.dtype != torch.float32:
-            plan.notes.setdefault("dmff_fp32_token_stream", {})[f"C={C}"] = False
         for it in range(nloops):
-            n1 = plan.tokens(2, rows, C)
-            plan.add(ops.layernorm(tok, n1, ln["a1w"], ln["a1b"], ln["a2w"], ln["a2b"], p["eps"][0], name="ln_attn"))
-            qkv = plan.tokens(2, rows, 3 * C)
-            self._gemm(plan, n1, p["qkv"], qkv, C, 3 * C, ops.ACT_NONE, name="qkv_proj")
-            att = plan.tokens(2, rows, C)
-            plan.add(ops.cross_attention(qkv, att, B, N, self.crossatt.h))
-            xatt = plan.tokens(2, rows, C)
-            self._gemm(plan, att, p["out"], xatt, C, C, ops.ACT_NONE, res=tok, alpha_res=(co[0], co[2]),
-                       alpha_acc=(co[1], co[3]), name="out_proj")
-            n2 = plan.tokens(2, rows, C)
-            plan.add(ops.layernorm(xatt, n2, ln["mw"], ln["mb"], ln["mw"], ln["mb"], p["eps"][2], name="ln_mlp"))
-            h = plan.tokens(2, rows, hid)
-            self._gemm(plan, n2, p["fc1"], h, C, hid, ops.ACT_GELU, name="mlp_fc1")
-            nxt = final_out if (final_out is not None and it == nloops - 1) else plan.tokens(2, rows, C)
-            self._gemm(plan, h, p["fc2"], nxt, hid, C, ops.ACT_NONE, res=xatt, alpha_res=(co[4], co[6]),
-                       alpha_acc=(co[5], co[7]), name="mlp_fc2")
+            if form == "two-launch":         # dmff_fused.hip: LayerNorm + QKV, then attention + out-projection + LayerNorm + MLP
+                plan.add(ops.dmff_ln_qkv(tok, qkv, p, ln, coef, p["eps"], B, N, heads))
+                nxt = out(it)
+                plan.add(ops.dmff_attn_mlp(tok, qkv, nxt, p, ln, coef, p["eps"], B, N, heads))
+            elif form == "three-launch":     # dmff_wide.hip: LayerNorm + QKV, attention, out-projection + LayerNorm + MLP (+ the reduce of a hidden split)
+                plan.add(ops.dmff_wide_ln_qkv(tok, qkv, p, ln, coef, p["eps"], B, N, heads))
+                plan.add(ops.cross_attention(qkv, att, B, N, heads))
+                nxt = out(it)
+                # (the LAST iteration writes y32 too although nothing reads it — 2 * rows * C * 4 bytes, 3 % of the launch's traffic at P3: the kernels' R32
+                #  instantiation writes both token streams or neither, and a third instantiation for one launch in `loops` was not worth its compile time)
+                for l in ops.dmff_launches(True, True, tok, None, att, nxt, p, ln, coef, p["eps"], B, N, heads, "dmff_proj_mlp", part, ks,
+                                           x32=(t32[(it - 1) & 1] if (r32 and it > 0) else None), y32=(t32[it & 1] if r32 else None)):
+                    plan.add(l)
+            else:
+                n1 = plan.tokens(2, rows, C)
+                plan.add(ops.layernorm(tok, n1, ln["a1w"], ln["a1b"], ln["a2w"], ln["a2b"], p["eps"][0], name="ln_attn"))
+                qkv = plan.tokens(2, rows, 3 * C)
+                self._gemm(plan, n1, p["qkv"], qkv, C, 3 * C, ops.ACT_NONE, name="qkv_proj")
+                att = plan.tokens(2, rows, C)
+                plan.add(ops.cross_attention(qkv, att, B, N, heads))
+                xatt = plan.tokens(2, rows, C)
+                self._gemm(plan, att, p["out"], xatt, C, C, ops.ACT_NONE, res=tok, alpha_res=(co[0], co[2]),
+                           alpha_acc=(co[1], co[3]), name="out_proj")
+                n2 = plan.tokens(2, rows, C)
+                plan.add(ops.layernorm(xatt, n2, ln["mw"], ln["mb"], ln["mw"], ln["mb"], p["eps"][2], name="ln_mlp"))
+                h = plan.tokens(2, rows, hid)
+                self._gemm(plan, n2, p["fc1"], h, C, hid, ops.ACT_GELU, name="mlp_fc1")
+                nxt = out(it)
+                self._gemm(plan, h, p["fc2"], nxt, hid, C, ops.ACT_NONE, res=xatt, alpha_res=(co[4], co[6]),
+                           alpha_acc=(co[5], co[7]), name="mlp_fc2")
             tok = nxt
         return tok
 

@@ -716,13 +716,15 @@ def attn_stream(on=True):
     return _caller_knob("attn_stream", on)
 
 
-def dmff_fused_lds_bytes(C_, N, heads, dt):
-    """LDS bytes one icaf_dmff_attn_mlp workgroup needs for this shape, or None when the fused block kernels do not cover it."""
-    if dt not in (torch.bfloat16, torch.float16, torch.float32):      # (fp32: the parity instantiation, C <= 128)
-        return None
-    sz = C.c_size_t(0)
-    check(lib().icaf_dmff_attn_mlp_lds_bytes(int(C_), int(N), int(heads), dtype_code(dt), C.byref(sz)), "dmff_attn_mlp_lds_bytes")
-    return None if sz.value == C.c_size_t(-1).value or sz.value > 160 * 1024 else sz.value
+def dmff_block_forms(dt, C_, N, heads, hidden, ksplit=1, stream32=False):
+    """(two-launch form built, three-launch form built at this ksplit with / without the fp32 token stream) for one block shape: the verdict of
+    the library's own resolve and table lookup (icaf.h: icaf_dmff_block_forms — host code, asked on every device)."""
+    if dt not in (torch.bfloat16, torch.float16, torch.float32):
+        return False, False
+    two, three = C.c_int(0), C.c_int(0)
+    check(lib().icaf_dmff_block_forms(dtype_code(dt), int(C_), int(N), int(heads), int(hidden), int(ksplit), int(bool(stream32)),
+                                      C.byref(two), C.byref(three)), "dmff_block_forms")
+    return bool(two.value), bool(three.value)
 
 
 def _dmff_args(x, qkv, y, packs, ln, coef, eps, B, N, heads):
@@ -757,94 +759,80 @@ def _dmff_args(x, qkv, y, packs, ln, coef, eps, B, N, heads):
     return a
 
 
-def dmff_ln_qkv(x, qkv, packs, ln, coef, eps, B, N, heads, name="dmff_ln_qkv"):
-    """LayerNorm + the six Linear(C, C) projections of CrossAttention as one launch (icaf_dmff_ln_qkv)."""
-    a = _dmff_args(x, qkv, None, packs, ln, coef, eps, B, N, heads)
-    rows, Cc = x.shape[1], x.shape[2]
-    es = x.element_size()
-    return Launch(lib().icaf_dmff_ln_qkv, (C.byref(a),), keep=(a, x, qkv, packs, ln), name=name, flops=2.0 * 2 * rows * Cc * 3 * Cc,
-                  nbytes=2 * (rows * Cc * es + 3 * Cc * Cc * es + rows * 3 * Cc * es))
-
-
-def dmff_attn_mlp(x, qkv, y, packs, ln, coef, eps, B, N, heads, name="dmff_attn_mlp"):
-    """Crossed attention + out-projection + LayerNorm + MLP of one block iteration as one launch (icaf_dmff_attn_mlp)."""
-    a = _dmff_args(x, qkv, y, packs, ln, coef, eps, B, N, heads)
-    rows, Cc = x.shape[1], x.shape[2]
-    es, hid = x.element_size(), coef["hidden"]
-    flops = 2.0 * (B * heads * 4.0 * N * N * (Cc // heads)) + 2.0 * 2 * rows * (Cc * Cc + 2 * Cc * hid)
-    nbytes = 2 * (rows * 3 * Cc * es + 2 * rows * Cc * es + (Cc * Cc + 2 * Cc * hid) * es)
-    return Launch(lib().icaf_dmff_attn_mlp, (C.byref(a),), keep=(a, x, qkv, y, packs, ln), name=name, flops=flops, nbytes=nbytes)
-
-
-def dmff_wide_ok(C_, hidden, dt):
-    """The three-launch block kernels (dmff_wide.hip) cover this shape: C = 128 (four wavefronts, 128-channel passes) / 256 / 512 (eight,
-    256-channel passes), 16-bit types, hidden a multiple of the pass width."""
-    wpass = 128 if C_ == 128 else 256
-    es = 4 if dt == torch.float32 else 2
-    lds = 64 * (C_ * es + 16) + 64 * (wpass * es + 16) + 8 * 64 * 4 + hidden * 4
-    if dt == torch.float32:                          # the parity instantiation: C = 128 only (same code, fp32 MFMAs, erff)
-        return C_ == 128 and hidden % wpass == 0 and lds <= 160 * 1024
-    return dt in (torch.bfloat16, torch.float16) and C_ in (128, 256, 512) and hidden % wpass == 0 and lds <= 160 * 1024
-
-
 def _wide_packs(packs):
     """packs with fragment-major weight copies (frag_weights: cached per packed tensor) — what the dmff_wide kernels read"""
     return {k: ((frag_weights(v[0]), v[1], v[2]) if k in ("qkv", "out", "fc1", "fc2") else v) for k, v in packs.items()}
 
 
-def dmff_wide_ln_qkv(x, qkv, packs, ln, coef, eps, B, N, heads, name="dmff_ln_qkv"):
-    """LayerNorm + the six Linear(C, C) projections, wide levels (icaf_dmff_wide_ln_qkv)."""
-    wp = _wide_packs(packs)
-    a = _dmff_args(x, qkv, None, wp, ln, coef, eps, B, N, heads)
-    a.reserved = OPT.dmff_qkv_npass                      # output-channel passes per workgroup: 0 = automatic (icaf.h)
+def dmff_launches(mlp, wide, x, qkv, att, y, packs, ln, coef, eps, B, N, heads, name, partial=None, ksplit=1, x32=None, y32=None):
+    """The launches of one half of a block iteration, as a list — mlp False: LayerNorm + the six Linear(C, C) projections; True: out-projection +
+    LayerNorm + MLP (two-launch form: with the crossed attention in front, in the same launch).  wide: the three-launch kernels, which read
+    fragment-major weights; ksplit > 1 splits the hidden columns over ksplit workgroups per tile (partial: fp32 (ksplit, 2, rows, C) scratch)
+    and a second small launch reduces the partial sums.  x32 / y32: the fp32 token stream across iterations (icaf.h: icaf_dmff_args)."""
+    L = lib()
     rows, Cc = x.shape[1], x.shape[2]
-    es = x.element_size()
-    return Launch(lib().icaf_dmff_wide_ln_qkv, (C.byref(a),), keep=(a, x, qkv, wp, packs, ln), name=name, flops=2.0 * 2 * rows * Cc * 3 * Cc,
-                  nbytes=2 * (rows * Cc * es + 3 * Cc * Cc * es + rows * 3 * Cc * es))
-
-
-def dmff_wide_ksplit(N, C_, hidden):
-    """Hidden-column split of icaf_dmff_wide_proj_mlp_split for a level: 2 where a modality's weights (9 C^2 16-bit elements) overflow an
-    XCD's 4 MB L2 AND the level has few tokens per image (N <= 128: P5 of yolov5s — 100 tokens, i.e. 100 tiles of 64 rows for 256 CUs at
-    batch 32, 4.7 MB of weights per modality), else 1.  Deliberately a function of the LEVEL (N, C), never of the batch size: the split
-    changes the fp32 association of the fc2 sum, and a shard of a batch must reproduce the same rows of the full batch bit for bit
-    (tests/test_gpu_fullsize.py; yolov5l's P4 — C = 512, N = 256, one tile per CU at batch 32 — measured slower with the split anyway)."""
-    if C_ < 256:
-        return 1                                     # icaf_dmff_wide_proj_mlp_split is built for the 256-channel passes (C = 256 / 512) only
-    if OPT.dmff_ksplit:
-        return OPT.dmff_ksplit if hidden % (256 * OPT.dmff_ksplit) == 0 else 1
-    return 2 if (9 * C_ * C_ * 2 > 3 * 2 ** 20 and N <= 128 and hidden % 512 == 0) else 1
-
-
-def dmff_wide_proj_mlp(x, att, y, packs, ln, coef, eps, B, N, heads, name="dmff_proj_mlp", partial=None, ksplit=1, x32=None, y32=None):
-    """Out-projection + LayerNorm + MLP of one block iteration as one launch behind cross_attention (icaf_dmff_wide_proj_mlp); with
-    ksplit > 1 (partial: fp32 (ksplit, 2, rows, C) scratch) the hidden columns are split over ksplit workgroups per tile and a second
-    small launch reduces the partial sums: returns the LIST [icaf_dmff_wide_proj_mlp_split, icaf_dmff_wide_reduce]."""
-    rows, Cc = x.shape[1], x.shape[2]
-    assert att.shape == (2, rows, Cc) and att.is_contiguous() and att.dtype == x.dtype
-    wp = _wide_packs(packs)
-    a = _dmff_args(x, None, y, wp, ln, coef, eps, B, N, heads)
     es, hid = x.element_size(), coef["hidden"]
+    wp = _wide_packs(packs) if wide else packs
+    a = _dmff_args(x, qkv, y, wp, ln, coef, eps, B, N, heads)
+    keep = (a, x, qkv, att, y, wp, packs, ln, partial, x32, y32)
+    if not mlp:
+        if wide:
+            a.reserved = OPT.dmff_qkv_npass                  # output-channel passes per workgroup: 0 = automatic (icaf.h)
+        return [Launch(L.icaf_dmff_wide_ln_qkv if wide else L.icaf_dmff_ln_qkv, (C.byref(a),), keep=keep, name=name, flops=2.0 * 2 * rows * Cc * 3 * Cc,
+                       nbytes=2 * (rows * Cc * es + 3 * Cc * Cc * es + rows * 3 * Cc * es))]
     flops = 2.0 * 2 * rows * (Cc * Cc + 2 * Cc * hid)
-    nbytes = 2 * (3 * rows * Cc * es + (Cc * Cc + 2 * Cc * hid) * es)
-    if y32 is not None:                # fp32 residual stream across the block's iterations (icaf.h: icaf_dmff_args.x32 / y32)
-        for t in (x32, y32):
-            assert t is None or (t.dtype == torch.float32 and t.shape == (2, rows, Cc) and t.is_contiguous())
+    wbytes = (Cc * Cc + 2 * Cc * hid) * es
+    if not wide:
+        return [Launch(L.icaf_dmff_attn_mlp, (C.byref(a),), keep=keep, name=name, flops=2.0 * (B * heads * 4.0 * N * N * (Cc // heads)) + flops,
+                       nbytes=2 * (rows * 3 * Cc * es + 2 * rows * Cc * es + wbytes))]
+    assert att.shape == (2, rows, Cc) and att.is_contiguous() and att.dtype == x.dtype
+    nbytes = 2 * (3 * rows * Cc * es + wbytes)
+    for t in (x32, y32):
+        assert t is None or (y32 is not None and t.dtype == torch.float32 and t.shape == (2, rows, Cc) and t.is_contiguous())
+    if y32 is not None:
         a.y32 = y32.data_ptr()
         a.x32 = x32.data_ptr() if x32 is not None else None
         nbytes += (2 if x32 is not None else 1) * 2 * rows * Cc * 4
-    else:
-        assert x32 is None
-    if ksplit > 1:
-        assert partial is not None and partial.dtype == torch.float32 and partial.is_contiguous() and partial.shape == (ksplit, 2, rows, Cc)
-        flops += 2.0 * 2 * rows * Cc * Cc * (ksplit - 1)                         # the repeated out-projection
-        nbytes += partial.numel() * 4
-        main = Launch(lib().icaf_dmff_wide_proj_mlp_split, (C.byref(a), att.data_ptr(), partial.data_ptr(), int(ksplit)),
-                      keep=(a, x, att, y, wp, packs, ln, partial, x32, y32), name=name, flops=flops, nbytes=nbytes)
-        red = Launch(lib().icaf_dmff_wide_reduce, (C.byref(a), partial.data_ptr(), int(ksplit)), keep=(a, y, partial, wp, packs, y32),
-                     name=name + "_reduce", nbytes=partial.numel() * 4 + 2 * 2 * rows * Cc * es)
-        return [main, red]
-    return Launch(lib().icaf_dmff_wide_proj_mlp, (C.byref(a), att.data_ptr()), keep=(a, x, att, y, wp, packs, ln, x32, y32), name=name, flops=flops, nbytes=nbytes)
+    if ksplit == 1:
+        return [Launch(L.icaf_dmff_wide_proj_mlp, (C.byref(a), att.data_ptr()), keep=keep, name=name, flops=flops, nbytes=nbytes)]
+    assert partial is not None and partial.dtype == torch.float32 and partial.is_contiguous() and partial.shape == (ksplit, 2, rows, Cc)
+    return [Launch(L.icaf_dmff_wide_proj_mlp_split, (C.byref(a), att.data_ptr(), partial.data_ptr(), int(ksplit)), keep=keep, name=name,
+                   flops=flops + 2.0 * 2 * rows * Cc * Cc * (ksplit - 1),                         # the repeated out-projection
+                   nbytes=nbytes + partial.numel() * 4),
+            Launch(L.icaf_dmff_wide_reduce, (C.byref(a), partial.data_ptr(), int(ksplit)), keep=keep, name=name + "_reduce",
+                   nbytes=partial.numel() * 4 + 2 * 2 * rows * Cc * es)]
+
+
+def dmff_ln_qkv(x, qkv, packs, ln, coef, eps, B, N, heads, name="dmff_ln_qkv"):
+    """LayerNorm + the six Linear(C, C) projections of CrossAttention as one launch (icaf_dmff_ln_qkv)."""
+    return dmff_launches(False, False, x, qkv, None, None, packs, ln, coef, eps, B, N, heads, name)[0]
+
+
+def dmff_attn_mlp(x, qkv, y, packs, ln, coef, eps, B, N, heads, name="dmff_attn_mlp"):
+    """Crossed attention + out-projection + LayerNorm + MLP of one block iteration as one launch (icaf_dmff_attn_mlp)."""
+    return dmff_launches(True, False, x, qkv, None, y, packs, ln, coef, eps, B, N, heads, name)[0]
+
+
+def dmff_wide_ln_qkv(x, qkv, packs, ln, coef, eps, B, N, heads, name="dmff_ln_qkv"):
+    """LayerNorm + the six Linear(C, C) projections, three-launch form (icaf_dmff_wide_ln_qkv)."""
+    return dmff_launches(False, True, x, qkv, None, None, packs, ln, coef, eps, B, N, heads, name)[0]
+
+
+def dmff_wide_proj_mlp(x, att, y, packs, ln, coef, eps, B, N, heads, name="dmff_proj_mlp", partial=None, ksplit=1, x32=None, y32=None):
+    """Out-projection + LayerNorm + MLP of one block iteration behind cross_attention: one launch (icaf_dmff_wide_proj_mlp), or with ksplit > 1
+    the LIST [icaf_dmff_wide_proj_mlp_split, icaf_dmff_wide_reduce] — the shape the kernel tests call it by; plans take dmff_launches' list."""
+    ls = dmff_launches(True, True, x, None, att, y, packs, ln, coef, eps, B, N, heads, name, partial, ksplit, x32, y32)
+    return ls if ksplit > 1 else ls[0]
+
+
+def dmff_wide_ksplit(N, C_):
+    """The hidden-column split PREFERRED for a level (what is built is the library's business: CrossTransformerBlock.block_form asks it): 2 where
+    a modality's weights (9 C^2 16-bit elements) overflow an XCD's 4 MB L2 AND the level has few tokens per image (N <= 128: P5 of yolov5s — 100
+    tokens, i.e. 100 tiles of 64 rows for 256 CUs at batch 32, 4.7 MB of weights per modality), else 1.  Deliberately a function of the LEVEL
+    (N, C), never of the batch size: the split changes the fp32 association of the fc2 sum, and a shard of a batch must reproduce the same rows
+    of the full batch bit for bit (tests/test_gpu_fullsize.py; yolov5l's P4 — C = 512, N = 256, one tile per CU at batch 32 — measured slower
+    with the split anyway).  ICAF_OPTIONS=dmff_ksplit=n forces n."""
+    return OPT.dmff_ksplit or (2 if (9 * C_ * C_ * 2 > 3 * 2 ** 20 and N <= 128) else 1)
 
 
 def dmff_upsample_merge(tokens, fea_rgb, fea_ir, out, th, tw, name="dmff_upsample_merge"):

@@ -367,8 +367,8 @@ typedef struct icaf_dmff_args {
 } icaf_dmff_args;
 int icaf_dmff_ln_qkv(ICAF_HOST const icaf_dmff_args* a, icaf_stream_t s);
 int icaf_dmff_attn_mlp(ICAF_HOST const icaf_dmff_args* a, icaf_stream_t s);
-/* The block for the WIDE levels (C = 256 or 512, 16-bit types; dmff_wide.hip): one iteration = icaf_dmff_wide_ln_qkv,
- * icaf_cross_attention, icaf_dmff_wide_proj_mlp.
+/* The three-launch block (dmff_wide.hip: C = 128, 256 or 512 in the 16-bit types, and the fp32 parity build at C = 128): one iteration =
+ * icaf_dmff_wide_ln_qkv, icaf_cross_attention, icaf_dmff_wide_proj_mlp.
  *   icaf_dmff_wide_ln_qkv    as icaf_dmff_ln_qkv (LayerNorm :661-662 + the six projections :664-669);
  *   icaf_dmff_wide_proj_mlp  out-projection + coefficient mix (:682-685, :745-746), the shared LayerNorm (:749-750), MLP + mix
  *                            (:704-709, :751-752) of 64 token rows per workgroup; att = the attention output tokens [2][B*N][C]
@@ -387,6 +387,13 @@ int icaf_dmff_wide_proj_mlp(ICAF_HOST const icaf_dmff_args* a, const void* att, 
 int icaf_dmff_wide_proj_mlp_split(ICAF_HOST const icaf_dmff_args* a, const void* att, float* partial, int ksplit, icaf_stream_t s);
 int icaf_dmff_wide_reduce(ICAF_HOST const icaf_dmff_args* a, const float* partial, int ksplit, icaf_stream_t s);
 int icaf_dmff_attn_mlp_lds_bytes(int C, int N, int heads, int dtype, ICAF_HOST size_t* bytes);
+/* Which forms of a block iteration are built for a shape.  Pure host code (no HIP call: usable without a GPU) that runs the resolve and the
+ * table lookup of the launches themselves, so a form reported here is a form the entry points above launch, and one refused here they refuse
+ * with ICAF_ERR_UNSUPPORTED.  *two_launch: icaf_dmff_ln_qkv + icaf_dmff_attn_mlp cover (dtype, C, N, heads, hidden), the 160 KiB LDS limit
+ * included.  *three_launch: icaf_dmff_wide_ln_qkv + icaf_cross_attention + icaf_dmff_wide_proj_mlp (ksplit = 1) or _split + icaf_dmff_wide_reduce
+ * (ksplit = 2 / 4) are built for it, stream32 != 0: with the fp32 token stream (x32 / y32). */
+int icaf_dmff_block_forms(int dtype, int C, int N, int heads, int hidden, int ksplit, int stream32, ICAF_HOST int* two_launch,
+                          ICAF_HOST int* three_launch);
 
 /* ---- test-time augmentation (models/yolo_test.py:116-131, utils/torch_utils.py:257-267) ---------------------
  * Model.forward(augment=True) runs three passes, (scale, flip) = (1, -), (0.83, left-right), (0.67, -), and concatenates their decoded

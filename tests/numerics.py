@@ -870,7 +870,7 @@ LN_EPS_EXACT = 0.75                                  # 1 - s^2 for deviations of
 DMFF_ROWS = (64, 33, 154, 321)                       # one tile; one row in the second 32-row half; a last tile of 26 rows (second half empty);
 DMFF_ROWS_MAX = 321                                  # six tiles: a second group of eight workgroups, one tile per eight under ksplit = 4
 W2_NNZ = 32
-# (C, dtype, ksplit, r32): every build dispatch_wide_proj_mlp, dispatch_wide_split and launch_wide_reduce can reach
+# (C, dtype, ksplit, r32): every build WIDE_ROWS of dmff_wide.hip holds for the out-projection + MLP launch and its reduce
 DMFF_CELLS = ([(128, dt, 1, False) for dt in (BF16, F16, F32)] + [(C, dt, 1, False) for C in (256, 512) for dt in (BF16, F16)] +
               [(C, dt, 1, True) for C in (128, 256) for dt in (BF16, F16)] +
               [(C, dt, ks, False) for C in (256, 512) for dt in (BF16, F16) for ks in (2, 4)] +

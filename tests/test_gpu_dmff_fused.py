@@ -24,7 +24,7 @@ def make_block(C, heads, loops, seed):
 
 
 def run_block(blk, tok, B, N, dtype, fused, max_c=512, res32=True):
-    blk.fuse_block, blk.fuse_max_c = fused, max_c        # (the plan uses the two-launch kernels up to C = 128 by default; they are built to 512)
+    blk.fuse_block, blk.fuse_max_c = fused, max_c        # (the plan uses the two-launch kernels up to C = 64 by default; they are built to 512)
     blk.res32 = res32                                     # loops > 1, three-launch form: fp32 token stream between iterations (round 5)
     blk.fuse_fp32 = fused                                 # fp32: the parity instantiation of the same template (C <= 128)
     blk.invalidate()

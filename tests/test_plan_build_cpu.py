@@ -100,10 +100,13 @@ def test_dmff_block_launch_structure_at_every_level(loops):
     assert blocks[0] == ["dmff_ln_qkv", "cross_attention", "dmff_proj_mlp"] * loops          # (round 4: the four-wavefront build at C = 128)
     assert blocks[1] == ["dmff_ln_qkv", "cross_attention", "dmff_proj_mlp"] * loops
     assert blocks[2] == ["dmff_ln_qkv", "cross_attention", "dmff_proj_mlp", "dmff_proj_mlp_reduce"] * loops
-    from icafusion_amd import ops
-    assert ops.dmff_wide_ksplit(100, 512, 2048) == 2                                                      # P5 of yolov5s — at every batch size
-    assert ops.dmff_wide_ksplit(256, 256, 1024) == 1 and ops.dmff_wide_ksplit(256, 512, 2048) == 1        # P4 of yolov5s / yolov5l
+    from icafusion_amd.engine import Plan
     from icafusion_amd.models.common import CrossTransformerBlock
+
+    def ksplit(N, C):           # the split block_form settles on for a (C, 8 heads, hidden 4C) block: preference and library verdict together
+        return CrossTransformerBlock(C, C, C, 8, 4, 0.1, 0.1).eval().block_form(Plan("cpu", torch.bfloat16), C, N).ksplit
+    assert ksplit(100, 512) == 2                                                      # P5 of yolov5s — at every batch size
+    assert ksplit(256, 256) == 1 and ksplit(256, 512) == 1                            # P4 of yolov5s / yolov5l
     try:
         CrossTransformerBlock.fuse_wide = False                  # A/B switch: the wide levels fall back to the per-layer launches
         plain = _dmff_launches(names(m.build_plan(2, 320, 320, "cpu", torch.bfloat16)))
@@ -143,9 +146,12 @@ def test_resident_patch_kernel_shape_table():
     for bad in ((1, 1, 1, 1, 0, 0, 128, 128), (3, 3, 1, 1, 1, 1, 128, 64), (3, 3, 1, 1, 1, 1, 256, 256), (3, 3, 1, 1, 0, 0, 128, 128),
                 (3, 3, 2, 1, 1, 1, 64, 128), (3, 3, 2, 2, 1, 1, 32, 128), (3, 3, 1, 1, 1, 1, 64, 128)):
         assert s(*bad) == []
-    assert ops.dmff_wide_ok(256, 1024, torch.bfloat16) and ops.dmff_wide_ok(512, 2048, torch.float16)
-    assert ops.dmff_wide_ok(128, 512, torch.bfloat16) and not ops.dmff_wide_ok(384, 1536, torch.bfloat16) and not ops.dmff_wide_ok(1024, 4096, torch.bfloat16)
-    assert not ops.dmff_wide_ok(256, 1024, torch.float32) and not ops.dmff_wide_ok(512, 2048 + 128, torch.bfloat16)
+
+    def wide_ok(C, hidden, dt):          # the three-launch DMFF block, unsplit, 16-bit token stream: the library's verdict (icaf_dmff_block_forms)
+        return ops.dmff_block_forms(dt, C, 256, 8, hidden)[1]
+    assert wide_ok(256, 1024, torch.bfloat16) and wide_ok(512, 2048, torch.float16)
+    assert wide_ok(128, 512, torch.bfloat16) and not wide_ok(384, 1536, torch.bfloat16) and not wide_ok(1024, 4096, torch.bfloat16)
+    assert not wide_ok(256, 1024, torch.float32) and not wide_ok(512, 2048 + 128, torch.bfloat16)
 
 
 def test_c3_tail_launch_configurations_follow_the_map_size():

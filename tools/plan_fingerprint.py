@@ -93,6 +93,7 @@ YAMLS = ["yolov5n_Transfusion_kaist.yaml", "yolov5s_Transfusion_kaist.yaml", "yo
          "yolov5_ResNet50_NiNfusion_kaist.yaml", "yolov5s_Transfusion_kaist_loops3.yaml"]
 DTYPES = {"bf16": torch.bfloat16, "fp16": torch.float16, "fp32": torch.float32}
 S, V, R = "yolov5s_Transfusion_kaist.yaml", "yolov5_VGG16_Transfusion_kaist.yaml", "yolov5_ResNet50_Transfusion_kaist.yaml"
+N5, M5, L5 = "yolov5n_Transfusion_kaist.yaml", "yolov5m_Transfusion_kaist.yaml", "yolov5l_Transfusion_VEDAI.yaml"
 CTB = common.CrossTransformerBlock
 U8, UNPAIRED = ("u8", {"u8": True}, {}, [], None), ("pair_streams=False", {}, {"pair_streams": False}, [], None)
 # (name, yaml, dtype, (B, H, W), build_plan keywords, Model attributes, class-level switches, loops of the DMFF rows)
@@ -110,7 +111,16 @@ MATRIX = [(f"{y[:-5]}/{d}", y, d, SHAPE, {}, {}, [], None) for y in YAMLS for d 
              ("loops=3", {}, {}, [], 3)]),
         (V, [U8, UNPAIRED, ("fuse_stem=True", {}, {}, [(common.VGGblock, "fuse_stem", True)], None)]),
         (R, [U8, UNPAIRED])] for tag, kw, attrs, sw, loops in variants] + [
-    (f"{y[:-5]}/bf16/{SHAPE2[1]}x{SHAPE2[2]}", y, "bf16", SHAPE2, {}, {}, [], None) for y in (S, V, R)]
+    (f"{y[:-5]}/bf16/{SHAPE2[1]}x{SHAPE2[2]}", y, "bf16", SHAPE2, {}, {}, [], None) for y in (S, V, R)] + [
+    # the forms of the DMFF block (CrossTransformerBlock.block_form): C = 64 ... 1024 with and without iterations (yolov5l's P4 is the C = 512,
+    # ksplit = 1 case), the fp32 parity builds, and every class switch; run once per ICAF_OPTIONS=dmff_ksplit=1 / 2 / 4 for the forced splits
+    (f"{y[:-5]}/{d}/{tag}", y, d, SHAPE, {}, {}, sw, loops) for y, d, tag, sw, loops in [
+        (S, "fp32", "fuse_fp32=True", [(CTB, "fuse_fp32", True)], None),
+        (N5, "fp32", "fuse_fp32=True", [(CTB, "fuse_fp32", True)], None),
+        (S, "bf16", "res32=False,loops=3", [(CTB, "res32", False)], 3),
+        (N5, "bf16", "loops=3", [], 3), (M5, "bf16", "loops=3", [], 3), (L5, "bf16", "loops=3", [], 3),
+        (S, "bf16", "wide_max_c=128", [(CTB, "wide_max_c", 128)], None),
+        (S, "bf16", "fuse_block=False", [(CTB, "fuse_block", False)], None)]]
 
 
 @contextlib.contextmanager
