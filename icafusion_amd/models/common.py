@@ -10,7 +10,6 @@ There is deliberately no PyTorch / CPU fallback: calling a module with CPU tenso
 libicaf.so raises.
 """
 import collections
-import functools
 import math
 
 import torch
@@ -193,6 +192,110 @@ class HipModule(nn.Module):
 # ----------------------------------------------------------------------------------------------------------
 # convolution family
 # ----------------------------------------------------------------------------------------------------------
+def act_code(act):
+    """ops.ACT_* of the torch activation module behind a convolution."""
+    for kind, code in ((nn.SiLU, ops.ACT_SILU), (nn.Identity, ops.ACT_NONE), (nn.GELU, ops.ACT_GELU)):
+        if isinstance(act, kind):
+            return code
+    raise NotImplementedError(f"activation {type(act).__name__} is outside the hot path")
+
+
+def is_conv(k, kernel, stride=None, padding=None):
+    """Is the nn.Conv2d k a plain (groups 1, undilated) kernel x kernel window — of this stride, this padding, where given?"""
+    return (k.kernel_size == (kernel, kernel) and k.groups == 1 and k.dilation == (1, 1) and (stride is None or k.stride == (stride, stride))
+            and (padding is None or _pair(k.padding) == (padding, padding)))
+
+
+def silu16(plan, *convs):
+    """The condition every fused form shares: a 16-bit plan, and these Convs end in SiLU."""
+    return plan.dtype in (torch.bfloat16, torch.float16) and all(isinstance(c.act, nn.SiLU) for c in convs)
+
+
+class Chained(collections.namedtuple("Chained", "convs twins y keep x2", defaults=(None, None, False, None))):
+    """1x1 SiLU Convs riding on another launch's output tile, from C3.emit down to ops.conv2d / ops.bottleneck.  convs: the Convs, their outputs
+    concatenated (a C3's cv1 | cv2); twins: their counterparts of the other stream; y: what they write.  keep: the carrying layer's own output
+    (residual included) is written too and the 1x1 consumes it as stored (a Bottleneck's 3x3 followed by the next Bottleneck's 1x1) — otherwise
+    only y is written.  x2: the chained Conv reads cat(the carrying layer's output, x2) (a C3's last Bottleneck carrying cv3, x2 = cv2's output)."""
+    __slots__ = ()
+
+    def launch_form(self, plan, paired, swap_halves=False):
+        """-> ops.Chain: the same record with the Convs replaced by their packed weights."""
+        tw = self.twins if paired else None
+        w, kp, b = self.convs[0].packed(plan, tw[0] if tw else None, self.convs[1:], tw[1:] if tw else (), swap_halves=swap_halves)
+        return ops.Chain(w, kp, b, self.y, sum(c.conv.out_channels for c in self.convs), self.keep, self.x2)
+
+
+class Lead(collections.namedtuple("Lead", "conv twin stem stem_twin", defaults=(None, None, None))):
+    """A deferred row of the plan builder: the down-sampling Conv (and its twin) whose launch the C3 behind it emits, cv1 | cv2 chained on its
+    output tile; with `stem` the image-fed 6x6 / s2 Conv in front of it as well (icaf_stem2: rows 0-2a as one launch)."""
+    __slots__ = ()
+
+    @property
+    def from_image(self):
+        return self.stem is not None
+
+
+def check_conv(plan, k, who, c1=None, got=None):
+    """What a convolution launch refuses, stated once: groups and dilation, and — for an act of `got` channels where the launch reads c1 —
+    another channel count (ValueError) or a width that is no whole number of 16-byte vectors.  emit_conv runs it before it allocates or
+    appends anything; an emitter of several launches runs it up front for the widths inside, so that it refuses before its first launch."""
+    if k.groups != 1 or k.dilation != (1, 1):
+        raise NotImplementedError("grouped / dilated convolutions are outside the hot path")
+    if got is not None and got != c1:
+        raise ValueError(f"{who} expects {c1} input channels, got {got}")
+    if got is not None and c1 % ops.VEC[plan.dtype]:
+        raise NotImplementedError(f"channel count {c1} must be a multiple of {ops.VEC[plan.dtype]} for dtype {plan.dtype}")
+
+
+def emit_conv(plan, owner, x, streams, act, name, out=None, res=None, res_pre_act=False, pre_term=None, pre_nearest=False, swap_halves=False,
+              cin_slice=None, chain=None, s2d=False):
+    """Append ONE convolution launch (icaf_conv2d): nn.Conv2d [+ BatchNorm2d] + activation `act` over the act / pair act / ImageIn x.
+    name: the launch's name; {kh} {kw} {sh} are filled in from the window launched.
+    streams: per stream the (Conv2d, BatchNorm2d or None) pairs whose outputs are concatenated along Cout (HipModule.packed_convs); two
+          streams: x / out / res are pair acts and the launch has groups = 2.  owner: the module whose cache holds the packed weights.
+    An ImageIn is staged first (stage_image: NHWC, channels padded to whole vectors; s2d: in space-to-depth form, its 6x6 / s2 / p2 window
+          then running as 3x3 / s1 / p1 over four times the channels).
+    out: allocated when None.  res / res_pre_act: residual behind / in front of the activation (ops.conv2d).  pre_term: fp32 coarse map
+          (B, h, w, Cout) added, bilinearly resized (pre_nearest: nearest), before bias + activation (icaf.h).
+    cin_slice: (k0, k1) — use only these input-channel columns of the weights (x then has k1 - k0 channels): the full-resolution half of
+          a 1x1 conv over cat(up(a), b), whose other half arrives as the nearest pre_term.
+    swap_halves: x holds the two halves of the layer's input channels in swapped order (C3 after an odd number of fused Bottlenecks):
+          the weight columns are swapped to match when they are packed.
+    chain: Chained — its 1x1s run on this launch's output tile; -> chain.y, or `out` when chain.keep."""
+    k = streams[0][0][0]
+    (kh, kw), (sh, sw), (ph, pw), c1 = k.kernel_size, k.stride, _pair(k.padding), k.in_channels
+    assert all((e.kernel_size, e.stride, _pair(e.padding), e.in_channels) == ((kh, kw), (sh, sw), (ph, pw), c1) for s in streams for e, _ in s), \
+        "fused convs must share geometry"
+    c2 = sum(e.out_channels for e, _ in streams[0])
+    paired = len(streams) == 2
+    who = f"{type(owner).__name__} ({name})"
+    transform = cin_pad = None
+    if isinstance(x, ImageIn):
+        assert x.pair == paired and cin_slice is None
+        check_conv(plan, k, who)
+        x, c1 = stage_image(plan, x, c1, s2d)
+        cin_pad = c1
+        if s2d:                           # 6x6/s2/p2 over the image == 3x3/s1/p1 over space-to-depth(image)
+            transform, (kh, kw, sh, sw, ph, pw) = ops.s2d_conv_weight, (3, 3, 1, 1, 1, 1)
+    else:
+        assert (x.dim() == 5) == paired and not s2d
+        if cin_slice is not None:
+            assert (kh, kw) == (1, 1) and not swap_halves and 0 <= cin_slice[0] < cin_slice[1] <= c1
+            c1 = cin_slice[1] - cin_slice[0]
+        check_conv(plan, k, who, c1, x.shape[-1])
+    wp, kp, bp = owner.packed_convs(plan, streams, swap_halves, cin_slice, transform, cin_pad)
+    B, H, W = x.shape[-4:-1]
+    Ho, Wo = conv_out(H, kh, sh, ph), conv_out(W, kw, sw, pw)
+    if out is None:                       # (also in front of a chain that writes only chain.y: the order plans number their buffers in)
+        out = plan.act(B, Ho, Wo, c2, pair=paired)
+    ch = None if chain is None else chain.launch_form(plan, paired)
+    if ch is not None and not ch.keep:
+        out = ch.y[..., :c2] if ch.y.shape[-1] >= c2 else plan.act(B, Ho, Wo, c2, pair=paired)   # (y is ignored by the kernel)
+    plan.add(ops.conv2d(x, wp, kp, bp, out, kh, kw, sh, sw, ph, pw, c1, c2, act, res=res, res_pre_act=res_pre_act, pre=pre_term,
+                        pre_nearest=pre_nearest, chain=ch, name=name.format(kh=kh, kw=kw, sh=sh)))
+    return out if ch is None or ch.keep else ch.y
+
+
 class Conv(HipModule):
     """Conv2d(bias=False) + BatchNorm2d + SiLU (reference models/common.py:48-60).  On the device this is one
     implicit-GEMM launch with BN folded into the packed weights (as utils/torch_utils.py:182-202 does offline) and
@@ -209,15 +312,6 @@ class Conv(HipModule):
     def fuseforward(self, x):           # kept for API parity with Model.fuse(); same device path
         return self.forward(x)
 
-    def _act_code(self):
-        if isinstance(self.act, nn.SiLU):
-            return ops.ACT_SILU
-        if isinstance(self.act, nn.Identity):
-            return ops.ACT_NONE
-        if isinstance(self.act, nn.GELU):
-            return ops.ACT_GELU
-        raise NotImplementedError(f"activation {type(self.act).__name__} is outside the hot path")
-
     def folded(self):
         """fp32 (weight, bias) with BatchNorm folded in."""
         return fold_bn(self.conv, getattr(self, "bn", None))
@@ -227,119 +321,72 @@ class Conv(HipModule):
     def out_shape(self, src):
         return conv2d_shape(self.conv, src[1], src[2])
 
+    def _streams(self, twin=None, also=(), twin_also=()):
+        """packed_convs' / emit_conv's per-stream lists: this layer, `also` appended along Cout; with `twin` the other stream's as well."""
+        assert len(twin_also) == (len(also) if twin is not None else 0)
+        streams = [(self,) + tuple(also)] + ([(twin,) + tuple(twin_also)] if twin is not None else [])
+        return [[(c.conv, getattr(c, "bn", None)) for c in convs] for convs in streams]
+
     def packed(self, plan, twin=None, also=(), twin_also=(), swap_halves=False, cin_slice=None, transform=None, cin_pad=None):
         """-> (wp, kp, bp), the launch form of this layer's weights: BN folded, `also` appended along Cout, the K halves swapped /
         the K columns cin_slice kept, `transform` (ops.s2d_conv_weight) applied, Cin padded to cin_pad, cast to plan.dtype; with
         `twin` the two streams stacked.  Packed once per distinct set of arguments (HipModule.packed_convs, cached on self)."""
-        assert len(twin_also) == (len(also) if twin is not None else 0)
-        streams = [(self,) + tuple(also)] + ([(twin,) + tuple(twin_also)] if twin is not None else [])
-        return self.packed_convs(plan, [[(c.conv, getattr(c, "bn", None)) for c in convs] for convs in streams], swap_halves, cin_slice,
-                                 transform, cin_pad)
+        return self.packed_convs(plan, self._streams(twin, also, twin_also), swap_halves, cin_slice, transform, cin_pad)
 
     def emit(self, plan, x, out=None, res=None, twin=None, also=(), twin_also=(), pre_term=None, swap_halves=False,
              chain=None, pre_nearest=False, cin_slice=None):
-        """Append this layer's launch.
+        """Append this layer's launch (emit_conv).
 
         twin: the structurally identical Conv of the other backbone stream — x / out / res are then pair acts
               (2, B, H, W, C) and both streams run as ONE groups=2 launch with per-stream weights.
         also: further Convs with the same geometry and activation reading the same input (C3's cv1 and cv2): their
               output channels are appended to this layer's, one GEMM with N = sum of the widths (twin_also: the
               twin stream's counterparts).
-        pre_term: fp32 coarse map (B, h, w, Cout) added, bilinearly resized (pre_nearest: nearest), before bias + activation
-              (icaf.h).
-        cin_slice: (k0, k1) — use only these input-channel columns of the weights (x then has k1 - k0 channels): the
-              full-resolution half of a 1x1 conv over cat(up(a), b), whose other half arrives as the nearest pre_term.
-        chain: (convs, twin_convs, y2[, keep[, x2]]) — 1x1 SiLU Convs (their outputs concatenated, e.g. the cv1 | cv2 of the C3
-              behind a down-sampling Conv) applied to this layer's output tile inside the same launch; only y2 is written —
-              unless keep is set: then `out` (residual included) is written too and the 1x1 consumes it as stored (a
-              Bottleneck's 3x3 followed by the next Bottleneck's 1x1).  x2: the chained Conv reads cat(this layer's output, x2)
-              (a C3's last Bottleneck carrying cv3, x2 = cv2's output: C3.emit).
-        swap_halves: the input view holds the two halves of the layer's input channels in swapped order (C3 after an
-              odd number of fused Bottlenecks): the weight columns are swapped to match when they are packed."""
-        if self.conv.groups != 1 or self.conv.dilation != (1, 1):
-            raise NotImplementedError("grouped / dilated convolutions are outside the hot path")
-        kh, kw = self.conv.kernel_size
-        sh, sw = self.conv.stride
-        ph, pw = _pair(self.conv.padding)
-        c1 = self.conv.in_channels
-        c2 = self.conv.out_channels + sum(e.conv.out_channels for e in also)
-        if cin_slice is not None:
-            assert (kh, kw) == (1, 1) and not swap_halves and 0 <= cin_slice[0] < cin_slice[1] <= c1
-        for e in also:
-            assert (e.conv.kernel_size, e.conv.stride, _pair(e.conv.padding), e.conv.in_channels, e._act_code()) == \
-                   ((kh, kw), (sh, sw), (ph, pw), c1, self._act_code()), "fused convs must share geometry"
-        vec = ops.VEC[plan.dtype]
+        pre_term / pre_nearest / cin_slice / swap_halves: as emit_conv.
+        chain: Chained — 1x1 SiLU Convs (the cv1 | cv2 of the C3 behind a down-sampling Conv, the next Bottleneck's cv1, a C3's cv3)
+              applied to this layer's output tile inside the same launch."""
+        act = act_code(self.act)
+        assert all(act_code(e.act) == act for e in also), "fused convs must share an activation"
         paired = twin is not None
-        packed = functools.partial(self.packed, plan, twin, also, twin_also, swap_halves, cin_slice)
+        s2d = False
         if isinstance(x, ImageIn):
-            assert x.pair == paired
             B, _, H, W = x.shape
-            s2d = (kh, kw, sh, sw, ph, pw) == (6, 6, 2, 2, 2, 2) and H % 2 == 0 and W % 2 == 0
+            s2d = is_conv(self.conv, 6, 2, 2) and H % 2 == 0 and W % 2 == 0
+            c1, c2 = self.conv.in_channels, self.conv.out_channels
             if (s2d and self.fuse_stem and plan.dtype in (torch.bfloat16, torch.float16) and c1 == 3 and c2 in (32, 64)
                     and not also and res is None and (not x.u8 or (paired and x.c0 == 0))):
                 # staging + convolution in one persistent kernel reading the NCHW image itself (stem.hip)
-                wp, kp, bp = packed(transform=ops.s2d_conv_weight, cin_pad=16)
+                assert x.pair == paired
+                wp, kp, bp = self.packed(plan, twin, swap_halves=swap_halves, transform=ops.s2d_conv_weight, cin_pad=16)
                 if out is None:
                     out = plan.act(B, H // 2, W // 2, c2, pair=paired)
                 plan.add(ops.stem(x.t, wp, kp, bp, out, c2))
                 return out
-            x, c1 = stage_image(plan, x, c1, s2d)
-            wp, kp, bp = packed(transform=ops.s2d_conv_weight if s2d else None, cin_pad=c1)
-            if s2d:                       # 6x6/s2/p2 over the image == 3x3/s1/p1 over space-to-depth(image)
-                kh, kw, sh, sw, ph, pw = 3, 3, 1, 1, 1, 1
-        else:
-            assert (x.dim() == 5) == paired
-            if cin_slice is not None:
-                c1 = cin_slice[1] - cin_slice[0]
-            if x.shape[-1] != c1:
-                raise ValueError(f"Conv expects {c1} input channels, got {x.shape[-1]}")
-            if c1 % vec:
-                raise NotImplementedError(f"channel count {c1} must be a multiple of {vec} for dtype {plan.dtype}")
-            wp, kp, bp = packed()
-        B, H, W = x.shape[-4:-1]
-        Ho, Wo = conv_out(H, kh, sh, ph), conv_out(W, kw, sw, pw)
-        if out is None:
-            out = plan.act(B, Ho, Wo, c2, pair=paired)
-        ch = None
-        if chain is not None:
-            convs, twin_convs, y2 = chain[:3]
-            keep = len(chain) > 3 and bool(chain[3])
-            x2 = chain[4] if len(chain) > 4 else None
-            n2 = sum(c.conv.out_channels for c in convs)
-            w2p, kp2, b2p = convs[0].packed(plan, twin_convs[0] if paired else None, convs[1:], twin_convs[1:] if paired else ())
-            ch = dict(w=w2p, kp=kp2, bias=b2p, y=y2, cout=n2, keep=keep)
-            if x2 is not None:
-                ch["x2"] = x2
-            if not keep:
-                out = y2[..., :c2] if y2.shape[-1] >= c2 else plan.act(B, Ho, Wo, c2, pair=paired)   # (y is ignored by the kernel)
-        plan.add(ops.conv2d(x, wp, kp, bp, out, kh, kw, sh, sw, ph, pw, c1, c2, self._act_code(), res=res,
-                            name=f"conv{kh}x{kw}s{sh}" + (("+cv3" if ch.get("x2") is not None else "+1x1") if ch else ""), pre=pre_term, chain=ch,
-                            pre_nearest=pre_nearest))
-        return (out if ch["keep"] else y2) if ch else out
+        name = "conv{kh}x{kw}s{sh}" + ("" if chain is None else "+cv3" if chain.x2 is not None else "+1x1")
+        return emit_conv(plan, self, x, self._streams(twin, also, twin_also), act, name, out=out, res=res, pre_term=pre_term,
+                         pre_nearest=pre_nearest, swap_halves=swap_halves, cin_slice=cin_slice, chain=chain, s2d=s2d)
 
     fuse_stem2 = True    # stem + the 3x3/s2 Conv behind it + that Conv's chained cv1 | cv2 as ONE persistent kernel
 
     def stem2_ok(self, plan, x, nxt, c3):
         """self = image-fed 6x6/s2 stem, nxt = the Conv behind it, c3 = the C3 behind that: can icaf_stem2 run all three?
         (mirrors its argument checks: 16-bit, 3 -> 32 -> 64 -> 2 x 32 channels, i.e. the yolov5s width)"""
-        k0, k1 = self.conv, getattr(nxt, "conv", None)
         if not (self.fuse_stem2 and self.fuse_stem and isinstance(x, ImageIn) and x.pair and isinstance(nxt, Conv)
-                and plan.dtype in (torch.bfloat16, torch.float16) and (not x.u8 or x.c0 == 0)):
+                and silu16(plan, self) and (not x.u8 or x.c0 == 0)):
             return False
+        k0, k1 = self.conv, nxt.conv
         _, _, H, W = x.shape
-        return ((k0.kernel_size, k0.stride, _pair(k0.padding), k0.in_channels, k0.out_channels) == ((6, 6), (2, 2), (2, 2), 3, 32)
-                and k0.groups == 1 and isinstance(self.act, nn.SiLU) and H % 2 == 0 and W % 2 == 0
-                and (k1.kernel_size, k1.stride, _pair(k1.padding), k1.in_channels, k1.out_channels) == ((3, 3), (2, 2), (1, 1), 32, 64)
+        return (is_conv(k0, 6, 2, 2) and (k0.in_channels, k0.out_channels) == (3, 32) and H % 2 == 0 and W % 2 == 0
+                and is_conv(k1, 3, 2, 1) and (k1.in_channels, k1.out_channels) == (32, 64)
                 and nxt.chain_ok(plan, c3) and 2 * c3.cv1.conv.out_channels == 64)
 
-    def emit_stem2(self, plan, x, twin, nxt, nxt_twin, convs, twin_convs, y2):
-        """Rows 0-2a of both streams as one launch; y2 = the pair act the C3's cv1 | cv2 write."""
-        w0, kp0, b0 = self.packed(plan, twin, transform=ops.s2d_conv_weight, cin_pad=16)
-        w1, kp1, b1 = nxt.packed(plan, nxt_twin)
-        w2, kp2, b2 = convs[0].packed(plan, twin_convs[0], convs[1:], twin_convs[1:])
-        n2 = sum(c.conv.out_channels for c in convs)
-        plan.add(ops.stem2(x.t, w0, kp0, b0, w1, kp1, b1, w2, kp2, b2, y2, self.conv.out_channels, nxt.conv.out_channels, n2))
-        return y2
+    def emit_stem2(self, plan, x, lead, chain):
+        """Rows 0-2a of both streams as one launch: self = lead.stem, chain = the C3's cv1 | cv2 and the pair act they write."""
+        w0, kp0, b0 = self.packed(plan, lead.stem_twin, transform=ops.s2d_conv_weight, cin_pad=16)
+        w1, kp1, b1 = lead.conv.packed(plan, lead.twin)
+        c = chain.launch_form(plan, True)
+        plan.add(ops.stem2(x.t, w0, kp0, b0, w1, kp1, b1, c.w, c.kp, c.bias, c.y, self.conv.out_channels, lead.conv.conv.out_channels, c.cout))
+        return c.y
 
     chain_fuse = True    # let a C3 behind this Conv run its cv1 | cv2 GEMM on this layer's output tile (one launch)
 
@@ -347,10 +394,8 @@ class Conv(HipModule):
         """Can the fused cv1 | cv2 GEMM of `c3` ride on this conv's output tile?  (mirrors the checks of icaf_conv2d)"""
         k, cv = self.conv, c3.cv1.conv
         n1, n2 = k.out_channels, 2 * cv.out_channels
-        return (self.chain_fuse and plan.dtype in (torch.bfloat16, torch.float16) and isinstance(self.act, nn.SiLU)
-                and hasattr(k, "kernel_size") and k.kernel_size == (3, 3) and k.groups == 1 and k.in_channels % 32 == 0
-                and cv.kernel_size == (1, 1) and cv.stride == (1, 1) and cv.in_channels == n1
-                and c3.cv2.conv.out_channels == cv.out_channels and isinstance(c3.cv1.act, nn.SiLU)
+        return (self.chain_fuse and silu16(plan, self, c3.cv1) and is_conv(k, 3) and k.in_channels % 32 == 0
+                and is_conv(cv, 1, 1) and cv.in_channels == n1 and c3.cv2.conv.out_channels == cv.out_channels
                 and max(n1, n2) <= self.chain_max_width)
 
     chain_max_width = 128
@@ -359,10 +404,8 @@ class Conv(HipModule):
         """Can the 1x1 SiLU Conv `nxt` (the next Bottleneck's cv1) ride on this 3x3 layer's output tile, this layer's output
         (shortcut included) being written as well?  (icaf_conv2d: chain_keep)"""
         k, kn = self.conv, nxt.conv
-        return (self.chain_fuse and plan.dtype in (torch.bfloat16, torch.float16) and isinstance(self.act, nn.SiLU)
-                and isinstance(nxt.act, nn.SiLU) and k.kernel_size == (3, 3) and k.groups == 1 and k.in_channels % 64 == 0
-                and kn.kernel_size == (1, 1) and kn.stride == (1, 1) and kn.groups == 1 and kn.in_channels == k.out_channels
-                and max(k.out_channels, kn.out_channels) <= self.chain_max_width)
+        return (self.chain_fuse and silu16(plan, self, nxt) and is_conv(k, 3) and k.in_channels % 64 == 0
+                and is_conv(kn, 1, 1) and kn.in_channels == k.out_channels and max(k.out_channels, kn.out_channels) <= self.chain_max_width)
 
     chain_tail = OPT.c3_tail      # A/B switch: a C3's cv3 rides on its last Bottleneck's 3x3 (a class default, as fuse_decode)
 
@@ -370,10 +413,8 @@ class Conv(HipModule):
         """Can the C3's cv3 (1x1 SiLU over cat(m, cv2)) ride on this 3x3 layer — the block's last Bottleneck.cv2 — so that neither m nor
         the concatenation reach HBM?  (icaf_conv2d: x2; built in cwide.hip for 128 -> 128 layers with 256 output channels of cv3)"""
         k, k3 = self.conv, cv3.conv
-        return (self.chain_tail and OPT.cwide and plan.dtype in (torch.bfloat16, torch.float16) and isinstance(self.act, nn.SiLU)
-                and isinstance(cv3.act, nn.SiLU) and (k.kernel_size, k.stride, _pair(k.padding), k.groups) == ((3, 3), (1, 1), (1, 1), 1)
-                and (k.in_channels, k.out_channels) == (128, 128) and k3.kernel_size == (1, 1) and k3.stride == (1, 1) and k3.groups == 1
-                and _pair(k3.padding) == (0, 0) and k3.in_channels == 2 * k.out_channels and k3.out_channels == 256)
+        return (self.chain_tail and OPT.cwide and silu16(plan, self, cv3) and is_conv(k, 3, 1, 1) and (k.in_channels, k.out_channels) == (128, 128)
+                and is_conv(k3, 1, 1, 0) and k3.in_channels == 2 * k.out_channels and k3.out_channels == 256)
 
 
 class VGGblock(HipModule):
@@ -413,46 +454,38 @@ class VGGblock(HipModule):
         ws, bs = [ops.vgg_stem_weight(w, dt) for w, _ in rows], [b.contiguous() for _, b in rows]
         return (ws[0], 32, bs[0]) if len(rows) == 1 else (torch.stack(ws).contiguous(), 32, torch.stack(bs).contiguous())
 
+    def _streams(self, j, twin):
+        return [[(b.convs()[j], None)] for b in ((self,) if twin is None else (self, twin))]
+
     def _packed(self, plan, j, twin, cin_pad=None, stem=False):
         """(wp, kp, bp) of conv j in its launch form, or with stem=True in icaf_vgg_stem's; with `twin` the two streams stacked."""
-        blocks = (self,) if twin is None else (self, twin)
-        return self.packed_convs(plan, [[(b.convs()[j], None)] for b in blocks], cin_pad=cin_pad, pack=VGGblock._pack_stem if stem else None)
+        return self.packed_convs(plan, self._streams(j, twin), cin_pad=cin_pad, pack=VGGblock._pack_stem if stem else None)
 
     def emit(self, plan, x, out=None, twin=None):
         paired = twin is not None
-        vec = ops.VEC[plan.dtype]
         pool = self.vggblock[-1]
         if not isinstance(pool, nn.MaxPool2d) or pool.dilation not in (1, (1, 1)) or pool.ceil_mode:
             raise NotImplementedError("VGGblock ends with a plain nn.MaxPool2d")
         for s in list(self.vggblock)[:-1]:
             if not (isinstance(s, nn.Sequential) and len(s) == 2 and isinstance(s[0], nn.Conv2d) and isinstance(s[1], nn.ReLU)):
                 raise NotImplementedError("VGGblock rows are Sequential(Conv2d, ReLU): another activation is outside the hot path")
-        for j, k in enumerate(self.convs()):
-            if (k.kernel_size, k.stride, _pair(k.padding), k.groups, k.dilation) != ((3, 3), (1, 1), (1, 1), 1, (1, 1)) or k.bias is None:
-                raise NotImplementedError("VGGblock convolutions are 3x3 / stride 1 / padding 1 with bias")
-            c1, c2 = k.in_channels, k.out_channels
+        convs = self.convs()
+        if not all(is_conv(k, 3, 1, 1) and k.bias is not None for k in convs):
+            raise NotImplementedError("VGGblock convolutions are 3x3 / stride 1 / padding 1 with bias")
+        for j in range(1, len(convs)):          # the widths inside the block are refused before its first launch
+            check_conv(plan, convs[j], f"VGGblock conv {j}", convs[j].in_channels, convs[j - 1].out_channels)
+        for j, k in enumerate(convs):
+            y = None
             if isinstance(x, ImageIn):
-                assert j == 0 and x.pair == paired
                 B, _, H, W = x.shape
-                y = plan.act(B, H, W, c2, pair=paired)
-                if self.fuse_stem and plan.dtype in (torch.bfloat16, torch.float16) and (c1, c2) == (3, 64):
+                y = plan.act(B, H, W, k.out_channels, pair=paired)      # in FRONT of the staging buffer: the order plans number their buffers in
+                if self.fuse_stem and plan.dtype in (torch.bfloat16, torch.float16) and (k.in_channels, k.out_channels) == (3, 64):
+                    assert x.pair == paired
                     wp, _, bp = self._packed(plan, 0, twin, stem=True)
                     plan.add(ops.vgg_stem(x.t, wp, bp, y, c0=x.c0 if x.u8 else 0))
                     x = y
                     continue
-                x, c1 = stage_image(plan, x, c1)
-                wp, kp, bp = self._packed(plan, 0, twin, cin_pad=c1)
-            else:
-                assert (x.dim() == 5) == paired
-                if x.shape[-1] != c1:
-                    raise ValueError(f"VGGblock conv {j} expects {c1} input channels, got {x.shape[-1]}")
-                if c1 % vec:
-                    raise NotImplementedError(f"channel count {c1} must be a multiple of {vec} for dtype {plan.dtype}")
-                B, H, W = x.shape[-4:-1]
-                y = plan.act(B, H, W, c2, pair=paired)
-                wp, kp, bp = self._packed(plan, j, twin)
-            plan.add(ops.conv2d(x, wp, kp, bp, y, 3, 3, 1, 1, 1, 1, c1, c2, ops.ACT_RELU, name="vgg_conv3x3"))
-            x = y
+            x = emit_conv(plan, self, x, self._streams(j, twin), ops.ACT_RELU, "vgg_conv3x3", out=y)
         return emit_maxpool(plan, x, pool, out, "vgg_maxpool")
 
 
@@ -494,32 +527,15 @@ class ResNetblock(HipModule):
 
     def emit(self, plan, x, out=None, twin=None):
         self._check()
-        paired = twin is not None
-        assert (x.dim() == 5) == paired
-        vec = ops.VEC[plan.dtype]
-        c1, c2, c3 = self.conv1.in_channels, self.conv1.out_channels, self.conv3.out_channels
-        s = self.conv2.stride[0]
-        if x.shape[-1] != c1:
-            raise ValueError(f"ResNetblock expects {c1} input channels, got {x.shape[-1]}")
-        if c1 % vec or c2 % vec:
-            raise NotImplementedError(f"channel counts {c1}, {c2} must be multiples of {vec} for dtype {plan.dtype}")
+        check_conv(plan, self.conv2, "ResNetblock conv2", self.conv2.in_channels, self.conv1.out_channels)     # the width inside, before the first launch
         blocks = (self,) if twin is None else (self, twin)
-        # BatchNorm is folded HERE, when the weights are packed: the modules keep theirs, as the reference's fuse() leaves them (it only touches Conv)
-        pack = lambda k, bn: self.packed_convs(plan, [[(b.get_submodule(k), b.get_submodule(bn))] for b in blocks])     # noqa: E731
-        B, H, W = x.shape[-4:-1]
-        Ho, Wo = conv_out(H, 3, s, 1), conv_out(W, 3, s, 1)
-        t1 = plan.act(B, H, W, c2, pair=paired)
-        plan.add(ops.conv2d(x, *pack("conv1", "bn1"), t1, 1, 1, 1, 1, 0, 0, c1, c2, ops.ACT_RELU, name="resnet_conv1x1"))
-        t2 = plan.act(B, Ho, Wo, c2, pair=paired)
-        plan.add(ops.conv2d(t1, *pack("conv2", "bn2"), t2, 3, 3, s, s, 1, 1, c2, c2, ops.ACT_RELU, name=f"resnet_conv3x3s{s}"))
-        res = x
-        if len(self.shortcut):
-            res = plan.act(B, Ho, Wo, c3, pair=paired)
-            plan.add(ops.conv2d(x, *pack("shortcut.0", "shortcut.1"), res, 1, 1, s, s, 0, 0, c1, c3, ops.ACT_NONE, name=f"resnet_shortcut1x1s{s}"))
-        if out is None:
-            out = plan.act(B, Ho, Wo, c3, pair=paired)
-        plan.add(ops.conv2d(t2, *pack("conv3", "bn3"), out, 1, 1, 1, 1, 0, 0, c2, c3, ops.ACT_RELU, res=res, res_pre_act=True, name="resnet_conv1x1+res"))
-        return out
+
+        def conv(k, bn, x, name, act=ops.ACT_RELU, **kw):
+            # BatchNorm is folded HERE, when the weights are packed: the modules keep theirs, as the reference's fuse() leaves them (it only touches Conv)
+            return emit_conv(plan, self, x, [[(b.get_submodule(k), b.get_submodule(bn))] for b in blocks], act, name, **kw)
+        t = conv("conv2", "bn2", conv("conv1", "bn1", x, "resnet_conv1x1"), "resnet_conv3x3s{sh}")
+        res = conv("shortcut.0", "shortcut.1", x, "resnet_shortcut1x1s{sh}", ops.ACT_NONE) if len(self.shortcut) else x
+        return conv("conv3", "bn3", t, "resnet_conv1x1+res", out=out, res=res, res_pre_act=True)
 
 
 class ResNetlayer(HipModule):
@@ -565,27 +581,11 @@ class ResNetlayer(HipModule):
             return x
         mods = list(self.layer)
         if not (len(mods) == 4 and isinstance(mods[0], nn.Conv2d) and isinstance(mods[1], nn.BatchNorm2d) and isinstance(mods[2], nn.ReLU)
-                and isinstance(mods[3], nn.MaxPool2d) and mods[3].dilation in (1, (1, 1)) and not mods[3].ceil_mode
-                and mods[0].groups == 1 and mods[0].dilation == (1, 1)):
+                and isinstance(mods[3], nn.MaxPool2d) and mods[3].dilation in (1, (1, 1)) and not mods[3].ceil_mode):
             raise NotImplementedError("the first ResNetlayer is Conv2d + BatchNorm2d + ReLU + a plain MaxPool2d")
-        k, pool = mods[0], mods[3]
-        (kh, kw), (sh, sw), (ph, pw) = k.kernel_size, k.stride, _pair(k.padding)
-        vec = ops.VEC[plan.dtype]
-        c1, c2 = k.in_channels, k.out_channels
         layers = (self,) if twin is None else (self, twin)
-        if isinstance(x, ImageIn):
-            assert x.pair == paired
-            x, cin = stage_image(plan, x, c1)
-        else:
-            assert (x.dim() == 5) == paired
-            if x.shape[-1] != c1 or c1 % vec:
-                raise ValueError(f"ResNetlayer stem expects {c1} input channels in whole {vec}-element vectors, got {x.shape[-1]}")
-            cin = c1
-        wp, kp, bp = self.packed_convs(plan, [[(l.layer[0], l.layer[1])] for l in layers], cin_pad=cin)
-        _, Hc, Wc = conv2d_shape(k, *x.shape[-3:-1])
-        y = plan.act(x.shape[-4], Hc, Wc, c2, pair=paired)
-        plan.add(ops.conv2d(x, wp, kp, bp, y, kh, kw, sh, sw, ph, pw, cin, c2, ops.ACT_RELU, name=f"resnet_stem{kh}x{kw}s{sh}"))
-        return emit_maxpool(plan, y, pool, out, "resnet_maxpool")
+        y = emit_conv(plan, self, x, [[(l.layer[0], l.layer[1])] for l in layers], ops.ACT_RELU, "resnet_stem{kh}x{kw}s{sh}")
+        return emit_maxpool(plan, y, mods[3], out, "resnet_maxpool")
 
 
 class Bottleneck(HipModule):
@@ -614,28 +614,21 @@ class Bottleneck(HipModule):
         155 us against 30 + 62 us at 80x80 / c_ = 64, where two LDS patches leave room for one workgroup per CU."""
         a, b = self.cv1.conv, self.cv2.conv
         c = a.in_channels
-        return (self.fuse and plan.dtype in (torch.bfloat16, torch.float16) and c in self.fuse_widths
-                and a.out_channels == c and b.in_channels == c and b.out_channels == c
-                and a.kernel_size == (1, 1) and a.stride == (1, 1) and _pair(a.padding) == (0, 0)
-                and b.kernel_size == (3, 3) and b.stride == (1, 1) and _pair(b.padding) == (1, 1)
-                and a.groups == 1 and b.groups == 1 and isinstance(self.cv1.act, nn.SiLU) and isinstance(self.cv2.act, nn.SiLU)
+        return (self.fuse and silu16(plan, self.cv1, self.cv2) and c in self.fuse_widths
+                and a.out_channels == c and b.in_channels == c and b.out_channels == c and is_conv(a, 1, 1, 0) and is_conv(b, 3, 1, 1)
                 and x.shape[-2] >= 64)
 
     def emit_fused(self, plan, x, out, twin=None, cv3=None):
         """y = [x +] SiLU(conv3x3(SiLU(conv1x1(x)))) as ONE launch; `out` must be a different buffer (slice) than x.
-        cv3 = (Conv, twin Conv or None, x2, y3): the C3's cv3 rides on the launch — x2 is the cv2 half of its input, y3 its
-        output; the Bottleneck's own output is then never written (`out` is ignored)."""
+        cv3: Chained with x2 — the C3's cv3 rides on the launch: x2 is the cv2 half of its input, y its output; the Bottleneck's own
+        output is then never written (`out` is ignored)."""
         c = self.cv1.conv.in_channels
         paired = twin is not None
-        tail = None
-        if cv3 is not None:
-            k3, k3t, x2, y3 = cv3
-            w3, kp3, b3 = k3.packed(plan, k3t, swap_halves=True)          # K columns in the order [cv2 | m]
-            tail = dict(w=w3, kp=kp3, bias=b3, y=y3, cout=k3.conv.out_channels, x2=x2)
+        tail = None if cv3 is None else cv3.launch_form(plan, paired, swap_halves=True)          # K columns in the order [cv2 | m]
         w1, kp1, b1 = self.cv1.packed(plan, twin.cv1 if paired else None)
         w2, kp2, b2 = self.cv2.packed(plan, twin.cv2 if paired else None)
         plan.add(ops.bottleneck(x, w1, kp1, b1, w2, kp2, b2, None if tail else out, c, self.add, 1 if c == 32 else 2, cv3=tail))
-        return tail["y"] if tail else out
+        return tail.y if tail else out
 
 
 class C3(HipModule):
@@ -660,19 +653,19 @@ class C3(HipModule):
     chain_bottlenecks = True     # n > 1: a Bottleneck's 3x3 (+ shortcut) and the next Bottleneck's 1x1 as one launch
 
     def emit(self, plan, x, out=None, twin=None, lead=None):
-        """lead = (Conv, twin Conv or None): the down-sampling Conv in front of this block whose output only this block
-        reads; `x` is then THAT conv's input and cv1 | cv2 run chained on its output tile (the tensor between the two
-        yaml rows is never written)."""
+        """lead: Lead — the down-sampling Conv in front of this block whose output only this block reads; `x` is then THAT
+        conv's input (with lead.stem the image pair itself) and cv1 | cv2 run chained on its output tile (the tensor between
+        the two yaml rows is never written)."""
         vcat = x if isinstance(x, VirtualCat) else None
         if vcat is not None:
             assert lead is None and twin is None
             x = vcat.other
-        if lead is not None and len(lead) == 4:        # (Conv, twin, stem, stem twin): x is the image pair itself
+        if lead is not None and lead.from_image:
             B, _, H, W = x.shape
             H, W = conv_out(H // 2, 3, 2, 1), conv_out(W // 2, 3, 2, 1)          # behind the 6x6 / s2 stem, then the 3x3 / s2 Conv
         elif lead is not None:
             B = x.shape[-4]
-            _, H, W = conv2d_shape(lead[0].conv, *x.shape[-3:-1])
+            _, H, W = conv2d_shape(lead.conv.conv, *x.shape[-3:-1])
         else:
             B, H, W = x.shape[-4:-1]
         c_ = self.cv1.conv.out_channels
@@ -682,14 +675,15 @@ class C3(HipModule):
         # neighbours' patches read x), so the chain ping-pongs between slot 0 and slot 2; cv3 then reads [a | b] or
         # [b | a'] — in the second case with its weight columns swapped to match.
         k3 = self.cv3.conv
-        tail3 = (self.fuse_cv3 and len(self.m) == 1 and fused[0] and c_ == 32 and k3.out_channels == 64 and k3.kernel_size == (1, 1)
-                 and k3.stride == (1, 1) and k3.groups == 1 and k3.in_channels == 2 * c_ and isinstance(self.cv3.act, nn.SiLU))
+        tail3 = (self.fuse_cv3 and len(self.m) == 1 and fused[0] and silu16(plan, self.cv3) and c_ == 32 and k3.out_channels == 64
+                 and is_conv(k3, 1, 1) and k3.in_channels == 2 * c_)
         cat = plan.act(B, H, W, (3 if any(fused) and not tail3 else 2) * c_, pair=paired)
-        if lead is not None and len(lead) == 4:
-            lead[2].emit_stem2(plan, x, lead[3], lead[0], lead[1], (self.cv1, self.cv2), (twin.cv1, twin.cv2), cat[..., :2 * c_])
-        elif lead is not None:
-            lead[0].emit(plan, x, twin=lead[1], chain=((self.cv1, self.cv2), (twin.cv1, twin.cv2) if paired else None,
-                                                       cat[..., :2 * c_]))
+        if lead is not None:
+            both = Chained((self.cv1, self.cv2), (twin.cv1, twin.cv2) if paired else None, cat[..., :2 * c_])
+            if lead.from_image:
+                lead.stem.emit_stem2(plan, x, lead, both)
+            else:
+                lead.conv.emit(plan, x, twin=lead.twin, chain=both)
         elif vcat is not None:
             # cv(cat(up(a), b)) = SiLU(up(Wa . a) + Wb . b + bias): the 1x1 commutes with the nearest up-sampling, so the
             # a-half of cv1 | cv2 runs at LOW resolution (fp32 out, a quarter of the pixels) and enters the GEMM over b as its
@@ -707,7 +701,7 @@ class C3(HipModule):
             if out is None:
                 out = plan.act(B, H, W, k3.out_channels, pair=paired)
             return self.m[0].emit_fused(plan, cat[..., :c_], None, twin=twin.m[0] if paired else None,
-                                        cv3=(self.cv3, twin.cv3 if paired else None, cat[..., c_:2 * c_], out))
+                                        cv3=Chained((self.cv3,), (twin.cv3,) if paired else None, out, x2=cat[..., c_:2 * c_]))
         cur = 0
         t_next = None                       # the next Bottleneck's 1x1 output, when the previous 3x3 launch produced it
         for j, blk in enumerate(self.m):
@@ -722,14 +716,14 @@ class C3(HipModule):
             t_next, ch = None, None
             if nxt is not None and self.chain_bottlenecks and blk.cv2.chain_ok_1x1(plan, nxt.cv1):
                 t_next = plan.act(B, H, W, nxt.cv1.conv.out_channels, pair=paired)
-                ch = ((nxt.cv1,), (twin.m[j + 1].cv1,) if paired else None, t_next, True)
+                ch = Chained((nxt.cv1,), (twin.m[j + 1].cv1,) if paired else None, t_next, keep=True)
             if j == len(self.m) - 1 and cur == 0 and blk.cv2.chain_ok_tail(plan, self.cv3):
                 # the block's tail as ONE launch: m = [a +] SiLU(conv3x3(t)) stays in the kernel's staging tile, cv3 reads [m | b] from there
                 # and from cv2's half of the buffer (icaf.h: icaf_conv_args.x2) — m is never written, cat(m, b) never read
                 if out is None:
                     out = plan.act(B, H, W, k3.out_channels, pair=paired)
                 return blk.cv2.emit(plan, t, out=a, res=a if blk.add else None, twin=tw.cv2 if paired else None,
-                                    chain=((self.cv3,), (twin.cv3,) if paired else None, out, False, cat[..., c_:2 * c_]))
+                                    chain=Chained((self.cv3,), (twin.cv3,) if paired else None, out, x2=cat[..., c_:2 * c_]))
             blk.cv2.emit(plan, t, out=a, res=a if blk.add else None, twin=tw.cv2 if paired else None, chain=ch)
         src = cat[..., :2 * c_] if cur == 0 else cat[..., c_:3 * c_]
         return self.cv3.emit(plan, src, out=out, twin=twin.cv3 if paired else None, swap_halves=cur != 0)
@@ -827,17 +821,12 @@ class NiNfusion(HipModule):
         self.conv = nn.Conv2d(c1, c2, k, s, autopad(k, p), groups=g, bias=False)
         self.act = nn.SiLU()
 
-    # the packed-weight / launch logic is Conv's (a Conv without .bn and without bias)
-    packed = Conv.packed
-    _act_code = Conv._act_code
-    fuse_stem = False
-
     def out_shape(self, srcs):
         return conv2d_shape(self.conv, srcs[0][1], srcs[0][2])
 
     def emit(self, plan, xs, out=None):
         x = self.concat.emit(plan, list(xs))
-        return Conv.emit(self, plan, x, out=out)
+        return emit_conv(plan, self, x, [[(self.conv, None)]], act_code(self.act), "conv{kh}x{kw}s{sh}", out=out)
 
 
 def emit_upsample(m, plan, x, out=None):

@@ -20,7 +20,7 @@ import torch.nn as nn
 
 from .. import ops
 from ..engine import ImageIn, Plan, TtaPlan
-from .common import (C3, SPPF, Add, Bottleneck, Concat, Conv, Detect, HipModule, NiNfusion,  # noqa: F401
+from .common import (C3, SPPF, Add, Bottleneck, Concat, Conv, Detect, HipModule, Lead, NiNfusion,  # noqa: F401
                      ResNetblock, ResNetlayer, TransformerFusionBlock, VGGblock, VirtualCat, emit_upsample)
 
 logger = logging.getLogger(__name__)
@@ -461,24 +461,24 @@ class Model(HipModule):
 
     @staticmethod
     def _defer(lead, row, convs, src):
-        """This row launches nothing: `convs` (with their input `src`) are emitted inside the launch of `row`, which pops them from `lead`."""
+        """This row launches nothing: `convs` (a Lead, with its input `src`) is emitted inside the launch of `row`, which pops it from `lead`."""
         lead[row] = (convs, src)
 
     def _emit_twin_row(self, plan, m, src, ir0, rgb_rows, lead, dmff_pair):
         """RGB row m and its IR twin as one launch sequence over the pair act / image pair `src` -> their pair act, or None when the row
-        is deferred into a later row's launch (`lead`: {that row: (the Convs in front of it, their input)})."""
+        is deferred into a later row's launch (`lead`: {that row: (the Lead in front of it, its input)})."""
         i, twin, nxt, nx2 = m.i, self.model[ir0 + m.i], self._row(m.i + 1), self._row(m.i + 2)
         if (i == 0 and isinstance(m, Conv) and isinstance(nx2, C3) and {1, 2} <= rgb_rows and nxt.f == -1
                 and nx2.f == -1 and not ({0, 1, ir0, ir0 + 1} & (set(self.save) | set(dmff_pair)))
                 and m.stem2_ok(plan, src, nxt, nx2)):
-            return self._defer(lead, 1, (m, twin), src)              # rows 0-2a become one launch, emitted with the C3 row
+            return self._defer(lead, 1, Lead(m, twin), src)          # rows 0-2a become one launch, emitted with the C3 row
         if i == 1 and 1 in lead:                                     # ... the 3x3 behind that stem
             stem, image = lead.pop(1)
-            return self._defer(lead, 2, (m, twin) + stem, image)
+            return self._defer(lead, 2, Lead(m, twin, stem.conv, stem.twin), image)
         if (isinstance(m, Conv) and i > 0 and isinstance(nxt, C3) and (i + 1) in rgb_rows and nxt.f == -1
                 and i not in self.save and (ir0 + i) not in self.save and i not in dmff_pair
                 and m.chain_ok(plan, nxt)):
-            return self._defer(lead, i + 1, (m, twin), src)          # a down-sampling Conv, emitted together with the C3 row
+            return self._defer(lead, i + 1, Lead(m, twin), src)      # a down-sampling Conv, emitted together with the C3 row
         convs, src = lead.pop(i, (None, src))
         pout = None
         if i in dmff_pair and dmff_pair[i][3] == ir0 + i:            # pair act = the two halves of the DMFF buffer

@@ -156,12 +156,27 @@ def s2d_conv_weight(w4d):
 # ------------------------------------------------------------------------------------------------------------
 # launches
 # ------------------------------------------------------------------------------------------------------------
+# A 1x1 + SiLU layer riding on another launch's output tile (conv2d's chain=, bottleneck's cv3=): w / kp / bias its packed weights (stacked per
+# stream for pair acts), y its output, cout its width.  keep: the carrying layer's own output is written too and the 1x1 consumes it as stored.
+# x2: the 1x1 reads K = [the carrying layer's tile | x2] (a C3's cv3 over cat(m, cv2)).
+class Chain(collections.namedtuple("Chain", "w kp bias y cout keep x2", defaults=(False, None))):
+    __slots__ = ()
+
+    @classmethod
+    def of(cls, v):                       # a chain= / cv3= argument: None, a Chain, or a mapping with its field names (the kernel tests' spelling)
+        return v if v is None or isinstance(v, cls) else cls(**v)
+
+    def __getitem__(self, k):             # a field by its name too: Launch.keep holds the record, and its readers ask chain["y"]
+        return getattr(self, k) if isinstance(k, str) else tuple.__getitem__(self, k)
+
+
 def conv2d(x, w_packed, kp, bias, y, kh, kw, sh, sw, ph, pw, cin, cout, act, res=None, alpha_acc=1.0,
            alpha_res=1.0, groups=1, group_strides=None, tile=0, name="conv2d", pre=None, chain=None, pre_nearest=False, res_pre_act=False):
     """Record an implicit-GEMM conv / linear.  x, y, res are acts; for groups=2 they are the group-0 views and
     group_strides = dict(x=, w=, bias=, y=, res=) gives element strides to group 1.
     res_pre_act: the residual is added IN FRONT of the activation, y = relu(conv(x) + bias + res) rounded once (icaf.h: res_mode = 1; a
     ResNet bottleneck's conv3): ReLU layers with a residual, unit alphas, no pre term and no chained layer only — the library refuses the rest."""
+    chain = Chain.of(chain)
     B, H, W, cx, ldx = _act_geom(x)
     By, Ho, Wo, cy, ldy = _act_geom(y)
     assert cx >= cin and cy >= cout and By == B
@@ -197,18 +212,18 @@ def conv2d(x, w_packed, kp, bias, y, kh, kw, sh, sw, ph, pw, cin, cout, act, res
         assert pre.dtype == torch.float32 and Bp == B and cp >= cout and groups == 1
         a.pre, a.pre_h, a.pre_w, a.ldpre = pre.data_ptr(), hp, wp_, ldp
         a.pre_mode = int(bool(pre_nearest))     # nearest: the map is the low-resolution half of a 1x1 conv over cat(up(a), b)
-    if chain is not None:             # chained 1x1 + SiLU on the output tile (icaf.h): dict(w=, kp=, bias=, y=, cout=[, keep=][, x2=])
-        y2 = chain["y"]
+    if chain is not None:             # chained 1x1 + SiLU on the output tile (icaf.h)
+        y2 = chain.y
         B2, H2, W2, c2y, ldy2 = _act_geom(y2)
-        assert (B2, H2, W2) == (B, Ho, Wo) and c2y >= chain["cout"] and y2.dtype == x.dtype and (y2.dim() == 5) == (x.dim() == 5)
-        a.w2, a.y2 = chain["w"].data_ptr(), y2.data_ptr()
-        a.bias2 = chain["bias"].data_ptr() if chain.get("bias") is not None else None
-        a.Kp2, a.Cout2, a.ldy2 = chain["kp"], chain["cout"], ldy2
-        a.chain_keep = int(bool(chain.get("keep")))
+        assert (B2, H2, W2) == (B, Ho, Wo) and c2y >= chain.cout and y2.dtype == x.dtype and (y2.dim() == 5) == (x.dim() == 5)
+        a.w2, a.y2 = chain.w.data_ptr(), y2.data_ptr()
+        a.bias2 = chain.bias.data_ptr() if chain.bias is not None else None
+        a.Kp2, a.Cout2, a.ldy2 = chain.kp, chain.cout, ldy2
+        a.chain_keep = int(bool(chain.keep))
         if x.dim() == 5:
-            a.w2_gs, a.y2_gs = chain["w"].stride(0), y2.stride(0)
-            a.bias2_gs = chain["bias"].stride(0) if chain.get("bias") is not None else 0
-        x2 = chain.get("x2")
+            a.w2_gs, a.y2_gs = chain.w.stride(0), y2.stride(0)
+            a.bias2_gs = chain.bias.stride(0) if chain.bias is not None else 0
+        x2 = chain.x2
         if x2 is not None:            # C3 tail: the chained layer reads K = [this layer's tile | x2] (icaf.h: icaf_conv_args.x2)
             Bx, Hx, Wx, cx2, ldx2 = _act_geom(x2)
             assert (Bx, Hx, Wx) == (B, Ho, Wo) and cx2 >= cout and x2.dtype == x.dtype and (x2.dim() == 5) == (x.dim() == 5)
@@ -223,11 +238,11 @@ def conv2d(x, w_packed, kp, bias, y, kh, kw, sh, sw, ph, pw, cin, cout, act, res
     nbytes = groups * (B * H * W * cin * es + cout * kh * kw * cin * es + m * cout * eo
                        + (m * cout * es if res is not None else 0))
     if chain is not None:
-        k2 = cout * (2 if chain.get("x2") is not None else 1)
-        flops += 2.0 * m * k2 * chain["cout"] * groups
-        nbytes += groups * (m * chain["cout"] - (0 if chain.get("keep") else m * cout)) * eo      # y2 is written instead of / besides y
-        if chain.get("x2") is not None:
-            nbytes += groups * (m * cout + k2 * chain["cout"]) * es       # the x2 half of the chained layer's input, its weights
+        k2 = cout * (2 if chain.x2 is not None else 1)
+        flops += 2.0 * m * k2 * chain.cout * groups
+        nbytes += groups * (m * chain.cout - (0 if chain.keep else m * cout)) * eo      # y2 is written instead of / besides y
+        if chain.x2 is not None:
+            nbytes += groups * (m * cout + k2 * chain.cout) * es       # the x2 half of the chained layer's input, its weights
     return Launch(lib().icaf_conv2d, (C.byref(a),), keep=(a, x, w_packed, bias, y, res, pre, chain, wf), name=name, flops=flops,
                   nbytes=nbytes)
 
@@ -235,12 +250,13 @@ def conv2d(x, w_packed, kp, bias, y, kh, kw, sh, sw, ph, pw, cin, cout, act, res
 def bottleneck(x, w1_packed, kp1, bias1, w2_packed, kp2, bias2, y, c, add, shape, name="bottleneck", cv3=None):
     """Whole Bottleneck (1x1 -> 3x3 [+ x]) in one launch (icaf_bottleneck).  x, y: acts or pair acts of c channels in
     DIFFERENT buffers; w1 / w2: packed 1x1 / 3x3 weights (stacked per stream for pair acts).
-    cv3 = dict(w=, kp=, bias=, y=, cout=, x2=): the C3's cv3 rides on the block — x2 is the cv2 half of its input, w its
-    packed weights with K columns ordered [cv2 | m]; only cv3's output (y of the dict) is written and `y` may be None."""
+    cv3: Chain with x2 — the C3's cv3 rides on the block: x2 is the cv2 half of its input, w its packed weights with K columns ordered
+    [cv2 | m]; only cv3's output (cv3.y) is written and `y` may be None."""
+    cv3 = Chain.of(cv3)
     if cv3 is not None and y is None:
-        y = cv3["y"][..., :c]                     # (ignored by the kernel; satisfies the argument checks)
+        y = cv3.y[..., :c]                       # (ignored by the kernel; satisfies the argument checks)
     inner = conv2d(x, w2_packed, kp2, bias2, y, 3, 3, 1, 1, 1, 1, c, c, ACT_SILU, res=x if add else None, name=name,
-                   chain=None if cv3 is None else dict(w=cv3["w"], kp=cv3["kp"], bias=cv3["bias"], y=cv3["y"], cout=cv3["cout"]))
+                   chain=None if cv3 is None else cv3._replace(x2=None))
     b = BneckArgs()
     C.memmove(C.byref(b.conv), C.byref(inner.keep[0]), C.sizeof(ConvArgs))
     b.w1, b.bias1 = w1_packed.data_ptr(), bias1.data_ptr()
@@ -253,12 +269,12 @@ def bottleneck(x, w1_packed, kp1, bias1, w2_packed, kp2, bias2, y, c, add, shape
     es = x.element_size()
     nbytes = g * (B * H * W * c * es * (3 if add else 2) + (9 * c * c + c * c) * es)
     if cv3 is not None:
-        x2 = cv3["x2"]
+        x2 = cv3.x2
         B2, H2, W2, c2, ldx2 = _act_geom(x2)
         assert (B2, H2, W2) == (B, H, W) and c2 >= c and x2.dtype == x.dtype and (x2.dim() == 5) == paired
         b.x2, b.ldx2, b.x2_gs = x2.data_ptr(), ldx2, x2.stride(0) if paired else 0
-        nbytes = g * (B * H * W * es * (2 * c + cv3["cout"]) + (10 * c * c + 2 * c * cv3["cout"]) * es)
-        flops += 2.0 * g * B * H * W * c * cv3["cout"]          # (conv2d counted K = c for the chained layer; cv3 has K = 2c)
+        nbytes = g * (B * H * W * es * (2 * c + cv3.cout) + (10 * c * c + 2 * c * cv3.cout) * es)
+        flops += 2.0 * g * B * H * W * c * cv3.cout          # (conv2d counted K = c for the chained layer; cv3 has K = 2c)
     return Launch(lib().icaf_bottleneck, (C.byref(b),), keep=(b, inner.keep, w1_packed, bias1, cv3), name=name + ("+cv3" if cv3 else ""),
                   flops=flops, nbytes=nbytes)
 
@@ -494,19 +510,27 @@ def preprocess_u8(img, out, mode, c0=0, name="preprocess_u8"):
                                              H, W, cpad, mode), keep=(img, out), name=name, nbytes=nb)
 
 
-def stem(img, w_packed, kp, bias, y, cout, name="stem"):
-    """Staging + 6x6/s2/p2 stem conv in one persistent kernel (icaf_stem).  img: fp32 (B, 3, H, W) / (2, B, 3, H, W)
-    [both streams], or uint8 (B, 6, H, W) [both streams]; y: act or pair act of cout channels at half resolution."""
+def _image_arg(img, paired):
+    """(u8, ctot, B, H, W) of the network image an image-fed kernel reads: fp32 (B, 3, H, W) / (2, B, 3, H, W) [both streams], or the dataloader's
+    uint8 (B, ctot, H, W) batch, whose channels hold the streams side by side."""
     u8 = img.dtype == torch.uint8
-    paired = y.dim() == 5
     assert img.is_contiguous() and (u8 or img.dtype == torch.float32)
     if u8:
-        assert img.dim() == 4 and paired and img.shape[1] >= 6
+        assert img.dim() == 4
         B, ctot, H, W = img.shape
     else:
         assert img.dim() == (5 if paired else 4)
         B, _, H, W = img.shape[-4:]
         ctot = 3
+    return u8, ctot, B, H, W
+
+
+def stem(img, w_packed, kp, bias, y, cout, name="stem"):
+    """Staging + 6x6/s2/p2 stem conv in one persistent kernel (icaf_stem).  img: fp32 (B, 3, H, W) / (2, B, 3, H, W)
+    [both streams], or uint8 (B, 6, H, W) [both streams]; y: act or pair act of cout channels at half resolution."""
+    paired = y.dim() == 5
+    u8, ctot, B, H, W = _image_arg(img, paired)
+    assert not u8 or (paired and ctot >= 6)
     By, Ho, Wo, cy, ldy = _act_geom(y)
     assert (By, Ho, Wo) == (B, H // 2, W // 2) and cy >= cout and w_packed.dtype == y.dtype
     g = 2 if paired else 1
@@ -522,16 +546,9 @@ def stem(img, w_packed, kp, bias, y, cout, name="stem"):
 def stem2(img, w0, kp0, b0, w1, kp1, b1, w2, kp2, b2, y, c0, c1, c2, name="stem+conv3x3s2+1x1"):
     """Stem, the 3x3/s2 conv behind it and a chained 1x1 in one persistent kernel (icaf_stem2): img as `stem`; w0 / w1 /
     w2: the packed weights of the three layers (stacked per stream for a pair act y); y: (B, H/4, W/4, >= c2) act."""
-    u8 = img.dtype == torch.uint8
     paired = y.dim() == 5
-    assert img.is_contiguous() and (u8 or img.dtype == torch.float32)
-    if u8:
-        assert img.dim() == 4 and paired and img.shape[1] >= 6
-        B, ctot, H, W = img.shape
-    else:
-        assert img.dim() == (5 if paired else 4)
-        B, _, H, W = img.shape[-4:]
-        ctot = 3
+    u8, ctot, B, H, W = _image_arg(img, paired)
+    assert not u8 or (paired and ctot >= 6)
     By, Ho, Wo, cy, ldy = _act_geom(y)
     assert (By, Ho, Wo) == (B, (H // 2 - 1) // 2 + 1, (W // 2 - 1) // 2 + 1) and cy >= c2
     assert w0.dtype == w1.dtype == w2.dtype == y.dtype
@@ -563,17 +580,10 @@ def vgg_stem(img, w, bias, y, c0=0, name="vgg_stem"):
     """Image-fed 3x3 / s1 / p1 conv 3 -> 64 + bias + ReLU in one launch (icaf_vgg_stem).  img: fp32 (B, 3, H, W) / (2, B, 3, H, W) [both
     streams], or uint8 (B, Ctot, H, W) read from channel c0 on (both streams: [c0, c0 + 6)); w: vgg_stem_weight packs ([64][32], stacked per
     stream for a pair act y), bias fp32 [64] / [2][64]; y: act or pair act of 64 channels at the image's resolution."""
-    u8 = img.dtype == torch.uint8
     paired = y.dim() == 5
     g = 2 if paired else 1
-    assert img.is_contiguous() and (u8 or img.dtype == torch.float32)
-    if u8:
-        assert img.dim() == 4 and c0 + 3 * g <= img.shape[1]
-        B, ctot, H, W = img.shape
-    else:
-        assert img.dim() == (5 if paired else 4) and img.shape[-3] == 3 and c0 == 0
-        B, _, H, W = img.shape[-4:]
-        ctot = 3
+    u8, ctot, B, H, W = _image_arg(img, paired)
+    assert c0 + 3 * g <= ctot if u8 else (img.shape[-3] == 3 and c0 == 0)
     By, Ho, Wo, cy, ldy = _act_geom(y)
     assert (By, Ho, Wo) == (B, H, W) and cy >= 64 and w.dtype == y.dtype and w.shape[-2:] == (64, 32) and w.dim() == (3 if paired else 2)
     assert bias.dtype == torch.float32 and bias.shape[-1] >= 64 and w.is_contiguous() and bias.stride(-1) == 1
