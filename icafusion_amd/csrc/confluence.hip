@@ -25,8 +25,12 @@
 // coordinate, ((|dx1| + |dx2|) + |dy1|) + |dy2| — without contraction, reciprocals or reassociation: kept indices equal the reference's.
 // A sweep does not pay those eight divisions for every pair: an fp32 estimate with a proven band (cf_estimate) finds the few pairs that can
 // attain the minimum, or lie within the band around p_thres, and only those go through the fp64 arithmetic, which alone decides.
+// The candidate scan (wg_incl_scan), the xywh decode and the ordered compaction of the kept rows (wg_rank) are box_core.h's.  The pick kernel keeps
+// its member list and its own copy of the two-pass sweep written out.  A build with one sweep template for both kernels and the member list on
+// wg_rank compiled the pick kernel to 94 instead of 108 registers and measured 3 - 7 % over its limits at 1,024 and 4,096 candidates; which of
+// the two pieces cost that was not separated.  With this text the pick and the sweep kernel are the parent's assembly (profiles/postproc_share_ab.json).
 #pragma clang fp contract(off)
-#include "icaf_common.h"
+#include "box_core.h"
 
 namespace icaf {
 
@@ -90,7 +94,7 @@ __device__ __forceinline__ void cf_wave_min(double& p, int& j) {
 __global__ __launch_bounds__(CF_THREADS) void confluence_cand_kernel(const float* __restrict__ pred, long long rows, int nc, float conf,
                                                                      int max_cand, float* __restrict__ cand, int* __restrict__ ncand) {
     __shared__ int wsum[CF_WAVES];
-    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int b = blockIdx.x, tid = threadIdx.x;
     const int no = 5 + nc;
     const float* pb = pred + (long long)b * rows * no;
     float* cb = cand + (long long)b * max_cand * 6;
@@ -104,27 +108,13 @@ __global__ __launch_bounds__(CF_THREADS) void confluence_cand_kernel(const float
             if (obj > conf)
                 for (int j = 0; j < nc; ++j) mine += (pb[r * no + 5 + j] * obj > conf) ? 1 : 0;
         }
-        int inc = mine;                                  // inclusive scan over the workgroup
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const int t = __shfl_up(inc, o);
-            if (lane >= o) inc += t;
-        }
-        if (lane == 63) wsum[wave] = inc;
-        __syncthreads();
-        int before = 0, total = 0;
-#pragma unroll
-        for (int w = 0; w < CF_WAVES; ++w) {
-            const int s = wsum[w];
-            if (w < wave) before += s;
-            total += s;
-        }
-        __syncthreads();
+        int total;
+        const int incl = wg_incl_scan<CF_WAVES>(mine, wsum, total);
         if (mine) {
-            long long k = base + before + inc - mine;
+            long long k = base + incl - mine;
             const float* p = pb + r * no;
-            const float hw = p[2] / 2.0f, hh = p[3] / 2.0f;
-            const float x1 = p[0] - hw, y1 = p[1] - hh, x2 = p[0] + hw, y2 = p[1] + hh;
+            float x1, y1, x2, y2;
+            xywh_to_xyxy(p, x1, y1, x2, y2);
             for (int j = 0; j < nc && k < max_cand; ++j) {
                 const float c = p[5 + j] * obj;
                 if (c > conf) {
@@ -369,7 +359,7 @@ __global__ __launch_bounds__(CF_THREADS) void confluence_compact_kernel(const fl
                                                                         int* __restrict__ keep_idx) {
     __shared__ unsigned char flag[CF_MAX];
     __shared__ int wsum[CF_WAVES];
-    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int b = blockIdx.x, tid = threadIdx.x;
     const int n_raw = n_in[b];
     const int n = (n_raw < 0 || n_raw > max_cand) ? 0 : n_raw;
     const float* cb = cand + (long long)b * max_cand * 6;
@@ -381,19 +371,10 @@ __global__ __launch_bounds__(CF_THREADS) void confluence_compact_kernel(const fl
     for (int i0 = 0; i0 < n; i0 += CF_THREADS) {
         const int i = i0 + tid;
         const bool mine = i < n && flag[i];
-        const unsigned long long bal = __ballot(mine);
-        if (lane == 0) wsum[wave] = __popcll(bal);
-        __syncthreads();
-        int before = 0, total = 0;
-#pragma unroll
-        for (int w = 0; w < CF_WAVES; ++w) {
-            const int v = wsum[w];
-            if (w < wave) before += v;
-            total += v;
-        }
-        __syncthreads();
+        int total;
+        const int before = wg_rank<CF_WAVES>(mine, wsum, total);
         if (mine) {
-            const int k = kept + before + __popcll(bal & ((1ull << lane) - 1ull));       // k <= i: rows are only read from cand
+            const int k = kept + before;                     // k <= i: rows are only read from cand
             const float* a = cb + (long long)i * 6;
             float* o = db + (long long)k * 6;
             o[0] = a[0]; o[1] = a[1]; o[2] = a[2]; o[3] = a[3]; o[4] = a[4]; o[5] = a[5];
@@ -411,21 +392,17 @@ __global__ __launch_bounds__(CF_THREADS) void confluence_compact_kernel(const fl
 
 struct CfWs { float* cand; int* ncand; double* minp; int* nbr; size_t total; };
 
-static inline size_t cf_align(size_t v) { return (v + 255) / 256 * 256; }
-
 static int cf_layout(int B, long long rows, int nc, int max_cand, void* base, CfWs& ws) {
     if (B < 1 || rows < 1 || nc < 1) return fail(ICAF_ERR_ARG, "icaf_confluence: bad B/rows/nc");
     if (max_cand < 1 || max_cand > CF_MAX) return fail(ICAF_ERR_ARG, "icaf_confluence: max_cand must be in [1, %d] (%d)", CF_MAX, max_cand);
     if ((long long)B * nc > 0x7fffffffLL || rows * nc > 0x7fffffffLL)
         return fail(ICAF_ERR_UNSUPPORTED, "icaf_confluence: B * nc and rows * nc must stay below 2^31");
-    unsigned char* p = (unsigned char*)base;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { unsigned char* r = p ? p + off : nullptr; off = cf_align(off + bytes); return r; };
-    ws.cand = (float*)take((size_t)B * max_cand * 6 * 4);
-    ws.minp = (double*)take((size_t)B * max_cand * 8);
-    ws.nbr = (int*)take((size_t)B * max_cand * 4);
-    ws.ncand = (int*)take((size_t)B * 4);
-    ws.total = off;
+    WsArena ar(base);
+    ws.cand = ar.take_as<float>((size_t)B * max_cand * 6 * 4);
+    ws.minp = ar.take_as<double>((size_t)B * max_cand * 8);
+    ws.nbr = ar.take_as<int>((size_t)B * max_cand * 4);
+    ws.ncand = ar.take_as<int>((size_t)B * 4);
+    ws.total = ar.total;
     return ICAF_OK;
 }
 

@@ -214,7 +214,19 @@ __host__ __device__ __forceinline__ void fd_divmod(unsigned int n, FastDiv f, un
     r = n - q * f.d;
 }
 
-constexpr int ICAF_MAX_DEVICES = 64;      // per-device one-time kernel attribute flags (hipFuncSetAttribute is per device)
+// ---- workspace layout ---------------------------------------------------------------------------------------------------------------
+static inline size_t align256(size_t v) { return (v + 255) / 256 * 256; }
+// Carves a caller's workspace into 256-byte aligned pieces: take() gives the next piece's offset (and, with a base, its address); `total` is
+// the size the workspace must have.  Without a base the same calls size the workspace (the *_workspace_bytes queries).
+struct WsArena {
+    unsigned char* base;
+    size_t total = 0;
+    explicit WsArena(void* b = nullptr) : base((unsigned char*)b) {}
+    size_t take(size_t bytes) { const size_t at = total; total = align256(total + bytes); return at; }
+    template <typename T> T* take_as(size_t bytes) { const size_t at = take(bytes); return base ? (T*)(base + at) : nullptr; }
+};
+
+constexpr int ICAF_MAX_DEVICES = 64;     // per-device one-time kernel attribute flags (hipFuncSetAttribute is per device)
 
 // One-time opt-in of ONE kernel instantiation to `bytes` of dynamic LDS, per DEVICE: hipFuncSetAttribute is per device, and a process may
 // drive several GPUs (tests, one process per node).  Expands to a function-local static flag array, i.e. one per template / lambda

@@ -35,10 +35,11 @@
 //                              table (decode_slot<true>); the plain path runs the <false> instantiations — the code it always ran.
 //   4.  nms_merge_kernel       (merge-NMS, :594-600) one workgroup per image behind the walk and the rank kernel.
 // All box arithmetic is fp32 with contraction disabled, in the reference's operation order, so kept indices are
-// bit-identical to the CPU algorithm on the same prediction tensor.
+// bit-identical to the CPU algorithm on the same prediction tensor.  The workgroup scan, the xywh decode, box_iou and the mapping to
+// the native image (scale_detections_kernel) are box_core.h's; the validation matching that consumes these detections is valstats.hip's.
 #pragma clang fp contract(off)
 #include <cstring>
-#include "icaf_common.h"
+#include "box_core.h"
 
 namespace icaf {
 
@@ -168,29 +169,6 @@ __device__ __forceinline__ bool iou_gt(float ax1, float ay1, float ax2, float ay
     return sure_yes;
 }
 
-// inclusive prefix sum over the 1024 threads of the walk kernel (v per thread); total returned through `total`
-__device__ __forceinline__ unsigned int block_incl_scan_1024(unsigned int v, unsigned int* wsum, unsigned int& total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    unsigned int inc = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const unsigned int t = __shfl_up(inc, o);
-        if (lane >= o) inc += t;
-    }
-    if (lane == 63) wsum[wave] = inc;
-    __syncthreads();
-    unsigned int base = 0, tot = 0;
-#pragma unroll
-    for (int w = 0; w < 16; ++w) {
-        const unsigned int s = wsum[w];
-        if (w < wave) base += s;
-        tot += s;
-    }
-    __syncthreads();
-    total = tot;
-    return base + inc;
-}
-
 struct WalkSmem {
     unsigned long long keys[NMS_CAP];                                     // gathered / sorted keys of the round
     float kx1[MAX_KEEP], ky1[MAX_KEEP], kx2[MAX_KEEP], ky2[MAX_KEEP], kar[MAX_KEEP];      // kept boxes (class-offset), areas
@@ -202,32 +180,284 @@ struct WalkSmem {
     unsigned int wsum[16];
     unsigned long long deadmask;
     unsigned long long supp[64];                                          // supp[j]: lanes of the step that candidate j suppresses
-    unsigned long long lo, hi;
+    unsigned long long lo;
     unsigned int batch_n, sel_cnt, sel_val, nkept;
-    int mode_b_bin;
+};
+
+// what the walk and the merge kernel read of their image: prediction rows, key words, single-label classes, first label row (LAB only)
+struct NmsImage {
+    const float* __restrict__ pb;
+    const unsigned int* __restrict__ kb;
+    const unsigned short* __restrict__ cb;
+    const float* __restrict__ lb;
+    long long rows, cap;
+    int nc, multi;
 };
 
 // decode the box of candidate slot `slot`: xywh -> xyxy exactly as the reference (utils/general.py:332-339).  LAB: rows at or beyond `rows` are
 // the image's apriori labels (lb = its first label row, [cls, cx, cy, w, h]): obj = 1, one-hot class confidence (:548-551), read where they lie
 template <bool LAB>
-__device__ __forceinline__ void decode_slot(const float* __restrict__ pb, const unsigned short* __restrict__ cb, int nc, int multi,
-                                            unsigned int slot, const float* __restrict__ lb, long long rows, float& x1, float& y1, float& x2,
-                                            float& y2, float& sc, int& cl) {
-    const unsigned int row = multi ? slot / (unsigned)nc : slot;
-    if (LAB && (long long)row >= rows) {
-        const float* l = lb + ((long long)row - rows) * 5;
+__device__ __forceinline__ void decode_slot(const NmsImage& im, unsigned int slot, float& x1, float& y1, float& x2, float& y2, float& sc,
+                                            int& cl) {
+    const unsigned int row = im.multi ? slot / (unsigned)im.nc : slot;
+    if (LAB && (long long)row >= im.rows) {
+        const float* l = im.lb + ((long long)row - im.rows) * 5;
         const int lc = (int)l[0];
-        cl = multi ? (int)(slot - row * (unsigned)nc) : lc;
-        const float hw = l[3] / 2.0f, hh = l[4] / 2.0f;
-        x1 = l[1] - hw; y1 = l[2] - hh; x2 = l[1] + hw; y2 = l[2] + hh;
+        cl = im.multi ? (int)(slot - row * (unsigned)im.nc) : lc;
+        xywh_to_xyxy(l + 1, x1, y1, x2, y2);
         sc = (cl == lc ? 1.0f : 0.0f) * 1.0f;
         return;
     }
-    cl = multi ? (int)(slot - row * (unsigned)nc) : (int)cb[row];
-    const float* p = pb + (long long)row * (5 + nc);
-    const float hw = p[2] / 2.0f, hh = p[3] / 2.0f;
-    x1 = p[0] - hw; y1 = p[1] - hh; x2 = p[0] + hw; y2 = p[1] + hh;
+    cl = im.multi ? (int)(slot - row * (unsigned)im.nc) : (int)im.cb[row];
+    const float* p = im.pb + (long long)row * (5 + im.nc);
+    xywh_to_xyxy(p, x1, y1, x2, y2);
     sc = p[5 + cl] * p[4];
+}
+
+// ---- the walk kernel: its cursor and its phases ---------------------------------------------------------------------------------------------------
+// where the walk stands.  Rounds visit disjoint, descending ranges [lo, hi) of the 64-bit key space; every field is workgroup-uniform
+struct WalkCursor {
+    int hib = NMS_NB;                              // histogram bins [0, hib) are entirely unvisited
+    unsigned long long hi = ~0ull;                 // keys >= hi have been visited
+    unsigned long long lo = 0ull;                  // the round in flight gathers the keys of [lo, hi)
+    unsigned int in_bin_left = 0;                  // refinement mode: unvisited keys left in bin hib (which is then partially visited)
+    unsigned int processed = 0, nkept = 0;
+    int round = 0;
+};
+
+// select: lo = the floor of the lowest of the highest unvisited bins that together hold <= target keys — NMS_FIRST in the first round, widened
+// to NMS_CAP when the next non-empty bin alone exceeds it.  When that bin alone exceeds NMS_CAP as well, refinement mode is entered instead
+// (in_bin_left != 0, walk_refine finds lo).  false: nothing is left anywhere.
+__device__ __forceinline__ bool walk_select(WalkSmem& sm, WalkCursor& cur) {
+    const int tid = threadIdx.x;
+    // P(d) = keys in bins (hib-1-d .. hib-1]; largest d with P(d) <= target
+    unsigned int target = cur.round == 0 ? NMS_FIRST : NMS_CAP;
+    for (;;) {
+        unsigned int loc[3], s = 0;
+#pragma unroll
+        for (int e = 0; e < 3; ++e) {
+            const int d = tid * 3 + e;
+            loc[e] = d < cur.hib ? sm.hist[cur.hib - 1 - d] : 0u;
+            s += loc[e];
+        }
+        unsigned int total;
+        const unsigned int incl = wg_incl_scan<16>(s, sm.wsum, total);
+        if (tid == 0) { sm.sel_cnt = 0; sm.sel_val = 0; }
+        __syncthreads();
+        unsigned int run = incl - s, nle = 0, last = 0;
+#pragma unroll
+        for (int e = 0; e < 3; ++e) {
+            run += loc[e];
+            if (tid * 3 + e < cur.hib && run <= target) { ++nle; last = run; }
+        }
+        if (nle) { atomicAdd(&sm.sel_cnt, nle); atomicMax(&sm.sel_val, last); }
+        __syncthreads();
+        const unsigned int dcnt = sm.sel_cnt, val = sm.sel_val;     // dcnt bins from the top hold `val` keys in total
+        __syncthreads();
+        if (total == 0) { cur.hib = 0; return false; }              // nothing left anywhere
+        cur.hib -= (int)dcnt;                                        // (val == 0: these are the empty bins above the next non-empty one)
+        if (val > 0) { cur.lo = bin_floor_key(cur.hib); return true; }
+        // the next non-empty bin alone exceeds the target
+        if (target < NMS_CAP) { target = NMS_CAP; continue; }
+        cur.hib -= 1;                                                // > NMS_CAP keys in one bin: refine inside it
+        cur.in_bin_left = sm.hist[cur.hib];                          // (bins between it and `hi` are empty: hi stays a valid bound)
+        return true;
+    }
+}
+
+// radix refinement inside bin `hib` over the keys in [bin_floor_key(hib), hi): find lo with 1 <= #[lo, hi) <= NMS_CAP
+__device__ __forceinline__ void walk_refine(WalkSmem& sm, const unsigned int* __restrict__ kb, long long cap, WalkCursor& cur) {
+    const int tid = threadIdx.x;
+    const unsigned long long blo = bin_floor_key(cur.hib), hi = cur.hi;
+    if (cur.in_bin_left <= NMS_CAP) { cur.lo = blo; return; }
+    unsigned long long lo = 0ull;
+    unsigned long long prefix = 0ull;      // the digits chosen so far (upper bits of lo)
+    for (int level = 0; level < 8; ++level) {
+        const int shift = 56 - 8 * level;
+        for (int i = tid; i < 256; i += WALK_THREADS) sm.dh[i] = 0;
+        __syncthreads();
+        for (long long i = tid; i < cap; i += WALK_THREADS) {
+            const unsigned int k32 = kb[i];
+            if (!k32) continue;
+            const unsigned long long k = ((unsigned long long)k32 << 32) | (unsigned long long)(0xffffffffu - (unsigned)i);
+            if (k < blo || k >= hi) continue;
+            if (level > 0 && (k >> (shift + 8)) != (prefix >> (shift + 8))) continue;
+            atomicAdd(&sm.dh[(unsigned)(k >> shift) & 255u], 1u);
+        }
+        __syncthreads();
+        if (tid == 0) {
+            int dmax = 255;
+            while (dmax > 0 && sm.dh[dmax] == 0) --dmax;
+            if (sm.dh[dmax] > NMS_CAP) {                         // descend into the top digit (no key of the range lies above it)
+                sm.lo = prefix | ((unsigned long long)dmax << shift);
+                sm.sel_val = 0;
+            } else {
+                unsigned int suf = 0;
+                int d = dmax;
+                while (d >= 0 && suf + sm.dh[d] <= NMS_CAP) { suf += sm.dh[d]; --d; }
+                sm.lo = prefix | ((unsigned long long)(d + 1) << shift);
+                sm.sel_val = suf;                                // >= 1
+            }
+        }
+        __syncthreads();
+        prefix = sm.lo;
+        const unsigned int got = sm.sel_val;
+        __syncthreads();
+        if (got) { lo = prefix; break; }
+    }
+    cur.lo = lo < blo ? blo : lo;
+}
+
+// gather the keys of [lo, hi) into LDS (any order); returns their number (<= NMS_CAP by construction of lo)
+__device__ __forceinline__ unsigned int walk_gather(WalkSmem& sm, const unsigned int* __restrict__ kb, long long cap, const WalkCursor& cur) {
+    const int tid = threadIdx.x, lane = tid & 63;
+    const unsigned long long lo = cur.lo, hi = cur.hi;
+    if (tid == 0) sm.batch_n = 0;
+    __syncthreads();
+    for (long long i0 = 0; i0 < cap; i0 += 8 * WALK_THREADS) {
+        unsigned int k32[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {                      // eight independent loads in flight per thread (the scan is latency-bound)
+            const long long i = i0 + u * WALK_THREADS + tid;
+            k32[u] = i < cap ? kb[i] : 0u;
+        }
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+            const long long i = i0 + u * WALK_THREADS + tid;
+            const unsigned long long k = ((unsigned long long)k32[u] << 32) | (unsigned long long)(0xffffffffu - (unsigned)i);
+            const bool take = k32[u] != 0u && k >= lo && k < hi;
+            const unsigned long long m = __ballot(take);
+            if (m) {
+                unsigned int base = 0;
+                if (lane == 0) base = atomicAdd(&sm.batch_n, (unsigned)__popcll(m));
+                base = __shfl(base, 0);
+                if (take) {
+                    const unsigned int slot = base + (unsigned)__popcll(m & ((1ull << lane) - 1ull));
+                    if (slot < NMS_CAP) sm.keys[slot] = k;
+                }
+            }
+        }
+    }
+    __syncthreads();
+    return sm.batch_n < NMS_CAP ? sm.batch_n : NMS_CAP;
+}
+
+// bitonic sort of keys[0, bn) in LDS, descending (padding = key 0, the smallest)
+// (a rank sort — every thread counting the keys greater than its own through broadcast reads — measured 150 k cycles for 1020
+//  keys: 64-bit compares x n^2 are VALU-bound; the network below is 55 barrier stages for 1024 keys, 78 for 4096)
+__device__ __forceinline__ void walk_sort(WalkSmem& sm, unsigned int bn) {
+    const int tid = threadIdx.x;
+    unsigned int P = 64;
+    while (P < bn) P <<= 1;
+    for (unsigned int i = bn + tid; i < P; i += WALK_THREADS) sm.keys[i] = 0ull;
+    __syncthreads();
+    for (unsigned int k = 2; k <= P; k <<= 1)
+        for (unsigned int j = k >> 1; j > 0; j >>= 1) {
+            for (unsigned int t = tid; t < P / 2; t += WALK_THREADS) {
+                const unsigned int i = ((t & ~(j - 1u)) << 1) | (t & (j - 1u));
+                const unsigned int l = i | j;
+                const bool up = (i & k) != 0u;                // ascending sub-blocks of the network; the last merge is all-descending
+                const unsigned long long a = sm.keys[i], c = sm.keys[l];
+                if ((a < c) != up) { sm.keys[i] = c; sm.keys[l] = a; }
+            }
+            __syncthreads();
+        }
+}
+
+// greedy walk over the sorted round: the first `limit` keys (max_nms cap, by score rank), 1024 decoded at a time, 64 resolved per step
+template <bool LAB>
+__device__ __forceinline__ void walk_steps(WalkSmem& sm, const NmsImage& im, WalkCursor& cur, unsigned int limit, float iou_thr, float cls_off,
+                                           int max_det) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    unsigned int nkept = cur.nkept;
+    for (unsigned int base = 0; base < limit && nkept < (unsigned)max_det; base += WALK_THREADS) {
+        {
+            const unsigned int pos = base + tid;
+            if (pos < limit) {
+                const unsigned int slot = 0xffffffffu - (unsigned)(sm.keys[pos] & 0xffffffffull);
+                float x1, y1, x2, y2, sc;
+                int cl;
+                decode_slot<LAB>(im, slot, x1, y1, x2, y2, sc, cl);
+                const float off = (float)cl * cls_off;                 // boxes + cls * max_wh (reference :589-590)
+                x1 = x1 + off; y1 = y1 + off; x2 = x2 + off; y2 = y2 + off;
+                sm.cx1[tid] = x1; sm.cy1[tid] = y1; sm.cx2[tid] = x2; sm.cy2[tid] = y2;
+                sm.car[tid] = (x2 - x1) * (y2 - y1);
+            }
+        }
+        __syncthreads();
+        const unsigned int span = (limit - base) < WALK_THREADS ? (limit - base) : WALK_THREADS;
+        for (unsigned int c0 = 0; c0 < span && nkept < (unsigned)max_det; c0 += 64) {
+            const unsigned int ci = c0 + lane;
+            const bool valid = ci < span;
+            float x1 = 0.f, y1 = 0.f, x2 = 0.f, y2 = 0.f, area = 0.f;
+            if (valid) { x1 = sm.cx1[ci]; y1 = sm.cy1[ci]; x2 = sm.cx2[ci]; y2 = sm.cy2[ci]; area = sm.car[ci]; }
+            // phase A: the 16 wavefronts test the step against interleaved sixteenths of the kept list
+            bool dead = !valid;
+            for (unsigned int k = wave; k < nkept && !__all(dead); k += 16) {
+                const bool hit = iou_gt(sm.kx1[k], sm.ky1[k], sm.kx2[k], sm.ky2[k], sm.kar[k], x1, y1, x2, y2, area, iou_thr);    // (all lanes: wave-uniform control flow)
+                dead = dead || hit;
+            }
+            const unsigned long long dm = __ballot(dead);
+            if (lane == 0 && dm) atomicOr(&sm.deadmask, dm);
+            // ... and the step's own 64 x 64 suppression relation, four candidates j per wavefront: supp[j] = the lanes that
+            // overlap candidate j (box broadcast from lane j's registers); the serial pass below then needs no IoU at all
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const int j = wave * 4 + u;
+                const float jx1 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, x1), j));
+                const float jy1 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, y1), j));
+                const float jx2 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, x2), j));
+                const float jy2 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, y2), j));
+                const float jar = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, area), j));
+                const bool over = iou_gt(jx1, jy1, jx2, jy2, jar, x1, y1, x2, y2, area, iou_thr);
+                const unsigned long long m = __ballot(over && valid);
+                if (lane == 0) sm.supp[j] = m;
+            }
+            __syncthreads();
+            if (wave == 0) {
+                // phase B: resolve the step in order — a kept candidate j removes the LATER lanes of supp[j].  Lane l holds supp[l]
+                // in registers; per kept box the serial pass is a find-first-set, two v_readlane and scalar mask arithmetic.
+                const unsigned long long mysupp = sm.supp[lane];
+                const int slo = (int)(unsigned)(mysupp & 0xffffffffull), shi = (int)(unsigned)(mysupp >> 32);
+                unsigned long long alive = ~sm.deadmask, keptmask = 0ull;
+                const unsigned int nkept0 = nkept;
+                while (alive && nkept < (unsigned)max_det) {
+                    const int j = __ffsll((long long)alive) - 1;          // wave-uniform
+                    keptmask |= 1ull << j;
+                    ++nkept;
+                    const unsigned long long sj = ((unsigned long long)(unsigned)__builtin_amdgcn_readlane(shi, j) << 32) |
+                                                  (unsigned long long)(unsigned)__builtin_amdgcn_readlane(slo, j);
+                    alive &= ~((sj & ~((2ull << j) - 1ull)) | (1ull << j));
+                }
+                if ((keptmask >> lane) & 1ull) {
+                    const unsigned int kk = nkept0 + (unsigned)__popcll(keptmask & ((1ull << lane) - 1ull));
+                    sm.kx1[kk] = x1; sm.ky1[kk] = y1; sm.kx2[kk] = x2; sm.ky2[kk] = y2; sm.kar[kk] = area;
+                    sm.kslot[kk] = 0xffffffffu - (unsigned)(sm.keys[base + ci] & 0xffffffffull);
+                    sm.kpos[kk] = cur.processed + base + ci;
+                }
+                if (lane == 0) { sm.nkept = nkept; sm.deadmask = 0ull; }
+            }
+            __syncthreads();
+            nkept = sm.nkept;
+        }
+    }
+    cur.nkept = nkept;
+}
+
+// outputs, all kept boxes in parallel
+template <bool LAB>
+__device__ __forceinline__ void walk_write(const WalkSmem& sm, const NmsImage& im, int b, unsigned int nkept, bool reordered, int max_det,
+                                           float* __restrict__ det, int* __restrict__ count, int* __restrict__ keep_idx) {
+    const int tid = threadIdx.x;
+    if (tid == 0) count[b] = (int)nkept;
+    for (unsigned int k = tid; k < nkept; k += WALK_THREADS) {
+        float x1, y1, x2, y2, sc;
+        int cl;
+        decode_slot<LAB>(im, sm.kslot[k], x1, y1, x2, y2, sc, cl);
+        float* o = det + ((long long)b * max_det + k) * 6;
+        o[0] = x1; o[1] = y1; o[2] = x2; o[3] = y2; o[4] = sc; o[5] = (float)cl;
+        if (keep_idx) keep_idx[(long long)b * max_det + k] = (int)(reordered ? sm.kpos[k] : sm.kslot[k]);
+    }
 }
 
 #ifdef ICAF_NMS_DEBUG
@@ -246,11 +476,9 @@ __global__ __launch_bounds__(WALK_THREADS) void nms_walk_kernel(const float* __r
                                                                 int* __restrict__ count, int* __restrict__ keep_idx) {
     extern __shared__ __attribute__((aligned(16))) unsigned char walk_smem_raw[];
     WalkSmem& sm = *reinterpret_cast<WalkSmem*>(walk_smem_raw);
-    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const float* pb = pred + (long long)b * rows * (5 + nc);
-    const unsigned int* kb = key32 + (long long)b * cap;
-    const unsigned short* cb = cls16 + (long long)b * rows;
-    const float* lb = LAB ? labels + (long long)label_off[b] * 5 : nullptr;
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const NmsImage im = {pred + (long long)b * rows * (5 + nc), key32 + (long long)b * cap, cls16 + (long long)b * rows,
+                          LAB ? labels + (long long)label_off[b] * 5 : nullptr, rows, cap, nc, multi};
 #ifdef ICAF_NMS_DEBUG
     __shared__ long long stamps[16];
     for (int i = tid; i < 16; i += WALK_THREADS) stamps[i] = 0;
@@ -261,249 +489,35 @@ __global__ __launch_bounds__(WALK_THREADS) void nms_walk_kernel(const float* __r
     const bool reordered = n_all > (unsigned)max_nms;             // reference re-indexes x by score rank in that case (:586)
     const unsigned int n = reordered ? (unsigned)max_nms : n_all;
     for (int i = tid; i < NMS_NB; i += WALK_THREADS) sm.hist[i] = ghist[(long long)b * NMS_NB + i];
-    if (tid == 0) { sm.nkept = 0; sm.deadmask = 0ull; sm.mode_b_bin = -1; }
+    if (tid == 0) { sm.nkept = 0; sm.deadmask = 0ull; }
     __syncthreads();
-    int hib = NMS_NB;                              // histogram bins [0, hib) are entirely unvisited
-    unsigned long long hi = ~0ull;                 // keys >= hi have been visited
-    unsigned int processed = 0, nkept = 0;
-    unsigned int in_bin_left = 0;                  // refinement mode: unvisited keys left in bin hib (which is then partially visited)
-    int round = 0;
-    while (nkept < (unsigned)max_det && processed < n) {
-        // ------------------------------------------------------------------ select [lo, hi)
-        unsigned long long lo = 0ull;
-        unsigned int expect = 0;
-        int mode_b = -1;
-        if (in_bin_left == 0) {
-            // P(d) = keys in bins (hib-1-d .. hib-1]; largest d with P(d) <= target
-            unsigned int target = round == 0 ? NMS_FIRST : NMS_CAP;
-            for (;;) {
-                unsigned int loc[3], s = 0;
-#pragma unroll
-                for (int e = 0; e < 3; ++e) {
-                    const int d = tid * 3 + e;
-                    loc[e] = d < hib ? sm.hist[hib - 1 - d] : 0u;
-                    s += loc[e];
-                }
-                unsigned int total;
-                const unsigned int incl = block_incl_scan_1024(s, sm.wsum, total);
-                if (tid == 0) { sm.sel_cnt = 0; sm.sel_val = 0; }
-                __syncthreads();
-                unsigned int run = incl - s, nle = 0, last = 0;
-#pragma unroll
-                for (int e = 0; e < 3; ++e) {
-                    run += loc[e];
-                    if (tid * 3 + e < hib && run <= target) { ++nle; last = run; }
-                }
-                if (nle) { atomicAdd(&sm.sel_cnt, nle); atomicMax(&sm.sel_val, last); }
-                __syncthreads();
-                const unsigned int dcnt = sm.sel_cnt, val = sm.sel_val;     // dcnt bins from the top hold `val` keys in total
-                __syncthreads();
-                if (total == 0) { expect = 0; hib = 0; break; }             // nothing left anywhere
-                if (val > 0) { expect = val; hib -= (int)dcnt; lo = bin_floor_key(hib); break; }
-                // the next non-empty bin alone exceeds the target
-                hib -= (int)dcnt;                                            // skip the empty bins above it
-                if (target < NMS_CAP) { target = NMS_CAP; continue; }
-                mode_b = hib - 1;                                            // > NMS_CAP keys in one bin: refine inside it
-                break;
-            }
-            if (expect == 0 && mode_b < 0) break;
-            if (mode_b >= 0) { in_bin_left = sm.hist[mode_b]; hib = mode_b; }      // (bins between it and `hi` are empty: hi stays a valid bound)
-        }
-        if (in_bin_left != 0) {
-            // radix refinement inside bin `hib` over the keys in [bin_floor_key(hib), hi): find lo with 1 <= #[lo, hi) <= NMS_CAP
-            const unsigned long long blo = bin_floor_key(hib);
-            if (in_bin_left <= NMS_CAP) {
-                lo = blo; expect = in_bin_left;
-            } else {
-                unsigned long long prefix = 0ull;      // the digits chosen so far (upper bits of lo)
-                unsigned int acc = 0;                  // keys above the current prefix range that the batch already includes
-                for (int level = 0; level < 8; ++level) {
-                    const int shift = 56 - 8 * level;
-                    for (int i = tid; i < 256; i += WALK_THREADS) sm.dh[i] = 0;
-                    __syncthreads();
-                    for (long long i = tid; i < cap; i += WALK_THREADS) {
-                        const unsigned int k32 = kb[i];
-                        if (!k32) continue;
-                        const unsigned long long k = ((unsigned long long)k32 << 32) | (unsigned long long)(0xffffffffu - (unsigned)i);
-                        if (k < blo || k >= hi) continue;
-                        if (level > 0 && (k >> (shift + 8)) != (prefix >> (shift + 8))) continue;
-                        atomicAdd(&sm.dh[(unsigned)(k >> shift) & 255u], 1u);
-                    }
-                    __syncthreads();
-                    if (tid == 0) {
-                        int dmax = 255;
-                        while (dmax > 0 && sm.dh[dmax] == 0) --dmax;
-                        if (acc + sm.dh[dmax] > NMS_CAP) {                   // descend into the top digit
-                            sm.lo = prefix | ((unsigned long long)dmax << shift);
-                            sm.sel_val = 0;
-                        } else {
-                            unsigned int suf = 0;
-                            int d = dmax;
-                            while (d >= 0 && acc + suf + sm.dh[d] <= NMS_CAP) { suf += sm.dh[d]; --d; }
-                            sm.lo = prefix | ((unsigned long long)(d + 1) << shift);
-                            sm.sel_val = acc + suf;                          // >= 1
-                        }
-                    }
-                    __syncthreads();
-                    prefix = sm.lo;
-                    const unsigned int got = sm.sel_val;
-                    __syncthreads();
-                    if (got) { lo = prefix; expect = got; break; }
-                }
-                if (lo < blo) lo = blo;
-            }
-        }
-        if (round == 0) NMS_STAMP(1);
-        // ------------------------------------------------------------------ gather the keys of [lo, hi) into LDS (any order)
-        if (tid == 0) sm.batch_n = 0;
-        __syncthreads();
-        for (long long i0 = 0; i0 < cap; i0 += 8 * WALK_THREADS) {
-            unsigned int k32[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {                      // eight independent loads in flight per thread (the scan is latency-bound)
-                const long long i = i0 + u * WALK_THREADS + tid;
-                k32[u] = i < cap ? kb[i] : 0u;
-            }
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                const long long i = i0 + u * WALK_THREADS + tid;
-                const unsigned long long k = ((unsigned long long)k32[u] << 32) | (unsigned long long)(0xffffffffu - (unsigned)i);
-                const bool take = k32[u] != 0u && k >= lo && k < hi;
-                const unsigned long long m = __ballot(take);
-                if (m) {
-                    unsigned int base = 0;
-                    if (lane == 0) base = atomicAdd(&sm.batch_n, (unsigned)__popcll(m));
-                    base = __shfl(base, 0);
-                    if (take) {
-                        const unsigned int slot = base + (unsigned)__popcll(m & ((1ull << lane) - 1ull));
-                        if (slot < NMS_CAP) sm.keys[slot] = k;
-                    }
-                }
-            }
-        }
-        __syncthreads();
-        const unsigned int bn = sm.batch_n < NMS_CAP ? sm.batch_n : NMS_CAP;       // (== expect by construction)
-        if (round == 0) NMS_STAMP(2);
-        // ------------------------------------------------------------------ bitonic sort in LDS, descending (padding = key 0, the smallest)
-        // (a rank sort — every thread counting the keys greater than its own through broadcast reads — measured 150 k cycles for 1020
-        //  keys: 64-bit compares x n^2 are VALU-bound; the network below is 55 barrier stages for 1024 keys, 78 for 4096)
-        {
-            unsigned int P = 64;
-            while (P < bn) P <<= 1;
-            for (unsigned int i = bn + tid; i < P; i += WALK_THREADS) sm.keys[i] = 0ull;
-            __syncthreads();
-            for (unsigned int k = 2; k <= P; k <<= 1)
-                for (unsigned int j = k >> 1; j > 0; j >>= 1) {
-                    for (unsigned int t = tid; t < P / 2; t += WALK_THREADS) {
-                        const unsigned int i = ((t & ~(j - 1u)) << 1) | (t & (j - 1u));
-                        const unsigned int l = i | j;
-                        const bool up = (i & k) != 0u;                // ascending sub-blocks of the network; the last merge is all-descending
-                        const unsigned long long a = sm.keys[i], c = sm.keys[l];
-                        if ((a < c) != up) { sm.keys[i] = c; sm.keys[l] = a; }
-                    }
-                    __syncthreads();
-                }
-        }
-        if (round == 0) NMS_STAMP(3);
-        // ------------------------------------------------------------------ greedy walk over the sorted round
-        const unsigned int limit = (n - processed) < bn ? (n - processed) : bn;     // max_nms cap (by score rank)
-        for (unsigned int base = 0; base < limit && nkept < (unsigned)max_det; base += WALK_THREADS) {
-            {
-                const unsigned int pos = base + tid;
-                if (pos < limit) {
-                    const unsigned int slot = 0xffffffffu - (unsigned)(sm.keys[pos] & 0xffffffffull);
-                    float x1, y1, x2, y2, sc;
-                    int cl;
-                    decode_slot<LAB>(pb, cb, nc, multi, slot, lb, rows, x1, y1, x2, y2, sc, cl);
-                    const float off = (float)cl * cls_off;                 // boxes + cls * max_wh (reference :589-590)
-                    x1 = x1 + off; y1 = y1 + off; x2 = x2 + off; y2 = y2 + off;
-                    sm.cx1[tid] = x1; sm.cy1[tid] = y1; sm.cx2[tid] = x2; sm.cy2[tid] = y2;
-                    sm.car[tid] = (x2 - x1) * (y2 - y1);
-                }
-            }
-            __syncthreads();
-            const unsigned int span = (limit - base) < WALK_THREADS ? (limit - base) : WALK_THREADS;
-            for (unsigned int c0 = 0; c0 < span && nkept < (unsigned)max_det; c0 += 64) {
-                const unsigned int ci = c0 + lane;
-                const bool valid = ci < span;
-                float x1 = 0.f, y1 = 0.f, x2 = 0.f, y2 = 0.f, area = 0.f;
-                if (valid) { x1 = sm.cx1[ci]; y1 = sm.cy1[ci]; x2 = sm.cx2[ci]; y2 = sm.cy2[ci]; area = sm.car[ci]; }
-                // phase A: the 16 wavefronts test the step against interleaved sixteenths of the kept list
-                bool dead = !valid;
-                for (unsigned int k = wave; k < nkept && !__all(dead); k += 16) {
-                    const bool hit = iou_gt(sm.kx1[k], sm.ky1[k], sm.kx2[k], sm.ky2[k], sm.kar[k], x1, y1, x2, y2, area, iou_thr);    // (all lanes: wave-uniform control flow)
-                    dead = dead || hit;
-                }
-                const unsigned long long dm = __ballot(dead);
-                if (lane == 0 && dm) atomicOr(&sm.deadmask, dm);
-                // ... and the step's own 64 x 64 suppression relation, four candidates j per wavefront: supp[j] = the lanes that
-                // overlap candidate j (box broadcast from lane j's registers); the serial pass below then needs no IoU at all
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    const int j = wave * 4 + u;
-                    const float jx1 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, x1), j));
-                    const float jy1 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, y1), j));
-                    const float jx2 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, x2), j));
-                    const float jy2 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, y2), j));
-                    const float jar = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, area), j));
-                    const bool over = iou_gt(jx1, jy1, jx2, jy2, jar, x1, y1, x2, y2, area, iou_thr);
-                    const unsigned long long m = __ballot(over && valid);
-                    if (lane == 0) sm.supp[j] = m;
-                }
-                __syncthreads();
-                if (wave == 0) {
-                    // phase B: resolve the step in order — a kept candidate j removes the LATER lanes of supp[j].  Lane l holds supp[l]
-                    // in registers; per kept box the serial pass is a find-first-set, two v_readlane and scalar mask arithmetic.
-                    const unsigned long long mysupp = sm.supp[lane];
-                    const int slo = (int)(unsigned)(mysupp & 0xffffffffull), shi = (int)(unsigned)(mysupp >> 32);
-                    unsigned long long alive = ~sm.deadmask, keptmask = 0ull;
-                    const unsigned int nkept0 = nkept;
-                    while (alive && nkept < (unsigned)max_det) {
-                        const int j = __ffsll((long long)alive) - 1;          // wave-uniform
-                        keptmask |= 1ull << j;
-                        ++nkept;
-                        const unsigned long long sj = ((unsigned long long)(unsigned)__builtin_amdgcn_readlane(shi, j) << 32) |
-                                                      (unsigned long long)(unsigned)__builtin_amdgcn_readlane(slo, j);
-                        alive &= ~((sj & ~((2ull << j) - 1ull)) | (1ull << j));
-                    }
-                    if ((keptmask >> lane) & 1ull) {
-                        const unsigned int kk = nkept0 + (unsigned)__popcll(keptmask & ((1ull << lane) - 1ull));
-                        sm.kx1[kk] = x1; sm.ky1[kk] = y1; sm.kx2[kk] = x2; sm.ky2[kk] = y2; sm.kar[kk] = area;
-                        sm.kslot[kk] = 0xffffffffu - (unsigned)(sm.keys[base + ci] & 0xffffffffull);
-                        sm.kpos[kk] = processed + base + ci;
-                    }
-                    if (lane == 0) { sm.nkept = nkept; sm.deadmask = 0ull; }
-                }
-                __syncthreads();
-                nkept = sm.nkept;
-            }
-        }
-        if (round == 0) NMS_STAMP(4);
-        processed += bn;
-        hi = lo;
-        if (in_bin_left != 0) {
-            in_bin_left = in_bin_left > bn ? in_bin_left - bn : 0u;       // bin `hib` done once nothing is left in it
-        }
-        ++round;
-        if (bn == 0) break;                                                // defensive: no progress is impossible by construction
+    WalkCursor cur;
+    while (cur.nkept < (unsigned)max_det && cur.processed < n) {
+        cur.lo = 0ull;
+        if (cur.in_bin_left == 0 && !walk_select(sm, cur)) break;
+        if (cur.in_bin_left != 0) walk_refine(sm, im.kb, cap, cur);
+        if (cur.round == 0) NMS_STAMP(1);
+        const unsigned int bn = walk_gather(sm, im.kb, cap, cur);
+        if (cur.round == 0) NMS_STAMP(2);
+        walk_sort(sm, bn);
+        if (cur.round == 0) NMS_STAMP(3);
+        walk_steps<LAB>(sm, im, cur, (n - cur.processed) < bn ? (n - cur.processed) : bn, iou_thr, cls_off, max_det);
+        if (cur.round == 0) NMS_STAMP(4);
+        cur.processed += bn;
+        cur.hi = cur.lo;
+        if (cur.in_bin_left != 0) cur.in_bin_left = cur.in_bin_left > bn ? cur.in_bin_left - bn : 0u;       // bin `hib` done once nothing is left in it
+        ++cur.round;
+        if (bn == 0) break;                                        // defensive: no progress is impossible by construction
     }
     NMS_STAMP(5);
 #ifdef ICAF_NMS_DEBUG
     __syncthreads();
     if (blockIdx.x == 0 && tid == 0)
-        printf("nms_walk b0: n_all=%u rounds=%d processed=%u kept=%u | clocks: select %lld gather %lld sort %lld walk(round0) %lld later rounds %lld\n", n_all, round,
-               processed, nkept, stamps[1] - stamps[0], stamps[2] - stamps[1], stamps[3] - stamps[2], stamps[4] - stamps[3], stamps[5] - stamps[4]);
+        printf("nms_walk b0: n_all=%u rounds=%d processed=%u kept=%u | clocks: select %lld gather %lld sort %lld walk(round0) %lld later rounds %lld\n", n_all,
+               cur.round, cur.processed, cur.nkept, stamps[1] - stamps[0], stamps[2] - stamps[1], stamps[3] - stamps[2], stamps[4] - stamps[3],
+               stamps[5] - stamps[4]);
 #endif
-    // ---------------------------------------------------------------------- outputs, all kept boxes in parallel
-    if (tid == 0) count[b] = (int)nkept;
-    for (unsigned int k = tid; k < nkept; k += WALK_THREADS) {
-        float x1, y1, x2, y2, sc;
-        int cl;
-        decode_slot<LAB>(pb, cb, nc, multi, sm.kslot[k], lb, rows, x1, y1, x2, y2, sc, cl);
-        float* o = det + ((long long)b * max_det + k) * 6;
-        o[0] = x1; o[1] = y1; o[2] = x2; o[3] = y2; o[4] = sc; o[5] = (float)cl;
-        if (keep_idx) keep_idx[(long long)b * max_det + k] = (int)(reordered ? sm.kpos[k] : sm.kslot[k]);
-    }
+    walk_write<LAB>(sm, im, b, cur.nkept, reordered, max_det, det, count, keep_idx);
 }
 
 // keep_idx holds candidate SLOTS (row * nc + class) after the walk; torchvision returns indices into the candidate list,
@@ -600,10 +614,8 @@ __global__ __launch_bounds__(WALK_THREADS) void nms_merge_kernel(const float* __
     const unsigned int n = ncand[b];
     if (!(n > 1u && n < (unsigned)MERGE_N)) return;                       // workgroup-uniform
     const int nk = min(count[b], max_det);
-    const float* pb = pred + (long long)b * rows * (5 + nc);
-    const unsigned int* kb = key32 + (long long)b * cap;
-    const unsigned short* cb = cls16 + (long long)b * rows;
-    const float* lb = LAB ? labels + (long long)label_off[b] * 5 : nullptr;
+    const NmsImage im = {pred + (long long)b * rows * (5 + nc), key32 + (long long)b * cap, cls16 + (long long)b * rows,
+                         LAB ? labels + (long long)label_off[b] * 5 : nullptr, rows, cap, nc, multi};
     // ------------------------------------------------------------------ 1. candidates into LDS, slot order
     unsigned int base = 0;
     for (long long i0 = 0; i0 < cap; i0 += 4 * WALK_THREADS) {
@@ -612,8 +624,11 @@ __global__ __launch_bounds__(WALK_THREADS) void nms_merge_kernel(const float* __
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
             const long long i = i0 + u * WALK_THREADS + tid;
-            k32[u] = i < cap ? kb[i] : 0u;
+            k32[u] = i < cap ? im.kb[i] : 0u;
         }
+        // the ordered rank of four predicates a thread behind ONE barrier pair, written out (box_core.h's wg_rank ranks one predicate).  A build
+        // that had this loop on a four-slot wg_rank measured the kernel 2 - 6 % over its limit at nc = 3; what inside the kernel cost that was not
+        // separated, and with this text the kernel is within its limits (profiles/postproc_share_ab.json)
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
             m[u] = __ballot(k32[u] != 0u);
@@ -638,7 +653,7 @@ __global__ __launch_bounds__(WALK_THREADS) void nms_merge_kernel(const float* __
             if (pos >= (unsigned)MERGE_N) continue;                        // (cannot happen: n < MERGE_N keys exist)
             float x1, y1, x2, y2, sc;
             int cl;
-            decode_slot<LAB>(pb, cb, nc, multi, (unsigned)(i0 + u * WALK_THREADS + tid), lb, rows, x1, y1, x2, y2, sc, cl);
+            decode_slot<LAB>(im, (unsigned)(i0 + u * WALK_THREADS + tid), x1, y1, x2, y2, sc, cl);
             sm.x1[pos] = x1; sm.y1[pos] = y1; sm.x2[pos] = x2; sm.y2[pos] = y2; sm.sc[pos] = sc; sm.off[pos] = (float)cl * cls_off;
         }
         __syncthreads();
@@ -657,10 +672,7 @@ __global__ __launch_bounds__(WALK_THREADS) void nms_merge_kernel(const float* __
             const float ux1 = sm.x1[j], uy1 = sm.y1[j], ux2 = sm.x2[j], uy2 = sm.y2[j], o = sm.off[j];
             const float cx1 = ux1 + o, cy1 = uy1 + o, cx2 = ux2 + o, cy2 = uy2 + o;
             const float carea = (cx2 - cx1) * (cy2 - cy1);
-            const float w = fmaxf(fminf(kx2, cx2) - fmaxf(kx1, cx1), 0.0f), h = fmaxf(fminf(ky2, cy2) - fmaxf(ky1, cy1), 0.0f);
-            const float inter = w * h;
-            const float iou = inter / (karea + carea - inter);
-            if (iou > iou_thr) {
+            if (box_iou(kx1, ky1, kx2, ky2, karea, cx1, cy1, cx2, cy2, carea) > iou_thr) {
                 const double s = (double)sm.sc[j];
                 sw += s;
                 a0 += s * (double)ux1; a1 += s * (double)uy1; a2 += s * (double)ux2; a3 += s * (double)uy2;
@@ -690,7 +702,7 @@ __global__ __launch_bounds__(WALK_THREADS) void nms_merge_kernel(const float* __
         flag = (!redundant || sm.hits[tid] > 1u) ? 1u : 0u;
     }
     unsigned int total;
-    const unsigned int incl = block_incl_scan_1024(flag, sm.wsum, total);      // (its barriers order the reads above before the writes below)
+    const unsigned int incl = wg_incl_scan<16>(flag, sm.wsum, total);      // (its barriers order the reads above before the writes below)
     if (flag) {
         const unsigned int pos = incl - 1u;
         float* o = det + ((long long)b * max_det + pos) * 6;
@@ -705,8 +717,6 @@ struct NmsWs {
     size_t zero_bytes; int nchunks; size_t total;
 };
 
-static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-
 // max_labels: label rows per image behind the prediction rows (0: the layout of icaf_nms)
 static int nms_layout(int B, long long rows, int nc, int multi, int max_labels, void* base, NmsWs& ws) {
     if (B < 1 || rows < 1 || nc < 1) return fail(ICAF_ERR_ARG, "icaf_nms: bad B/rows/nc");
@@ -714,41 +724,18 @@ static int nms_layout(int B, long long rows, int nc, int multi, int max_labels, 
     if (max_labels < 0 || max_labels > ICAF_NMS_MAX_LABELS) return fail(ICAF_ERR_ARG, "icaf_nms: max_labels must be in [0, %d]", (int)ICAF_NMS_MAX_LABELS);
     const long long cap = (rows + max_labels) * ((multi && nc > 1) ? nc : 1);
     if (cap > 0xfffffff0LL || (long long)B > 65535) return fail(ICAF_ERR_UNSUPPORTED, "icaf_nms: rows*nc exceeds 2^32 candidate slots per image");
-    size_t off = 0;
-    unsigned char* p = (unsigned char*)base;
-    auto take = [&](size_t bytes) { unsigned char* r = p ? p + off : nullptr; off = align_up(off + bytes, 256); return r; };
+    WsArena ar(base);
     ws.nchunks = (int)((rows + max_labels + NMS_CHUNK_ROWS - 1) / NMS_CHUNK_ROWS);
-    ws.ghist = (unsigned int*)take((size_t)B * NMS_NB * 4 + (size_t)B * 4);       // histograms + candidate counters: cleared per call
-    ws.ncand = ws.ghist ? ws.ghist + (size_t)B * NMS_NB : nullptr;
     ws.zero_bytes = (size_t)B * NMS_NB * 4 + (size_t)B * 4;
-    ws.key32 = (unsigned int*)take((size_t)B * cap * 4);
-    ws.cls16 = (unsigned short*)take((size_t)B * rows * 2);
-    ws.chunk_cnt = (unsigned int*)take((size_t)B * ws.nchunks * 4);
-    ws.total = off;
+    ws.ghist = ar.take_as<unsigned int>(ws.zero_bytes);                            // histograms + candidate counters: cleared per call
+    ws.ncand = ws.ghist ? ws.ghist + (size_t)B * NMS_NB : nullptr;
+    ws.key32 = ar.take_as<unsigned int>((size_t)B * cap * 4);
+    ws.cls16 = ar.take_as<unsigned short>((size_t)B * rows * 2);
+    ws.chunk_cnt = ar.take_as<unsigned int>((size_t)B * ws.nchunks * 4);
+    ws.total = ar.total;
     return ICAF_OK;
 }
 
-
-// ---------------------------------------------------------------------------------------------------------------
-// Validation statistics (reference test.py:196-230): TP flags of every detection at every IoU threshold
-// ---------------------------------------------------------------------------------------------------------------
-// One workgroup per image.  Detections arrive as the NMS output block (letterboxed pixel space) and are first mapped to
-// the native image (scale_coords + clip_coords, utils/general.py:386-407: subtract the pad, divide by the gain, clip).
-// Phase 1, one thread per detection: best IoU over the labels of its class and the FIRST label reaching it (box_iou +
-// torch max).  Phase 2, one thread: detections in index order claim their best label if nobody has and the IoU exceeds
-// iouv[0]; a claim marks correct[i][t] = best > iouv[t].  (The reference walks class by class; claims of different
-// classes never touch the same label, so index order gives the same flags.)  fp32, no contraction: the IoU values are
-// bit-identical to the numpy statement of the same formula (icafusion_amd/utils/metrics.py, the test oracle).
-constexpr int MATCH_MAX_DET = 1024, MATCH_MAX_LABELS = 2048;
-
-// scale_coords + clip_coords (utils/general.py:386-407) of one xyxy box, sc = {gain, pad_x, pad_y, w0, h0}: THE expression of the mapping,
-// shared by match_predictions_kernel and scale_detections_kernel (tests/golden/match_predictions.npz, made by the reference, guards both)
-__device__ __forceinline__ void native_box(const float* __restrict__ sc, float& x1, float& y1, float& x2, float& y2) {
-    const float gain = sc[0], padx = sc[1], pady = sc[2], w0 = sc[3], h0 = sc[4];
-    x1 = (x1 - padx) / gain; x2 = (x2 - padx) / gain; y1 = (y1 - pady) / gain; y2 = (y2 - pady) / gain;
-    x1 = fminf(fmaxf(x1, 0.0f), w0); x2 = fminf(fmaxf(x2, 0.0f), w0);
-    y1 = fminf(fmaxf(y1, 0.0f), h0); y2 = fminf(fmaxf(y2, 0.0f), h0);
-}
 
 // det [B][max_det][6] -> out (may alias det: a thread reads its row before it writes it): rows < count[b] mapped to the native image,
 // optionally rounded half-to-even (torch.round, detect_twostream.py:80), conf / cls copied; rows >= count[b] zeroed
@@ -764,53 +751,6 @@ __global__ __launch_bounds__(256) void scale_detections_kernel(const float* det,
         if (round) { x1 = rintf(x1); y1 = rintf(y1); x2 = rintf(x2); y2 = rintf(y2); }
     }
     out[row] = x1; out[row + 1] = y1; out[row + 2] = x2; out[row + 3] = y2; out[row + 4] = conf; out[row + 5] = cls;
-}
-
-__global__ __launch_bounds__(256) void match_predictions_kernel(const float* __restrict__ det, const int* __restrict__ count, int max_det,
-                                                                const float* __restrict__ labels, const int* __restrict__ label_off,
-                                                                const float* __restrict__ scale, const float* __restrict__ iouv, int T,
-                                                                unsigned char* __restrict__ correct, float* __restrict__ predn) {
-    __shared__ float best[MATCH_MAX_DET];
-    __shared__ int arg[MATCH_MAX_DET];
-    __shared__ unsigned char claimed[MATCH_MAX_LABELS];
-    const int b = blockIdx.x, tid = threadIdx.x;
-    const int n = min(count[b], max_det), l0 = label_off[b], nl = label_off[b + 1] - l0;
-    const float* db = det + (long long)b * max_det * 6;
-    for (int i = tid; i < nl; i += 256) claimed[i] = 0;
-    for (int i = tid; i < n; i += 256) {
-        float x1 = db[i * 6], y1 = db[i * 6 + 1], x2 = db[i * 6 + 2], y2 = db[i * 6 + 3];
-        const float cls = db[i * 6 + 5];
-        if (scale) native_box(scale + b * 5, x1, y1, x2, y2);
-        if (predn) {
-            float* o = predn + ((long long)b * max_det + i) * 4;
-            o[0] = x1; o[1] = y1; o[2] = x2; o[3] = y2;
-        }
-        const float area_a = (x2 - x1) * (y2 - y1);
-        float bst = -1.0f;
-        int ba = -1;
-        for (int j = 0; j < nl; ++j) {
-            const float* lb = labels + (long long)(l0 + j) * 5;
-            if (lb[0] != cls) continue;
-            const float iw = fmaxf(fminf(x2, lb[3]) - fmaxf(x1, lb[1]), 0.0f), ih = fmaxf(fminf(y2, lb[4]) - fmaxf(y1, lb[2]), 0.0f);
-            const float inter = iw * ih, area_b = (lb[3] - lb[1]) * (lb[4] - lb[2]);
-            const float iou = inter / (area_a + area_b - inter);
-            if (iou > bst) { bst = iou; ba = j; }
-        }
-        best[i] = bst;
-        arg[i] = ba;
-        for (int t = 0; t < T; ++t) correct[((long long)b * max_det + i) * T + t] = 0;
-    }
-    __syncthreads();
-    if (tid == 0) {
-        const float thr0 = iouv[0];
-        int found = 0;
-        for (int i = 0; i < n && found < nl; ++i) {
-            if (arg[i] < 0 || !(best[i] > thr0) || claimed[arg[i]]) continue;
-            claimed[arg[i]] = 1;
-            ++found;
-            for (int t = 0; t < T; ++t) correct[((long long)b * max_det + i) * T + t] = best[i] > iouv[t] ? 1 : 0;
-        }
-    }
 }
 
 }  // namespace icaf
@@ -841,15 +781,8 @@ static int nms_launch(const icaf_nms_args* a, const NmsWs& ws, const ClassMask& 
     const long long rows = a->rows, cap = (rows + ml) * (multi ? a->nc : 1);
     const int B = a->B, nc = a->nc, use_cm = a->n_classes > 0 ? 1 : 0;
     const float cls_off = a->agnostic ? 0.0f : a->max_wh;
-    static std::atomic<bool> attr_set[ICAF_MAX_DEVICES];      // hipFuncSetAttribute is per device (and per instantiation)
-    int dev = 0;
-    ICAF_HIP(hipGetDevice(&dev));
-    if (dev < 0 || dev >= ICAF_MAX_DEVICES) return fail(ICAF_ERR_UNSUPPORTED, "icaf_nms: device ordinal %d", dev);
-    if (!attr_set[dev]) {
-        ICAF_HIP(hipFuncSetAttribute((const void*)nms_walk_kernel<LAB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(WalkSmem)));
-        ICAF_HIP(hipFuncSetAttribute((const void*)nms_merge_kernel<LAB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(MergeSmem)));
-        attr_set[dev] = true;
-    }
+    ICAF_LDS_OPTIN(nms_walk_kernel<LAB>, sizeof(WalkSmem));
+    ICAF_LDS_OPTIN(nms_merge_kernel<LAB>, sizeof(MergeSmem));
     ICAF_HIP(hipMemsetAsync(ws.ghist, 0, ws.zero_bytes, hs));
     nms_keys_kernel<<<dim3((unsigned)ws.nchunks, (unsigned)B), dim3(256), 0, hs>>>(a->pred, rows, nc, a->conf_thres, multi, cm, use_cm, cap,
                                                                                    ws.nchunks, ws.key32, ws.cls16, ws.ghist, ws.ncand,
@@ -917,18 +850,6 @@ extern "C" int icaf_nms(const float* pred, int B, long long rows, int nc, float 
     a.max_det = max_det; a.max_nms = max_nms; a.max_wh = max_wh; a.det = det; a.count = count; a.keep_idx = keep_idx;
     a.workspace = workspace; a.workspace_bytes = workspace_bytes;
     return icaf_nms_ex(&a, s);
-}
-
-extern "C" int icaf_match_predictions(const float* det, const int* count, int B, int max_det, const float* labels, const int* label_off,
-                                      int max_labels_per_image, const float* scale, const float* iouv, int T, unsigned char* correct,
-                                      float* predn, icaf_stream_t s) {
-    if (!det || !count || !label_off || !iouv || !correct) return fail(ICAF_ERR_ARG, "icaf_match_predictions: null pointer");
-    if (B < 1 || T < 1 || max_det < 1 || max_det > MATCH_MAX_DET) return fail(ICAF_ERR_ARG, "icaf_match_predictions: max_det must be in [1, %d]", MATCH_MAX_DET);
-    if (max_labels_per_image > MATCH_MAX_LABELS) return fail(ICAF_ERR_UNSUPPORTED, "icaf_match_predictions: at most %d labels per image", MATCH_MAX_LABELS);
-    if (max_labels_per_image > 0 && !labels) return fail(ICAF_ERR_ARG, "icaf_match_predictions: labels missing");
-    match_predictions_kernel<<<dim3((unsigned)B), dim3(256), 0, S(s)>>>(det, count, max_det, labels, label_off, scale, iouv, T, correct, predn);
-    ICAF_LAUNCH_CHECK();
-    return ICAF_OK;
 }
 
 extern "C" int icaf_scale_detections(const float* det, const int* count, int B, int max_det, const float* scale, int round, float* out,

@@ -1,5 +1,7 @@
 // Validation statistics on the device (the reference's test.py:144-230 bookkeeping, utils/metrics.py:18-82, 85-110 and 113-159) for gfx950.
 //
+//   icaf_match_predictions  one workgroup per image: the detections mapped to the native image (predn, which the confusion matrix reads) and
+//                           their TP flags at every IoU threshold; described at its kernel.
 //   icaf_stats_stage        one 1024-thread workgroup per batch: exclusive prefix of the clamped counts, then every row below its image's count
 //                           goes to the data-set-wide store at cursor + prefix + row — image order, then row order, the order in which the host
 //                           loop concatenates its per-image statistics.  The cursor is read once and advanced once by the same workgroup: no
@@ -18,8 +20,10 @@
 //                           report one workgroup: F1 curves, first argmax of the class mean, TP / FP / FN at that index.
 //   icaf_confusion_matrix   one workgroup per image; integer atomics into the (nc + 1)^2 matrix (integer adds commute: deterministic).
 // fp64 with contraction off wherever the reference computes in numpy float64; np.interp is restated rule for rule (vs_interp).
+// The exclusive scans (stage, sort) are a per-thread run around box_core.h's wg_incl_scan, the TP count is its wg_rank, and both IoU
+// loops call its box_iou — the matching with the detection first, the confusion matrix with the label first, as the reference does.
 #pragma clang fp contract(off)
-#include "icaf_common.h"
+#include "box_core.h"
 
 namespace icaf {
 
@@ -36,33 +40,80 @@ constexpr int CM_MAX_DET = 1024;
 
 __device__ __forceinline__ int vs_clampi(int v, int lo, int hi) { return min(max(v, lo), hi); }
 
+// ---- matching: TP flags of every detection at every IoU threshold (reference test.py:196-230) ------------------------------------------------------
+// One workgroup per image.  Detections arrive as the NMS output block (letterboxed pixel space) and are first mapped to
+// the native image (scale_coords + clip_coords, utils/general.py:386-407: subtract the pad, divide by the gain, clip).
+// Phase 1, one thread per detection: best IoU over the labels of its class and the FIRST label reaching it (box_iou +
+// torch max).  Phase 2, one thread: detections in index order claim their best label if nobody has and the IoU exceeds
+// iouv[0]; a claim marks correct[i][t] = best > iouv[t].  (The reference walks class by class; claims of different
+// classes never touch the same label, so index order gives the same flags.)  fp32, no contraction: the IoU values are
+// bit-identical to the numpy statement of the same formula (icafusion_amd/utils/metrics.py, the test oracle).
+constexpr int MATCH_MAX_DET = 1024, MATCH_MAX_LABELS = 2048;
+
+__global__ __launch_bounds__(256) void match_predictions_kernel(const float* __restrict__ det, const int* __restrict__ count, int max_det,
+                                                                const float* __restrict__ labels, const int* __restrict__ label_off,
+                                                                const float* __restrict__ scale, const float* __restrict__ iouv, int T,
+                                                                unsigned char* __restrict__ correct, float* __restrict__ predn) {
+    __shared__ float best[MATCH_MAX_DET];
+    __shared__ int arg[MATCH_MAX_DET];
+    __shared__ unsigned char claimed[MATCH_MAX_LABELS];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const int n = min(count[b], max_det), l0 = label_off[b], nl = label_off[b + 1] - l0;
+    const float* db = det + (long long)b * max_det * 6;
+    for (int i = tid; i < nl; i += 256) claimed[i] = 0;
+    for (int i = tid; i < n; i += 256) {
+        float x1 = db[i * 6], y1 = db[i * 6 + 1], x2 = db[i * 6 + 2], y2 = db[i * 6 + 3];
+        const float cls = db[i * 6 + 5];
+        if (scale) native_box(scale + b * 5, x1, y1, x2, y2);
+        if (predn) {
+            float* o = predn + ((long long)b * max_det + i) * 4;
+            o[0] = x1; o[1] = y1; o[2] = x2; o[3] = y2;
+        }
+        const float area_a = (x2 - x1) * (y2 - y1);
+        float bst = -1.0f;
+        int ba = -1;
+        for (int j = 0; j < nl; ++j) {
+            const float* lb = labels + (long long)(l0 + j) * 5;
+            if (lb[0] != cls) continue;
+            const float iou = box_iou(x1, y1, x2, y2, area_a, lb[1], lb[2], lb[3], lb[4], (lb[3] - lb[1]) * (lb[4] - lb[2]));
+            if (iou > bst) { bst = iou; ba = j; }
+        }
+        best[i] = bst;
+        arg[i] = ba;
+        for (int t = 0; t < T; ++t) correct[((long long)b * max_det + i) * T + t] = 0;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        const float thr0 = iouv[0];
+        int found = 0;
+        for (int i = 0; i < n && found < nl; ++i) {
+            if (arg[i] < 0 || !(best[i] > thr0) || claimed[arg[i]]) continue;
+            claimed[arg[i]] = 1;
+            ++found;
+            for (int t = 0; t < T; ++t) correct[((long long)b * max_det + i) * T + t] = best[i] > iouv[t] ? 1 : 0;
+        }
+    }
+}
+
 // ---- stage ---------------------------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(VS_WG) void stats_stage_kernel(const unsigned char* __restrict__ correct, const float* __restrict__ det,
                                                             const int* __restrict__ count, int B, int max_det, int T,
                                                             unsigned short* __restrict__ store_mask, float* __restrict__ store_conf,
                                                             int* __restrict__ store_cls, int capacity, int* cursor, int* any_tp) {
     __shared__ int s_off[VS_MAX_BATCH + 1];
-    __shared__ int s_part[VS_WG];
+    __shared__ int s_ws[VS_WG / 64];
     const int tid = threadIdx.x;
-    const int per = (B + VS_WG - 1) / VS_WG, b0 = min(tid * per, B), b1 = min(b0 + per, B);
-    int sum = 0;
+    const int per = (B + VS_WG - 1) / VS_WG, b0 = min(tid * per, B), b1 = min(b0 + per, B);      // a thread owns `per` consecutive images
+    int sum = 0, total;
     for (int b = b0; b < b1; ++b) sum += vs_clampi(count[b], 0, max_det);
-    s_part[tid] = sum;
-    __syncthreads();
-    for (int off = 1; off < VS_WG; off <<= 1) {
-        const int v = tid >= off ? s_part[tid - off] : 0;
-        __syncthreads();
-        s_part[tid] += v;
-        __syncthreads();
-    }
-    int run = s_part[tid] - sum;
+    int run = wg_incl_scan<VS_WG / 64>(sum, s_ws, total) - sum;
     for (int b = b0; b < b1; ++b) {
         s_off[b] = run;
         run += vs_clampi(count[b], 0, max_det);
     }
-    if (tid == VS_WG - 1) s_off[B] = s_part[VS_WG - 1];
-    __syncthreads();
-    const int base = *cursor, total = s_off[B];
+    if (tid == 0) s_off[B] = total;
+    __syncthreads();                                                            // s_off is complete before the rows below look images up in it
+    const int base = *cursor;
     const long long cells = (long long)B * max_det;
     unsigned int any = 0;
     if (base >= 0 && base <= capacity) {
@@ -116,21 +167,13 @@ __global__ __launch_bounds__(VS_SORT_THREADS) void sort_hist_kernel(const unsign
 
 // exclusive scan of m ints in place, one workgroup
 __global__ __launch_bounds__(VS_WG) void sort_scan_kernel(int* __restrict__ a, int m) {
-    __shared__ int s_part[VS_WG];
+    __shared__ int s_ws[VS_WG / 64];
     const int tid = threadIdx.x;
     const int per = (m + VS_WG - 1) / VS_WG;
     const long long lo = min((long long)tid * per, (long long)m), hi = min(lo + per, (long long)m);
-    int sum = 0;
+    int sum = 0, total;
     for (long long i = lo; i < hi; ++i) sum += a[i];
-    s_part[tid] = sum;
-    __syncthreads();
-    for (int off = 1; off < VS_WG; off <<= 1) {
-        const int v = tid >= off ? s_part[tid - off] : 0;
-        __syncthreads();
-        s_part[tid] += v;
-        __syncthreads();
-    }
-    int run = s_part[tid] - sum;
+    int run = wg_incl_scan<VS_WG / 64>(sum, s_ws, total) - sum;
     for (long long i = lo; i < hi; ++i) {
         const int v = a[i];
         a[i] = run;
@@ -236,24 +279,14 @@ __global__ __launch_bounds__(VS_WG) void ap_class_kernel(const unsigned short* _
         return;
     }
     int* tp = tpc + (long long)t * n + s;                     // tp[j]: inclusive TP count of the class's row j at threshold t
-    const unsigned long long le = lane == 63 ? ~0ull : ((1ull << (lane + 1)) - 1ull);
     int running = 0;
     for (int c0 = 0; c0 < np_; c0 += VS_WG) {
         const int j = c0 + tid;
         const bool bit = j < np_ && ((smask[s + j] >> t) & 1);
-        const unsigned long long bal = __ballot(bit);
-        if (lane == 0) s_ws[wave] = __popcll(bal);
-        __syncthreads();
-        int pre = 0, tot = 0;
-#pragma unroll
-        for (int w = 0; w < 16; ++w) {
-            const int v = s_ws[w];
-            pre += w < wave ? v : 0;
-            tot += v;
-        }
-        if (j < np_) tp[j] = running + pre + __popcll(bal & le);
+        int tot;
+        const int before = wg_rank<16>(bit, s_ws, tot);
+        if (j < np_) tp[j] = running + before + (bit ? 1 : 0);
         running += tot;
-        __syncthreads();
     }
     __threadfence_block();
     __syncthreads();                                          // the workgroup reads its own tpc row below
@@ -404,9 +437,7 @@ __global__ __launch_bounds__(256) void confusion_matrix_kernel(const float* __re
             for (int j = 0; j < nl; ++j) {                   // box_iou(labels, detections), utils/general.py:455-477
                 const float* lb = labels + (long long)(l0 + j) * 5;
                 const float area_l = (lb[3] - lb[1]) * (lb[4] - lb[2]);
-                const float iw = fmaxf(fminf(lb[3], x2) - fmaxf(lb[1], x1), 0.0f), ih = fmaxf(fminf(lb[4], y2) - fmaxf(lb[2], y1), 0.0f);
-                const float inter = iw * ih;
-                const float iou = inter / (area_l + area_d - inter);
+                const float iou = box_iou(lb[1], lb[2], lb[3], lb[4], area_l, x1, y1, x2, y2, area_d);
                 if (iou > iou_thres && (bl < 0 || iou > bi)) { bl = j; bi = iou; }        // the lowest label index wins a tie
             }
         }
@@ -448,23 +479,34 @@ struct ApWs {
 
 static ApWs ap_layout(int n, int T) {
     ApWs w;
-    size_t o = 0;
-    auto take = [&](size_t b) { const size_t at = o; o += (b + 255) / 256 * 256; return at; };
+    WsArena ar;
     const size_t rows = (size_t)(n > 0 ? n : 1);
     w.ntiles = (n + VS_TILE - 1) / VS_TILE;
-    for (int k = 0; k < 2; ++k) w.key[k] = take(rows * 4);
-    for (int k = 0; k < 2; ++k) w.idx[k] = take(rows * 4);
-    w.hist = take((size_t)256 * (size_t)(w.ntiles > 0 ? w.ntiles : 1) * 4);
-    w.smask = take(rows * 2);
-    w.sconf = take(rows * 4);
-    w.tpc = take(rows * 4 * (size_t)T);
-    w.bytes = o;
+    for (int k = 0; k < 2; ++k) w.key[k] = ar.take(rows * 4);
+    for (int k = 0; k < 2; ++k) w.idx[k] = ar.take(rows * 4);
+    w.hist = ar.take((size_t)256 * (size_t)(w.ntiles > 0 ? w.ntiles : 1) * 4);
+    w.smask = ar.take(rows * 2);
+    w.sconf = ar.take(rows * 4);
+    w.tpc = ar.take(rows * 4 * (size_t)T);
+    w.bytes = ar.total;
     return w;
 }
 
 }  // namespace icaf
 
 using namespace icaf;
+
+extern "C" int icaf_match_predictions(const float* det, const int* count, int B, int max_det, const float* labels, const int* label_off,
+                                      int max_labels_per_image, const float* scale, const float* iouv, int T, unsigned char* correct,
+                                      float* predn, icaf_stream_t s) {
+    if (!det || !count || !label_off || !iouv || !correct) return fail(ICAF_ERR_ARG, "icaf_match_predictions: null pointer");
+    if (B < 1 || T < 1 || max_det < 1 || max_det > MATCH_MAX_DET) return fail(ICAF_ERR_ARG, "icaf_match_predictions: max_det must be in [1, %d]", MATCH_MAX_DET);
+    if (max_labels_per_image > MATCH_MAX_LABELS) return fail(ICAF_ERR_UNSUPPORTED, "icaf_match_predictions: at most %d labels per image", MATCH_MAX_LABELS);
+    if (max_labels_per_image > 0 && !labels) return fail(ICAF_ERR_ARG, "icaf_match_predictions: labels missing");
+    match_predictions_kernel<<<dim3((unsigned)B), dim3(256), 0, S(s)>>>(det, count, max_det, labels, label_off, scale, iouv, T, correct, predn);
+    ICAF_LAUNCH_CHECK();
+    return ICAF_OK;
+}
 
 extern "C" int icaf_stats_stage(const unsigned char* correct, const float* det, const int* count, int B, int max_det, int T,
                                 void* store_mask, float* store_conf, int* store_cls, int capacity, int* cursor, int* any_tp,

@@ -41,7 +41,7 @@ from icafusion_amd.utils.results import ResultWriter, frame_index, label_listing
 from icafusion_amd.utils.metrics import ConfusionMatrix, ap_per_class
 from icafusion_amd.utils.torch_utils import select_device, time_synchronized
 
-MATCH_MAX_DET = 1024                                             # detections per image icaf_match_predictions takes (nms.hip)
+MATCH_MAX_DET = 1024                                             # detections per image icaf_match_predictions takes (valstats.hip)
 IOUV = np.linspace(0.5, 0.95, 10)                                # the IoU thresholds of mAP@0.5:0.95
 
 

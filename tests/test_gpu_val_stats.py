@@ -189,6 +189,47 @@ def test_stage_equals_the_host_concatenation(capacity):
         assert state[0].item() > capacity and state[1].item() == 1
 
 
+@functools.lru_cache(maxsize=None)
+def wide_batch(B, max_det=3):
+    """One batch of B images, max_det 3, counts in [0, 3] with runs of zeros (up to 40 images, so whole threads' shares are empty); poison
+    beyond the counts.  Returns the batch and its host concatenation."""
+    g = np.random.default_rng(100 + B)
+    counts = g.integers(0, max_det + 1, B)
+    for start in g.integers(0, B, B // 64):
+        counts[start:start + g.integers(1, 41)] = 0
+    counts[-1] = max_det                                                              # the last image of the last thread's share stores rows
+    correct = np.full((B, max_det, T), 0xFF, np.uint8)
+    det = np.full((B, max_det, 6), np.nan, np.float32)
+    for b, c in enumerate(counts):
+        correct[b, :c] = np.logical_and.accumulate(g.random((c, T)) < 0.6, 1)
+        det[b, :c] = np.concatenate((g.uniform(0, 600, (c, 4)), g.uniform(0.001, 1, (c, 1)), g.integers(0, 3, (c, 1))), 1)
+    batch = (correct, det, counts.astype(np.int32))
+    return batch, host_concat([batch])
+
+
+@pytest.mark.parametrize("B", [1025, _lib.STATS_MAX_BATCH])
+def test_stage_at_batch_counts_where_a_thread_owns_several_images(B):
+    """B = 1025 (two images a thread, half the threads without any) and B = 4096 (four a thread, the limit): the prefix of the counts runs
+    inside a thread's share and across the workgroup.  The store equals the host concatenation, the cursor the total, nothing else is written."""
+    (c, d, cnt), (tp, conf, cls) = wide_batch(B)
+    total = len(conf)
+    assert total == int(cnt.sum()) and 0 < total < 3 * B and (cnt == 0).sum() > B // 8
+    capacity = total + 5
+    fm, mask = guarded((capacity,), torch.int16, 0x5A5A)
+    fc, sconf = guarded((capacity,), torch.float32, -7.0)
+    fk, scls = guarded((capacity,), torch.int32, -77)
+    fs, state = guarded((2,), torch.int32, -5)
+    state.zero_()
+    ops.stats_stage(torch.from_numpy(c).to(DEV), torch.from_numpy(d).to(DEV), torch.from_numpy(cnt).to(DEV), mask, sconf, scls,
+                    state[0:1], state[1:2])(ops.current_stream_ptr())
+    torch.cuda.synchronize()
+    assert state.tolist() == [total, 1]
+    assert np.array_equal(mask[:total].cpu().numpy(), pack(tp)) and np.array_equal(sconf[:total].cpu().numpy(), conf)
+    assert np.array_equal(scls[:total].cpu().numpy(), cls)
+    assert bool((mask[total:] == 0x5A5A).all()) and bool((sconf[total:] == -7.0).all()) and bool((scls[total:] == -77).all())
+    assert guards_intact(fm, capacity, 0x5A5A) and guards_intact(fc, capacity, -7.0) and guards_intact(fk, capacity, -77) and guards_intact(fs, 2, -5)
+
+
 def test_store_object_round_trip_and_any_tp():
     batches = stage_batches(seed=6)
     tp, conf, cls = host_concat(batches)
